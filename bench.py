@@ -3,7 +3,15 @@
 bench.py -- the MOD16 forward-run benchmark (BASELINE.json metric: pixels/s and
 achieved HBM GB/s on the 43200 x 21600 global ET grid, float64).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (and with
+--dump-outputs writes what the last timed step computed: DIR/et_day.npy,
+DIR/et_night.npy -- a fixed sample of the grid, see dump_sample() -- and
+DIR/diagnostics.npy, every value finite: where an output is NaN or inf it holds 0
+and DIR/<name>_nonfinite.npy says which, see finite_parts()). Everything else below -- CPU baseline, parity, the plain-array
+layout, sensors, the copy kernel, the other configurations, ingest, the numpy call --
+runs with --full only; the --no-* options leave parts of a --full run out.
 
 With N > 1 and no torch.distributed environment the command starts its own
 ranks: the parent -- which never touches a GPU -- starts the N ranks directly as
@@ -27,13 +35,14 @@ overlapped with the next step. The global grid is fixed and cut into N row bands
 The raster is resident in the engine's tiled layout (mod16_layout: the 14 driver
 arrays interleaved tile by tile); the same kernel on 16
 plain arrays -- the layout the reference's arguments have -- is timed beside it
-(`roofline.plain_arrays`).
+(`roofline.plain_arrays`, --full).
 
 Rank 0 prints ONE JSON line. Besides the contract fields it carries
   roofline      dominant kernel (fused ET) vs the 8 TB/s HBM peak; `achieved`
                 = 129 B/pixel (float64) x pixels per launch / mean launch time,
                 timed with HIP events on the launch stream; `frac_of_measured_copy`
-                relates it to a copy kernel measured in this process;
+                relates it to a copy kernel measured in this process (--full);
+and with --full
   cpu_baseline  the numpy oracle (reference-shaped port) timed on this box's
                 host cores on 1200 x 1200 tiles of the same synthetic workload
                 (N = 1 only);
@@ -59,6 +68,7 @@ if ROOT not in sys.path:
 HBM_PEAK_GBPS = 8000.0        # MI355X HBM3E peak (MI355X_MICROARCH.md)
 TILE = (1200, 1200)           # BASELINE.json configs[1], the CPU sample unit
 SEED = 16
+DUMP_SAMPLE = 1 << 21         # --dump-outputs: pixels kept per output raster (float64: 16 MiB + 8 MiB of codes each)
 DIAG_NAMES = ('sum_day', 'sum_night', 'n_valid_day', 'n_valid_night',
               'n_nan_day', 'n_nan_night', 'max_day', 'max_night')
 
@@ -416,6 +426,50 @@ def merge_compare(dst, src):
             dst[k] = max(dst[k], v)
 
 
+def dump_sample(np, total):
+    """Global pixel indices of --dump-outputs: every pixel of a grid of at most DUMP_SAMPLE pixels,
+    otherwise one pixel per stride of total // DUMP_SAMPLE, its place in the stride drawn with SEED --
+    the same pixels on every run with the same --rows / --cols."""
+    if total <= DUMP_SAMPLE:
+        return np.arange(total, dtype=np.int64)
+    stride = total // DUMP_SAMPLE
+    rng = np.random.default_rng(SEED)
+    return np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + rng.integers(0, stride, DUMP_SAMPLE)
+
+
+def finite_parts(np, name, values):
+    """One output as arrays of finite values only: <name> with its NaN / inf set to 0, and
+    <name>_nonfinite, 0 where the output is finite, 1 NaN, 2 +inf, 3 -inf -- together the whole
+    output (the grid has NaN pixels: fill values), comparable value by value."""
+    code = np.zeros(values.shape, np.float32)
+    code[np.isnan(values)] = 1
+    code[np.isposinf(values)] = 2
+    code[np.isneginf(values)] = 3
+    return {name: np.where(code == 0, values, 0).astype(values.dtype), name + '_nonfinite': code}
+
+
+def dump_outputs(np, torch, group, dirname, total, offset, n, fields, pick, diag, rank):
+    """--dump-outputs: DIR/<name>.npy for each output raster of the step (the pixels of dump_sample()
+    that lie in this rank's band [offset, offset + n), gathered to rank 0 in rank order = pixel order)
+    and DIR/diagnostics.npy, the step's diagnostics vector (already reduced over the ranks); each
+    beside its DIR/<name>_nonfinite.npy (finite_parts)."""
+    idx = dump_sample(np, total)
+    mine = idx[(idx >= offset) & (idx < offset + n)] - offset
+    at = torch.from_numpy(mine).to(diag.device)
+    parts = {name: pick(field, at).cpu().numpy() for name, field in fields.items()}
+    if group is not None:
+        gathered = [None] * group.get_world_size()
+        group.all_gather_object(gathered, parts)
+        parts = {name: np.concatenate([g[name] for g in gathered]) for name in fields}
+    if rank != 0:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    parts['diagnostics'] = diag.cpu().numpy().astype(np.float64)
+    for name, values in parts.items():
+        for fname, arr in finite_parts(np, name, values).items():
+            np.save(os.path.join(dirname, fname + '.npy'), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -446,7 +500,21 @@ def main():
                     help='skip the numpy-in / numpy-out call over the GPUs of the run (rank 0, devices=range(N))')
     ap.add_argument('--cpu-workers', type=int, default=16)
     ap.add_argument('--series-steps', type=int, default=46)
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline step as well: CPU baseline, parity, plain arrays, sensors, '
+                         'copy kernel, the other configurations, ingest and the numpy call (the --no-* options '
+                         'leave parts of it out). Default: set up, warm up, time the steps, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write what the last timed step computed to DIR/<name>.npy: the day and night ET "
+                         "rasters (a fixed sample of at most %d pixels of the global grid) and the diagnostics vector, "
+                         "NaN / inf as 0 with their places in DIR/<name>_nonfinite.npy" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if not args.full:
+        # a plain run does what the headline figure needs and nothing else
+        for name in ('no_cpu_baseline', 'no_parity', 'no_plain', 'no_sensors', 'no_configs', 'no_ingest',
+                     'no_host_call'):
+            setattr(args, name, True)
+        args.plain = False
 
     in_group = 'RANK' in os.environ and 'WORLD_SIZE' in os.environ
     # MOD16_BENCH_FORCE_GROUP=1: the N > 1 step (process group, side stream, collective) also
@@ -456,8 +524,12 @@ def main():
         os.environ.update(rank_env({}, 0, 1, free_port()))
         in_group = True
     if not in_group and args.gpus > 1:
-        # the parent of a multi-GPU run: no torch.cuda, no mod16_amd, no GPU
-        return spawn(sys.argv[1:], args.gpus)
+        # the parent of a multi-GPU run: no torch.cuda, no mod16_amd, no GPU (the ranks run in ROOT:
+        # the output directory goes to them as an absolute path)
+        argv = sys.argv[1:]
+        if args.dump_outputs:
+            argv += ['--dump-outputs', os.path.abspath(args.dump_outputs)]
+        return spawn(argv, args.gpus)
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -606,6 +678,16 @@ def main():
     kernel_ms_min = min(step_ms)
     achieved = bpp * n / (kernel_ms * 1e-3) / 1e9
     torch.cuda.synchronize()
+    if args.dump_outputs:
+        # the last timed step's outputs, before any other leg reuses the raster or its memory
+        last_diag = diags[(counter[0] - 1) & 1]
+        if ras is not None:
+            pick = lambda field, at: field[at // ras.tile, at % ras.tile]
+        else:
+            pick = lambda field, at: field[at]
+        dump_outputs(np, torch, dist if grouped else None, args.dump_outputs, total, offset, n,
+                     {'et_day': ras.day if ras is not None else day, 'et_night': ras.night if ras is not None else night},
+                     pick, last_diag, rank)
     # clock and power under this load (same count of extra steps on every rank: `elapsed` is the maximum over them)
     under_load = None
     if not args.no_sensors:
@@ -718,7 +800,7 @@ def main():
                  'frac': bpp * n / (p_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 'slab': tune}
         del pstep, pcls, pdrv, pday, pnight
         torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and args.full:
         copy_gbps = eng.measure_copy(4 << 30, 3)
 
     # real-data ingest in the light input form (every rank has its own PCIe link): N > 1 runs it on every
@@ -771,7 +853,7 @@ def main():
             'metric': 'pixels/sec, fused Penman-Monteith ET forward run (day+night), 43200x21600 global grid',
             'value': value, 'unit': 'pixels/s', 'n_gpus': world, 'ranks_seen': ranks_seen,
             'process_group': {'backend': backend, 'world_size': world, 'forced_for_one_rank': bool(force_group and world == 1)},
-            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps,
+            'steps': args.steps, 'warmup': args.warmup, 'full': args.full, 'ms_per_step': 1e3 * elapsed / args.steps,
             'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None,
             'dtype': 'f64' if args.dtype == 'float64' else 'f32', 'data': 'synthetic',
             'config': {

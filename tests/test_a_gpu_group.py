@@ -13,21 +13,22 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-ARGS = ['--gpus', '1', '--rows', '5400', '--steps', '60', '--warmup', '5', '--no-cpu-baseline',
+ARGS = ['--gpus', '1', '--rows', '5400', '--steps', '60', '--warmup', '5', '--full', '--no-cpu-baseline',
         '--no-configs', '--no-plain']
 
 
-def run_bench(extra_env):
+def run_bench(extra_env, extra_args=()):
     env = dict(os.environ, OMP_NUM_THREADS='4', **extra_env)
     for key in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(key, None)
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + ARGS, env=env, cwd=ROOT,
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + ARGS + list(extra_args), env=env, cwd=ROOT,
                           capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     lines = [l for l in proc.stdout.splitlines() if l.startswith('{')]
@@ -37,9 +38,9 @@ def run_bench(extra_env):
     return json.loads(lines[0])
 
 
-def test_one_rank_rccl_group_runs_the_multi_gpu_step():
-    plain = run_bench({})
-    forced = run_bench({'MOD16_BENCH_FORCE_GROUP': '1'})
+def test_one_rank_rccl_group_runs_the_multi_gpu_step(tmp_path):
+    plain = run_bench({}, ['--dump-outputs', str(tmp_path / 'plain')])
+    forced = run_bench({'MOD16_BENCH_FORCE_GROUP': '1'}, ['--dump-outputs', str(tmp_path / 'forced')])
     assert plain['process_group'] == {'backend': None, 'world_size': 1, 'forced_for_one_rank': False}
     assert forced['process_group'] == {'backend': 'nccl', 'world_size': 1, 'forced_for_one_rank': True}
     assert forced['ranks_seen'] == 1 and forced['n_gpus'] == 1
@@ -47,6 +48,15 @@ def test_one_rank_rccl_group_runs_the_multi_gpu_step():
     # the diagnostics went through the gather and the rank-order fold: the same bits
     assert forced['diagnostics'] == plain['diagnostics']
     assert forced['diagnostics']['n_valid_day'] + forced['diagnostics']['n_nan_day'] == 5400 * 43200
+    # --dump-outputs: the last step's outputs, gathered through the group, are the plain run's bits
+    for name in ('et_day', 'et_night', 'diagnostics'):
+        for part, dtype in ((name, np.float64), (name + '_nonfinite', np.float32)):
+            a, b = np.load(tmp_path / 'plain' / (part + '.npy')), np.load(tmp_path / 'forced' / (part + '.npy'))
+            assert a.dtype == dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), part
+            assert np.isfinite(a).all(), part
+    assert np.load(tmp_path / 'plain' / 'et_day_nonfinite.npy').any()          # the grid's NaN pixels, coded
+    assert np.load(tmp_path / 'plain' / 'et_day.npy').shape == (min(5400 * 43200, 1 << 21),)
+    assert np.load(tmp_path / 'plain' / 'diagnostics.npy').tolist() == list(plain['diagnostics'].values())
     # parity summaries travelled through the group's all-reduces (MAX, SUM)
     for key in ('max_rel_err', 'masks_equal'):
         assert forced['parity'][key] == plain['parity'][key]

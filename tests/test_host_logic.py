@@ -329,3 +329,47 @@ def test_build_is_judged_by_the_digest_in_the_library(tmp_path):
     os.utime(other, None)                                  # newer than every source
     assert build.built_id(str(other)) == '0123456789abcdef' and not build.up_to_date(str(other))
     assert build.built_id(str(tmp_path / 'absent.so')) is None
+
+
+def test_bench_dump_outputs_sample_and_files(tmp_path):
+    """bench.py --dump-outputs: the same pixels on every run (one per stride of the grid, drawn with
+    the fixed seed; every pixel of a small grid), inside the grid, in pixel order, and a tiled raster's
+    values picked at the right places; every value written is finite -- NaN / +inf / -inf become 0
+    and <name>_nonfinite.npy holds 1 / 2 / 3 there -- DUMP_SAMPLE pixels per raster, within 64 MB in all."""
+    import torch
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+    total = 43200 * 21600
+    idx = bench.dump_sample(np, total)
+    assert idx.shape == (bench.DUMP_SAMPLE,) and np.array_equal(idx, bench.dump_sample(np, total))
+    assert idx[0] >= 0 and idx[-1] < total and np.all(np.diff(idx) > 0)
+    assert np.array_equal(bench.dump_sample(np, 1000), np.arange(1000))
+    # a band [offset, offset + n) of a grid held as (tiles, tile) views: the value of pixel i is i,
+    # except NaN / +inf / -inf on pixels i = 1 / 2 / 3 (mod 7)
+    rows, cols, tile = 5400, 43200, 4096
+    total, offset = rows * cols, 1 << 20
+    n = total - offset
+    ntiles = -(-n // tile)
+    pixel = torch.arange(ntiles * tile, dtype=torch.float64).view(ntiles, tile) + offset
+    day = pixel.clone()
+    for k, special in ((1, float('nan')), (2, float('inf')), (3, -float('inf'))):
+        day[pixel % 7 == k] = special
+    fields = {'et_day': day, 'et_night': -pixel}
+    pick = lambda field, at: field[at // tile, at % tile]
+    diag = torch.arange(8, dtype=torch.float64)
+    bench.dump_outputs(np, torch, None, str(tmp_path / 'out'), total, offset, n, fields, pick, diag, 0)
+    got = {p.stem: np.load(p) for p in (tmp_path / 'out').iterdir()}
+    assert sorted(got) == ['diagnostics', 'diagnostics_nonfinite', 'et_day', 'et_day_nonfinite',
+                           'et_night', 'et_night_nonfinite']
+    assert all(np.isfinite(a).all() and a.dtype in (np.float32, np.float64) for a in got.values())
+    want = bench.dump_sample(np, total)
+    want = want[want >= offset].astype(np.float64)
+    code = np.where(want % 7 <= 3, want % 7, 0).astype(np.float32)
+    assert 0 < np.count_nonzero(code == 1) and 0 < np.count_nonzero(code == 3)
+    assert got['et_day'].dtype == np.float64 and np.array_equal(got['et_day'], np.where(code == 0, want, 0))
+    assert np.array_equal(got['et_day_nonfinite'], code)
+    assert np.array_equal(got['et_night'], -want) and not got['et_night_nonfinite'].any()
+    assert got['diagnostics'].tolist() == list(range(8)) and not got['diagnostics_nonfinite'].any()
+    # the full-size files of a float64 run stay within 64 MB
+    assert 2 * bench.DUMP_SAMPLE * (8 + 4) + 8 * (8 + 4) <= 64 << 20

@@ -5,7 +5,7 @@
 out=$1; shift
 mkdir -p "$out"
 rocm-smi --showclocks --showpower --showmaxpower --showperflevel > "$out/idle.txt" 2>&1
-python bench.py --steps 600 --no-configs --no-parity --no-cpu-baseline --no-plain "$@" > "$out/bench.json" 2> "$out/bench.err" &
+python bench.py --steps 600 --full --no-configs --no-parity --no-cpu-baseline --no-plain "$@" > "$out/bench.json" 2> "$out/bench.err" &
 pid=$!
 sleep 12
 for i in $(seq 1 40); do

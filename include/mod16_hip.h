@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 5
+#define MOD16_ABI_VERSION 6
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -744,6 +744,49 @@ MOD16_API int mod16_classify_f64(mod16_ctx* ctx, const double* const* params, co
 MOD16_API int mod16_classify_f32(mod16_ctx* ctx, const float* const* params, const int64_t* pstride,
                                  int64_t n, const float* rows, int nrows, uint8_t* cls,
                                  int64_t* unmatched, void* stream);
+
+/*
+ * Sobol sensitivity analysis (ABI 6; mod16_amd/sensitivity.py): what the reference's
+ * sensitivity.py does with SALib, on the device. float64 only. The arithmetic -- the Sobol
+ * sequence, the Saltelli row layout, the indices and the bootstrap's index generator -- is stated
+ * in full at the top of mod16_amd/csrc/mod16_sobol.hpp; in short:
+ *   - the sequence is the unscrambled Sobol sequence of scipy.stats.qmc.Sobol(2d, scramble=False,
+ *     bits=32) (Joe-Kuo direction numbers, 32 dimensions committed as constants), point skip + j for
+ *     base sample j; a value is lo + (hi - lo) * u (no contraction);
+ *   - a base sample has R = 2d + 2 rows (second_order) or d + 2: A, AB^(1..d), [BA^(1..d)], B --
+ *     SALib's documented layout (not checked against SALib itself);
+ *   - idx_out and std_out are [S1 d | ST d | S2 d*d] (S2[j][k] for j < k, NaN elsewhere and without
+ *     second order); std_out is the standard deviation (ddof 1) of each index over `resamples`
+ *     bootstrap resamples of the n base samples (multiply by the normal quantile for a confidence
+ *     half-width); NaN in y propagates.
+ * Checks (MOD16_ERR_ARG): 1 <= d <= 14; n a power of two, n <= 2^26; lo < hi, both finite;
+ * 0 <= skip, skip + n <= 2^32; vary[d] distinct driver indices (enum mod16_driver);
+ * 0 <= resamples <= 2^20. Device memory that cannot be had is MOD16_ERR_NOMEM.
+ * where = MOD16_HOST: the arrays are host memory, the call is synchronous; MOD16_DEVICE: device
+ * memory, asynchronous on `stream`.
+ *
+ *   mod16_sobol_sample_f64   the sample: out[n*R][d] row-major (the rows SALib's sample() returns).
+ *   mod16_sobol_rows_f64     sample, MOD16._et and output in one kernel: y[n][R] = day + night
+ *       (W m-2) of each row, evaluated as MOD16._et(params, *row) with scalars -- the reference's
+ *       operation order (MOD16_MATH_EXACT), and the whole-array switch any(g_surf > 0) decided per
+ *       row. Driver vary[s] takes column s of the sample; the others take base[14] (all 14 given,
+ *       mod16_driver order); params[11] in mod16_param order. Nothing but y is written.
+ *   mod16_sobol_analyze_f64  y[n][R] -> indices and bootstrap spreads; `normalize`: y is first
+ *       standardised over all n*R values (SALib's step). Sums are in a fixed order, without
+ *       floating-point atomics: two calls give the same bits. Device memory: about
+ *       8 * ((resamples + 1) * (nchunks * m(m+1)/2 + 2d + d^2)) bytes of workspace (m = 3 + 2d with
+ *       second order, 3 + d without; nchunks about 1024 / (resamples + 1)), plus y in HOST mode.
+ */
+MOD16_API int mod16_sobol_sample_f64(mod16_ctx* ctx, int d, const double* lo, const double* hi,
+                                     int64_t n, int64_t skip, int second_order, double* out,
+                                     int where, void* stream);
+MOD16_API int mod16_sobol_rows_f64(mod16_ctx* ctx, const double* params, const double* base,
+                                   const int* vary, const double* lo, const double* hi, int d,
+                                   int64_t n, int64_t skip, int second_order, double* y, int where,
+                                   void* stream);
+MOD16_API int mod16_sobol_analyze_f64(mod16_ctx* ctx, const double* y, int d, int64_t n,
+                                      int second_order, int normalize, int resamples, uint64_t seed,
+                                      double* idx_out, double* std_out, int where, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,3 +9,4 @@
 #include "capi/calibration.hip"
 #include "capi/diagnostics.hip"
 #include "capi/tiled.hip"
+#include "capi/sensitivity.hip"

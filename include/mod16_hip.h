@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 6
+#define MOD16_ABI_VERSION 7
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -537,6 +537,62 @@ MOD16_API int mod16_static_batch_info(const mod16_batch* problem, int64_t* n, in
                         int64_t* n_outside_domain);
 MOD16_API int mod16_static_batch_time(mod16_batch* problem, int launches, float* ms);
 MOD16_API int mod16_static_batch_destroy(mod16_batch* problem);
+
+/*
+ * DE-MCMC-Z calibration sampler (ABI 7; mod16_amd/calibration.py): independent chains of PyMC's
+ * DEMetropolisZ -- the project's restatement of it, stated in full at the top of
+ * mod16_amd/csrc/mod16_mcmc.hpp -- over the free parameters of a RESIDENT problem
+ * (mod16_static_batch_bind_f64), with proposals, priors, the likelihood, the Metropolis decision,
+ * tuning and the history in device memory. One lane per chain; K = `segment` steps (propose ->
+ * the problem's objective launches -> accept, on the problem's stream, a single chain of nodes) are
+ * captured as one graph and replayed; the step counter lives on the device, so every replay is the
+ * same graph. Steps that do not fill a K run as one more graph of the remainder.
+ *
+ *   mod16_mcmc_create   problem: float64, bound with MOD16_MATH_FAST and with observations;
+ *       spec->chains <= the problem's max_draws. x0: NULL (every chain starts at the priors'
+ *       support points: Uniform the midpoint, LogNormal exp(mu + s^2/2), Triangular (a + b + c) / 3)
+ *       or [chains][nfree] x-values inside the supports. Evaluates the initial log posterior;
+ *       one that is not finite is MOD16_ERR_ARG.
+ *   mod16_mcmc_run      `steps` more steps of every chain (synchronous). ms, if not NULL: the GPU
+ *       time of the graphs (HIP events).
+ *   mod16_mcmc_read     steps [t0, t0 + count) of the trace, each output optional:
+ *       x, y [count][chains][nfree] (x-values, sampler y-values), loglik, logpost [count][chains],
+ *       accepted [count][chains] (0 / 1); and the current per-chain scaling, lamb [chains] and the
+ *       number of steps taken so far. t0 + count <= steps taken.
+ *   mod16_mcmc_destroy  frees the sampler; destroy every sampler of a problem before the problem.
+ * Checks (MOD16_ERR_ARG): 1 <= nfree <= 11 distinct columns; Uniform / Triangular lower < upper,
+ * lower <= c <= upper, LogNormal sigma > 0, all finite; tune_target 0 (none), 1 (scaling), 2 (lamb);
+ * tune_interval >= 1; tune_steps >= 0; 0 <= tune_drop_fraction < 1; objective 0 (rmsd:
+ * loglik = -sqrt(sse / count)) or 1 (gaussian: -sse / 2); lamb, scaling finite; segment 0 (64) or
+ * 1 .. 1024. Device memory: about 8 (2 nfree + 2) + 1 bytes per chain and step taken (history and
+ * trace, grown by each run -- the graphs are captured again then), plus the objective's workspace
+ * for `chains` draws; what cannot be had is MOD16_ERR_NOMEM. Calls hold the problem's ctx mutex.
+ */
+enum mod16_prior { MOD16_PRIOR_UNIFORM = 0, MOD16_PRIOR_LOGNORMAL = 1, MOD16_PRIOR_TRIANGULAR = 2 };
+typedef struct mod16_mcmc_spec {
+    int32_t chains;
+    int32_t nfree;
+    int32_t index[11];          /* column of free parameter i (mod16_param order), ascending */
+    int32_t family[11];         /* enum mod16_prior */
+    double p0[11], p1[11], p2[11];   /* (lower, upper, -) / (mu, sigma, -) / (lower, upper, c) */
+    double fixed[11];           /* the parameter row; free columns are ignored */
+    double lamb, scaling;
+    int32_t tune_target;
+    int32_t tune_interval;
+    int64_t tune_steps;
+    double tune_drop_fraction;
+    int32_t objective;
+    int32_t segment;
+    uint64_t seed;
+} mod16_mcmc_spec;
+typedef struct mod16_mcmc mod16_mcmc;
+MOD16_API int mod16_mcmc_create(mod16_batch* problem, const mod16_mcmc_spec* spec, const double* x0,
+                                mod16_mcmc** out);
+MOD16_API int mod16_mcmc_run(mod16_mcmc* sampler, int64_t steps, float* ms);
+MOD16_API int mod16_mcmc_read(mod16_mcmc* sampler, int64_t t0, int64_t count, double* x, double* y,
+                              double* loglik, double* logpost, uint8_t* accepted, double* scaling,
+                              double* lamb, int64_t* steps_taken);
+MOD16_API int mod16_mcmc_destroy(mod16_mcmc* sampler);
 
 /*
  * Waits for the ctx's outstanding work on `stream` and reports deferred

@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -66,6 +66,19 @@ class Layout(C.Structure):
 
 
 _LAYP = C.POINTER(Layout)
+
+
+PRIOR_UNIFORM, PRIOR_LOGNORMAL, PRIOR_TRIANGULAR = 0, 1, 2     # enum mod16_prior
+
+
+class McmcSpec(C.Structure):
+    '''``mod16_mcmc_spec`` (include/mod16_hip.h): the sampler's chains, free parameters, priors and tuning.'''
+    _fields_ = [('chains', C.c_int32), ('nfree', C.c_int32), ('index', C.c_int32 * 11),
+                ('family', C.c_int32 * 11), ('p0', C.c_double * 11), ('p1', C.c_double * 11),
+                ('p2', C.c_double * 11), ('fixed', C.c_double * 11), ('lamb', C.c_double),
+                ('scaling', C.c_double), ('tune_target', C.c_int32), ('tune_interval', C.c_int32),
+                ('tune_steps', C.c_int64), ('tune_drop_fraction', C.c_double), ('objective', C.c_int32),
+                ('segment', C.c_int32), ('seed', C.c_uint64)]
 
 # name -> (restype, argtypes); one entry per function declared in the header
 PROTOTYPES = {
@@ -217,6 +230,11 @@ PROTOTYPES = {
     'mod16_sobol_analyze_f64': (C.c_int, [
         C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64,
         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'mod16_mcmc_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    'mod16_mcmc_run': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]),
+    'mod16_mcmc_read': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _I64P]),
+    'mod16_mcmc_destroy': (C.c_int, [C.c_void_p]),
 }
 
 _lib = None

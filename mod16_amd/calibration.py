@@ -1,0 +1,444 @@
+r'''
+MCMC calibration of MOD16 parameters on the GPU: the reference's ``mod16/calibration.py`` sampler
+without PyMC.
+
+The reference's ``MOD16StochasticSampler`` (calibration.py:152-267) builds a PyMC model whose
+priors come from a prior YAML (``CalibrationAPI.tune``, calibration.py:923-931), wraps
+``MOD16._et`` as a black-box likelihood (mod17's ``BlackBoxLikelihood``) and samples it with PyMC's
+``DEMetropolisZ``, one chain per process, evaluating the model one draw at a time on the CPU.
+
+Here the whole chain lives on the device (``mod16_mcmc_*``, C ABI ``include/mod16_hip.h``; the
+arithmetic is stated in full at the top of ``mod16_amd/csrc/mod16_mcmc.hpp``):
+
+- ``load_prior(path, pft)``: the prior dict ``tune()`` builds from a YAML laid out as the
+  reference's (per parameter, lists indexed by PFT, ``~`` for none);
+- ``DEMetropolisZ(problem, params, prior, ...)``: independent DE-MCMC-Z chains (ter Braak & Vrugt
+  2008) over the free parameters of a ``MOD16._et_bind`` problem. Proposals, prior densities, the
+  likelihood, the Metropolis decision, tuning and the Z-history are in device memory; K steps run
+  as one captured graph; any number of chains (up to the problem's ``max_draws``) run in one batch;
+- ``Trace``: the samples (x-values) of the free parameters, log-likelihood, log-posterior and
+  acceptance per step, ``posterior(burn, thin)``, ``rhat()`` (classic split R-hat, BDA3) and
+  ``to_npz``.
+
+The sampler is the project's own restatement of PyMC's ``DEMetropolisZ`` (its ``astep``, ``tune``
+table and ``stop_tuning`` history drop), and the likelihoods -- ``'rmsd'``: ``-sqrt(sse / count)``,
+mod17's ``BlackBoxLikelihood`` as the reference's shipped config uses it; ``'gaussian'``:
+``-sse / 2`` -- are the project's restatements of mod17's. Neither PyMC nor mod17 is available to
+check against, and the random stream is the project's own (counter-based), so chains are not
+PyMC's draw for draw. The defaults (``tune=1000``, ``scaling=1e-3``, ``tune_interval=100``,
+``tune_drop_fraction=0.9``, ``lamb = 2.38 / sqrt(2 d)``) are PyMC's and the reference config's;
+``tune=1000`` is pm.sample's default, which mod17's ``run()`` is believed, not verified, to keep.
+Every chain starts at the priors' support points (Uniform: the midpoint; LogNormal:
+exp(mu + sigma^2 / 2); Triangular: (lower + upper + c) / 3) -- believed, not verified, to be PyMC's
+initial point -- unless ``initial`` is given. The caller states the fixed parameters explicitly
+(the reference fixes ``tmin_close``, ``tmin_open`` and ``vpd_open`` from the BPLUT row plus
+``config['optimization']['fixed']``).
+
+Not provided: HDF5 loading (h5py is absent; ``tools/h5_to_store.py`` covers the field map), k-fold
+cross-validation, the annual-precipitation constraint (``constrain_by_map``), plots, netCDF / arviz
+backends, population DE-MCMC (proposals drawn from other chains), several GPUs, float32 problems.
+There is no CPU fallback: without an MI355X the sampler raises ``Mod16Error``.
+'''
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+from . import MOD16
+
+PARAM_NAMES = list(MOD16.required_parameters)
+FAMILIES = ('uniform', 'lognormal', 'triangular')
+_FAMILY_CODE = {'uniform': _lib.PRIOR_UNIFORM, 'lognormal': _lib.PRIOR_LOGNORMAL,
+                'triangular': _lib.PRIOR_TRIANGULAR}
+OBJECTIVES = ('rmsd', 'gaussian')
+HALF_LOG_2PI = float.fromhex('0x1.d67f1c864beb4p-1')
+_M64 = (1 << 64) - 1
+
+
+def load_prior(path, pft):
+    '''The prior of PFT ``pft`` from a YAML laid out as the reference's prior files: what
+    ``CalibrationAPI.tune`` builds (calibration.py:923-931), ``{name: {key: value}}`` for the
+    parameters of ``MOD16.required_parameters`` the file names, in that order.'''
+    import yaml
+    with open(path, 'r') as f:
+        prior = yaml.safe_load(f)
+    return {p: {k: v[pft] for k, v in prior[p].items()} for p in PARAM_NAMES if p in prior}
+
+
+def prior_family(spec):
+    '''(family, (p0, p1, p2)) of one parameter's prior, inferred from its keys as in the reference's
+    prior YAML: ``lower``/``upper`` Uniform, ``mu``/``sigma`` LogNormal, ``lower``/``upper``/``c``
+    Triangular. Refuses (``ValueError``) other key sets and bad values.'''
+    keys = set(spec)
+    val = lambda k: float(spec[k]) if spec[k] is not None else float('nan')
+    if keys == {'lower', 'upper'}:
+        fam, p = 'uniform', (val('lower'), val('upper'), 0.0)
+    elif keys == {'mu', 'sigma'}:
+        fam, p = 'lognormal', (val('mu'), val('sigma'), 0.0)
+    elif keys == {'lower', 'upper', 'c'}:
+        fam, p = 'triangular', (val('lower'), val('upper'), val('c'))
+    else:
+        raise ValueError('prior keys %s: expected lower/upper, mu/sigma or lower/upper/c' % sorted(keys))
+    if not all(np.isfinite(p)):
+        raise ValueError('%s prior %r: every value must be a finite number' % (fam, dict(spec)))
+    if fam == 'lognormal' and not p[1] > 0:
+        raise ValueError('lognormal prior: sigma must be > 0 (got %r)' % p[1])
+    if fam != 'lognormal' and not p[0] < p[1]:
+        raise ValueError('%s prior: lower < upper needed (got %r, %r)' % (fam, p[0], p[1]))
+    if fam == 'triangular' and not p[0] <= p[2] <= p[1]:
+        raise ValueError('triangular prior: c must lie in [lower, upper] (got %r)' % p[2])
+    return fam, p
+
+
+# ---- the arithmetic of mod16_mcmc.hpp in numpy (host reference of the device code)
+def _softplus(z):
+    z = np.asarray(z, np.float64)
+    with np.errstate(over='ignore'):
+        return np.where(z > 36.0, z, np.log1p(np.exp(np.minimum(z, 36.0))))
+
+
+def x_of_y(family, p, y):
+    '''The model's x of the sampler's y (float64, numpy).'''
+    y = np.asarray(y, np.float64)
+    if family == 'lognormal':
+        return np.exp(y)
+    with np.errstate(over='ignore'):
+        s = 1.0 / (1.0 + np.exp(-y))
+    return p[0] + (p[1] - p[0]) * s
+
+
+def y_of_x(family, p, x):
+    '''The sampler's y of an x inside the support.'''
+    x = np.asarray(x, np.float64)
+    if family == 'lognormal':
+        return np.log(x)
+    q = (x - p[0]) / (p[1] - p[0])
+    return np.log(q / (1.0 - q))
+
+
+def log_prior(family, p, y):
+    '''log p(y) of the prior in y-space, the Jacobian of x(y) included (-inf where the density is
+    0 or undefined).'''
+    y = np.asarray(y, np.float64)
+    if family == 'lognormal':
+        u = y - p[0]
+        return (-np.log(p[1]) - HALF_LOG_2PI) - (u * u) / (2.0 * p[1] * p[1])
+    logistic = -y - 2.0 * _softplus(-y)
+    if family == 'uniform':
+        return logistic
+    a, b, c = p
+    x = x_of_y(family, p, y)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        f = np.where(x < c, 2.0 * (x - a) / ((b - a) * (c - a)), 2.0 * (b - x) / ((b - a) * (b - c)))
+        lf = np.where(f > 0.0, np.log(np.where(f > 0.0, f, 1.0)), -np.inf)
+    return ((lf + np.log(b - a)) - y) - 2.0 * _softplus(-y)
+
+
+def support_point(family, p):
+    '''The initial x of a chain: Uniform the midpoint, LogNormal exp(mu + sigma^2 / 2),
+    Triangular (lower + upper + c) / 3.'''
+    if family == 'uniform':
+        return p[0] + (p[1] - p[0]) / 2.0
+    if family == 'lognormal':
+        return math.exp(p[0] + p[1] * p[1] / 2.0)
+    return (p[0] + p[1] + p[2]) / 3.0
+
+
+def tune_factor(rate):
+    '''PyMC's tune(): the factor scaling (or lamb) is multiplied by, from the acceptance rate.'''
+    if rate < 0.001:
+        return 0.1
+    if rate < 0.05:
+        return 0.5
+    if rate < 0.2:
+        return 0.9
+    if rate > 0.95:
+        return 10.0
+    if rate > 0.75:
+        return 2.0
+    if rate > 0.5:
+        return 1.1
+    return 1.0
+
+
+def mix(z):
+    '''splitmix64's finaliser on a Python int (uint64).'''
+    z &= _M64
+    z ^= z >> 30
+    z = (z * 0xbf58476d1ce4e5b9) & _M64
+    z ^= z >> 27
+    z = (z * 0x94d049bb133111eb) & _M64
+    return z ^ (z >> 31)
+
+
+def stream(seed, c, t, k):
+    '''r(c, t, k) = mix(mix(mix(seed) ^ c) ^ ((t << 6) | k)): the sampler's random word of chain c,
+    step t, slot k.'''
+    return mix(mix(mix(int(seed)) ^ int(c)) ^ ((int(t) << 6) | int(k)))
+
+
+def unit(z):
+    return float(z >> 11) * 2.0 ** -53
+
+
+def index(z, m):
+    return (z * int(m)) >> 64
+
+
+class Trace(object):
+    '''The draws of a ``DEMetropolisZ.sample`` call: ``samples[name]`` (chains, draws) x-values of
+    the free parameters; ``log_likelihood``, ``log_posterior`` (chains, draws) float64; ``accepted``
+    (chains, draws) bool; ``scaling``, ``lamb`` (chains,) at the end of the call; ``acceptance_rate``
+    (chains,) over these draws.'''
+
+    def __init__(self, names, samples, log_likelihood, log_posterior, accepted, scaling, lamb):
+        self.names = list(names)
+        self.samples = samples
+        self.log_likelihood = log_likelihood
+        self.log_posterior = log_posterior
+        self.accepted = accepted
+        self.scaling = scaling
+        self.lamb = lamb
+        self.acceptance_rate = accepted.mean(axis=1) if accepted.shape[1] else np.full(accepted.shape[0], np.nan)
+
+    @property
+    def chains(self):
+        return self.accepted.shape[0]
+
+    @property
+    def draws(self):
+        return self.accepted.shape[1]
+
+    def posterior(self, burn=0, thin=1):
+        '''{name: (chains, k)}: the draws after the first ``burn``, every ``thin``-th.'''
+        burn, thin = int(burn), int(thin)
+        if burn < 0 or thin < 1:
+            raise ValueError('burn >= 0 and thin >= 1 needed')
+        return {k: v[:, burn::thin] for k, v in self.samples.items()}
+
+    def rhat(self, burn=0, thin=1):
+        '''Split R-hat (BDA3, Gelman et al. 2013, 11.4) per free parameter: each chain's draws cut
+        in two halves (the middle draw dropped when odd), then sqrt(var+ / W) over the halves.'''
+        out = {}
+        for name, v in self.posterior(burn, thin).items():
+            n = v.shape[1] // 2
+            if n < 2:
+                raise ValueError('split R-hat needs at least 4 draws per chain')
+            halves = np.concatenate([v[:, :n], v[:, v.shape[1] - n:]], axis=0)
+            m = halves.shape[0]
+            means = halves.mean(axis=1)
+            B = n / (m - 1.0) * np.sum((means - means.mean()) ** 2)
+            W = halves.var(axis=1, ddof=1).mean()
+            var_plus = (n - 1.0) / n * W + B / n
+            out[name] = float(np.sqrt(var_plus / W)) if W > 0 else float('nan')
+        return out
+
+    def to_npz(self, path):
+        '''All of the trace in one ``.npz`` (samples under their parameter names).'''
+        np.savez(path, names=np.array(self.names), log_likelihood=self.log_likelihood,
+                 log_posterior=self.log_posterior, accepted=self.accepted, scaling=self.scaling,
+                 lamb=self.lamb, acceptance_rate=self.acceptance_rate,
+                 **{'sample_' + k: v for k, v in self.samples.items()})
+
+
+def _row(params):
+    if hasattr(params, 'items'):
+        unknown = [k for k in params if k not in PARAM_NAMES]
+        if unknown:
+            raise ValueError('unknown parameter name(s) %s; expected some of %s' % (unknown, PARAM_NAMES))
+        return [params.get(k) for k in PARAM_NAMES]
+    row = list(params)
+    if len(row) != len(PARAM_NAMES):
+        raise ValueError('params must be a dict or a sequence of %d values (MOD16.required_parameters order)'
+                         % len(PARAM_NAMES))
+    return row
+
+
+def _number(v):
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        return float('nan')
+    return v
+
+
+class DEMetropolisZ(object):
+    '''
+    Independent DE-MCMC-Z chains on the GPU over the free parameters of a resident calibration
+    problem (``MOD16._et_bind(..., observed=..., weights=..., max_draws >= chains)``, float64,
+    ``math=MATH_FAST``).
+
+    ``params``: a BPLUT row (dict or 11 values, ``MOD16.required_parameters`` order) that supplies
+    the fixed values. ``prior``: ``{name: {lower, upper} | {mu, sigma} | {lower, upper, c}}`` (what
+    ``load_prior`` returns); a parameter with a prior is free unless ``fixed`` names it. ``fixed``:
+    ``{name: value}`` overriding ``params`` (a ``None`` value fixes nothing, as in the reference).
+    Every parameter must end up free or with a finite value -- a NaN ``beta`` with neither is an
+    error (the reference silently puts in 250). ``tune_target``: ``'scaling'``, ``'lambda'``
+    (``'lamb'``) or ``None``. ``objective``: ``'rmsd'`` or ``'gaussian'`` (any case). ``initial``:
+    optional (chains, d) x-values of the free parameters. ``segment``: steps per captured graph.
+    Everything is checked on the host before any device call (``ValueError``).
+    '''
+
+    def __init__(self, problem, params, prior, fixed=None, chains=3, tune=1000, tune_target='scaling',
+                 tune_interval=100, tune_drop_fraction=0.9, scaling=1e-3, lamb=None, objective='rmsd',
+                 seed=0, initial=None, segment=64):
+        self.problem = problem
+        self._handle = C.c_void_p()
+        row = _row(params)
+        prior = dict(prior or {})
+        fixed = dict(fixed or {})
+        for what, names in (('prior', prior), ('fixed', fixed)):
+            unknown = [k for k in names if k not in PARAM_NAMES]
+            if unknown:
+                raise ValueError('unknown parameter name(s) in %s: %s; expected some of %s'
+                                 % (what, unknown, PARAM_NAMES))
+        free, values = [], []
+        for j, name in enumerate(PARAM_NAMES):
+            is_fixed = name in fixed and fixed[name] is not None
+            has_prior = prior.get(name) is not None and any(v is not None for v in prior[name].values())
+            if is_fixed:
+                v = _number(fixed[name])
+                if not np.isfinite(v):
+                    raise ValueError('fixed[%r] = %r: a fixed value must be a finite number' % (name, fixed[name]))
+                values.append(v)
+            elif has_prior:
+                free.append((j, name) + prior_family(prior[name]))
+                values.append(0.0)
+            else:
+                v = _number(row[j])
+                if not np.isfinite(v):
+                    raise ValueError('%r is neither free (no prior) nor fixed (no fixed value, params gives %r)'
+                                     % (name, row[j]))
+                values.append(v)
+        if not free:
+            raise ValueError('no free parameter: give at least one a prior')
+        self.names = [f[1] for f in free]
+        self.families = {f[1]: f[2] for f in free}
+        self.prior_params = {f[1]: f[3] for f in free}
+        self.fixed_row = np.array(values)
+        d = len(free)
+        self.chains = int(chains)
+        self.tune = int(tune)
+        self.tune_interval = int(tune_interval)
+        self.tune_drop_fraction = float(tune_drop_fraction)
+        self.scaling = float(scaling)
+        self.lamb = 2.38 / math.sqrt(2 * d) if lamb is None else float(lamb)
+        self.seed = int(seed) & _M64
+        target = {None: 0, 'scaling': 1, 'lambda': 2, 'lamb': 2}
+        key = tune_target.lower() if isinstance(tune_target, str) else tune_target
+        if key not in target:
+            raise ValueError("tune_target must be 'scaling', 'lambda' or None (got %r)" % (tune_target,))
+        self.tune_target = key if key != 'lamb' else 'lambda'
+        obj = str(objective).lower()
+        if obj not in OBJECTIVES:
+            raise ValueError('objective must be one of %s (got %r)' % (OBJECTIVES, objective))
+        self.objective = obj
+        if self.chains < 1:
+            raise ValueError('chains must be >= 1')
+        if self.tune < 0 or self.tune_interval < 1 or not 0.0 <= self.tune_drop_fraction < 1.0:
+            raise ValueError('tune >= 0, tune_interval >= 1 and 0 <= tune_drop_fraction < 1 needed')
+        if not (np.isfinite(self.scaling) and np.isfinite(self.lamb)):
+            raise ValueError('scaling and lamb must be finite')
+        if not 0 <= int(segment) <= 1024:
+            raise ValueError('segment must be 0 .. 1024')
+        # the problem: float64, FAST, with observations, room for the chains
+        if getattr(problem, 'dtype', None) != np.float64:
+            raise ValueError('the sampler needs a float64 problem (this one is %s)' % getattr(problem, 'dtype', None))
+        if (int(problem.math) & 3) != _lib.MATH_FAST:
+            raise ValueError('the sampler needs a problem bound with math=MATH_FAST (EXACT cannot be captured)')
+        if not problem.has_observed:
+            raise ValueError('the problem was bound without observed')
+        if self.chains > problem.max_draws:
+            raise ValueError('%d chains, the problem was bound for max_draws = %d' % (self.chains, problem.max_draws))
+        x0 = None
+        if initial is not None:
+            x0 = np.ascontiguousarray(initial, np.float64)
+            if x0.shape != (self.chains, d):
+                raise ValueError('initial must be (chains, %d) = (%d, %d)' % (d, self.chains, d))
+            for i, name in enumerate(self.names):
+                fam, p = self.families[name], self.prior_params[name]
+                ok = (x0[:, i] > 0) & np.isfinite(x0[:, i]) if fam == 'lognormal' else (x0[:, i] > p[0]) & (x0[:, i] < p[1])
+                if not ok.all():
+                    raise ValueError('initial values of %r outside the support of its prior' % name)
+        spec = _lib.McmcSpec()
+        spec.chains, spec.nfree = self.chains, d
+        for i, (j, name, fam, p) in enumerate(free):
+            spec.index[i] = j
+            spec.family[i] = _FAMILY_CODE[fam]
+            spec.p0[i], spec.p1[i], spec.p2[i] = p
+        for j in range(11):
+            spec.fixed[j] = values[j]
+        spec.lamb, spec.scaling = self.lamb, self.scaling
+        spec.tune_target = target[key]
+        spec.tune_interval = self.tune_interval
+        spec.tune_steps = self.tune
+        spec.tune_drop_fraction = self.tune_drop_fraction
+        spec.objective = OBJECTIVES.index(obj)
+        spec.segment = int(segment)
+        spec.seed = self.seed
+        self._ctx = problem._ctx
+        self._keep = (spec, x0)
+        status = self._ctx.lib.mod16_mcmc_create(problem._handle, C.byref(spec),
+                                                 x0.ctypes.data if x0 is not None else None,
+                                                 C.byref(self._handle))
+        if status == _lib.ERR_ARG:
+            raise ValueError(self._ctx.lib.mod16_last_error(self._ctx.handle).decode())
+        self._ctx.check(status)
+        self.steps = 0          # steps taken by every chain, tuning included
+        #: GPU milliseconds of the graphs of the last sample() call
+        self.last_gpu_ms = 0.0
+
+    @property
+    def d(self):
+        return len(self.names)
+
+    def run(self, steps):
+        '''``steps`` more steps of every chain (no trace returned); the GPU milliseconds they took.'''
+        ms = C.c_float(0)
+        self._ctx.check(self._ctx.lib.mod16_mcmc_run(self._handle, int(steps), C.byref(ms)))
+        self.steps += int(steps)
+        self.last_gpu_ms = ms.value
+        return ms.value
+
+    def read(self, t0, count):
+        '''Steps [t0, t0 + count) of every chain: (x (count, chains, d), y, loglik (count, chains),
+        logpost, accepted, scaling (chains,), lamb).'''
+        C_, d = self.chains, self.d
+        x = np.empty((count, C_, d))
+        y = np.empty((count, C_, d))
+        ll = np.empty((count, C_))
+        lp = np.empty((count, C_))
+        acc = np.empty((count, C_), np.uint8)
+        sc = np.empty(C_)
+        lb = np.empty(C_)
+        taken = C.c_int64(0)
+        self._ctx.check(self._ctx.lib.mod16_mcmc_read(
+            self._handle, int(t0), int(count), x.ctypes.data, y.ctypes.data, ll.ctypes.data, lp.ctypes.data,
+            acc.ctypes.data, sc.ctypes.data, lb.ctypes.data, C.byref(taken)))
+        return x, y, ll, lp, acc.astype(bool), sc, lb
+
+    def sample(self, draws):
+        '''``draws`` more draws of every chain -- tuning first on the first call -- as a ``Trace`` of
+        these draws. A later call continues the same chains.'''
+        draws = int(draws)
+        if draws < 0:
+            raise ValueError('draws must be >= 0')
+        first = self.tune if self.steps == 0 else 0
+        start = self.steps + first
+        self.run(first + draws)
+        x, _, ll, lp, acc, sc, lb = self.read(start, draws)
+        samples = {name: np.ascontiguousarray(x[:, :, i].T) for i, name in enumerate(self.names)}
+        return Trace(self.names, samples, np.ascontiguousarray(ll.T), np.ascontiguousarray(lp.T),
+                     np.ascontiguousarray(acc.T), sc, lb)
+
+    def close(self):
+        if getattr(self, '_handle', None) is not None and self._handle.value:
+            self._ctx.lib.mod16_mcmc_destroy(self._handle)
+            self._handle.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

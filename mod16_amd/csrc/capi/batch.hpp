@@ -1,0 +1,105 @@
+// libmod16hip.so, host side: the resident calibration problem (mod16_batch) and the launches of one
+// FAST objective evaluation on it -- shared by the problem's own entry points (calibration.hip) and
+// the sampler that captures them into its graphs (mcmc.hip).
+#pragma once
+#include "internal.hpp"
+#include "../mod16_methods.hpp"
+
+// ---- the calibration problem RESIDENT on the device (mod16_static_batch_bind_*): drivers,
+// observations and weights go up once; an evaluation is parameters up, one graph launch (kernels
+// only), (sse, count) down.
+struct mod16_batch {
+    mod16_ctx* ctx = nullptr;
+    int device = 0;
+    bool f32 = false;
+    unsigned flags = 0;
+    int64_t n = 0, max_draws = 0;
+    int gx = 0;
+    void* owned = nullptr;              // the resident copies (HOST bind); NULL when the caller's device arrays are used
+    const void* drv[14] = {};
+    uint32_t dense_drv = 0;
+    const void* obs = nullptr;
+    const void* wts = nullptr;
+    uint8_t* skip = nullptr;            // [n]: 1 = outside the FAST domain
+    int64_t* list = nullptr;            // those pixels, ascending
+    int64_t nlist = 0;
+    void* ws = nullptr;                 // evaluation workspace (one allocation)
+    void* dparams = nullptr;            // [max_draws][11] of the data type
+    double *par16 = nullptr, *partial = nullptr, *redo = nullptr, *dsse = nullptr, *dcnt = nullptr;
+    unsigned *any_gs = nullptr, *any_draw = nullptr, *dflags = nullptr;
+    void* eval_ws = nullptr;            // partial + any_gs of the FAST objective: sized for the draws actually evaluated
+    int64_t eval_draws = 0;             //   (grown on demand; max_draws x blocks x 20 bytes would be GBs for large n)
+    void* rows = nullptr;               // [ndraw][n] x up to 3: rows workspace, allocated when first asked for
+    size_t rows_bytes = 0;
+    void* hparams = nullptr;            // pinned staging
+    double* hout = nullptr;             // pinned [2][max_draws]
+    hipStream_t st = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int64_t graph_ndraw = -1;
+};
+
+// The evaluation workspace of the FAST objective: the parameter rows it reads and everything it
+// writes. The problem owns one (b->dparams ..., grown by batch_eval_ws); a sampler (capi/mcmc.hip)
+// owns its own, so that a larger objective() call, which regrows the problem's, never pulls memory
+// from under a graph the sampler has captured.
+struct EvalWs {
+    const void* params = nullptr;       // [ndraw][11] of the data type
+    double *par16 = nullptr, *partial = nullptr, *redo = nullptr, *sse = nullptr, *cnt = nullptr;
+    unsigned *any_gs = nullptr, *any_draw = nullptr;
+};
+static EvalWs batch_own_ws(const mod16_batch* b) {
+    EvalWs w;
+    w.params = b->dparams;
+    w.par16 = b->par16;
+    w.partial = b->partial;
+    w.redo = b->redo;
+    w.sse = b->dsse;
+    w.cnt = b->dcnt;
+    w.any_gs = b->any_gs;
+    w.any_draw = b->any_draw;
+    return w;
+}
+
+template <typename T>
+static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int64_t ndraw) {
+    hipStream_t st = b->st;
+    const unsigned gd = (unsigned)((ndraw + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL((static_obj_params_kernel<T>), dim3(gd), dim3(kBlock), 0, st, static_cast<const T*>(w.params), ndraw, w.par16);
+    StaticObjArgs<T> a;
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < 14; ++k) a.drv[k] = static_cast<const T*>(b->drv[k]);
+    a.dense_drv = b->dense_drv;
+    a.n = b->n;
+    a.observed = static_cast<const T*>(b->obs);
+    a.weights = static_cast<const T*>(b->wts);
+    a.skip = b->nlist ? b->skip : nullptr;
+    a.par16 = w.par16;
+    a.tab = b->ctx->tab64;
+    a.ndraw = ndraw;
+    a.any_draw = w.any_draw;
+    a.partial = w.partial;
+    a.any_gs = w.any_gs;
+    const dim3 grid((unsigned)b->gx, (unsigned)((ndraw + kObjDraws - 1) / kObjDraws));
+    hipLaunchKernelGGL((static_obj_kernel<T, true>), grid, dim3(kBlock), 0, st, a);
+    if (b->nlist) {
+        StaticObjRedoArgs<T> r;
+        memset(&r, 0, sizeof r);
+        for (int k = 0; k < 14; ++k) r.drv[k] = static_cast<const T*>(b->drv[k]);
+        r.dense_drv = b->dense_drv;
+        r.params = static_cast<const T*>(w.params);
+        r.observed = a.observed;
+        r.weights = a.weights;
+        r.list = b->list;
+        r.nlist = b->nlist;
+        r.redo = w.redo;
+        hipLaunchKernelGGL((static_obj_redo_kernel<T>), dim3((unsigned)ndraw), dim3(kBlock), 0, st, r);
+    }
+    const double* redo = b->nlist ? w.redo : nullptr;
+    const unsigned gr = (unsigned)((ndraw + kObjPerBlock - 1) / kObjPerBlock);
+    hipLaunchKernelGGL(static_obj_any_kernel, dim3(gr), dim3(kBlock), 0, st, w.any_gs, redo, ndraw, b->gx, w.any_draw);
+    hipLaunchKernelGGL((static_obj_kernel<T, false>), grid, dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(static_obj_final_kernel, dim3(gr), dim3(kBlock), 0, st, w.partial, redo, w.any_draw, ndraw, b->gx,
+                       w.sse, w.cnt);
+}
+

@@ -1,6 +1,5 @@
 // libmod16hip.so -- the vectorised calibration path (N2): mod16_et_static_*, mod16_et_static_batch_*, mod16_static_batch_*
-#include "internal.hpp"
-#include "../mod16_methods.hpp"
+#include "batch.hpp"
 
 // ------------------------------------------- vectorised calibration path (N2)
 // HOST-mode workspace of the calibration entry points, kept in the context between calls (a
@@ -326,40 +325,6 @@ extern "C" int mod16_et_static_batch_f32(mod16_ctx* ctx, const float* const* dri
                                      out_total, observed, weights, sse, count, flags, where, stream);
 }
 
-// ---- the calibration problem RESIDENT on the device (mod16_static_batch_bind_*): drivers,
-// observations and weights go up once; an evaluation is parameters up, one graph launch (kernels
-// only), (sse, count) down.
-struct mod16_batch {
-    mod16_ctx* ctx = nullptr;
-    int device = 0;
-    bool f32 = false;
-    unsigned flags = 0;
-    int64_t n = 0, max_draws = 0;
-    int gx = 0;
-    void* owned = nullptr;              // the resident copies (HOST bind); NULL when the caller's device arrays are used
-    const void* drv[14] = {};
-    uint32_t dense_drv = 0;
-    const void* obs = nullptr;
-    const void* wts = nullptr;
-    uint8_t* skip = nullptr;            // [n]: 1 = outside the FAST domain
-    int64_t* list = nullptr;            // those pixels, ascending
-    int64_t nlist = 0;
-    void* ws = nullptr;                 // evaluation workspace (one allocation)
-    void* dparams = nullptr;            // [max_draws][11] of the data type
-    double *par16 = nullptr, *partial = nullptr, *redo = nullptr, *dsse = nullptr, *dcnt = nullptr;
-    unsigned *any_gs = nullptr, *any_draw = nullptr, *dflags = nullptr;
-    void* eval_ws = nullptr;            // partial + any_gs of the FAST objective: sized for the draws actually evaluated
-    int64_t eval_draws = 0;             //   (grown on demand; max_draws x blocks x 20 bytes would be GBs for large n)
-    void* rows = nullptr;               // [ndraw][n] x up to 3: rows workspace, allocated when first asked for
-    size_t rows_bytes = 0;
-    void* hparams = nullptr;            // pinned staging
-    double* hout = nullptr;             // pinned [2][max_draws]
-    hipStream_t st = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int64_t graph_ndraw = -1;
-};
-
 extern "C" int mod16_static_batch_destroy(mod16_batch* b) {
     if (!b) return MOD16_OK;
     (void)hipSetDevice(b->device);
@@ -547,48 +512,6 @@ static int batch_eval_ws(mod16_batch* b, int64_t ndraw) {
 }
 
 template <typename T>
-static void batch_objective_launches(mod16_batch* b, int64_t ndraw) {
-    hipStream_t st = b->st;
-    const unsigned gd = (unsigned)((ndraw + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL((static_obj_params_kernel<T>), dim3(gd), dim3(kBlock), 0, st, static_cast<const T*>(b->dparams), ndraw, b->par16);
-    StaticObjArgs<T> a;
-    memset(&a, 0, sizeof a);
-    for (int k = 0; k < 14; ++k) a.drv[k] = static_cast<const T*>(b->drv[k]);
-    a.dense_drv = b->dense_drv;
-    a.n = b->n;
-    a.observed = static_cast<const T*>(b->obs);
-    a.weights = static_cast<const T*>(b->wts);
-    a.skip = b->nlist ? b->skip : nullptr;
-    a.par16 = b->par16;
-    a.tab = b->ctx->tab64;
-    a.ndraw = ndraw;
-    a.any_draw = b->any_draw;
-    a.partial = b->partial;
-    a.any_gs = b->any_gs;
-    const dim3 grid((unsigned)b->gx, (unsigned)((ndraw + kObjDraws - 1) / kObjDraws));
-    hipLaunchKernelGGL((static_obj_kernel<T, true>), grid, dim3(kBlock), 0, st, a);
-    if (b->nlist) {
-        StaticObjRedoArgs<T> r;
-        memset(&r, 0, sizeof r);
-        for (int k = 0; k < 14; ++k) r.drv[k] = static_cast<const T*>(b->drv[k]);
-        r.dense_drv = b->dense_drv;
-        r.params = static_cast<const T*>(b->dparams);
-        r.observed = a.observed;
-        r.weights = a.weights;
-        r.list = b->list;
-        r.nlist = b->nlist;
-        r.redo = b->redo;
-        hipLaunchKernelGGL((static_obj_redo_kernel<T>), dim3((unsigned)ndraw), dim3(kBlock), 0, st, r);
-    }
-    const double* redo = b->nlist ? b->redo : nullptr;
-    const unsigned gr = (unsigned)((ndraw + kObjPerBlock - 1) / kObjPerBlock);
-    hipLaunchKernelGGL(static_obj_any_kernel, dim3(gr), dim3(kBlock), 0, st, b->any_gs, redo, ndraw, b->gx, b->any_draw);
-    hipLaunchKernelGGL((static_obj_kernel<T, false>), grid, dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(static_obj_final_kernel, dim3(gr), dim3(kBlock), 0, st, b->partial, redo, b->any_draw, ndraw, b->gx,
-                       b->dsse, b->dcnt);
-}
-
-template <typename T>
 static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, double* sse, double* count) {
     mod16_ctx* ctx = b->ctx;
     if (!params || !sse || !count || ndraw < 0 || ndraw > b->max_draws)
@@ -626,7 +549,7 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, doubl
             b->graph = nullptr;
             b->graph_ndraw = -1;
             HIPCHK(ctx, hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
-            batch_objective_launches<T>(b, ndraw);
+            batch_objective_launches<T>(b, batch_own_ws(b), ndraw);
             hipError_t e = hipStreamEndCapture(b->st, &b->graph);
             HIPCHK(ctx, e);
             HIPCHK(ctx, hipGraphInstantiate(&b->exec, b->graph, nullptr, nullptr, 0));

@@ -1,0 +1,342 @@
+// libmod16hip.so -- the DE-MCMC-Z sampler on a resident problem: mod16_mcmc_* (kernels and the
+// arithmetic: ../mod16_mcmc.hpp)
+#include "batch.hpp"
+#include "../mod16_mcmc.hpp"
+
+constexpr int kMcmcSegment = 64;          // steps per captured graph unless the spec says otherwise
+
+struct mod16_mcmc {
+    mod16_batch* b = nullptr;
+    McmcArgs a;                           // the kernels' arguments (device pointers below)
+    void* state = nullptr;                // y, yp, xc, logp ... t: one allocation
+    void* eval = nullptr;                 // the objective's workspace for `chains` draws (EvalWs)
+    EvalWs w;
+    void* trace = nullptr;                // hist, xtr, tr_ll, tr_lp, tr_acc for `cap` steps
+    int64_t cap = 0, steps = 0;
+    int segment = kMcmcSegment;
+    hipGraph_t g_full = nullptr, g_rem = nullptr;
+    hipGraphExec_t e_full = nullptr, e_rem = nullptr;
+    int64_t rem_len = 0;                  // steps of the remainder graph held in e_rem
+    bool broken = false;                  // a run failed: the device step counters and `steps` may disagree
+};
+
+static void mcmc_drop_graphs(mod16_mcmc* m) {
+    if (m->e_full) (void)hipGraphExecDestroy(m->e_full);
+    if (m->g_full) (void)hipGraphDestroy(m->g_full);
+    if (m->e_rem) (void)hipGraphExecDestroy(m->e_rem);
+    if (m->g_rem) (void)hipGraphDestroy(m->g_rem);
+    m->e_full = m->e_rem = nullptr;
+    m->g_full = m->g_rem = nullptr;
+    m->rem_len = 0;
+}
+
+extern "C" int mod16_mcmc_destroy(mod16_mcmc* m) {
+    if (!m) return MOD16_OK;
+    MOD16_LOCK(m->b->ctx);
+    (void)hipSetDevice(m->b->device);
+    (void)hipStreamSynchronize(m->b->st);
+    mcmc_drop_graphs(m);
+    if (m->state) (void)hipFree(m->state);
+    if (m->eval) (void)hipFree(m->eval);
+    if (m->trace) (void)hipFree(m->trace);
+    delete m;
+    return MOD16_OK;
+}
+
+static int mcmc_nomem(mod16_ctx* ctx, const char* what) {
+    (void)hipGetLastError();
+    return fail(ctx, MOD16_ERR_NOMEM, what);
+}
+
+static size_t mcmc_al(size_t x) { return (x + 255) / 256 * 256; }
+
+// the trace arrays of `cap` steps inside one allocation at `base` (NULL: sizes only)
+static size_t mcmc_trace_layout(const McmcArgs& a, int64_t cap, char* base, McmcArgs* out) {
+    const size_t per_x = mcmc_al((size_t)cap * a.chains * a.d * 8), per_s = mcmc_al((size_t)cap * a.chains * 8),
+                 per_b = mcmc_al((size_t)cap * a.chains);
+    if (out) {
+        out->hist = reinterpret_cast<double*>(base);
+        out->xtr = reinterpret_cast<double*>(base + per_x);
+        out->tr_ll = reinterpret_cast<double*>(base + 2 * per_x);
+        out->tr_lp = reinterpret_cast<double*>(base + 2 * per_x + per_s);
+        out->tr_acc = reinterpret_cast<uint8_t*>(base + 2 * per_x + 2 * per_s);
+    }
+    return 2 * per_x + 2 * per_s + per_b;
+}
+
+// room for `need` steps: a larger allocation, the steps taken copied over, the graphs (which hold the
+// old addresses) dropped
+static int mcmc_reserve(mod16_mcmc* m, int64_t need) {
+    if (need <= m->cap) return MOD16_OK;
+    mod16_ctx* ctx = m->b->ctx;
+    void* nt = nullptr;
+    if (hipMalloc(&nt, mcmc_trace_layout(m->a, need, nullptr, nullptr)) != hipSuccess)
+        return mcmc_nomem(ctx, "mod16_mcmc_run: device memory for the history and trace of this many steps");
+    McmcArgs na = m->a;
+    mcmc_trace_layout(m->a, need, static_cast<char*>(nt), &na);
+    HIPCHK(ctx, hipStreamSynchronize(m->b->st));
+    if (m->steps) {
+        const size_t nx = (size_t)m->steps * m->a.chains * m->a.d * 8, ns = (size_t)m->steps * m->a.chains;
+        HIPCHK(ctx, hipMemcpy(na.hist, m->a.hist, nx, hipMemcpyDeviceToDevice));
+        HIPCHK(ctx, hipMemcpy(na.xtr, m->a.xtr, nx, hipMemcpyDeviceToDevice));
+        HIPCHK(ctx, hipMemcpy(na.tr_ll, m->a.tr_ll, ns * 8, hipMemcpyDeviceToDevice));
+        HIPCHK(ctx, hipMemcpy(na.tr_lp, m->a.tr_lp, ns * 8, hipMemcpyDeviceToDevice));
+        HIPCHK(ctx, hipMemcpy(na.tr_acc, m->a.tr_acc, ns, hipMemcpyDeviceToDevice));
+    }
+    mcmc_drop_graphs(m);
+    if (m->trace) HIPCHK(ctx, hipFree(m->trace));
+    m->trace = nt;
+    m->a = na;
+    m->cap = need;
+    return MOD16_OK;
+}
+
+// `steps` steps as one graph on the problem's stream: propose -> objective -> accept, a single chain
+static int mcmc_capture(mod16_mcmc* m, int64_t steps, hipGraph_t* g, hipGraphExec_t* e) {
+    mod16_batch* b = m->b;
+    mod16_ctx* ctx = b->ctx;
+    const unsigned gc = (unsigned)((m->a.chains + kBlock - 1) / kBlock);
+    HIPCHK(ctx, hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
+    for (int64_t s = 0; s < steps; ++s) {
+        hipLaunchKernelGGL(mcmc_propose_kernel, dim3(gc), dim3(kBlock), 0, b->st, m->a);
+        batch_objective_launches<double>(b, m->w, m->a.chains);
+        hipLaunchKernelGGL(mcmc_accept_kernel, dim3(gc), dim3(kBlock), 0, b->st, m->a);
+    }
+    const hipError_t le = hipGetLastError();
+    const hipError_t ce = hipStreamEndCapture(b->st, g);
+    HIPCHK(ctx, le);
+    HIPCHK(ctx, ce);
+    HIPCHK(ctx, hipGraphInstantiate(e, *g, nullptr, nullptr, 0));
+    return MOD16_OK;
+}
+
+static int mcmc_check_spec(mod16_ctx* ctx, const mod16_batch* b, const mod16_mcmc_spec* s) {
+    if (b->f32 || (b->flags & MOD16_MATH_EXACT) || !b->obs)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: the problem must be float64, MOD16_MATH_FAST and bound with observations");
+    if (s->chains < 1 || s->chains > b->max_draws)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: chains outside 1 .. the problem's max_draws");
+    if (s->nfree < 1 || s->nfree > kMcmcMaxD) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: nfree outside 1 .. 11");
+    for (int i = 0; i < s->nfree; ++i) {
+        if (s->index[i] < 0 || s->index[i] > 10 || (i && s->index[i] <= s->index[i - 1]))
+            return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: free columns must be ascending in 0 .. 10");
+        const double p0 = s->p0[i], p1 = s->p1[i], p2 = s->p2[i];
+        bool ok;
+        switch (s->family[i]) {
+        case MOD16_PRIOR_UNIFORM: ok = std::isfinite(p0) && std::isfinite(p1) && p0 < p1; break;
+        case MOD16_PRIOR_LOGNORMAL: ok = std::isfinite(p0) && std::isfinite(p1) && p1 > 0.0; break;
+        case MOD16_PRIOR_TRIANGULAR:
+            ok = std::isfinite(p0) && std::isfinite(p1) && std::isfinite(p2) && p0 < p1 && p0 <= p2 && p2 <= p1; break;
+        default: ok = false;
+        }
+        if (!ok) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: bad prior (family, lower < upper, lower <= c <= upper, sigma > 0)");
+    }
+    if (s->tune_target < 0 || s->tune_target > 2 || s->tune_interval < 1 || s->tune_steps < 0 ||
+        !(s->tune_drop_fraction >= 0.0 && s->tune_drop_fraction < 1.0) || s->objective < 0 || s->objective > 1 ||
+        !std::isfinite(s->lamb) || !std::isfinite(s->scaling) || s->segment < 0 || s->segment > 1024)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: bad tuning, objective, lamb, scaling or segment");
+    return MOD16_OK;
+}
+
+static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, const double* x0, mod16_mcmc** out) {
+    mod16_ctx* ctx = b->ctx;
+    int rc = mcmc_check_spec(ctx, b, s);
+    if (rc != MOD16_OK) return rc;
+    const int C = s->chains, d = s->nfree;
+    // the initial x-values, [C][d]: the caller's (inside the supports) or the support points
+    std::vector<double> init((size_t)C * d);
+    for (int c = 0; c < C; ++c)
+        for (int i = 0; i < d; ++i) {
+            const double p0 = s->p0[i], p1 = s->p1[i], p2 = s->p2[i];
+            double x;
+            if (x0) {
+                x = x0[(size_t)c * d + i];
+                const bool in = s->family[i] == MOD16_PRIOR_LOGNORMAL ? (x > 0.0 && std::isfinite(x)) : (x > p0 && x < p1);
+                if (!in) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: an initial value outside its prior's support");
+            } else if (s->family[i] == MOD16_PRIOR_UNIFORM) {
+                x = p0 + (p1 - p0) / 2.0;
+            } else if (s->family[i] == MOD16_PRIOR_LOGNORMAL) {
+                x = std::exp(p0 + p1 * p1 / 2.0);
+            } else {
+                x = (p0 + p1 + p2) / 3.0;
+            }
+            init[(size_t)c * d + i] = x;
+        }
+    HIPCHK(ctx, hipSetDevice(b->device));
+    mod16_mcmc* m = new (std::nothrow) mod16_mcmc;
+    if (!m) return MOD16_ERR_NOMEM;
+    m->b = b;
+    m->segment = s->segment ? s->segment : kMcmcSegment;
+    McmcArgs& a = m->a;
+    memset(&a, 0, sizeof a);
+    a.chains = C;
+    a.d = d;
+    for (int i = 0; i < d; ++i) {
+        a.idx[i] = s->index[i];
+        a.fam[i] = s->family[i];
+        a.p0[i] = s->p0[i];
+        a.p1[i] = s->p1[i];
+        a.p2[i] = s->p2[i];
+    }
+    for (int k = 0; k < 11; ++k) a.fixed[k] = s->fixed[k];
+    a.tune_target = s->tune_target;
+    a.tune_interval = s->tune_interval;
+    a.tune_steps = s->tune_steps;
+    a.drop_lo = (int64_t)std::floor(s->tune_drop_fraction * (double)s->tune_steps);
+    a.objective = s->objective;
+    a.seed_mixed = mcmc_mix(s->seed);
+    a.scaling0 = s->scaling;
+    a.lamb0 = s->lamb;
+    rc = [&]() -> int {
+        // per-chain state
+        const size_t sd = mcmc_al((size_t)C * d * 8), s1 = mcmc_al((size_t)C * 8), sx0 = mcmc_al(init.size() * 8);
+        if (hipMalloc(&m->state, 3 * sd + 6 * s1 + mcmc_al((size_t)C * 4) + sx0) != hipSuccess)
+            return mcmc_nomem(ctx, "mod16_mcmc_create: device memory for the chains' state");
+        char* cur = static_cast<char*>(m->state);
+        auto take = [&](size_t x) { char* p = cur; cur += x; return p; };
+        a.y = reinterpret_cast<double*>(take(sd));
+        a.yp = reinterpret_cast<double*>(take(sd));
+        a.xc = reinterpret_cast<double*>(take(sd));
+        a.logp = reinterpret_cast<double*>(take(s1));
+        a.loglik = reinterpret_cast<double*>(take(s1));
+        a.lprior_p = reinterpret_cast<double*>(take(s1));
+        a.scaling = reinterpret_cast<double*>(take(s1));
+        a.lamb = reinterpret_cast<double*>(take(s1));
+        a.t = reinterpret_cast<int64_t*>(take(s1));
+        double* dx0 = reinterpret_cast<double*>(take(sx0));
+        a.acc = reinterpret_cast<int*>(take(mcmc_al((size_t)C * 4)));
+        // the objective's workspace for C draws: the sampler's own (see EvalWs)
+        const size_t sp = mcmc_al((size_t)C * 11 * 8), s16 = mcmc_al((size_t)C * kPar16 * 8),
+                     spart = mcmc_al((size_t)C * b->gx * 16), sany = mcmc_al((size_t)C * b->gx * 4),
+                     su = mcmc_al((size_t)C * 4), sredo = mcmc_al((size_t)C * 40);
+        if (hipMalloc(&m->eval, sp + s16 + spart + sany + su + sredo + 2 * s1) != hipSuccess)
+            return mcmc_nomem(ctx, "mod16_mcmc_create: device memory for the objective's workspace");
+        cur = static_cast<char*>(m->eval);
+        a.params = reinterpret_cast<double*>(take(sp));
+        m->w.params = a.params;
+        m->w.par16 = reinterpret_cast<double*>(take(s16));
+        m->w.partial = reinterpret_cast<double*>(take(spart));
+        m->w.any_gs = reinterpret_cast<unsigned*>(take(sany));
+        m->w.any_draw = reinterpret_cast<unsigned*>(take(su));
+        m->w.redo = reinterpret_cast<double*>(take(sredo));
+        m->w.sse = reinterpret_cast<double*>(take(s1));
+        m->w.cnt = reinterpret_cast<double*>(take(s1));
+        a.sse = m->w.sse;
+        a.cnt = m->w.cnt;
+        // the initial point and its log posterior
+        hipStream_t st = b->st;
+        const unsigned gc = (unsigned)((C + kBlock - 1) / kBlock);
+        HIPCHK(ctx, hipMemcpyAsync(dx0, init.data(), init.size() * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(mcmc_init_kernel, dim3(gc), dim3(kBlock), 0, st, a, (const double*)dx0);
+        batch_objective_launches<double>(b, m->w, C);
+        hipLaunchKernelGGL(mcmc_init_accept_kernel, dim3(gc), dim3(kBlock), 0, st, a);
+        HIPCHK(ctx, hipGetLastError());
+        std::vector<double> lp((size_t)C);
+        HIPCHK(ctx, hipMemcpyAsync(lp.data(), a.logp, (size_t)C * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        for (int c = 0; c < C; ++c)
+            if (!std::isfinite(lp[(size_t)c]))
+                return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: the initial log posterior is not finite");
+        return MOD16_OK;
+    }();
+    if (rc != MOD16_OK) {
+        mod16_mcmc_destroy(m);
+        return rc;
+    }
+    *out = m;
+    return MOD16_OK;
+}
+
+extern "C" int mod16_mcmc_create(mod16_batch* b, const mod16_mcmc_spec* spec, const double* x0, mod16_mcmc** out) {
+    if (!b || !spec || !out) return MOD16_ERR_ARG;
+    *out = nullptr;
+    MOD16_LOCK(b->ctx);
+    return mcmc_create(b, spec, x0, out);
+}
+
+static int mcmc_run(mod16_mcmc* m, int64_t steps, float* ms) {
+    mod16_batch* b = m->b;
+    mod16_ctx* ctx = b->ctx;
+    if (steps < 0 || steps > ((int64_t)1 << 40)) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_run: steps outside 0 .. 2^40");
+    if (m->broken) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_run: an earlier run of this sampler failed");
+    if (ms) *ms = 0.f;
+    if (steps == 0) return MOD16_OK;
+    HIPCHK(ctx, hipSetDevice(b->device));
+    int rc = mcmc_reserve(m, m->steps + steps);
+    if (rc != MOD16_OK) return rc;
+    const int64_t K = m->segment, full = steps / K, rem = steps % K;
+    if (full && !m->e_full) {
+        rc = mcmc_capture(m, K, &m->g_full, &m->e_full);
+        if (rc != MOD16_OK) return rc;
+    }
+    if (rem && m->rem_len != rem) {
+        if (m->e_rem) (void)hipGraphExecDestroy(m->e_rem);
+        if (m->g_rem) (void)hipGraphDestroy(m->g_rem);
+        m->e_rem = nullptr;
+        m->g_rem = nullptr;
+        m->rem_len = 0;
+        rc = mcmc_capture(m, rem, &m->g_rem, &m->e_rem);
+        if (rc != MOD16_OK) return rc;
+        m->rem_len = rem;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ms) {
+        HIPCHK(ctx, hipEventCreate(&e0));
+        HIPCHK(ctx, hipEventCreate(&e1));
+        HIPCHK(ctx, hipEventRecord(e0, b->st));
+    }
+    bool ok = true;
+    for (int64_t i = 0; i < full && ok; ++i) ok = hipGraphLaunch(m->e_full, b->st) == hipSuccess;
+    if (rem && ok) ok = hipGraphLaunch(m->e_rem, b->st) == hipSuccess;
+    if (ms) ok = ok && hipEventRecord(e1, b->st) == hipSuccess;
+    ok = hipStreamSynchronize(b->st) == hipSuccess && ok;
+    if (ms) {
+        float t = 0.f;
+        ok = ok && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
+        *ms = t;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    if (!ok) {
+        m->broken = true;
+        return fail(ctx, MOD16_ERR_HIP, "mod16_mcmc_run: a graph launch failed");
+    }
+    m->steps += steps;
+    return MOD16_OK;
+}
+
+extern "C" int mod16_mcmc_run(mod16_mcmc* m, int64_t steps, float* ms) {
+    if (!m) return MOD16_ERR_ARG;
+    MOD16_LOCK(m->b->ctx);
+    return mcmc_run(m, steps, ms);
+}
+
+static int mcmc_read(mod16_mcmc* m, int64_t t0, int64_t count, double* x, double* y, double* loglik, double* logpost,
+                     uint8_t* accepted, double* scaling, double* lamb, int64_t* steps_taken) {
+    mod16_ctx* ctx = m->b->ctx;
+    if (t0 < 0 || count < 0 || t0 + count > m->steps)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_read: steps outside those taken");
+    HIPCHK(ctx, hipSetDevice(m->b->device));
+    hipStream_t st = m->b->st;
+    const McmcArgs& a = m->a;
+    const size_t nx = (size_t)count * a.chains * a.d, ns = (size_t)count * a.chains;
+    const size_t ox = (size_t)t0 * a.chains * a.d, os = (size_t)t0 * a.chains;
+    if (count) {
+        if (x) HIPCHK(ctx, hipMemcpyAsync(x, a.xtr + ox, nx * 8, hipMemcpyDeviceToHost, st));
+        if (y) HIPCHK(ctx, hipMemcpyAsync(y, a.hist + ox, nx * 8, hipMemcpyDeviceToHost, st));
+        if (loglik) HIPCHK(ctx, hipMemcpyAsync(loglik, a.tr_ll + os, ns * 8, hipMemcpyDeviceToHost, st));
+        if (logpost) HIPCHK(ctx, hipMemcpyAsync(logpost, a.tr_lp + os, ns * 8, hipMemcpyDeviceToHost, st));
+        if (accepted) HIPCHK(ctx, hipMemcpyAsync(accepted, a.tr_acc + os, ns, hipMemcpyDeviceToHost, st));
+    }
+    if (scaling) HIPCHK(ctx, hipMemcpyAsync(scaling, a.scaling, (size_t)a.chains * 8, hipMemcpyDeviceToHost, st));
+    if (lamb) HIPCHK(ctx, hipMemcpyAsync(lamb, a.lamb, (size_t)a.chains * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (steps_taken) *steps_taken = m->steps;
+    return MOD16_OK;
+}
+
+extern "C" int mod16_mcmc_read(mod16_mcmc* m, int64_t t0, int64_t count, double* x, double* y, double* loglik,
+                               double* logpost, uint8_t* accepted, double* scaling, double* lamb, int64_t* steps_taken) {
+    if (!m) return MOD16_ERR_ARG;
+    MOD16_LOCK(m->b->ctx);
+    return mcmc_read(m, t0, count, x, y, loglik, logpost, accepted, scaling, lamb, steps_taken);
+}

@@ -10,3 +10,4 @@
 #include "capi/diagnostics.hip"
 #include "capi/tiled.hip"
 #include "capi/sensitivity.hip"
+#include "capi/mcmc.hip"

@@ -1,5 +1,6 @@
 // libmod16hip.so -- the vectorised calibration path (N2): mod16_et_static_*, mod16_et_static_batch_*, mod16_static_batch_*
 #include "batch.hpp"
+#include "host.hpp"
 
 // ------------------------------------------- vectorised calibration path (N2)
 // HOST-mode workspace of the calibration entry points, kept in the context between calls (a
@@ -74,35 +75,26 @@ static int static_entry(mod16_ctx* ctx, const T* const* drivers, const int64_t* 
     }
     if (where != MOD16_HOST) return fail(ctx, MOD16_ERR_ARG, "mod16_et_static: bad `where`");
     constexpr int kArr = 14 + 11 + 2 + 2;
-    size_t per_arr_small = 0;
-    if (n <= ctx->small_pixels && small_reserve(ctx, n, sizeof(T), kArr, &per_arr_small)) {
+    if (n <= ctx->small_pixels) {
         // what a sampler calls once per draw (a few sites x a year): no allocation, no copy commands --
-        // the two kernels read the page-locked buffer and write their outputs there (run_host_small)
-        const size_t per_arr = per_arr_small;
-        hipStream_t st = ctx->streams[0];
-        char* hb = static_cast<char*>(ctx->small_host);
-        char* db = static_cast<char*>(ctx->small_dev);
-        StaticArgs<T> d = a;
-        int slot = 0;
-        auto put = [&](const T* src, bool dense) -> const T* {
-            const size_t off = 256 + per_arr * slot++;
-            memcpy(hb + off, src, sizeof(T) * (dense ? n : 1));
-            return reinterpret_cast<const T*>(db + off);
-        };
-        for (int k = 0; k < 14; ++k) d.drv[k] = put(a.drv[k], (a.dense_drv >> k) & 1u);
-        for (int k = 0; k < 11; ++k) d.par[k] = put(a.par[k], (a.dense_par >> k) & 1u);
-        for (int k = 0; k < 2; ++k) d.rc[k] = a.rc[k] ? put(a.rc[k], (a.dense_rc >> k) & 1u) : nullptr;
-        const size_t o0 = 256 + per_arr * 27, o1 = 256 + per_arr * 28;
-        d.out[0] = reinterpret_cast<T*>(db + o0);
-        d.out[1] = reinterpret_cast<T*>(db + o1);
-        HIPCHK(ctx, hipMemsetAsync(d.flag, 0, sizeof(unsigned), st));
-        hipLaunchKernelGGL((static_flag_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, d);
-        hipLaunchKernelGGL((static_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, d);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        memcpy(out_day, hb + o0, sizeof(T) * n);
-        memcpy(out_night, hb + o1, sizeof(T) * n);
-        return MOD16_OK;
+        // the two kernels read the page-locked buffer and write their outputs there
+        HostPlan p(sizeof(T));
+        for (int k = 0; k < 14; ++k) p.add(((a.dense_drv >> k) & 1u) ? kIn : kScalar, a.drv[k]);
+        for (int k = 0; k < 11; ++k) p.add(((a.dense_par >> k) & 1u) ? kIn : kScalar, a.par[k]);
+        for (int k = 0; k < 2; ++k) p.add(((a.dense_rc >> k) & 1u) ? kIn : kScalar, a.rc[k]);   // (absent: NULL)
+        for (int k = 0; k < 2; ++k) p.add(kOut, a.out[k]);
+        const int rc = host_small(ctx, p, n, false, [&](const HostTile& t) {
+            StaticArgs<T> d = a;
+            for (int k = 0; k < 14; ++k) d.drv[k] = static_cast<const T*>(t.dev[k]);
+            for (int k = 0; k < 11; ++k) d.par[k] = static_cast<const T*>(t.dev[14 + k]);
+            for (int k = 0; k < 2; ++k) d.rc[k] = static_cast<const T*>(t.dev[25 + k]);
+            for (int k = 0; k < 2; ++k) d.out[k] = static_cast<T*>(t.dev[27 + k]);
+            HIPCHK(ctx, hipMemsetAsync(d.flag, 0, sizeof(unsigned), t.st));
+            hipLaunchKernelGGL((static_flag_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, t.st, d);
+            hipLaunchKernelGGL((static_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, t.st, d);
+            return MOD16_OK;
+        });
+        if (rc != kSmallUnavailable) return rc;
     }
     // HOST: the whole-array branch needs every pixel before any output, so the
     // inputs are made resident once (calibration-sized arrays, not rasters)

@@ -1,5 +1,61 @@
 // libmod16hip.so -- the forward run on numpy / device arrays: mod16_et_*, mod16_et2_*, mod16_et_hdiag_*, mod16_et_diag_*, graphs of it, potential ET
-#include "internal.hpp"
+#include "host.hpp"
+
+// HOST mode: 14 drivers, 11 parameters, 10 outputs (T each), the class raster. (N,) rows and
+// (T, 1) columns (mod16_et2_*) are uploaded whole, once per call, next to the tiles.
+template <typename T>
+static int et_host(mod16_ctx* ctx, const EtArgs<T>& h, unsigned flags, double* tile_diag = nullptr) {
+    const int64_t n = h.n;
+    if (n == 0) return MOD16_OK;
+    HostPlan p(sizeof(T));
+    size_t whole[kHostMaxArrays] = {};      // bytes of each row / column input
+    auto input = [&](const T* x, uint32_t dense, uint32_t row, uint32_t col, int k) {
+        const int i = p.count;
+        if (((row | col) >> k) & 1u) whole[i] = ((row >> k) & 1u ? h.inner : n / h.inner) * sizeof(T);
+        p.add(((dense >> k) & 1u) ? kIn : whole[i] ? kResident : kScalar, x);
+    };
+    for (int k = 0; k < 14; ++k) input(h.drv[k], h.dense_drv, h.row_drv, h.col_drv, k);
+    for (int k = 0; k < 11; ++k) input(h.par[k], h.dense_par, h.row_par, h.col_par, k);
+    for (int k = 0; k < 10; ++k) p.add(kOut, h.out[k]);
+    if (h.cls && h.cls_mode != MOD16_BC_DENSE)
+        whole[35] = h.cls_mode == MOD16_BC_SCALAR ? 1 : h.cls_mode == MOD16_BC_ROW ? h.inner : n / h.inner;
+    p.add(whole[35] ? kResident : kIn, h.cls, true);
+    p.cls = h.cls;
+    auto launch = [&](const HostTile& t) {
+        EtArgs<T> d = h;
+        d.n = t.m;
+        d.base = t.off;
+        for (int k = 0; k < 14; ++k) d.drv[k] = static_cast<const T*>(t.dev[k]);
+        for (int k = 0; k < 11; ++k) d.par[k] = static_cast<const T*>(t.dev[14 + k]);
+        for (int k = 0; k < 10; ++k) d.out[k] = static_cast<T*>(t.dev[25 + k]);
+        d.cls = static_cast<const uint8_t*>(t.dev[35]);
+        return launch_et<T>(ctx, d, flags, t.st, t.diag);
+    };
+    if (n <= ctx->small_pixels && !tile_diag && !has_rows_or_cols(h)) {
+        const int rc = host_small(ctx, p, n, true, launch);
+        if (rc != kSmallUnavailable) return rc;
+    }
+    if (has_rows_or_cols(h)) {
+        size_t need = 256;
+        for (size_t b : whole) need += (b + 255) / 256 * 256;
+        if (ctx->bc_bytes < need) {
+            if (ctx->bc_buf) HIPCHK(ctx, hipFree(ctx->bc_buf));
+            ctx->bc_buf = nullptr;
+            ctx->bc_bytes = 0;
+            HIPCHK(ctx, hipMalloc(&ctx->bc_buf, need));
+            ctx->bc_bytes = need;
+        }
+        char* cur = static_cast<char*>(ctx->bc_buf);
+        for (int i = 0; i < p.count; ++i) {
+            if (!whole[i]) continue;
+            if (hipMemcpy(cur, p.a[i].host, whole[i], hipMemcpyHostToDevice) != hipSuccess)
+                return fail(ctx, MOD16_ERR_HIP, "mod16_et2: upload of a broadcast input failed");
+            p.a[i].dev = cur;
+            cur += (whole[i] + 255) / 256 * 256;
+        }
+    }
+    return host_tiled(ctx, p, n, ctx->host_threads, true, launch, tile_diag);
+}
 
 template <typename T>
 static int et_entry(mod16_ctx* ctx, const uint8_t* cls, const T* const* drivers,
@@ -13,7 +69,7 @@ static int et_entry(mod16_ctx* ctx, const uint8_t* cls, const T* const* drivers,
     if (rc != MOD16_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (where == MOD16_DEVICE) return launch_et<T>(ctx, a, flags, static_cast<hipStream_t>(stream));
-    if (where == MOD16_HOST) return run_host<T>(ctx, a, flags);
+    if (where == MOD16_HOST) return et_host<T>(ctx, a, flags);
     return fail(ctx, MOD16_ERR_ARG, "mod16_et: `where` must be MOD16_HOST or MOD16_DEVICE");
 }
 
@@ -73,7 +129,7 @@ static int hdiag_entry(mod16_ctx* ctx, const uint8_t* cls, const T* const* drive
     int rc = fill_args<T>(ctx, a, cls, drivers, dstride, params, pstride, n, out_day, out_night, nullptr);
     if (rc != MOD16_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return run_host<T>(ctx, a, flags, tile_diag);
+    return et_host<T>(ctx, a, flags, tile_diag);
 }
 extern "C" int mod16_et_hdiag_f64(mod16_ctx* ctx, const uint8_t* cls, const double* const* drivers,
                                   const int64_t* dstride, const double* const* params, const int64_t* pstride,

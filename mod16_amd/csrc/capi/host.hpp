@@ -1,0 +1,230 @@
+// libmod16hip.so, host side: the HOST mode (host arrays in, host arrays out) of the pixel-wise
+// families -- mod16_et_* / mod16_et2_* / mod16_et_pet_* / mod16_et_hdiag_* (forward.hip),
+// mod16_et_raw_* (raw.hip), mod16_method_* (methods.hip), mod16_et_static_* (calibration.hip). A family
+// describes the arrays of one call (HostPlan) and enqueues one tile's kernels (a callback); the two
+// paths here do everything else: host_small (small calls, no copy commands) and host_tiled (tiles
+// staged through the context's slabs).
+#pragma once
+#include "internal.hpp"
+
+namespace {
+constexpr int64_t kTilePixels = int64_t(1) << 21;   // HOST mode: pixels per staged tile
+constexpr size_t kStagger = 33 * 1024;              // see RasterEngine.STAGGER_BYTES
+constexpr int kSmallUnavailable = 1;                // host_small: no page-locked buffer -- the caller stages the call
+constexpr int kHostMaxArrays = 36;
+enum HostKind {
+    kIn,         // per pixel, staged tile by tile
+    kOut,        // per pixel, copied back tile by tile
+    kScalar,     // one value, in the scalar block: index x size, within its 256 bytes
+    kResident,   // a device copy the family uploaded itself, whole (mod16_et2_*'s (N,) and (T, 1) inputs)
+};
+}  // namespace
+
+// The arrays of one HOST-mode call in slab order: the T-sized arrays first (per_arr apart, so the 14
+// drivers -- and raw's per-pixel day_hours -- stay equally spaced and the pipeline takes its pitched
+// instance), the byte rasters behind them. An absent optional array keeps its place (host = NULL)
+// and reaches the kernel as NULL.
+struct HostPlan {
+    struct Array { void* host; void* dev; int elem; int kind; };
+    Array a[kHostMaxArrays];
+    int count = 0, nwide = 0;
+    int elem;                          // sizeof(T)
+    const uint8_t* cls = nullptr;      // the class raster: the small path checks its codes on the host
+    explicit HostPlan(int elem_) : elem(elem_) {}
+    void add(int kind, const void* host, bool bytes = false) {
+        a[count++] = Array{const_cast<void*>(host), nullptr, bytes ? 1 : elem, kind};
+        if (!bytes) ++nwide;
+    }
+    size_t offset(int i, size_t per_arr, size_t per_b) const {
+        return i < nwide ? per_arr * i : per_arr * nwide + per_b * (i - nwide);
+    }
+    void put_scalars(char* block) const {
+        for (int i = 0; i < count; ++i)
+            if (a[i].host && a[i].kind == kScalar) memcpy(block + a[i].elem * i, a[i].host, a[i].elem);
+    }
+    // device address of array i: its slot of the slab (or buffer), the scalar block, its resident copy
+    void* where(int i, char* slot, char* scalars) const {
+        if (!a[i].host) return nullptr;
+        return a[i].kind == kScalar ? scalars + a[i].elem * i : a[i].kind == kResident ? a[i].dev : slot;
+    }
+};
+
+// What a family's callback gets: the device address of every array of the plan for this tile (plan
+// order), its pixels, the stream; it enqueues the tile's kernels and returns a status.
+struct HostTile {
+    void* dev[kHostMaxArrays];
+    int64_t m, off;      // pixels of the tile, its first pixel in the call
+    hipStream_t st;
+    double* diag;        // host_tiled with tile_diag: where this tile's diagnostics vector goes (device)
+};
+
+// The page-locked buffer of the small calls: 256 bytes of scalars, `arrays` arrays of `elem`-byte
+// values and up to three of bytes behind them, for n pixels. It grows with the largest call seen
+// (powers of two from 1024 pixels: a caller of scalars pins 0.3 MB, one of 256 x 256 windows 18 MB).
+// Also makes sure of streams[0]. -> false: no page-locked memory to be had (the context stops
+// asking: its calls are staged from now on).
+static bool small_reserve(mod16_ctx* ctx, int64_t n, size_t elem, int arrays, size_t* per_arr) {
+    int64_t cap = 1024;
+    while (cap < n) cap *= 2;
+    *per_arr = (size_t)cap * elem;
+    const size_t need = 256 + *per_arr * arrays + 3 * (size_t)cap + 256;
+    bool ok = true;
+    if (ctx->small_bytes < need) {
+        if (ctx->small_host) (void)hipHostFree(ctx->small_host);
+        ctx->small_host = ctx->small_dev = nullptr;
+        ctx->small_bytes = 0;
+        ok = hipHostMalloc(&ctx->small_host, need, hipHostMallocDefault) == hipSuccess &&
+             hipHostGetDevicePointer(&ctx->small_dev, ctx->small_host, 0) == hipSuccess;
+        if (ok) ctx->small_bytes = need;
+    }
+    if (ok && !ctx->streams[0]) ok = hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (ctx->small_host) (void)hipHostFree(ctx->small_host);
+        ctx->small_host = ctx->small_dev = nullptr;
+        ctx->small_bytes = 0;
+        ctx->small_pixels = 0;
+    }
+    return ok;
+}
+
+// HOST mode, small calls. The staged path costs a dozen copy commands whatever the size (each
+// dense input its own, pageable memory: the runtime stages and waits), a status read-back and
+// three synchronisations -- 64 us for ONE pixel, where the reference's numpy takes 86 us for its
+// whole forward run (BASELINE.json configs[0]: a flux-tower site), ~290 us up to 16 k pixels.
+// Measured against it (tools/smallcall.py, profiles/r05_small_calls.jsonl): 18 us against 64 for one
+// pixel, 102 against 273 at 100 x 100, 371 against 420 at 256 x 256, even at ~90 k pixels, slower
+// beyond (the CPU's copies into the buffer grow faster than the runtime's DMA): kSmallPixels.
+// Here the CPU copies the inputs into one page-locked buffer, the kernel reads them from there and
+// writes its outputs there (host memory is in the device's address space: a few KB over the link),
+// and the CPU copies the outputs on: one launch sequence, one synchronisation, the same kernels on
+// the same values -- the same bits as the staged path gives. Class codes are checked here instead of
+// by the kernel (the staged path reads the kernel's status word back).
+// pad: whole 16-byte vectors -- a ragged end would cost a second launch (the one-pixel-per-thread
+// kernel behind the vector kernel); the buffer has the room, the pad pixels repeat the last pixel
+// (so they are no new case for the domain guard), and their outputs stay in the buffer.
+template <typename Launch>
+static int host_small(mod16_ctx* ctx, const HostPlan& p, int64_t n, bool pad, Launch&& launch) {
+    size_t per_arr = 0;
+    if (!small_reserve(ctx, n, p.elem, p.nwide, &per_arr)) return kSmallUnavailable;
+    if (p.cls)
+        for (int64_t i = 0; i < n; ++i)
+            if (p.cls[i] >= MOD16_N_CLASSES)
+                return fail(ctx, MOD16_ERR_CLASS_RANGE, "class raster holds a code >= 13 (numpy would raise IndexError)");
+    char* hb = static_cast<char*>(ctx->small_host);
+    char* db = static_cast<char*>(ctx->small_dev);
+    const size_t cap = per_arr / p.elem;           // the buffer's capacity in pixels
+    auto at = [&](int i) { return 256 + p.offset(i, per_arr, cap); };
+    const int64_t V = 16 / p.elem;
+    const int64_t npad = pad ? (n + V - 1) / V * V : n;
+    p.put_scalars(hb);                             // the scalars in the first 256 bytes
+    HostTile t;
+    t.m = npad;
+    t.off = 0;
+    t.st = ctx->streams[0];
+    t.diag = nullptr;
+    for (int i = 0; i < p.count; ++i) {
+        const HostPlan::Array& x = p.a[i];
+        t.dev[i] = p.where(i, db + at(i), db);
+        if (!x.host || x.kind != kIn) continue;
+        memcpy(hb + at(i), x.host, x.elem * n);
+        for (int64_t j = n; j < npad; ++j) memcpy(hb + at(i) + x.elem * j, static_cast<const char*>(x.host) + x.elem * (n - 1), x.elem);
+    }
+    int rc = launch(t);
+    if (rc != MOD16_OK) return rc;
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(t.st));
+    for (int i = 0; i < p.count; ++i)
+        if (p.a[i].host && p.a[i].kind == kOut) memcpy(p.a[i].host, hb + at(i), p.a[i].elem * n);
+    return MOD16_OK;
+}
+
+// HOST mode: tiles of kTilePixels staged through the context's slabs, one host thread and one stream
+// per slot, tile t on slot t % nslots (nslots <= max_slots). The copies from and to pageable memory
+// are what bounds this mode (the HIP runtime stages them through its own pinned buffers on the
+// calling thread), so the slots run them concurrently; kernel launches are serialised (they share the
+// context's workspace). pipeline: the callback may launch the production pipeline -- its workspace is
+// reserved at its final size before any thread launches, and the status word is read back at the end.
+// tile_diag: one diagnostics vector per tile (host, 8 doubles each), reduced by the callback into
+// HostTile::diag while the tile's outputs are on the device.
+template <typename Launch>
+static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slots, bool pipeline,
+                      Launch&& launch, double* tile_diag = nullptr) {
+    const int64_t tile = std::min<int64_t>(n, kTilePixels);
+    const int64_t ntiles = (n + tile - 1) / tile;
+    const int nslots = (int)std::min<int64_t>(ntiles, max_slots);
+    if (nslots > 1) ctx->ws_multi = true;       // one stream per slot: the launches leave their events (ws_release)
+    // successive staged arrays are kStagger bytes apart on top of their size
+    const size_t per_arr = ((size_t)tile * p.elem + 255) / 256 * 256 + kStagger;
+    const size_t per_b = ((size_t)tile + 255) / 256 * 256;
+    const size_t need = p.offset(p.count, per_arr, per_b) + 256;
+    if (ctx->slab_bytes < need) {
+        for (int s = 0; s < kSlots; ++s) {
+            if (ctx->slab[s]) HIPCHK(ctx, hipFree(ctx->slab[s]));
+            ctx->slab[s] = nullptr;
+        }
+        ctx->slab_bytes = need;
+    }
+    for (int s = 0; s < nslots; ++s) {
+        if (!ctx->slab[s]) HIPCHK(ctx, hipMalloc(&ctx->slab[s], ctx->slab_bytes));
+        if (!ctx->streams[s]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[s], hipStreamNonBlocking));
+    }
+    // broadcast scalars live in one small device array
+    char hs[256] = {};
+    p.put_scalars(hs);
+    HIPCHK(ctx, hipMemcpy(ctx->scalars, hs, sizeof hs, hipMemcpyHostToDevice));
+    char* dscal = static_cast<char*>(ctx->scalars);
+    if (pipeline) {   // the kernels' shared workspace at its final size before any thread launches
+        const int64_t npiece = (tile / (16 / p.elem) + 63) / 64;
+        int rc = reserve_diag(ctx, npiece / 2 + 2048);
+        if (rc != MOD16_OK) return rc;
+    }
+    auto stage = [&](int slot, int64_t off) -> int {
+        char* base = static_cast<char*>(ctx->slab[slot]);
+        HostTile t;
+        t.m = std::min(tile, n - off);
+        t.off = off;
+        t.st = ctx->streams[slot];
+        t.diag = tile_diag ? ctx->hdiag_dev + (size_t)slot * kDiag : nullptr;
+        for (int i = 0; i < p.count; ++i) {
+            const HostPlan::Array& x = p.a[i];
+            t.dev[i] = p.where(i, base + p.offset(i, per_arr, per_b), dscal);
+            if (x.host && x.kind == kIn)
+                HIPCHK(ctx, hipMemcpyAsync(t.dev[i], static_cast<const char*>(x.host) + x.elem * off, x.elem * t.m,
+                                           hipMemcpyHostToDevice, t.st));
+        }
+        {
+            std::lock_guard<std::mutex> lock(ctx->launch_mu);
+            int rc = launch(t);
+            if (rc != MOD16_OK) return rc;
+            HIPCHK(ctx, hipGetLastError());
+        }
+        for (int i = 0; i < p.count; ++i) {
+            const HostPlan::Array& x = p.a[i];
+            if (x.host && x.kind == kOut)
+                HIPCHK(ctx, hipMemcpyAsync(static_cast<char*>(x.host) + x.elem * off, t.dev[i], x.elem * t.m,
+                                           hipMemcpyDeviceToHost, t.st));
+        }
+        if (t.diag) HIPCHK(ctx, hipMemcpyAsync(tile_diag + off / tile * kDiag, t.diag, sizeof(double) * kDiag, hipMemcpyDeviceToHost, t.st));
+        HIPCHK(ctx, hipStreamSynchronize(t.st));      // the slab of this slot is free again
+        return MOD16_OK;
+    };
+    if (nslots == 1) {
+        for (int64_t off = 0; off < n; off += tile) {
+            int rc = stage(0, off);
+            if (rc != MOD16_OK) return rc;
+        }
+    } else {
+        int rcs[kSlots] = {};
+        std::vector<std::thread> workers;
+        for (int s = 0; s < nslots; ++s)
+            workers.emplace_back([&, s]() {
+                if (hipSetDevice(ctx->device) != hipSuccess) { rcs[s] = MOD16_ERR_HIP; return; }
+                for (int64_t t = s; t < ntiles && rcs[s] == MOD16_OK; t += nslots) rcs[s] = stage(s, t * tile);
+            });
+        for (auto& w : workers) w.join();
+        for (int s = 0; s < nslots; ++s)
+            if (rcs[s] != MOD16_OK) return rcs[s];
+    }
+    return pipeline ? read_status(ctx, ctx->streams[0]) : MOD16_OK;
+}

@@ -1,5 +1,5 @@
 // libmod16hip.so, host side: what the entry-point families (capi/*.hip) share -- the device
-// context, the launch machinery of the pipeline and of the plain kernels, the HOST-mode tiler.
+// context, the launch machinery of the pipeline and of the plain kernels (the HOST mode: host.hpp).
 // Internal linkage throughout (every translation unit holds its own copy of what it uses);
 // mod16_capi.hip includes all families into ONE unit for single-command builds (variants,
 // tests/host_asan, listings), mod16_amd/csrc/build.py compiles them side by side.
@@ -25,13 +25,10 @@
 using namespace mod16;
 
 namespace {
-constexpr int64_t kTilePixels = int64_t(1) << 21;   // HOST mode: pixels per staged tile
 constexpr int kDiagBlocks = 1024;
 constexpr int kSlots = 12;                          // staging slots = host threads of the HOST mode
-constexpr size_t kStagger = 33 * 1024;              // see RasterEngine.STAGGER_BYTES
 constexpr int kSmallPixels = 65536;                 // HOST mode: calls up to this size take the copy-free path
 constexpr int kSmallPixelsMax = 1 << 18;            // ... and what MOD16_SMALL_PIXELS may raise it to
-constexpr int kSmallUnavailable = 1;                // run_host_small: no page-locked buffer -- the caller stages the call
 }  // namespace
 
 // Workspace of the per-run diagnostics partials of et_stream_kernel (and of the
@@ -638,287 +635,6 @@ static int read_status(mod16_ctx* ctx, hipStream_t st) {
         return fail(ctx, MOD16_ERR_CLASS_RANGE, "class raster holds a code >= 13 (numpy would raise IndexError)");
     return MOD16_OK;
 }
-
-// HOST mode: tiles of kTilePixels staged through kSlots device slabs, one host
-// thread and one stream per slot. The copies from and to pageable numpy memory
-// are what bounds this mode (the HIP runtime stages them through its own pinned
-// buffers on the calling thread), so the slots run them concurrently; kernel
-// launches are serialised (they share the context's workspace).
-// device copies of the inputs that are neither dense nor scalars: (N,) rows and
-// (T, 1) columns, uploaded whole once per call
-template <typename T> struct BcTable {
-    const T* drv[14] = {};
-    const T* par[11] = {};
-    const uint8_t* cls = nullptr;
-};
-
-template <typename T>
-static int stage_tile(mod16_ctx* ctx, const EtArgs<T>& h, unsigned flags, const T* dscal,
-                      size_t per_arr, int slot, int64_t off, int64_t m, const BcTable<T>& bc,
-                      double* tile_diag = nullptr) {
-    hipStream_t st = ctx->streams[slot];
-    char* base = static_cast<char*>(ctx->slab[slot]);
-    EtArgs<T> d = h;
-    d.n = m;
-    d.base = off;
-    for (int k = 0; k < 14; ++k) {
-        if ((h.dense_drv >> k) & 1u) {
-            T* dp = reinterpret_cast<T*>(base + per_arr * k);
-            HIPCHK(ctx, hipMemcpyAsync(dp, h.drv[k] + off, sizeof(T) * m, hipMemcpyHostToDevice, st));
-            d.drv[k] = dp;
-        } else if (bc.drv[k]) {
-            d.drv[k] = bc.drv[k];
-        } else {
-            d.drv[k] = dscal + k;
-        }
-    }
-    if (h.cls) {
-        if (h.cls_mode == MOD16_BC_DENSE) {
-            uint8_t* dc = reinterpret_cast<uint8_t*>(base + per_arr * 35);
-            HIPCHK(ctx, hipMemcpyAsync(dc, h.cls + off, (size_t)m, hipMemcpyHostToDevice, st));
-            d.cls = dc;
-        } else {
-            d.cls = bc.cls;
-        }
-    } else {
-        for (int k = 0; k < 11; ++k) {
-            if ((h.dense_par >> k) & 1u) {
-                T* dp = reinterpret_cast<T*>(base + per_arr * (14 + k));
-                HIPCHK(ctx, hipMemcpyAsync(dp, h.par[k] + off, sizeof(T) * m, hipMemcpyHostToDevice, st));
-                d.par[k] = dp;
-            } else if (bc.par[k]) {
-                d.par[k] = bc.par[k];
-            } else {
-                d.par[k] = dscal + 14 + k;
-            }
-        }
-    }
-    for (int k = 0; k < 10; ++k)
-        d.out[k] = h.out[k] ? reinterpret_cast<T*>(base + per_arr * (25 + k)) : nullptr;
-    // tile_diag: the diagnostics vector of THIS tile (host, 8 doubles), reduced on the device
-    // while the tile's outputs are there
-    double* dd = tile_diag ? ctx->hdiag_dev + (size_t)slot * kDiag : nullptr;
-    {
-        std::lock_guard<std::mutex> lock(ctx->launch_mu);
-        int rc = launch_et<T>(ctx, d, flags, st, dd);
-        if (rc != MOD16_OK) return rc;
-    }
-    for (int k = 0; k < 10; ++k)
-        if (h.out[k]) HIPCHK(ctx, hipMemcpyAsync(h.out[k] + off, d.out[k], sizeof(T) * m, hipMemcpyDeviceToHost, st));
-    if (dd) HIPCHK(ctx, hipMemcpyAsync(tile_diag, dd, sizeof(double) * kDiag, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));      // the slab of this slot is free again
-    return MOD16_OK;
-}
-
-// The page-locked buffer of the small calls: 256 bytes of scalars, `arrays` arrays of `elem`-byte
-// values and up to three of bytes behind them, for n pixels. It grows with the largest call seen
-// (powers of two from 1024 pixels: a caller of scalars pins 0.3 MB, one of 256 x 256 windows 18 MB).
-// Also makes sure of streams[0]. -> false: no page-locked memory to be had (the context stops
-// asking: its calls are staged from now on).
-static bool small_reserve(mod16_ctx* ctx, int64_t n, size_t elem, int arrays, size_t* per_arr) {
-    int64_t cap = 1024;
-    while (cap < n) cap *= 2;
-    *per_arr = (size_t)cap * elem;
-    const size_t need = 256 + *per_arr * arrays + 3 * (size_t)cap + 256;
-    bool ok = true;
-    if (ctx->small_bytes < need) {
-        if (ctx->small_host) (void)hipHostFree(ctx->small_host);
-        ctx->small_host = ctx->small_dev = nullptr;
-        ctx->small_bytes = 0;
-        ok = hipHostMalloc(&ctx->small_host, need, hipHostMallocDefault) == hipSuccess &&
-             hipHostGetDevicePointer(&ctx->small_dev, ctx->small_host, 0) == hipSuccess;
-        if (ok) ctx->small_bytes = need;
-    }
-    if (ok && !ctx->streams[0]) ok = hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        if (ctx->small_host) (void)hipHostFree(ctx->small_host);
-        ctx->small_host = ctx->small_dev = nullptr;
-        ctx->small_bytes = 0;
-        ctx->small_pixels = 0;
-    }
-    return ok;
-}
-
-// HOST mode, small calls. The staged path costs a dozen copy commands whatever the size (each
-// dense input its own, pageable memory: the runtime stages and waits), a status read-back and
-// three synchronisations -- 64 us for ONE pixel, where the reference's numpy takes 86 us for its
-// whole forward run (BASELINE.json configs[0]: a flux-tower site), ~290 us up to 16 k pixels.
-// Measured against it (tools/smallcall.py, profiles/r05_small_calls.jsonl): 18 us against 64 for one
-// pixel, 102 against 273 at 100 x 100, 371 against 420 at 256 x 256, even at ~90 k pixels, slower
-// beyond (the CPU's copies into the buffer grow faster than the runtime's DMA): kSmallPixels.
-// Here the CPU copies the inputs into one page-locked buffer, the kernel reads them from there and
-// writes its outputs there (host memory is in the device's address space: a few KB over the link),
-// and the CPU copies the outputs on: one launch, one synchronisation, the same kernels on the same
-// values -- the same bits as the staged path gives. Class codes are checked here instead of by the
-// kernel (the staged path reads the kernel's status word back).
-template <typename T>
-static int run_host_small(mod16_ctx* ctx, const EtArgs<T>& h, unsigned flags) {
-    const int64_t n = h.n;
-    size_t per_arr = 0;
-    if (!small_reserve(ctx, n, sizeof(T), 14 + 11 + 10, &per_arr)) return kSmallUnavailable;
-    hipStream_t st = ctx->streams[0];
-    if (h.cls) {       // (dense: a broadcast class raster is has_rows_or_cols' business)
-        for (int64_t i = 0; i < n; ++i)
-            if (h.cls[i] >= MOD16_N_CLASSES)
-                return fail(ctx, MOD16_ERR_CLASS_RANGE, "class raster holds a code >= 13 (numpy would raise IndexError)");
-    }
-    char* hb = static_cast<char*>(ctx->small_host);
-    char* db = static_cast<char*>(ctx->small_dev);
-    T* hs = reinterpret_cast<T*>(hb);              // 25 broadcast scalars in the first 256 bytes
-    const T* dscal = reinterpret_cast<const T*>(db);
-    EtArgs<T> d = h;
-    d.base = 0;
-    // whole 16-byte vectors: a ragged end would cost a second launch (the one-pixel-per-thread
-    // kernel behind the vector kernel) -- the buffer has the room, the pad pixels repeat the last
-    // pixel (so they are no new case for the domain guard), and their outputs stay in the buffer
-    constexpr int V = VecOf<T>::v;
-    const int64_t npad = (n + V - 1) / V * V;
-    d.n = npad;
-    auto arr = [&](int k) { return (size_t)256 + per_arr * k; };
-    auto put = [&](size_t off, const void* src, size_t elem) {
-        memcpy(hb + off, src, elem * n);
-        for (int64_t i = n; i < npad; ++i) memcpy(hb + off + elem * i, static_cast<const char*>(src) + elem * (n - 1), elem);
-    };
-    for (int k = 0; k < 14; ++k) {
-        if ((h.dense_drv >> k) & 1u) {
-            put(arr(k), h.drv[k], sizeof(T));
-            d.drv[k] = reinterpret_cast<const T*>(db + arr(k));
-        } else {
-            hs[k] = h.drv[k][0];
-            d.drv[k] = dscal + k;
-        }
-    }
-    if (h.cls) {
-        const size_t off = arr(35);
-        put(off, h.cls, 1);
-        d.cls = reinterpret_cast<const uint8_t*>(db + off);
-    } else {
-        for (int k = 0; k < 11; ++k) {
-            if ((h.dense_par >> k) & 1u) {
-                put(arr(14 + k), h.par[k], sizeof(T));
-                d.par[k] = reinterpret_cast<const T*>(db + arr(14 + k));
-            } else {
-                hs[14 + k] = h.par[k][0];
-                d.par[k] = dscal + 14 + k;
-            }
-        }
-    }
-    for (int k = 0; k < 10; ++k)
-        d.out[k] = h.out[k] ? reinterpret_cast<T*>(db + arr(25 + k)) : nullptr;
-    int rc = launch_et<T>(ctx, d, flags, st);
-    if (rc != MOD16_OK) return rc;
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    for (int k = 0; k < 10; ++k)
-        if (h.out[k]) memcpy(h.out[k], hb + arr(25 + k), sizeof(T) * n);
-    return MOD16_OK;
-}
-
-template <typename T>
-static int run_host(mod16_ctx* ctx, const EtArgs<T>& h, unsigned flags, double* tile_diag = nullptr) {
-    const int64_t n = h.n;
-    if (n == 0) return MOD16_OK;
-    if (n <= ctx->small_pixels && !tile_diag && !has_rows_or_cols(h)) {
-        const int rc = run_host_small<T>(ctx, h, flags);
-        if (rc != kSmallUnavailable) return rc;
-    }
-    const int64_t tile = std::min<int64_t>(n, kTilePixels);
-    const int64_t ntiles = (n + tile - 1) / tile;
-    const int nslots = (int)std::min<int64_t>(ntiles, ctx->host_threads);
-    if (nslots > 1) ctx->ws_multi = true;       // one stream per slot: the launches leave their events (ws_release)
-    // slab layout per slot: 14 drivers | 11 params | 10 outputs (T each) | class bytes
-    // successive staged arrays are kStagger bytes apart on top of their size
-    const size_t per_arr = (((size_t)tile * sizeof(T)) + 255) / 256 * 256 + kStagger;
-    const size_t need = per_arr * (14 + 11 + 10) + (size_t)tile + 256;
-    if (ctx->slab_bytes < need) {
-        for (int s = 0; s < kSlots; ++s) {
-            if (ctx->slab[s]) HIPCHK(ctx, hipFree(ctx->slab[s]));
-            ctx->slab[s] = nullptr;
-        }
-        ctx->slab_bytes = need;
-    }
-    for (int s = 0; s < nslots; ++s) {
-        if (!ctx->slab[s]) HIPCHK(ctx, hipMalloc(&ctx->slab[s], ctx->slab_bytes));
-        if (!ctx->streams[s]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[s], hipStreamNonBlocking));
-    }
-    // broadcast scalars live in one small device array
-    T hs[32];
-    for (int k = 0; k < 14; ++k) hs[k] = ((h.dense_drv >> k) & 1u) ? T(0) : h.drv[k][0];
-    for (int k = 0; k < 11; ++k) hs[14 + k] = (!h.cls && !((h.dense_par >> k) & 1u)) ? h.par[k][0] : T(0);
-    HIPCHK(ctx, hipMemcpy(ctx->scalars, hs, sizeof(T) * 25, hipMemcpyHostToDevice));
-    const T* dscal = static_cast<const T*>(ctx->scalars);
-    // (N,) rows and (T, 1) columns: whole, once, next to the tiles
-    BcTable<T> bc;
-    if (has_rows_or_cols(h)) {
-        const int64_t nrow = h.inner, ncol = n / h.inner;
-        auto len_of = [&](bool row) { return (size_t)(row ? nrow : ncol); };
-        size_t need_bc = 256;
-        for (int k = 0; k < 14; ++k)
-            if (((h.row_drv | h.col_drv) >> k) & 1u) need_bc += (len_of((h.row_drv >> k) & 1u) * sizeof(T) + 255) / 256 * 256;
-        for (int k = 0; k < 11 && !h.cls; ++k)
-            if (((h.row_par | h.col_par) >> k) & 1u) need_bc += (len_of((h.row_par >> k) & 1u) * sizeof(T) + 255) / 256 * 256;
-        if (h.cls && h.cls_mode != MOD16_BC_DENSE)
-            need_bc += (h.cls_mode == MOD16_BC_SCALAR ? 1 : len_of(h.cls_mode == MOD16_BC_ROW)) + 256;
-        if (ctx->bc_bytes < need_bc) {
-            if (ctx->bc_buf) HIPCHK(ctx, hipFree(ctx->bc_buf));
-            ctx->bc_buf = nullptr;
-            ctx->bc_bytes = 0;
-            HIPCHK(ctx, hipMalloc(&ctx->bc_buf, need_bc));
-            ctx->bc_bytes = need_bc;
-        }
-        char* cur = static_cast<char*>(ctx->bc_buf);
-        auto up = [&](const void* src, size_t bytes) -> const void* {
-            char* p = cur;
-            if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-            cur += (bytes + 255) / 256 * 256;
-            return p;
-        };
-        for (int k = 0; k < 14; ++k)
-            if (((h.row_drv | h.col_drv) >> k) & 1u) {
-                bc.drv[k] = static_cast<const T*>(up(h.drv[k], len_of((h.row_drv >> k) & 1u) * sizeof(T)));
-                if (!bc.drv[k]) return fail(ctx, MOD16_ERR_HIP, "mod16_et2: upload of a broadcast input failed");
-            }
-        for (int k = 0; k < 11 && !h.cls; ++k)
-            if (((h.row_par | h.col_par) >> k) & 1u) {
-                bc.par[k] = static_cast<const T*>(up(h.par[k], len_of((h.row_par >> k) & 1u) * sizeof(T)));
-                if (!bc.par[k]) return fail(ctx, MOD16_ERR_HIP, "mod16_et2: upload of a broadcast input failed");
-            }
-        if (h.cls && h.cls_mode != MOD16_BC_DENSE) {
-            bc.cls = static_cast<const uint8_t*>(up(h.cls, h.cls_mode == MOD16_BC_SCALAR ? 1 : len_of(h.cls_mode == MOD16_BC_ROW)));
-            if (!bc.cls) return fail(ctx, MOD16_ERR_HIP, "mod16_et2: upload of the class raster failed");
-        }
-    }
-    // the kernels' shared workspace at its final size before any thread launches
-    {
-        const int64_t npiece = (tile / VecOf<T>::v + 63) / 64;
-        int rc = reserve_diag(ctx, npiece / 2 + 2048);
-        if (rc != MOD16_OK) return rc;
-    }
-    if (nslots == 1) {
-        for (int64_t off = 0; off < n; off += tile) {
-            int rc = stage_tile<T>(ctx, h, flags, dscal, per_arr, 0, off, std::min(tile, n - off), bc,
-                                   tile_diag ? tile_diag + (off / tile) * kDiag : nullptr);
-            if (rc != MOD16_OK) return rc;
-        }
-    } else {
-        int rcs[kSlots] = {};
-        std::vector<std::thread> workers;
-        for (int s = 0; s < nslots; ++s)
-            workers.emplace_back([&, s]() {
-                if (hipSetDevice(ctx->device) != hipSuccess) { rcs[s] = MOD16_ERR_HIP; return; }
-                for (int64_t t = s; t < ntiles && rcs[s] == MOD16_OK; t += nslots)
-                    rcs[s] = stage_tile<T>(ctx, h, flags, dscal, per_arr, s, t * tile, std::min(tile, n - t * tile), bc,
-                                           tile_diag ? tile_diag + t * kDiag : nullptr);
-            });
-        for (auto& w : workers) w.join();
-        for (int s = 0; s < nslots; ++s)
-            if (rcs[s] != MOD16_OK) return rcs[s];
-    }
-    for (int s = 0; s < nslots; ++s) HIPCHK(ctx, hipStreamSynchronize(ctx->streams[s]));
-    return read_status(ctx, ctx->streams[0]);
-}
-
 
 // ---- the forward run + diagnostics of one raster as a HIP graph: the launch
 // sequence of mod16_et_diag_* (counter reset, pipeline kernel, staged fixed-order

@@ -1,5 +1,5 @@
 // libmod16hip.so -- the class-surface sub-methods (mod16_method_*)
-#include "internal.hpp"
+#include "host.hpp"
 #include "../mod16_methods.hpp"
 
 // ------------------------------------------------------- class-surface methods
@@ -52,100 +52,26 @@ static int method_entry(mod16_ctx* ctx, int method, const T* const* in, const in
         return MOD16_OK;
     }
     if (where != MOD16_HOST) return fail(ctx, MOD16_ERR_ARG, "mod16_method: bad `where`");
-    size_t per_arr_small = 0;
-    if (n <= ctx->small_pixels && small_reserve(ctx, n, sizeof(T), kMethodMaxIn + 11 + 2, &per_arr_small)) {
-        const size_t per_arr = per_arr_small;
-        // small calls (what the class surface is used for: scalars, a site's series): no copy
-        // commands, the kernel reads and writes one page-locked buffer (run_host_small)
-        hipStream_t st = ctx->streams[0];
-        char* hb = static_cast<char*>(ctx->small_host);
-        char* db = static_cast<char*>(ctx->small_dev);
-        T* hs = reinterpret_cast<T*>(hb);
-        const T* dscal = reinterpret_cast<const T*>(db);
-        static_assert(sizeof(double) * (kMethodMaxIn + 11) <= 256, "scalars of a method call fit the buffer's head");
-        auto arr = [&](int k) { return (size_t)256 + per_arr * k; };
+    // HOST mode: the inputs (absent: NULL), the parameters (absent: NaN scalars), 2 outputs
+    HostPlan p(sizeof(T));
+    static_assert(sizeof(double) * (kMethodMaxIn + 11) <= 256, "scalars of a method call fit the scalar block");
+    for (int k = 0; k < kMethodMaxIn; ++k) p.add(((a.dense_in >> k) & 1u) ? kIn : kScalar, a.in[k]);
+    for (int k = 0; k < 11; ++k) p.add(((a.dense_par >> k) & 1u) ? kIn : kScalar, a.par[k] ? a.par[k] : &nan_param);
+    for (int k = 0; k < 2; ++k) p.add(kOut, a.out[k]);
+    auto launch_tile = [&](const HostTile& t) {
         MethodArgs<T> d = a;
-        for (int k = 0; k < kMethodMaxIn; ++k) {
-            if (!a.in[k]) continue;
-            if ((a.dense_in >> k) & 1u) {
-                memcpy(hb + arr(k), a.in[k], sizeof(T) * n);
-                d.in[k] = reinterpret_cast<const T*>(db + arr(k));
-            } else {
-                hs[k] = a.in[k][0];
-                d.in[k] = dscal + k;
-            }
-        }
-        for (int k = 0; k < 11; ++k) {
-            if (a.par[k] && ((a.dense_par >> k) & 1u)) {
-                memcpy(hb + arr(kMethodMaxIn + k), a.par[k], sizeof(T) * n);
-                d.par[k] = reinterpret_cast<const T*>(db + arr(kMethodMaxIn + k));
-            } else {
-                hs[kMethodMaxIn + k] = a.par[k] ? a.par[k][0] : nan_param;
-                d.par[k] = dscal + kMethodMaxIn + k;
-            }
-        }
-        for (int k = 0; k < 2; ++k)
-            d.out[k] = a.out[k] ? reinterpret_cast<T*>(db + arr(kMethodMaxIn + 11 + k)) : nullptr;
-        launch(d, st);
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        for (int k = 0; k < 2; ++k)
-            if (a.out[k]) memcpy(a.out[k], hb + arr(kMethodMaxIn + 11 + k), sizeof(T) * n);
+        d.n = t.m;
+        for (int k = 0; k < kMethodMaxIn; ++k) d.in[k] = static_cast<const T*>(t.dev[k]);
+        for (int k = 0; k < 11; ++k) d.par[k] = static_cast<const T*>(t.dev[kMethodMaxIn + k]);
+        for (int k = 0; k < 2; ++k) d.out[k] = static_cast<T*>(t.dev[kMethodMaxIn + 11 + k]);
+        launch(d, t.st);
         return MOD16_OK;
+    };
+    if (n <= ctx->small_pixels) {
+        const int rc = host_small(ctx, p, n, false, launch_tile);
+        if (rc != kSmallUnavailable) return rc;
     }
-    // HOST: one slab, tile by tile (no double buffering)
-    const int64_t tile = std::min<int64_t>(n, kTilePixels);
-    const size_t per_arr = (((size_t)tile * sizeof(T)) + 255) / 256 * 256;
-    const size_t need = per_arr * (14 + 11 + 8) + (size_t)tile + 256;
-    if (ctx->slab_bytes < need) {
-        for (int s = 0; s < kSlots; ++s) {
-            if (ctx->slab[s]) HIPCHK(ctx, hipFree(ctx->slab[s]));
-            ctx->slab[s] = nullptr;
-        }
-        ctx->slab_bytes = need;
-    }
-    if (!ctx->slab[0]) HIPCHK(ctx, hipMalloc(&ctx->slab[0], ctx->slab_bytes));      // (this mode uses one slot)
-    if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
-    hipStream_t st = ctx->streams[0];
-    T hs[32];
-    for (int k = 0; k < kMethodMaxIn; ++k) hs[k] = (a.in[k] && !((a.dense_in >> k) & 1u)) ? a.in[k][0] : T(0);
-    for (int k = 0; k < 11; ++k)
-        hs[kMethodMaxIn + k] = !a.par[k] ? nan_param : (((a.dense_par >> k) & 1u) ? T(0) : a.par[k][0]);
-    HIPCHK(ctx, hipMemcpy(ctx->scalars, hs, sizeof(T) * (kMethodMaxIn + 11), hipMemcpyHostToDevice));
-    const T* dscal = static_cast<const T*>(ctx->scalars);
-    char* base = static_cast<char*>(ctx->slab[0]);
-    for (int64_t off = 0; off < n; off += tile) {
-        const int64_t m = std::min(tile, n - off);
-        MethodArgs<T> d = a;
-        d.n = m;
-        for (int k = 0; k < kMethodMaxIn; ++k) {
-            if (!a.in[k]) continue;
-            if ((a.dense_in >> k) & 1u) {
-                T* dp = reinterpret_cast<T*>(base + per_arr * k);
-                HIPCHK(ctx, hipMemcpyAsync(dp, a.in[k] + off, sizeof(T) * m, hipMemcpyHostToDevice, st));
-                d.in[k] = dp;
-            } else {
-                d.in[k] = dscal + k;
-            }
-        }
-        for (int k = 0; k < 11; ++k) {
-            if (a.par[k] && ((a.dense_par >> k) & 1u)) {
-                T* dp = reinterpret_cast<T*>(base + per_arr * (kMethodMaxIn + k));
-                HIPCHK(ctx, hipMemcpyAsync(dp, a.par[k] + off, sizeof(T) * m, hipMemcpyHostToDevice, st));
-                d.par[k] = dp;
-            } else {
-                d.par[k] = dscal + kMethodMaxIn + k;
-            }
-        }
-        for (int k = 0; k < 2; ++k)
-            d.out[k] = a.out[k] ? reinterpret_cast<T*>(base + per_arr * (kMethodMaxIn + 11 + k)) : nullptr;
-        launch(d, st);
-        HIPCHK(ctx, hipGetLastError());
-        for (int k = 0; k < 2; ++k)
-            if (a.out[k]) HIPCHK(ctx, hipMemcpyAsync(a.out[k] + off, d.out[k], sizeof(T) * m, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    }
-    return MOD16_OK;
+    return host_tiled(ctx, p, n, 1, false, launch_tile);     // (one slot: no double buffering)
 }
 
 extern "C" int mod16_method_f64(mod16_ctx* ctx, int method, const double* const* in,

@@ -1,5 +1,5 @@
 // libmod16hip.so -- raw reanalysis drivers (N1): mod16_et_raw_*
-#include "internal.hpp"
+#include "host.hpp"
 #include "../mod16_methods.hpp"
 
 // ----------------------------------------------------- raw drivers (N1)
@@ -99,160 +99,32 @@ static int raw_entry(mod16_ctx* ctx, const uint8_t* cls, const T* const* raw,
         return MOD16_OK;
     }
     if (where != MOD16_HOST) return fail(ctx, MOD16_ERR_ARG, "mod16_et_raw: bad `where`");
-    size_t per_arr_small = 0;
-    if (n <= ctx->small_pixels && small_reserve(ctx, n, sizeof(T), 14 + 1 + 3, &per_arr_small)) {
-        // small calls: no copy commands, the kernel reads and writes one page-locked buffer
-        // (run_host_small; whole vectors, the pad pixels repeat the last one; classes checked here)
-        for (int64_t i = 0; i < n; ++i)
-            if (cls[i] >= MOD16_N_CLASSES)
-                return fail(ctx, MOD16_ERR_CLASS_RANGE, "class raster holds a code >= 13 (numpy would raise IndexError)");
-        const size_t per_arr = per_arr_small;
-        int rc = MOD16_OK;
-        hipStream_t st = ctx->streams[0];
-        char* hb = static_cast<char*>(ctx->small_host);
-        char* db = static_cast<char*>(ctx->small_dev);
-        T* hsc = reinterpret_cast<T*>(hb);
-        const T* dscal = reinterpret_cast<const T*>(db);
-        constexpr int V = VecOf<T>::v;
-        const int64_t npad = (n + V - 1) / V * V;
-        const size_t per_b = per_arr / sizeof(T);       // the buffer's capacity in pixels
-        auto arr = [&](int k) { return (size_t)256 + per_arr * k; };
-        auto put = [&](size_t off, const void* src, size_t elem) {
-            memcpy(hb + off, src, elem * n);
-            for (int64_t i = n; i < npad; ++i) memcpy(hb + off + elem * i, static_cast<const char*>(src) + elem * (n - 1), elem);
-        };
+    // HOST mode: 14 drivers, day_hours, 3 outputs (T each), then the fPAR, LAI and class bytes
+    HostPlan p(sizeof(T));
+    for (int k = 0; k < 14; ++k) p.add(((a.dense_drv >> k) & 1u) ? kIn : kScalar, a.drv[k]);
+    p.add(a.dense_hours ? kIn : kScalar, a.day_hours);
+    for (int k = 0; k < 3; ++k) p.add(kOut, a.out[k]);
+    p.add(kIn, fpar_pct, true);
+    p.add(kIn, lai_x10, true);
+    p.add(kIn, cls, true);
+    p.cls = cls;
+    const T* host_hours = (a.day_hours && !a.dense_hours) ? a.day_hours : nullptr;
+    auto launch_tile = [&](const HostTile& t) {
         RawArgs<T> d = a;
-        d.n = npad;
-        for (int k = 0; k < 14; ++k) {
-            if ((a.dense_drv >> k) & 1u) {
-                put(arr(k), a.drv[k], sizeof(T));
-                d.drv[k] = reinterpret_cast<const T*>(db + arr(k));
-            } else {
-                hsc[k] = a.drv[k][0];
-                d.drv[k] = dscal + k;
-            }
-        }
-        T host_hours = T(0);
-        if (a.day_hours) {
-            if (a.dense_hours) {
-                put(arr(14), a.day_hours, sizeof(T));
-                d.day_hours = reinterpret_cast<const T*>(db + arr(14));
-            } else {
-                host_hours = hsc[14] = a.day_hours[0];
-                d.day_hours = dscal + 14;
-            }
-        }
-        const uint8_t* hbytes[3] = {a.fpar_pct, a.lai_x10, a.cls};
-        const uint8_t** dbytes[3] = {&d.fpar_pct, &d.lai_x10, &d.cls};
-        for (int k = 0; k < 3; ++k) {
-            const size_t off = arr(18) + per_b * k;
-            put(off, hbytes[k], 1);
-            *dbytes[k] = reinterpret_cast<const uint8_t*>(db + off);
-        }
-        for (int k = 0; k < 3; ++k) d.out[k] = a.out[k] ? reinterpret_cast<T*>(db + arr(15 + k)) : nullptr;
-        rc = launch(d, st, (a.day_hours && !a.dense_hours) ? &host_hours : nullptr);
-        if (rc != MOD16_OK) return rc;
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        for (int k = 0; k < 3; ++k)
-            if (a.out[k]) memcpy(a.out[k], hb + arr(15 + k), sizeof(T) * n);
-        return MOD16_OK;
-    }
-    // HOST: tiles of kTilePixels staged through the context's slabs, one host thread and one stream
-    // per slot, as run_host does for the processed drivers (round 5; one slab and one thread before:
-    // the copies from pageable memory, which the runtime stages on the calling thread, are what bounds
-    // this mode, and the light input form -- 58 bytes per pixel in float32 -- is the one worth feeding
-    // at the link's rate)
-    const int64_t tile = std::min<int64_t>(n, kTilePixels);
-    const int64_t ntiles = (n + tile - 1) / tile;
-    const int nslots = (int)std::min<int64_t>(ntiles, ctx->host_threads);
-    if (nslots > 1) ctx->ws_multi = true;       // one stream per slot: the launches leave their events (ws_release)
-    const size_t per_arr = (((size_t)tile * sizeof(T)) + 255) / 256 * 256 + kStagger;
-    const size_t need = per_arr * (14 + 1 + 3) + 3 * ((size_t)tile + 256) + 256;
-    if (ctx->slab_bytes < need) {
-        for (int s = 0; s < kSlots; ++s) {
-            if (ctx->slab[s]) HIPCHK(ctx, hipFree(ctx->slab[s]));
-            ctx->slab[s] = nullptr;
-        }
-        ctx->slab_bytes = need;
-    }
-    for (int s = 0; s < nslots; ++s) {
-        if (!ctx->slab[s]) HIPCHK(ctx, hipMalloc(&ctx->slab[s], ctx->slab_bytes));
-        if (!ctx->streams[s]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[s], hipStreamNonBlocking));
-    }
-    T hs[16];
-    for (int k = 0; k < 14; ++k) hs[k] = ((a.dense_drv >> k) & 1u) ? T(0) : a.drv[k][0];
-    hs[14] = (a.day_hours && !a.dense_hours) ? a.day_hours[0] : T(0);
-    HIPCHK(ctx, hipMemcpy(ctx->scalars, hs, sizeof(T) * 15, hipMemcpyHostToDevice));
-    const T* dscal = static_cast<const T*>(ctx->scalars);
-    const size_t per_b = ((size_t)tile + 255) / 256 * 256;
-    {   // the kernels' shared workspace at its final size before any thread launches
-        const int64_t npiece = (tile / VecOf<T>::v + 63) / 64;
-        int rc = reserve_diag(ctx, npiece / 2 + 2048);
-        if (rc != MOD16_OK) return rc;
-    }
-    auto stage = [&](int slot, int64_t off, int64_t m) -> int {
-        hipStream_t st = ctx->streams[slot];
-        char* base = static_cast<char*>(ctx->slab[slot]);
-        uint8_t* bytes = reinterpret_cast<uint8_t*>(base + per_arr * 18);
-        RawArgs<T> d = a;
-        d.n = m;
-        for (int k = 0; k < 14; ++k) {
-            if ((a.dense_drv >> k) & 1u) {
-                T* dp = reinterpret_cast<T*>(base + per_arr * k);
-                HIPCHK(ctx, hipMemcpyAsync(dp, a.drv[k] + off, sizeof(T) * m, hipMemcpyHostToDevice, st));
-                d.drv[k] = dp;
-            } else {
-                d.drv[k] = dscal + k;
-            }
-        }
-        if (a.day_hours) {
-            if (a.dense_hours) {
-                T* dp = reinterpret_cast<T*>(base + per_arr * 14);
-                HIPCHK(ctx, hipMemcpyAsync(dp, a.day_hours + off, sizeof(T) * m, hipMemcpyHostToDevice, st));
-                d.day_hours = dp;
-            } else {
-                d.day_hours = dscal + 14;
-            }
-        }
-        const uint8_t* hb[3] = {a.fpar_pct, a.lai_x10, a.cls};
-        const uint8_t** db[3] = {&d.fpar_pct, &d.lai_x10, &d.cls};
-        for (int k = 0; k < 3; ++k) {
-            uint8_t* dp = bytes + per_b * k;
-            HIPCHK(ctx, hipMemcpyAsync(dp, hb[k] + off, (size_t)m, hipMemcpyHostToDevice, st));
-            *db[k] = dp;
-        }
-        for (int k = 0; k < 3; ++k) d.out[k] = a.out[k] ? reinterpret_cast<T*>(base + per_arr * (15 + k)) : nullptr;
-        {
-            std::lock_guard<std::mutex> lock(ctx->launch_mu);      // (the launches share the context's workspace)
-            int rc = launch(d, st, (a.day_hours && !a.dense_hours) ? &hs[14] : nullptr);
-            if (rc != MOD16_OK) return rc;
-            HIPCHK(ctx, hipGetLastError());
-        }
-        for (int k = 0; k < 3; ++k)
-            if (a.out[k]) HIPCHK(ctx, hipMemcpyAsync(a.out[k] + off, d.out[k], sizeof(T) * m, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));      // the slab of this slot is free again
-        return MOD16_OK;
+        d.n = t.m;
+        for (int k = 0; k < 14; ++k) d.drv[k] = static_cast<const T*>(t.dev[k]);
+        d.day_hours = static_cast<const T*>(t.dev[14]);
+        for (int k = 0; k < 3; ++k) d.out[k] = static_cast<T*>(t.dev[15 + k]);
+        d.fpar_pct = static_cast<const uint8_t*>(t.dev[18]);
+        d.lai_x10 = static_cast<const uint8_t*>(t.dev[19]);
+        d.cls = static_cast<const uint8_t*>(t.dev[20]);
+        return launch(d, t.st, host_hours);
     };
-    if (nslots == 1) {
-        for (int64_t off = 0; off < n; off += tile) {
-            int rc = stage(0, off, std::min(tile, n - off));
-            if (rc != MOD16_OK) return rc;
-        }
-    } else {
-        int rcs[kSlots] = {};
-        std::vector<std::thread> workers;
-        for (int s = 0; s < nslots; ++s)
-            workers.emplace_back([&, s]() {
-                if (hipSetDevice(ctx->device) != hipSuccess) { rcs[s] = MOD16_ERR_HIP; return; }
-                for (int64_t t = s; t < ntiles && rcs[s] == MOD16_OK; t += nslots)
-                    rcs[s] = stage(s, t * tile, std::min(tile, n - t * tile));
-            });
-        for (auto& w : workers) w.join();
-        for (int s = 0; s < nslots; ++s)
-            if (rcs[s] != MOD16_OK) return rcs[s];
+    if (n <= ctx->small_pixels) {
+        const int rc = host_small(ctx, p, n, true, launch_tile);
+        if (rc != kSmallUnavailable) return rc;
     }
-    return read_status(ctx, ctx->streams[0]);
+    return host_tiled(ctx, p, n, ctx->host_threads, true, launch_tile);
 }
 
 extern "C" int mod16_et_raw_f64(mod16_ctx* ctx, const uint8_t* cls, const double* const* raw,

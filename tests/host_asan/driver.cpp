@@ -47,6 +47,9 @@ template <> struct TypeOps<double> {
     static int graph(mod16_ctx* c, const mod16_layout* l, const uint8_t* cls, const double* const* d, int64_t n, double* a, double* b, unsigned f, double* dd, mod16_graph** g) { return mod16_graph_et_tiled_f64(c, l, cls, d, n, a, b, f, dd, g); }
     static int synth(mod16_ctx* c, const mod16_layout* l, int64_t n, uint8_t* cls, double* const* d) { return mod16_synth_tiled_f64(c, l, 16, 0, 0, n, cls, d, nullptr); }
     static int diag(mod16_ctx* c, const uint8_t* cls, const double* const* d, const int64_t* ds, int64_t n, double* a, double* b, unsigned f, double* dd) { return mod16_et_diag_f64(c, cls, d, ds, n, a, b, f, dd, nullptr); }
+    static int method(mod16_ctx* c, int m, const double* const* in, const int64_t* is, const double* const* p, const int64_t* ps, int64_t n, double* const* o) { return mod16_method_f64(c, m, in, is, p, ps, n, o, 1.26, 1e-7, MOD16_HOST, nullptr); }
+    static int stat(mod16_ctx* c, const double* const* d, const int64_t* ds, const double* const* p, const int64_t* ps, const double* const* rc, const int64_t* rs,
+                    int64_t n, double* a, double* b) { return mod16_et_static_f64(c, d, ds, p, ps, rc, rs, n, a, b, 1e-7, MOD16_HOST, nullptr); }
 };
 template <> struct TypeOps<float> {
     static constexpr int V = 4;
@@ -57,6 +60,9 @@ template <> struct TypeOps<float> {
     static int graph(mod16_ctx* c, const mod16_layout* l, const uint8_t* cls, const float* const* d, int64_t n, float* a, float* b, unsigned f, double* dd, mod16_graph** g) { return mod16_graph_et_tiled_f32(c, l, cls, d, n, a, b, f, dd, g); }
     static int synth(mod16_ctx* c, const mod16_layout* l, int64_t n, uint8_t* cls, float* const* d) { return mod16_synth_tiled_f32(c, l, 16, 0, 0, n, cls, d, nullptr); }
     static int diag(mod16_ctx* c, const uint8_t* cls, const float* const* d, const int64_t* ds, int64_t n, float* a, float* b, unsigned f, double* dd) { return mod16_et_diag_f32(c, cls, d, ds, n, a, b, f, dd, nullptr); }
+    static int method(mod16_ctx* c, int m, const float* const* in, const int64_t* is, const float* const* p, const int64_t* ps, int64_t n, float* const* o) { return mod16_method_f32(c, m, in, is, p, ps, n, o, 1.26f, 1e-7f, MOD16_HOST, nullptr); }
+    static int stat(mod16_ctx* c, const float* const* d, const int64_t* ds, const float* const* p, const int64_t* ps, const float* const* rc, const int64_t* rs,
+                    int64_t n, float* a, float* b) { return mod16_et_static_f32(c, d, ds, p, ps, rc, rs, n, a, b, 1e-7f, MOD16_HOST, nullptr); }
 };
 
 // A tiled raster of one form: [tile][field][tile pixels] as mod16_amd/raster.py lays it out
@@ -271,6 +277,39 @@ static void host_cases(mod16_ctx* ctx, const char* what) {
             OK(mod16_et_raw_f32(ctx, cls.data(), R, rs, fpar.data(), lai.data(), nullptr, 0, n,
                                 reinterpret_cast<float*>(day.data()), reinterpret_cast<float*>(night.data()), nullptr, MOD16_MATH_FAST, MOD16_HOST, nullptr));
         }
+    }
+    // the class-surface methods: the small path, and tile by tile on one slot; inputs dense and scalar,
+    // optional inputs and parameters absent
+    for (int64_t n : {(int64_t)5, (int64_t)tile + 12345}) {
+        std::vector<std::vector<T>> in(6, std::vector<T>(n, T(280)));
+        std::vector<T> par(n, T(2)), sat(n), unsat(n);
+        T pa = T(90000);
+        const T* ip[13] = {&pa, in[1].data(), in[2].data(), in[3].data(), in[4].data(), nullptr, nullptr, in[5].data()};
+        int64_t is[13] = {0, 1, 1, 1, 1, 0, 0, 1};
+        const T* pp[11] = {};
+        int64_t ps[11] = {};
+        pp[3] = par.data(); ps[3] = 1;
+        pp[4] = &pa;
+        T* outs[2] = {sat.data(), unsat.data()};
+        OK(TypeOps<T>::method(ctx, MOD16_M_POT_SOIL_EVAP, ip, is, pp, ps, n, outs));
+        const T* rh[13] = {in[1].data(), &pa};
+        int64_t rhs[13] = {1, 0};
+        outs[1] = nullptr;
+        OK(TypeOps<T>::method(ctx, MOD16_M_RHUMIDITY, rh, rhs, nullptr, nullptr, n, outs));
+    }
+    {   // the calibration path's small calls: with and without r_corr_list, scalars among every kind
+        const int64_t n = 365;
+        std::vector<std::vector<T>> drv(14, std::vector<T>(n, T(280))), par(11, std::vector<T>(n, T(2)));
+        std::vector<T> rc(n, T(1)), day(n), night(n);
+        const T *dp[14], *pp[11];
+        int64_t ds[14], ps[11];
+        T one = T(300);
+        for (int k = 0; k < 14; ++k) { dp[k] = k % 4 ? drv[k].data() : &one; ds[k] = k % 4 ? 1 : 0; }
+        for (int k = 0; k < 11; ++k) { pp[k] = k % 3 ? par[k].data() : &one; ps[k] = k % 3 ? 1 : 0; }
+        const T* rp[2] = {rc.data(), &one};
+        int64_t rs[2] = {1, 0};
+        OK(TypeOps<T>::stat(ctx, dp, ds, pp, ps, rp, rs, n, day.data(), night.data()));
+        OK(TypeOps<T>::stat(ctx, dp, ds, pp, ps, nullptr, nullptr, n, day.data(), night.data()));
     }
     double x[8];
     EXPECT(mod16_fold_diag_host(nullptr, 1, x) == MOD16_ERR_ARG);

@@ -15,7 +15,8 @@
 // and skipped.
 //
 // Compiled as HIP (host only) so that it sees the kernels' own argument structures
-// (StreamArgs, EtArgs, SynthArgs: mod16_amd/csrc/*.hpp) instead of copies of them.
+// (StreamArgs, EtArgs, SynthArgs, MethodArgs, RawArgs, StaticArgs: mod16_amd/csrc/*.hpp) instead of
+// copies of them.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 
@@ -36,6 +37,7 @@
 #define mod16 mod16_shadow
 #include "../../mod16_amd/csrc/mod16_kernels.hpp"
 #include "../../mod16_amd/csrc/mod16_stream.hpp"
+#include "../../mod16_amd/csrc/mod16_methods.hpp"
 
 using namespace mod16;
 
@@ -227,6 +229,56 @@ static void shadow_synth(const SynthArgs<T>& a, const char* name) {
     }
 }
 
+// a dense array is read or written at [p, p + n), a broadcast scalar at p[0]
+template <typename T>
+static void need_arr(const T* p, bool dense, int64_t n, const char* what, const char* name) {
+    need(p, sizeof(T) * (dense ? (size_t)n : 1), sizeof(T), what, name);
+}
+
+// method_kernel<T>: the present inputs, all 11 parameters, the outputs given
+template <typename T>
+static void shadow_method(const MethodArgs<T>& a, const char* name) {
+    if (a.n <= 0) die("%s: n = %lld", name, (long long)a.n);
+    for (int k = 0; k < kMethodMaxIn; ++k)
+        if ((a.present_in >> k) & 1u) need_arr(a.in[k], (a.dense_in >> k) & 1u, a.n, "input", name);
+    for (int k = 0; k < 11; ++k) need_arr(a.par[k], (a.dense_par >> k) & 1u, a.n, "parameter", name);
+    for (int k = 0; k < 2; ++k)
+        if (a.out[k]) need_arr(a.out[k], true, a.n, "output", name);
+}
+
+// et_raw_kernel<T, FAST>: drivers, the three byte rasters, day_hours (with the 8-day total), outputs, tables
+template <typename T>
+static void shadow_raw(const RawArgs<T>& a, bool fast, const char* name) {
+    if (a.n <= 0) die("%s: n = %lld", name, (long long)a.n);
+    for (int k = 0; k < 14; ++k) need_arr(a.drv[k], (a.dense_drv >> k) & 1u, a.n, "driver", name);
+    need(a.fpar_pct, (size_t)a.n, 1, "fPAR raster", name);
+    need(a.lai_x10, (size_t)a.n, 1, "LAI raster", name);
+    need(a.cls, (size_t)a.n, 1, "class raster", name);
+    if (a.out[2]) need_arr(a.day_hours, a.dense_hours & 1u, a.n, "day_hours", name);
+    for (int k = 0; k < 3; ++k)
+        if (a.out[k]) need_arr(a.out[k], true, a.n, "output", name);
+    if (fast) {
+        need(a.lut64, sizeof(double) * MOD16_LUT_ROWS * kLutCols, 8, "BPLUT", name);
+        need(a.tab, sizeof(double) * FastMath<double>::kTabDoubles, 16, "exp / log tables", name);
+    } else {
+        need(a.lut, sizeof(T) * MOD16_LUT_ROWS * kLutCols, sizeof(T), "BPLUT", name);
+    }
+    need(a.status, 4, 4, "status word", name);
+}
+
+// static_flag_kernel<T> (pixels = false) / static_kernel<T>: drivers, parameters, r_corr if given, the flag word
+template <typename T>
+static void shadow_static(const StaticArgs<T>& a, bool pixels, const char* name) {
+    if (a.n <= 0) die("%s: n = %lld", name, (long long)a.n);
+    for (int k = 0; k < 14; ++k) need_arr(a.drv[k], (a.dense_drv >> k) & 1u, a.n, "driver", name);
+    for (int k = 0; k < 11; ++k) need_arr(a.par[k], (a.dense_par >> k) & 1u, a.n, "parameter", name);
+    if (a.rc[0])
+        for (int k = 0; k < (pixels ? 2 : 1); ++k) need_arr(a.rc[k], (a.dense_rc >> k) & 1u, a.n, "r_corr", name);
+    need(a.flag, 4, 4, "flag word", name);
+    if (pixels)
+        for (int k = 0; k < 2; ++k) need_arr(a.out[k], true, a.n, "output", name);
+}
+
 static bool has(const std::string& s, const char* sub) { return s.find(sub) != std::string::npos; }
 
 static void run_shadow(const std::string& name, dim3 grid, dim3 block, void** args) {
@@ -264,6 +316,20 @@ static void run_shadow(const std::string& name, dim3 grid, dim3 block, void** ar
         const size_t at = name.find("9et_kernelI") + 11;
         if (name[at] == 'd') shadow_et(*static_cast<const EtArgs<double>*>(args[0]), grid, block, n);
         else shadow_et(*static_cast<const EtArgs<float>*>(args[0]), grid, block, n);
+    } else if (has(name, "13method_kernelI")) {
+        if (name[name.find("13method_kernelI") + 16] == 'd') shadow_method(*static_cast<const MethodArgs<double>*>(args[0]), n);
+        else shadow_method(*static_cast<const MethodArgs<float>*>(args[0]), n);
+    } else if (has(name, "13et_raw_kernelI")) {
+        // ...et_raw_kernelI{d|f}Lb<FAST>EE...
+        const size_t at = name.find("13et_raw_kernelI") + 16;
+        const bool fast = name[at + 3] == '1';
+        if (name[at] == 'd') shadow_raw(*static_cast<const RawArgs<double>*>(args[0]), fast, n);
+        else shadow_raw(*static_cast<const RawArgs<float>*>(args[0]), fast, n);
+    } else if (has(name, "18static_flag_kernelI") || has(name, "13static_kernelI")) {
+        const bool pixels = has(name, "13static_kernelI");
+        const size_t at = name.find(pixels ? "13static_kernelI" : "18static_flag_kernelI") + (pixels ? 16 : 21);
+        if (name[at] == 'd') shadow_static(*static_cast<const StaticArgs<double>*>(args[0]), pixels, n);
+        else shadow_static(*static_cast<const StaticArgs<float>*>(args[0]), pixels, n);
     } else if (has(name, "12synth_kernelI")) {
         const size_t at = name.find("12synth_kernelI") + 15;
         if (name[at] == 'd') shadow_synth(*static_cast<const SynthArgs<double>*>(args[0]), n);

@@ -643,7 +643,7 @@ def test_special_value_pairs_fast_kernel(m16, golden):
 @pytest.mark.parametrize('n', [1, 2, 3, 5, 365, 1025, 65535, 65536, 65537])
 def test_small_calls_give_the_bits_of_the_staged_path(m16, golden, n):
     """HOST mode, calls of up to 65536 pixels: no copy commands -- the kernel reads its inputs
-    from a page-locked buffer and writes its outputs there (run_host_small, mod16_capi.hip).
+    from a page-locked buffer and writes its outputs there (host_small, capi/host.hpp).
     Same kernels, same values: every output of every form equals the staged path's
     (MOD16_SMALL_PIXELS=0) bit for bit, float64 and float32, class raster and parameter
     arrays, ragged sizes (the buffer pads to whole vectors), one pixel above the limit."""

@@ -244,7 +244,7 @@ def test_pipeline_at_piece_run_and_chip_boundaries(env, dtype):
 @pytest.mark.parametrize('n', [1, 7, 365, 4099, 65536])
 def test_small_raw_calls_give_the_bits_of_the_staged_path(env, n):
     """evapotranspiration_raw on numpy arrays of up to 65536 pixels: the kernel reads and writes one
-    page-locked buffer (the small path of mod16_et_raw_*, mod16_capi.hip) -- the staged path's bits
+    page-locked buffer (the small path of mod16_et_raw_*, host_small in capi/host.hpp) -- the staged path's bits
     (MOD16_SMALL_PIXELS=0), every hours-of-daylight form, float64 and float32 (FAST and MIXED);
     a class code numpy would refuse is an IndexError from both."""
     torch, RasterEngine, table = env

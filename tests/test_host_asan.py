@@ -23,6 +23,11 @@ def test_host_half_of_the_library_is_clean_under_asan_and_ubsan(tmp_path):
     # the shadows that carry the launch geometry ran, on both data types and on the big rasters
     assert 'et_stream_kernel' in out and 'et_stream_redo_kernel' in out and 'et_kernel' in out
     assert 'graph lifetime: done' in out
+    # the kernels of the other HOST-mode families ran under their shadows, not on launch shapes alone
+    lines = out.splitlines()
+    for kernel in ('13method_kernel', '13et_raw_kernel', '18static_flag_kernel', '13static_kernel'):
+        assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
+        assert not any(kernel in l for l in lines if 'launch shape only' in l), kernel
     for what in ('tiled rasters, float64', 'tiled rasters, float32', 'plain device arrays, float64',
                  'HOST mode, float64', 'HOST mode, float32'):
         assert what in out, what

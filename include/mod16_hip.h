@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 7
+#define MOD16_ABI_VERSION 8
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -507,8 +507,8 @@ MOD16_API int mod16_et_static_batch_f32(mod16_ctx* ctx, const float* const* driv
  *   mod16_static_batch_rows       the [ndraw][n] rows (HOST; day / night / total, any may be
  *       NULL): the unbound call's kernels on the resident drivers -- bit-identical rows.
  *   mod16_static_batch_info       n, max_draws and the number of pixels outside the FAST domain.
- *   mod16_static_batch_time       mean milliseconds of the GPU part of the last-shaped
- *       objective evaluation (graph replays bracketed by HIP events).
+ *   mod16_static_batch_time       mean milliseconds of the GPU part of the last objective
+ *       call's evaluation, plain or fold (graph replays bracketed by HIP events).
  * Calls on one object are serialised by its ctx's mutex. Synchronous.
  *
  * where = MOD16_DEVICE: the object works on a private stream and the interface takes none, so the
@@ -539,6 +539,29 @@ MOD16_API int mod16_static_batch_time(mod16_batch* problem, int launches, float*
 MOD16_API int mod16_static_batch_destroy(mod16_batch* problem);
 
 /*
+ * k-fold cross-validation on a resident problem (ABI 8; mod16_amd/calibration.py). Every pixel
+ * (site-day) carries a fold label in 0 .. nfolds - 1, 2 <= nfolds <= 255, each value used at least
+ * once; every draw of a fold call carries a code f | (MOD16_FOLD_HELDOUT or 0):
+ *   TRAIN (bit clear)   the draw sees the pixels whose label != f,
+ *   HELDOUT             the draw sees the pixels whose label == f.
+ * A pixel the draw does not see adds nothing to its (sse, count). The reference's whole-array
+ * branch any(g_surf > 0) ranges over the seen pixels whose observation is a number (its k-fold path
+ * drops the rows with a NaN observation, calibration.py:896-901): a fold draw returns what
+ * mod16_et_static_batch_* (MOD16_MATH_FAST) returns on the compacted seen rows, up to summation
+ * order. Plain calls on the problem are unchanged, bit for bit, labels or not.
+ *   mod16_static_batch_set_folds        labels [n] (HOST). Once per problem, before any sampler
+ *       exists on it; the problem must be float64, MOD16_MATH_FAST, bound with observations.
+ *   mod16_static_batch_objective_folds  as mod16_static_batch_objective, code [ndraw] (HOST): folds
+ *       and modes may differ between the draws of one call. Plain and fold calls keep a captured
+ *       graph each.
+ * Anything else is MOD16_ERR_ARG with a message (mod16_last_error).
+ */
+#define MOD16_FOLD_HELDOUT 0x100
+MOD16_API int mod16_static_batch_set_folds(mod16_batch* problem, const uint8_t* labels, int nfolds);
+MOD16_API int mod16_static_batch_objective_folds(mod16_batch* problem, const void* params, int64_t ndraw,
+                        const int32_t* code, double* sse, double* count);
+
+/*
  * DE-MCMC-Z calibration sampler (ABI 7; mod16_amd/calibration.py): independent chains of PyMC's
  * DEMetropolisZ -- the project's restatement of it, stated in full at the top of
  * mod16_amd/csrc/mod16_mcmc.hpp -- over the free parameters of a RESIDENT problem
@@ -560,6 +583,12 @@ MOD16_API int mod16_static_batch_destroy(mod16_batch* problem);
  *       accepted [count][chains] (0 / 1); and the current per-chain scaling, lamb [chains] and the
  *       number of steps taken so far. t0 + count <= steps taken.
  *   mod16_mcmc_destroy  frees the sampler; destroy every sampler of a problem before the problem.
+ *   mod16_mcmc_create_groups  (ABI 8) cross-validation in one sampler: spec->chains chains for each
+ *       of the `ngroups` distinct folds fold[g] of a problem with labels (mod16_static_batch_set_folds),
+ *       chains x ngroups <= max_draws. Chain j of group g is chain g * chains + j of x0, of the trace
+ *       and of every per-chain output; it evaluates its objective with the TRAIN code fold[g], and its
+ *       random stream is the plain sampler's with seed (seed + fold[g]) mod 2^64 and chain index j
+ *       (mod16_mcmc.hpp) -- so its draws do not depend on which other groups run alongside.
  * Checks (MOD16_ERR_ARG): 1 <= nfree <= 11 distinct columns; Uniform / Triangular lower < upper,
  * lower <= c <= upper, LogNormal sigma > 0, all finite; tune_target 0 (none), 1 (scaling), 2 (lamb);
  * tune_interval >= 1; tune_steps >= 0; 0 <= tune_drop_fraction < 1; objective 0 (rmsd:
@@ -588,6 +617,8 @@ typedef struct mod16_mcmc_spec {
 typedef struct mod16_mcmc mod16_mcmc;
 MOD16_API int mod16_mcmc_create(mod16_batch* problem, const mod16_mcmc_spec* spec, const double* x0,
                                 mod16_mcmc** out);
+MOD16_API int mod16_mcmc_create_groups(mod16_batch* problem, const mod16_mcmc_spec* spec, int ngroups,
+                                       const int32_t* fold, const double* x0, mod16_mcmc** out);
 MOD16_API int mod16_mcmc_run(mod16_mcmc* sampler, int64_t steps, float* ms);
 MOD16_API int mod16_mcmc_read(mod16_mcmc* sampler, int64_t t0, int64_t count, double* x, double* y,
                               double* loglik, double* logpost, uint8_t* accepted, double* scaling,

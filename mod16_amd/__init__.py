@@ -863,7 +863,7 @@ class MOD16(object):
     def _et_bind(lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
                  temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
                  pressure, fpar, lai, observed=None, weights=None, max_draws=4096,
-                 math=_lib.MATH_FAST, device=0):
+                 math=_lib.MATH_FAST, device=0, folds=None):
         '''
         (Extension.) The calibration problem made RESIDENT on the GPU: what the
         reference's sampler (calibration.py:907-909) and Sobol analysis
@@ -878,12 +878,17 @@ class MOD16(object):
         ``math``: ``MATH_FAST`` (default here: the strength-reduced float64
         arithmetic, within 1e-9 of the reference order; pixels outside its domain
         are computed in the reference's order, as in the forward run) or
-        ``MATH_EXACT``.
+        ``MATH_EXACT``. ``folds`` (k-fold cross-validation; float64 ``MATH_FAST``
+        problems with ``observed``): an int K -- the reference's random partition,
+        ``mod16_amd.calibration.kfold_labels(n, K)`` -- or the fold label
+        (0 .. K-1) of every site-day, of the problem's shape; then
+        ``problem.objective(params, folds=..., heldout=...)`` and
+        ``DEMetropolisZ(problem, ..., folds=...)``.
         '''
         drivers = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
                    sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
                    vpd_night, pressure, fpar, lai]
-        return BoundCalibration(drivers, observed, weights, max_draws, math, device)
+        return BoundCalibration(drivers, observed, weights, max_draws, math, device, folds)
 
     @staticmethod
     def air_density(temp_k, pressure, rhumidity):
@@ -989,7 +994,7 @@ class BoundCalibration(object):
     '''A calibration problem resident on the GPU (``MOD16._et_bind``;
     ``mod16_static_batch_bind_*`` of the C ABI).'''
 
-    def __init__(self, drivers, observed, weights, max_draws, math, device):
+    def __init__(self, drivers, observed, weights, max_draws, math, device, folds=None):
         import ctypes as C
         if weights is not None and observed is None:
             raise ValueError('weights need observed')
@@ -1001,6 +1006,10 @@ class BoundCalibration(object):
             raise ValueError('a calibration problem needs at least one pixel')
         self.max_draws = int(max_draws)
         self.math = int(math)
+        #: fold label of every site-day (flat, uint8) and the number of folds; None / 0: no folds
+        self.labels, self.nfolds = None, 0
+        if folds is not None:
+            self.labels, self.nfolds = self._fold_labels(folds, observed)
         self._ctx = _lib.context(device)
         keep, dptr, dstr = _marshal(drivers, self.shape, self.dtype)
         full = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, self.dtype), self.shape))
@@ -1018,6 +1027,49 @@ class BoundCalibration(object):
         self._ctx.check(self._ctx.lib.mod16_static_batch_info(self._handle, None, None, C.byref(n_out)))
         #: pixels outside the domain of the FAST arithmetic (computed in the reference's order)
         self.n_outside_domain = n_out.value
+        if self.labels is not None:
+            self._ctx.check(self._ctx.lib.mod16_static_batch_set_folds(
+                self._handle, self.labels.ctypes.data, self.nfolds))
+
+    def _fold_labels(self, folds, observed):
+        '''(labels (n,) uint8, K) of ``folds``: an int K (``calibration.kfold_labels(n, K)``) or
+        labels of the problem's shape; checked on the host.'''
+        if self.dtype != np.float64 or (self.math & 3) != _lib.MATH_FAST or observed is None:
+            raise ValueError('folds need a float64 problem bound with math=MATH_FAST and observed')
+        if np.ndim(folds) == 0:
+            from .calibration import kfold_labels
+            k = int(folds)
+            return kfold_labels(self.n, k), k
+        lab = np.asarray(folds)
+        if lab.shape != self.shape and lab.shape != (self.n,):
+            raise ValueError('fold labels of shape %s, the problem is %s' % (lab.shape, self.shape))
+        if not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError('fold labels must be integers (got %s)' % lab.dtype)
+        lab = lab.ravel()
+        if lab.min() < 0 or lab.max() > 254:
+            raise ValueError('fold labels must lie in 0 .. K-1 with K <= 255')
+        k = int(lab.max()) + 1
+        if k < 2:
+            raise ValueError('fold labels need at least two folds')
+        missing = np.setdiff1d(np.arange(k), lab)
+        if missing.size:
+            raise ValueError('fold labels: fold(s) %s have no site-day' % missing.tolist())
+        return np.ascontiguousarray(lab, np.uint8), k
+
+    def fold_codes(self, folds, ndraw, heldout=False):
+        '''The (ndraw,) int32 fold codes of ``folds`` (an int or (ndraw,) ints): the fold, or
+        fold | ``_lib.FOLD_HELDOUT`` with ``heldout``.'''
+        if not self.nfolds:
+            raise ValueError('the problem was bound without folds')
+        f = np.asarray(folds)
+        if f.ndim == 0:
+            f = np.full(ndraw, f)
+        if f.shape != (ndraw,) or not np.issubdtype(f.dtype, np.integer):
+            raise ValueError('folds must be an int or (%d,) ints' % ndraw)
+        if ndraw and (f.min() < 0 or f.max() >= self.nfolds):
+            raise ValueError('folds outside 0 .. %d' % (self.nfolds - 1))
+        code = f.astype(np.int32)
+        return code | np.int32(_lib.FOLD_HELDOUT) if heldout else code
 
     def _params(self, params):
         par = np.ascontiguousarray(params, self.dtype)
@@ -1028,18 +1080,28 @@ class BoundCalibration(object):
                              % (par.shape[0], self.max_draws))
         return par
 
-    def objective(self, params):
+    def objective(self, params, folds=None, heldout=False):
         '''``(sse, count)``: two float64 arrays (D,) with ``sse[d] = sum((weights *
         (_et_d - observed))**2)`` over the non-NaN pairs and their number, as
         ``MOD16._et_batch(params, *drivers, observed=..., weights=...)``; e.g.
-        ``rmsd = np.sqrt(sse / count)``.'''
+        ``rmsd = np.sqrt(sse / count)``. ``folds`` (a problem bound with folds):
+        an int or (D,) ints; draw d then sees the site-days whose label is not
+        ``folds[d]`` (training), or with ``heldout`` those whose label is: what
+        ``_et_batch`` returns on those rows without their NaN observations.'''
         if not self.has_observed:
             raise ValueError('the problem was bound without observed')
+        if folds is None and heldout:
+            raise ValueError('heldout needs folds')
         par = self._params(params)
+        code = None if folds is None else self.fold_codes(folds, par.shape[0], heldout)
         sse, count = np.zeros(par.shape[0]), np.zeros(par.shape[0])
-        if par.shape[0]:
+        if par.shape[0] and code is None:
             self._ctx.check(self._ctx.lib.mod16_static_batch_objective(
                 self._handle, par.ctypes.data, par.shape[0], sse.ctypes.data, count.ctypes.data))
+        elif par.shape[0]:
+            self._ctx.check(self._ctx.lib.mod16_static_batch_objective_folds(
+                self._handle, par.ctypes.data, par.shape[0], code.ctypes.data, sse.ctypes.data,
+                count.ctypes.data))
         return sse, count
 
     def rows(self, params, separate=False):

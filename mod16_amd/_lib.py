@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -69,6 +69,7 @@ _LAYP = C.POINTER(Layout)
 
 
 PRIOR_UNIFORM, PRIOR_LOGNORMAL, PRIOR_TRIANGULAR = 0, 1, 2     # enum mod16_prior
+FOLD_HELDOUT = 0x100      # MOD16_FOLD_HELDOUT: or it into a fold code (include/mod16_hip.h)
 
 
 class McmcSpec(C.Structure):
@@ -168,6 +169,9 @@ PROTOTYPES = {
     'mod16_static_batch_info': (C.c_int, [C.c_void_p, _I64P, _I64P, _I64P]),
     'mod16_static_batch_time': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     'mod16_static_batch_destroy': (C.c_int, [C.c_void_p]),
+    'mod16_static_batch_set_folds': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    'mod16_static_batch_objective_folds': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
     'mod16_check_status': (C.c_int, [C.c_void_p, C.c_void_p]),
     'mod16_reduce_diag_f64': (C.c_int, [
         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
@@ -231,6 +235,8 @@ PROTOTYPES = {
         C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_uint64,
         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'mod16_mcmc_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    'mod16_mcmc_create_groups': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_void_p)]),
     'mod16_mcmc_run': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]),
     'mod16_mcmc_read': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _I64P]),

@@ -18,7 +18,21 @@ arithmetic is stated in full at the top of ``mod16_amd/csrc/mod16_mcmc.hpp``):
   as one captured graph; any number of chains (up to the problem's ``max_draws``) run in one batch;
 - ``Trace``: the samples (x-values) of the free parameters, log-likelihood, log-posterior and
   acceptance per step, ``posterior(burn, thin)``, ``rhat()`` (classic split R-hat, BDA3) and
-  ``to_npz``.
+  ``to_npz``;
+- k-fold cross-validation, the reference's ``CalibrationAPI.tune(pft, k_folds=K)``
+  (calibration.py:851-958): ``kfold_labels(n, K)`` (its random partition of the tower-days),
+  ``MOD16._et_bind(..., folds=K or labels)``, and ``DEMetropolisZ(problem, ..., folds=True)``: the
+  chains of every fold in ONE sampler -- each fold's chains train on the site-days outside it -- with
+  a ``KFoldTrace`` (``trace.fold(f)`` a plain ``Trace``; R-hat per fold) and ``sampler.heldout(trace)``
+  (the held-out RMSD of every kept draw and of the posterior mean).
+
+  The reference's own k-fold loop does not do what its docstring says, and this port does what the
+  docstring says. (1) The restore-and-mask block (``tower_obs[idx] = np.nan`` and the driver filter,
+  :889-901) is indented inside ``if k_folds > 1 and fold == 1:``, so folds 2..K never mask their own
+  test set: they refit fold 1's training subset under new backend names. Here fold f trains on
+  everything except its own test slice. (2) ``fold_idx[-1][-1] = indices.max()`` ends the last slice
+  at ``n - 1``, exclusive, so the last shuffled row is never held out; here the last slice runs to
+  the end. Do not "fix" either back toward the reference.
 
 The sampler is the project's own restatement of PyMC's ``DEMetropolisZ`` (its ``astep``, ``tune``
 table and ``stop_tuning`` history drop), and the likelihoods -- ``'rmsd'``: ``-sqrt(sse / count)``,
@@ -34,9 +48,9 @@ initial point -- unless ``initial`` is given. The caller states the fixed parame
 (the reference fixes ``tmin_close``, ``tmin_open`` and ``vpd_open`` from the BPLUT row plus
 ``config['optimization']['fixed']``).
 
-Not provided: HDF5 loading (h5py is absent; ``tools/h5_to_store.py`` covers the field map), k-fold
-cross-validation, the annual-precipitation constraint (``constrain_by_map``), plots, netCDF / arviz
-backends, population DE-MCMC (proposals drawn from other chains), several GPUs, float32 problems.
+Not provided: HDF5 loading (h5py is absent; ``tools/h5_to_store.py`` covers the field map), the
+annual-precipitation constraint (``constrain_by_map``), plots, netCDF / arviz backends, population
+DE-MCMC (proposals drawn from other chains), several GPUs, float32 problems.
 There is no CPU fallback: without an MI355X the sampler raises ``Mod16Error``.
 '''
 import ctypes as C
@@ -186,6 +200,31 @@ def index(z, m):
     return (z * int(m)) >> 64
 
 
+def group_stream(seed, fold, j, t, k):
+    '''The random word of chain j of the group of fold ``fold`` (``DEMetropolisZ(..., folds=...)``):
+    the plain stream with seed (seed + fold) mod 2^64 and chain index j.'''
+    return stream((int(seed) + int(fold)) & _M64, j, t, k)
+
+
+def kfold_labels(n, k, seed=0):
+    '''The fold label (0 .. k-1, uint8, (n,)) of each of ``n`` site-days: the reference's partition
+    (calibration.py:859-869) -- a permutation of range(n) (here
+    ``np.random.default_rng(seed).permutation(n)``; the reference's is unseeded) cut into k
+    consecutive slices of n // k, the last slice taking the remainder through the final index (the
+    reference's ends one short, see the module docstring); a row's label is its slice.'''
+    n, k = int(n), int(k)
+    if not 2 <= k <= 255:
+        raise ValueError('k must lie in 2 .. 255 (got %d)' % k)
+    if n < k:
+        raise ValueError('k = %d folds need at least k site-days (got n = %d)' % (k, n))
+    perm = np.random.default_rng(seed).permutation(n)
+    size = n // k
+    labels = np.empty(n, np.uint8)
+    for f in range(k):
+        labels[perm[f * size:(f + 1) * size if f < k - 1 else n]] = f
+    return labels
+
+
 class Trace(object):
     '''The draws of a ``DEMetropolisZ.sample`` call: ``samples[name]`` (chains, draws) x-values of
     the free parameters; ``log_likelihood``, ``log_posterior`` (chains, draws) float64; ``accepted``
@@ -234,12 +273,56 @@ class Trace(object):
             out[name] = float(np.sqrt(var_plus / W)) if W > 0 else float('nan')
         return out
 
-    def to_npz(self, path):
+    def to_npz(self, path, **extra):
         '''All of the trace in one ``.npz`` (samples under their parameter names).'''
         np.savez(path, names=np.array(self.names), log_likelihood=self.log_likelihood,
                  log_posterior=self.log_posterior, accepted=self.accepted, scaling=self.scaling,
                  lamb=self.lamb, acceptance_rate=self.acceptance_rate,
-                 **{'sample_' + k: v for k, v in self.samples.items()})
+                 **dict({'sample_' + k: v for k, v in self.samples.items()}, **extra))
+
+    def _take(self, chains):
+        return Trace(self.names, {k: v[chains] for k, v in self.samples.items()},
+                     self.log_likelihood[chains], self.log_posterior[chains], self.accepted[chains],
+                     self.scaling[chains], self.lamb[chains])
+
+
+def test_indices(labels, k):
+    '''The reference-shaped ``test_indices`` (k, max fold size) int64 of fold labels: row f the
+    site-days of fold f, ascending, padded with -1 (the reference pads with NaN in a uint32 array).'''
+    rows = [np.flatnonzero(labels == f) for f in range(k)]
+    out = np.full((k, max(r.size for r in rows)), -1, np.int64)
+    for f, r in enumerate(rows):
+        out[f, :r.size] = r
+    return out
+
+
+class KFoldTrace(Trace):
+    '''The trace of a cross-validating sampler (``DEMetropolisZ(..., folds=...)``): a ``Trace`` over
+    every chain of every fold, and ``chain_fold`` (chains,), the fold each chain trains for.
+    ``fold(f)`` is the plain ``Trace`` of fold f's chains; ``rhat()`` is ``{f: {name: R-hat}}``,
+    per fold (chains of different folds sample different posteriors).'''
+
+    def __init__(self, names, samples, log_likelihood, log_posterior, accepted, scaling, lamb,
+                 chain_fold, labels, nfolds):
+        super().__init__(names, samples, log_likelihood, log_posterior, accepted, scaling, lamb)
+        self.chain_fold = np.asarray(chain_fold)
+        self.folds = sorted(set(int(f) for f in self.chain_fold))
+        self.labels = labels
+        self.nfolds = nfolds
+
+    def fold(self, f):
+        if int(f) not in self.folds:
+            raise ValueError('fold %r is not sampled here (folds %s)' % (f, self.folds))
+        return self._take(np.flatnonzero(self.chain_fold == int(f)))
+
+    def rhat(self, burn=0, thin=1):
+        return {f: self.fold(f).rhat(burn, thin) for f in self.folds}
+
+    def to_npz(self, path):
+        '''As ``Trace.to_npz``, plus ``chain_fold``, the fold ``labels`` of the site-days and the
+        reference-shaped ``test_indices`` (``test_indices()``).'''
+        super().to_npz(path, chain_fold=self.chain_fold, labels=self.labels,
+                       test_indices=test_indices(self.labels, self.nfolds))
 
 
 def _row(params):
@@ -277,12 +360,19 @@ class DEMetropolisZ(object):
     error (the reference silently puts in 250). ``tune_target``: ``'scaling'``, ``'lambda'``
     (``'lamb'``) or ``None``. ``objective``: ``'rmsd'`` or ``'gaussian'`` (any case). ``initial``:
     optional (chains, d) x-values of the free parameters. ``segment``: steps per captured graph.
+    ``folds`` (k-fold cross-validation, a problem bound with ``folds``): ``True`` (every fold) or a
+    list of distinct folds; then ``chains`` chains run for each listed fold in the same graphs
+    (``chains x folds <= max_draws``), each training on the site-days outside its fold. Chain j of
+    the group of fold f (global chain g chains + j) is, draw for draw, the plain sampler with seed
+    ``seed + f`` on the problem with fold f's observations set to NaN, whenever some training row
+    has g_surf > 0 (``mod16_mcmc.hpp``); ``initial`` is then (chains, d), the same for every fold,
+    or (folds, chains, d). ``sample`` returns a ``KFoldTrace``; ``heldout(trace)`` scores it.
     Everything is checked on the host before any device call (``ValueError``).
     '''
 
     def __init__(self, problem, params, prior, fixed=None, chains=3, tune=1000, tune_target='scaling',
                  tune_interval=100, tune_drop_fraction=0.9, scaling=1e-3, lamb=None, objective='rmsd',
-                 seed=0, initial=None, segment=64):
+                 seed=0, initial=None, segment=64, folds=None):
         self.problem = problem
         self._handle = C.c_void_p()
         row = _row(params)
@@ -349,13 +439,37 @@ class DEMetropolisZ(object):
             raise ValueError('the sampler needs a problem bound with math=MATH_FAST (EXACT cannot be captured)')
         if not problem.has_observed:
             raise ValueError('the problem was bound without observed')
-        if self.chains > problem.max_draws:
-            raise ValueError('%d chains, the problem was bound for max_draws = %d' % (self.chains, problem.max_draws))
+        #: the folds of the chain groups (None: a plain sampler)
+        self.folds = None
+        if isinstance(folds, (bool, np.bool_)):
+            folds = True if folds else None         # (False: a plain sampler)
+        elif folds is not None:
+            arr = np.asarray(folds)
+            if arr.ndim != 1 or (arr.size and not np.issubdtype(arr.dtype, np.integer)):
+                raise ValueError('folds must be True or a list of folds (got %r)' % (folds,))
+        if folds is not None:
+            nf = getattr(problem, 'nfolds', 0)
+            if not nf:
+                raise ValueError('folds need a problem bound with folds (MOD16._et_bind(..., folds=...))')
+            fl = list(range(nf)) if folds is True else [int(f) for f in folds]
+            if not fl or len(set(fl)) != len(fl) or min(fl) < 0 or max(fl) >= nf:
+                raise ValueError('folds must be True or distinct folds in 0 .. %d (got %r)' % (nf - 1, folds))
+            self.folds = fl
+        groups = len(self.folds) if self.folds else 1
+        if self.chains * groups > problem.max_draws:
+            raise ValueError('%d chains x %d fold(s), the problem was bound for max_draws = %d'
+                             % (self.chains, groups, problem.max_draws))
         x0 = None
         if initial is not None:
-            x0 = np.ascontiguousarray(initial, np.float64)
-            if x0.shape != (self.chains, d):
-                raise ValueError('initial must be (chains, %d) = (%d, %d)' % (d, self.chains, d))
+            x0 = np.asarray(initial, np.float64)
+            if self.folds and x0.shape == (self.chains, d):
+                x0 = np.concatenate([x0] * groups)
+            elif self.folds and x0.shape == (groups, self.chains, d):
+                x0 = x0.reshape(groups * self.chains, d)
+            elif self.folds or x0.shape != (self.chains, d):
+                raise ValueError('initial must be (chains, %d) = (%d, %d)%s' % (
+                    d, self.chains, d, ' or (folds, chains, d)' if self.folds else ''))
+            x0 = np.ascontiguousarray(x0)
             for i, name in enumerate(self.names):
                 fam, p = self.families[name], self.prior_params[name]
                 ok = (x0[:, i] > 0) & np.isfinite(x0[:, i]) if fam == 'lognormal' else (x0[:, i] > p[0]) & (x0[:, i] < p[1])
@@ -378,10 +492,15 @@ class DEMetropolisZ(object):
         spec.segment = int(segment)
         spec.seed = self.seed
         self._ctx = problem._ctx
-        self._keep = (spec, x0)
-        status = self._ctx.lib.mod16_mcmc_create(problem._handle, C.byref(spec),
-                                                 x0.ctypes.data if x0 is not None else None,
-                                                 C.byref(self._handle))
+        x0p = x0.ctypes.data if x0 is not None else None
+        if self.folds:
+            fold_arr = np.array(self.folds, np.int32)
+            self._keep = (spec, x0, fold_arr)
+            status = self._ctx.lib.mod16_mcmc_create_groups(problem._handle, C.byref(spec), groups,
+                                                            fold_arr.ctypes.data, x0p, C.byref(self._handle))
+        else:
+            self._keep = (spec, x0)
+            status = self._ctx.lib.mod16_mcmc_create(problem._handle, C.byref(spec), x0p, C.byref(self._handle))
         if status == _lib.ERR_ARG:
             raise ValueError(self._ctx.lib.mod16_last_error(self._ctx.handle).decode())
         self._ctx.check(status)
@@ -392,6 +511,11 @@ class DEMetropolisZ(object):
     @property
     def d(self):
         return len(self.names)
+
+    @property
+    def total_chains(self):
+        '''Chains in the sampler: ``chains`` x the number of folds.'''
+        return self.chains * (len(self.folds) if self.folds else 1)
 
     def run(self, steps):
         '''``steps`` more steps of every chain (no trace returned); the GPU milliseconds they took.'''
@@ -404,7 +528,7 @@ class DEMetropolisZ(object):
     def read(self, t0, count):
         '''Steps [t0, t0 + count) of every chain: (x (count, chains, d), y, loglik (count, chains),
         logpost, accepted, scaling (chains,), lamb).'''
-        C_, d = self.chains, self.d
+        C_, d = self.total_chains, self.d
         x = np.empty((count, C_, d))
         y = np.empty((count, C_, d))
         ll = np.empty((count, C_))
@@ -429,11 +553,59 @@ class DEMetropolisZ(object):
         self.run(first + draws)
         x, _, ll, lp, acc, sc, lb = self.read(start, draws)
         samples = {name: np.ascontiguousarray(x[:, :, i].T) for i, name in enumerate(self.names)}
-        return Trace(self.names, samples, np.ascontiguousarray(ll.T), np.ascontiguousarray(lp.T),
-                     np.ascontiguousarray(acc.T), sc, lb)
+        args = (self.names, samples, np.ascontiguousarray(ll.T), np.ascontiguousarray(lp.T),
+                np.ascontiguousarray(acc.T), sc, lb)
+        if not self.folds:
+            return Trace(*args)
+        return KFoldTrace(*args, chain_fold=np.repeat(self.folds, self.chains),
+                          labels=self.problem.labels, nfolds=self.problem.nfolds)
+
+    def rows(self, samples):
+        '''Parameter rows (m, 11): the fixed row with the free columns from ``samples`` (m, d).'''
+        samples = np.asarray(samples, np.float64).reshape(-1, self.d)
+        rows = np.repeat(self.fixed_row[None], samples.shape[0], axis=0)
+        for i, name in enumerate(self.names):
+            rows[:, PARAM_NAMES.index(name)] = samples[:, i]
+        return rows
+
+    def heldout(self, trace, burn=0, thin=1):
+        '''Scores a ``KFoldTrace`` of this sampler on the site-days each fold held out:
+        ``{f: {'sse', 'count', 'rmsd': (chains, k) of every kept draw (after ``burn``, every
+        ``thin``-th), 'mean': the posterior-mean x-values (d,), 'mean_rmsd': the held-out RMSD of
+        that row}}``. Every fold's rows are evaluated in HELDOUT mode, up to ``max_draws`` rows (of
+        any folds) per launch.'''
+        if not self.folds or not isinstance(trace, KFoldTrace):
+            raise ValueError('heldout() scores the KFoldTrace of a sampler made with folds')
+        post = {f: trace.fold(f).posterior(burn, thin) for f in trace.folds}
+        rows, codes, shapes = [], [], {}
+        for f in trace.folds:
+            x = np.stack([post[f][name] for name in self.names], axis=-1)     # (chains, k, d)
+            shapes[f] = x.shape[:2]
+            mean = x.reshape(-1, self.d).mean(axis=0) if x.size else np.full(self.d, np.nan)
+            rows.append(self.rows(np.concatenate([x.reshape(-1, self.d), mean[None]])))
+            codes.append(np.full(rows[-1].shape[0], f))
+        rows, codes = np.concatenate(rows), np.concatenate(codes)
+        sse, cnt = np.empty(rows.shape[0]), np.empty(rows.shape[0])
+        step = self.problem.max_draws
+        for a in range(0, rows.shape[0], step):
+            sse[a:a + step], cnt[a:a + step] = self.problem.objective(
+                rows[a:a + step], folds=codes[a:a + step], heldout=True)
+        out, a = {}, 0
+        with np.errstate(invalid='ignore', divide='ignore'):
+            for f in trace.folds:
+                m = shapes[f][0] * shapes[f][1]
+                s, c = sse[a:a + m].reshape(shapes[f]), cnt[a:a + m].reshape(shapes[f])
+                out[f] = {'sse': s, 'count': c, 'rmsd': np.sqrt(s / c),
+                          'mean': rows[a + m, [PARAM_NAMES.index(k) for k in self.names]],
+                          'mean_rmsd': float(np.sqrt(sse[a + m] / cnt[a + m]))}
+                a += m + 1
+        return out
 
     def close(self):
-        if getattr(self, '_handle', None) is not None and self._handle.value:
+        '''Frees the sampler. Once its context is destroyed (interpreter teardown can finalise the
+        context before the sampler) there is nothing to free through it -- the context's lock went
+        with it -- and close() does nothing.'''
+        if getattr(self, '_handle', None) is not None and self._handle.value and self._ctx.handle.value:
             self._ctx.lib.mod16_mcmc_destroy(self._handle)
             self._handle.value = None
 

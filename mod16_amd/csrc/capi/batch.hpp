@@ -37,6 +37,17 @@ struct mod16_batch {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     int64_t graph_ndraw = -1;
+    // cross-validation (mod16_static_batch_set_folds): a fold label per pixel, resident; the fold
+    // objective's codes and its own cached graph (plain and fold calls never share one)
+    uint8_t* label = nullptr;           // [n], NULL: no folds
+    int nfolds = 0;
+    int32_t* dcode = nullptr;           // [max_draws] device
+    int32_t* hcode = nullptr;           // [max_draws] pinned staging
+    hipGraph_t fgraph = nullptr;
+    hipGraphExec_t fexec = nullptr;
+    int64_t fgraph_ndraw = -1;
+    hipGraphExec_t last_exec = nullptr; // the graph of the last objective call (mod16_static_batch_time)
+    int samplers = 0;                   // samplers alive on the problem (capi/mcmc.hip)
 };
 
 // The evaluation workspace of the FAST objective: the parameter rows it reads and everything it
@@ -47,6 +58,7 @@ struct EvalWs {
     const void* params = nullptr;       // [ndraw][11] of the data type
     double *par16 = nullptr, *partial = nullptr, *redo = nullptr, *sse = nullptr, *cnt = nullptr;
     unsigned *any_gs = nullptr, *any_draw = nullptr;
+    const int32_t* code = nullptr;      // [ndraw] fold code per draw (the FOLD kernels); NULL: plain draws
 };
 static EvalWs batch_own_ws(const mod16_batch* b) {
     EvalWs w;
@@ -61,8 +73,12 @@ static EvalWs batch_own_ws(const mod16_batch* b) {
     return w;
 }
 
+// w.code set: the FOLD instances (the problem's labels, the draws' fold codes); otherwise the plain ones.
+// (Folds exist on float64 problems only: kFold keeps float32 FOLD instances out of the library.)
 template <typename T>
 static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int64_t ndraw) {
+    constexpr bool kFold = std::is_same<T, double>::value;
+    const bool fold = kFold && w.code != nullptr;
     hipStream_t st = b->st;
     const unsigned gd = (unsigned)((ndraw + kBlock - 1) / kBlock);
     hipLaunchKernelGGL((static_obj_params_kernel<T>), dim3(gd), dim3(kBlock), 0, st, static_cast<const T*>(w.params), ndraw, w.par16);
@@ -80,8 +96,11 @@ static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int6
     a.any_draw = w.any_draw;
     a.partial = w.partial;
     a.any_gs = w.any_gs;
+    a.code = w.code;
+    a.label = fold ? b->label : nullptr;
     const dim3 grid((unsigned)b->gx, (unsigned)((ndraw + kObjDraws - 1) / kObjDraws));
-    hipLaunchKernelGGL((static_obj_kernel<T, true>), grid, dim3(kBlock), 0, st, a);
+    if (fold) hipLaunchKernelGGL((static_obj_kernel<T, true, kFold>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((static_obj_kernel<T, true>), grid, dim3(kBlock), 0, st, a);
     if (b->nlist) {
         StaticObjRedoArgs<T> r;
         memset(&r, 0, sizeof r);
@@ -93,12 +112,16 @@ static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int6
         r.list = b->list;
         r.nlist = b->nlist;
         r.redo = w.redo;
-        hipLaunchKernelGGL((static_obj_redo_kernel<T>), dim3((unsigned)ndraw), dim3(kBlock), 0, st, r);
+        r.code = w.code;
+        r.label = a.label;
+        if (fold) hipLaunchKernelGGL((static_obj_redo_kernel<T, kFold>), dim3((unsigned)ndraw), dim3(kBlock), 0, st, r);
+        else hipLaunchKernelGGL((static_obj_redo_kernel<T>), dim3((unsigned)ndraw), dim3(kBlock), 0, st, r);
     }
     const double* redo = b->nlist ? w.redo : nullptr;
     const unsigned gr = (unsigned)((ndraw + kObjPerBlock - 1) / kObjPerBlock);
     hipLaunchKernelGGL(static_obj_any_kernel, dim3(gr), dim3(kBlock), 0, st, w.any_gs, redo, ndraw, b->gx, w.any_draw);
-    hipLaunchKernelGGL((static_obj_kernel<T, false>), grid, dim3(kBlock), 0, st, a);
+    if (fold) hipLaunchKernelGGL((static_obj_kernel<T, false, kFold>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((static_obj_kernel<T, false>), grid, dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(static_obj_final_kernel, dim3(gr), dim3(kBlock), 0, st, w.partial, redo, w.any_draw, ndraw, b->gx,
                        w.sse, w.cnt);
 }

@@ -323,6 +323,11 @@ extern "C" int mod16_static_batch_destroy(mod16_batch* b) {
     if (b->st) (void)hipStreamSynchronize(b->st);
     if (b->exec) (void)hipGraphExecDestroy(b->exec);
     if (b->graph) (void)hipGraphDestroy(b->graph);
+    if (b->fexec) (void)hipGraphExecDestroy(b->fexec);
+    if (b->fgraph) (void)hipGraphDestroy(b->fgraph);
+    if (b->label) (void)hipFree(b->label);
+    if (b->dcode) (void)hipFree(b->dcode);
+    if (b->hcode) (void)hipHostFree(b->hcode);
     if (b->owned) (void)hipFree(b->owned);
     if (b->skip) (void)hipFree(b->skip);
     if (b->list) (void)hipFree(b->list);
@@ -472,6 +477,17 @@ extern "C" int mod16_static_batch_info(const mod16_batch* b, int64_t* n, int64_t
     return MOD16_OK;
 }
 
+// the problem's cached objective graphs (plain and fold)
+static void batch_drop_graphs(mod16_batch* b) {
+    if (b->exec) (void)hipGraphExecDestroy(b->exec);
+    if (b->graph) (void)hipGraphDestroy(b->graph);
+    if (b->fexec) (void)hipGraphExecDestroy(b->fexec);
+    if (b->fgraph) (void)hipGraphDestroy(b->fgraph);
+    b->exec = b->fexec = b->last_exec = nullptr;
+    b->graph = b->fgraph = nullptr;
+    b->graph_ndraw = b->fgraph_ndraw = -1;
+}
+
 // the kernels of one objective evaluation (FAST arithmetic), enqueued on b->st
 // The per-block partials and flags of the FAST objective for `ndraw` draws (grown to the next power
 // of two, at most max_draws; a captured graph holds the old addresses: dropped with them).
@@ -481,11 +497,7 @@ static int batch_eval_ws(mod16_batch* b, int64_t ndraw) {
     int64_t want = 64;
     while (want < ndraw) want *= 2;
     want = std::min(want, b->max_draws);
-    if (b->exec) (void)hipGraphExecDestroy(b->exec);
-    if (b->graph) (void)hipGraphDestroy(b->graph);
-    b->exec = nullptr;
-    b->graph = nullptr;
-    b->graph_ndraw = -1;
+    batch_drop_graphs(b);
     HIPCHK(ctx, hipStreamSynchronize(b->st));
     if (b->eval_ws) HIPCHK(ctx, hipFree(b->eval_ws));
     b->eval_ws = nullptr;
@@ -503,8 +515,9 @@ static int batch_eval_ws(mod16_batch* b, int64_t ndraw) {
     return MOD16_OK;
 }
 
+// code: NULL (plain draws) or the fold code of every draw (mod16_static_batch_objective_folds, checked)
 template <typename T>
-static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, double* sse, double* count) {
+static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const int32_t* code, double* sse, double* count) {
     mod16_ctx* ctx = b->ctx;
     if (!params || !sse || !count || ndraw < 0 || ndraw > b->max_draws)
         return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_objective: NULL argument or more draws than the problem was bound for");
@@ -513,6 +526,10 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, doubl
     HIPCHK(ctx, hipSetDevice(b->device));
     memcpy(b->hparams, params, sizeof(T) * (size_t)ndraw * 11);
     HIPCHK(ctx, hipMemcpyAsync(b->dparams, b->hparams, sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
+    if (code) {
+        memcpy(b->hcode, code, sizeof(int32_t) * (size_t)ndraw);
+        HIPCHK(ctx, hipMemcpyAsync(b->dcode, b->hcode, sizeof(int32_t) * (size_t)ndraw, hipMemcpyHostToDevice, b->st));
+    }
     if (b->flags & MOD16_MATH_EXACT) {
         // reference order: rows into a workspace, then the residuals' sums (the kernels of the unbound call)
         const size_t need = sizeof(T) * (size_t)ndraw * (size_t)b->n;
@@ -534,20 +551,28 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, doubl
     } else {
         int rc = batch_eval_ws(b, ndraw);
         if (rc != MOD16_OK) return rc;
-        if (b->graph_ndraw != ndraw) {          // (re)capture: the kernels' arguments hold the number of draws
-            if (b->exec) (void)hipGraphExecDestroy(b->exec);
-            if (b->graph) (void)hipGraphDestroy(b->graph);
-            b->exec = nullptr;
-            b->graph = nullptr;
-            b->graph_ndraw = -1;
+        // plain and fold calls keep a graph each: the launches differ (kernels, the codes' address)
+        hipGraph_t& graph = code ? b->fgraph : b->graph;
+        hipGraphExec_t& exec = code ? b->fexec : b->exec;
+        int64_t& graph_ndraw = code ? b->fgraph_ndraw : b->graph_ndraw;
+        if (graph_ndraw != ndraw) {             // (re)capture: the kernels' arguments hold the number of draws
+            if (exec) (void)hipGraphExecDestroy(exec);
+            if (graph) (void)hipGraphDestroy(graph);
+            if (b->last_exec == exec) b->last_exec = nullptr;
+            exec = nullptr;
+            graph = nullptr;
+            graph_ndraw = -1;
+            EvalWs w = batch_own_ws(b);
+            w.code = code ? b->dcode : nullptr;
             HIPCHK(ctx, hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
-            batch_objective_launches<T>(b, batch_own_ws(b), ndraw);
-            hipError_t e = hipStreamEndCapture(b->st, &b->graph);
+            batch_objective_launches<T>(b, w, ndraw);
+            hipError_t e = hipStreamEndCapture(b->st, &graph);
             HIPCHK(ctx, e);
-            HIPCHK(ctx, hipGraphInstantiate(&b->exec, b->graph, nullptr, nullptr, 0));
-            b->graph_ndraw = ndraw;
+            HIPCHK(ctx, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            graph_ndraw = ndraw;
         }
-        HIPCHK(ctx, hipGraphLaunch(b->exec, b->st));
+        HIPCHK(ctx, hipGraphLaunch(exec, b->st));
+        b->last_exec = exec;
     }
     HIPCHK(ctx, hipMemcpyAsync(b->hout, b->dsse, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
     HIPCHK(ctx, hipMemcpyAsync(b->hout + b->max_draws, b->dcnt, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
@@ -560,8 +585,64 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, doubl
 extern "C" int mod16_static_batch_objective(mod16_batch* b, const void* params, int64_t ndraw, double* sse, double* count) {
     if (!b) return MOD16_ERR_ARG;
     MOD16_LOCK(b->ctx);
-    return b->f32 ? batch_objective<float>(b, static_cast<const float*>(params), ndraw, sse, count)
-                  : batch_objective<double>(b, static_cast<const double*>(params), ndraw, sse, count);
+    return b->f32 ? batch_objective<float>(b, static_cast<const float*>(params), ndraw, nullptr, sse, count)
+                  : batch_objective<double>(b, static_cast<const double*>(params), ndraw, nullptr, sse, count);
+}
+
+// ---- cross-validation: fold labels per pixel, fold codes per draw
+extern "C" int mod16_static_batch_set_folds(mod16_batch* b, const uint8_t* labels, int nfolds) {
+    if (!b) return MOD16_ERR_ARG;
+    MOD16_LOCK(b->ctx);
+    mod16_ctx* ctx = b->ctx;
+    if (b->f32 || (b->flags & MOD16_MATH_EXACT) || !b->obs)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: folds need a float64 MOD16_MATH_FAST problem bound with observations");
+    if (b->label) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: the problem already has folds");
+    if (b->samplers) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: a sampler exists on the problem");
+    if (!labels || nfolds < 2 || nfolds > 255)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: NULL labels or nfolds outside 2 .. 255");
+    std::vector<int64_t> seen((size_t)nfolds, 0);
+    for (int64_t i = 0; i < b->n; ++i) {
+        if (labels[i] >= nfolds) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: a label outside 0 .. nfolds - 1");
+        ++seen[labels[i]];
+    }
+    for (int f = 0; f < nfolds; ++f)
+        if (!seen[(size_t)f]) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: a fold without any pixel");
+    HIPCHK(ctx, hipSetDevice(b->device));
+    int rc = [&]() -> int {
+        if (hipMalloc(reinterpret_cast<void**>(&b->label), (size_t)b->n) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&b->dcode), sizeof(int32_t) * (size_t)b->max_draws) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, MOD16_ERR_NOMEM, "mod16_static_batch_set_folds: device memory for the labels");
+        }
+        HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&b->hcode), sizeof(int32_t) * (size_t)b->max_draws));
+        HIPCHK(ctx, hipMemcpyAsync(b->label, labels, (size_t)b->n, hipMemcpyHostToDevice, b->st));
+        HIPCHK(ctx, hipStreamSynchronize(b->st));
+        return MOD16_OK;
+    }();
+    if (rc != MOD16_OK) {
+        if (b->label) (void)hipFree(b->label);
+        if (b->dcode) (void)hipFree(b->dcode);
+        if (b->hcode) (void)hipHostFree(b->hcode);
+        b->label = nullptr;
+        b->dcode = b->hcode = nullptr;
+        return rc;
+    }
+    b->nfolds = nfolds;
+    return MOD16_OK;
+}
+
+extern "C" int mod16_static_batch_objective_folds(mod16_batch* b, const void* params, int64_t ndraw, const int32_t* code,
+                                                  double* sse, double* count) {
+    if (!b) return MOD16_ERR_ARG;
+    MOD16_LOCK(b->ctx);
+    mod16_ctx* ctx = b->ctx;
+    if (!b->label) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_objective_folds: the problem has no folds (mod16_static_batch_set_folds)");
+    if (ndraw < 0 || ndraw > b->max_draws || (!code && ndraw > 0))
+        return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_objective_folds: NULL codes or more draws than the problem was bound for");
+    for (int64_t d = 0; d < ndraw; ++d)
+        if ((code[d] & ~(0xff | MOD16_FOLD_HELDOUT)) || (code[d] & 0xff) >= b->nfolds)
+            return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_objective_folds: a code that is not fold | MOD16_FOLD_HELDOUT with fold < nfolds");
+    return batch_objective<double>(b, static_cast<const double*>(params), ndraw, code, sse, count);
 }
 
 // rows [ndraw][n] (host) of the bound problem: the kernels of the unbound call on the resident drivers
@@ -609,16 +690,17 @@ extern "C" int mod16_static_batch_rows(mod16_batch* b, const void* params, int64
                                        static_cast<double*>(out_night), static_cast<double*>(out_total));
 }
 
-// mean milliseconds of the GPU part of an objective evaluation (graph replays on the problem's
-// stream, HIP events): what bench.py puts next to the wall-clock rate of the call
+// mean milliseconds of the GPU part of an objective evaluation (replays of the graph of the last
+// objective call, plain or fold, on the problem's stream, HIP events): what bench.py puts next to the
+// wall-clock rate of the call
 extern "C" int mod16_static_batch_time(mod16_batch* b, int launches, float* ms) {
-    if (!b || !ms || launches <= 0 || !b->exec) return MOD16_ERR_ARG;
+    if (!b || !ms || launches <= 0 || !b->last_exec) return MOD16_ERR_ARG;
     MOD16_LOCK(b->ctx);
     if (hipSetDevice(b->device) != hipSuccess) return MOD16_ERR_HIP;
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return MOD16_ERR_HIP;
     bool ok = hipEventRecord(e0, b->st) == hipSuccess;
-    for (int i = 0; i < launches && ok; ++i) ok = hipGraphLaunch(b->exec, b->st) == hipSuccess;
+    for (int i = 0; i < launches && ok; ++i) ok = hipGraphLaunch(b->last_exec, b->st) == hipSuccess;
     ok = ok && hipEventRecord(e1, b->st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
     float t = 0.f;
     ok = ok && hipEventElapsedTime(&t, e0, e1) == hipSuccess;

@@ -18,6 +18,7 @@ struct mod16_mcmc {
     hipGraphExec_t e_full = nullptr, e_rem = nullptr;
     int64_t rem_len = 0;                  // steps of the remainder graph held in e_rem
     bool broken = false;                  // a run failed: the device step counters and `steps` may disagree
+    bool counted = false;                 // in the problem's count of samplers
 };
 
 static void mcmc_drop_graphs(mod16_mcmc* m) {
@@ -36,6 +37,7 @@ extern "C" int mod16_mcmc_destroy(mod16_mcmc* m) {
     (void)hipSetDevice(m->b->device);
     (void)hipStreamSynchronize(m->b->st);
     mcmc_drop_graphs(m);
+    if (m->counted) --m->b->samplers;
     if (m->state) (void)hipFree(m->state);
     if (m->eval) (void)hipFree(m->eval);
     if (m->trace) (void)hipFree(m->trace);
@@ -110,11 +112,20 @@ static int mcmc_capture(mod16_mcmc* m, int64_t steps, hipGraph_t* g, hipGraphExe
     return MOD16_OK;
 }
 
-static int mcmc_check_spec(mod16_ctx* ctx, const mod16_batch* b, const mod16_mcmc_spec* s) {
+static int mcmc_check_spec(mod16_ctx* ctx, const mod16_batch* b, const mod16_mcmc_spec* s, int ngroups, const int32_t* fold) {
     if (b->f32 || (b->flags & MOD16_MATH_EXACT) || !b->obs)
         return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: the problem must be float64, MOD16_MATH_FAST and bound with observations");
-    if (s->chains < 1 || s->chains > b->max_draws)
-        return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: chains outside 1 .. the problem's max_draws");
+    if (fold) {
+        if (!b->label) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create_groups: the problem has no folds (mod16_static_batch_set_folds)");
+        if (ngroups < 1 || ngroups > b->nfolds) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create_groups: ngroups outside 1 .. nfolds");
+        for (int g = 0; g < ngroups; ++g) {
+            if (fold[g] < 0 || fold[g] >= b->nfolds) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create_groups: a fold outside 0 .. nfolds - 1");
+            for (int h = 0; h < g; ++h)
+                if (fold[h] == fold[g]) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create_groups: a fold listed twice");
+        }
+    }
+    if (s->chains < 1 || (int64_t)s->chains * ngroups > b->max_draws)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: chains (x groups) outside 1 .. the problem's max_draws");
     if (s->nfree < 1 || s->nfree > kMcmcMaxD) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: nfree outside 1 .. 11");
     for (int i = 0; i < s->nfree; ++i) {
         if (s->index[i] < 0 || s->index[i] > 10 || (i && s->index[i] <= s->index[i - 1]))
@@ -137,11 +148,22 @@ static int mcmc_check_spec(mod16_ctx* ctx, const mod16_batch* b, const mod16_mcm
     return MOD16_OK;
 }
 
-static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, const double* x0, mod16_mcmc** out) {
+// ngroups groups of spec->chains chains; fold: NULL (a plain sampler, one group) or the groups' folds
+static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, int ngroups, const int32_t* fold, const double* x0,
+                       mod16_mcmc** out) {
     mod16_ctx* ctx = b->ctx;
-    int rc = mcmc_check_spec(ctx, b, s);
+    int rc = mcmc_check_spec(ctx, b, s, ngroups, fold);
     if (rc != MOD16_OK) return rc;
-    const int C = s->chains, d = s->nfree;
+    const int C = s->chains * ngroups, d = s->nfree;
+    // the chains' stream keys and fold codes (mod16_mcmc.hpp, "Groups")
+    std::vector<uint64_t> keys((size_t)C);
+    std::vector<int32_t> codes((size_t)C);
+    for (int g = 0; g < ngroups; ++g)
+        for (int j = 0; j < s->chains; ++j) {
+            const int32_t f = fold ? fold[g] : 0;
+            keys[(size_t)g * s->chains + j] = mcmc_mix(mcmc_mix(s->seed + (uint64_t)f) ^ (uint64_t)j);
+            codes[(size_t)g * s->chains + j] = f;
+        }
     // the initial x-values, [C][d]: the caller's (inside the supports) or the support points
     std::vector<double> init((size_t)C * d);
     for (int c = 0; c < C; ++c)
@@ -165,6 +187,8 @@ static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, const double* x
     mod16_mcmc* m = new (std::nothrow) mod16_mcmc;
     if (!m) return MOD16_ERR_NOMEM;
     m->b = b;
+    ++b->samplers;
+    m->counted = true;
     m->segment = s->segment ? s->segment : kMcmcSegment;
     McmcArgs& a = m->a;
     memset(&a, 0, sizeof a);
@@ -183,13 +207,12 @@ static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, const double* x
     a.tune_steps = s->tune_steps;
     a.drop_lo = (int64_t)std::floor(s->tune_drop_fraction * (double)s->tune_steps);
     a.objective = s->objective;
-    a.seed_mixed = mcmc_mix(s->seed);
     a.scaling0 = s->scaling;
     a.lamb0 = s->lamb;
     rc = [&]() -> int {
         // per-chain state
         const size_t sd = mcmc_al((size_t)C * d * 8), s1 = mcmc_al((size_t)C * 8), sx0 = mcmc_al(init.size() * 8);
-        if (hipMalloc(&m->state, 3 * sd + 6 * s1 + mcmc_al((size_t)C * 4) + sx0) != hipSuccess)
+        if (hipMalloc(&m->state, 3 * sd + 7 * s1 + mcmc_al((size_t)C * 4) + sx0) != hipSuccess)
             return mcmc_nomem(ctx, "mod16_mcmc_create: device memory for the chains' state");
         char* cur = static_cast<char*>(m->state);
         auto take = [&](size_t x) { char* p = cur; cur += x; return p; };
@@ -202,13 +225,15 @@ static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, const double* x
         a.scaling = reinterpret_cast<double*>(take(s1));
         a.lamb = reinterpret_cast<double*>(take(s1));
         a.t = reinterpret_cast<int64_t*>(take(s1));
+        uint64_t* dkey = reinterpret_cast<uint64_t*>(take(s1));
+        a.key = dkey;
         double* dx0 = reinterpret_cast<double*>(take(sx0));
         a.acc = reinterpret_cast<int*>(take(mcmc_al((size_t)C * 4)));
         // the objective's workspace for C draws: the sampler's own (see EvalWs)
         const size_t sp = mcmc_al((size_t)C * 11 * 8), s16 = mcmc_al((size_t)C * kPar16 * 8),
                      spart = mcmc_al((size_t)C * b->gx * 16), sany = mcmc_al((size_t)C * b->gx * 4),
                      su = mcmc_al((size_t)C * 4), sredo = mcmc_al((size_t)C * 40);
-        if (hipMalloc(&m->eval, sp + s16 + spart + sany + su + sredo + 2 * s1) != hipSuccess)
+        if (hipMalloc(&m->eval, sp + s16 + spart + sany + su + sredo + 2 * s1 + (fold ? su : 0)) != hipSuccess)
             return mcmc_nomem(ctx, "mod16_mcmc_create: device memory for the objective's workspace");
         cur = static_cast<char*>(m->eval);
         a.params = reinterpret_cast<double*>(take(sp));
@@ -222,8 +247,14 @@ static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, const double* x
         m->w.cnt = reinterpret_cast<double*>(take(s1));
         a.sse = m->w.sse;
         a.cnt = m->w.cnt;
-        // the initial point and its log posterior
         hipStream_t st = b->st;
+        HIPCHK(ctx, hipMemcpyAsync(dkey, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, st));
+        if (fold) {     // the groups' TRAIN codes: constant for the sampler's life, read by its graphs
+            int32_t* dcode = reinterpret_cast<int32_t*>(take(su));
+            HIPCHK(ctx, hipMemcpyAsync(dcode, codes.data(), codes.size() * 4, hipMemcpyHostToDevice, st));
+            m->w.code = dcode;
+        }
+        // the initial point and its log posterior
         const unsigned gc = (unsigned)((C + kBlock - 1) / kBlock);
         HIPCHK(ctx, hipMemcpyAsync(dx0, init.data(), init.size() * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(mcmc_init_kernel, dim3(gc), dim3(kBlock), 0, st, a, (const double*)dx0);
@@ -250,7 +281,15 @@ extern "C" int mod16_mcmc_create(mod16_batch* b, const mod16_mcmc_spec* spec, co
     if (!b || !spec || !out) return MOD16_ERR_ARG;
     *out = nullptr;
     MOD16_LOCK(b->ctx);
-    return mcmc_create(b, spec, x0, out);
+    return mcmc_create(b, spec, 1, nullptr, x0, out);
+}
+
+extern "C" int mod16_mcmc_create_groups(mod16_batch* b, const mod16_mcmc_spec* spec, int ngroups, const int32_t* fold,
+                                        const double* x0, mod16_mcmc** out) {
+    if (!b || !spec || !fold || !out) return MOD16_ERR_ARG;
+    *out = nullptr;
+    MOD16_LOCK(b->ctx);
+    return mcmc_create(b, spec, ngroups, fold, x0, out);
 }
 
 static int mcmc_run(mod16_mcmc* m, int64_t steps, float* ms) {

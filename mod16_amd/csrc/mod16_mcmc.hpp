@@ -24,6 +24,12 @@
 // Random stream (mix: splitmix64's finaliser, the sobol_mix of mod16_sobol.hpp):
 //     r(c, t, k) = mix(mix(mix(seed) ^ c) ^ ((t << 6) | k))      chain c, step t (0-based, tuning
 //                                                                 included), slot k < 64
+// Groups (mod16_mcmc_create_groups: `chains` chains for each listed fold f_g, one graph): chain j of
+// group g is global chain g chains + j, and its stream is the plain sampler's with seed
+// (seed + f_g) mod 2^64 and chain index j:
+//     r = mix(mix(mix(seed + f_g) ^ j) ^ ((t << 6) | k))
+// The key mix(mix(seed + f_g) ^ j) of every chain is made on the host (a plain sampler: one group,
+// f = 0). Group g's chains evaluate their objective with the fold code f_g (TRAIN).
 //     unit(z) = (z >> 11) 2^-53;  index(z, m) = floor(z m / 2^64) (the high half of the product)
 // Slots: 0 .. d-1 proposal noise; 16 the first history index, 17, 18, ... the second, redrawn on
 // the next slot while it equals the first (after slot 47: first + 1 mod m); 63 the Metropolis uniform.
@@ -59,7 +65,7 @@ struct McmcArgs {
     int tune_target, tune_interval;     // 0 none, 1 scaling, 2 lamb
     int64_t tune_steps, drop_lo;
     int objective;                      // 0 rmsd, 1 gaussian
-    uint64_t seed_mixed;                // mix(seed)
+    const uint64_t* key;                // [chains] the chain's stream key (see "Groups")
     double scaling0, lamb0;
     // state, [d][chains] or [chains]
     double *y, *yp, *xc;
@@ -190,7 +196,7 @@ __global__ void __launch_bounds__(kBlock) mcmc_propose_kernel(const McmcArgs a) 
         a.lamb[c] = lb;
         a.acc[c] = 0;
     }
-    const uint64_t key = mcmc_mix(a.seed_mixed ^ (uint64_t)c);
+    const uint64_t key = a.key[c];
     const int64_t lo = t < a.tune_steps ? 0 : a.drop_lo;
     const int64_t m = t - lo;
     const double *z1 = nullptr, *z2 = nullptr;
@@ -224,7 +230,7 @@ __global__ void __launch_bounds__(kBlock) mcmc_accept_kernel(const McmcArgs a) {
     const int c = blockIdx.x * kBlock + threadIdx.x;
     if (c >= a.chains) return;
     const int64_t t = a.t[c];
-    const uint64_t key = mcmc_mix(a.seed_mixed ^ (uint64_t)c);
+    const uint64_t key = a.key[c];
     const double ll = mcmc_loglik(a, c);
     const double lp = a.lprior_p[c] + ll;
     const double mr = lp - a.logp[c];

@@ -388,10 +388,22 @@ __global__ void __launch_bounds__(kBlock) static_batch_sse_kernel(const T* total
 //   static_obj_kernel<false>   the draws without it, evaluated again without transpiration (normally
 //                              none: every block reads 32 flags and ends)
 //   static_obj_final_kernel    partials of a draw added up in block order -> sse[d], count[d]
+// Cross-validation (FOLD instances of the first two kernels and of the redo kernel): each pixel
+// carries a fold label (one byte), each draw a fold code f | kFoldHeldout. A TRAIN draw (bit clear)
+// admits the pixels with label != f, a HELDOUT draw those with label == f; a pixel that is not
+// admitted adds neither a pair nor a g_surf flag, and the whole-array branch ranges over the
+// admitted pixels whose observation is a number (the reference's k-fold path drops the rows with a
+// NaN observation before _et sees them, calibration.py:896-901).
 constexpr int kObjDraws = 32;
 constexpr int kObjPass = 16;     // draws reduced at a time (LDS: 16 x 64 doubles per wave)
 constexpr int kPar16 = 16;       // doubles per draw: 11 parameters, 1 / (tmin_open - tmin_close), 1 / (vpd_close -
                                  // vpd_open), rbl slope, 1 / beta, 273.15 + tmin_open
+constexpr int kFoldHeldout = 0x100;  // fold code: MOD16_FOLD_HELDOUT (include/mod16_hip.h)
+
+// pixel of label `lab` taken by a draw of fold code `code`
+__device__ __forceinline__ bool fold_admits(unsigned lab, int code) {
+    return (lab == (unsigned)(code & 0xff)) == ((code & kFoldHeldout) != 0);
+}
 
 template <typename T>
 __global__ void __launch_bounds__(kBlock) static_obj_params_kernel(const T* params, int64_t ndraw, double* par16) {
@@ -423,12 +435,16 @@ template <typename T> struct StaticObjArgs {
     const unsigned* any_draw;   // TR = false: [ndraw], only the draws with 0 here are evaluated
     double* partial;            // [gridDim.x][ndraw][2]: sse, count
     unsigned* any_gs;           // TR = true: [gridDim.x][ndraw], 1 = a pixel of the block has g_surf > 0
+    const int32_t* code;        // FOLD: [ndraw] fold code of each draw
+    const uint8_t* label;       // FOLD: [n] fold label of each pixel
 };
 
 // TR: evaluate with the transpiration term (any(g_surf > 0) assumed true; the block also reports
 // whether one of ITS pixels has g_surf > 0). !TR: only the draws for which no block reported one,
 // transpiration = 0 (mod16/__init__.py:343-348) -- normally none: the block reads 32 flags and ends.
-template <typename T, bool TR>
+// FOLD: a draw sees only the pixels its fold code admits (fold_admits); the label is read once per
+// thread, the code is a scalar load next to the draw's parameters.
+template <typename T, bool TR, bool FOLD = false>
 __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<T> a) {
     constexpr int kTab = FastMath<double>::kTabDoubles;
     constexpr int kWaves = kBlock / 64;
@@ -458,12 +474,14 @@ __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<
     const bool live = i < a.n && !(a.skip && a.skip[i]);
     StaticPixel c;
     double obs = 0.0, w = 1.0;
+    unsigned lab = 0;
     if (live) {
         auto dv = [&](int k) { return (double)(((a.dense_drv >> k) & 1u) ? a.drv[k][i] : a.drv[k][0]); };
         const PixelIn<double> x = {dv(0), dv(1), dv(2), dv(3), dv(4), dv(5), dv(6), dv(7), dv(8), dv(9), dv(10), dv(11), dv(12), dv(13)};
         c = static_pixel_prep(x, tab);
         obs = (double)a.observed[i];
         w = a.weights ? (double)a.weights[i] : 1.0;
+        if (FOLD) lab = a.label[i];
     }
     unsigned cnt = 0;            // bit j: draw c0 + j has a pair (the residual is a number) at this pixel
     unsigned gs = 0;             // bit j: g_surf > 0 at this pixel for draw c0 + j
@@ -473,7 +491,8 @@ __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<
         for (int jj = 0; jj < kObjPass; ++jj) {
             const int j = h + jj;
             double r2 = 0.0;
-            if (live && ((want >> j) & 1u)) {
+            // (the code is read only for a wanted draw: draw c0 + j exists)
+            if (live && ((want >> j) & 1u) && (!FOLD || fold_admits(lab, a.code[c0 + j]))) {
                 const double* q = a.par16 + (c0 + j) * kPar16;       // block-uniform: scalar loads
                 ClassPar<double> p;
                 p.tmin_close = q[0]; p.tmin_open = q[1]; p.vpd_open = q[2]; p.vpd_close = q[3];
@@ -487,7 +506,7 @@ __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<
                 d.inv_beta = q[14];
                 d.cond = c.base_cond && (c.t_ann > q[15]);                    // :230-234 (tmin_open, strict)
                 const int k = d.cond ? 1 : 0;
-                if (TR) gs |= (static_gsurf(c.d, d, p) > 0.0) ? 1u << j : 0u;
+                if (TR) gs |= ((static_gsurf(c.d, d, p) > 0.0) && (!FOLD || obs == obs)) ? 1u << j : 0u;
                 const double day = static_period_eval<true>(c, c.d, d, p, c.rs_d[k], TR, tab);
                 const double night = static_period_eval<false>(c, c.n, d, p, c.rs_n[k], false, tab);
                 const double r = ((day + night) - obs) * w;                    // MOD16._et, :193
@@ -548,14 +567,20 @@ template <typename T> struct StaticObjRedoArgs {
     const int64_t* list;        // flagged pixels
     int64_t nlist;
     double* redo;               // [ndraw][5]: sse with t, count with t, sse without, count without, pixels with g_surf > 0
+    const int32_t* code;        // FOLD: [ndraw] fold code of each draw
+    const uint8_t* label;       // FOLD: [n] fold label of each pixel
 };
-template <typename T>
+// FOLD: the pixels the draw's fold code does not admit are passed over; the g_surf count takes the
+// admitted pixels whose observation is a number (as static_obj_kernel<FOLD>)
+template <typename T, bool FOLD = false>
 __global__ void __launch_bounds__(kBlock) static_obj_redo_kernel(const StaticObjRedoArgs<T> a) {
     const int64_t draw = blockIdx.x;
     double acc[5] = {0, 0, 0, 0, 0};
+    const int code = FOLD ? a.code[draw] : 0;
     for (int64_t u = threadIdx.x; u < a.nlist; u += kBlock) {
 #pragma clang fp contract(off)
         const int64_t i = a.list[u];
+        if (FOLD && !fold_admits(a.label[i], code)) continue;
         auto dv = [&](int k) { return ((a.dense_drv >> k) & 1u) ? a.drv[k][i] : a.drv[k][0]; };
         PixelIn<T> x = {dv(0), dv(1), dv(2), dv(3), dv(4), dv(5), dv(6), dv(7), dv(8), dv(9), dv(10), dv(11), dv(12), dv(13)};
         const T* q = a.params + draw * 11;
@@ -576,7 +601,7 @@ __global__ void __launch_bounds__(kBlock) static_obj_redo_kernel(const StaticObj
         ok = r == r;
         acc[2] += ok ? r * r : 0.0;
         acc[3] += ok ? 1.0 : 0.0;
-        acc[4] += any ? 1.0 : 0.0;
+        acc[4] += (any && (!FOLD || obs == obs)) ? 1.0 : 0.0;
     }
     __shared__ double sm[5][kBlock / 64];
 #pragma unroll

@@ -5,6 +5,75 @@
 #include "internal.hpp"
 #include "../mod16_methods.hpp"
 
+// The evaluation workspace of the FAST objective: the parameter rows it reads and everything it
+// writes. The problem owns one (mod16_batch::own); a sampler (capi/mcmc.hip) owns its own, so that a
+// larger objective() call, which regrows the problem's per-block part, never pulls memory from under a
+// graph the sampler has captured.
+struct EvalWs {
+    void* params = nullptr;             // [ndraw][11] of the data type
+    double *par16 = nullptr, *partial = nullptr, *redo = nullptr, *sse = nullptr, *cnt = nullptr;
+    unsigned *any_gs = nullptr, *any_draw = nullptr;
+    const int32_t* code = nullptr;      // [ndraw] fold code per draw (the FOLD kernels); NULL: plain draws
+};
+// Its two parts inside an allocation at `base` (NULL: sizes only), with the extents the kernels of
+// mod16_methods.hpp index. Per draw (`el`: bytes of the data type): params [draws][11], par16
+// [draws][kPar16], sse / cnt / any_draw [draws], redo [draws][5] ...
+static size_t eval_layout_draws(int64_t draws, size_t el, void* base, EvalWs* w) {
+    EvalWs sizes_only;
+    if (!w) w = &sizes_only;
+    Carver c(base);
+    const size_t D = (size_t)draws;
+    w->params = c.take<char>(D * 11 * el);
+    w->par16 = c.take<double>(D * kPar16 * sizeof(double));
+    w->sse = c.take<double>(D * sizeof(double));
+    w->cnt = c.take<double>(D * sizeof(double));
+    w->redo = c.take<double>(D * 5 * sizeof(double));
+    w->any_draw = c.take<unsigned>(D * sizeof(unsigned));
+    return c.used;
+}
+// ... and per block of kBlock pixels: partial [gx][draws][2], any_gs [gx][draws] (draws x blocks x 20
+// bytes: 3.2 GB at 4096 draws x 10 M pixels, so the problem sizes this part for the draws an
+// evaluation actually brings, not for max_draws; an EXACT problem never has it)
+static size_t eval_layout_blocks(int64_t draws, int gx, void* base, EvalWs* w) {
+    EvalWs sizes_only;
+    if (!w) w = &sizes_only;
+    Carver c(base);
+    const size_t cells = (size_t)draws * (size_t)gx;
+    w->partial = c.take<double>(cells * 2 * sizeof(double));
+    w->any_gs = c.take<unsigned>(cells * sizeof(unsigned));
+    return c.used;
+}
+
+// A chain of kernel launches on one stream, captured and instantiated once and kept under a key (what
+// the kernels' arguments hold: the draws of an objective graph, the steps of a sampler graph).
+struct CachedGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int64_t key = -1;
+    void drop() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr;
+        graph = nullptr;
+        key = -1;
+    }
+    // what `enqueue()` launches on `st` becomes the graph; the capture is always ended before a failed
+    // launch is reported
+    template <typename F>
+    int capture(mod16_ctx* ctx, hipStream_t st, int64_t k, F enqueue) {
+        drop();
+        HIPCHK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        enqueue();
+        const hipError_t launched = hipGetLastError();
+        const hipError_t ended = hipStreamEndCapture(st, &graph);
+        HIPCHK(ctx, launched);
+        HIPCHK(ctx, ended);
+        HIPCHK(ctx, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        key = k;
+        return MOD16_OK;
+    }
+};
+
 // ---- the calibration problem RESIDENT on the device (mod16_static_batch_bind_*): drivers,
 // observations and weights go up once; an evaluation is parameters up, one graph launch (kernels
 // only), (sse, count) down.
@@ -23,55 +92,27 @@ struct mod16_batch {
     uint8_t* skip = nullptr;            // [n]: 1 = outside the FAST domain
     int64_t* list = nullptr;            // those pixels, ascending
     int64_t nlist = 0;
-    void* ws = nullptr;                 // evaluation workspace (one allocation)
-    void* dparams = nullptr;            // [max_draws][11] of the data type
-    double *par16 = nullptr, *partial = nullptr, *redo = nullptr, *dsse = nullptr, *dcnt = nullptr;
-    unsigned *any_gs = nullptr, *any_draw = nullptr, *dflags = nullptr;
-    void* eval_ws = nullptr;            // partial + any_gs of the FAST objective: sized for the draws actually evaluated
-    int64_t eval_draws = 0;             //   (grown on demand; max_draws x blocks x 20 bytes would be GBs for large n)
+    void* ws = nullptr;                 // the per-draw part of `own` for max_draws draws, and dflags
+    EvalWs own;
+    unsigned* dflags = nullptr;         // [max_draws]: the rows kernels' any(g_surf > 0) words
+    void* eval_ws = nullptr;            // the per-block part of `own` for eval_draws draws (grown on demand: batch_eval_ws)
+    int64_t eval_draws = 0;
     void* rows = nullptr;               // [ndraw][n] x up to 3: rows workspace, allocated when first asked for
     size_t rows_bytes = 0;
     void* hparams = nullptr;            // pinned staging
     double* hout = nullptr;             // pinned [2][max_draws]
     hipStream_t st = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int64_t graph_ndraw = -1;
     // cross-validation (mod16_static_batch_set_folds): a fold label per pixel, resident; the fold
-    // objective's codes and its own cached graph (plain and fold calls never share one)
+    // objective's codes and its own cached graph (plain and fold calls never share one: the launches
+    // differ in kernels and in the codes' address)
     uint8_t* label = nullptr;           // [n], NULL: no folds
     int nfolds = 0;
     int32_t* dcode = nullptr;           // [max_draws] device
     int32_t* hcode = nullptr;           // [max_draws] pinned staging
-    hipGraph_t fgraph = nullptr;
-    hipGraphExec_t fexec = nullptr;
-    int64_t fgraph_ndraw = -1;
-    hipGraphExec_t last_exec = nullptr; // the graph of the last objective call (mod16_static_batch_time)
+    CachedGraph graph, fgraph;          // the plain and the fold objective, key = draws
+    CachedGraph* last = nullptr;        // the one the last objective call launched (mod16_static_batch_time)
     int samplers = 0;                   // samplers alive on the problem (capi/mcmc.hip)
 };
-
-// The evaluation workspace of the FAST objective: the parameter rows it reads and everything it
-// writes. The problem owns one (b->dparams ..., grown by batch_eval_ws); a sampler (capi/mcmc.hip)
-// owns its own, so that a larger objective() call, which regrows the problem's, never pulls memory
-// from under a graph the sampler has captured.
-struct EvalWs {
-    const void* params = nullptr;       // [ndraw][11] of the data type
-    double *par16 = nullptr, *partial = nullptr, *redo = nullptr, *sse = nullptr, *cnt = nullptr;
-    unsigned *any_gs = nullptr, *any_draw = nullptr;
-    const int32_t* code = nullptr;      // [ndraw] fold code per draw (the FOLD kernels); NULL: plain draws
-};
-static EvalWs batch_own_ws(const mod16_batch* b) {
-    EvalWs w;
-    w.params = b->dparams;
-    w.par16 = b->par16;
-    w.partial = b->partial;
-    w.redo = b->redo;
-    w.sse = b->dsse;
-    w.cnt = b->dcnt;
-    w.any_gs = b->any_gs;
-    w.any_draw = b->any_draw;
-    return w;
-}
 
 // w.code set: the FOLD instances (the problem's labels, the draws' fold codes); otherwise the plain ones.
 // (Folds exist on float64 problems only: kFold keeps float32 FOLD instances out of the library.)

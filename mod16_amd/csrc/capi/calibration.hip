@@ -12,19 +12,28 @@ static int batch_reserve(mod16_ctx* ctx, size_t total) {
     if (ctx->batch_buf) HIPCHK(ctx, hipFree(ctx->batch_buf));
     ctx->batch_buf = nullptr;
     ctx->batch_bytes = 0;
-    if (hipMalloc(&ctx->batch_buf, total) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->batch_buf = nullptr;
-        return fail(ctx, MOD16_ERR_NOMEM, "mod16_et_static*: device memory for the calibration workspace");
-    }
-    ctx->batch_bytes = total;
-    return MOD16_OK;
+    int rc = dev_alloc(ctx, &ctx->batch_buf, total, "mod16_et_static*: device memory for the calibration workspace");
+    if (rc == MOD16_OK) ctx->batch_bytes = total;
+    return rc;
 }
 static void batch_trim(mod16_ctx* ctx) {
     if (ctx->batch_bytes <= kBatchKeepBytes) return;
     (void)hipFree(ctx->batch_buf);
     ctx->batch_buf = nullptr;
     ctx->batch_bytes = 0;
+}
+
+// The 14 drivers (dense [n], or one element each) from host memory into slots 0 .. 13 of `per_arr`
+// bytes at `base`, on `st`; dev[k]: where driver k went. The first copy that fails is returned.
+template <typename T, typename P>
+static hipError_t upload_drivers(const T* const* drv, uint32_t dense, int64_t n, void* base, size_t per_arr, hipStream_t st, P* dev) {
+    for (int k = 0; k < 14; ++k) {
+        T* dp = reinterpret_cast<T*>(static_cast<char*>(base) + per_arr * k);
+        dev[k] = dp;
+        hipError_t e = hipMemcpyAsync(dp, drv[k], sizeof(T) * (((dense >> k) & 1u) ? n : 1), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 template <typename T>
@@ -65,11 +74,16 @@ static int static_entry(mod16_ctx* ctx, const T* const* drivers, const int64_t* 
     auto grid_of = [&](int64_t m) {
         return (int)std::max<int64_t>(1, std::min<int64_t>((m + kBlock - 1) / kBlock, (int64_t)ctx->cus * 8));
     };
+    // the flag word cleared, any(g_surf > 0) over the whole array, then the pixels
+    auto enqueue = [&](const StaticArgs<T>& d, hipStream_t st) -> hipError_t {
+        hipError_t e = hipMemsetAsync(d.flag, 0, sizeof(unsigned), st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((static_flag_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, d);
+        hipLaunchKernelGGL((static_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, d);
+        return hipSuccess;
+    };
     if (where == MOD16_DEVICE) {
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        HIPCHK(ctx, hipMemsetAsync(a.flag, 0, sizeof(unsigned), st));
-        hipLaunchKernelGGL((static_flag_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, a);
-        hipLaunchKernelGGL((static_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, a);
+        HIPCHK(ctx, enqueue(a, static_cast<hipStream_t>(stream)));
         HIPCHK(ctx, hipGetLastError());
         return MOD16_OK;
     }
@@ -89,16 +103,14 @@ static int static_entry(mod16_ctx* ctx, const T* const* drivers, const int64_t* 
             for (int k = 0; k < 11; ++k) d.par[k] = static_cast<const T*>(t.dev[14 + k]);
             for (int k = 0; k < 2; ++k) d.rc[k] = static_cast<const T*>(t.dev[25 + k]);
             for (int k = 0; k < 2; ++k) d.out[k] = static_cast<T*>(t.dev[27 + k]);
-            HIPCHK(ctx, hipMemsetAsync(d.flag, 0, sizeof(unsigned), t.st));
-            hipLaunchKernelGGL((static_flag_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, t.st, d);
-            hipLaunchKernelGGL((static_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, t.st, d);
+            HIPCHK(ctx, enqueue(d, t.st));
             return MOD16_OK;
         });
         if (rc != kSmallUnavailable) return rc;
     }
     // HOST: the whole-array branch needs every pixel before any output, so the
     // inputs are made resident once (calibration-sized arrays, not rasters)
-    const size_t per_arr = (((size_t)n * sizeof(T)) + 255) / 256 * 256;
+    const size_t per_arr = align256((size_t)n * sizeof(T));
     // the workspace the context keeps between calibration calls (mod16_et_static_batch_* shares it;
     // until round 5 this entry point allocated and freed its own on every call)
     int rcw = batch_reserve(ctx, per_arr * kArr);
@@ -107,25 +119,21 @@ static int static_entry(mod16_ctx* ctx, const T* const* drivers, const int64_t* 
     hipStream_t st = ctx->streams[0];
     char* base = static_cast<char*>(ctx->batch_buf);
     StaticArgs<T> d = a;
-    int slot = 0;
-    int rc_status = MOD16_OK;
+    int slot = 14;
+    int rc_status = upload_drivers(a.drv, a.dense_drv, n, base, per_arr, st, d.drv) == hipSuccess ? MOD16_OK : MOD16_ERR_HIP;
     auto up = [&](const T* src, bool dense) -> const T* {
         T* dp = reinterpret_cast<T*>(base + per_arr * slot++);
         hipError_t e = hipMemcpyAsync(dp, src, sizeof(T) * (dense ? n : 1), hipMemcpyHostToDevice, st);
         if (e != hipSuccess) rc_status = MOD16_ERR_HIP;
         return dp;
     };
-    for (int k = 0; k < 14; ++k) d.drv[k] = up(a.drv[k], (a.dense_drv >> k) & 1u);
     for (int k = 0; k < 11; ++k) d.par[k] = up(a.par[k], (a.dense_par >> k) & 1u);
     for (int k = 0; k < 2; ++k) d.rc[k] = a.rc[k] ? up(a.rc[k], (a.dense_rc >> k) & 1u) : nullptr;
     slot = 27;
     d.out[0] = reinterpret_cast<T*>(base + per_arr * slot++);
     d.out[1] = reinterpret_cast<T*>(base + per_arr * slot++);
     if (rc_status == MOD16_OK) {
-        (void)hipMemsetAsync(d.flag, 0, sizeof(unsigned), st);
-        hipLaunchKernelGGL((static_flag_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, d);
-        hipLaunchKernelGGL((static_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, d);
-        if (hipGetLastError() != hipSuccess) rc_status = MOD16_ERR_HIP;
+        if (enqueue(d, st) != hipSuccess || hipGetLastError() != hipSuccess) rc_status = MOD16_ERR_HIP;
         if (hipMemcpyAsync(out_day, d.out[0], sizeof(T) * n, hipMemcpyDeviceToHost, st) != hipSuccess) rc_status = MOD16_ERR_HIP;
         if (hipMemcpyAsync(out_night, d.out[1], sizeof(T) * n, hipMemcpyDeviceToHost, st) != hipSuccess) rc_status = MOD16_ERR_HIP;
     }
@@ -240,15 +248,11 @@ static int static_batch_entry(mod16_ctx* ctx, const T* const* drivers, const int
     // HOST: drivers / parameters resident once, outputs [ndraw][n] come back
     if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
     hipStream_t st = ctx->streams[0];
-    const size_t per_arr = (((size_t)n * sizeof(T)) + 255) / 256 * 256;
-    const size_t per_out = (((size_t)n * (size_t)ndraw * sizeof(T)) + 255) / 256 * 256;
+    const size_t per_arr = align256((size_t)n * sizeof(T)), per_out = align256((size_t)n * (size_t)ndraw * sizeof(T));
     const bool want[3] = {out_day != nullptr, out_night != nullptr, out_total != nullptr || sse != nullptr};
     T* const host_out[3] = {out_day, out_night, out_total};
-    const size_t par_b = (((size_t)ndraw * 11 * sizeof(T)) + 255) / 256 * 256;
-    const size_t red_b = (((size_t)ndraw * sizeof(double)) + 255) / 256 * 256;
-    const size_t flag_b = (((size_t)ndraw * sizeof(unsigned)) + 255) / 256 * 256;
-    const size_t skip_b = ((size_t)n + 255) / 256 * 256;
-    const size_t total = per_arr * 16 + par_b + 2 * red_b + flag_b + skip_b +
+    const size_t par_b = (size_t)ndraw * 11 * sizeof(T), red_b = (size_t)ndraw * sizeof(double), flag_b = (size_t)ndraw * sizeof(unsigned);
+    const size_t total = per_arr * 16 + align256(par_b) + 2 * align256(red_b) + align256(flag_b) + align256((size_t)n) +
                          per_out * ((int)want[0] + (int)want[1] + (int)want[2]);
     // workspace kept in the context between calls (a calibration loop repeats the same
     // shape thousands of times -- better still: mod16_static_batch_bind_*); it only grows, up to
@@ -257,29 +261,23 @@ static int static_batch_entry(mod16_ctx* ctx, const T* const* drivers, const int
         int rcw = batch_reserve(ctx, total);
         if (rcw != MOD16_OK) return rcw;
     }
-    char* base = static_cast<char*>(ctx->batch_buf);
     int rc = MOD16_OK;
     auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MOD16_OK) { rc = MOD16_ERR_HIP; ctx->err = hipGetErrorString(e); } };
-    char* cur = base;
-    auto take = [&](size_t b) { char* p = cur; cur += b; return p; };
+    Carver c(ctx->batch_buf);
     StaticBatchArgs<T> d = a;
-    for (int k = 0; k < 14; ++k) {
-        T* dp = reinterpret_cast<T*>(take(per_arr));
-        chk(hipMemcpyAsync(dp, a.drv[k], sizeof(T) * (((a.dense_drv >> k) & 1u) ? n : 1), hipMemcpyHostToDevice, st));
-        d.drv[k] = dp;
-    }
-    T* dobs = reinterpret_cast<T*>(take(per_arr));
-    T* dw = reinterpret_cast<T*>(take(per_arr));
+    chk(upload_drivers(a.drv, a.dense_drv, n, c.take<char>(per_arr * 14), per_arr, st, d.drv));
+    T* dobs = c.take<T>(per_arr);
+    T* dw = c.take<T>(per_arr);
     if (sse) chk(hipMemcpyAsync(dobs, observed, sizeof(T) * n, hipMemcpyHostToDevice, st));
     if (sse && weights) chk(hipMemcpyAsync(dw, weights, sizeof(T) * n, hipMemcpyHostToDevice, st));
-    T* dpar = reinterpret_cast<T*>(take(par_b));
-    chk(hipMemcpyAsync(dpar, params, sizeof(T) * ndraw * 11, hipMemcpyHostToDevice, st));
+    T* dpar = c.take<T>(par_b);
+    chk(hipMemcpyAsync(dpar, params, par_b, hipMemcpyHostToDevice, st));
     d.params = dpar;
-    double* dsse = reinterpret_cast<double*>(take(red_b));
-    double* dcnt = reinterpret_cast<double*>(take(red_b));
-    unsigned* dflags = reinterpret_cast<unsigned*>(take(flag_b));
-    uint8_t* dskip = reinterpret_cast<uint8_t*>(take(skip_b));
-    for (int k = 0; k < 3; ++k) d.out[k] = want[k] ? reinterpret_cast<T*>(take(per_out)) : nullptr;
+    double* dsse = c.take<double>(red_b);
+    double* dcnt = c.take<double>(red_b);
+    unsigned* dflags = c.take<unsigned>(flag_b);
+    uint8_t* dskip = c.take<uint8_t>((size_t)n);
+    for (int k = 0; k < 3; ++k) d.out[k] = want[k] ? c.take<T>(per_out) : nullptr;
     if (rc == MOD16_OK)
         rc = static_batch_rows<T>(ctx, d, ndraw, dobs, (sse && weights) ? dw : nullptr, sse ? dsse : nullptr, dcnt,
                                   dflags, dskip, flags, st);
@@ -317,14 +315,18 @@ extern "C" int mod16_et_static_batch_f32(mod16_ctx* ctx, const float* const* dri
                                      out_total, observed, weights, sse, count, flags, where, stream);
 }
 
+// the problem's cached objective graphs (plain and fold)
+static void batch_drop_graphs(mod16_batch* b) {
+    b->graph.drop();
+    b->fgraph.drop();
+    b->last = nullptr;
+}
+
 extern "C" int mod16_static_batch_destroy(mod16_batch* b) {
     if (!b) return MOD16_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    if (b->exec) (void)hipGraphExecDestroy(b->exec);
-    if (b->graph) (void)hipGraphDestroy(b->graph);
-    if (b->fexec) (void)hipGraphExecDestroy(b->fexec);
-    if (b->fgraph) (void)hipGraphDestroy(b->fgraph);
+    batch_drop_graphs(b);
     if (b->label) (void)hipFree(b->label);
     if (b->dcode) (void)hipFree(b->dcode);
     if (b->hcode) (void)hipHostFree(b->hcode);
@@ -348,7 +350,7 @@ static StaticBatchArgs<T> batch_args(const mod16_batch* b) {
     for (int k = 0; k < 14; ++k) a.drv[k] = static_cast<const T*>(b->drv[k]);
     a.dense_drv = b->dense_drv;
     a.n = b->n;
-    a.params = static_cast<const T*>(b->dparams);
+    a.params = static_cast<const T*>(b->own.params);
     return a;
 }
 
@@ -379,24 +381,14 @@ static int batch_bind(mod16_ctx* ctx, const T* const* drivers, const int64_t* ds
     b->gx = (int)((n + kBlock - 1) / kBlock);
     int rc = [&]() -> int {
         HIPCHK(ctx, hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
-        const size_t per_arr = (((size_t)n * sizeof(T)) + 255) / 256 * 256;
+        const size_t per_arr = align256((size_t)n * sizeof(T));
         for (int k = 0; k < 14; ++k) if (dstride[k]) b->dense_drv |= 1u << k;
-        // device memory that cannot be had is MOD16_ERR_NOMEM, not a HIP error
-        auto dmalloc = [&](void** p, size_t bytes, const char* what) -> int {
-            if (hipMalloc(p, bytes) == hipSuccess) return MOD16_OK;
-            (void)hipGetLastError();
-            *p = nullptr;
-            ctx->err = std::string("mod16_static_batch_bind: device memory for ") + what;
-            return MOD16_ERR_NOMEM;
-        };
-#define MOD16_DMALLOC(p, bytes, what) do { int r_ = dmalloc(reinterpret_cast<void**>(p), bytes, what); if (r_ != MOD16_OK) return r_; } while (0)
+        int r;
         if (where == MOD16_HOST) {
-            MOD16_DMALLOC(&b->owned, per_arr * 16, "the resident drivers");
+            r = dev_alloc(ctx, &b->owned, per_arr * 16, "mod16_static_batch_bind: device memory for the resident drivers");
+            if (r != MOD16_OK) return r;
             char* base = static_cast<char*>(b->owned);
-            for (int k = 0; k < 14; ++k) {
-                HIPCHK(ctx, hipMemcpyAsync(base + per_arr * k, drivers[k], sizeof(T) * (dstride[k] ? n : 1), hipMemcpyHostToDevice, b->st));
-                b->drv[k] = base + per_arr * k;
-            }
+            HIPCHK(ctx, upload_drivers(drivers, b->dense_drv, n, base, per_arr, b->st, b->drv));
             if (observed) {
                 HIPCHK(ctx, hipMemcpyAsync(base + per_arr * 14, observed, sizeof(T) * n, hipMemcpyHostToDevice, b->st));
                 b->obs = base + per_arr * 14;
@@ -410,28 +402,18 @@ static int batch_bind(mod16_ctx* ctx, const T* const* drivers, const int64_t* ds
             b->obs = observed;
             b->wts = weights;
         }
-        // evaluation workspace
+        // evaluation workspace: the per-draw part for max_draws (the per-block part: batch_eval_ws)
         const int64_t D = max_draws;
-        auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-        // (the per-block partials of the FAST objective -- draws x blocks x 20 bytes, 3.2 GB at 4096
-        // draws x 10 M pixels -- are NOT part of this: batch_eval_ws sizes them for the draws an
-        // evaluation actually brings; an EXACT problem never has them)
-        const size_t sz_par = al((size_t)D * 11 * sizeof(T)), sz_p16 = al((size_t)D * kPar16 * 8),
-                     sz_d = al((size_t)D * 8), sz_redo = al((size_t)D * 40), sz_u = al((size_t)D * 4);
-        MOD16_DMALLOC(&b->ws, sz_par + sz_p16 + 2 * sz_d + sz_redo + 2 * sz_u, "the evaluation workspace");
-        char* cur = static_cast<char*>(b->ws);
-        auto take = [&](size_t x) { char* p = cur; cur += x; return p; };
-        b->dparams = take(sz_par);
-        b->par16 = reinterpret_cast<double*>(take(sz_p16));
-        b->dsse = reinterpret_cast<double*>(take(sz_d));
-        b->dcnt = reinterpret_cast<double*>(take(sz_d));
-        b->redo = reinterpret_cast<double*>(take(sz_redo));
-        b->any_draw = reinterpret_cast<unsigned*>(take(sz_u));
-        b->dflags = reinterpret_cast<unsigned*>(take(sz_u));
+        const size_t per_draw = eval_layout_draws(D, sizeof(T), nullptr, nullptr);
+        r = dev_alloc(ctx, &b->ws, per_draw + align256((size_t)D * sizeof(unsigned)), "mod16_static_batch_bind: device memory for the evaluation workspace");
+        if (r != MOD16_OK) return r;
+        eval_layout_draws(D, sizeof(T), b->ws, &b->own);
+        b->dflags = reinterpret_cast<unsigned*>(static_cast<char*>(b->ws) + per_draw);
         HIPCHK(ctx, hipHostMalloc(&b->hparams, (size_t)D * 11 * sizeof(T)));
         HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&b->hout), (size_t)D * 16));
         // the pixels outside the domain of the FAST arithmetic: marked once, listed in ascending order
-        MOD16_DMALLOC(&b->skip, (size_t)n, "the domain mask");
+        r = dev_alloc(ctx, &b->skip, (size_t)n, "mod16_static_batch_bind: device memory for the domain mask");
+        if (r != MOD16_OK) return r;
         StaticBatchArgs<T> a = batch_args<T>(b);
         hipLaunchKernelGGL((static_domain_kernel<T>), dim3((unsigned)b->gx), dim3(kBlock), 0, b->st, a, b->skip);
         HIPCHK(ctx, hipGetLastError());
@@ -442,8 +424,8 @@ static int batch_bind(mod16_ctx* ctx, const T* const* drivers, const int64_t* ds
         for (int64_t i = 0; i < n; ++i) if (mask[(size_t)i]) list.push_back(i);
         b->nlist = (int64_t)list.size();
         if (b->nlist) {
-            MOD16_DMALLOC(&b->list, sizeof(int64_t) * list.size(), "the list of pixels outside the domain");
-#undef MOD16_DMALLOC
+            r = dev_alloc(ctx, &b->list, sizeof(int64_t) * list.size(), "mod16_static_batch_bind: device memory for the list of pixels outside the domain");
+            if (r != MOD16_OK) return r;
             HIPCHK(ctx, hipMemcpy(b->list, list.data(), sizeof(int64_t) * list.size(), hipMemcpyHostToDevice));
         }
         return MOD16_OK;
@@ -477,18 +459,6 @@ extern "C" int mod16_static_batch_info(const mod16_batch* b, int64_t* n, int64_t
     return MOD16_OK;
 }
 
-// the problem's cached objective graphs (plain and fold)
-static void batch_drop_graphs(mod16_batch* b) {
-    if (b->exec) (void)hipGraphExecDestroy(b->exec);
-    if (b->graph) (void)hipGraphDestroy(b->graph);
-    if (b->fexec) (void)hipGraphExecDestroy(b->fexec);
-    if (b->fgraph) (void)hipGraphDestroy(b->fgraph);
-    b->exec = b->fexec = b->last_exec = nullptr;
-    b->graph = b->fgraph = nullptr;
-    b->graph_ndraw = b->fgraph_ndraw = -1;
-}
-
-// the kernels of one objective evaluation (FAST arithmetic), enqueued on b->st
 // The per-block partials and flags of the FAST objective for `ndraw` draws (grown to the next power
 // of two, at most max_draws; a captured graph holds the old addresses: dropped with them).
 static int batch_eval_ws(mod16_batch* b, int64_t ndraw) {
@@ -502,17 +472,23 @@ static int batch_eval_ws(mod16_batch* b, int64_t ndraw) {
     if (b->eval_ws) HIPCHK(ctx, hipFree(b->eval_ws));
     b->eval_ws = nullptr;
     b->eval_draws = 0;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t sz_part = al((size_t)want * b->gx * 16), sz_any = al((size_t)want * b->gx * 4);
-    if (hipMalloc(&b->eval_ws, sz_part + sz_any) != hipSuccess) {
-        (void)hipGetLastError();
-        b->eval_ws = nullptr;
-        return fail(ctx, MOD16_ERR_NOMEM, "mod16_static_batch_objective: device memory for the per-block partials of this many draws");
-    }
-    b->partial = reinterpret_cast<double*>(b->eval_ws);
-    b->any_gs = reinterpret_cast<unsigned*>(static_cast<char*>(b->eval_ws) + sz_part);
+    int rc = dev_alloc(ctx, &b->eval_ws, eval_layout_blocks(want, b->gx, nullptr, nullptr),
+                       "mod16_static_batch_objective: device memory for the per-block partials of this many draws");
+    if (rc != MOD16_OK) return rc;
+    eval_layout_blocks(want, b->gx, b->eval_ws, &b->own);
     b->eval_draws = want;
     return MOD16_OK;
+}
+
+// room for `need` bytes of rows (the workspace only grows)
+static int rows_reserve(mod16_batch* b, size_t need, const char* what) {
+    if (b->rows_bytes >= need) return MOD16_OK;
+    if (b->rows) HIPCHK(b->ctx, hipFree(b->rows));
+    b->rows = nullptr;
+    b->rows_bytes = 0;
+    int rc = dev_alloc(b->ctx, &b->rows, need, what);
+    if (rc == MOD16_OK) b->rows_bytes = need;
+    return rc;
 }
 
 // code: NULL (plain draws) or the fold code of every draw (mod16_static_batch_objective_folds, checked)
@@ -525,57 +501,36 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const
     if (ndraw == 0) return MOD16_OK;
     HIPCHK(ctx, hipSetDevice(b->device));
     memcpy(b->hparams, params, sizeof(T) * (size_t)ndraw * 11);
-    HIPCHK(ctx, hipMemcpyAsync(b->dparams, b->hparams, sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
+    HIPCHK(ctx, hipMemcpyAsync(b->own.params, b->hparams, sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
     if (code) {
         memcpy(b->hcode, code, sizeof(int32_t) * (size_t)ndraw);
         HIPCHK(ctx, hipMemcpyAsync(b->dcode, b->hcode, sizeof(int32_t) * (size_t)ndraw, hipMemcpyHostToDevice, b->st));
     }
     if (b->flags & MOD16_MATH_EXACT) {
         // reference order: rows into a workspace, then the residuals' sums (the kernels of the unbound call)
-        const size_t need = sizeof(T) * (size_t)ndraw * (size_t)b->n;
-        if (b->rows_bytes < need) {
-            if (b->rows) HIPCHK(ctx, hipFree(b->rows));
-            b->rows = nullptr;
-            b->rows_bytes = 0;
-            if (hipMalloc(&b->rows, need) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(ctx, MOD16_ERR_NOMEM, "mod16_static_batch_objective: device memory for the [ndraw][n] rows");
-            }
-            b->rows_bytes = need;
-        }
+        int rc = rows_reserve(b, sizeof(T) * (size_t)ndraw * (size_t)b->n, "mod16_static_batch_objective: device memory for the [ndraw][n] rows");
+        if (rc != MOD16_OK) return rc;
         StaticBatchArgs<T> a = batch_args<T>(b);
         a.out[2] = static_cast<T*>(b->rows);
-        int rc = static_batch_rows<T>(ctx, a, ndraw, static_cast<const T*>(b->obs), static_cast<const T*>(b->wts), b->dsse, b->dcnt,
-                                      b->dflags, b->skip, b->flags, b->st, true);
+        rc = static_batch_rows<T>(ctx, a, ndraw, static_cast<const T*>(b->obs), static_cast<const T*>(b->wts), b->own.sse, b->own.cnt,
+                                  b->dflags, b->skip, b->flags, b->st, true);
         if (rc != MOD16_OK) return rc;
     } else {
         int rc = batch_eval_ws(b, ndraw);
         if (rc != MOD16_OK) return rc;
-        // plain and fold calls keep a graph each: the launches differ (kernels, the codes' address)
-        hipGraph_t& graph = code ? b->fgraph : b->graph;
-        hipGraphExec_t& exec = code ? b->fexec : b->exec;
-        int64_t& graph_ndraw = code ? b->fgraph_ndraw : b->graph_ndraw;
-        if (graph_ndraw != ndraw) {             // (re)capture: the kernels' arguments hold the number of draws
-            if (exec) (void)hipGraphExecDestroy(exec);
-            if (graph) (void)hipGraphDestroy(graph);
-            if (b->last_exec == exec) b->last_exec = nullptr;
-            exec = nullptr;
-            graph = nullptr;
-            graph_ndraw = -1;
-            EvalWs w = batch_own_ws(b);
+        CachedGraph& g = code ? b->fgraph : b->graph;       // (plain and fold calls keep a graph each)
+        if (g.key != ndraw) {                   // (re)capture: the kernels' arguments hold the number of draws
+            if (b->last == &g) b->last = nullptr;
+            EvalWs w = b->own;
             w.code = code ? b->dcode : nullptr;
-            HIPCHK(ctx, hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
-            batch_objective_launches<T>(b, w, ndraw);
-            hipError_t e = hipStreamEndCapture(b->st, &graph);
-            HIPCHK(ctx, e);
-            HIPCHK(ctx, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            graph_ndraw = ndraw;
+            rc = g.capture(ctx, b->st, ndraw, [&] { batch_objective_launches<T>(b, w, ndraw); });
+            if (rc != MOD16_OK) return rc;
         }
-        HIPCHK(ctx, hipGraphLaunch(exec, b->st));
-        b->last_exec = exec;
+        HIPCHK(ctx, hipGraphLaunch(g.exec, b->st));
+        b->last = &g;
     }
-    HIPCHK(ctx, hipMemcpyAsync(b->hout, b->dsse, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
-    HIPCHK(ctx, hipMemcpyAsync(b->hout + b->max_draws, b->dcnt, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
+    HIPCHK(ctx, hipMemcpyAsync(b->hout, b->own.sse, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
+    HIPCHK(ctx, hipMemcpyAsync(b->hout + b->max_draws, b->own.cnt, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
     HIPCHK(ctx, hipStreamSynchronize(b->st));
     memcpy(sse, b->hout, sizeof(double) * (size_t)ndraw);
     memcpy(count, b->hout + b->max_draws, sizeof(double) * (size_t)ndraw);
@@ -609,11 +564,10 @@ extern "C" int mod16_static_batch_set_folds(mod16_batch* b, const uint8_t* label
         if (!seen[(size_t)f]) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: a fold without any pixel");
     HIPCHK(ctx, hipSetDevice(b->device));
     int rc = [&]() -> int {
-        if (hipMalloc(reinterpret_cast<void**>(&b->label), (size_t)b->n) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&b->dcode), sizeof(int32_t) * (size_t)b->max_draws) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, MOD16_ERR_NOMEM, "mod16_static_batch_set_folds: device memory for the labels");
-        }
+        const char* what = "mod16_static_batch_set_folds: device memory for the labels";
+        int r = dev_alloc(ctx, &b->label, (size_t)b->n, what);
+        if (r == MOD16_OK) r = dev_alloc(ctx, &b->dcode, sizeof(int32_t) * (size_t)b->max_draws, what);
+        if (r != MOD16_OK) return r;
         HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&b->hcode), sizeof(int32_t) * (size_t)b->max_draws));
         HIPCHK(ctx, hipMemcpyAsync(b->label, labels, (size_t)b->n, hipMemcpyHostToDevice, b->st));
         HIPCHK(ctx, hipStreamSynchronize(b->st));
@@ -654,28 +608,20 @@ static int batch_rows(mod16_batch* b, const T* params, int64_t ndraw, T* out_day
     if (ndraw == 0) return MOD16_OK;
     HIPCHK(ctx, hipSetDevice(b->device));
     T* const host_out[3] = {out_day, out_night, out_total};
-    const size_t per_out = (sizeof(T) * (size_t)ndraw * (size_t)b->n + 255) / 256 * 256;
-    const size_t need = per_out * ((out_day != nullptr) + (out_night != nullptr) + (out_total != nullptr));
-    if (b->rows_bytes < need) {
-        if (b->rows) HIPCHK(ctx, hipFree(b->rows));
-        b->rows = nullptr;
-        b->rows_bytes = 0;
-        if (hipMalloc(&b->rows, need) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, MOD16_ERR_NOMEM, "mod16_static_batch_rows: device memory for the [ndraw][n] rows");
-        }
-        b->rows_bytes = need;
-    }
+    const size_t per_out = sizeof(T) * (size_t)ndraw * (size_t)b->n;
+    int rc = rows_reserve(b, align256(per_out) * ((out_day != nullptr) + (out_night != nullptr) + (out_total != nullptr)),
+                          "mod16_static_batch_rows: device memory for the [ndraw][n] rows");
+    if (rc != MOD16_OK) return rc;
     memcpy(b->hparams, params, sizeof(T) * (size_t)ndraw * 11);
-    HIPCHK(ctx, hipMemcpyAsync(b->dparams, b->hparams, sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
+    HIPCHK(ctx, hipMemcpyAsync(b->own.params, b->hparams, sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
     StaticBatchArgs<T> a = batch_args<T>(b);
-    char* cur = static_cast<char*>(b->rows);
+    Carver c(b->rows);
     for (int k = 0; k < 3; ++k)
-        if (host_out[k]) { a.out[k] = reinterpret_cast<T*>(cur); cur += per_out; }
-    int rc = static_batch_rows<T>(ctx, a, ndraw, nullptr, nullptr, nullptr, nullptr, b->dflags, b->skip, b->flags, b->st, true);
+        if (host_out[k]) a.out[k] = c.take<T>(per_out);
+    rc = static_batch_rows<T>(ctx, a, ndraw, nullptr, nullptr, nullptr, nullptr, b->dflags, b->skip, b->flags, b->st, true);
     if (rc != MOD16_OK) return rc;
     for (int k = 0; k < 3; ++k)
-        if (host_out[k]) HIPCHK(ctx, hipMemcpyAsync(host_out[k], a.out[k], sizeof(T) * (size_t)ndraw * (size_t)b->n, hipMemcpyDeviceToHost, b->st));
+        if (host_out[k]) HIPCHK(ctx, hipMemcpyAsync(host_out[k], a.out[k], per_out, hipMemcpyDeviceToHost, b->st));
     HIPCHK(ctx, hipStreamSynchronize(b->st));
     return MOD16_OK;
 }
@@ -694,13 +640,13 @@ extern "C" int mod16_static_batch_rows(mod16_batch* b, const void* params, int64
 // objective call, plain or fold, on the problem's stream, HIP events): what bench.py puts next to the
 // wall-clock rate of the call
 extern "C" int mod16_static_batch_time(mod16_batch* b, int launches, float* ms) {
-    if (!b || !ms || launches <= 0 || !b->last_exec) return MOD16_ERR_ARG;
+    if (!b || !ms || launches <= 0 || !b->last) return MOD16_ERR_ARG;
     MOD16_LOCK(b->ctx);
     if (hipSetDevice(b->device) != hipSuccess) return MOD16_ERR_HIP;
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return MOD16_ERR_HIP;
     bool ok = hipEventRecord(e0, b->st) == hipSuccess;
-    for (int i = 0; i < launches && ok; ++i) ok = hipGraphLaunch(b->last_exec, b->st) == hipSuccess;
+    for (int i = 0; i < launches && ok; ++i) ok = hipGraphLaunch(b->last->exec, b->st) == hipSuccess;
     ok = ok && hipEventRecord(e1, b->st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
     float t = 0.f;
     ok = ok && hipEventElapsedTime(&t, e0, e1) == hipSuccess;

@@ -135,6 +135,39 @@ static int fail(mod16_ctx* ctx, int code, const char* msg) {
     return code;
 }
 
+// Device memory that cannot be had is MOD16_ERR_NOMEM with `what` as the message, not a HIP error:
+// *p is NULL and the runtime's last error is cleared, so that the next hipGetLastError() behind a
+// launch on this thread reports its own launch. (dev_alloc_async: stream-ordered, freed with hipFreeAsync.)
+static int dev_alloc_failed(mod16_ctx* ctx, void** p, const char* what) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return fail(ctx, MOD16_ERR_NOMEM, what);
+}
+template <typename P>
+static int dev_alloc(mod16_ctx* ctx, P** p, size_t bytes, const char* what) {
+    void** v = reinterpret_cast<void**>(p);
+    return hipMalloc(v, bytes) == hipSuccess ? MOD16_OK : dev_alloc_failed(ctx, v, what);
+}
+template <typename P>
+static int dev_alloc_async(mod16_ctx* ctx, P** p, size_t bytes, hipStream_t st, const char* what) {
+    void** v = reinterpret_cast<void**>(p);
+    return hipMallocAsync(v, bytes, st) == hipSuccess ? MOD16_OK : dev_alloc_failed(ctx, v, what);
+}
+
+// One allocation carved into arrays: pieces of whole 256-byte lines taken in order from `base`.
+// With base NULL the pointers are NULL and `used` is the size to allocate.
+static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+struct Carver {
+    char* base;
+    size_t used = 0;
+    explicit Carver(void* b = nullptr) : base(static_cast<char*>(b)) {}
+    template <typename T> T* take(size_t bytes) {
+        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += align256(bytes);
+        return p;
+    }
+};
+
 // ------------------------------------------------------------------ launch
 template <typename T> static const T* ctx_lut(const mod16_ctx* ctx);
 template <> const double* ctx_lut<double>(const mod16_ctx* ctx) { return ctx->lut64; }

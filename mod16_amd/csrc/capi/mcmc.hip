@@ -14,21 +14,14 @@ struct mod16_mcmc {
     void* trace = nullptr;                // hist, xtr, tr_ll, tr_lp, tr_acc for `cap` steps
     int64_t cap = 0, steps = 0;
     int segment = kMcmcSegment;
-    hipGraph_t g_full = nullptr, g_rem = nullptr;
-    hipGraphExec_t e_full = nullptr, e_rem = nullptr;
-    int64_t rem_len = 0;                  // steps of the remainder graph held in e_rem
+    CachedGraph full, rem;                // `segment` steps, and the last run's remainder; key = steps
     bool broken = false;                  // a run failed: the device step counters and `steps` may disagree
     bool counted = false;                 // in the problem's count of samplers
 };
 
 static void mcmc_drop_graphs(mod16_mcmc* m) {
-    if (m->e_full) (void)hipGraphExecDestroy(m->e_full);
-    if (m->g_full) (void)hipGraphDestroy(m->g_full);
-    if (m->e_rem) (void)hipGraphExecDestroy(m->e_rem);
-    if (m->g_rem) (void)hipGraphDestroy(m->g_rem);
-    m->e_full = m->e_rem = nullptr;
-    m->g_full = m->g_rem = nullptr;
-    m->rem_len = 0;
+    m->full.drop();
+    m->rem.drop();
 }
 
 extern "C" int mod16_mcmc_destroy(mod16_mcmc* m) {
@@ -45,17 +38,10 @@ extern "C" int mod16_mcmc_destroy(mod16_mcmc* m) {
     return MOD16_OK;
 }
 
-static int mcmc_nomem(mod16_ctx* ctx, const char* what) {
-    (void)hipGetLastError();
-    return fail(ctx, MOD16_ERR_NOMEM, what);
-}
-
-static size_t mcmc_al(size_t x) { return (x + 255) / 256 * 256; }
-
 // the trace arrays of `cap` steps inside one allocation at `base` (NULL: sizes only)
 static size_t mcmc_trace_layout(const McmcArgs& a, int64_t cap, char* base, McmcArgs* out) {
-    const size_t per_x = mcmc_al((size_t)cap * a.chains * a.d * 8), per_s = mcmc_al((size_t)cap * a.chains * 8),
-                 per_b = mcmc_al((size_t)cap * a.chains);
+    const size_t per_x = align256((size_t)cap * a.chains * a.d * 8), per_s = align256((size_t)cap * a.chains * 8),
+                 per_b = align256((size_t)cap * a.chains);
     if (out) {
         out->hist = reinterpret_cast<double*>(base);
         out->xtr = reinterpret_cast<double*>(base + per_x);
@@ -72,8 +58,8 @@ static int mcmc_reserve(mod16_mcmc* m, int64_t need) {
     if (need <= m->cap) return MOD16_OK;
     mod16_ctx* ctx = m->b->ctx;
     void* nt = nullptr;
-    if (hipMalloc(&nt, mcmc_trace_layout(m->a, need, nullptr, nullptr)) != hipSuccess)
-        return mcmc_nomem(ctx, "mod16_mcmc_run: device memory for the history and trace of this many steps");
+    int rc = dev_alloc(ctx, &nt, mcmc_trace_layout(m->a, need, nullptr, nullptr), "mod16_mcmc_run: device memory for the history and trace of this many steps");
+    if (rc != MOD16_OK) return rc;
     McmcArgs na = m->a;
     mcmc_trace_layout(m->a, need, static_cast<char*>(nt), &na);
     HIPCHK(ctx, hipStreamSynchronize(m->b->st));
@@ -94,22 +80,16 @@ static int mcmc_reserve(mod16_mcmc* m, int64_t need) {
 }
 
 // `steps` steps as one graph on the problem's stream: propose -> objective -> accept, a single chain
-static int mcmc_capture(mod16_mcmc* m, int64_t steps, hipGraph_t* g, hipGraphExec_t* e) {
+static int mcmc_capture(mod16_mcmc* m, int64_t steps, CachedGraph* g) {
     mod16_batch* b = m->b;
-    mod16_ctx* ctx = b->ctx;
     const unsigned gc = (unsigned)((m->a.chains + kBlock - 1) / kBlock);
-    HIPCHK(ctx, hipStreamBeginCapture(b->st, hipStreamCaptureModeThreadLocal));
-    for (int64_t s = 0; s < steps; ++s) {
-        hipLaunchKernelGGL(mcmc_propose_kernel, dim3(gc), dim3(kBlock), 0, b->st, m->a);
-        batch_objective_launches<double>(b, m->w, m->a.chains);
-        hipLaunchKernelGGL(mcmc_accept_kernel, dim3(gc), dim3(kBlock), 0, b->st, m->a);
-    }
-    const hipError_t le = hipGetLastError();
-    const hipError_t ce = hipStreamEndCapture(b->st, g);
-    HIPCHK(ctx, le);
-    HIPCHK(ctx, ce);
-    HIPCHK(ctx, hipGraphInstantiate(e, *g, nullptr, nullptr, 0));
-    return MOD16_OK;
+    return g->capture(b->ctx, b->st, steps, [&] {
+        for (int64_t s = 0; s < steps; ++s) {
+            hipLaunchKernelGGL(mcmc_propose_kernel, dim3(gc), dim3(kBlock), 0, b->st, m->a);
+            batch_objective_launches<double>(b, m->w, m->a.chains);
+            hipLaunchKernelGGL(mcmc_accept_kernel, dim3(gc), dim3(kBlock), 0, b->st, m->a);
+        }
+    });
 }
 
 static int mcmc_check_spec(mod16_ctx* ctx, const mod16_batch* b, const mod16_mcmc_spec* s, int ngroups, const int32_t* fold) {
@@ -210,47 +190,44 @@ static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, int ngroups, co
     a.scaling0 = s->scaling;
     a.lamb0 = s->lamb;
     rc = [&]() -> int {
-        // per-chain state
-        const size_t sd = mcmc_al((size_t)C * d * 8), s1 = mcmc_al((size_t)C * 8), sx0 = mcmc_al(init.size() * 8);
-        if (hipMalloc(&m->state, 3 * sd + 7 * s1 + mcmc_al((size_t)C * 4) + sx0) != hipSuccess)
-            return mcmc_nomem(ctx, "mod16_mcmc_create: device memory for the chains' state");
-        char* cur = static_cast<char*>(m->state);
-        auto take = [&](size_t x) { char* p = cur; cur += x; return p; };
-        a.y = reinterpret_cast<double*>(take(sd));
-        a.yp = reinterpret_cast<double*>(take(sd));
-        a.xc = reinterpret_cast<double*>(take(sd));
-        a.logp = reinterpret_cast<double*>(take(s1));
-        a.loglik = reinterpret_cast<double*>(take(s1));
-        a.lprior_p = reinterpret_cast<double*>(take(s1));
-        a.scaling = reinterpret_cast<double*>(take(s1));
-        a.lamb = reinterpret_cast<double*>(take(s1));
-        a.t = reinterpret_cast<int64_t*>(take(s1));
-        uint64_t* dkey = reinterpret_cast<uint64_t*>(take(s1));
-        a.key = dkey;
-        double* dx0 = reinterpret_cast<double*>(take(sx0));
-        a.acc = reinterpret_cast<int*>(take(mcmc_al((size_t)C * 4)));
-        // the objective's workspace for C draws: the sampler's own (see EvalWs)
-        const size_t sp = mcmc_al((size_t)C * 11 * 8), s16 = mcmc_al((size_t)C * kPar16 * 8),
-                     spart = mcmc_al((size_t)C * b->gx * 16), sany = mcmc_al((size_t)C * b->gx * 4),
-                     su = mcmc_al((size_t)C * 4), sredo = mcmc_al((size_t)C * 40);
-        if (hipMalloc(&m->eval, sp + s16 + spart + sany + su + sredo + 2 * s1 + (fold ? su : 0)) != hipSuccess)
-            return mcmc_nomem(ctx, "mod16_mcmc_create: device memory for the objective's workspace");
-        cur = static_cast<char*>(m->eval);
-        a.params = reinterpret_cast<double*>(take(sp));
-        m->w.params = a.params;
-        m->w.par16 = reinterpret_cast<double*>(take(s16));
-        m->w.partial = reinterpret_cast<double*>(take(spart));
-        m->w.any_gs = reinterpret_cast<unsigned*>(take(sany));
-        m->w.any_draw = reinterpret_cast<unsigned*>(take(su));
-        m->w.redo = reinterpret_cast<double*>(take(sredo));
-        m->w.sse = reinterpret_cast<double*>(take(s1));
-        m->w.cnt = reinterpret_cast<double*>(take(s1));
+        // per-chain state: sized with a NULL base, then placed
+        uint64_t* dkey = nullptr;
+        double* dx0 = nullptr;
+        auto state = [&](void* base) {
+            Carver c(base);
+            const size_t sd = (size_t)C * d * 8, s1 = (size_t)C * 8;
+            a.y = c.take<double>(sd);
+            a.yp = c.take<double>(sd);
+            a.xc = c.take<double>(sd);
+            a.logp = c.take<double>(s1);
+            a.loglik = c.take<double>(s1);
+            a.lprior_p = c.take<double>(s1);
+            a.scaling = c.take<double>(s1);
+            a.lamb = c.take<double>(s1);
+            a.t = c.take<int64_t>(s1);
+            a.key = dkey = c.take<uint64_t>(s1);
+            dx0 = c.take<double>(init.size() * 8);
+            a.acc = c.take<int>((size_t)C * 4);
+            return c.used;
+        };
+        int r = dev_alloc(ctx, &m->state, state(nullptr), "mod16_mcmc_create: device memory for the chains' state");
+        if (r != MOD16_OK) return r;
+        state(m->state);
+        // the objective's workspace for C draws, both parts: the sampler's own (see EvalWs); behind it
+        // the groups' TRAIN codes, constant for the sampler's life and read by its graphs
+        const size_t per_draw = eval_layout_draws(C, 8, nullptr, nullptr), per_block = eval_layout_blocks(C, b->gx, nullptr, nullptr);
+        r = dev_alloc(ctx, &m->eval, per_draw + per_block + (fold ? align256((size_t)C * 4) : 0), "mod16_mcmc_create: device memory for the objective's workspace");
+        if (r != MOD16_OK) return r;
+        char* ev = static_cast<char*>(m->eval);
+        eval_layout_draws(C, 8, ev, &m->w);
+        eval_layout_blocks(C, b->gx, ev + per_draw, &m->w);
+        a.params = static_cast<double*>(m->w.params);
         a.sse = m->w.sse;
         a.cnt = m->w.cnt;
         hipStream_t st = b->st;
         HIPCHK(ctx, hipMemcpyAsync(dkey, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, st));
-        if (fold) {     // the groups' TRAIN codes: constant for the sampler's life, read by its graphs
-            int32_t* dcode = reinterpret_cast<int32_t*>(take(su));
+        if (fold) {
+            int32_t* dcode = reinterpret_cast<int32_t*>(ev + per_draw + per_block);
             HIPCHK(ctx, hipMemcpyAsync(dcode, codes.data(), codes.size() * 4, hipMemcpyHostToDevice, st));
             m->w.code = dcode;
         }
@@ -303,20 +280,9 @@ static int mcmc_run(mod16_mcmc* m, int64_t steps, float* ms) {
     int rc = mcmc_reserve(m, m->steps + steps);
     if (rc != MOD16_OK) return rc;
     const int64_t K = m->segment, full = steps / K, rem = steps % K;
-    if (full && !m->e_full) {
-        rc = mcmc_capture(m, K, &m->g_full, &m->e_full);
-        if (rc != MOD16_OK) return rc;
-    }
-    if (rem && m->rem_len != rem) {
-        if (m->e_rem) (void)hipGraphExecDestroy(m->e_rem);
-        if (m->g_rem) (void)hipGraphDestroy(m->g_rem);
-        m->e_rem = nullptr;
-        m->g_rem = nullptr;
-        m->rem_len = 0;
-        rc = mcmc_capture(m, rem, &m->g_rem, &m->e_rem);
-        if (rc != MOD16_OK) return rc;
-        m->rem_len = rem;
-    }
+    if (full && m->full.key != K) rc = mcmc_capture(m, K, &m->full);
+    if (rc == MOD16_OK && rem && m->rem.key != rem) rc = mcmc_capture(m, rem, &m->rem);
+    if (rc != MOD16_OK) return rc;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ms) {
         HIPCHK(ctx, hipEventCreate(&e0));
@@ -324,8 +290,8 @@ static int mcmc_run(mod16_mcmc* m, int64_t steps, float* ms) {
         HIPCHK(ctx, hipEventRecord(e0, b->st));
     }
     bool ok = true;
-    for (int64_t i = 0; i < full && ok; ++i) ok = hipGraphLaunch(m->e_full, b->st) == hipSuccess;
-    if (rem && ok) ok = hipGraphLaunch(m->e_rem, b->st) == hipSuccess;
+    for (int64_t i = 0; i < full && ok; ++i) ok = hipGraphLaunch(m->full.exec, b->st) == hipSuccess;
+    if (rem && ok) ok = hipGraphLaunch(m->rem.exec, b->st) == hipSuccess;
     if (ms) ok = ok && hipEventRecord(e1, b->st) == hipSuccess;
     ok = hipStreamSynchronize(b->st) == hipSuccess && ok;
     if (ms) {

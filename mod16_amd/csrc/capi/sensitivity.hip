@@ -71,8 +71,8 @@ int sobol_to(mod16_ctx* ctx, double* out, size_t bytes, int where, void* stream,
     if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
     hipStream_t st = ctx->streams[0];
     double* dev = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&dev), bytes) != hipSuccess)
-        return fail(ctx, MOD16_ERR_NOMEM, "mod16_sobol: device memory for the output");
+    int rc = dev_alloc(ctx, &dev, bytes, "mod16_sobol: device memory for the output");
+    if (rc != MOD16_OK) return rc;
     launch(dev, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, st);
@@ -179,24 +179,21 @@ extern "C" int mod16_sobol_analyze_f64(mod16_ctx* ctx, const double* y, int d, i
         st = ctx->streams[0];
     }
     // one workspace: [Y (HOST only)] stats | sum partials | Gram partials | indices | outputs
-    auto round = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t y_b = where == MOD16_HOST ? round(sizeof(double) * (size_t)n * a.R) : 0;
-    const size_t stats_b = round(sizeof(double) * 4);
-    const size_t sum_b = round(sizeof(double) * kSobolSumBlocks);
-    const size_t gram_b = round(sizeof(double) * (size_t)(resamples + 1) * a.nchunks * a.nent);
-    const size_t idx_b = round(sizeof(double) * (size_t)(resamples + 1) * a.nidx);
-    const size_t out_b = round(sizeof(double) * 2 * a.nidx);
+    double* ydev = nullptr;
+    auto layout = [&](void* base) {
+        Carver c(base);
+        if (where == MOD16_HOST) ydev = c.take<double>(sizeof(double) * (size_t)n * a.R);
+        a.stats = c.take<double>(sizeof(double) * 4);
+        a.sum_partial = c.take<double>(sizeof(double) * kSobolSumBlocks);
+        a.gram = c.take<double>(sizeof(double) * (size_t)(resamples + 1) * a.nchunks * a.nent);
+        a.idx = c.take<double>(sizeof(double) * (size_t)(resamples + 1) * a.nidx);
+        a.out = c.take<double>(sizeof(double) * 2 * a.nidx);
+        return c.used;
+    };
     char* ws = nullptr;
-    if (hipMallocAsync(reinterpret_cast<void**>(&ws), y_b + stats_b + sum_b + gram_b + idx_b + out_b, st) != hipSuccess)
-        return fail(ctx, MOD16_ERR_NOMEM, "mod16_sobol_analyze_f64: device memory for the workspace");
-    char* at = ws;
-    auto take = [&](size_t b) { char* p = at; at += b; return reinterpret_cast<double*>(p); };
-    double* ydev = y_b ? take(y_b) : nullptr;
-    a.stats = take(stats_b);
-    a.sum_partial = take(sum_b);
-    a.gram = take(gram_b);
-    a.idx = take(idx_b);
-    a.out = take(out_b);
+    rc = dev_alloc_async(ctx, &ws, layout(nullptr), st, "mod16_sobol_analyze_f64: device memory for the workspace");
+    if (rc != MOD16_OK) return rc;
+    layout(ws);
     a.y = ydev ? ydev : y;
 
     hipError_t e = hipSuccess;

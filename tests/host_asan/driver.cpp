@@ -317,6 +317,206 @@ static void host_cases(mod16_ctx* ctx, const char* what) {
     printf("host_asan: HOST mode, %s: done\n", what);
 }
 
+// ---- the calibration family under its shadows: a resident problem's workspaces as they grow, the
+// sampler that owns its own, folds, float32 and EXACT problems, DEVICE-mode arrays, many draws
+template <typename T> struct Problem {
+    int64_t n;
+    std::vector<std::vector<T>> drv;
+    std::vector<T> obs, wts;
+    const T* dp[14];
+    int64_t ds[14];
+    explicit Problem(int64_t n_) : n(n_), drv(14, std::vector<T>(n_, T(280))), obs(n_, T(10)), wts(n_, T(1)) {
+        for (int k = 0; k < 14; ++k) { dp[k] = drv[k].data(); ds[k] = 1; }
+        ds[7] = 0;      // a broadcast scalar among the drivers
+    }
+};
+
+static mod16_mcmc_spec sampler_spec(int chains, int segment) {
+    mod16_mcmc_spec s;
+    memset(&s, 0, sizeof s);
+    s.chains = chains;
+    s.nfree = 2;
+    s.index[0] = 4; s.family[0] = MOD16_PRIOR_UNIFORM; s.p0[0] = 0.0; s.p1[0] = 1.0;
+    s.index[1] = 10; s.family[1] = MOD16_PRIOR_LOGNORMAL; s.p0[1] = 0.0; s.p1[1] = 1.0;
+    for (int k = 0; k < 11; ++k) s.fixed[k] = 1.0;
+    s.lamb = 0.8;
+    s.scaling = 0.001;
+    s.tune_target = 1;
+    s.tune_interval = 10;
+    s.tune_steps = 20;
+    s.tune_drop_fraction = 0.5;
+    s.segment = segment;
+    s.seed = 42;
+    return s;
+}
+
+static void calibration_cases(mod16_ctx* ctx) {
+    const int64_t n = 1000, maxd = 300;
+    Problem<double> p(n);
+    std::vector<double> par(maxd * 11, 1.0), sse(maxd), cnt(maxd);
+    float ms = 0;
+    {   // float64, FAST, bound for many more draws than the first calls bring
+        mod16_batch* b = nullptr;
+        OK(mod16_static_batch_bind_f64(ctx, p.dp, p.ds, n, p.obs.data(), p.wts.data(), maxd, MOD16_MATH_FAST, MOD16_HOST, &b));
+        int64_t outside = -1;
+        OK(mod16_static_batch_info(b, nullptr, nullptr, &outside));
+        EXPECT(outside == n);       // (the stand-in's mask lists every pixel: the redo kernels launch)
+        EXPECT(mod16_static_batch_time(b, 1, &ms) == MOD16_ERR_ARG);      // no objective call yet
+        OK(mod16_static_batch_objective(b, par.data(), 7, sse.data(), cnt.data()));
+        // a sampler created BEFORE the problem's per-block workspace grows and run AFTER it: its graphs
+        // must hold its own workspace, not the problem's
+        mod16_mcmc_spec spec = sampler_spec(5, 4);
+        mod16_mcmc *m1 = nullptr, *m2 = nullptr;
+        OK(mod16_mcmc_create(b, &spec, nullptr, &m1));
+        OK(mod16_static_batch_objective(b, par.data(), 100, sse.data(), cnt.data()));    // 64 -> 128 draws: graphs dropped
+        OK(mod16_static_batch_objective(b, par.data(), 7, sse.data(), cnt.data()));      // ... and captured again
+        OK(mod16_static_batch_time(b, 2, &ms));
+        OK(mod16_mcmc_run(m1, 10, &ms));                // two segments and a remainder of 2
+        OK(mod16_static_batch_objective(b, par.data(), maxd, sse.data(), cnt.data()));   // grows to max_draws, not to 512
+        OK(mod16_mcmc_run(m1, 7, nullptr));             // the trace is outgrown (copied over, graphs dropped); remainder 3
+        OK(mod16_mcmc_run(m1, 9, nullptr));             // remainder 1
+        OK(mod16_mcmc_run(m1, 0, nullptr));
+        {
+            const int64_t t0 = 5, count = 12;
+            std::vector<double> x(count * 5 * 2), y(count * 5 * 2), ll(count * 5), lp(count * 5), sc(5), lamb(5);
+            std::vector<uint8_t> acc(count * 5);
+            int64_t steps = -1;
+            OK(mod16_mcmc_read(m1, t0, count, x.data(), y.data(), ll.data(), lp.data(), acc.data(), sc.data(), lamb.data(), &steps));
+            EXPECT(steps == 26);
+            EXPECT(mod16_mcmc_read(m1, 20, 7, x.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == MOD16_ERR_ARG);
+        }
+        // a second sampler (given initial values, the default segment) on the same problem
+        mod16_mcmc_spec spec2 = sampler_spec(3, 0);
+        std::vector<double> x0(3 * 2, 0.5);
+        OK(mod16_mcmc_create(b, &spec2, x0.data(), &m2));
+        OK(mod16_mcmc_run(m2, 70, nullptr));            // one segment of 64 and 6
+        OK(mod16_mcmc_run(m1, 4, nullptr));             // the first one's graphs are its own
+        std::vector<uint8_t> labels(n);
+        for (int64_t i = 0; i < n; ++i) labels[i] = (uint8_t)(i % 3);
+        EXPECT(mod16_static_batch_set_folds(b, labels.data(), 3) == MOD16_ERR_ARG);     // a sampler lives
+        mod16_mcmc* bad = nullptr;
+        x0[3] = -1.0;
+        EXPECT(mod16_mcmc_create(b, &spec2, x0.data(), &bad) == MOD16_ERR_ARG && !bad);  // outside the prior's support
+        spec2.chains = (int)maxd + 1;
+        EXPECT(mod16_mcmc_create(b, &spec2, nullptr, &bad) == MOD16_ERR_ARG && !bad);
+        // two samplers on one problem, destroyed in either order (always before the problem)
+        EXPECT(mod16_mcmc_destroy(m1) == MOD16_OK);
+        EXPECT(mod16_mcmc_destroy(m2) == MOD16_OK);
+        OK(mod16_mcmc_create(b, &spec, nullptr, &m1));
+        spec2 = sampler_spec(3, 7);
+        OK(mod16_mcmc_create(b, &spec2, nullptr, &m2));
+        OK(mod16_mcmc_run(m2, 7, nullptr));             // exactly one segment: no remainder graph
+        EXPECT(mod16_mcmc_destroy(m2) == MOD16_OK);
+        EXPECT(mod16_mcmc_destroy(m1) == MOD16_OK);
+        // folds, now that no sampler lives: plain and fold calls keep a graph each
+        OK(mod16_static_batch_set_folds(b, labels.data(), 3));
+        EXPECT(mod16_static_batch_set_folds(b, labels.data(), 3) == MOD16_ERR_ARG);     // once per problem
+        std::vector<int32_t> code(maxd);
+        for (int64_t d = 0; d < maxd; ++d) code[d] = (int32_t)(d % 3) | ((d & 1) ? MOD16_FOLD_HELDOUT : 0);
+        OK(mod16_static_batch_objective_folds(b, par.data(), 40, code.data(), sse.data(), cnt.data()));
+        OK(mod16_static_batch_objective(b, par.data(), 40, sse.data(), cnt.data()));
+        OK(mod16_static_batch_objective_folds(b, par.data(), 40, code.data(), sse.data(), cnt.data()));
+        OK(mod16_static_batch_objective_folds(b, par.data(), 9, code.data(), sse.data(), cnt.data()));
+        OK(mod16_static_batch_objective(b, par.data(), 40, sse.data(), cnt.data()));
+        OK(mod16_static_batch_time(b, 1, &ms));
+        code[3] = 3;
+        EXPECT(mod16_static_batch_objective_folds(b, par.data(), 9, code.data(), sse.data(), cnt.data()) == MOD16_ERR_ARG);
+        code[3] = 1 | 0x200;
+        EXPECT(mod16_static_batch_objective_folds(b, par.data(), 9, code.data(), sse.data(), cnt.data()) == MOD16_ERR_ARG);
+        code[3] = MOD16_FOLD_HELDOUT;
+        // every fold in one sampler: two groups of four chains
+        int32_t folds[2] = {2, 0};
+        mod16_mcmc_spec spec3 = sampler_spec(4, 3);
+        OK(mod16_mcmc_create_groups(b, &spec3, 2, folds, nullptr, &m1));
+        OK(mod16_mcmc_run(m1, 8, &ms));
+        OK(mod16_static_batch_objective_folds(b, par.data(), maxd, code.data(), sse.data(), cnt.data()));
+        OK(mod16_mcmc_run(m1, 3, nullptr));
+        folds[1] = 2;
+        EXPECT(mod16_mcmc_create_groups(b, &spec3, 2, folds, nullptr, &bad) == MOD16_ERR_ARG && !bad);    // a fold twice
+        folds[1] = 3;
+        EXPECT(mod16_mcmc_create_groups(b, &spec3, 2, folds, nullptr, &bad) == MOD16_ERR_ARG && !bad);
+        EXPECT(mod16_mcmc_destroy(m1) == MOD16_OK);
+        std::vector<double> day(7 * n), total(7 * n);
+        OK(mod16_static_batch_rows(b, par.data(), 7, day.data(), nullptr, total.data()));
+        EXPECT(mod16_static_batch_destroy(b) == MOD16_OK);
+    }
+    {   // float32 (no folds, no sampler), without weights
+        Problem<float> q(n);
+        std::vector<float> par32(16 * 11, 1.0f), rows(5 * n);
+        mod16_batch* b = nullptr;
+        OK(mod16_static_batch_bind_f32(ctx, q.dp, q.ds, n, q.obs.data(), nullptr, 16, MOD16_MATH_FAST, MOD16_HOST, &b));
+        OK(mod16_static_batch_objective(b, par32.data(), 5, sse.data(), cnt.data()));
+        OK(mod16_static_batch_rows(b, par32.data(), 5, nullptr, rows.data(), nullptr));
+        std::vector<uint8_t> labels(n, 0);
+        labels[0] = 1;
+        EXPECT(mod16_static_batch_set_folds(b, labels.data(), 2) == MOD16_ERR_ARG);
+        mod16_mcmc_spec spec = sampler_spec(2, 0);
+        mod16_mcmc* bad = nullptr;
+        EXPECT(mod16_mcmc_create(b, &spec, nullptr, &bad) == MOD16_ERR_ARG && !bad);
+        EXPECT(mod16_static_batch_destroy(b) == MOD16_OK);
+    }
+    {   // EXACT: the rows workspace through objective and through rows, growing
+        std::vector<double> rows(3 * 9 * n);
+        mod16_batch* b = nullptr;
+        OK(mod16_static_batch_bind_f64(ctx, p.dp, p.ds, n, p.obs.data(), p.wts.data(), 16, MOD16_MATH_EXACT, MOD16_HOST, &b));
+        OK(mod16_static_batch_objective(b, par.data(), 3, sse.data(), cnt.data()));
+        OK(mod16_static_batch_objective(b, par.data(), 9, sse.data(), cnt.data()));
+        OK(mod16_static_batch_rows(b, par.data(), 9, rows.data(), rows.data() + 9 * n, rows.data() + 18 * n));
+        OK(mod16_static_batch_rows(b, par.data(), 2, nullptr, rows.data(), nullptr));
+        OK(mod16_static_batch_objective(b, par.data(), 9, sse.data(), cnt.data()));
+        EXPECT(mod16_static_batch_time(b, 1, &ms) == MOD16_ERR_ARG);      // an EXACT problem has no graph
+        EXPECT(mod16_static_batch_destroy(b) == MOD16_OK);
+    }
+    {   // DEVICE mode: the caller's device arrays, bound and unbound
+        const size_t per = ((size_t)n * 8 + 255) / 256 * 256;
+        char* slab = static_cast<char*>(dmalloc(17 * per + 9 * 11 * 8 + 9 * n * 8 + 2 * 9 * 8));
+        const double* dp[14];
+        for (int k = 0; k < 14; ++k) dp[k] = reinterpret_cast<const double*>(slab + k * per);
+        const double* dobs = reinterpret_cast<const double*>(slab + 14 * per);
+        const double* dw = reinterpret_cast<const double*>(slab + 15 * per);
+        mod16_batch* b = nullptr;
+        OK(mod16_static_batch_bind_f64(ctx, dp, p.ds, n, dobs, dw, 9, MOD16_MATH_FAST, MOD16_DEVICE, &b));
+        OK(mod16_static_batch_objective(b, par.data(), 9, sse.data(), cnt.data()));
+        std::vector<double> total(9 * n);
+        OK(mod16_static_batch_rows(b, par.data(), 9, nullptr, nullptr, total.data()));
+        EXPECT(mod16_static_batch_destroy(b) == MOD16_OK);
+        double* dpar = reinterpret_cast<double*>(slab + 17 * per);
+        double* dtotal = dpar + 9 * 11;
+        double* dsse = dtotal + 9 * n;
+        for (unsigned flags : {(unsigned)MOD16_MATH_FAST, (unsigned)MOD16_MATH_EXACT})
+            OK(mod16_et_static_batch_f64(ctx, dp, p.ds, n, dpar, 9, nullptr, nullptr, dtotal, dobs, dw, dsse, dsse + 9, flags, MOD16_DEVICE, nullptr));
+        (void)hipFree(slab);
+    }
+    {   // more draws than one launch takes (32768 block rows): the launches of a call cover them all
+        const int64_t m = 2, ndraw = (int64_t)32768 * 32 + 5;
+        Problem<double> q(m);
+        std::vector<double> many((size_t)ndraw * 11, 1.0), s2(ndraw), c2(ndraw);
+        OK(mod16_et_static_batch_f64(ctx, q.dp, q.ds, m, many.data(), ndraw, nullptr, nullptr, nullptr, q.obs.data(), nullptr, s2.data(),
+                                     c2.data(), MOD16_MATH_FAST, MOD16_HOST, nullptr));
+    }
+    printf("host_asan: calibration family: done\n");
+}
+
+// the Sobol entry points in HOST mode: their workspaces and their release (launch shapes only)
+static void sobol_cases(mod16_ctx* ctx) {
+    const int d = 3;
+    const int64_t n = 64;
+    const double lo[3] = {0.0, 1.0, 2.0}, hi[3] = {1.0, 2.0, 3.0};
+    for (int second = 0; second < 2; ++second) {
+        const int R = second ? 2 * d + 2 : d + 2;
+        std::vector<double> sample(n * R * d), y(n * R), idx(2 * d + d * d), sd(2 * d + d * d);
+        OK(mod16_sobol_sample_f64(ctx, d, lo, hi, n, 0, second, sample.data(), MOD16_HOST, nullptr));
+        double params[11], base[14];
+        for (double& v : params) v = 1.0;
+        for (double& v : base) v = 280.0;
+        const int vary[3] = {0, 3, 5};
+        OK(mod16_sobol_rows_f64(ctx, params, base, vary, lo, hi, d, n, 0, second, y.data(), MOD16_HOST, nullptr));
+        OK(mod16_sobol_analyze_f64(ctx, y.data(), d, n, second, second, second ? 10 : 0, 7, idx.data(), sd.data(), MOD16_HOST, nullptr));
+    }
+    EXPECT(mod16_sobol_sample_f64(ctx, d, lo, hi, n + 1, 0, 0, nullptr, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
+    printf("host_asan: Sobol entry points: done\n");
+}
+
 int main(int argc, char** argv) {
     mod16_ctx* ctx = nullptr;
     EXPECT(mod16_create(3, &ctx) == MOD16_ERR_NO_DEVICE);
@@ -400,6 +600,8 @@ int main(int argc, char** argv) {
         OK(mod16_et_static_batch_f64(ctx, dp, ds, n, par.data(), ndraw, nullptr, nullptr, nullptr, obs.data(), nullptr, sse.data(),
                                      cnt.data(), MOD16_MATH_EXACT, MOD16_HOST, nullptr));
     }
+    calibration_cases(ctx);
+    sobol_cases(ctx);
     EXPECT(mod16_destroy(ctx) == MOD16_OK);
     {   // no page-locked memory for the small calls' buffer: the call is staged instead (and the
         // context stops asking), every entry point that has the small path

@@ -15,8 +15,13 @@
 // and skipped.
 //
 // Compiled as HIP (host only) so that it sees the kernels' own argument structures
-// (StreamArgs, EtArgs, SynthArgs, MethodArgs, RawArgs, StaticArgs: mod16_amd/csrc/*.hpp) instead of
-// copies of them.
+// (StreamArgs, EtArgs, SynthArgs, MethodArgs, RawArgs, StaticArgs, StaticBatchArgs, StaticObjArgs,
+// McmcArgs: mod16_amd/csrc/*.hpp) instead of copies of them.
+//
+// Fresh "device" memory is filled with 0xA5. No kernel runs, so that is what the library reads
+// back: as a double 0xA5A5A5A5A5A5A5A5 is finite (about -2e-127), which mod16_mcmc_create's check
+// of the initial log posterior needs; as a domain mask every byte is set, so a resident problem
+// lists every pixel as outside the FAST domain and the redo kernels always launch.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 
@@ -38,6 +43,7 @@
 #include "../../mod16_amd/csrc/mod16_kernels.hpp"
 #include "../../mod16_amd/csrc/mod16_stream.hpp"
 #include "../../mod16_amd/csrc/mod16_methods.hpp"
+#include "../../mod16_amd/csrc/mod16_mcmc.hpp"
 
 using namespace mod16;
 
@@ -279,7 +285,145 @@ static void shadow_static(const StaticArgs<T>& a, bool pixels, const char* name)
         for (int k = 0; k < 2; ++k) need_arr(a.out[k], true, a.n, "output", name);
 }
 
+// ---- the calibration family (capi/calibration.hip, capi/batch.hpp, capi/mcmc.hip): every extent below
+// is what the kernel indexes, in the kernels' own constants
+static void need_block(dim3 block, const char* name) {
+    if (block.x != (unsigned)kBlock || block.y != 1 || block.z != 1) die("%s: block %u x %u x %u", name, block.x, block.y, block.z);
+}
+// gridDim chunks of `per` items: they cover `count`, and none of them is empty
+static void need_cover(unsigned chunks, int64_t per, int64_t count, const char* what, const char* name) {
+    if (count <= 0 || (int64_t)chunks * per < count || ((int64_t)chunks - 1) * per >= count)
+        die("%s: %u chunks of %lld for %lld %s", name, chunks, (long long)per, (long long)count, what);
+}
+
+// static_obj_params_kernel<T>: params [ndraw][11] -> par16 [ndraw][kPar16]
+template <typename T>
+static void shadow_obj_params(void** args, dim3 grid, dim3 block, const char* name) {
+    const T* params = *static_cast<const T* const*>(args[0]);
+    const int64_t ndraw = *static_cast<const int64_t*>(args[1]);
+    double* par16 = *static_cast<double* const*>(args[2]);
+    need_block(block, name);
+    need_cover(grid.x, kBlock, ndraw, "draws", name);
+    need(params, sizeof(T) * 11 * (size_t)ndraw, sizeof(T), "params", name);
+    need(par16, sizeof(double) * kPar16 * (size_t)ndraw, 8, "par16", name);
+}
+
+// static_obj_kernel<T, TR, FOLD>: a thread per pixel, kObjDraws draws per block row
+template <typename T>
+static void shadow_obj(const StaticObjArgs<T>& a, bool fold, dim3 grid, dim3 block, const char* name) {
+    need_block(block, name);
+    if ((int64_t)grid.x * kBlock < a.n || a.n <= 0) die("%s: %u blocks for %lld pixels", name, grid.x, (long long)a.n);
+    need_cover(grid.y, kObjDraws, a.ndraw, "draws", name);
+    const size_t nd = (size_t)a.ndraw;
+    for (int k = 0; k < 14; ++k) need_arr(a.drv[k], (a.dense_drv >> k) & 1u, a.n, "driver", name);
+    need_arr(a.observed, true, a.n, "observed", name);
+    if (a.weights) need_arr(a.weights, true, a.n, "weights", name);
+    if (a.skip) need(a.skip, (size_t)a.n, 1, "domain mask", name);
+    need(a.par16, sizeof(double) * kPar16 * nd, 8, "par16", name);
+    need(a.tab, sizeof(double) * FastMath<double>::kTabDoubles, 16, "exp / log tables", name);
+    need(a.any_draw, sizeof(unsigned) * nd, 4, "any_draw", name);
+    need(a.partial, sizeof(double) * 2 * nd * grid.x, 16, "partial", name);
+    need(a.any_gs, sizeof(unsigned) * nd * grid.x, 4, "any_gs", name);
+    if (fold) {
+        need(a.code, sizeof(int32_t) * nd, 4, "fold codes", name);
+        need(a.label, (size_t)a.n, 1, "fold labels", name);
+    }
+}
+
+// static_obj_redo_kernel<T, FOLD>: a block per draw over the listed pixels
+template <typename T>
+static void shadow_obj_redo(const StaticObjRedoArgs<T>& a, bool fold, dim3 grid, dim3 block, const char* name) {
+    need_block(block, name);
+    if (a.nlist <= 0) die("%s: %lld listed pixels", name, (long long)a.nlist);
+    const size_t nd = grid.x;
+    need(a.params, sizeof(T) * 11 * nd, sizeof(T), "params", name);
+    need(a.list, sizeof(int64_t) * (size_t)a.nlist, 8, "pixel list", name);
+    need(a.redo, sizeof(double) * 5 * nd, 8, "redo", name);
+    // the pixels are known by the list alone: where its memory is real, every entry is an index
+    // into observed (and the dense drivers, the weights, the labels)
+    bool fake = true;
+    int64_t top = 0;
+    if (inside(a.list, sizeof(int64_t) * (size_t)a.nlist, &fake) && !fake)
+        for (int64_t u = 0; u < a.nlist; ++u) {
+            if (a.list[u] < 0) die("%s: list[%lld] = %lld", name, (long long)u, (long long)a.list[u]);
+            top = std::max(top, a.list[u]);
+        }
+    const int64_t n = top + 1;
+    for (int k = 0; k < 14; ++k) need_arr(a.drv[k], (a.dense_drv >> k) & 1u, n, "driver", name);
+    need_arr(a.observed, true, n, "observed", name);
+    if (a.weights) need_arr(a.weights, true, n, "weights", name);
+    if (fold) {
+        need(a.code, sizeof(int32_t) * nd, 4, "fold codes", name);
+        need(a.label, (size_t)n, 1, "fold labels", name);
+    }
+}
+
+// static_domain_kernel<T> (skip_out set) and the static_batch_* kernels that take a StaticBatchArgs
+static std::map<std::string, int64_t>& batch_next() { static auto* m = new std::map<std::string, int64_t>; return *m; }   // kernel -> first draw its next launch must bring
+template <typename T>
+static void shadow_batch(const StaticBatchArgs<T>& a, const uint8_t* skip_out, bool fast, bool skipped, dim3 grid, dim3 block,
+                         const char* name) {
+    need_block(block, name);
+    if (a.n <= 0) die("%s: n = %lld", name, (long long)a.n);
+    for (int k = 0; k < 14; ++k) need_arr(a.drv[k], (a.dense_drv >> k) & 1u, a.n, "driver", name);
+    if (skip_out) {     // a thread per pixel, no draws
+        if ((int64_t)grid.x * kBlock < a.n || grid.y != 1) die("%s: %u x %u blocks for %lld pixels", name, grid.x, grid.y, (long long)a.n);
+        need(skip_out, (size_t)a.n, 1, "domain mask", name);
+        return;
+    }
+    // the launches of one call bring the draws in order, kBatchDraws per block row, all of them
+    if (a.draw0 < 0 || a.draw0 >= a.ndraw) die("%s: draw0 %lld of %lld", name, (long long)a.draw0, (long long)a.ndraw);
+    if (((int64_t)grid.y - 1) * kBatchDraws >= a.ndraw - a.draw0) die("%s: %u block rows for %lld draws left", name, grid.y, (long long)(a.ndraw - a.draw0));
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        int64_t& next = batch_next()[name];
+        if (a.draw0 != next) die("%s: draw0 %lld where %lld was due", name, (long long)a.draw0, (long long)next);
+        next = a.draw0 + (int64_t)grid.y * kBatchDraws;
+        if (next >= a.ndraw) batch_next().erase(name);
+    }
+    const size_t nd = (size_t)a.ndraw;
+    need(a.params, sizeof(T) * 11 * nd, sizeof(T), "params", name);
+    for (int k = 0; k < 3; ++k)
+        if (a.out[k]) need(a.out[k], sizeof(T) * nd * (size_t)a.n, sizeof(T), "output rows", name);
+    need(a.flags, sizeof(unsigned) * nd, 4, "flags", name);
+    if (fast) need(a.tab, sizeof(double) * FastMath<double>::kTabDoubles, 16, "exp / log tables", name);
+    if (skipped || (fast && a.skip)) need(a.skip, (size_t)a.n, 1, "domain mask", name);
+}
+
+// mcmc_init_kernel (x0 set) / mcmc_propose_kernel / mcmc_accept_kernel / mcmc_init_accept_kernel. The
+// step counter a.t lives in memory no shadow advances: the history and trace are checked for one step.
+static void shadow_mcmc(const McmcArgs& a, const double* x0, bool history, bool trace, dim3 grid, dim3 block, const char* name) {
+    need_block(block, name);
+    if (a.d < 1 || a.d > kMcmcMaxD) die("%s: d = %d", name, a.d);
+    need_cover(grid.x, kBlock, a.chains, "chains", name);
+    const size_t c = (size_t)a.chains, cd = c * a.d;
+    need(a.y, 8 * cd, 8, "y", name);
+    need(a.yp, 8 * cd, 8, "yp", name);
+    need(a.xc, 8 * cd, 8, "xc", name);
+    need(a.logp, 8 * c, 8, "logp", name);
+    need(a.loglik, 8 * c, 8, "loglik", name);
+    need(a.lprior_p, 8 * c, 8, "lprior_p", name);
+    need(a.scaling, 8 * c, 8, "scaling", name);
+    need(a.lamb, 8 * c, 8, "lamb", name);
+    need(a.acc, sizeof(int) * c, 4, "acc", name);
+    need(a.t, 8 * c, 8, "t", name);
+    need(a.key, 8 * c, 8, "key", name);
+    need(a.params, 8 * 11 * c, 8, "params", name);
+    need(a.sse, 8 * c, 8, "sse", name);
+    need(a.cnt, 8 * c, 8, "cnt", name);
+    if (x0) need(x0, 8 * cd, 8, "x0", name);
+    if (history || trace) need(a.hist, 8 * cd, 8, "history", name);
+    if (trace) {
+        need(a.xtr, 8 * cd, 8, "x trace", name);
+        need(a.tr_ll, 8 * c, 8, "log-likelihood trace", name);
+        need(a.tr_lp, 8 * c, 8, "log-posterior trace", name);
+        need(a.tr_acc, c, 1, "accepted trace", name);
+    }
+}
+
 static bool has(const std::string& s, const char* sub) { return s.find(sub) != std::string::npos; }
+// the position behind `key` in a mangled name (its first template argument follows an ...I)
+static size_t after(const std::string& s, const char* key) { return s.find(key) + strlen(key); }
 
 static void run_shadow(const std::string& name, dim3 grid, dim3 block, void** args) {
     {
@@ -330,6 +474,75 @@ static void run_shadow(const std::string& name, dim3 grid, dim3 block, void** ar
         const size_t at = name.find(pixels ? "13static_kernelI" : "18static_flag_kernelI") + (pixels ? 16 : 21);
         if (name[at] == 'd') shadow_static(*static_cast<const StaticArgs<double>*>(args[0]), pixels, n);
         else shadow_static(*static_cast<const StaticArgs<float>*>(args[0]), pixels, n);
+    } else if (has(name, "24static_obj_params_kernelI")) {
+        if (name[after(name, "24static_obj_params_kernelI")] == 'd') shadow_obj_params<double>(args, grid, block, n);
+        else shadow_obj_params<float>(args, grid, block, n);
+    } else if (has(name, "17static_obj_kernelI")) {
+        // ...static_obj_kernelI{d|f}Lb<TR>ELb<FOLD>EE...
+        const size_t at = after(name, "17static_obj_kernelI");
+        const bool fold = name[at + 7] == '1';
+        if (name[at] == 'd') shadow_obj(*static_cast<const StaticObjArgs<double>*>(args[0]), fold, grid, block, n);
+        else shadow_obj(*static_cast<const StaticObjArgs<float>*>(args[0]), fold, grid, block, n);
+    } else if (has(name, "22static_obj_redo_kernelI")) {
+        // ...static_obj_redo_kernelI{d|f}Lb<FOLD>EE...
+        const size_t at = after(name, "22static_obj_redo_kernelI");
+        const bool fold = name[at + 3] == '1';
+        if (name[at] == 'd') shadow_obj_redo(*static_cast<const StaticObjRedoArgs<double>*>(args[0]), fold, grid, block, n);
+        else shadow_obj_redo(*static_cast<const StaticObjRedoArgs<float>*>(args[0]), fold, grid, block, n);
+    } else if (has(name, "21static_obj_any_kernel") || has(name, "23static_obj_final_kernel")) {
+        // (any_gs, redo, ndraw, gx, any_draw) / (partial, redo, any_draw, ndraw, gx, sse, count)
+        const bool fin = has(name, "23static_obj_final_kernel");
+        const double* redo = *static_cast<const double* const*>(args[1]);
+        const int64_t ndraw = *static_cast<const int64_t*>(args[fin ? 3 : 2]);
+        const int gx = *static_cast<const int*>(args[fin ? 4 : 3]);
+        need_block(block, n);
+        need_cover(grid.x, kObjPerBlock, ndraw, "draws", n);
+        if (gx < 1) die("%s: gx = %d", n, gx);
+        const size_t nd = (size_t)ndraw;
+        if (fin) need(*static_cast<const double* const*>(args[0]), sizeof(double) * 2 * nd * gx, 16, "partial", n);
+        else need(*static_cast<const unsigned* const*>(args[0]), sizeof(unsigned) * nd * gx, 4, "any_gs", n);
+        if (redo) need(redo, sizeof(double) * 5 * nd, 8, "redo", n);
+        need(*static_cast<const unsigned* const*>(args[fin ? 2 : 4]), sizeof(unsigned) * nd, 4, "any_draw", n);
+        if (fin) {
+            need(*static_cast<double* const*>(args[5]), sizeof(double) * nd, 8, "sse", n);
+            need(*static_cast<double* const*>(args[6]), sizeof(double) * nd, 8, "count", n);
+        }
+    } else if (has(name, "20static_domain_kernelI")) {
+        uint8_t* skip = *static_cast<uint8_t* const*>(args[1]);
+        if (!skip) die("%s: no domain mask", n);
+        if (name[after(name, "20static_domain_kernelI")] == 'd') shadow_batch(*static_cast<const StaticBatchArgs<double>*>(args[0]), skip, false, false, grid, block, n);
+        else shadow_batch(*static_cast<const StaticBatchArgs<float>*>(args[0]), skip, false, false, grid, block, n);
+    } else if (has(name, "24static_batch_flag_kernelI") || has(name, "19static_batch_kernelI") ||
+               has(name, "29static_batch_flag_fast_kernelI") || has(name, "24static_batch_fast_kernelI") ||
+               has(name, "32static_batch_flag_skipped_kernelI") || has(name, "29static_batch_redo_rows_kernelI")) {
+        const bool fast = has(name, "_fast_kernelI");
+        const bool skipped = has(name, "flag_skipped_kernelI") || has(name, "redo_rows_kernelI");
+        if (name[name.find("kernelI") + 7] == 'd') shadow_batch(*static_cast<const StaticBatchArgs<double>*>(args[0]), nullptr, fast, skipped, grid, block, n);
+        else shadow_batch(*static_cast<const StaticBatchArgs<float>*>(args[0]), nullptr, fast, skipped, grid, block, n);
+    } else if (has(name, "23static_batch_sse_kernelI")) {
+        // (total [gridDim.x][n], obs [n], weights [n] or NULL, n, sse, cnt [gridDim.x])
+        const size_t el = name[after(name, "23static_batch_sse_kernelI")] == 'd' ? 8 : 4;
+        const int64_t cnt = *static_cast<const int64_t*>(args[3]);
+        need_block(block, n);
+        if (cnt <= 0) die("%s: n = %lld", n, (long long)cnt);
+        need(*static_cast<const void* const*>(args[0]), el * (size_t)cnt * grid.x, el, "total rows", n);
+        need(*static_cast<const void* const*>(args[1]), el * (size_t)cnt, el, "observed", n);
+        if (*static_cast<const void* const*>(args[2])) need(*static_cast<const void* const*>(args[2]), el * (size_t)cnt, el, "weights", n);
+        need(*static_cast<double* const*>(args[4]), sizeof(double) * grid.x, 8, "sse", n);
+        need(*static_cast<double* const*>(args[5]), sizeof(double) * grid.x, 8, "count", n);
+    } else if (has(name, "15zero_u32_kernel")) {
+        const int64_t cnt = *static_cast<const int64_t*>(args[1]);
+        need_block(block, n);
+        need_cover(grid.x, kBlock, cnt, "words", n);
+        need(*static_cast<unsigned* const*>(args[0]), sizeof(unsigned) * (size_t)cnt, 4, "words", n);
+    } else if (has(name, "16mcmc_init_kernel")) {
+        shadow_mcmc(*static_cast<const McmcArgs*>(args[0]), *static_cast<const double* const*>(args[1]), false, false, grid, block, n);
+    } else if (has(name, "23mcmc_init_accept_kernel")) {
+        shadow_mcmc(*static_cast<const McmcArgs*>(args[0]), nullptr, false, false, grid, block, n);
+    } else if (has(name, "19mcmc_propose_kernel")) {
+        shadow_mcmc(*static_cast<const McmcArgs*>(args[0]), nullptr, true, false, grid, block, n);
+    } else if (has(name, "18mcmc_accept_kernel")) {
+        shadow_mcmc(*static_cast<const McmcArgs*>(args[0]), nullptr, false, true, grid, block, n);
     } else if (has(name, "12synth_kernelI")) {
         const size_t at = name.find("12synth_kernelI") + 15;
         if (name[at] == 'd') shadow_synth(*static_cast<const SynthArgs<double>*>(args[0]), n);
@@ -371,6 +584,7 @@ static void run_shadow(const std::string& name, dim3 grid, dim3 block, void** ar
 }  // namespace stub
 
 extern "C" void mod16_stub_report(FILE* f) {
+    for (auto& kv : stub::batch_next()) stub::die("%s: its launches stopped before draw %lld", kv.first.c_str(), (long long)kv.second);
     fprintf(f, "hip_stub: %ld address ranges checked; live allocations %zu\n", stub::g_checked_ranges, stub::g_blocks.size());
     for (auto& kv : stub::g_launches) fprintf(f, "  launches  %-44s %ld\n", kv.first.c_str(), kv.second);
     for (auto& kv : stub::g_unchecked) fprintf(f, "  launch shape only (no shadow)  %-48s %ld\n", kv.first.c_str(), kv.second);

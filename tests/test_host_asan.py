@@ -3,7 +3,9 @@
 runtime (tests/host_asan/hip_stub.hip: device memory = host heap under AddressSanitizer, kernel
 launches = shadows that replay the launch's address arithmetic against the allocation table) and
 driven through the C ABI over ragged sizes, every form and layout, bad layouts, the global grid,
-2^31 + 12344 pixels, graphs, the HOST-mode tiler and the resident calibration problem. Clean = no
+2^31 + 12344 pixels, graphs, the HOST-mode tiler, and the calibration family: resident problems
+(float64 / float32, FAST / EXACT, HOST / DEVICE) whose workspaces grow under cached graphs, folds,
+DE-MCMC-Z samplers with their own workspace and a growing trace, the Sobol entry points. Clean = no
 sanitizer report, no address outside an allocation, nothing leaked; and a planted fault (a raster one
 tile short) is reported. Sanitizers run on the CPU build only (the GPU pool refuses them)."""
 import os
@@ -28,6 +30,17 @@ def test_host_half_of_the_library_is_clean_under_asan_and_ubsan(tmp_path):
     for kernel in ('13method_kernel', '13et_raw_kernel', '18static_flag_kernel', '13static_kernel'):
         assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
         assert not any(kernel in l for l in lines if 'launch shape only' in l), kernel
+    # the calibration family: every array of the objective's, the rows' and the sampler's launches is
+    # checked with the extent its kernel indexes
+    for kernel in ('24static_obj_params_kernel', '17static_obj_kernel', '22static_obj_redo_kernel',
+                   '21static_obj_any_kernel', '23static_obj_final_kernel', '20static_domain_kernel',
+                   '24static_batch_flag_kernel', '19static_batch_kernel', '29static_batch_flag_fast_kernel',
+                   '24static_batch_fast_kernel', '32static_batch_flag_skipped_kernel',
+                   '29static_batch_redo_rows_kernel', '23static_batch_sse_kernel', '15zero_u32_kernel',
+                   '16mcmc_init_kernel', '19mcmc_propose_kernel', '18mcmc_accept_kernel', '23mcmc_init_accept_kernel'):
+        assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
+        assert not any(kernel in l for l in lines if 'launch shape only' in l), kernel
+    assert 'calibration family: done' in out and 'Sobol entry points: done' in out
     for what in ('tiled rasters, float64', 'tiled rasters, float32', 'plain device arrays, float64',
                  'HOST mode, float64', 'HOST mode, float32'):
         assert what in out, what

@@ -483,9 +483,15 @@ __global__ void MOD16_STREAM_BOUNDS et_stream_kernel(const StreamArgs<T> a) {
         }
         const double cnt_d = (double)__builtin_amdgcn_readfirstlane(nan_d);
         const double cnt_n = (double)__builtin_amdgcn_readfirstlane(nan_n);
-        unsigned long long flag_word = flags;
-        if constexpr (kLists)
-            flag_word |= (unsigned long long)(cancel_cnt < (unsigned)kCancelCap ? cancel_cnt : (unsigned)kCancelCap) << kCancelShift;
+        // (the record and the count are written by the lanes that COMPUTED a piece: of a ragged last piece
+        // of one or two vectors lane kFlagField is none of them, lane 0 always is -- its copy is the one
+        // that counts; a cross-lane read in vector registers, like the record itself)
+        unsigned long long flag_word = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(flags >> 32), 0, 64) << 32) |
+                                       (unsigned long long)(unsigned)__shfl((int)(unsigned)flags, 0, 64);
+        if constexpr (kLists) {
+            const unsigned cnt0 = (unsigned)__shfl((int)cancel_cnt, 0, 64);
+            flag_word |= (unsigned long long)(cnt0 < (unsigned)kCancelCap ? cnt0 : (unsigned)kCancelCap) << kCancelShift;
+        }
         const double f = lane == 0 ? dsum_d : lane == 1 ? dsum_n : lane == kFlagField ? (double)flag_word
                        : lane == kSerialField ? launch_marker(serial)
                        : lane == 4 ? cnt_d : lane == 5 ? cnt_n : lane == 6 ? dmax_d : lane == 7 ? dmax_n : 0.0;
@@ -690,10 +696,13 @@ __global__ void MOD16_STREAM_BOUNDS et_stream_kernel(const StreamArgs<T> a) {
                         // pixel): it is MARKED -- its first output holds kCancelPoison, both totals count as NaN
                         // in the run's diagnostics -- and what runs behind the loop puts the float64 result in
                         // its place. Dynamic schedule: the pixel joins its run's list, in the order (piece,
-                        // pixel, lane), which et_stream_redo_kernel works off with the pixels of 64 runs side by
-                        // side in the lanes of a wave; a run whose list is full leaves the pixel its float32
-                        // value. Static schedule (small rasters): the piece is flagged like one with a pixel
-                        // outside the domain and the wave revisits it behind its loop (redo_piece).
+                        // pixel, lane), which et_stream_cancel_kernel works off with the pixels of 64 runs side by
+                        // side in the lanes of a wave; a ballot group (one pixel pair) that would take the list past
+                        // kCancelCap entries is not listed but marked all the same: its piece is flagged like one
+                        // with a pixel outside the domain, and et_stream_redo_kernel finds the marked pixels by
+                        // their poison (redo_piece with `marked`) -- later, smaller groups of the run may still
+                        // join the list. Static schedule (small rasters): nothing is listed, every such piece
+                        // is flagged and the wave revisits it behind its loop (redo_piece).
                         if (__builtin_expect(__any(cancel2[0] | cancel2[1]), 0)) {
                             const unsigned long long b0 = __ballot(cancel2[0]), b1 = __ballot(cancel2[1]);
                             const unsigned more = (unsigned)__builtin_popcountll(b0) + (unsigned)__builtin_popcountll(b1);

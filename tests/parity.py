@@ -99,3 +99,26 @@ def same_bits(a, b):
         return False
     u = {4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
     return bool(np.array_equal(np.ascontiguousarray(a).view(u)[~na], np.ascontiguousarray(b).view(u)[~nb]))
+
+
+def ulps(torch, a, b):
+    """float32 ulps between the elements of two float32 tensors (as int64): 0 where both are NaN,
+    2^40 where one is; -0 and +0 are the same number."""
+    def ordered(t):
+        i = t.contiguous().view(torch.int32).to(torch.int64)
+        return torch.where(i < 0, -(i & 0x7fffffff), i)
+    d = (ordered(a) - ordered(b)).abs()
+    na, nb = torch.isnan(a), torch.isnan(b)
+    return torch.where(na & nb, torch.zeros_like(d), torch.where(na ^ nb, torch.full_like(d, 1 << 40), d))
+
+
+def bits_equal(torch, a, b):
+    """elementwise: the same float32 bits, or NaN in both"""
+    return (a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)) | (torch.isnan(a) & torch.isnan(b))
+
+
+def untouched_or_redone(torch, guarded, trusted, fast):
+    """The mixed form's invariant (float32 tensors): every value of the guarded run is either the
+    trusted instance's, bit for bit -- untouched mixed arithmetic -- or within 1 ulp of the FAST
+    engine's -- a pixel computed again in float64. Returns the number of values that are neither."""
+    return int((~(bits_equal(torch, guarded, trusted) | (ulps(torch, guarded, fast) <= 1))).sum())

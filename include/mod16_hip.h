@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 8
+#define MOD16_ABI_VERSION 9
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -562,6 +562,33 @@ MOD16_API int mod16_static_batch_objective_folds(mod16_batch* problem, const voi
                         const int32_t* code, double* sse, double* count);
 
 /*
+ * The annual-precipitation constraint on a resident problem (ABI 9; the reference's constrain_by_map,
+ * mod16/calibration.py:776-796). The problem is T days x N sites, pixel t N + s; day t belongs to
+ * year year_index[t] in 0 .. Y - 1; annual_precip [Y][N] in mm per year; lhv [T][N] in J kg-1. For a
+ * parameter row with le = the row's ET in W m-2 (every pixel, observed or not):
+ *   mass = max(le 86400 / lhv, 0), tot[y][s] = its sum over the days of year y,
+ *   over = max(tot - annual_precip, 0), penalty = -100 mean(over^2) / sum(annual_precip)
+ * both max keeping a NaN: penalty <= 0, or NaN. float64, sums in a fixed order (the same bits on every
+ * launch), no array of size draws x n.
+ *   mod16_static_batch_set_annual        once per problem, before any objective call or sampler: a
+ *       float64 MOD16_MATH_FAST problem bound from MOD16_HOST arrays with observations, without
+ *       folds, n = T N; every year index used; annual_precip finite with a sum > 0; lhv finite and
+ *       > 0. The resident copies are laid out anew, site-year by site-year, each padded to a multiple
+ *       of 64 pixels (so device memory grows by up to 63 pixels per site-year, plus 8 bytes per
+ *       pixel); n of mod16_static_batch_info, the rows of mod16_static_batch_rows and the (sse,
+ *       count) of mod16_static_batch_objective stay the caller's (sse up to summation order).
+ *   mod16_static_batch_objective_annual  as mod16_static_batch_objective, and penalty [ndraw]; one
+ *       graph launch, its own cached graph.
+ * Not combined with folds (the reference's own combination cannot run: its closure indexes a (T,)
+ * mask into ravelled, compacted rows). Anything else is MOD16_ERR_ARG with a message; memory that
+ * cannot be had is MOD16_ERR_NOMEM and leaves the problem as it was.
+ */
+MOD16_API int mod16_static_batch_set_annual(mod16_batch* problem, int64_t T, int64_t N, const int32_t* year_index,
+                        int Y, const double* annual_precip, const double* lhv);
+MOD16_API int mod16_static_batch_objective_annual(mod16_batch* problem, const void* params, int64_t ndraw,
+                        double* sse, double* count, double* penalty);
+
+/*
  * DE-MCMC-Z calibration sampler (ABI 7; mod16_amd/calibration.py): independent chains of PyMC's
  * DEMetropolisZ -- the project's restatement of it, stated in full at the top of
  * mod16_amd/csrc/mod16_mcmc.hpp -- over the free parameters of a RESIDENT problem
@@ -596,7 +623,14 @@ MOD16_API int mod16_static_batch_objective_folds(mod16_batch* problem, const voi
  * 1 .. 1024. Device memory: about 8 (2 nfree + 2) + 1 bytes per chain and step taken (history and
  * trace, grown by each run -- the graphs are captured again then), plus the objective's workspace
  * for `chains` draws; what cannot be had is MOD16_ERR_NOMEM. Calls hold the problem's ctx mutex.
+ * spec->constraints (ABI 9): MOD16_CONSTRAINT_ANNUAL_PRECIP on a problem with
+ * mod16_static_batch_set_annual adds the row's penalty to the log-likelihood of either objective (the
+ * trace's loglik includes it; a NaN penalty rejects the step, and an initial point with one is
+ * MOD16_ERR_ARG); the sampler's graphs then hold the constrained launches. With folds
+ * (mod16_mcmc_create_groups), on a problem without the constraint, or with unknown bits:
+ * MOD16_ERR_ARG. 0 is a sampler without constraint, on any problem.
  */
+#define MOD16_CONSTRAINT_ANNUAL_PRECIP 1
 enum mod16_prior { MOD16_PRIOR_UNIFORM = 0, MOD16_PRIOR_LOGNORMAL = 1, MOD16_PRIOR_TRIANGULAR = 2 };
 typedef struct mod16_mcmc_spec {
     int32_t chains;
@@ -613,6 +647,8 @@ typedef struct mod16_mcmc_spec {
     int32_t objective;
     int32_t segment;
     uint64_t seed;
+    int32_t constraints;        /* (ABI 9) bits of MOD16_CONSTRAINT_*; 0: none */
+    int32_t reserved_;          /* 0 */
 } mod16_mcmc_spec;
 typedef struct mod16_mcmc mod16_mcmc;
 MOD16_API int mod16_mcmc_create(mod16_batch* problem, const mod16_mcmc_spec* spec, const double* x0,

@@ -863,7 +863,7 @@ class MOD16(object):
     def _et_bind(lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
                  temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
                  pressure, fpar, lai, observed=None, weights=None, max_draws=4096,
-                 math=_lib.MATH_FAST, device=0, folds=None):
+                 math=_lib.MATH_FAST, device=0, folds=None, annual_precip=None):
         '''
         (Extension.) The calibration problem made RESIDENT on the GPU: what the
         reference's sampler (calibration.py:907-909) and Sobol analysis
@@ -883,12 +883,22 @@ class MOD16(object):
         ``mod16_amd.calibration.kfold_labels(n, K)`` -- or the fold label
         (0 .. K-1) of every site-day, of the problem's shape; then
         ``problem.objective(params, folds=..., heldout=...)`` and
-        ``DEMetropolisZ(problem, ..., folds=...)``.
+        ``DEMetropolisZ(problem, ..., folds=...)``. ``annual_precip`` (the
+        reference's annual-precipitation constraint, calibration.py:776-796 and
+        :827-849; a 2-D (T days x N sites) float64 ``MATH_FAST`` problem with
+        ``observed``, without ``folds``): ``(years, precip)`` with ``years`` the
+        (T,) integer year of every day and ``precip`` (Y, N) in mm per year, rows
+        in the order of ``np.unique(years)``; the latent heat of vaporization is
+        ``latent_heat_vaporization((temp_day + temp_night) / 2)``, as in the
+        reference. Then ``problem.penalty(params)``,
+        ``problem.objective(params, penalty=True)`` and
+        ``DEMetropolisZ(problem, ..., constraints=True)``; see
+        ``mod16_amd.calibration.annual_precip_penalty`` for the formula.
         '''
         drivers = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
                    sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
                    vpd_night, pressure, fpar, lai]
-        return BoundCalibration(drivers, observed, weights, max_draws, math, device, folds)
+        return BoundCalibration(drivers, observed, weights, max_draws, math, device, folds, annual_precip)
 
     @staticmethod
     def air_density(temp_k, pressure, rhumidity):
@@ -994,7 +1004,7 @@ class BoundCalibration(object):
     '''A calibration problem resident on the GPU (``MOD16._et_bind``;
     ``mod16_static_batch_bind_*`` of the C ABI).'''
 
-    def __init__(self, drivers, observed, weights, max_draws, math, device, folds=None):
+    def __init__(self, drivers, observed, weights, max_draws, math, device, folds=None, annual_precip=None):
         import ctypes as C
         if weights is not None and observed is None:
             raise ValueError('weights need observed')
@@ -1010,6 +1020,12 @@ class BoundCalibration(object):
         self.labels, self.nfolds = None, 0
         if folds is not None:
             self.labels, self.nfolds = self._fold_labels(folds, observed)
+        #: the annual-precipitation constraint: years (T,), annual_precip (Y, N) and -- once bound --
+        #: lhv (T, N), as ``calibration.annual_precip_penalty`` takes them; None: no constraint
+        self.years = self.annual_precip = self.lhv = None
+        year_index = None
+        if annual_precip is not None:
+            self.years, self.annual_precip, year_index = self._annual(annual_precip, observed, folds)
         self._ctx = _lib.context(device)
         keep, dptr, dstr = _marshal(drivers, self.shape, self.dtype)
         full = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, self.dtype), self.shape))
@@ -1030,6 +1046,52 @@ class BoundCalibration(object):
         if self.labels is not None:
             self._ctx.check(self._ctx.lib.mod16_static_batch_set_folds(
                 self._handle, self.labels.ctypes.data, self.nfolds))
+        if year_index is not None:
+            # (reference calibration.py:838-842: the mean of the two temperatures, then its LHV)
+            air_t = (np.asarray(drivers[5], np.float64) + np.asarray(drivers[6], np.float64)) / 2
+            lhv = np.ascontiguousarray(np.broadcast_to(latent_heat_vaporization(air_t), self.shape), np.float64)
+            status = self._ctx.lib.mod16_static_batch_set_annual(
+                self._handle, self.shape[0], self.shape[1], year_index.ctypes.data,
+                self.annual_precip.shape[0], self.annual_precip.ctypes.data, lhv.ctypes.data)
+            if status == _lib.ERR_ARG:
+                message = self._ctx.lib.mod16_last_error(self._ctx.handle).decode()
+                self.close()
+                raise ValueError(message)
+            self._ctx.check(status)
+            self.lhv = lhv
+
+    @property
+    def has_annual(self):
+        '''Whether the problem carries the annual-precipitation constraint.'''
+        return self.lhv is not None
+
+    def _annual(self, annual_precip, observed, folds):
+        '''(years (T,), annual_precip (Y, N) float64, year index (T,) int32) of the
+        ``annual_precip=(years, precip)`` argument; checked on the host.'''
+        if self.dtype != np.float64 or (self.math & 3) != _lib.MATH_FAST or observed is None:
+            raise ValueError('annual_precip needs a float64 problem bound with math=MATH_FAST and observed')
+        if folds is not None:
+            raise ValueError('annual_precip cannot be combined with folds')
+        if len(self.shape) != 2:
+            raise ValueError('annual_precip needs a 2-D problem (T days x N sites); this one is %s' % (self.shape,))
+        try:
+            years, precip = annual_precip
+        except (TypeError, ValueError):
+            raise ValueError('annual_precip must be (years, precip)')
+        years = np.asarray(years)
+        precip = np.ascontiguousarray(precip, np.float64)
+        T, N = self.shape
+        if years.shape != (T,) or not np.issubdtype(years.dtype, np.integer):
+            raise ValueError('years must be (%d,) integers (got %s %s)' % (T, years.shape, years.dtype))
+        uniq, index = np.unique(years, return_inverse=True)
+        if precip.shape != (uniq.size, N):
+            raise ValueError('annual_precip of shape %s; %d distinct years x %d sites need (%d, %d)'
+                             % (precip.shape, uniq.size, N, uniq.size, N))
+        if not np.isfinite(precip).all():
+            raise ValueError('annual_precip must be finite')
+        if not precip.sum() > 0:
+            raise ValueError('the sum of annual_precip must be > 0')
+        return years, precip, np.ascontiguousarray(index.reshape(T), np.int32)
 
     def _fold_labels(self, folds, observed):
         '''(labels (n,) uint8, K) of ``folds``: an int K (``calibration.kfold_labels(n, K)``) or
@@ -1080,16 +1142,34 @@ class BoundCalibration(object):
                              % (par.shape[0], self.max_draws))
         return par
 
-    def objective(self, params, folds=None, heldout=False):
+    def penalty(self, params):
+        '''The annual-precipitation penalty (D,) float64 of each parameter vector (<= 0, or
+        NaN): ``calibration.annual_precip_penalty(self.rows(params), self.years, self.lhv,
+        self.annual_precip)`` up to summation order.'''
+        return self.objective(params, penalty=True)[2]
+
+    def objective(self, params, folds=None, heldout=False, penalty=False):
         '''``(sse, count)``: two float64 arrays (D,) with ``sse[d] = sum((weights *
         (_et_d - observed))**2)`` over the non-NaN pairs and their number, as
         ``MOD16._et_batch(params, *drivers, observed=..., weights=...)``; e.g.
         ``rmsd = np.sqrt(sse / count)``. ``folds`` (a problem bound with folds):
         an int or (D,) ints; draw d then sees the site-days whose label is not
         ``folds[d]`` (training), or with ``heldout`` those whose label is: what
-        ``_et_batch`` returns on those rows without their NaN observations.'''
+        ``_et_batch`` returns on those rows without their NaN observations.
+        ``penalty`` (a problem bound with ``annual_precip``): ``(sse, count,
+        penalty)`` from one launch, see ``penalty()``.'''
         if not self.has_observed:
             raise ValueError('the problem was bound without observed')
+        if penalty:
+            if not self.has_annual:
+                raise ValueError('the problem was bound without annual_precip')
+            par = self._params(params)
+            sse, count, pen = (np.zeros(par.shape[0]) for _ in range(3))
+            if par.shape[0]:
+                self._ctx.check(self._ctx.lib.mod16_static_batch_objective_annual(
+                    self._handle, par.ctypes.data, par.shape[0], sse.ctypes.data, count.ctypes.data,
+                    pen.ctypes.data))
+            return sse, count, pen
         if folds is None and heldout:
             raise ValueError('heldout needs folds')
         par = self._params(params)

@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -69,6 +69,7 @@ _LAYP = C.POINTER(Layout)
 
 
 PRIOR_UNIFORM, PRIOR_LOGNORMAL, PRIOR_TRIANGULAR = 0, 1, 2     # enum mod16_prior
+CONSTRAINT_ANNUAL_PRECIP = 1      # MOD16_CONSTRAINT_ANNUAL_PRECIP: a bit of mod16_mcmc_spec.constraints
 FOLD_HELDOUT = 0x100      # MOD16_FOLD_HELDOUT: or it into a fold code (include/mod16_hip.h)
 
 
@@ -79,7 +80,8 @@ class McmcSpec(C.Structure):
                 ('p2', C.c_double * 11), ('fixed', C.c_double * 11), ('lamb', C.c_double),
                 ('scaling', C.c_double), ('tune_target', C.c_int32), ('tune_interval', C.c_int32),
                 ('tune_steps', C.c_int64), ('tune_drop_fraction', C.c_double), ('objective', C.c_int32),
-                ('segment', C.c_int32), ('seed', C.c_uint64)]
+                ('segment', C.c_int32), ('seed', C.c_uint64), ('constraints', C.c_int32),
+                ('reserved_', C.c_int32)]
 
 # name -> (restype, argtypes); one entry per function declared in the header
 PROTOTYPES = {
@@ -172,6 +174,10 @@ PROTOTYPES = {
     'mod16_static_batch_set_folds': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     'mod16_static_batch_objective_folds': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]),
+    'mod16_static_batch_set_annual': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p]),
+    'mod16_static_batch_objective_annual': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]),
     'mod16_check_status': (C.c_int, [C.c_void_p, C.c_void_p]),
     'mod16_reduce_diag_f64': (C.c_int, [
         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

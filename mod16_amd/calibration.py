@@ -24,7 +24,13 @@ arithmetic is stated in full at the top of ``mod16_amd/csrc/mod16_mcmc.hpp``):
   ``MOD16._et_bind(..., folds=K or labels)``, and ``DEMetropolisZ(problem, ..., folds=True)``: the
   chains of every fold in ONE sampler -- each fold's chains train on the site-days outside it -- with
   a ``KFoldTrace`` (``trace.fold(f)`` a plain ``Trace``; R-hat per fold) and ``sampler.heldout(trace)``
-  (the held-out RMSD of every kept draw and of the posterior mean).
+  (the held-out RMSD of every kept draw and of the posterior mean);
+- the annual-precipitation constraint, the reference's ``constrain_by_map`` (calibration.py:776-796,
+  wired in at :827-849; the only constraint it supports, what its ``classes_are_dynamic``
+  calibrations use): ``MOD16._et_bind(..., annual_precip=(years, precip))`` on a (T days x N sites)
+  problem, ``problem.penalty(params)``, ``DEMetropolisZ(problem, ..., constraints=True)`` and
+  ``sampler.penalty(trace)``; ``annual_precip_penalty`` states the formula in numpy. The sums per
+  site-year are made on the device inside the objective's launches; nothing of size draws x n exists.
 
   The reference's own k-fold loop does not do what its docstring says, and this port does what the
   docstring says. (1) The restore-and-mask block (``tower_obs[idx] = np.nan`` and the driver filter,
@@ -39,7 +45,13 @@ table and ``stop_tuning`` history drop), and the likelihoods -- ``'rmsd'``: ``-s
 mod17's ``BlackBoxLikelihood`` as the reference's shipped config uses it; ``'gaussian'``:
 ``-sse / 2`` -- are the project's restatements of mod17's. Neither PyMC nor mod17 is available to
 check against, and the random stream is the project's own (counter-based), so chains are not
-PyMC's draw for draw. The defaults (``tune=1000``, ``scaling=1e-3``, ``tune_interval=100``,
+PyMC's draw for draw. With ``constraints`` the penalty is ADDED to the log-likelihood of either
+objective: how mod17's ``BlackBoxLikelihood`` combines its ``constraints`` with the objective cannot
+be read here (mod17 is absent), so adding is likewise this project's restatement. The reference
+config's hint to "use nRMSD if there are constraints" names an objective that is defined nowhere in
+the reference; it is left out. A NaN penalty (a NaN prediction anywhere in a site-year) makes the log
+posterior NaN: such a step is rejected, such an initial point refused -- what the reference's
+arithmetic gives too. The defaults (``tune=1000``, ``scaling=1e-3``, ``tune_interval=100``,
 ``tune_drop_fraction=0.9``, ``lamb = 2.38 / sqrt(2 d)``) are PyMC's and the reference config's;
 ``tune=1000`` is pm.sample's default, which mod17's ``run()`` is believed, not verified, to keep.
 Every chain starts at the priors' support points (Uniform: the midpoint; LogNormal:
@@ -49,8 +61,10 @@ initial point -- unless ``initial`` is given. The caller states the fixed parame
 ``config['optimization']['fixed']``).
 
 Not provided: HDF5 loading (h5py is absent; ``tools/h5_to_store.py`` covers the field map), the
-annual-precipitation constraint (``constrain_by_map``), plots, netCDF / arviz backends, population
-DE-MCMC (proposals drawn from other chains), several GPUs, float32 problems.
+constraint together with k-fold cross-validation (the reference's own combination cannot run: its
+closure indexes a (T,)-long mask into ravelled, compacted rows), the constraint on float32, EXACT or
+device-bound problems, plots, netCDF / arviz backends, population DE-MCMC (proposals drawn from
+other chains), several GPUs, float32 problems.
 There is no CPU fallback: without an MI355X the sampler raises ``Mod16Error``.
 '''
 import ctypes as C
@@ -66,6 +80,7 @@ FAMILIES = ('uniform', 'lognormal', 'triangular')
 _FAMILY_CODE = {'uniform': _lib.PRIOR_UNIFORM, 'lognormal': _lib.PRIOR_LOGNORMAL,
                 'triangular': _lib.PRIOR_TRIANGULAR}
 OBJECTIVES = ('rmsd', 'gaussian')
+CONSTRAINTS = ('annual_precipitation',)
 HALF_LOG_2PI = float.fromhex('0x1.d67f1c864beb4p-1')
 _M64 = (1 << 64) - 1
 
@@ -204,6 +219,35 @@ def group_stream(seed, fold, j, t, k):
     '''The random word of chain j of the group of fold ``fold`` (``DEMetropolisZ(..., folds=...)``):
     the plain stream with seed (seed + fold) mod 2^64 and chain index j.'''
     return stream((int(seed) + int(fold)) & _M64, j, t, k)
+
+
+def annual_precip_penalty(le, years, lhv, annual_precip):
+    '''The reference's ``constrain_by_map`` (calibration.py:776-796) in numpy, float64: ``le``
+    (..., T, N) predicted latent heat flux [W m-2], ``years`` (T,) the year of each day, ``lhv``
+    (T, N) latent heat of vaporization [J kg-1], ``annual_precip`` (Y, N) [mm per year], rows in the
+    order of ``np.unique(years)``:
+
+        mass = max(le * 86400 / lhv, 0); tot[y, n] = sum of mass over the days of year y
+        over = max(tot - annual_precip, 0); penalty = -100 * mean(over ** 2) / annual_precip.sum()
+
+    with NaN kept by both max (``x[x < 0] = 0``), over every day, observed or not. Returns (...):
+    <= 0, or NaN. (Host statement of what ``problem.penalty`` computes on the device.)'''
+    le = np.asarray(le, np.float64)
+    lhv = np.asarray(lhv, np.float64)
+    annual_precip = np.asarray(annual_precip, np.float64)
+    uniq, inv = np.unique(np.asarray(years), return_inverse=True)
+    inv = inv.reshape(-1)
+    if le.ndim < 2 or le.shape[-2:] != lhv.shape or inv.size != le.shape[-2] or \
+            annual_precip.shape != (uniq.size, le.shape[-1]):
+        raise ValueError('le (..., T, N), years (T,), lhv (T, N) and annual_precip (Y, N) do not fit: %s, %s, %s, %s'
+                         % (le.shape, np.shape(years), lhv.shape, annual_precip.shape))
+    with np.errstate(invalid='ignore', over='ignore'):
+        mass = (le * 60 * 60 * 24) / lhv
+        mass = np.where(mass < 0, 0.0, mass)
+        tot = np.stack([mass[..., inv == k, :].sum(axis=-2) for k in range(uniq.size)], axis=-2)
+        diff = tot - annual_precip
+        diff = np.where(diff < 0, 0.0, diff)
+        return -(100 * ((diff ** 2).mean(axis=(-2, -1)) / annual_precip.sum()))
 
 
 def kfold_labels(n, k, seed=0):
@@ -367,12 +411,15 @@ class DEMetropolisZ(object):
     ``seed + f`` on the problem with fold f's observations set to NaN, whenever some training row
     has g_surf > 0 (``mod16_mcmc.hpp``); ``initial`` is then (chains, d), the same for every fold,
     or (folds, chains, d). ``sample`` returns a ``KFoldTrace``; ``heldout(trace)`` scores it.
+    ``constraints`` (a problem bound with ``annual_precip``, no ``folds``): ``None``, ``True`` or
+    ``('annual_precipitation',)``; the penalty of the row is then added to the log-likelihood of
+    either objective -- ``Trace.log_likelihood`` includes it -- and ``penalty(trace)`` gives it alone.
     Everything is checked on the host before any device call (``ValueError``).
     '''
 
     def __init__(self, problem, params, prior, fixed=None, chains=3, tune=1000, tune_target='scaling',
                  tune_interval=100, tune_drop_fraction=0.9, scaling=1e-3, lamb=None, objective='rmsd',
-                 seed=0, initial=None, segment=64, folds=None):
+                 seed=0, initial=None, segment=64, folds=None, constraints=None):
         self.problem = problem
         self._handle = C.c_void_p()
         row = _row(params)
@@ -455,6 +502,22 @@ class DEMetropolisZ(object):
             if not fl or len(set(fl)) != len(fl) or min(fl) < 0 or max(fl) >= nf:
                 raise ValueError('folds must be True or distinct folds in 0 .. %d (got %r)' % (nf - 1, folds))
             self.folds = fl
+        #: the constraints in force, names of ``CONSTRAINTS``
+        self.constraints = ()
+        if isinstance(constraints, (bool, np.bool_)):
+            constraints = CONSTRAINTS if constraints else None
+        if constraints is not None:
+            names = (constraints,) if isinstance(constraints, str) else tuple(constraints)
+            unknown = [k for k in names if k not in CONSTRAINTS]
+            if unknown:
+                raise ValueError('unknown constraint(s) %s; expected some of %s' % (unknown, CONSTRAINTS))
+            self.constraints = tuple(k for k in CONSTRAINTS if k in names)
+        if self.constraints:
+            if self.folds:
+                raise ValueError('constraints cannot be combined with folds')
+            if not getattr(problem, 'has_annual', False):
+                raise ValueError('constraints need a problem bound with annual_precip '
+                                 '(MOD16._et_bind(..., annual_precip=(years, precip)))')
         groups = len(self.folds) if self.folds else 1
         if self.chains * groups > problem.max_draws:
             raise ValueError('%d chains x %d fold(s), the problem was bound for max_draws = %d'
@@ -491,6 +554,7 @@ class DEMetropolisZ(object):
         spec.objective = OBJECTIVES.index(obj)
         spec.segment = int(segment)
         spec.seed = self.seed
+        spec.constraints = _lib.CONSTRAINT_ANNUAL_PRECIP if self.constraints else 0
         self._ctx = problem._ctx
         x0p = x0.ctypes.data if x0 is not None else None
         if self.folds:
@@ -567,6 +631,21 @@ class DEMetropolisZ(object):
         for i, name in enumerate(self.names):
             rows[:, PARAM_NAMES.index(name)] = samples[:, i]
         return rows
+
+    def penalty(self, trace, burn=0, thin=1):
+        '''The annual-precipitation penalty (chains, k) of every kept draw of ``trace`` (after
+        ``burn``, every ``thin``-th), up to ``max_draws`` rows per launch; a problem bound with
+        ``annual_precip``, whether or not the sampler ran with ``constraints``.'''
+        if not getattr(self.problem, 'has_annual', False):
+            raise ValueError('penalty() needs a problem bound with annual_precip')
+        post = trace.posterior(burn, thin)
+        x = np.stack([post[name] for name in self.names], axis=-1)          # (chains, k, d)
+        rows = self.rows(x.reshape(-1, self.d))
+        out = np.empty(rows.shape[0])
+        step = self.problem.max_draws
+        for a in range(0, rows.shape[0], step):
+            out[a:a + step] = self.problem.penalty(rows[a:a + step])
+        return out.reshape(x.shape[:2])
 
     def heldout(self, trace, burn=0, thin=1):
         '''Scores a ``KFoldTrace`` of this sampler on the site-days each fold held out:

@@ -14,11 +14,14 @@ struct EvalWs {
     double *par16 = nullptr, *partial = nullptr, *redo = nullptr, *sse = nullptr, *cnt = nullptr;
     unsigned *any_gs = nullptr, *any_draw = nullptr;
     const int32_t* code = nullptr;      // [ndraw] fold code per draw (the FOLD kernels); NULL: plain draws
+    // the annual-precipitation constraint (mod16_static_batch_set_annual); mass NULL: plain draws
+    double *mass = nullptr, *rmass = nullptr, *penalty = nullptr;
 };
 // Its two parts inside an allocation at `base` (NULL: sizes only), with the extents the kernels of
 // mod16_methods.hpp index. Per draw (`el`: bytes of the data type): params [draws][11], par16
-// [draws][kPar16], sse / cnt / any_draw [draws], redo [draws][5] ...
-static size_t eval_layout_draws(int64_t draws, size_t el, void* base, EvalWs* w) {
+// [draws][kPar16], sse / cnt / any_draw [draws], redo [draws][5], and for a problem with G site-years
+// (G = 0: none) penalty [draws], rmass [draws][G][2] ...
+static size_t eval_layout_draws(int64_t draws, size_t el, void* base, EvalWs* w, int G = 0) {
     EvalWs sizes_only;
     if (!w) w = &sizes_only;
     Carver c(base);
@@ -29,18 +32,24 @@ static size_t eval_layout_draws(int64_t draws, size_t el, void* base, EvalWs* w)
     w->cnt = c.take<double>(D * sizeof(double));
     w->redo = c.take<double>(D * 5 * sizeof(double));
     w->any_draw = c.take<unsigned>(D * sizeof(unsigned));
+    if (G) {
+        w->penalty = c.take<double>(D * sizeof(double));
+        w->rmass = c.take<double>(D * (size_t)G * 2 * sizeof(double));
+    }
     return c.used;
 }
 // ... and per block of kBlock pixels: partial [gx][draws][2], any_gs [gx][draws] (draws x blocks x 20
 // bytes: 3.2 GB at 4096 draws x 10 M pixels, so the problem sizes this part for the draws an
-// evaluation actually brings, not for max_draws; an EXACT problem never has it)
-static size_t eval_layout_blocks(int64_t draws, int gx, void* base, EvalWs* w) {
+// evaluation actually brings, not for max_draws; an EXACT problem never has it); `annual`: and per wave
+// of 64 pixels mass [gx * kBlock / 64][draws]
+static size_t eval_layout_blocks(int64_t draws, int gx, void* base, EvalWs* w, bool annual = false) {
     EvalWs sizes_only;
     if (!w) w = &sizes_only;
     Carver c(base);
     const size_t cells = (size_t)draws * (size_t)gx;
     w->partial = c.take<double>(cells * 2 * sizeof(double));
     w->any_gs = c.take<unsigned>(cells * sizeof(unsigned));
+    if (annual) w->mass = c.take<double>(cells * (kBlock / 64) * sizeof(double));
     return c.used;
 }
 
@@ -82,7 +91,8 @@ struct mod16_batch {
     int device = 0;
     bool f32 = false;
     unsigned flags = 0;
-    int64_t n = 0, max_draws = 0;
+    int64_t n = 0, max_draws = 0;       // n: the resident arrays' pixels (with the constraint: padding included)
+    int64_t n_user = 0;                 // the caller's n (mod16_static_batch_info, the rows)
     int gx = 0;
     void* owned = nullptr;              // the resident copies (HOST bind); NULL when the caller's device arrays are used
     const void* drv[14] = {};
@@ -109,17 +119,30 @@ struct mod16_batch {
     int nfolds = 0;
     int32_t* dcode = nullptr;           // [max_draws] device
     int32_t* hcode = nullptr;           // [max_draws] pinned staging
-    CachedGraph graph, fgraph;          // the plain and the fold objective, key = draws
+    // the annual-precipitation constraint (mod16_static_batch_set_annual): the resident arrays are laid
+    // out site-year-major, every site-year padded to whole waves (the kernels' comment in
+    // mod16_methods.hpp); G = 0: none
+    int G = 0;                          // site-years, g = year * sites + site
+    double S = 0.0;                     // sum of the limits
+    void* annual = nullptr;             // one allocation: the tables below
+    const double* scale = nullptr;      // [n] 86400 / lhv, 0 = padding (inside `owned`)
+    int32_t* wstart = nullptr;          // [G + 1] first wave of each site-year
+    double* limit = nullptr;            // [G] annual_precip
+    int64_t* lstart = nullptr;          // [G + 1] first entry of `list` of each site-year
+    int64_t* pos = nullptr;             // [n_user] where the caller's pixel lies
+    CachedGraph graph, fgraph, agraph;  // the plain, the fold and the constrained objective, key = draws
     CachedGraph* last = nullptr;        // the one the last objective call launched (mod16_static_batch_time)
     int samplers = 0;                   // samplers alive on the problem (capi/mcmc.hip)
 };
 
 // w.code set: the FOLD instances (the problem's labels, the draws' fold codes); otherwise the plain ones.
 // (Folds exist on float64 problems only: kFold keeps float32 FOLD instances out of the library.)
+// w.mass set (never together with w.code): the ANNUAL instances and the penalty's two kernels.
 template <typename T>
 static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int64_t ndraw) {
     constexpr bool kFold = std::is_same<T, double>::value;
     const bool fold = kFold && w.code != nullptr;
+    const bool annual = kFold && !fold && w.mass != nullptr;
     hipStream_t st = b->st;
     const unsigned gd = (unsigned)((ndraw + kBlock - 1) / kBlock);
     hipLaunchKernelGGL((static_obj_params_kernel<T>), dim3(gd), dim3(kBlock), 0, st, static_cast<const T*>(w.params), ndraw, w.par16);
@@ -139,8 +162,11 @@ static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int6
     a.any_gs = w.any_gs;
     a.code = w.code;
     a.label = fold ? b->label : nullptr;
+    a.scale = annual ? b->scale : nullptr;
+    a.mass = annual ? w.mass : nullptr;
     const dim3 grid((unsigned)b->gx, (unsigned)((ndraw + kObjDraws - 1) / kObjDraws));
     if (fold) hipLaunchKernelGGL((static_obj_kernel<T, true, kFold>), grid, dim3(kBlock), 0, st, a);
+    else if (annual) hipLaunchKernelGGL((static_obj_kernel<T, true, false, kFold>), grid, dim3(kBlock), 0, st, a);
     else hipLaunchKernelGGL((static_obj_kernel<T, true>), grid, dim3(kBlock), 0, st, a);
     if (b->nlist) {
         StaticObjRedoArgs<T> r;
@@ -157,13 +183,30 @@ static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int6
         r.label = a.label;
         if (fold) hipLaunchKernelGGL((static_obj_redo_kernel<T, kFold>), dim3((unsigned)ndraw), dim3(kBlock), 0, st, r);
         else hipLaunchKernelGGL((static_obj_redo_kernel<T>), dim3((unsigned)ndraw), dim3(kBlock), 0, st, r);
+        if constexpr (kFold) if (annual) {      // (float64 only, as the ANNUAL instances)
+            StaticAnnualRedoArgs<T> m;
+            memset(&m, 0, sizeof m);
+            for (int k = 0; k < 14; ++k) m.drv[k] = r.drv[k];
+            m.dense_drv = r.dense_drv;
+            m.params = r.params;
+            m.scale = b->scale;
+            m.list = b->list;
+            m.lstart = b->lstart;
+            m.G = b->G;
+            m.rmass = w.rmass;
+            hipLaunchKernelGGL((static_annual_redo_kernel<T>), dim3((unsigned)ndraw), dim3(kBlock), 0, st, m);
+        }
     }
     const double* redo = b->nlist ? w.redo : nullptr;
     const unsigned gr = (unsigned)((ndraw + kObjPerBlock - 1) / kObjPerBlock);
     hipLaunchKernelGGL(static_obj_any_kernel, dim3(gr), dim3(kBlock), 0, st, w.any_gs, redo, ndraw, b->gx, w.any_draw);
     if (fold) hipLaunchKernelGGL((static_obj_kernel<T, false, kFold>), grid, dim3(kBlock), 0, st, a);
+    else if (annual) hipLaunchKernelGGL((static_obj_kernel<T, false, false, kFold>), grid, dim3(kBlock), 0, st, a);
     else hipLaunchKernelGGL((static_obj_kernel<T, false>), grid, dim3(kBlock), 0, st, a);
     hipLaunchKernelGGL(static_obj_final_kernel, dim3(gr), dim3(kBlock), 0, st, w.partial, redo, w.any_draw, ndraw, b->gx,
                        w.sse, w.cnt);
+    if (annual)
+        hipLaunchKernelGGL(static_annual_final_kernel, dim3(gr), dim3(kBlock), 0, st, w.mass, b->nlist ? w.rmass : nullptr,
+                           w.any_draw, b->wstart, b->limit, b->G, b->S, ndraw, w.penalty);
 }
 

@@ -315,10 +315,11 @@ extern "C" int mod16_et_static_batch_f32(mod16_ctx* ctx, const float* const* dri
                                      out_total, observed, weights, sse, count, flags, where, stream);
 }
 
-// the problem's cached objective graphs (plain and fold)
+// the problem's cached objective graphs (plain, fold and constrained)
 static void batch_drop_graphs(mod16_batch* b) {
     b->graph.drop();
     b->fgraph.drop();
+    b->agraph.drop();
     b->last = nullptr;
 }
 
@@ -330,6 +331,7 @@ extern "C" int mod16_static_batch_destroy(mod16_batch* b) {
     if (b->label) (void)hipFree(b->label);
     if (b->dcode) (void)hipFree(b->dcode);
     if (b->hcode) (void)hipHostFree(b->hcode);
+    if (b->annual) (void)hipFree(b->annual);
     if (b->owned) (void)hipFree(b->owned);
     if (b->skip) (void)hipFree(b->skip);
     if (b->list) (void)hipFree(b->list);
@@ -376,7 +378,7 @@ static int batch_bind(mod16_ctx* ctx, const T* const* drivers, const int64_t* ds
     b->device = ctx->device;
     b->f32 = std::is_same<T, float>::value;
     b->flags = flags;
-    b->n = n;
+    b->n = b->n_user = n;
     b->max_draws = max_draws;
     b->gx = (int)((n + kBlock - 1) / kBlock);
     int rc = [&]() -> int {
@@ -453,7 +455,7 @@ extern "C" int mod16_static_batch_bind_f32(mod16_ctx* ctx, const float* const* d
 
 extern "C" int mod16_static_batch_info(const mod16_batch* b, int64_t* n, int64_t* max_draws, int64_t* n_outside_domain) {
     if (!b) return MOD16_ERR_ARG;
-    if (n) *n = b->n;
+    if (n) *n = b->n_user;
     if (max_draws) *max_draws = b->max_draws;
     if (n_outside_domain) *n_outside_domain = b->nlist;
     return MOD16_OK;
@@ -472,10 +474,10 @@ static int batch_eval_ws(mod16_batch* b, int64_t ndraw) {
     if (b->eval_ws) HIPCHK(ctx, hipFree(b->eval_ws));
     b->eval_ws = nullptr;
     b->eval_draws = 0;
-    int rc = dev_alloc(ctx, &b->eval_ws, eval_layout_blocks(want, b->gx, nullptr, nullptr),
+    int rc = dev_alloc(ctx, &b->eval_ws, eval_layout_blocks(want, b->gx, nullptr, nullptr, b->G != 0),
                        "mod16_static_batch_objective: device memory for the per-block partials of this many draws");
     if (rc != MOD16_OK) return rc;
-    eval_layout_blocks(want, b->gx, b->eval_ws, &b->own);
+    eval_layout_blocks(want, b->gx, b->eval_ws, &b->own, b->G != 0);
     b->eval_draws = want;
     return MOD16_OK;
 }
@@ -491,9 +493,11 @@ static int rows_reserve(mod16_batch* b, size_t need, const char* what) {
     return rc;
 }
 
-// code: NULL (plain draws) or the fold code of every draw (mod16_static_batch_objective_folds, checked)
+// code: NULL (plain draws) or the fold code of every draw (mod16_static_batch_objective_folds, checked);
+// penalty: NULL, or where the constraint's penalty of every draw goes (mod16_static_batch_objective_annual)
 template <typename T>
-static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const int32_t* code, double* sse, double* count) {
+static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const int32_t* code, double* sse, double* count,
+                           double* penalty = nullptr) {
     mod16_ctx* ctx = b->ctx;
     if (!params || !sse || !count || ndraw < 0 || ndraw > b->max_draws)
         return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_objective: NULL argument or more draws than the problem was bound for");
@@ -518,11 +522,12 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const
     } else {
         int rc = batch_eval_ws(b, ndraw);
         if (rc != MOD16_OK) return rc;
-        CachedGraph& g = code ? b->fgraph : b->graph;       // (plain and fold calls keep a graph each)
+        CachedGraph& g = penalty ? b->agraph : code ? b->fgraph : b->graph;     // (each kind of call keeps a graph)
         if (g.key != ndraw) {                   // (re)capture: the kernels' arguments hold the number of draws
             if (b->last == &g) b->last = nullptr;
             EvalWs w = b->own;
             w.code = code ? b->dcode : nullptr;
+            if (!penalty) w.mass = nullptr;
             rc = g.capture(ctx, b->st, ndraw, [&] { batch_objective_launches<T>(b, w, ndraw); });
             if (rc != MOD16_OK) return rc;
         }
@@ -531,9 +536,12 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const
     }
     HIPCHK(ctx, hipMemcpyAsync(b->hout, b->own.sse, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
     HIPCHK(ctx, hipMemcpyAsync(b->hout + b->max_draws, b->own.cnt, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
+    if (penalty)
+        HIPCHK(ctx, hipMemcpyAsync(b->hout + 2 * b->max_draws, b->own.penalty, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
     HIPCHK(ctx, hipStreamSynchronize(b->st));
     memcpy(sse, b->hout, sizeof(double) * (size_t)ndraw);
     memcpy(count, b->hout + b->max_draws, sizeof(double) * (size_t)ndraw);
+    if (penalty) memcpy(penalty, b->hout + 2 * b->max_draws, sizeof(double) * (size_t)ndraw);
     return MOD16_OK;
 }
 
@@ -552,6 +560,7 @@ extern "C" int mod16_static_batch_set_folds(mod16_batch* b, const uint8_t* label
     if (b->f32 || (b->flags & MOD16_MATH_EXACT) || !b->obs)
         return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: folds need a float64 MOD16_MATH_FAST problem bound with observations");
     if (b->label) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: the problem already has folds");
+    if (b->G) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: the problem has the annual-precipitation constraint (not combined with folds)");
     if (b->samplers) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: a sampler exists on the problem");
     if (!labels || nfolds < 2 || nfolds > 255)
         return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: NULL labels or nfolds outside 2 .. 255");
@@ -599,6 +608,193 @@ extern "C" int mod16_static_batch_objective_folds(mod16_batch* b, const void* pa
     return batch_objective<double>(b, static_cast<const double*>(params), ndraw, code, sse, count);
 }
 
+// ---- the annual-precipitation constraint: the problem laid out site-year-major (mod16_methods.hpp,
+// above static_annual_redo_kernel), the limits and the scale 86400 / lhv resident
+extern "C" int mod16_static_batch_set_annual(mod16_batch* b, int64_t T, int64_t N, const int32_t* year_index, int Y,
+                                             const double* annual_precip, const double* lhv) {
+    if (!b) return MOD16_ERR_ARG;
+    MOD16_LOCK(b->ctx);
+    mod16_ctx* ctx = b->ctx;
+    if (b->f32 || (b->flags & MOD16_MATH_EXACT) || !b->obs || !b->owned)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: the constraint needs a float64 MOD16_MATH_FAST problem bound from HOST arrays with observations");
+    if (b->G) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: the problem already has the constraint");
+    if (b->label) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: the problem has folds (not combined with the constraint)");
+    if (b->samplers) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: a sampler exists on the problem");
+    const int64_t n = b->n;
+    if (!year_index || !annual_precip || !lhv || T < 1 || N < 1 || T > n || N > n || T * N != n)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: NULL argument, or T x N is not the problem's n");
+    if (Y < 1 || (int64_t)Y > T || (int64_t)Y * N > (int64_t)1 << 28)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: Y outside 1 .. T, or more than 2^28 site-years");
+    std::vector<int64_t> days((size_t)Y, 0), rank((size_t)T);
+    for (int64_t t = 0; t < T; ++t) {
+        if (year_index[t] < 0 || year_index[t] >= Y)
+            return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: a year index outside 0 .. Y - 1");
+        rank[(size_t)t] = days[(size_t)year_index[t]]++;
+    }
+    for (int y = 0; y < Y; ++y)
+        if (!days[(size_t)y]) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: a year without any day");
+    const int G = (int)(Y * N);
+    double S = 0.0;
+    for (int g = 0; g < G; ++g) {
+        if (!std::isfinite(annual_precip[g])) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: annual_precip must be finite");
+        S += annual_precip[g];
+    }
+    if (!(S > 0.0) || !std::isfinite(S)) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: the sum of annual_precip must be > 0 and finite");
+    for (int64_t i = 0; i < n; ++i)
+        if (!(lhv[i] > 0.0) || !std::isfinite(lhv[i])) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: lhv must be finite and > 0");
+    // the layout: site-year g = y N + s holds its days in order, then copies of its last day up to a
+    // multiple of 64 (src < 0: padding, -(pixel + 1))
+    std::vector<int64_t> gstart((size_t)G + 1, 0);
+    for (int g = 0; g < G; ++g) gstart[(size_t)g + 1] = gstart[(size_t)g] + (days[(size_t)(g / N)] + 63) / 64 * 64;
+    const int64_t ni = gstart[(size_t)G];
+    if (ni / 64 > 0x7fffffff) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_annual: too many pixels");
+    std::vector<int64_t> src, pos;
+    std::vector<double> in, out;
+    std::vector<uint8_t> mask_in, mask;
+    std::vector<int64_t> list, lstart((size_t)G + 1, 0);
+    std::vector<int32_t> wstart((size_t)G + 1);
+    try {
+        src.assign((size_t)ni, -1);
+        pos.resize((size_t)n);
+        in.resize((size_t)n);
+        out.resize((size_t)ni);
+        mask_in.resize((size_t)n);
+        mask.resize((size_t)ni);
+    } catch (const std::bad_alloc&) {
+        return fail(ctx, MOD16_ERR_NOMEM, "mod16_static_batch_set_annual: host memory for the reordering");
+    }
+    for (int64_t t = 0; t < T; ++t)
+        for (int64_t s = 0; s < N; ++s) {
+            const int64_t g = (int64_t)year_index[t] * N + s, k = gstart[(size_t)g] + rank[(size_t)t];
+            src[(size_t)k] = t * N + s;
+            pos[(size_t)(t * N + s)] = k;
+        }
+    for (int g = 0; g < G; ++g) {
+        const int64_t real = days[(size_t)(g / N)], k0 = gstart[(size_t)g];
+        for (int64_t k = k0 + real; k < gstart[(size_t)g + 1]; ++k) src[(size_t)k] = -(src[(size_t)(k0 + real - 1)] + 1);
+        wstart[(size_t)g] = (int32_t)(k0 / 64);
+    }
+    wstart[(size_t)G] = (int32_t)(ni / 64);
+    auto from = [&](int64_t k) { const int64_t v = src[(size_t)k]; return (size_t)(v < 0 ? -(v + 1) : v); };
+    HIPCHK(ctx, hipSetDevice(b->device));
+    HIPCHK(ctx, hipStreamSynchronize(b->st));
+    // everything new is made first; the problem changes only once nothing can fail any more
+    void *owned = nullptr, *tables = nullptr, *ws = nullptr, *hout = nullptr;
+    uint8_t* skip = nullptr;
+    int64_t* dlist = nullptr;
+    const size_t per_new = align256((size_t)ni * sizeof(double));
+    const int64_t D = b->max_draws;
+    const size_t per_draw = eval_layout_draws(D, sizeof(double), nullptr, nullptr, G);
+    Carver tc;
+    int rc = [&]() -> int {
+        const char* what = "mod16_static_batch_set_annual: device memory for the reordered problem";
+        int r = dev_alloc(ctx, &owned, per_new * 17, what);
+        if (r != MOD16_OK) return r;
+        char* base = static_cast<char*>(owned);
+        for (int k = 0; k < 16; ++k) {
+            const void* cur = k < 14 ? b->drv[k] : k == 14 ? b->obs : b->wts;
+            if (!cur) continue;
+            const bool dense = k >= 14 || ((b->dense_drv >> k) & 1u);
+            HIPCHK(ctx, hipMemcpy(in.data(), cur, sizeof(double) * (size_t)(dense ? n : 1), hipMemcpyDeviceToHost));
+            if (dense)
+                for (int64_t j = 0; j < ni; ++j)
+                    out[(size_t)j] = (k == 14 && src[(size_t)j] < 0) ? std::numeric_limits<double>::quiet_NaN() : in[from(j)];
+            else
+                out[0] = in[0];
+            HIPCHK(ctx, hipMemcpy(base + per_new * k, out.data(), sizeof(double) * (size_t)(dense ? ni : 1), hipMemcpyHostToDevice));
+        }
+        for (int64_t j = 0; j < ni; ++j) out[(size_t)j] = src[(size_t)j] < 0 ? 0.0 : 86400.0 / lhv[from(j)];
+        HIPCHK(ctx, hipMemcpy(base + per_new * 16, out.data(), sizeof(double) * (size_t)ni, hipMemcpyHostToDevice));
+        // the domain mask goes with its pixels; the list and each site-year's part of it
+        HIPCHK(ctx, hipMemcpy(mask_in.data(), b->skip, (size_t)n, hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < ni; ++j) {
+            mask[(size_t)j] = mask_in[from(j)];
+            if (mask[(size_t)j]) list.push_back(j);
+        }
+        for (int g = 0, u = 0; g <= G; ++g) {
+            while ((size_t)u < list.size() && list[(size_t)u] < gstart[(size_t)g]) ++u;
+            lstart[(size_t)g] = u;
+        }
+        r = dev_alloc(ctx, &skip, (size_t)ni, what);
+        if (r != MOD16_OK) return r;
+        HIPCHK(ctx, hipMemcpy(skip, mask.data(), (size_t)ni, hipMemcpyHostToDevice));
+        if (!list.empty()) {
+            r = dev_alloc(ctx, &dlist, sizeof(int64_t) * list.size(), what);
+            if (r != MOD16_OK) return r;
+            HIPCHK(ctx, hipMemcpy(dlist, list.data(), sizeof(int64_t) * list.size(), hipMemcpyHostToDevice));
+        }
+        auto carve = [&](void* at) {
+            tc = Carver(at);
+            b->wstart = tc.take<int32_t>(sizeof(int32_t) * ((size_t)G + 1));
+            b->limit = tc.take<double>(sizeof(double) * (size_t)G);
+            b->lstart = tc.take<int64_t>(sizeof(int64_t) * ((size_t)G + 1));
+            b->pos = tc.take<int64_t>(sizeof(int64_t) * (size_t)n);
+            return tc.used;
+        };
+        r = dev_alloc(ctx, &tables, carve(nullptr), what);
+        if (r == MOD16_OK) r = dev_alloc(ctx, &ws, per_draw + align256((size_t)D * sizeof(unsigned)), what);
+        if (r != MOD16_OK) return r;
+        HIPCHK(ctx, hipHostMalloc(&hout, (size_t)D * 24));
+        carve(tables);
+        HIPCHK(ctx, hipMemcpy(b->wstart, wstart.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(b->limit, annual_precip, sizeof(double) * (size_t)G, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(b->lstart, lstart.data(), sizeof(int64_t) * ((size_t)G + 1), hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(b->pos, pos.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice));
+        return MOD16_OK;
+    }();
+    if (rc != MOD16_OK) {
+        if (owned) (void)hipFree(owned);
+        if (tables) (void)hipFree(tables);
+        if (ws) (void)hipFree(ws);
+        if (hout) (void)hipHostFree(hout);
+        if (skip) (void)hipFree(skip);
+        if (dlist) (void)hipFree(dlist);
+        b->wstart = nullptr;
+        b->limit = nullptr;
+        b->lstart = b->pos = nullptr;
+        return rc;
+    }
+    // the problem takes the new arrays; the graphs and the per-block workspace held the old geometry
+    batch_drop_graphs(b);
+    if (b->eval_ws) (void)hipFree(b->eval_ws);
+    b->eval_ws = nullptr;
+    b->eval_draws = 0;
+    (void)hipFree(b->owned);
+    (void)hipFree(b->skip);
+    if (b->list) (void)hipFree(b->list);
+    (void)hipFree(b->ws);
+    (void)hipHostFree(b->hout);
+    b->owned = owned;
+    char* base = static_cast<char*>(owned);
+    for (int k = 0; k < 14; ++k) b->drv[k] = base + per_new * k;
+    b->obs = base + per_new * 14;
+    if (b->wts) b->wts = base + per_new * 15;
+    b->scale = reinterpret_cast<const double*>(base + per_new * 16);
+    b->skip = skip;
+    b->list = dlist;
+    b->nlist = (int64_t)list.size();
+    b->annual = tables;
+    b->ws = ws;
+    b->own = EvalWs();
+    eval_layout_draws(D, sizeof(double), b->ws, &b->own, G);
+    b->dflags = reinterpret_cast<unsigned*>(static_cast<char*>(b->ws) + per_draw);
+    b->hout = static_cast<double*>(hout);
+    b->n = ni;
+    b->gx = (int)((ni + kBlock - 1) / kBlock);
+    b->G = G;
+    b->S = S;
+    return MOD16_OK;
+}
+
+extern "C" int mod16_static_batch_objective_annual(mod16_batch* b, const void* params, int64_t ndraw, double* sse, double* count,
+                                                   double* penalty) {
+    if (!b) return MOD16_ERR_ARG;
+    MOD16_LOCK(b->ctx);
+    if (!b->G) return fail(b->ctx, MOD16_ERR_ARG, "mod16_static_batch_objective_annual: the problem has no constraint (mod16_static_batch_set_annual)");
+    if (!penalty) return fail(b->ctx, MOD16_ERR_ARG, "mod16_static_batch_objective_annual: NULL penalty");
+    return batch_objective<double>(b, static_cast<const double*>(params), ndraw, nullptr, sse, count, penalty);
+}
+
 // rows [ndraw][n] (host) of the bound problem: the kernels of the unbound call on the resident drivers
 template <typename T>
 static int batch_rows(mod16_batch* b, const T* params, int64_t ndraw, T* out_day, T* out_night, T* out_total) {
@@ -608,8 +804,10 @@ static int batch_rows(mod16_batch* b, const T* params, int64_t ndraw, T* out_day
     if (ndraw == 0) return MOD16_OK;
     HIPCHK(ctx, hipSetDevice(b->device));
     T* const host_out[3] = {out_day, out_night, out_total};
-    const size_t per_out = sizeof(T) * (size_t)ndraw * (size_t)b->n;
-    int rc = rows_reserve(b, align256(per_out) * ((out_day != nullptr) + (out_night != nullptr) + (out_total != nullptr)),
+    // (a problem laid out site-year-major, b->pos: the rows of the resident pixels, then the caller's gathered from them)
+    const size_t per_out = sizeof(T) * (size_t)ndraw * (size_t)b->n, per_user = sizeof(T) * (size_t)ndraw * (size_t)b->n_user;
+    int rc = rows_reserve(b, (align256(per_out) + (b->pos ? align256(per_user) : 0)) *
+                                 ((out_day != nullptr) + (out_night != nullptr) + (out_total != nullptr)),
                           "mod16_static_batch_rows: device memory for the [ndraw][n] rows");
     if (rc != MOD16_OK) return rc;
     memcpy(b->hparams, params, sizeof(T) * (size_t)ndraw * 11);
@@ -620,8 +818,20 @@ static int batch_rows(mod16_batch* b, const T* params, int64_t ndraw, T* out_day
         if (host_out[k]) a.out[k] = c.take<T>(per_out);
     rc = static_batch_rows<T>(ctx, a, ndraw, nullptr, nullptr, nullptr, nullptr, b->dflags, b->skip, b->flags, b->st, true);
     if (rc != MOD16_OK) return rc;
+    if (b->pos) {
+        const int64_t total = ndraw * b->n_user;
+        const unsigned gg = (unsigned)std::min<int64_t>((total + kBlock - 1) / kBlock, (int64_t)b->ctx->cus * 64);
+        for (int k = 0; k < 3; ++k)
+            if (host_out[k]) {
+                T* user = c.take<T>(per_user);
+                hipLaunchKernelGGL((static_rows_gather_kernel<T>), dim3(gg), dim3(kBlock), 0, b->st, (const T*)a.out[k], b->pos, b->n,
+                                   b->n_user, ndraw, user);
+                a.out[k] = user;
+            }
+        HIPCHK(ctx, hipGetLastError());
+    }
     for (int k = 0; k < 3; ++k)
-        if (host_out[k]) HIPCHK(ctx, hipMemcpyAsync(host_out[k], a.out[k], per_out, hipMemcpyDeviceToHost, b->st));
+        if (host_out[k]) HIPCHK(ctx, hipMemcpyAsync(host_out[k], a.out[k], per_user, hipMemcpyDeviceToHost, b->st));
     HIPCHK(ctx, hipStreamSynchronize(b->st));
     return MOD16_OK;
 }

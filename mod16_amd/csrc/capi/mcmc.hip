@@ -104,6 +104,10 @@ static int mcmc_check_spec(mod16_ctx* ctx, const mod16_batch* b, const mod16_mcm
                 if (fold[h] == fold[g]) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create_groups: a fold listed twice");
         }
     }
+    if (s->constraints & ~MOD16_CONSTRAINT_ANNUAL_PRECIP)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: unknown bits in constraints");
+    if (s->constraints && (fold || !b->G))
+        return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: the annual-precipitation constraint needs a problem that has it (mod16_static_batch_set_annual) and no folds");
     if (s->chains < 1 || (int64_t)s->chains * ngroups > b->max_draws)
         return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: chains (x groups) outside 1 .. the problem's max_draws");
     if (s->nfree < 1 || s->nfree > kMcmcMaxD) return fail(ctx, MOD16_ERR_ARG, "mod16_mcmc_create: nfree outside 1 .. 11");
@@ -215,12 +219,16 @@ static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, int ngroups, co
         state(m->state);
         // the objective's workspace for C draws, both parts: the sampler's own (see EvalWs); behind it
         // the groups' TRAIN codes, constant for the sampler's life and read by its graphs
-        const size_t per_draw = eval_layout_draws(C, 8, nullptr, nullptr), per_block = eval_layout_blocks(C, b->gx, nullptr, nullptr);
+        // (with the constraint: its per-draw and per-wave parts too, so the graphs run the ANNUAL launches)
+        const bool annual = (s->constraints & MOD16_CONSTRAINT_ANNUAL_PRECIP) != 0;
+        const int G = annual ? b->G : 0;
+        const size_t per_draw = eval_layout_draws(C, 8, nullptr, nullptr, G), per_block = eval_layout_blocks(C, b->gx, nullptr, nullptr, annual);
         r = dev_alloc(ctx, &m->eval, per_draw + per_block + (fold ? align256((size_t)C * 4) : 0), "mod16_mcmc_create: device memory for the objective's workspace");
         if (r != MOD16_OK) return r;
         char* ev = static_cast<char*>(m->eval);
-        eval_layout_draws(C, 8, ev, &m->w);
-        eval_layout_blocks(C, b->gx, ev + per_draw, &m->w);
+        eval_layout_draws(C, 8, ev, &m->w, G);
+        eval_layout_blocks(C, b->gx, ev + per_draw, &m->w, annual);
+        a.penalty = m->w.penalty;
         a.params = static_cast<double*>(m->w.params);
         a.sse = m->w.sse;
         a.cnt = m->w.cnt;

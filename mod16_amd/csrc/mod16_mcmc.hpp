@@ -19,7 +19,10 @@
 // (LogNormal) or log(p / (1 - p)) with p = (x - a) / (b - a).
 //
 // Log-likelihood of the row's weighted (sse, count) (static_obj_final_kernel): objective 0 (rmsd)
-// -sqrt(sse / count); objective 1 (gaussian) -0.5 sse.
+// -sqrt(sse / count); objective 1 (gaussian) -0.5 sse. With the annual-precipitation constraint
+// (spec.constraints bit 0, a problem with mod16_static_batch_set_annual) the row's penalty
+// (static_annual_final_kernel, <= 0 or NaN) is added to either: loglik = objective + penalty. A NaN
+// penalty makes the log posterior NaN: rule 6 rejects the step.
 //
 // Random stream (mix: splitmix64's finaliser, the sobol_mix of mod16_sobol.hpp):
 //     r(c, t, k) = mix(mix(mix(seed) ^ c) ^ ((t << 6) | k))      chain c, step t (0-based, tuning
@@ -78,6 +81,7 @@ struct McmcArgs {
     // the objective's rows [chains][11] and its result [chains]
     double* params;
     const double *sse, *cnt;
+    const double* penalty;              // [chains] the constraint's penalty of the row, NULL: no constraint
 };
 
 // (mod16_sobol.hpp's kernels are not included here: its sobol_mix, restated)
@@ -152,7 +156,8 @@ __device__ inline void mcmc_row(const McmcArgs& a, int c) {
 __device__ inline double mcmc_loglik(const McmcArgs& a, int c) {
 #pragma clang fp contract(off)
     const double sse = a.sse[c], cnt = a.cnt[c];
-    return a.objective == 0 ? -sqrt(sse / cnt) : -0.5 * sse;
+    const double ll = a.objective == 0 ? -sqrt(sse / cnt) : -0.5 * sse;
+    return a.penalty ? ll + a.penalty[c] : ll;
 }
 
 // the initial point: x0 [chains][d] -> y, its row (the objective runs behind this kernel)

@@ -388,6 +388,9 @@ __global__ void __launch_bounds__(kBlock) static_batch_sse_kernel(const T* total
 //   static_obj_kernel<false>   the draws without it, evaluated again without transpiration (normally
 //                              none: every block reads 32 flags and ends)
 //   static_obj_final_kernel    partials of a draw added up in block order -> sse[d], count[d]
+// With the annual-precipitation constraint (ANNUAL instances of static_obj_kernel,
+// static_annual_redo_kernel behind the redo kernel, static_annual_final_kernel at the end) the same
+// chain also gives penalty[d]; see the comment above static_annual_redo_kernel.
 // Cross-validation (FOLD instances of the first two kernels and of the redo kernel): each pixel
 // carries a fold label (one byte), each draw a fold code f | kFoldHeldout. A TRAIN draw (bit clear)
 // admits the pixels with label != f, a HELDOUT draw those with label == f; a pixel that is not
@@ -437,6 +440,8 @@ template <typename T> struct StaticObjArgs {
     unsigned* any_gs;           // TR = true: [gridDim.x][ndraw], 1 = a pixel of the block has g_surf > 0
     const int32_t* code;        // FOLD: [ndraw] fold code of each draw
     const uint8_t* label;       // FOLD: [n] fold label of each pixel
+    const double* scale;        // ANNUAL: [n] 86400 / lhv of each pixel, 0 = a padding pixel (no mass)
+    double* mass;               // ANNUAL: [gridDim.x * kBlock / 64][ndraw], the mass of each wave's 64 pixels
 };
 
 // TR: evaluate with the transpiration term (any(g_surf > 0) assumed true; the block also reports
@@ -444,10 +449,17 @@ template <typename T> struct StaticObjArgs {
 // transpiration = 0 (mod16/__init__.py:343-348) -- normally none: the block reads 32 flags and ends.
 // FOLD: a draw sees only the pixels its fold code admits (fold_admits); the label is read once per
 // thread, the code is a scalar load next to the draw's parameters.
-template <typename T, bool TR, bool FOLD = false>
+// ANNUAL (the annual-precipitation constraint, see static_annual_final_kernel): also the mass
+// max(le scale, 0) of each draw, summed over the wave's 64 pixels -- one site-year, by the layout
+// the problem was given -- through the same staging in the same lane order: a pass stages 8 draws,
+// the residuals in rows 0 .. 7 and the masses in rows 8 .. 15, so the residual sums keep the bits of
+// the plain instance. One value per (wave, draw) goes to a.mass.
+template <typename T, bool TR, bool FOLD = false, bool ANNUAL = false>
 __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<T> a) {
     constexpr int kTab = FastMath<double>::kTabDoubles;
     constexpr int kWaves = kBlock / 64;
+    constexpr int kPass = ANNUAL ? kObjPass / 2 : kObjPass;      // draws staged at a time
+    __shared__ double wmass[ANNUAL ? kWaves : 1][kObjDraws];
     __shared__ __attribute__((aligned(16))) double tab[kTab];
     // (rows of 65: the column sums below read 16 rows at one lane offset -- with 64 doubles per row all
     // sixteen would hit the same banks)
@@ -475,6 +487,7 @@ __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<
     StaticPixel c;
     double obs = 0.0, w = 1.0;
     unsigned lab = 0;
+    double sc = 0.0;
     if (live) {
         auto dv = [&](int k) { return (double)(((a.dense_drv >> k) & 1u) ? a.drv[k][i] : a.drv[k][0]); };
         const PixelIn<double> x = {dv(0), dv(1), dv(2), dv(3), dv(4), dv(5), dv(6), dv(7), dv(8), dv(9), dv(10), dv(11), dv(12), dv(13)};
@@ -482,15 +495,16 @@ __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<
         obs = (double)a.observed[i];
         w = a.weights ? (double)a.weights[i] : 1.0;
         if (FOLD) lab = a.label[i];
+        if (ANNUAL) sc = a.scale[i];
     }
     unsigned cnt = 0;            // bit j: draw c0 + j has a pair (the residual is a number) at this pixel
     unsigned gs = 0;             // bit j: g_surf > 0 at this pixel for draw c0 + j
 #pragma unroll 1
-    for (int h = 0; h < kObjDraws; h += kObjPass) {
+    for (int h = 0; h < kObjDraws; h += kPass) {
 #pragma unroll 1
-        for (int jj = 0; jj < kObjPass; ++jj) {
+        for (int jj = 0; jj < kPass; ++jj) {
             const int j = h + jj;
-            double r2 = 0.0;
+            double r2 = 0.0, ms = 0.0;
             // (the code is read only for a wanted draw: draw c0 + j exists)
             if (live && ((want >> j) & 1u) && (!FOLD || fold_admits(lab, a.code[c0 + j]))) {
                 const double* q = a.par16 + (c0 + j) * kPar16;       // block-uniform: scalar loads
@@ -513,8 +527,13 @@ __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<
                 const bool ok = r == r;
                 r2 = ok ? r * r : 0.0;
                 cnt |= ok ? 1u << j : 0u;
+                if (ANNUAL) {
+                    const double v = (day + night) * sc;                       // mm per day; NaN stays NaN
+                    ms = sc > 0.0 ? (v < 0.0 ? 0.0 : v) : 0.0;
+                }
             }
             red[wave][jj][lane] = r2;
+            if (ANNUAL) red[wave][jj + kPass][lane] = ms;
         }
         // per-draw sums over the wave's 64 pixels, in lane order (lane l of quarter q adds lanes
         // 16 q .. 16 q + 15 of draw l & 15; then the quarters in order)
@@ -524,7 +543,13 @@ __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<
 #pragma unroll
         for (int l = 1; l < 16; ++l) s += red[wave][dj][qt * 16 + l];
         const double s1 = __shfl(s, dj + 16, 64), s2 = __shfl(s, dj + 32, 64), s3 = __shfl(s, dj + 48, 64);
-        if (lane < 16) wsum[wave][h + lane][0] = ((s + s1) + s2) + s3;
+        if (!ANNUAL) {
+            if (lane < 16) wsum[wave][h + lane][0] = ((s + s1) + s2) + s3;
+        } else if (lane < kPass) {
+            wsum[wave][h + lane][0] = ((s + s1) + s2) + s3;
+        } else if (lane < 16) {
+            wmass[wave][h + lane - kPass] = ((s + s1) + s2) + s3;
+        }
         __builtin_amdgcn_wave_barrier();
     }
     // pairs per draw: population counts of the lanes' bits
@@ -552,6 +577,11 @@ __global__ void __launch_bounds__(kBlock) static_obj_kernel(const StaticObjArgs<
         out[0] = s;
         out[1] = n;
         if (TR) a.any_gs[(int64_t)blockIdx.x * a.ndraw + (c0 + j)] = any;
+    }
+    if (ANNUAL) {
+        const int j = threadIdx.x & (kObjDraws - 1), wv = threadIdx.x / kObjDraws;
+        if (wv < kWaves && j < nd && ((want >> j) & 1u))
+            a.mass[((int64_t)blockIdx.x * kWaves + wv) * a.ndraw + (c0 + j)] = wmass[wv][j];
     }
 }
 
@@ -681,6 +711,104 @@ static __global__ void __launch_bounds__(kBlock) static_obj_final_kernel(const d
         }
         sse[d] = s;
         count[d] = n;
+    }
+}
+
+// ---- the annual-precipitation constraint (reference calibration.py:776-796, constrain_by_map):
+//   mass[t][n] = max(le[t][n] 86400 / lhv[t][n], 0), tot[y][n] = its sum over the days of year y,
+//   over = max(tot - annual_precip, 0), penalty = -100 mean(over^2) / sum(annual_precip)
+// with NaN kept by both max. The problem's pixels are laid out site-year-major (site-year
+// g = y N + n, its days in order, padded to a multiple of 64 with pixels that carry scale = 0), so a
+// wave of static_obj_kernel<ANNUAL> sees one site-year and waves wstart[g] .. wstart[g + 1] - 1 make
+// up site-year g.
+//
+// The listed pixels (outside the FAST domain, ascending: sorted by site-year; lstart[g] ..
+// lstart[g + 1] - 1 are site-year g's) in the reference's operation order, their mass per site-year
+// with and without transpiration, as static_obj_redo_kernel does their residuals. One block per
+// draw, one thread per site-year walking its pixels in order.
+template <typename T> struct StaticAnnualRedoArgs {
+    const T* drv[14];
+    uint32_t dense_drv;
+    const T* params;            // [ndraw][11]
+    const double* scale;        // [n]
+    const int64_t* list;        // flagged pixels
+    const int64_t* lstart;      // [G + 1]
+    int G;
+    double* rmass;              // [ndraw][G][2]: mass with transpiration, without
+};
+template <typename T>
+__global__ void __launch_bounds__(kBlock) static_annual_redo_kernel(const StaticAnnualRedoArgs<T> a) {
+    const int64_t draw = blockIdx.x;
+    for (int g = threadIdx.x; g < a.G; g += kBlock) {
+        double m1 = 0.0, m0 = 0.0;
+        for (int64_t u = a.lstart[g]; u < a.lstart[g + 1]; ++u) {
+#pragma clang fp contract(off)
+            const int64_t i = a.list[u];
+            const double sc = a.scale[i];
+            if (!(sc > 0.0)) continue;
+            auto dv = [&](int k) { return ((a.dense_drv >> k) & 1u) ? a.drv[k][i] : a.drv[k][0]; };
+            PixelIn<T> x = {dv(0), dv(1), dv(2), dv(3), dv(4), dv(5), dv(6), dv(7), dv(8), dv(9), dv(10), dv(11), dv(12), dv(13)};
+            const T* q = a.params + draw * 11;
+            ClassPar<T> p;
+            p.tmin_close = q[0]; p.tmin_open = q[1]; p.vpd_open = q[2]; p.vpd_close = q[3];
+            p.gl_sh = q[4]; p.gl_wv = q[5]; p.g_cut = q[6]; p.csl = q[7];
+            p.rbl_min = q[8]; p.rbl_max = q[9]; p.beta = q[10];
+            T day, night;
+            et_static_pixel(x, p, false, T(0), T(0), true, day, night);
+            double v = (double)(T)(day + night) * sc;
+            m1 += v < 0.0 ? 0.0 : v;
+            et_static_pixel(x, p, false, T(0), T(0), false, day, night);
+            v = (double)(T)(day + night) * sc;
+            m0 += v < 0.0 ? 0.0 : v;
+        }
+        a.rmass[(draw * a.G + g) * 2] = m1;
+        a.rmass[(draw * a.G + g) * 2 + 1] = m0;
+    }
+}
+
+// penalty[d]: per site-year the wave partials in wave order, then the listed pixels' mass (the
+// outcome any_draw[d] selects), over^2 of the site-years -- slice k adds site-years k, k + 8, ... in
+// order, the slices are added in order -- times -100 / G / S. A fixed order: the same bits on every
+// launch. Threads as static_obj_final_kernel (32 draws x 8 slices a block; [wave][draw] partials, so
+// 32 lanes read 32 consecutive doubles).
+static __global__ void __launch_bounds__(kBlock) static_annual_final_kernel(const double* mass, const double* rmass,
+                                                                     const unsigned* any_draw, const int32_t* wstart,
+                                                                     const double* limit, int G, double S, int64_t ndraw,
+                                                                     double* penalty) {
+    __shared__ double sm[kObjSlices][kObjPerBlock];
+    const int dl = threadIdx.x % kObjPerBlock, slice = threadIdx.x / kObjPerBlock;
+    const int64_t d = (int64_t)blockIdx.x * kObjPerBlock + dl;
+    double s = 0.0;
+    if (d < ndraw) {
+        const int o = rmass ? (any_draw[d] ? 0 : 1) : 0;
+        for (int g = slice; g < G; g += kObjSlices) {
+            const int w1 = wstart[g + 1];
+            double tot = 0.0;
+#pragma unroll 4
+            for (int w = wstart[g]; w < w1; ++w) tot += mass[(int64_t)w * ndraw + d];
+            if (rmass) tot += rmass[(d * G + g) * 2 + o];
+            const double df = tot - limit[g];
+            const double over = df < 0.0 ? 0.0 : df;            // NaN stays NaN
+            s += over * over;
+        }
+    }
+    sm[slice][dl] = s;
+    __syncthreads();
+    if (slice == 0 && d < ndraw) {
+#pragma unroll
+        for (int k = 1; k < kObjSlices; ++k) s += sm[k][dl];
+        penalty[d] = -100.0 * (s / (double)G) / S;
+    }
+}
+
+// HOST rows of a problem laid out site-year-major: out[d][i] = in[d][pos[i]], the caller's order
+template <typename T>
+__global__ void __launch_bounds__(kBlock) static_rows_gather_kernel(const T* in, const int64_t* pos, int64_t n_in, int64_t n,
+                                                                    int64_t ndraw, T* out) {
+    const int64_t total = ndraw * n, step = (int64_t)gridDim.x * kBlock;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += step) {
+        const int64_t d = e / n, i = e - d * n;
+        out[e] = in[d * n_in + pos[i]];
     }
 }
 

@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 9
+#define MOD16_ABI_VERSION 10
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -910,6 +910,57 @@ MOD16_API int mod16_sobol_rows_f64(mod16_ctx* ctx, const double* params, const d
 MOD16_API int mod16_sobol_analyze_f64(mod16_ctx* ctx, const double* y, int d, int64_t n,
                                       int second_order, int normalize, int resamples, uint64_t seed,
                                       double* idx_out, double* std_out, int where, void* stream);
+
+/*
+ * Ensemble forward run (ABI 10; mod16_amd.evapotranspiration_ensemble, RasterEngine.ensemble):
+ * MOD16.evapotranspiration for `members` parameter tables over one raster, reduced per pixel to
+ * the mean and the spread over the members. One kernel reads each pixel's drivers and class once,
+ * evaluates every member (the pixel's class picks its row in every table) and writes five arrays;
+ * nothing of size members x n exists, there are no atomics, two calls give the same bits.
+ *
+ *   function                 what it does
+ *   mod16_ensemble_create    tables[members][13][11] (HOST, float64, mod16_param column order) ->
+ *                            an ensemble on the ctx's device: the derived tables of
+ *                            mod16_set_bplut_f64, one per member, uploaded once (2 KiB each).
+ *                            MOD16_ERR_ARG unless 1 <= members <= 65536:
+ *                            "mod16_ensemble_create: members must be between 1 and 65536"
+ *   mod16_ensemble_destroy   frees it (NULL is fine); the ctx may be gone already
+ *   mod16_et_ensemble_f64    cls[n], drivers[14] with dstride[14] = 0 (broadcast scalar) / 1 (dense),
+ *   mod16_et_ensemble_f32    as mod16_et_*; out[5], all required, each [n]:
+ *                              out[0] mean_day    mean over the members of the day total
+ *                              out[1] mean_night  ... of the night total
+ *                              out[2] std_day     standard deviation (ddof = 0) of the day total
+ *                              out[3] std_night   ... of the night total
+ *                              out[4] std_total   ... of day + night (its mean is out[0] + out[1])
+ *
+ *   flags   MOD16_MATH_FAST (default): every member with the FAST float64 arithmetic, the part of it
+ *           that depends on the drivers alone computed once per pixel; pixels outside its domain
+ *           (the test of MOD16_MATH_FAST above) have ALL their members computed in the reference's
+ *           operation order. MOD16_MATH_EXACT: every pixel that way. Refused (MOD16_ERR_ARG):
+ *           "MOD16_MATH_MIXED is not available for the ensemble run" and
+ *           "MOD16_DOMAIN_TRUSTED is not available for the ensemble run".
+ *   float32 data: float64 arithmetic and accumulation under either flag, one rounding on store.
+ *   sums    sequential in member order, float64, one pass, shifted by member 0: identical tables give
+ *           a spread of exactly 0 and the mean of a one-member ensemble, bit for bit.
+ *   NaN     a member's NaN (classes without parameters, a NaN driver, a NaN row in ONE table) makes
+ *           that period's mean and spread and std_total NaN; an infinite member value leaves them
+ *           non-finite (which non-finite value is not specified).
+ *   class   a code >= 13 gives NaN and MOD16_ERR_CLASS_RANGE -- from the call with where =
+ *           MOD16_HOST, from mod16_check_status after a MOD16_DEVICE call.
+ *   where   MOD16_DEVICE: device pointers, asynchronous on `stream`; MOD16_HOST: host arrays, the
+ *           shared staging path of the other pixel-wise families (small calls copy-free, larger ones
+ *           in tiles of mod16_host_tile_pixels()), synchronous; the same kernel, the same bits.
+ */
+typedef struct mod16_ensemble mod16_ensemble;
+MOD16_API int mod16_ensemble_create(mod16_ctx* ctx, const double* tables, int64_t members,
+                                    mod16_ensemble** out);
+MOD16_API int mod16_ensemble_destroy(mod16_ensemble* ensemble);
+MOD16_API int mod16_et_ensemble_f64(mod16_ctx* ctx, const mod16_ensemble* ensemble, const uint8_t* cls,
+                                    const double* const* drivers, const int64_t* dstride, int64_t n,
+                                    double* const* out, unsigned flags, int where, void* stream);
+MOD16_API int mod16_et_ensemble_f32(mod16_ctx* ctx, const mod16_ensemble* ensemble, const uint8_t* cls,
+                                    const float* const* drivers, const int64_t* dstride, int64_t n,
+                                    float* const* out, unsigned flags, int where, void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,7 @@ Two ways in:
 
 __version__ = 'v1.2.0+mi355x.r1'
 
+import collections as _collections
 import ctypes as _ctypes
 
 import numpy as np
@@ -1310,6 +1311,97 @@ def evapotranspiration_raster(
         pressure, fpar, lai)
     return _forward(cls, drivers, None, separate, math, device, pet=pet, out=out,
                     devices=devices, table=table, diagnostics=diagnostics)
+
+
+EnsembleET = _collections.namedtuple('EnsembleET', 'mean_day mean_night std_day std_night std_total')
+
+
+def _ensemble_stack(tables, beta=None):
+    '''``tables`` of the ensemble entry points -> float64 (D, 13, 11): a (D, 13, 11) array, or a
+    sequence of D ``restore_bplut`` dicts; ``beta`` fills the ``beta`` column where a table has none.'''
+    from .utils import bplut_table
+    if isinstance(tables, np.ndarray) or not len(tables) or not isinstance(tables[0], dict):
+        stack = np.array(tables, np.float64)
+        if stack.ndim != 3 or stack.shape[1:] != (_lib.N_CLASSES, _lib.N_PARAMS):
+            raise ValueError('tables must have shape (members, 13, 11), got %r' % (stack.shape,))
+        if beta is not None:
+            fill = np.isnan(stack[:, :, 10]) & ~np.isnan(stack[:, :, 0])
+            stack[:, :, 10][fill] = beta
+        return stack
+    return np.stack([bplut_table(t, beta=beta) for t in tables])
+
+
+def evapotranspiration_ensemble(
+        tables, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, beta=None, math=_lib.MATH_FAST, device=0, out=None):
+    r'''
+    (Extension.) Forward run of an ENSEMBLE of parameter tables over a multi-class raster: what a
+    loop over ``evapotranspiration_raster(tables[m], cls, *drivers)`` followed by ``np.mean`` /
+    ``np.std`` over the members returns, from one kernel that reads each pixel's drivers once,
+    evaluates every member and keeps only the running sums (``mod16_et_ensemble_*``): the posterior
+    of a calibration (``mod16_amd.calibration.ensemble_tables``) as an ET map with its parameter
+    uncertainty.
+
+    Parameters
+    ----------
+    tables : numpy.ndarray or sequence of dict
+        (D, 13, 11) parameter tables (``MOD16.required_parameters`` column order), or D dicts as
+        ``restore_bplut`` returns them; 1 <= D <= 65536
+    cls : numpy.ndarray
+        Class raster as for ``evapotranspiration_raster``: a pixel's class picks its row in EVERY
+        table; codes without parameters give NaN, a code >= 13 raises IndexError
+    beta : float
+        (Optional) value for the ``beta`` column where a table has none
+    math : int
+        ``MATH_FAST`` (default) or ``MATH_EXACT``; the mixed and the trusted forms are refused
+    out : sequence of numpy.ndarray
+        (Optional) the five output arrays to write into
+
+    Returns
+    -------
+    EnsembleET
+        ``(mean_day, mean_night, std_day, std_night, std_total)`` [kg m-2 s-1]: mean and standard
+        deviation (``ddof = 0``) over the members of the day and night totals, and the standard
+        deviation of their sum (whose mean is ``mean_day + mean_night``). float32 only if every
+        driver array is float32 (computed in float64, rounded once). A NaN in any member makes that
+        period's mean and spread NaN. Pixels broadcast as in numpy; scalars stay scalars.
+    '''
+    stack = _ensemble_stack(tables, beta)
+    drivers = (
+        lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+        temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+        pressure, fpar, lai)
+    dtype = _result_dtype(drivers)
+    cls = np.asarray(cls)
+    if cls.dtype != np.uint8:
+        if cls.size and (cls.min() < 0 or cls.max() > 255):
+            raise IndexError('class code outside [0, 255]')
+        cls = cls.astype(np.uint8)
+    shape, n = _broadcast([_shape(v) for v in drivers] + [cls.shape])
+    keep, dptr, dstride = _marshal(drivers, shape, dtype)
+    cls = np.ascontiguousarray(np.broadcast_to(cls, shape))
+    if out is not None:
+        outs = list(out)
+        if len(outs) != 5:
+            raise ValueError('out must hold 5 arrays')
+        for o in outs:
+            if not (isinstance(o, np.ndarray) and o.shape == shape and o.dtype == dtype
+                    and o.flags.c_contiguous and o.flags.writeable):
+                raise ValueError('out arrays must be writeable C-contiguous %s arrays of shape %s'
+                                 % (dtype, shape))
+    else:
+        outs = [_lib.pinned.empty(shape, dtype) for _ in range(5)]
+    ens = _lib.Ensemble(_lib.context(device), stack)
+    try:
+        if n:
+            ens.run(dtype, cls.ctypes.data, dptr, dstride, n, [o.ctypes.data for o in outs],
+                    flags=math, where=_lib.HOST)
+    finally:
+        ens.close()
+    if not shape:
+        outs = [o[()] for o in outs]
+    return EnsembleET(*outs)
 
 
 def evapotranspiration_raw(

@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -247,6 +247,12 @@ PROTOTYPES = {
     'mod16_mcmc_read': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _I64P]),
     'mod16_mcmc_destroy': (C.c_int, [C.c_void_p]),
+    'mod16_ensemble_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    'mod16_ensemble_destroy': (C.c_int, [C.c_void_p]),
+    'mod16_et_ensemble_f64': (C.c_int, [
+        C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, _PP, C.c_uint, C.c_int, C.c_void_p]),
+    'mod16_et_ensemble_f32': (C.c_int, [
+        C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, _PP, C.c_uint, C.c_int, C.c_void_p]),
 }
 
 _lib = None
@@ -446,6 +452,41 @@ class Context:
 
     def check_status(self, stream=None):
         self.check(self.lib.mod16_check_status(self.handle, stream))
+
+
+class Ensemble:
+    '''D parameter tables on a context's device (``mod16_ensemble``): the members of an ensemble
+    forward run (``mod16_et_ensemble_*``). ``tables``: float64 (D, 13, 11), each as ``set_bplut`` takes.'''
+
+    def __init__(self, ctx, tables):
+        tables = np.ascontiguousarray(tables, np.float64)
+        if tables.ndim != 3 or tables.shape[1:] != (N_CLASSES, N_PARAMS):
+            raise ValueError('ensemble tables must have shape (members, 13, 11), got %r' % (tables.shape,))
+        self.ctx = ctx                  # keeps the context alive as long as its ensemble
+        self.handle = C.c_void_p()
+        self.members = int(tables.shape[0])
+        ctx.check(ctx.lib.mod16_ensemble_create(ctx.handle, tables.ctypes.data, self.members,
+                                                C.byref(self.handle)))
+
+    def run(self, dtype, cls, drivers, dstride, n, outs, flags=MATH_FAST, where=HOST, stream=None):
+        '''Thin wrapper of mod16_et_ensemble_f64 / _f32; every array argument is a raw address.'''
+        if not self.handle.value:
+            raise ValueError('the ensemble has been closed')
+        fn = self.ctx.lib.mod16_et_ensemble_f32 if np.dtype(dtype) == np.float32 \
+            else self.ctx.lib.mod16_et_ensemble_f64
+        self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers), i64_array(dstride),
+                          int(n), ptr_array(outs), int(flags), int(where), stream))
+
+    def close(self):
+        if getattr(self, 'handle', None) and self.handle.value:
+            self.ctx.lib.mod16_ensemble_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _host_ram_bytes():

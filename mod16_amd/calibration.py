@@ -30,7 +30,11 @@ arithmetic is stated in full at the top of ``mod16_amd/csrc/mod16_mcmc.hpp``):
   calibrations use): ``MOD16._et_bind(..., annual_precip=(years, precip))`` on a (T days x N sites)
   problem, ``problem.penalty(params)``, ``DEMetropolisZ(problem, ..., constraints=True)`` and
   ``sampler.penalty(trace)``; ``annual_precip_penalty`` states the formula in numpy. The sums per
-  site-year are made on the device inside the objective's launches; nothing of size draws x n exists.
+  site-year are made on the device inside the objective's launches; nothing of size draws x n exists;
+- ``ensemble_tables(table, posterior, members)``: from posteriors to the parameter tables of an
+  ensemble forward run (``mod16_amd.evapotranspiration_ensemble``, ``RasterEngine.ensemble``): joint
+  draws without replacement per PFT, host only -- what the reference's ``export_posterior``
+  (calibration.py:633-709) hands on, put onto a raster.
 
   The reference's own k-fold loop does not do what its docstring says, and this port does what the
   docstring says. (1) The restore-and-mask block (``tower_obs[idx] = np.nan`` and the driver filter,
@@ -367,6 +371,69 @@ class KFoldTrace(Trace):
         reference-shaped ``test_indices`` (``test_indices()``).'''
         super().to_npz(path, chain_fold=self.chain_fold, labels=self.labels,
                        test_indices=test_indices(self.labels, self.nfolds))
+
+
+def ensemble_tables(table, posterior, members, seed=0, burn=0, thin=1):
+    '''
+    From posteriors to the parameter tables of an ensemble forward run
+    (``mod16_amd.evapotranspiration_ensemble``, ``RasterEngine.ensemble``): what the reference's
+    ``export_posterior`` (calibration.py:633-709) hands on as one (PFT, samples) array per parameter,
+    drawn down to ``members`` tables. Host only.
+
+    Parameters
+    ----------
+    table : numpy.ndarray
+        (13, 11) base table (``mod16_amd.utils.bplut_table``): the value of every parameter that
+        was not calibrated and every row of a PFT that was not
+    posterior : dict
+        ``{pft: Trace}`` or ``{pft: {name: (chains, k) array}}`` (``Trace.posterior()``)
+    members : int
+        tables to draw
+    seed : int
+        PFT ``pft`` draws with ``numpy.random.default_rng([seed, pft])``
+    burn, thin : int
+        every chain's draws after the first ``burn``, every ``thin``-th, are the pool
+
+    For each PFT the kept draws of all chains are pooled chain-major (pool index = chain * k + draw)
+    and ``members`` pool indices are picked WITHOUT replacement; one index serves all of that PFT's
+    free parameters -- a member's row is a joint draw, so the posterior's correlations survive.
+    ``ValueError`` if a pool holds fewer than ``members`` draws. Returns (members, 13, 11) float64.
+    '''
+    base = np.array(table, np.float64)
+    if base.shape != (_lib.N_CLASSES, _lib.N_PARAMS):
+        raise ValueError('table must have shape (13, 11), got %r' % (base.shape,))
+    members, burn, thin = int(members), int(burn), int(thin)
+    if members < 1:
+        raise ValueError('members >= 1 needed')
+    if burn < 0 or thin < 1:
+        raise ValueError('burn >= 0 and thin >= 1 needed')
+    out = np.repeat(base[None], members, axis=0)
+    for pft, post in posterior.items():
+        if int(pft) != pft or not 0 <= int(pft) < _lib.N_CLASSES:
+            raise ValueError('PFT code %r is not one of 0..12' % (pft,))
+        samples = post.samples if isinstance(post, Trace) else post
+        unknown = [k for k in samples if k not in PARAM_NAMES]
+        if unknown:
+            raise ValueError('unknown parameter name(s) %s; expected some of %s' % (unknown, PARAM_NAMES))
+        kept, shape = {}, None
+        for name, v in samples.items():
+            v = np.asarray(v, np.float64)
+            if v.ndim != 2:
+                raise ValueError('samples of %r must have shape (chains, draws), got %r' % (name, v.shape))
+            if shape is not None and v.shape != shape:
+                raise ValueError('samples of PFT %d differ in shape: %r and %r' % (pft, shape, v.shape))
+            shape = v.shape
+            kept[name] = np.ascontiguousarray(v[:, burn::thin]).reshape(-1)      # chain-major
+        if not kept:
+            continue
+        pool = next(iter(kept.values())).size
+        if pool < members:
+            raise ValueError('PFT %d: %d draws in the pool (chains x kept draws), %d members wanted'
+                             % (pft, pool, members))
+        pick = np.random.default_rng([int(seed), int(pft)]).choice(pool, size=members, replace=False)
+        for name, v in kept.items():
+            out[:, int(pft), PARAM_NAMES.index(name)] = v[pick]
+    return out
 
 
 def _row(params):

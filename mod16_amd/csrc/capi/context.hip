@@ -164,31 +164,10 @@ extern "C" int mod16_set_bplut_f64(mod16_ctx* ctx, const double* lut) {
     MOD16_LOCK(ctx);
     if (!ctx || !lut) return fail(ctx, MOD16_ERR_ARG, "mod16_set_bplut_f64: NULL argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const double nan = std::numeric_limits<double>::quiet_NaN();
     double h64[MOD16_LUT_ROWS * kLutCols];
     float h32[MOD16_LUT_ROWS * kLutCols];
-    for (int c = 0; c < kLutCols; ++c) {
-        double row[MOD16_LUT_ROWS];
-        for (int k = 0; k < MOD16_LUT_ROWS; ++k) row[k] = nan;
-        if (c < MOD16_N_CLASSES) {
-            const double* p = lut + (size_t)c * MOD16_N_PARAMS;
-            for (int k = 0; k < MOD16_N_PARAMS; ++k) row[k] = p[k];
-            row[11] = 1.0 / (p[MOD16_TMIN_OPEN] - p[MOD16_TMIN_CLOSE]);
-            row[12] = 1.0 / (p[MOD16_VPD_CLOSE] - p[MOD16_VPD_OPEN]);
-            row[13] = (p[MOD16_RBL_MAX] - p[MOD16_RBL_MIN]) / (p[MOD16_VPD_CLOSE] - p[MOD16_VPD_OPEN]);
-            row[14] = 1.0 / p[MOD16_BETA];
-            // smallest float32 >= 273.15 + tmin_close: for a float32 x,
-            // x >= 273.15 + tmin_close (in float64) <=> x >= this (mixed-precision form)
-            const double thr = 273.15 + p[MOD16_TMIN_CLOSE];
-            float tf = (float)thr;
-            if ((double)tf < thr) tf = std::nextafterf(tf, std::numeric_limits<float>::infinity());
-            row[15] = (double)tf;
-        }
-        for (int k = 0; k < MOD16_LUT_ROWS; ++k) {
-            h64[k * kLutCols + c] = row[k];
-            h32[k * kLutCols + c] = (float)row[k];
-        }
-    }
+    derive_lut(lut, h64);
+    for (int i = 0; i < MOD16_LUT_ROWS * kLutCols; ++i) h32[i] = (float)h64[i];
     HIPCHK(ctx, hipMemcpy(ctx->lut64, h64, sizeof h64, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->lut32, h32, sizeof h32, hipMemcpyHostToDevice));
     ctx->have_lut = true;

@@ -168,6 +168,32 @@ struct Carver {
     }
 };
 
+// A (13, 11) parameter table -> the table the kernels index by class code: [MOD16_LUT_ROWS][kLutCols]
+// float64, row-major by parameter -- the 11 parameters, the derived reciprocals, NaN in the columns
+// behind class 12 (mod16_set_bplut_f64, and every member of mod16_ensemble_create).
+static void derive_lut(const double* lut, double* h64) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int c = 0; c < kLutCols; ++c) {
+        double row[MOD16_LUT_ROWS];
+        for (int k = 0; k < MOD16_LUT_ROWS; ++k) row[k] = nan;
+        if (c < MOD16_N_CLASSES) {
+            const double* p = lut + (size_t)c * MOD16_N_PARAMS;
+            for (int k = 0; k < MOD16_N_PARAMS; ++k) row[k] = p[k];
+            row[11] = 1.0 / (p[MOD16_TMIN_OPEN] - p[MOD16_TMIN_CLOSE]);
+            row[12] = 1.0 / (p[MOD16_VPD_CLOSE] - p[MOD16_VPD_OPEN]);
+            row[13] = (p[MOD16_RBL_MAX] - p[MOD16_RBL_MIN]) / (p[MOD16_VPD_CLOSE] - p[MOD16_VPD_OPEN]);
+            row[14] = 1.0 / p[MOD16_BETA];
+            // smallest float32 >= 273.15 + tmin_close: for a float32 x,
+            // x >= 273.15 + tmin_close (in float64) <=> x >= this (mixed-precision form)
+            const double thr = 273.15 + p[MOD16_TMIN_CLOSE];
+            float tf = (float)thr;
+            if ((double)tf < thr) tf = std::nextafterf(tf, std::numeric_limits<float>::infinity());
+            row[15] = (double)tf;
+        }
+        for (int k = 0; k < MOD16_LUT_ROWS; ++k) h64[k * kLutCols + c] = row[k];
+    }
+}
+
 // ------------------------------------------------------------------ launch
 template <typename T> static const T* ctx_lut(const mod16_ctx* ctx);
 template <> const double* ctx_lut<double>(const mod16_ctx* ctx) { return ctx->lut64; }

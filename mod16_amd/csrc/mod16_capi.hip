@@ -11,3 +11,4 @@
 #include "capi/tiled.hip"
 #include "capi/sensitivity.hip"
 #include "capi/mcmc.hip"
+#include "capi/ensemble.hip"

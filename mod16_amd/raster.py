@@ -147,6 +147,39 @@ class BoundStep(object):
         return ms.value
 
 
+class EnsembleRun(object):
+    '''The members of an ensemble forward run resident on an engine's device
+    (``RasterEngine.ensemble``): ``members`` parameter tables uploaded once, ``run`` as often as
+    there are rasters.'''
+
+    def __init__(self, engine, tables):
+        from . import _ensemble_stack
+        self.engine = engine
+        self._ens = _lib.Ensemble(engine.ctx, _ensemble_stack(tables))
+        self.members = self._ens.members
+
+    def run(self, cls, drivers, out=None):
+        '''Enqueue the ensemble kernel on the current stream: per-pixel mean and spread of ET over
+        the members for device-resident drivers (tensors, or scalars to broadcast). Returns the five
+        tensors ``(mean_day, mean_night, std_day, std_night, std_total)`` (``out`` may give them).
+        Asynchronous: call the engine's ``check()`` (or synchronise the stream) before trusting the
+        data; a class code >= 13 raises IndexError there.'''
+        eng, torch = self.engine, _torch()
+        n = cls.numel()
+        cptr = eng._check_tensor(cls, torch.uint8, n, 'cls')
+        keep, dptr, dstride = eng._marshal_drivers(drivers, n)
+        out = tuple(out) if out is not None else tuple(eng.empty(n, 5))
+        if len(out) != 5:
+            raise ValueError('out must hold 5 tensors')
+        optr = [eng._check_tensor(t, eng.dtype, n, 'out') for t in out]
+        self._ens.run(eng.np_dtype, cptr, dptr, dstride, n, optr, flags=eng.math, where=_lib.DEVICE,
+                      stream=eng._stream())
+        return out
+
+    def close(self):
+        self._ens.close()
+
+
 class RasterEngine(object):
     '''
     Parameters
@@ -362,6 +395,15 @@ class RasterEngine(object):
         self.ctx.et(self.np_dtype, cptr, dptr, dstride, None, None, n, pd, pn, sep,
                     flags=self.math, where=_lib.DEVICE, stream=self._stream())
         return out_day, out_night
+
+    def ensemble(self, tables):
+        '''The members of an ensemble forward run on this engine's device: ``tables`` is a (D, 13,
+        11) array or a sequence of D ``restore_bplut`` dicts (``mod16_amd.calibration.ensemble_tables``
+        draws them from a posterior). Returns an ``EnsembleRun``: ``.members``, ``.run(cls, drivers,
+        out=None)`` -> five device tensors (mean and standard deviation over the members of the day
+        and night totals, standard deviation of their sum), ``.close()``. The engine's own table
+        plays no part; its ``math`` must be ``MATH_FAST`` or ``MATH_EXACT`` (``mod16_et_ensemble_*``).'''
+        return EnsembleRun(self, tables)
 
     def run_pet(self, cls, drivers, out=None):
         '''ET and potential ET from one pass over device-resident drivers

@@ -53,86 +53,63 @@ static size_t eval_layout_blocks(int64_t draws, int gx, void* base, EvalWs* w, b
     return c.used;
 }
 
-// A chain of kernel launches on one stream, captured and instantiated once and kept under a key (what
-// the kernels' arguments hold: the draws of an objective graph, the steps of a sampler graph).
-struct CachedGraph {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int64_t key = -1;
-    void drop() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        exec = nullptr;
-        graph = nullptr;
-        key = -1;
-    }
-    // what `enqueue()` launches on `st` becomes the graph; the capture is always ended before a failed
-    // launch is reported
-    template <typename F>
-    int capture(mod16_ctx* ctx, hipStream_t st, int64_t k, F enqueue) {
-        drop();
-        HIPCHK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        enqueue();
-        const hipError_t launched = hipGetLastError();
-        const hipError_t ended = hipStreamEndCapture(st, &graph);
-        HIPCHK(ctx, launched);
-        HIPCHK(ctx, ended);
-        HIPCHK(ctx, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        key = k;
-        return MOD16_OK;
-    }
-};
-
-// ---- the calibration problem RESIDENT on the device (mod16_static_batch_bind_*): drivers,
-// observations and weights go up once; an evaluation is parameters up, one graph launch (kernels
-// only), (sse, count) down.
-struct mod16_batch {
-    mod16_ctx* ctx = nullptr;
-    int device = 0;
-    bool f32 = false;
-    unsigned flags = 0;
-    int64_t n = 0, max_draws = 0;       // n: the resident arrays' pixels (with the constraint: padding included)
-    int64_t n_user = 0;                 // the caller's n (mod16_static_batch_info, the rows)
+// The resident arrays and what is sized by them: bind fills one, and mod16_static_batch_set_annual
+// builds a second one (the same pixels laid out site-year-major) and moves it into the problem whole.
+struct BatchArrays {
+    int64_t n = 0;                      // the resident arrays' pixels (with the constraint: padding included)
     int gx = 0;
-    void* owned = nullptr;              // the resident copies (HOST bind); NULL when the caller's device arrays are used
-    const void* drv[14] = {};
-    uint32_t dense_drv = 0;
-    const void* obs = nullptr;
+    DevMem owned;                       // the resident copies (HOST bind); empty when the caller's device arrays are used
+    const void* drv[14] = {};           // views: into `owned`, or the caller's
+    const void* obs = nullptr;          // ...
     const void* wts = nullptr;
-    uint8_t* skip = nullptr;            // [n]: 1 = outside the FAST domain
-    int64_t* list = nullptr;            // those pixels, ascending
+    DevMem skip;                        // uint8 [n]: 1 = outside the FAST domain
+    DevMem list;                        // int64: those pixels, ascending
     int64_t nlist = 0;
-    void* ws = nullptr;                 // the per-draw part of `own` for max_draws draws, and dflags
-    EvalWs own;
-    unsigned* dflags = nullptr;         // [max_draws]: the rows kernels' any(g_surf > 0) words
-    void* eval_ws = nullptr;            // the per-block part of `own` for eval_draws draws (grown on demand: batch_eval_ws)
-    int64_t eval_draws = 0;
-    void* rows = nullptr;               // [ndraw][n] x up to 3: rows workspace, allocated when first asked for
-    size_t rows_bytes = 0;
-    void* hparams = nullptr;            // pinned staging
-    double* hout = nullptr;             // pinned [2][max_draws]
-    hipStream_t st = nullptr;
-    // cross-validation (mod16_static_batch_set_folds): a fold label per pixel, resident; the fold
-    // objective's codes and its own cached graph (plain and fold calls never share one: the launches
-    // differ in kernels and in the codes' address)
-    uint8_t* label = nullptr;           // [n], NULL: no folds
-    int nfolds = 0;
-    int32_t* dcode = nullptr;           // [max_draws] device
-    int32_t* hcode = nullptr;           // [max_draws] pinned staging
+    DevMem ws;                          // the per-draw part of `own` for max_draws draws, and dflags
+    EvalWs own;                         // views into `ws` and (the per-block part) into mod16_batch::eval_ws
+    unsigned* dflags = nullptr;         // [max_draws]: the rows kernels' any(g_surf > 0) words; a view into `ws`
+    PinnedMem hout;                     // pinned double [2][max_draws] ([3]: with the constraint)
     // the annual-precipitation constraint (mod16_static_batch_set_annual): the resident arrays are laid
     // out site-year-major, every site-year padded to whole waves (the kernels' comment in
     // mod16_methods.hpp); G = 0: none
     int G = 0;                          // site-years, g = year * sites + site
     double S = 0.0;                     // sum of the limits
-    void* annual = nullptr;             // one allocation: the tables below
-    const double* scale = nullptr;      // [n] 86400 / lhv, 0 = padding (inside `owned`)
-    int32_t* wstart = nullptr;          // [G + 1] first wave of each site-year
+    DevMem annual;                      // one allocation: the tables below
+    const double* scale = nullptr;      // [n] 86400 / lhv, 0 = padding; a view into `owned`
+    int32_t* wstart = nullptr;          // [G + 1] first wave of each site-year; views into `annual` ...
     double* limit = nullptr;            // [G] annual_precip
     int64_t* lstart = nullptr;          // [G + 1] first entry of `list` of each site-year
     int64_t* pos = nullptr;             // [n_user] where the caller's pixel lies
+};
+
+// ---- the calibration problem RESIDENT on the device (mod16_static_batch_bind_*): drivers,
+// observations and weights go up once; an evaluation is parameters up, one graph launch (kernels
+// only), (sse, count) down.
+// Ownership: members go in reverse order of declaration, then the BatchArrays -- the stream first
+// (mod16_static_batch_destroy has synchronized it), then the graphs, then the memory they point into.
+struct mod16_batch : BatchArrays {
+    mod16_ctx* ctx = nullptr;           // a view: the context outlives its problems
+    int device = 0;
+    bool f32 = false;
+    unsigned flags = 0;
+    int64_t max_draws = 0;
+    int64_t n_user = 0;                 // the caller's n (mod16_static_batch_info, the rows)
+    uint32_t dense_drv = 0;
+    DevMem eval_ws;                     // the per-block part of `own` for eval_draws draws (grown on demand: batch_eval_ws)
+    int64_t eval_draws = 0;
+    DevMem rows;                        // [ndraw][n] x up to 3: rows workspace, allocated when first asked for; only grows
+    PinnedMem hparams;                  // pinned staging
+    // cross-validation (mod16_static_batch_set_folds): a fold label per pixel, resident; the fold
+    // objective's codes and its own cached graph (plain and fold calls never share one: the launches
+    // differ in kernels and in the codes' address)
+    DevMem label;                       // uint8 [n], empty: no folds
+    int nfolds = 0;
+    DevMem dcode;                       // int32 [max_draws] device
+    PinnedMem hcode;                    // int32 [max_draws] pinned staging
     CachedGraph graph, fgraph, agraph;  // the plain, the fold and the constrained objective, key = draws
-    CachedGraph* last = nullptr;        // the one the last objective call launched (mod16_static_batch_time)
+    CachedGraph* last = nullptr;        // the one the last objective call launched (mod16_static_batch_time); a view
     int samplers = 0;                   // samplers alive on the problem (capi/mcmc.hip)
+    Stream st;
 };
 
 // w.code set: the FOLD instances (the problem's labels, the draws' fold codes); otherwise the plain ones.
@@ -153,15 +130,15 @@ static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int6
     a.n = b->n;
     a.observed = static_cast<const T*>(b->obs);
     a.weights = static_cast<const T*>(b->wts);
-    a.skip = b->nlist ? b->skip : nullptr;
+    a.skip = b->nlist ? b->skip.as<uint8_t>() : nullptr;
     a.par16 = w.par16;
-    a.tab = b->ctx->tab64;
+    a.tab = b->ctx->tab64.as<double>();
     a.ndraw = ndraw;
     a.any_draw = w.any_draw;
     a.partial = w.partial;
     a.any_gs = w.any_gs;
     a.code = w.code;
-    a.label = fold ? b->label : nullptr;
+    a.label = fold ? b->label.as<uint8_t>() : nullptr;
     a.scale = annual ? b->scale : nullptr;
     a.mass = annual ? w.mass : nullptr;
     const dim3 grid((unsigned)b->gx, (unsigned)((ndraw + kObjDraws - 1) / kObjDraws));
@@ -176,7 +153,7 @@ static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int6
         r.params = static_cast<const T*>(w.params);
         r.observed = a.observed;
         r.weights = a.weights;
-        r.list = b->list;
+        r.list = b->list.as<int64_t>();
         r.nlist = b->nlist;
         r.redo = w.redo;
         r.code = w.code;
@@ -190,7 +167,7 @@ static void batch_objective_launches(const mod16_batch* b, const EvalWs& w, int6
             m.dense_drv = r.dense_drv;
             m.params = r.params;
             m.scale = b->scale;
-            m.list = b->list;
+            m.list = b->list.as<int64_t>();
             m.lstart = b->lstart;
             m.G = b->G;
             m.rmass = w.rmass;

@@ -7,20 +7,9 @@
 // calibration loop repeats the same shape thousands of times): it only grows; above kBatchKeepBytes
 // it is given back after the call.
 constexpr size_t kBatchKeepBytes = size_t(8) << 30;
-static int batch_reserve(mod16_ctx* ctx, size_t total) {
-    if (ctx->batch_bytes >= total) return MOD16_OK;
-    if (ctx->batch_buf) HIPCHK(ctx, hipFree(ctx->batch_buf));
-    ctx->batch_buf = nullptr;
-    ctx->batch_bytes = 0;
-    int rc = dev_alloc(ctx, &ctx->batch_buf, total, "mod16_et_static*: device memory for the calibration workspace");
-    if (rc == MOD16_OK) ctx->batch_bytes = total;
-    return rc;
-}
+static const char kBatchWhat[] = "mod16_et_static*: device memory for the calibration workspace";
 static void batch_trim(mod16_ctx* ctx) {
-    if (ctx->batch_bytes <= kBatchKeepBytes) return;
-    (void)hipFree(ctx->batch_buf);
-    ctx->batch_buf = nullptr;
-    ctx->batch_bytes = 0;
+    if (ctx->batch_buf.bytes() > kBatchKeepBytes) ctx->batch_buf.release();
 }
 
 // The 14 drivers (dense [n], or one element each) from host memory into slots 0 .. 13 of `per_arr`
@@ -69,8 +58,11 @@ static int static_entry(mod16_ctx* ctx, const T* const* drivers, const int64_t* 
     a.tiny = tiny;
     if (n == 0) return MOD16_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->static_flag) HIPCHK(ctx, hipMalloc(&ctx->static_flag, sizeof(unsigned)));
-    a.flag = ctx->static_flag;
+    if (!ctx->static_flag) {
+        int rc = ctx->static_flag.alloc(ctx, sizeof(unsigned), "mod16_et_static: device memory for the flag word");
+        if (rc != MOD16_OK) return rc;
+    }
+    a.flag = ctx->static_flag.as<unsigned>();
     auto grid_of = [&](int64_t m) {
         return (int)std::max<int64_t>(1, std::min<int64_t>((m + kBlock - 1) / kBlock, (int64_t)ctx->cus * 8));
     };
@@ -113,11 +105,11 @@ static int static_entry(mod16_ctx* ctx, const T* const* drivers, const int64_t* 
     const size_t per_arr = align256((size_t)n * sizeof(T));
     // the workspace the context keeps between calibration calls (mod16_et_static_batch_* shares it;
     // until round 5 this entry point allocated and freed its own on every call)
-    int rcw = batch_reserve(ctx, per_arr * kArr);
+    int rcw = ctx->batch_buf.reserve(ctx, per_arr * kArr, kBatchWhat);
     if (rcw != MOD16_OK) return rcw;
-    if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
+    HIPCHK(ctx, ctx->streams[0].ensure());
     hipStream_t st = ctx->streams[0];
-    char* base = static_cast<char*>(ctx->batch_buf);
+    char* base = ctx->batch_buf.as<char>();
     StaticArgs<T> d = a;
     int slot = 14;
     int rc_status = upload_drivers(a.drv, a.dense_drv, n, base, per_arr, st, d.drv) == hipSuccess ? MOD16_OK : MOD16_ERR_HIP;
@@ -176,7 +168,7 @@ static int static_batch_rows(mod16_ctx* ctx, StaticBatchArgs<T> d, int64_t ndraw
                              hipStream_t st, bool skip_ready = false) {
     const int64_t n = d.n;
     d.flags = dflags;
-    d.tab = ctx->tab64;
+    d.tab = ctx->tab64.as<double>();
     d.ndraw = ndraw;
     const bool fast = (flags & MOD16_MATH_EXACT) == 0;
     d.skip = fast ? dskip : nullptr;
@@ -232,21 +224,20 @@ static int static_batch_entry(mod16_ctx* ctx, const T* const* drivers, const int
     if (ndraw > 0x7fffffff) return fail(ctx, MOD16_ERR_ARG, "mod16_et_static_batch: too many draws");
     if (where == MOD16_DEVICE) {
         hipStream_t st = static_cast<hipStream_t>(stream);
-        unsigned* dflags = nullptr;
-        uint8_t* dskip = nullptr;
         // flags and the domain mask: per-call allocations freed on the stream (asynchronous)
-        HIPCHK(ctx, hipMallocAsync(reinterpret_cast<void**>(&dflags), sizeof(unsigned) * ndraw, st));
-        HIPCHK(ctx, hipMallocAsync(reinterpret_cast<void**>(&dskip), (size_t)n, st));
+        AsyncMem dflags(st), dskip(st);
+        const char* what = "mod16_et_static_batch: device memory for the flags and the domain mask";
+        int rc = dflags.alloc(ctx, sizeof(unsigned) * ndraw, what);
+        if (rc == MOD16_OK) rc = dskip.alloc(ctx, (size_t)n, what);
+        if (rc != MOD16_OK) return rc;
         a.params = params;
         a.out[0] = out_day; a.out[1] = out_night; a.out[2] = out_total;
-        int rc = static_batch_rows<T>(ctx, a, ndraw, observed, weights, sse, count, dflags, dskip, flags, st);
-        (void)hipFreeAsync(dflags, st);
-        (void)hipFreeAsync(dskip, st);
-        return rc;
+        return static_batch_rows<T>(ctx, a, ndraw, observed, weights, sse, count, static_cast<unsigned*>(dflags.p),
+                                    static_cast<uint8_t*>(dskip.p), flags, st);
     }
     if (where != MOD16_HOST) return fail(ctx, MOD16_ERR_ARG, "mod16_et_static_batch: bad `where`");
     // HOST: drivers / parameters resident once, outputs [ndraw][n] come back
-    if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
+    HIPCHK(ctx, ctx->streams[0].ensure());
     hipStream_t st = ctx->streams[0];
     const size_t per_arr = align256((size_t)n * sizeof(T)), per_out = align256((size_t)n * (size_t)ndraw * sizeof(T));
     const bool want[3] = {out_day != nullptr, out_night != nullptr, out_total != nullptr || sse != nullptr};
@@ -258,12 +249,12 @@ static int static_batch_entry(mod16_ctx* ctx, const T* const* drivers, const int
     // shape thousands of times -- better still: mod16_static_batch_bind_*); it only grows, up to
     // kBatchKeepBytes it is kept
     {
-        int rcw = batch_reserve(ctx, total);
+        int rcw = ctx->batch_buf.reserve(ctx, total, kBatchWhat);
         if (rcw != MOD16_OK) return rcw;
     }
     int rc = MOD16_OK;
     auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == MOD16_OK) { rc = MOD16_ERR_HIP; ctx->err = hipGetErrorString(e); } };
-    Carver c(ctx->batch_buf);
+    Carver c(ctx->batch_buf.get());
     StaticBatchArgs<T> d = a;
     chk(upload_drivers(a.drv, a.dense_drv, n, c.take<char>(per_arr * 14), per_arr, st, d.drv));
     T* dobs = c.take<T>(per_arr);
@@ -327,20 +318,6 @@ extern "C" int mod16_static_batch_destroy(mod16_batch* b) {
     if (!b) return MOD16_OK;
     (void)hipSetDevice(b->device);
     if (b->st) (void)hipStreamSynchronize(b->st);
-    batch_drop_graphs(b);
-    if (b->label) (void)hipFree(b->label);
-    if (b->dcode) (void)hipFree(b->dcode);
-    if (b->hcode) (void)hipHostFree(b->hcode);
-    if (b->annual) (void)hipFree(b->annual);
-    if (b->owned) (void)hipFree(b->owned);
-    if (b->skip) (void)hipFree(b->skip);
-    if (b->list) (void)hipFree(b->list);
-    if (b->ws) (void)hipFree(b->ws);
-    if (b->eval_ws) (void)hipFree(b->eval_ws);
-    if (b->rows) (void)hipFree(b->rows);
-    if (b->hparams) (void)hipHostFree(b->hparams);
-    if (b->hout) (void)hipHostFree(b->hout);
-    if (b->st) (void)hipStreamDestroy(b->st);
     delete b;
     return MOD16_OK;
 }
@@ -382,14 +359,14 @@ static int batch_bind(mod16_ctx* ctx, const T* const* drivers, const int64_t* ds
     b->max_draws = max_draws;
     b->gx = (int)((n + kBlock - 1) / kBlock);
     int rc = [&]() -> int {
-        HIPCHK(ctx, hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
+        HIPCHK(ctx, b->st.ensure());
         const size_t per_arr = align256((size_t)n * sizeof(T));
         for (int k = 0; k < 14; ++k) if (dstride[k]) b->dense_drv |= 1u << k;
         int r;
         if (where == MOD16_HOST) {
-            r = dev_alloc(ctx, &b->owned, per_arr * 16, "mod16_static_batch_bind: device memory for the resident drivers");
+            r = b->owned.alloc(ctx, per_arr * 16, "mod16_static_batch_bind: device memory for the resident drivers");
             if (r != MOD16_OK) return r;
-            char* base = static_cast<char*>(b->owned);
+            char* base = b->owned.as<char>();
             HIPCHK(ctx, upload_drivers(drivers, b->dense_drv, n, base, per_arr, b->st, b->drv));
             if (observed) {
                 HIPCHK(ctx, hipMemcpyAsync(base + per_arr * 14, observed, sizeof(T) * n, hipMemcpyHostToDevice, b->st));
@@ -407,28 +384,29 @@ static int batch_bind(mod16_ctx* ctx, const T* const* drivers, const int64_t* ds
         // evaluation workspace: the per-draw part for max_draws (the per-block part: batch_eval_ws)
         const int64_t D = max_draws;
         const size_t per_draw = eval_layout_draws(D, sizeof(T), nullptr, nullptr);
-        r = dev_alloc(ctx, &b->ws, per_draw + align256((size_t)D * sizeof(unsigned)), "mod16_static_batch_bind: device memory for the evaluation workspace");
+        r = b->ws.alloc(ctx, per_draw + align256((size_t)D * sizeof(unsigned)), "mod16_static_batch_bind: device memory for the evaluation workspace");
         if (r != MOD16_OK) return r;
-        eval_layout_draws(D, sizeof(T), b->ws, &b->own);
-        b->dflags = reinterpret_cast<unsigned*>(static_cast<char*>(b->ws) + per_draw);
-        HIPCHK(ctx, hipHostMalloc(&b->hparams, (size_t)D * 11 * sizeof(T)));
-        HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&b->hout), (size_t)D * 16));
+        eval_layout_draws(D, sizeof(T), b->ws.get(), &b->own);
+        b->dflags = reinterpret_cast<unsigned*>(b->ws.as<char>() + per_draw);
+        const char* pinned = "mod16_static_batch_bind: page-locked memory for the parameters and the results";
+        r = b->hparams.alloc(ctx, (size_t)D * 11 * sizeof(T), pinned);
+        if (r == MOD16_OK) r = b->hout.alloc(ctx, (size_t)D * 16, pinned);
         // the pixels outside the domain of the FAST arithmetic: marked once, listed in ascending order
-        r = dev_alloc(ctx, &b->skip, (size_t)n, "mod16_static_batch_bind: device memory for the domain mask");
+        if (r == MOD16_OK) r = b->skip.alloc(ctx, (size_t)n, "mod16_static_batch_bind: device memory for the domain mask");
         if (r != MOD16_OK) return r;
         StaticBatchArgs<T> a = batch_args<T>(b);
-        hipLaunchKernelGGL((static_domain_kernel<T>), dim3((unsigned)b->gx), dim3(kBlock), 0, b->st, a, b->skip);
+        hipLaunchKernelGGL((static_domain_kernel<T>), dim3((unsigned)b->gx), dim3(kBlock), 0, b->st, a, b->skip.as<uint8_t>());
         HIPCHK(ctx, hipGetLastError());
         std::vector<uint8_t> mask((size_t)n);
-        HIPCHK(ctx, hipMemcpyAsync(mask.data(), b->skip, (size_t)n, hipMemcpyDeviceToHost, b->st));
+        HIPCHK(ctx, hipMemcpyAsync(mask.data(), b->skip.get(), (size_t)n, hipMemcpyDeviceToHost, b->st));
         HIPCHK(ctx, hipStreamSynchronize(b->st));
         std::vector<int64_t> list;
         for (int64_t i = 0; i < n; ++i) if (mask[(size_t)i]) list.push_back(i);
         b->nlist = (int64_t)list.size();
         if (b->nlist) {
-            r = dev_alloc(ctx, &b->list, sizeof(int64_t) * list.size(), "mod16_static_batch_bind: device memory for the list of pixels outside the domain");
+            r = b->list.alloc(ctx, sizeof(int64_t) * list.size(), "mod16_static_batch_bind: device memory for the list of pixels outside the domain");
             if (r != MOD16_OK) return r;
-            HIPCHK(ctx, hipMemcpy(b->list, list.data(), sizeof(int64_t) * list.size(), hipMemcpyHostToDevice));
+            HIPCHK(ctx, hipMemcpy(b->list.get(), list.data(), sizeof(int64_t) * list.size(), hipMemcpyHostToDevice));
         }
         return MOD16_OK;
     }();
@@ -471,26 +449,13 @@ static int batch_eval_ws(mod16_batch* b, int64_t ndraw) {
     want = std::min(want, b->max_draws);
     batch_drop_graphs(b);
     HIPCHK(ctx, hipStreamSynchronize(b->st));
-    if (b->eval_ws) HIPCHK(ctx, hipFree(b->eval_ws));
-    b->eval_ws = nullptr;
     b->eval_draws = 0;
-    int rc = dev_alloc(ctx, &b->eval_ws, eval_layout_blocks(want, b->gx, nullptr, nullptr, b->G != 0),
-                       "mod16_static_batch_objective: device memory for the per-block partials of this many draws");
+    int rc = b->eval_ws.reserve(ctx, eval_layout_blocks(want, b->gx, nullptr, nullptr, b->G != 0),
+                                "mod16_static_batch_objective: device memory for the per-block partials of this many draws");
     if (rc != MOD16_OK) return rc;
-    eval_layout_blocks(want, b->gx, b->eval_ws, &b->own, b->G != 0);
+    eval_layout_blocks(want, b->gx, b->eval_ws.get(), &b->own, b->G != 0);
     b->eval_draws = want;
     return MOD16_OK;
-}
-
-// room for `need` bytes of rows (the workspace only grows)
-static int rows_reserve(mod16_batch* b, size_t need, const char* what) {
-    if (b->rows_bytes >= need) return MOD16_OK;
-    if (b->rows) HIPCHK(b->ctx, hipFree(b->rows));
-    b->rows = nullptr;
-    b->rows_bytes = 0;
-    int rc = dev_alloc(b->ctx, &b->rows, need, what);
-    if (rc == MOD16_OK) b->rows_bytes = need;
-    return rc;
 }
 
 // code: NULL (plain draws) or the fold code of every draw (mod16_static_batch_objective_folds, checked);
@@ -504,20 +469,20 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const
     if (!b->obs) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_objective: the problem was bound without observations");
     if (ndraw == 0) return MOD16_OK;
     HIPCHK(ctx, hipSetDevice(b->device));
-    memcpy(b->hparams, params, sizeof(T) * (size_t)ndraw * 11);
-    HIPCHK(ctx, hipMemcpyAsync(b->own.params, b->hparams, sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
+    memcpy(b->hparams.get(), params, sizeof(T) * (size_t)ndraw * 11);
+    HIPCHK(ctx, hipMemcpyAsync(b->own.params, b->hparams.get(), sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
     if (code) {
-        memcpy(b->hcode, code, sizeof(int32_t) * (size_t)ndraw);
-        HIPCHK(ctx, hipMemcpyAsync(b->dcode, b->hcode, sizeof(int32_t) * (size_t)ndraw, hipMemcpyHostToDevice, b->st));
+        memcpy(b->hcode.get(), code, sizeof(int32_t) * (size_t)ndraw);
+        HIPCHK(ctx, hipMemcpyAsync(b->dcode.get(), b->hcode.get(), sizeof(int32_t) * (size_t)ndraw, hipMemcpyHostToDevice, b->st));
     }
     if (b->flags & MOD16_MATH_EXACT) {
         // reference order: rows into a workspace, then the residuals' sums (the kernels of the unbound call)
-        int rc = rows_reserve(b, sizeof(T) * (size_t)ndraw * (size_t)b->n, "mod16_static_batch_objective: device memory for the [ndraw][n] rows");
+        int rc = b->rows.reserve(ctx, sizeof(T) * (size_t)ndraw * (size_t)b->n, "mod16_static_batch_objective: device memory for the [ndraw][n] rows");
         if (rc != MOD16_OK) return rc;
         StaticBatchArgs<T> a = batch_args<T>(b);
-        a.out[2] = static_cast<T*>(b->rows);
+        a.out[2] = b->rows.as<T>();
         rc = static_batch_rows<T>(ctx, a, ndraw, static_cast<const T*>(b->obs), static_cast<const T*>(b->wts), b->own.sse, b->own.cnt,
-                                  b->dflags, b->skip, b->flags, b->st, true);
+                                  b->dflags, b->skip.as<uint8_t>(), b->flags, b->st, true);
         if (rc != MOD16_OK) return rc;
     } else {
         int rc = batch_eval_ws(b, ndraw);
@@ -526,7 +491,7 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const
         if (g.key != ndraw) {                   // (re)capture: the kernels' arguments hold the number of draws
             if (b->last == &g) b->last = nullptr;
             EvalWs w = b->own;
-            w.code = code ? b->dcode : nullptr;
+            w.code = code ? b->dcode.as<int32_t>() : nullptr;
             if (!penalty) w.mass = nullptr;
             rc = g.capture(ctx, b->st, ndraw, [&] { batch_objective_launches<T>(b, w, ndraw); });
             if (rc != MOD16_OK) return rc;
@@ -534,14 +499,15 @@ static int batch_objective(mod16_batch* b, const T* params, int64_t ndraw, const
         HIPCHK(ctx, hipGraphLaunch(g.exec, b->st));
         b->last = &g;
     }
-    HIPCHK(ctx, hipMemcpyAsync(b->hout, b->own.sse, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
-    HIPCHK(ctx, hipMemcpyAsync(b->hout + b->max_draws, b->own.cnt, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
+    double* hout = b->hout.as<double>();
+    HIPCHK(ctx, hipMemcpyAsync(hout, b->own.sse, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
+    HIPCHK(ctx, hipMemcpyAsync(hout + b->max_draws, b->own.cnt, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
     if (penalty)
-        HIPCHK(ctx, hipMemcpyAsync(b->hout + 2 * b->max_draws, b->own.penalty, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
+        HIPCHK(ctx, hipMemcpyAsync(hout + 2 * b->max_draws, b->own.penalty, sizeof(double) * (size_t)ndraw, hipMemcpyDeviceToHost, b->st));
     HIPCHK(ctx, hipStreamSynchronize(b->st));
-    memcpy(sse, b->hout, sizeof(double) * (size_t)ndraw);
-    memcpy(count, b->hout + b->max_draws, sizeof(double) * (size_t)ndraw);
-    if (penalty) memcpy(penalty, b->hout + 2 * b->max_draws, sizeof(double) * (size_t)ndraw);
+    memcpy(sse, hout, sizeof(double) * (size_t)ndraw);
+    memcpy(count, hout + b->max_draws, sizeof(double) * (size_t)ndraw);
+    if (penalty) memcpy(penalty, hout + 2 * b->max_draws, sizeof(double) * (size_t)ndraw);
     return MOD16_OK;
 }
 
@@ -572,24 +538,19 @@ extern "C" int mod16_static_batch_set_folds(mod16_batch* b, const uint8_t* label
     for (int f = 0; f < nfolds; ++f)
         if (!seen[(size_t)f]) return fail(ctx, MOD16_ERR_ARG, "mod16_static_batch_set_folds: a fold without any pixel");
     HIPCHK(ctx, hipSetDevice(b->device));
-    int rc = [&]() -> int {
-        const char* what = "mod16_static_batch_set_folds: device memory for the labels";
-        int r = dev_alloc(ctx, &b->label, (size_t)b->n, what);
-        if (r == MOD16_OK) r = dev_alloc(ctx, &b->dcode, sizeof(int32_t) * (size_t)b->max_draws, what);
-        if (r != MOD16_OK) return r;
-        HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void**>(&b->hcode), sizeof(int32_t) * (size_t)b->max_draws));
-        HIPCHK(ctx, hipMemcpyAsync(b->label, labels, (size_t)b->n, hipMemcpyHostToDevice, b->st));
-        HIPCHK(ctx, hipStreamSynchronize(b->st));
-        return MOD16_OK;
-    }();
-    if (rc != MOD16_OK) {
-        if (b->label) (void)hipFree(b->label);
-        if (b->dcode) (void)hipFree(b->dcode);
-        if (b->hcode) (void)hipHostFree(b->hcode);
-        b->label = nullptr;
-        b->dcode = b->hcode = nullptr;
-        return rc;
-    }
+    // everything new is made first; the problem takes it once nothing can fail any more
+    DevMem label, dcode;
+    PinnedMem hcode;
+    const char* what = "mod16_static_batch_set_folds: memory for the labels and the codes";
+    int rc = label.alloc(ctx, (size_t)b->n, what);
+    if (rc == MOD16_OK) rc = dcode.alloc(ctx, sizeof(int32_t) * (size_t)b->max_draws, what);
+    if (rc == MOD16_OK) rc = hcode.alloc(ctx, sizeof(int32_t) * (size_t)b->max_draws, what);
+    if (rc != MOD16_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(label.get(), labels, (size_t)b->n, hipMemcpyHostToDevice, b->st));
+    HIPCHK(ctx, hipStreamSynchronize(b->st));
+    b->label = std::move(label);
+    b->dcode = std::move(dcode);
+    b->hcode = std::move(hcode);
     b->nfolds = nfolds;
     return MOD16_OK;
 }
@@ -678,111 +639,81 @@ extern "C" int mod16_static_batch_set_annual(mod16_batch* b, int64_t T, int64_t 
     auto from = [&](int64_t k) { const int64_t v = src[(size_t)k]; return (size_t)(v < 0 ? -(v + 1) : v); };
     HIPCHK(ctx, hipSetDevice(b->device));
     HIPCHK(ctx, hipStreamSynchronize(b->st));
-    // everything new is made first; the problem changes only once nothing can fail any more
-    void *owned = nullptr, *tables = nullptr, *ws = nullptr, *hout = nullptr;
-    uint8_t* skip = nullptr;
-    int64_t* dlist = nullptr;
+    // Build, then commit: everything the constraint adds or replaces is made in `fresh`; a failure
+    // returns (and frees it), success moves it into the problem in one place.
+    BatchArrays fresh;
+    fresh.n = ni;
+    fresh.gx = (int)((ni + kBlock - 1) / kBlock);
+    fresh.G = G;
+    fresh.S = S;
     const size_t per_new = align256((size_t)ni * sizeof(double));
     const int64_t D = b->max_draws;
     const size_t per_draw = eval_layout_draws(D, sizeof(double), nullptr, nullptr, G);
-    Carver tc;
-    int rc = [&]() -> int {
-        const char* what = "mod16_static_batch_set_annual: device memory for the reordered problem";
-        int r = dev_alloc(ctx, &owned, per_new * 17, what);
-        if (r != MOD16_OK) return r;
-        char* base = static_cast<char*>(owned);
-        for (int k = 0; k < 16; ++k) {
-            const void* cur = k < 14 ? b->drv[k] : k == 14 ? b->obs : b->wts;
-            if (!cur) continue;
-            const bool dense = k >= 14 || ((b->dense_drv >> k) & 1u);
-            HIPCHK(ctx, hipMemcpy(in.data(), cur, sizeof(double) * (size_t)(dense ? n : 1), hipMemcpyDeviceToHost));
-            if (dense)
-                for (int64_t j = 0; j < ni; ++j)
-                    out[(size_t)j] = (k == 14 && src[(size_t)j] < 0) ? std::numeric_limits<double>::quiet_NaN() : in[from(j)];
-            else
-                out[0] = in[0];
-            HIPCHK(ctx, hipMemcpy(base + per_new * k, out.data(), sizeof(double) * (size_t)(dense ? ni : 1), hipMemcpyHostToDevice));
-        }
-        for (int64_t j = 0; j < ni; ++j) out[(size_t)j] = src[(size_t)j] < 0 ? 0.0 : 86400.0 / lhv[from(j)];
-        HIPCHK(ctx, hipMemcpy(base + per_new * 16, out.data(), sizeof(double) * (size_t)ni, hipMemcpyHostToDevice));
-        // the domain mask goes with its pixels; the list and each site-year's part of it
-        HIPCHK(ctx, hipMemcpy(mask_in.data(), b->skip, (size_t)n, hipMemcpyDeviceToHost));
-        for (int64_t j = 0; j < ni; ++j) {
-            mask[(size_t)j] = mask_in[from(j)];
-            if (mask[(size_t)j]) list.push_back(j);
-        }
-        for (int g = 0, u = 0; g <= G; ++g) {
-            while ((size_t)u < list.size() && list[(size_t)u] < gstart[(size_t)g]) ++u;
-            lstart[(size_t)g] = u;
-        }
-        r = dev_alloc(ctx, &skip, (size_t)ni, what);
-        if (r != MOD16_OK) return r;
-        HIPCHK(ctx, hipMemcpy(skip, mask.data(), (size_t)ni, hipMemcpyHostToDevice));
-        if (!list.empty()) {
-            r = dev_alloc(ctx, &dlist, sizeof(int64_t) * list.size(), what);
-            if (r != MOD16_OK) return r;
-            HIPCHK(ctx, hipMemcpy(dlist, list.data(), sizeof(int64_t) * list.size(), hipMemcpyHostToDevice));
-        }
-        auto carve = [&](void* at) {
-            tc = Carver(at);
-            b->wstart = tc.take<int32_t>(sizeof(int32_t) * ((size_t)G + 1));
-            b->limit = tc.take<double>(sizeof(double) * (size_t)G);
-            b->lstart = tc.take<int64_t>(sizeof(int64_t) * ((size_t)G + 1));
-            b->pos = tc.take<int64_t>(sizeof(int64_t) * (size_t)n);
-            return tc.used;
-        };
-        r = dev_alloc(ctx, &tables, carve(nullptr), what);
-        if (r == MOD16_OK) r = dev_alloc(ctx, &ws, per_draw + align256((size_t)D * sizeof(unsigned)), what);
-        if (r != MOD16_OK) return r;
-        HIPCHK(ctx, hipHostMalloc(&hout, (size_t)D * 24));
-        carve(tables);
-        HIPCHK(ctx, hipMemcpy(b->wstart, wstart.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(b->limit, annual_precip, sizeof(double) * (size_t)G, hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(b->lstart, lstart.data(), sizeof(int64_t) * ((size_t)G + 1), hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(b->pos, pos.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice));
-        return MOD16_OK;
-    }();
-    if (rc != MOD16_OK) {
-        if (owned) (void)hipFree(owned);
-        if (tables) (void)hipFree(tables);
-        if (ws) (void)hipFree(ws);
-        if (hout) (void)hipHostFree(hout);
-        if (skip) (void)hipFree(skip);
-        if (dlist) (void)hipFree(dlist);
-        b->wstart = nullptr;
-        b->limit = nullptr;
-        b->lstart = b->pos = nullptr;
-        return rc;
+    const char* what = "mod16_static_batch_set_annual: memory for the reordered problem";
+    int rc = fresh.owned.alloc(ctx, per_new * 17, what);
+    if (rc != MOD16_OK) return rc;
+    char* base = fresh.owned.as<char>();
+    for (int k = 0; k < 16; ++k) {
+        const void* cur = k < 14 ? b->drv[k] : k == 14 ? b->obs : b->wts;
+        if (k < 14) fresh.drv[k] = base + per_new * k;
+        if (!cur) continue;
+        const bool dense = k >= 14 || ((b->dense_drv >> k) & 1u);
+        HIPCHK(ctx, hipMemcpy(in.data(), cur, sizeof(double) * (size_t)(dense ? n : 1), hipMemcpyDeviceToHost));
+        if (dense)
+            for (int64_t j = 0; j < ni; ++j)
+                out[(size_t)j] = (k == 14 && src[(size_t)j] < 0) ? std::numeric_limits<double>::quiet_NaN() : in[from(j)];
+        else
+            out[0] = in[0];
+        HIPCHK(ctx, hipMemcpy(base + per_new * k, out.data(), sizeof(double) * (size_t)(dense ? ni : 1), hipMemcpyHostToDevice));
     }
-    // the problem takes the new arrays; the graphs and the per-block workspace held the old geometry
+    fresh.obs = base + per_new * 14;
+    fresh.wts = b->wts ? base + per_new * 15 : nullptr;
+    fresh.scale = reinterpret_cast<const double*>(base + per_new * 16);
+    for (int64_t j = 0; j < ni; ++j) out[(size_t)j] = src[(size_t)j] < 0 ? 0.0 : 86400.0 / lhv[from(j)];
+    HIPCHK(ctx, hipMemcpy(base + per_new * 16, out.data(), sizeof(double) * (size_t)ni, hipMemcpyHostToDevice));
+    // the domain mask goes with its pixels; the list and each site-year's part of it
+    HIPCHK(ctx, hipMemcpy(mask_in.data(), b->skip.get(), (size_t)n, hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < ni; ++j) {
+        mask[(size_t)j] = mask_in[from(j)];
+        if (mask[(size_t)j]) list.push_back(j);
+    }
+    for (int g = 0, u = 0; g <= G; ++g) {
+        while ((size_t)u < list.size() && list[(size_t)u] < gstart[(size_t)g]) ++u;
+        lstart[(size_t)g] = u;
+    }
+    fresh.nlist = (int64_t)list.size();
+    rc = fresh.skip.alloc(ctx, (size_t)ni, what);
+    if (rc != MOD16_OK) return rc;
+    HIPCHK(ctx, hipMemcpy(fresh.skip.get(), mask.data(), (size_t)ni, hipMemcpyHostToDevice));
+    if (!list.empty()) {
+        rc = fresh.list.alloc(ctx, sizeof(int64_t) * list.size(), what);
+        if (rc != MOD16_OK) return rc;
+        HIPCHK(ctx, hipMemcpy(fresh.list.get(), list.data(), sizeof(int64_t) * list.size(), hipMemcpyHostToDevice));
+    }
+    auto carve = [&](void* at) {
+        Carver tc(at);
+        fresh.wstart = tc.take<int32_t>(sizeof(int32_t) * ((size_t)G + 1));
+        fresh.limit = tc.take<double>(sizeof(double) * (size_t)G);
+        fresh.lstart = tc.take<int64_t>(sizeof(int64_t) * ((size_t)G + 1));
+        fresh.pos = tc.take<int64_t>(sizeof(int64_t) * (size_t)n);
+        return tc.used;
+    };
+    rc = fresh.annual.alloc(ctx, carve(nullptr), what);
+    if (rc == MOD16_OK) rc = fresh.ws.alloc(ctx, per_draw + align256((size_t)D * sizeof(unsigned)), what);
+    if (rc == MOD16_OK) rc = fresh.hout.alloc(ctx, (size_t)D * 24, what);
+    if (rc != MOD16_OK) return rc;
+    carve(fresh.annual.get());
+    HIPCHK(ctx, hipMemcpy(fresh.wstart, wstart.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(fresh.limit, annual_precip, sizeof(double) * (size_t)G, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(fresh.lstart, lstart.data(), sizeof(int64_t) * ((size_t)G + 1), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(fresh.pos, pos.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice));
+    eval_layout_draws(D, sizeof(double), fresh.ws.get(), &fresh.own, G);
+    fresh.dflags = reinterpret_cast<unsigned*>(fresh.ws.as<char>() + per_draw);
+    // commit: the graphs and the per-block workspace held the old geometry; the old arrays go with the assignment
     batch_drop_graphs(b);
-    if (b->eval_ws) (void)hipFree(b->eval_ws);
-    b->eval_ws = nullptr;
+    b->eval_ws.release();
     b->eval_draws = 0;
-    (void)hipFree(b->owned);
-    (void)hipFree(b->skip);
-    if (b->list) (void)hipFree(b->list);
-    (void)hipFree(b->ws);
-    (void)hipHostFree(b->hout);
-    b->owned = owned;
-    char* base = static_cast<char*>(owned);
-    for (int k = 0; k < 14; ++k) b->drv[k] = base + per_new * k;
-    b->obs = base + per_new * 14;
-    if (b->wts) b->wts = base + per_new * 15;
-    b->scale = reinterpret_cast<const double*>(base + per_new * 16);
-    b->skip = skip;
-    b->list = dlist;
-    b->nlist = (int64_t)list.size();
-    b->annual = tables;
-    b->ws = ws;
-    b->own = EvalWs();
-    eval_layout_draws(D, sizeof(double), b->ws, &b->own, G);
-    b->dflags = reinterpret_cast<unsigned*>(static_cast<char*>(b->ws) + per_draw);
-    b->hout = static_cast<double*>(hout);
-    b->n = ni;
-    b->gx = (int)((ni + kBlock - 1) / kBlock);
-    b->G = G;
-    b->S = S;
+    static_cast<BatchArrays&>(*b) = std::move(fresh);
     return MOD16_OK;
 }
 
@@ -806,17 +737,17 @@ static int batch_rows(mod16_batch* b, const T* params, int64_t ndraw, T* out_day
     T* const host_out[3] = {out_day, out_night, out_total};
     // (a problem laid out site-year-major, b->pos: the rows of the resident pixels, then the caller's gathered from them)
     const size_t per_out = sizeof(T) * (size_t)ndraw * (size_t)b->n, per_user = sizeof(T) * (size_t)ndraw * (size_t)b->n_user;
-    int rc = rows_reserve(b, (align256(per_out) + (b->pos ? align256(per_user) : 0)) *
-                                 ((out_day != nullptr) + (out_night != nullptr) + (out_total != nullptr)),
-                          "mod16_static_batch_rows: device memory for the [ndraw][n] rows");
+    int rc = b->rows.reserve(ctx, (align256(per_out) + (b->pos ? align256(per_user) : 0)) *
+                                      ((out_day != nullptr) + (out_night != nullptr) + (out_total != nullptr)),
+                             "mod16_static_batch_rows: device memory for the [ndraw][n] rows");
     if (rc != MOD16_OK) return rc;
-    memcpy(b->hparams, params, sizeof(T) * (size_t)ndraw * 11);
-    HIPCHK(ctx, hipMemcpyAsync(b->own.params, b->hparams, sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
+    memcpy(b->hparams.get(), params, sizeof(T) * (size_t)ndraw * 11);
+    HIPCHK(ctx, hipMemcpyAsync(b->own.params, b->hparams.get(), sizeof(T) * (size_t)ndraw * 11, hipMemcpyHostToDevice, b->st));
     StaticBatchArgs<T> a = batch_args<T>(b);
-    Carver c(b->rows);
+    Carver c(b->rows.get());
     for (int k = 0; k < 3; ++k)
         if (host_out[k]) a.out[k] = c.take<T>(per_out);
-    rc = static_batch_rows<T>(ctx, a, ndraw, nullptr, nullptr, nullptr, nullptr, b->dflags, b->skip, b->flags, b->st, true);
+    rc = static_batch_rows<T>(ctx, a, ndraw, nullptr, nullptr, nullptr, nullptr, b->dflags, b->skip.as<uint8_t>(), b->flags, b->st, true);
     if (rc != MOD16_OK) return rc;
     if (b->pos) {
         const int64_t total = ndraw * b->n_user;
@@ -853,16 +784,11 @@ extern "C" int mod16_static_batch_time(mod16_batch* b, int launches, float* ms) 
     if (!b || !ms || launches <= 0 || !b->last) return MOD16_ERR_ARG;
     MOD16_LOCK(b->ctx);
     if (hipSetDevice(b->device) != hipSuccess) return MOD16_ERR_HIP;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return MOD16_ERR_HIP;
-    bool ok = hipEventRecord(e0, b->st) == hipSuccess;
+    EventTimer timer;
+    bool ok = timer.start(b->st) == hipSuccess;
     for (int i = 0; i < launches && ok; ++i) ok = hipGraphLaunch(b->last->exec, b->st) == hipSuccess;
-    ok = ok && hipEventRecord(e1, b->st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
     float t = 0.f;
-    ok = ok && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (!ok) return MOD16_ERR_HIP;
+    if (!ok || timer.stop_ms(b->st, &t) != MOD16_OK) return MOD16_ERR_HIP;
     *ms = t / (float)launches;
     return MOD16_OK;
 }

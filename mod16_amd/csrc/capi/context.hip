@@ -44,27 +44,6 @@ extern "C" int mod16_destroy(mod16_ctx* ctx) {
         ctx->graphs.clear();
     }
     (void)hipSetDevice(ctx->device);
-    for (int s = 0; s < kSlots; ++s) {
-        if (ctx->slab[s]) (void)hipFree(ctx->slab[s]);
-        if (ctx->streams[s]) (void)hipStreamDestroy(ctx->streams[s]);
-    }
-    if (ctx->scalars) (void)hipFree(ctx->scalars);
-    if (ctx->small_host) (void)hipHostFree(ctx->small_host);
-    if (ctx->batch_buf) (void)hipFree(ctx->batch_buf);
-    if (ctx->bc_buf) (void)hipFree(ctx->bc_buf);
-    if (ctx->lut64) (void)hipFree(ctx->lut64);
-    if (ctx->lut32) (void)hipFree(ctx->lut32);
-    if (ctx->tab64) (void)hipFree(ctx->tab64);
-    if (ctx->dyn_counters) (void)hipFree(ctx->dyn_counters);
-    if (ctx->status) (void)hipFree(ctx->status);
-    if (ctx->status_host) (void)hipHostFree(ctx->status_host);
-    if (ctx->static_flag) (void)hipFree(ctx->static_flag);
-    if (ctx->ws.partial) (void)hipFree(ctx->ws.partial);
-    for (void* p : ctx->retired) (void)hipFree(p);
-    if (ctx->ws_event) (void)hipEventDestroy(ctx->ws_event);
-    if (ctx->diag_dev) (void)hipFree(ctx->diag_dev);
-    if (ctx->diag_host) (void)hipHostFree(ctx->diag_host);
-    if (ctx->hdiag_dev) (void)hipFree(ctx->hdiag_dev);
     delete ctx;
     return MOD16_OK;
 }
@@ -103,18 +82,21 @@ extern "C" int mod16_create(int device, mod16_ctx** out) {
         if (const char* g = getenv("MOD16_POISON_TICKET")) ctx->poison_ticket = std::max(0, atoi(g));
         if (const char* g = getenv("MOD16_POISON_BYTE")) ctx->poison_byte = std::max(-1, std::min(255, atoi(g)));
 #endif
-        HIPCHK(ctx, hipMalloc(&ctx->dyn_counters, 64 * 128));
+        const char* what = "mod16_create: memory for the context's tables and workspaces";
+        int r = ctx->dyn_counters.alloc(ctx, 64 * 128, what);
+        if (r != MOD16_OK) return r;
         {   // ticket = 0, blocks done = 0, and a serial number (word [3]) that starts somewhere else in
             // every slot of the ring: successive launches take successive slots and share the
             // diagnostics workspace, so their markers (kSerialField) must differ -- launch j carries
             // (j % 64) * 1021 + j / 64
             unsigned init[64 * 32] = {};
             for (unsigned i = 0; i < 64; ++i) init[i * 32 + 3] = i * 1021u;
-            HIPCHK(ctx, hipMemcpy(ctx->dyn_counters, init, sizeof init, hipMemcpyHostToDevice));
+            HIPCHK(ctx, hipMemcpy(ctx->dyn_counters.get(), init, sizeof init, hipMemcpyHostToDevice));
         }
         const size_t nlut = MOD16_LUT_ROWS * kLutCols;
-        HIPCHK(ctx, hipMalloc(&ctx->lut64, nlut * sizeof(double)));
-        HIPCHK(ctx, hipMalloc(&ctx->lut32, nlut * sizeof(float)));
+        r = ctx->lut64.alloc(ctx, nlut * sizeof(double), what);
+        if (r == MOD16_OK) r = ctx->lut32.alloc(ctx, nlut * sizeof(float), what);
+        if (r != MOD16_OK) return r;
         {   // exp/log tables of FastMath<double> (mod16_math.hpp)
             constexpr int n = FastMath<double>::kTabDoubles;
             double t[n];
@@ -136,19 +118,22 @@ extern "C" int mod16_create(int device, mod16_ctx** out) {
                 0x1.730bd6d1a9cc9p+8, -0x1.096571085f8f7p+4, 0x1.01d9b2280ab84p-3, 0x1.3835059a0bfaap-9,
                 0x1.8732949feb6b7p-14, 0x1.555f18e36b65ap-18};
             for (int j = 0; j < 16; ++j) t[FastMath<double>::kTabRaw + j] = j < 10 ? kPressurePoly[j] : 0.0;
-            HIPCHK(ctx, hipMalloc(&ctx->tab64, sizeof t));
-            HIPCHK(ctx, hipMemcpy(ctx->tab64, t, sizeof t, hipMemcpyHostToDevice));
+            r = ctx->tab64.alloc(ctx, sizeof t, what);
+            if (r != MOD16_OK) return r;
+            HIPCHK(ctx, hipMemcpy(ctx->tab64.get(), t, sizeof t, hipMemcpyHostToDevice));
         }
-        HIPCHK(ctx, hipMalloc(&ctx->status, sizeof(unsigned)));
-        HIPCHK(ctx, hipMemset(ctx->status, 0, sizeof(unsigned)));
-        HIPCHK(ctx, hipHostMalloc(&ctx->status_host, sizeof(unsigned)));
-        HIPCHK(ctx, ws_alloc(ctx->ws, kDiagBlocks));
-        HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ws_event, hipEventDisableTiming));
-        HIPCHK(ctx, hipMalloc(&ctx->diag_dev, sizeof(double) * kDiag));
-        HIPCHK(ctx, hipHostMalloc(&ctx->diag_host, sizeof(double) * kDiag));
-        HIPCHK(ctx, hipMalloc(&ctx->hdiag_dev, sizeof(double) * kDiag * kSlots));
-        HIPCHK(ctx, hipMalloc(&ctx->scalars, 32 * sizeof(double)));
-        return MOD16_OK;
+        r = ctx->status.alloc(ctx, sizeof(unsigned), what);
+        if (r != MOD16_OK) return r;
+        HIPCHK(ctx, hipMemset(ctx->status.get(), 0, sizeof(unsigned)));
+        r = ctx->status_host.alloc(ctx, sizeof(unsigned), what);
+        if (r == MOD16_OK) r = ws_alloc(ctx, ctx->ws, kDiagBlocks);
+        if (r != MOD16_OK) return r;
+        HIPCHK(ctx, ctx->ws_event.ensure(hipEventDisableTiming));
+        r = ctx->diag_dev.alloc(ctx, sizeof(double) * kDiag, what);
+        if (r == MOD16_OK) r = ctx->diag_host.alloc(ctx, sizeof(double) * kDiag, what);
+        if (r == MOD16_OK) r = ctx->hdiag_dev.alloc(ctx, sizeof(double) * kDiag * kSlots, what);
+        if (r == MOD16_OK) r = ctx->scalars.alloc(ctx, 32 * sizeof(double), what);
+        return r;
     }();
     if (rc != MOD16_OK) {
         // keep the message for the caller? the ctx is gone: print it once
@@ -168,8 +153,8 @@ extern "C" int mod16_set_bplut_f64(mod16_ctx* ctx, const double* lut) {
     float h32[MOD16_LUT_ROWS * kLutCols];
     derive_lut(lut, h64);
     for (int i = 0; i < MOD16_LUT_ROWS * kLutCols; ++i) h32[i] = (float)h64[i];
-    HIPCHK(ctx, hipMemcpy(ctx->lut64, h64, sizeof h64, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->lut32, h32, sizeof h32, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->lut64.get(), h64, sizeof h64, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->lut32.get(), h32, sizeof h32, hipMemcpyHostToDevice));
     ctx->have_lut = true;
     return MOD16_OK;
 }
@@ -207,36 +192,23 @@ extern "C" int mod16_measure_copy(mod16_ctx* ctx, int64_t bytes, int reps, float
     if (!ctx || !gbps || bytes < 16 || reps <= 0) return fail(ctx, MOD16_ERR_ARG, "mod16_measure_copy: bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int64_t nvec = bytes / 16;
-    void *a = nullptr, *b = nullptr;
-    if (hipMalloc(&a, nvec * 16) != hipSuccess || hipMalloc(&b, nvec * 16) != hipSuccess) {
-        (void)hipGetLastError();
-        if (a) (void)hipFree(a);
-        return fail(ctx, MOD16_ERR_NOMEM, "mod16_measure_copy: device memory for the two buffers");
+    DevMem a, b;
+    const char* what = "mod16_measure_copy: device memory for the two buffers";
+    int rc = a.alloc(ctx, nvec * 16, what);
+    if (rc == MOD16_OK) rc = b.alloc(ctx, nvec * 16, what);
+    if (rc != MOD16_OK) return rc;
+    HIPCHK(ctx, hipMemset(a.get(), 1, nvec * 16));
+    HIPCHK(ctx, hipMemset(b.get(), 0, nvec * 16));
+    EventTimer timer;
+    const unsigned grid = (unsigned)((nvec + kBlock - 1) / kBlock);
+    float best = 1e30f;
+    for (int r = 0; r <= reps; ++r) {      // the first launch is a warm-up
+        HIPCHK(ctx, timer.start(nullptr));
+        hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(kBlock), 0, nullptr, a.as<const copy_vec_t>(), b.as<copy_vec_t>(), nvec);
+        float ms = 0.f;
+        if (timer.stop_ms(nullptr, &ms) != MOD16_OK) return fail(ctx, MOD16_ERR_HIP, "mod16_measure_copy: timing the copy failed");
+        if (r > 0 && ms < best) best = ms;
     }
-    int rc = [&]() -> int {
-        HIPCHK(ctx, hipMemset(a, 1, nvec * 16));
-        HIPCHK(ctx, hipMemset(b, 0, nvec * 16));
-        hipEvent_t e0, e1;
-        HIPCHK(ctx, hipEventCreate(&e0));
-        HIPCHK(ctx, hipEventCreate(&e1));
-        const unsigned grid = (unsigned)((nvec + kBlock - 1) / kBlock);
-        float best = 1e30f;
-        for (int r = 0; r <= reps; ++r) {      // the first launch is a warm-up
-            HIPCHK(ctx, hipEventRecord(e0, nullptr));
-            hipLaunchKernelGGL(copy_kernel, dim3(grid), dim3(kBlock), 0, nullptr,
-                               static_cast<const copy_vec_t*>(a), static_cast<copy_vec_t*>(b), nvec);
-            HIPCHK(ctx, hipEventRecord(e1, nullptr));
-            HIPCHK(ctx, hipEventSynchronize(e1));
-            float ms = 0.f;
-            HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
-            if (r > 0 && ms < best) best = ms;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        *gbps = (float)(2.0 * (double)nvec * 16.0 / (best * 1e-3) / 1e9);
-        return MOD16_OK;
-    }();
-    (void)hipFree(a);
-    (void)hipFree(b);
-    return rc;
+    *gbps = (float)(2.0 * (double)nvec * 16.0 / (best * 1e-3) / 1e9);
+    return MOD16_OK;
 }

@@ -54,9 +54,11 @@ static int classify_entry(mod16_ctx* ctx, const T* const* params, const int64_t*
         if (pstride[k]) a.dense |= 1u << k;
     }
     // rows (host) and the answer word share one small device block
-    char* block = nullptr;
+    DevMem mem;
     const size_t rbytes = (sizeof(T) * kClassRows * kClassPars + 15) / 16 * 16;      // (the 64-bit answer word behind them: aligned)
-    HIPCHK(ctx, hipMalloc(&block, rbytes + 8));
+    int rc = mem.alloc(ctx, rbytes + 8, "mod16_classify: device memory for the rows and the answer word");
+    if (rc != MOD16_OK) return rc;
+    char* block = mem.as<char>();
     const unsigned long long none = ~0ull;
     hipError_t e = hipMemcpyAsync(block, rows, sizeof(T) * nrows * kClassPars, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(block + rbytes, &none, 8, hipMemcpyHostToDevice, st);
@@ -73,7 +75,6 @@ static int classify_entry(mod16_ctx* ctx, const T* const* params, const int64_t*
     unsigned long long got = none;
     if (e == hipSuccess) e = hipMemcpyAsync(&got, block + rbytes, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(block);
     HIPCHK(ctx, e);
     *unmatched = got == none ? -1 : (int64_t)got;
     return MOD16_OK;

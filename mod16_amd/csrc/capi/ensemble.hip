@@ -6,13 +6,12 @@
 struct mod16_ensemble {
     int device = 0;
     int64_t members = 0;
-    double* tables = nullptr;    // device [members][MOD16_LUT_ROWS][kLutCols]
+    DevMem tables;               // device double [members][MOD16_LUT_ROWS][kLutCols]
 };
 
 extern "C" int mod16_ensemble_destroy(mod16_ensemble* ens) {
     if (!ens) return MOD16_OK;
     (void)hipSetDevice(ens->device);
-    if (ens->tables) (void)hipFree(ens->tables);
     delete ens;
     return MOD16_OK;
 }
@@ -32,8 +31,8 @@ extern "C" int mod16_ensemble_create(mod16_ctx* ctx, const double* tables, int64
     std::vector<double> host((size_t)members * kEnsTable);
     for (int64_t m = 0; m < members; ++m)
         derive_lut(tables + (size_t)m * MOD16_N_CLASSES * MOD16_N_PARAMS, host.data() + (size_t)m * kEnsTable);
-    int rc = dev_alloc(ctx, &ens->tables, host.size() * sizeof(double), "mod16_ensemble_create: device memory for the members' tables");
-    if (rc == MOD16_OK && hipMemcpy(ens->tables, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+    int rc = ens->tables.alloc(ctx, host.size() * sizeof(double), "mod16_ensemble_create: device memory for the members' tables");
+    if (rc == MOD16_OK && hipMemcpy(ens->tables.get(), host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         rc = fail(ctx, MOD16_ERR_HIP, "mod16_ensemble_create: upload of the members' tables failed");
     if (rc != MOD16_OK) {
         mod16_ensemble_destroy(ens);
@@ -47,10 +46,10 @@ extern "C" int mod16_ensemble_create(mod16_ctx* ctx, const double* tables, int64
 template <typename T>
 static int launch_ensemble(mod16_ctx* ctx, const mod16_ensemble* ens, EnsArgs<T> a, unsigned flags, hipStream_t st) {
     if (a.n <= 0) return MOD16_OK;
-    a.tables = ens->tables;
+    a.tables = ens->tables.as<double>();
     a.members = (int)ens->members;
-    a.tab = ctx->tab64;
-    a.status = ctx->status;
+    a.tab = ctx->tab64.as<double>();
+    a.status = ctx->status.as<unsigned>();
     const int64_t nbatch = (a.n + kBlock - 1) / kBlock;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t)ctx->cus * 8));
     if (flags & MOD16_MATH_EXACT) hipLaunchKernelGGL((ens_kernel<T, false>), dim3(grid), dim3(kBlock), 0, st, a);

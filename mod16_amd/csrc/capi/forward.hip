@@ -38,14 +38,9 @@ static int et_host(mod16_ctx* ctx, const EtArgs<T>& h, unsigned flags, double* t
     if (has_rows_or_cols(h)) {
         size_t need = 256;
         for (size_t b : whole) need += (b + 255) / 256 * 256;
-        if (ctx->bc_bytes < need) {
-            if (ctx->bc_buf) HIPCHK(ctx, hipFree(ctx->bc_buf));
-            ctx->bc_buf = nullptr;
-            ctx->bc_bytes = 0;
-            HIPCHK(ctx, hipMalloc(&ctx->bc_buf, need));
-            ctx->bc_bytes = need;
-        }
-        char* cur = static_cast<char*>(ctx->bc_buf);
+        int rc = ctx->bc_buf.reserve(ctx, need, "mod16_et2: device memory for the broadcast inputs");
+        if (rc != MOD16_OK) return rc;
+        char* cur = ctx->bc_buf.as<char>();
         for (int i = 0; i < p.count; ++i) {
             if (!whole[i]) continue;
             if (hipMemcpy(cur, p.a[i].host, whole[i], hipMemcpyHostToDevice) != hipSuccess)
@@ -200,10 +195,6 @@ extern "C" int mod16_graph_destroy(mod16_graph* g) {
         }
     }
     (void)hipSetDevice(g->device);           // the context may be gone already (interpreter exit)
-    if (g->exec) (void)hipGraphExecDestroy(g->exec);
-    if (g->graph) (void)hipGraphDestroy(g->graph);
-    if (g->counter) (void)hipFree(g->counter);
-    if (g->ws.partial) (void)hipFree(g->ws.partial);
     delete g;
     return MOD16_OK;
 }
@@ -215,7 +206,7 @@ static int graph_entry(mod16_ctx* ctx, const uint8_t* cls, const T* const* drive
     if (!ctx || !out) return MOD16_ERR_ARG;
     *out = nullptr;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
+    HIPCHK(ctx, ctx->streams[0].ensure());
     hipStream_t st = ctx->streams[0];
     mod16_graph* g = new (std::nothrow) mod16_graph;
     if (!g) return MOD16_ERR_NOMEM;
@@ -226,19 +217,21 @@ static int graph_entry(mod16_ctx* ctx, const uint8_t* cls, const T* const* drive
         // recording call, launch errors from the instantiation -- so no wait for whatever the
         // caller's streams are still doing to the raster is needed; replays are ordered by
         // the stream they are launched on)
-        HIPCHK(ctx, hipMalloc(&g->counter, 128));
-        HIPCHK(ctx, hipMemset(g->counter, 0, 128));       // (not captured: the launches keep it at zero)
-        ctx->force_counter = g->counter;
+        int r = g->counter.alloc(ctx, 128, "mod16_graph_et: device memory for the graph's ticket counter");
+        if (r != MOD16_OK) return r;
+        HIPCHK(ctx, hipMemset(g->counter.get(), 0, 128));       // (not captured: the launches keep it at zero)
+        ctx->force_counter = g->counter.as<unsigned long long>();
         // the graph's kernel nodes keep pointing at this workspace for as long as
         // the graph lives, whatever the context's own workspace does meanwhile
-        HIPCHK(ctx, ws_alloc(g->ws, std::max<int64_t>(kDiagBlocks, stream_ws_blocks(stream_geom(ctx, std::max<int64_t>(n, 0), VecOf<T>::v).nruns))));
+        r = ws_alloc(ctx, g->ws, std::max<int64_t>(kDiagBlocks, stream_ws_blocks(stream_geom(ctx, std::max<int64_t>(n, 0), VecOf<T>::v).nruns)));
+        if (r != MOD16_OK) return r;
         ctx->force_ws = &g->ws;
         HIPCHK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        int r = et_diag_entry<T>(ctx, cls, drivers, dstride, n, out_day, out_night, flags, ddiag, st);
-        hipError_t e = hipStreamEndCapture(st, &g->graph);
+        r = et_diag_entry<T>(ctx, cls, drivers, dstride, n, out_day, out_night, flags, ddiag, st);
+        hipError_t e = hipStreamEndCapture(st, &g->cg.graph);
         if (r != MOD16_OK) return r;
         HIPCHK(ctx, e);
-        HIPCHK(ctx, hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
+        HIPCHK(ctx, hipGraphInstantiate(&g->cg.exec, g->cg.graph, nullptr, nullptr, 0));
         return MOD16_OK;
     }();
     ctx->force_counter = nullptr;
@@ -267,14 +260,14 @@ extern "C" int mod16_graph_et_diag_f32(mod16_ctx* ctx, const uint8_t* cls, const
     return graph_entry<float>(ctx, cls, drivers, dstride, n, out_day, out_night, flags, ddiag, out);
 }
 extern "C" int mod16_graph_launch(mod16_graph* g, void* stream) {
-    if (!g || !g->exec) return MOD16_ERR_ARG;
+    if (!g || !g->cg.exec) return MOD16_ERR_ARG;
     // (a graph may outlive the context it was built with -- to be destroyed, not replayed: its
     // kernels point into the context's tables. No error text through g->ctx either way)
     if (!graph_alive(g)) {
         fprintf(stderr, "mod16_graph_launch: the context this graph was captured with has been destroyed\n");
         return MOD16_ERR_ARG;
     }
-    const hipError_t e = hipGraphLaunch(g->exec, static_cast<hipStream_t>(stream));
+    const hipError_t e = hipGraphLaunch(g->cg.exec, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) {
         fprintf(stderr, "mod16_graph_launch: %s\n", hipGetErrorString(e));
         return MOD16_ERR_HIP;
@@ -314,11 +307,9 @@ extern "C" int mod16_time_et(mod16_ctx* ctx, int is_f32, const uint8_t* cls,
     if (!ctx || !ms || launches <= 0) return fail(ctx, MOD16_ERR_ARG, "mod16_time_et: bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t e0, e1;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    HIPCHK(ctx, hipEventCreate(&e1));
+    EventTimer timer;
     int rc = MOD16_OK;
-    HIPCHK(ctx, hipEventRecord(e0, st));
+    HIPCHK(ctx, timer.start(st));
     for (int i = 0; i < launches && rc == MOD16_OK; ++i) {
         if (ddiag && is_f32)
             rc = mod16_et_diag_f32(ctx, cls, reinterpret_cast<const float* const*>(drivers), dstride, n,
@@ -339,12 +330,8 @@ extern "C" int mod16_time_et(mod16_ctx* ctx, int is_f32, const uint8_t* cls,
                               static_cast<double*>(out_day), static_cast<double*>(out_night),
                               reinterpret_cast<double* const*>(out_sep), flags, MOD16_DEVICE, stream);
     }
-    HIPCHK(ctx, hipEventRecord(e1, st));
-    HIPCHK(ctx, hipEventSynchronize(e1));
     float t = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&t, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (timer.stop_ms(st, &t) != MOD16_OK) return fail(ctx, MOD16_ERR_HIP, "mod16_time_et: timing the launches failed");
     *ms = t / (float)launches;
     return rc;
 }

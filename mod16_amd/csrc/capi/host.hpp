@@ -69,20 +69,14 @@ static bool small_reserve(mod16_ctx* ctx, int64_t n, size_t elem, int arrays, si
     *per_arr = (size_t)cap * elem;
     const size_t need = 256 + *per_arr * arrays + 3 * (size_t)cap + 256;
     bool ok = true;
-    if (ctx->small_bytes < need) {
-        if (ctx->small_host) (void)hipHostFree(ctx->small_host);
-        ctx->small_host = ctx->small_dev = nullptr;
-        ctx->small_bytes = 0;
-        ok = hipHostMalloc(&ctx->small_host, need, hipHostMallocDefault) == hipSuccess &&
-             hipHostGetDevicePointer(&ctx->small_dev, ctx->small_host, 0) == hipSuccess;
-        if (ok) ctx->small_bytes = need;
-    }
-    if (ok && !ctx->streams[0]) ok = hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking) == hipSuccess;
+    if (ctx->small_host.bytes() < need)
+        ok = ctx->small_host.alloc(ctx, need, "page-locked memory for the small calls' buffer") == MOD16_OK &&
+             hipHostGetDevicePointer(&ctx->small_dev, ctx->small_host.get(), 0) == hipSuccess;
+    ok = ok && ctx->streams[0].ensure() == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        if (ctx->small_host) (void)hipHostFree(ctx->small_host);
-        ctx->small_host = ctx->small_dev = nullptr;
-        ctx->small_bytes = 0;
+        ctx->small_host.release();
+        ctx->small_dev = nullptr;
         ctx->small_pixels = 0;
     }
     return ok;
@@ -111,7 +105,7 @@ static int host_small(mod16_ctx* ctx, const HostPlan& p, int64_t n, bool pad, La
         for (int64_t i = 0; i < n; ++i)
             if (p.cls[i] >= MOD16_N_CLASSES)
                 return fail(ctx, MOD16_ERR_CLASS_RANGE, "class raster holds a code >= 13 (numpy would raise IndexError)");
-    char* hb = static_cast<char*>(ctx->small_host);
+    char* hb = ctx->small_host.as<char>();
     char* db = static_cast<char*>(ctx->small_dev);
     const size_t cap = per_arr / p.elem;           // the buffer's capacity in pixels
     auto at = [&](int i) { return 256 + p.offset(i, per_arr, cap); };
@@ -159,33 +153,33 @@ static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slot
     const size_t per_b = ((size_t)tile + 255) / 256 * 256;
     const size_t need = p.offset(p.count, per_arr, per_b) + 256;
     if (ctx->slab_bytes < need) {
-        for (int s = 0; s < kSlots; ++s) {
-            if (ctx->slab[s]) HIPCHK(ctx, hipFree(ctx->slab[s]));
-            ctx->slab[s] = nullptr;
-        }
+        for (int s = 0; s < kSlots; ++s) ctx->slab[s].release();
         ctx->slab_bytes = need;
     }
     for (int s = 0; s < nslots; ++s) {
-        if (!ctx->slab[s]) HIPCHK(ctx, hipMalloc(&ctx->slab[s], ctx->slab_bytes));
-        if (!ctx->streams[s]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[s], hipStreamNonBlocking));
+        if (!ctx->slab[s]) {
+            int rc = ctx->slab[s].alloc(ctx, ctx->slab_bytes, "HOST mode: device memory for a staging slab");
+            if (rc != MOD16_OK) return rc;
+        }
+        HIPCHK(ctx, ctx->streams[s].ensure());
     }
     // broadcast scalars live in one small device array
     char hs[256] = {};
     p.put_scalars(hs);
-    HIPCHK(ctx, hipMemcpy(ctx->scalars, hs, sizeof hs, hipMemcpyHostToDevice));
-    char* dscal = static_cast<char*>(ctx->scalars);
+    HIPCHK(ctx, hipMemcpy(ctx->scalars.get(), hs, sizeof hs, hipMemcpyHostToDevice));
+    char* dscal = ctx->scalars.as<char>();
     if (pipeline) {   // the kernels' shared workspace at its final size before any thread launches
         const int64_t npiece = (tile / (16 / p.elem) + 63) / 64;
         int rc = reserve_diag(ctx, npiece / 2 + 2048);
         if (rc != MOD16_OK) return rc;
     }
     auto stage = [&](int slot, int64_t off) -> int {
-        char* base = static_cast<char*>(ctx->slab[slot]);
+        char* base = ctx->slab[slot].as<char>();
         HostTile t;
         t.m = std::min(tile, n - off);
         t.off = off;
         t.st = ctx->streams[slot];
-        t.diag = tile_diag ? ctx->hdiag_dev + (size_t)slot * kDiag : nullptr;
+        t.diag = tile_diag ? ctx->hdiag_dev.as<double>() + (size_t)slot * kDiag : nullptr;
         for (int i = 0; i < p.count; ++i) {
             const HostPlan::Array& x = p.a[i];
             t.dev[i] = p.where(i, base + p.offset(i, per_arr, per_b), dscal);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/mod16_hip.h"
+#include "own.hpp"
 #include "../mod16_kernels.hpp"
 #include "../mod16_stream.hpp"
 
@@ -36,17 +37,11 @@ constexpr int kSmallPixelsMax = 1 << 18;            // ... and what MOD16_SMALL_
 // graph owns its own, so growing the context's never pulls memory from under
 // a graph that is replayed later.
 struct DiagWs {
-    double* partial = nullptr;   // device [capacity][kDiag], then 128 bytes: the "blocks done" counter
+    DevMem mem;                  // device [capacity][kDiag], then 128 bytes: the "blocks done" counter
     int64_t capacity = 0;        // in partials
-    unsigned* done() const { return reinterpret_cast<unsigned*>(partial + capacity * 8); }
+    double* partial() const { return mem.as<double>(); }
+    unsigned* done() const { return reinterpret_cast<unsigned*>(partial() + capacity * 8); }
 };
-// hipMalloc of a workspace for `blocks` partials + the (zeroed) counter behind them
-static hipError_t ws_alloc(DiagWs& ws, int64_t blocks) {
-    hipError_t e = hipMalloc(&ws.partial, sizeof(double) * (blocks * 8 + 16));
-    if (e != hipSuccess) return e;
-    ws.capacity = blocks;
-    return hipMemset(ws.done(), 0, 128);
-}
 
 // A captured graph's kernel nodes point into its context (parameter table, exp / log tables, status
 // word): the context keeps a list of its live graphs, and mod16_destroy marks them dead -- a replay
@@ -72,46 +67,46 @@ struct mod16_ctx {
     int poison_byte = -1;            // ... MOD16_POISON_BYTE=b: the byte every byte of that ticket is set to (default: the ticket becomes 2^40)
     int poison_ticket = 0;           // experiments build, MOD16_POISON_TICKET=k: the k-th dynamically scheduled launch finds
                                      // its ticket counter in use (what an abandoned launch leaves behind): the test of kStatusIncomplete
-    unsigned long long* dyn_counters = nullptr;   // ring of ticket counters, 128 B apart
+    // Ownership: DevMem / PinnedMem / Event / Stream members own what they name and free it with the
+    // context, in reverse order of declaration (the streams, declared last, go first); raw pointers
+    // are views of memory owned elsewhere.
+    DevMem dyn_counters;             // ring of ticket counters (unsigned long long), 128 B apart
     int dyn_next = 0;
     bool have_lut = false;
-    double* lut64 = nullptr;     // device [MOD16_LUT_ROWS][kLutCols]
-    float* lut32 = nullptr;
-    double* tab64 = nullptr;         // exp/log tables of FastMath<double>
-    unsigned* status = nullptr;      // device status word
-    unsigned* status_host = nullptr; // pinned mirror
-    unsigned* static_flag = nullptr; // device word of mod16_et_static_*
+    DevMem lut64;                    // device double [MOD16_LUT_ROWS][kLutCols]
+    DevMem lut32;                    // ... float
+    DevMem tab64;                    // exp/log tables of FastMath<double>
+    DevMem status;                   // device status word (unsigned)
+    PinnedMem status_host;           // pinned mirror
+    DevMem static_flag;              // device word of mod16_et_static_*
     DiagWs ws;                       // diagnostics partials of launches outside a graph
-    std::vector<void*> retired;      // outgrown workspaces (freed with the context)
-    std::vector<mod16_graph*> graphs; // graphs captured with this context and still alive (graph_registry_mu)
-    DiagWs* force_ws = nullptr;      // workspace to use instead (graph capture)
-    hipEvent_t ws_event = nullptr;   // recorded behind the last launch that produced diagnostics in `ws`
-    hipStream_t ws_stream = nullptr; // ... and the stream it ran on
+    std::vector<DevMem> retired;     // outgrown workspaces (freed with the context)
+    std::vector<mod16_graph*> graphs; // graphs captured with this context and still alive (graph_registry_mu); views
+    DiagWs* force_ws = nullptr;      // workspace to use instead (graph capture); a view
+    Event ws_event;                  // recorded behind the last launch that produced diagnostics in `ws`
+    hipStream_t ws_stream = nullptr; // ... and the stream it ran on (the caller's)
     bool ws_pending = false;
     bool ws_recorded = false;        // ... and whether ws_event was recorded behind it
     bool ws_multi = false;           // the context has launched on more than one stream (or runs HOST tiles on
                                      // its slots): every launch records ws_event from now on
-    double* diag_dev = nullptr;      // device [kDiag]
-    double* diag_host = nullptr;     // pinned [kDiag]
-    double* hdiag_dev = nullptr;     // device [kSlots][kDiag]: per-tile diagnostics of the HOST mode (mod16_et_hdiag_*)
-    // HOST-mode staging: per slot one device slab + one stream
-    void* slab[kSlots] = {};
-    size_t slab_bytes = 0;
-    hipStream_t streams[kSlots] = {};
+    DevMem diag_dev;                 // device double [kDiag]
+    PinnedMem diag_host;             // pinned double [kDiag]
+    DevMem hdiag_dev;                // device double [kSlots][kDiag]: per-tile diagnostics of the HOST mode (mod16_et_hdiag_*)
+    // HOST-mode staging: per slot one device slab (+ one stream, below)
+    DevMem slab[kSlots];
+    size_t slab_bytes = 0;           // what every slab holds (the largest call seen)
     std::mutex launch_mu;            // HOST mode: kernel launches of the staging threads
-    void* scalars = nullptr;         // device copies of broadcast scalars
+    DevMem scalars;                  // device copies of broadcast scalars
     // HOST mode, small calls (a flux-tower site, a year of one pixel): one page-locked buffer the
     // kernel reads its inputs from and writes its outputs to over the link -- no copy commands at all
     int small_pixels = kSmallPixels; // MOD16_SMALL_PIXELS: calls of at most this many pixels go that way (0: none)
-    void* small_host = nullptr;      // hipHostMalloc'ed
-    void* small_dev = nullptr;       // ... as the device addresses it
-    size_t small_bytes = 0;
-    unsigned long long* force_counter = nullptr;   // ticket counter to use instead of the ring (graph capture)
-    void* bc_buf = nullptr;          // HOST mode: device copies of (N,) / (T, 1) inputs (mod16_et2_*)
-    size_t bc_bytes = 0;
-    void* batch_buf = nullptr;       // HOST-mode workspace of mod16_et_static_batch_*
-    size_t batch_bytes = 0;
+    PinnedMem small_host;
+    void* small_dev = nullptr;       // ... as the device addresses it; a view
+    unsigned long long* force_counter = nullptr;   // ticket counter to use instead of the ring (graph capture); a view
+    DevMem bc_buf;                   // HOST mode: device copies of (N,) / (T, 1) inputs (mod16_et2_*); only grows
+    DevMem batch_buf;                // HOST-mode workspace of mod16_et_static_batch_*; only grows
     std::string err;
+    Stream streams[kSlots];          // one per staging slot, made on first use; [0] also serves the other HOST-mode calls
 };
 
 #define HIPCHK(ctx, call)                                                          \
@@ -135,23 +130,14 @@ static int fail(mod16_ctx* ctx, int code, const char* msg) {
     return code;
 }
 
-// Device memory that cannot be had is MOD16_ERR_NOMEM with `what` as the message, not a HIP error:
-// *p is NULL and the runtime's last error is cleared, so that the next hipGetLastError() behind a
-// launch on this thread reports its own launch. (dev_alloc_async: stream-ordered, freed with hipFreeAsync.)
-static int dev_alloc_failed(mod16_ctx* ctx, void** p, const char* what) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return fail(ctx, MOD16_ERR_NOMEM, what);
-}
-template <typename P>
-static int dev_alloc(mod16_ctx* ctx, P** p, size_t bytes, const char* what) {
-    void** v = reinterpret_cast<void**>(p);
-    return hipMalloc(v, bytes) == hipSuccess ? MOD16_OK : dev_alloc_failed(ctx, v, what);
-}
-template <typename P>
-static int dev_alloc_async(mod16_ctx* ctx, P** p, size_t bytes, hipStream_t st, const char* what) {
-    void** v = reinterpret_cast<void**>(p);
-    return hipMallocAsync(v, bytes, st) == hipSuccess ? MOD16_OK : dev_alloc_failed(ctx, v, what);
+// A workspace for `blocks` partials + the (zeroed) counter behind them
+static int ws_alloc(mod16_ctx* ctx, DiagWs& ws, int64_t blocks) {
+    ws.capacity = 0;
+    int rc = ws.mem.alloc(ctx, sizeof(double) * (blocks * 8 + 16), "device memory for the diagnostics workspace");
+    if (rc != MOD16_OK) return rc;
+    ws.capacity = blocks;
+    HIPCHK(ctx, hipMemset(ws.done(), 0, 128));
+    return MOD16_OK;
 }
 
 // One allocation carved into arrays: pieces of whole 256-byte lines taken in order from `base`.
@@ -196,8 +182,8 @@ static void derive_lut(const double* lut, double* h64) {
 
 // ------------------------------------------------------------------ launch
 template <typename T> static const T* ctx_lut(const mod16_ctx* ctx);
-template <> const double* ctx_lut<double>(const mod16_ctx* ctx) { return ctx->lut64; }
-template <> const float* ctx_lut<float>(const mod16_ctx* ctx) { return ctx->lut32; }
+template <> const double* ctx_lut<double>(const mod16_ctx* ctx) { return ctx->lut64.as<double>(); }
+template <> const float* ctx_lut<float>(const mod16_ctx* ctx) { return ctx->lut32.as<float>(); }
 
 
 template <typename T> struct VecOf;
@@ -290,12 +276,9 @@ static int reserve_diag(mod16_ctx* ctx, int64_t blocks, DiagWs** out = nullptr) 
     // context; sizes at least double, so the retired blocks add up to less than the live one.
     // Launches that follow use the new block and are ordered behind the old one's by the
     // workspace event as before.
-    ctx->retired.push_back(ctx->ws.partial);
-    ctx->ws.partial = nullptr;
     const int64_t want = std::max<int64_t>(blocks, 2 * ctx->ws.capacity);
-    ctx->ws.capacity = 0;
-    HIPCHK(ctx, ws_alloc(ctx->ws, want));
-    return MOD16_OK;
+    ctx->retired.push_back(std::move(ctx->ws.mem));
+    return ws_alloc(ctx, ctx->ws, want);
 }
 
 // The context's workspace is shared by its launches (every pipeline launch
@@ -393,9 +376,9 @@ constexpr int64_t kFuseFinalBelow = 16384;   // partials up to which the pipelin
 template <typename T, int MODE, bool GUARD = true>
 static int launch_stream(mod16_ctx* ctx, StreamArgs<T> s, hipStream_t st, double* ddiag = nullptr) {
     constexpr int V = VecOf<T>::v;
-    s.lut64 = ctx->lut64;
-    s.tab = ctx->tab64;
-    s.status = ctx->status;
+    s.lut64 = ctx->lut64.as<double>();
+    s.tab = ctx->tab64.as<double>();
+    s.status = ctx->status.as<unsigned>();
     if (s.tile_shift <= 0) {       // plain arrays: one "tile"
         s.tile_shift = kNoTile;
         s.wide_row = s.out_row = s.byte_row = 0;
@@ -406,7 +389,7 @@ static int launch_stream(mod16_ctx* ctx, StreamArgs<T> s, hipStream_t st, double
     if (g.npiece > kMaxPieces || (uint64_t)s.wide_row >> 32 || (uint64_t)s.out_row >> 32 || (uint64_t)s.byte_row >> 32)
         return fail(ctx, MOD16_ERR_ARG, "pipeline launch: more than 2^30 pieces, or a tile row of 2^32 elements or more");
     unsigned long long* ctr = ctx->force_counter ? ctx->force_counter
-                                                 : ctx->dyn_counters + 16 * (ctx->dyn_next++ % 64);
+                                                 : ctx->dyn_counters.as<unsigned long long>() + 16 * (ctx->dyn_next++ % 64);
     // the ticket counter of the dynamic schedule (a statically scheduled raster never reads it):
     // zero when it was allocated, and every launch leaves it at zero again (the kernel's last
     // block resets it) -- no memset in front of the kernel, see et_stream_kernel
@@ -434,8 +417,8 @@ static int launch_stream(mod16_ctx* ctx, StreamArgs<T> s, hipStream_t st, double
     if (rc != MOD16_OK) return rc;
     rc = ws_acquire(ctx, st);
     if (rc != MOD16_OK) return rc;
-    s.diag_partial = ws->partial;
-    s.cancel_list = reinterpret_cast<uint16_t*>(ws->partial + (nruns + kStage) * kDiag);
+    s.diag_partial = ws->partial();
+    s.cancel_list = reinterpret_cast<uint16_t*>(ws->partial() + (nruns + kStage) * kDiag);
     // few partials: the kernel's last block adds them up itself (two dispatches less)
     // (only under the static schedule: a dynamically scheduled raster's flagged pieces are
     // revisited by the kernel BEHIND this one, which corrects the partials before they are summed)
@@ -472,18 +455,18 @@ static int launch_stream(mod16_ctx* ctx, StreamArgs<T> s, hipStream_t st, double
     }
 #endif
     if (ddiag && !fused_final) {
-        const double* fin = ws->partial;
+        const double* fin = ws->partial();
         int64_t count = nruns;
         // (a trusted launch has no kernel behind it that looks at every run: the kernel that reads
         // the runs' own partials compares every run's marker)
         bool check = !GUARD && !g.static_sched;
         const unsigned* serial_word = reinterpret_cast<const unsigned*>(ctr) + 3;
         if (count > 4 * kStage) {   // two-level: 1024 fixed slices, then one block
-            double* stage = ws->partial + nruns * kDiag;
+            double* stage = ws->partial() + nruns * kDiag;
             const int64_t per = (count + kStage - 1) / kStage;
             hipLaunchKernelGGL(diag_stage_kernel, dim3(kStage), dim3(kBlock), 0, st, fin, count, per, stage,
                                check ? serial_word : (const unsigned*)nullptr,
-                               check ? ctx->status : (unsigned*)nullptr);
+                               check ? ctx->status.as<unsigned>() : (unsigned*)nullptr);
             fin = stage;
             count = (count + per - 1) / per;
             check = false;
@@ -491,7 +474,7 @@ static int launch_stream(mod16_ctx* ctx, StreamArgs<T> s, hipStream_t st, double
         hipLaunchKernelGGL(diag_final_fused_kernel, dim3(1), dim3(kFinalBlock), 0, st,
                            fin, (int)count, s.n, ddiag,
                            check ? serial_word : (const unsigned*)nullptr,
-                           check ? ctx->status : (unsigned*)nullptr);
+                           check ? ctx->status.as<unsigned>() : (unsigned*)nullptr);
     }
     return ws_release(ctx, st);
 }
@@ -523,9 +506,9 @@ static int launch_et(mod16_ctx* ctx, EtArgs<T> a, unsigned flags, hipStream_t st
     const bool fast = (flags & MOD16_MATH_EXACT) == 0;
     if (a.n <= 0) return MOD16_OK;
     a.lut = ctx_lut<T>(ctx);
-    a.lut64 = ctx->lut64;
-    a.tab = ctx->tab64;
-    a.status = ctx->status;
+    a.lut64 = ctx->lut64.as<double>();
+    a.tab = ctx->tab64.as<double>();
+    a.status = ctx->status.as<unsigned>();
     // 16-byte vector path needs every dense pointer 16-byte aligned
     bool aligned = true;
     auto chk = [&](const void* p, size_t al) {
@@ -683,28 +666,64 @@ static int fill_args(mod16_ctx* ctx, EtArgs<T>& a, const uint8_t* cls, const T* 
 }
 
 static int read_status(mod16_ctx* ctx, hipStream_t st) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->status_host, ctx->status, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemsetAsync(ctx->status, 0, sizeof(unsigned), st));
+    const unsigned* host = ctx->status_host.as<unsigned>();
+    HIPCHK(ctx, hipMemcpyAsync(ctx->status_host.get(), ctx->status.get(), sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemsetAsync(ctx->status.get(), 0, sizeof(unsigned), st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    if (*ctx->status_host & kStatusIncomplete)
+    if (*host & kStatusIncomplete)
         return fail(ctx, MOD16_ERR_HIP, "a launch processed only part of its raster: it found its ticket counter in use "
                                         "(an earlier launch on this context ended abnormally, or more launches were in "
                                         "flight than the context has counters) -- the outputs of that step are not valid");
-    if (*ctx->status_host & kStatusClassRange)
+    if (*host & kStatusClassRange)
         return fail(ctx, MOD16_ERR_CLASS_RANGE, "class raster holds a code >= 13 (numpy would raise IndexError)");
     return MOD16_OK;
 }
 
+// A chain of kernel launches on one stream, captured and instantiated once and kept under a key (what
+// the kernels' arguments hold: the draws of an objective graph, the steps of a sampler graph; a
+// captured forward step has none). Owns the graph and its executable.
+struct CachedGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int64_t key = -1;
+    CachedGraph() = default;
+    CachedGraph(const CachedGraph&) = delete;
+    CachedGraph& operator=(const CachedGraph&) = delete;
+    ~CachedGraph() { drop(); }
+    void drop() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr;
+        graph = nullptr;
+        key = -1;
+    }
+    // what `enqueue()` launches on `st` becomes the graph; the capture is always ended before a failed
+    // launch is reported
+    template <typename F>
+    int capture(mod16_ctx* ctx, hipStream_t st, int64_t k, F enqueue) {
+        drop();
+        HIPCHK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        enqueue();
+        const hipError_t launched = hipGetLastError();
+        const hipError_t ended = hipStreamEndCapture(st, &graph);
+        HIPCHK(ctx, launched);
+        HIPCHK(ctx, ended);
+        HIPCHK(ctx, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        key = k;
+        return MOD16_OK;
+    }
+};
+
 // ---- the forward run + diagnostics of one raster as a HIP graph: the launch
 // sequence of mod16_et_diag_* (counter reset, pipeline kernel, staged fixed-order
 // sum) captured once and replayed with one call per time step.
+// (Members go in reverse order of declaration: the captured graph before the memory its nodes point into.)
 struct mod16_graph {
-    mod16_ctx* ctx = nullptr;                // NULL once the context has been destroyed (graph_registry_mu)
+    mod16_ctx* ctx = nullptr;                // NULL once the context has been destroyed (graph_registry_mu); a view
     int device = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    unsigned long long* counter = nullptr;   // its own ticket counter: replays never meet the ring
+    DevMem counter;                          // its own ticket counter: replays never meet the ring
     DiagWs ws;                               // its own diagnostics workspace (freed with the graph)
+    CachedGraph cg;                          // the captured step
 };
 static void graph_register(mod16_ctx* ctx, mod16_graph* g) {
     std::lock_guard<std::mutex> lock(graph_registry_mu());
@@ -730,16 +749,16 @@ static int reduce_entry(mod16_ctx* ctx, const T* day, const T* night, int64_t n,
     if (rc != MOD16_OK) return rc;
     rc = ws_acquire(ctx, st);
     if (rc != MOD16_OK) return rc;
-    hipLaunchKernelGGL((diag_partial_kernel<T>), dim3(blocks), dim3(kBlock), 0, st, day, night, n, ws->partial);
-    double* dst = ddiag ? ddiag : ctx->diag_dev;
-    hipLaunchKernelGGL(diag_final_kernel, dim3(1), dim3(kBlock), 0, st, ws->partial, blocks, dst);
+    hipLaunchKernelGGL((diag_partial_kernel<T>), dim3(blocks), dim3(kBlock), 0, st, day, night, n, ws->partial());
+    double* dst = ddiag ? ddiag : ctx->diag_dev.as<double>();
+    hipLaunchKernelGGL(diag_final_kernel, dim3(1), dim3(kBlock), 0, st, ws->partial(), blocks, dst);
     HIPCHK(ctx, hipGetLastError());
     rc = ws_release(ctx, st);
     if (rc != MOD16_OK) return rc;
     if (diag) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->diag_host, dst, sizeof(double) * kDiag, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->diag_host.get(), dst, sizeof(double) * kDiag, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
-        memcpy(diag, ctx->diag_host, sizeof(double) * kDiag);
+        memcpy(diag, ctx->diag_host.get(), sizeof(double) * kDiag);
     }
     return MOD16_OK;
 }

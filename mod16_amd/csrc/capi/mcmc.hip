@@ -5,13 +5,15 @@
 
 constexpr int kMcmcSegment = 64;          // steps per captured graph unless the spec says otherwise
 
+// (Members go in reverse order of declaration: the graphs before the memory their nodes point into;
+// they run on the problem's stream, which mod16_mcmc_destroy synchronizes first.)
 struct mod16_mcmc {
-    mod16_batch* b = nullptr;
-    McmcArgs a;                           // the kernels' arguments (device pointers below)
-    void* state = nullptr;                // y, yp, xc, logp ... t: one allocation
-    void* eval = nullptr;                 // the objective's workspace for `chains` draws (EvalWs)
-    EvalWs w;
-    void* trace = nullptr;                // hist, xtr, tr_ll, tr_lp, tr_acc for `cap` steps
+    mod16_batch* b = nullptr;             // a view: the problem outlives its samplers
+    McmcArgs a;                           // the kernels' arguments: views into the allocations below
+    DevMem state;                         // y, yp, xc, logp ... t: one allocation
+    DevMem eval;                          // the objective's workspace for `chains` draws (EvalWs)
+    EvalWs w;                             // views into `eval`
+    DevMem trace;                         // hist, xtr, tr_ll, tr_lp, tr_acc for `cap` steps
     int64_t cap = 0, steps = 0;
     int segment = kMcmcSegment;
     CachedGraph full, rem;                // `segment` steps, and the last run's remainder; key = steps
@@ -29,11 +31,7 @@ extern "C" int mod16_mcmc_destroy(mod16_mcmc* m) {
     MOD16_LOCK(m->b->ctx);
     (void)hipSetDevice(m->b->device);
     (void)hipStreamSynchronize(m->b->st);
-    mcmc_drop_graphs(m);
     if (m->counted) --m->b->samplers;
-    if (m->state) (void)hipFree(m->state);
-    if (m->eval) (void)hipFree(m->eval);
-    if (m->trace) (void)hipFree(m->trace);
     delete m;
     return MOD16_OK;
 }
@@ -57,11 +55,11 @@ static size_t mcmc_trace_layout(const McmcArgs& a, int64_t cap, char* base, Mcmc
 static int mcmc_reserve(mod16_mcmc* m, int64_t need) {
     if (need <= m->cap) return MOD16_OK;
     mod16_ctx* ctx = m->b->ctx;
-    void* nt = nullptr;
-    int rc = dev_alloc(ctx, &nt, mcmc_trace_layout(m->a, need, nullptr, nullptr), "mod16_mcmc_run: device memory for the history and trace of this many steps");
+    DevMem nt;
+    int rc = nt.alloc(ctx, mcmc_trace_layout(m->a, need, nullptr, nullptr), "mod16_mcmc_run: device memory for the history and trace of this many steps");
     if (rc != MOD16_OK) return rc;
     McmcArgs na = m->a;
-    mcmc_trace_layout(m->a, need, static_cast<char*>(nt), &na);
+    mcmc_trace_layout(m->a, need, nt.as<char>(), &na);
     HIPCHK(ctx, hipStreamSynchronize(m->b->st));
     if (m->steps) {
         const size_t nx = (size_t)m->steps * m->a.chains * m->a.d * 8, ns = (size_t)m->steps * m->a.chains;
@@ -72,8 +70,7 @@ static int mcmc_reserve(mod16_mcmc* m, int64_t need) {
         HIPCHK(ctx, hipMemcpy(na.tr_acc, m->a.tr_acc, ns, hipMemcpyDeviceToDevice));
     }
     mcmc_drop_graphs(m);
-    if (m->trace) HIPCHK(ctx, hipFree(m->trace));
-    m->trace = nt;
+    m->trace = std::move(nt);
     m->a = na;
     m->cap = need;
     return MOD16_OK;
@@ -214,18 +211,18 @@ static int mcmc_create(mod16_batch* b, const mod16_mcmc_spec* s, int ngroups, co
             a.acc = c.take<int>((size_t)C * 4);
             return c.used;
         };
-        int r = dev_alloc(ctx, &m->state, state(nullptr), "mod16_mcmc_create: device memory for the chains' state");
+        int r = m->state.alloc(ctx, state(nullptr), "mod16_mcmc_create: device memory for the chains' state");
         if (r != MOD16_OK) return r;
-        state(m->state);
+        state(m->state.get());
         // the objective's workspace for C draws, both parts: the sampler's own (see EvalWs); behind it
         // the groups' TRAIN codes, constant for the sampler's life and read by its graphs
         // (with the constraint: its per-draw and per-wave parts too, so the graphs run the ANNUAL launches)
         const bool annual = (s->constraints & MOD16_CONSTRAINT_ANNUAL_PRECIP) != 0;
         const int G = annual ? b->G : 0;
         const size_t per_draw = eval_layout_draws(C, 8, nullptr, nullptr, G), per_block = eval_layout_blocks(C, b->gx, nullptr, nullptr, annual);
-        r = dev_alloc(ctx, &m->eval, per_draw + per_block + (fold ? align256((size_t)C * 4) : 0), "mod16_mcmc_create: device memory for the objective's workspace");
+        r = m->eval.alloc(ctx, per_draw + per_block + (fold ? align256((size_t)C * 4) : 0), "mod16_mcmc_create: device memory for the objective's workspace");
         if (r != MOD16_OK) return r;
-        char* ev = static_cast<char*>(m->eval);
+        char* ev = m->eval.as<char>();
         eval_layout_draws(C, 8, ev, &m->w, G);
         eval_layout_blocks(C, b->gx, ev + per_draw, &m->w, annual);
         a.penalty = m->w.penalty;
@@ -291,24 +288,13 @@ static int mcmc_run(mod16_mcmc* m, int64_t steps, float* ms) {
     if (full && m->full.key != K) rc = mcmc_capture(m, K, &m->full);
     if (rc == MOD16_OK && rem && m->rem.key != rem) rc = mcmc_capture(m, rem, &m->rem);
     if (rc != MOD16_OK) return rc;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ms) {
-        HIPCHK(ctx, hipEventCreate(&e0));
-        HIPCHK(ctx, hipEventCreate(&e1));
-        HIPCHK(ctx, hipEventRecord(e0, b->st));
-    }
+    EventTimer timer;
+    if (ms) HIPCHK(ctx, timer.start(b->st));
     bool ok = true;
     for (int64_t i = 0; i < full && ok; ++i) ok = hipGraphLaunch(m->full.exec, b->st) == hipSuccess;
     if (rem && ok) ok = hipGraphLaunch(m->rem.exec, b->st) == hipSuccess;
-    if (ms) ok = ok && hipEventRecord(e1, b->st) == hipSuccess;
+    if (ms && ok) ok = timer.stop_ms(b->st, ms) == MOD16_OK;
     ok = hipStreamSynchronize(b->st) == hipSuccess && ok;
-    if (ms) {
-        float t = 0.f;
-        ok = ok && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
-        *ms = t;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
     if (!ok) {
         m->broken = true;
         return fail(ctx, MOD16_ERR_HIP, "mod16_mcmc_run: a graph launch failed");

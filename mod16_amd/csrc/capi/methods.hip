@@ -44,8 +44,8 @@ static int method_entry(mod16_ctx* ctx, int method, const T* const* in, const in
         bool need = false;
         for (int k = 0; k < 11; ++k) if (!a.par[k]) need = true;
         if (need) {
-            HIPCHK(ctx, hipMemcpyAsync(ctx->scalars, hs, sizeof hs, hipMemcpyHostToDevice, st));
-            for (int k = 0; k < 11; ++k) if (!a.par[k]) a.par[k] = static_cast<const T*>(ctx->scalars) + k;
+            HIPCHK(ctx, hipMemcpyAsync(ctx->scalars.get(), hs, sizeof hs, hipMemcpyHostToDevice, st));
+            for (int k = 0; k < 11; ++k) if (!a.par[k]) a.par[k] = ctx->scalars.as<const T>() + k;
         }
         launch(a, st);
         HIPCHK(ctx, hipGetLastError());

@@ -31,9 +31,9 @@ static int raw_entry(mod16_ctx* ctx, const uint8_t* cls, const T* const* raw,
     a.out[2] = out_total8;
     a.n = n;
     a.lut = ctx_lut<T>(ctx);
-    a.lut64 = ctx->lut64;
-    a.tab = ctx->tab64;
-    a.status = ctx->status;
+    a.lut64 = ctx->lut64.as<double>();
+    a.tab = ctx->tab64.as<double>();
+    a.status = ctx->status.as<unsigned>();
     if (n == 0) return MOD16_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool fast = (flags & MOD16_MATH_EXACT) == 0;

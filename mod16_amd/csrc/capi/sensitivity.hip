@@ -68,16 +68,15 @@ int sobol_to(mod16_ctx* ctx, double* out, size_t bytes, int where, void* stream,
         HIPCHK(ctx, hipGetLastError());
         return MOD16_OK;
     }
-    if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
+    HIPCHK(ctx, ctx->streams[0].ensure());
     hipStream_t st = ctx->streams[0];
-    double* dev = nullptr;
-    int rc = dev_alloc(ctx, &dev, bytes, "mod16_sobol: device memory for the output");
+    DevMem dev;
+    int rc = dev.alloc(ctx, bytes, "mod16_sobol: device memory for the output");
     if (rc != MOD16_OK) return rc;
-    launch(dev, st);
+    launch(dev.as<double>(), st);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dev.get(), bytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dev);
     HIPCHK(ctx, e);
     return MOD16_OK;
 }
@@ -175,7 +174,7 @@ extern "C" int mod16_sobol_analyze_f64(mod16_ctx* ctx, const double* y, int d, i
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (where == MOD16_HOST) {
-        if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
+        HIPCHK(ctx, ctx->streams[0].ensure());
         st = ctx->streams[0];
     }
     // one workspace: [Y (HOST only)] stats | sum partials | Gram partials | indices | outputs
@@ -190,10 +189,10 @@ extern "C" int mod16_sobol_analyze_f64(mod16_ctx* ctx, const double* y, int d, i
         a.out = c.take<double>(sizeof(double) * 2 * a.nidx);
         return c.used;
     };
-    char* ws = nullptr;
-    rc = dev_alloc_async(ctx, &ws, layout(nullptr), st, "mod16_sobol_analyze_f64: device memory for the workspace");
+    AsyncMem ws(st);
+    rc = ws.alloc(ctx, layout(nullptr), "mod16_sobol_analyze_f64: device memory for the workspace");
     if (rc != MOD16_OK) return rc;
-    layout(ws);
+    layout(ws.p);
     a.y = ydev ? ydev : y;
 
     hipError_t e = hipSuccess;
@@ -217,7 +216,7 @@ extern "C" int mod16_sobol_analyze_f64(mod16_ctx* ctx, const double* y, int d, i
     const hipMemcpyKind kind = where == MOD16_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (e == hipSuccess) e = hipMemcpyAsync(idx_out, a.out, sizeof(double) * a.nidx, kind, st);
     if (e == hipSuccess) e = hipMemcpyAsync(std_out, a.out + a.nidx, sizeof(double) * a.nidx, kind, st);
-    (void)hipFreeAsync(ws, st);
+    ws.release();
     if (e == hipSuccess && where == MOD16_HOST) e = hipStreamSynchronize(st);
     HIPCHK(ctx, e);
     return MOD16_OK;

@@ -176,7 +176,7 @@ static int graph_tiled_entry(mod16_ctx* ctx, const mod16_layout* lay, const uint
     *out = nullptr;
     if (!lay || !ddiag) return fail(ctx, MOD16_ERR_ARG, "mod16_graph_et_tiled: layout and ddiag are required");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->streams[0]) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[0], hipStreamNonBlocking));
+    HIPCHK(ctx, ctx->streams[0].ensure());
     hipStream_t st = ctx->streams[0];
     mod16_graph* g = new (std::nothrow) mod16_graph;
     if (!g) return MOD16_ERR_NOMEM;
@@ -187,20 +187,22 @@ static int graph_tiled_entry(mod16_ctx* ctx, const mod16_layout* lay, const uint
         // recording call, launch errors from the instantiation -- so no wait for whatever the
         // caller's streams are still doing to the raster is needed; replays are ordered by
         // the stream they are launched on)
-        HIPCHK(ctx, hipMalloc(&g->counter, 128));
-        HIPCHK(ctx, hipMemset(g->counter, 0, 128));       // (not captured: the launches keep it at zero)
-        ctx->force_counter = g->counter;
+        int r = g->counter.alloc(ctx, 128, "mod16_graph_et: device memory for the graph's ticket counter");
+        if (r != MOD16_OK) return r;
+        HIPCHK(ctx, hipMemset(g->counter.get(), 0, 128));       // (not captured: the launches keep it at zero)
+        ctx->force_counter = g->counter.as<unsigned long long>();
         int pv = 0, tsh = lay->tile > 0 ? tile_log2(lay->tile, 1) : -1;
         while ((1 << pv) < 64 * VecOf<T>::v) ++pv;
         if (tsh < pv) return fail(ctx, MOD16_ERR_ARG, "mod16_graph_et_tiled: bad tile");
-        HIPCHK(ctx, ws_alloc(g->ws, std::max<int64_t>(kDiagBlocks, stream_ws_blocks(stream_geom(ctx, std::max<int64_t>(n, 0), VecOf<T>::v, tsh - pv).nruns))));
+        r = ws_alloc(ctx, g->ws, std::max<int64_t>(kDiagBlocks, stream_ws_blocks(stream_geom(ctx, std::max<int64_t>(n, 0), VecOf<T>::v, tsh - pv).nruns)));
+        if (r != MOD16_OK) return r;
         ctx->force_ws = &g->ws;
         HIPCHK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        int r = tiled_entry<T>(ctx, lay, cls, drivers, n, out_day, out_night, flags, ddiag, st);
-        hipError_t e = hipStreamEndCapture(st, &g->graph);
+        r = tiled_entry<T>(ctx, lay, cls, drivers, n, out_day, out_night, flags, ddiag, st);
+        hipError_t e = hipStreamEndCapture(st, &g->cg.graph);
         if (r != MOD16_OK) return r;
         HIPCHK(ctx, e);
-        HIPCHK(ctx, hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
+        HIPCHK(ctx, hipGraphInstantiate(&g->cg.exec, g->cg.graph, nullptr, nullptr, 0));
         return MOD16_OK;
     }();
     ctx->force_counter = nullptr;
@@ -237,41 +239,30 @@ extern "C" int mod16_time_et_tiled(mod16_ctx* ctx, int is_f32, const mod16_layou
     if (!ctx || !ms || launches <= 0) return fail(ctx, MOD16_ERR_ARG, "mod16_time_et_tiled: bad argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t e0, e1;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    HIPCHK(ctx, hipEventCreate(&e1));
+    EventTimer timer;
     int rc = MOD16_OK;
-    HIPCHK(ctx, hipEventRecord(e0, st));
+    HIPCHK(ctx, timer.start(st));
     for (int i = 0; i < launches && rc == MOD16_OK; ++i)
         rc = is_f32 ? tiled_entry<float>(ctx, layout, cls, reinterpret_cast<const float* const*>(drivers), n,
                                          static_cast<float*>(out_day), static_cast<float*>(out_night), flags, ddiag, stream)
                     : tiled_entry<double>(ctx, layout, cls, reinterpret_cast<const double* const*>(drivers), n,
                                           static_cast<double*>(out_day), static_cast<double*>(out_night), flags, ddiag, stream);
-    HIPCHK(ctx, hipEventRecord(e1, st));
-    HIPCHK(ctx, hipEventSynchronize(e1));
     float t = 0.f;
-    HIPCHK(ctx, hipEventElapsedTime(&t, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (timer.stop_ms(st, &t) != MOD16_OK) return fail(ctx, MOD16_ERR_HIP, "mod16_time_et_tiled: timing the launches failed");
     *ms = t / (float)launches;
     return rc;
 }
 
 // mean milliseconds per replay of a captured step, HIP events on `stream`
 extern "C" int mod16_time_graph(mod16_graph* g, int launches, void* stream, float* ms) {
-    if (!g || !g->exec || !ms || launches <= 0 || !graph_alive(g)) return MOD16_ERR_ARG;
+    if (!g || !g->cg.exec || !ms || launches <= 0 || !graph_alive(g)) return MOD16_ERR_ARG;
     if (hipSetDevice(g->device) != hipSuccess) return MOD16_ERR_HIP;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return MOD16_ERR_HIP;
-    bool ok = hipEventRecord(e0, st) == hipSuccess;
-    for (int i = 0; i < launches && ok; ++i) ok = hipGraphLaunch(g->exec, st) == hipSuccess;
-    ok = ok && hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
+    EventTimer timer;
+    bool ok = timer.start(st) == hipSuccess;
+    for (int i = 0; i < launches && ok; ++i) ok = hipGraphLaunch(g->cg.exec, st) == hipSuccess;
     float t = 0.f;
-    ok = ok && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (!ok) return MOD16_ERR_HIP;
+    if (!ok || timer.stop_ms(st, &t) != MOD16_OK) return MOD16_ERR_HIP;
     *ms = t / (float)launches;
     return MOD16_OK;
 }

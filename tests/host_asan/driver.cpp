@@ -16,7 +16,8 @@
 
 extern "C" void mod16_stub_report(FILE* f);
 extern "C" size_t mod16_stub_live_allocations(void);
-extern "C" void mod16_stub_fail_host_malloc(int k);
+extern "C" void mod16_stub_fail_host_malloc(int k);      // k > 0: the next k calls fail; -k: the k-th next call fails, once
+extern "C" void mod16_stub_fail_malloc(int k);           // the k-th next hipMalloc / hipMallocAsync fails, once
 
 static int g_checks = 0;
 #define EXPECT(cond)                                                                       \
@@ -497,6 +498,240 @@ static void calibration_cases(mod16_ctx* ctx) {
     printf("host_asan: calibration family: done\n");
 }
 
+// ---- the annual-precipitation constraint: T x N = 6 x 3 pixels in years of 4 and 2 days (so every
+// site-year is padded to 64 by a different amount), a pixel outside the FAST domain, one scalar driver
+struct AnnualProblem {
+    static constexpr int64_t T = 6, N = 3, n = T * N, maxd = 40;
+    static constexpr int Y = 2;
+    Problem<double> p;
+    int32_t year[T] = {0, 0, 0, 0, 1, 1};
+    std::vector<double> precip, lhv;
+    AnnualProblem() : p(n), precip(Y * N, 500.0), lhv(n, 2.45e6) { p.drv[MOD16_PRESSURE][7] = 0.5; }
+    int bind(mod16_ctx* ctx, bool weights, mod16_batch** b) {
+        return mod16_static_batch_bind_f64(ctx, p.dp, p.ds, n, p.obs.data(), weights ? p.wts.data() : nullptr, maxd, MOD16_MATH_FAST, MOD16_HOST, b);
+    }
+    int set(mod16_batch* b) { return mod16_static_batch_set_annual(b, T, N, year, Y, precip.data(), lhv.data()); }
+};
+
+static void annual_cases(mod16_ctx* ctx) {
+    AnnualProblem a;
+    const int64_t n = a.n, maxd = a.maxd;
+    std::vector<double> par(maxd * 11, 1.0), sse(maxd), cnt(maxd), pen(maxd);
+    for (bool weights : {true, false}) {
+        mod16_batch* b = nullptr;
+        OK(a.bind(ctx, weights, &b));
+        EXPECT(mod16_static_batch_objective_annual(b, par.data(), 9, sse.data(), cnt.data(), pen.data()) == MOD16_ERR_ARG);   // no constraint yet
+        OK(a.set(b));
+        int64_t n_user = -1, outside = -1;
+        OK(mod16_static_batch_info(b, &n_user, nullptr, &outside));
+        EXPECT(n_user == n && outside > 0);
+        size_t live = mod16_stub_live_allocations();
+        EXPECT(a.set(b) == MOD16_ERR_ARG);                          // once per problem
+        EXPECT(mod16_stub_live_allocations() == live);
+        OK(mod16_static_batch_objective_annual(b, par.data(), 40, sse.data(), cnt.data(), pen.data()));
+        OK(mod16_static_batch_objective_annual(b, par.data(), 9, sse.data(), cnt.data(), pen.data()));     // captured again
+        OK(mod16_static_batch_objective_annual(b, par.data(), 40, sse.data(), cnt.data(), pen.data()));
+        OK(mod16_static_batch_objective(b, par.data(), 40, sse.data(), cnt.data()));                       // the plain graph of the same problem
+        std::vector<double> day(9 * n), night(9 * n), total(9 * n);
+        OK(mod16_static_batch_rows(b, par.data(), 9, day.data(), night.data(), total.data()));              // gathered through pos
+        mod16_mcmc_spec spec = sampler_spec(5, 4);
+        spec.constraints = MOD16_CONSTRAINT_ANNUAL_PRECIP;
+        mod16_mcmc* m = nullptr;
+        OK(mod16_mcmc_create(b, &spec, nullptr, &m));
+        OK(mod16_mcmc_run(m, 9, nullptr));              // the trace grows once; two segments and a remainder of 1
+        EXPECT(mod16_mcmc_destroy(m) == MOD16_OK);
+        EXPECT(mod16_static_batch_destroy(b) == MOD16_OK);
+    }
+    {   // refused: after folds, and while a sampler lives -- nothing allocated, nothing freed
+        std::vector<uint8_t> labels(n);
+        for (int64_t i = 0; i < n; ++i) labels[i] = (uint8_t)(i % 3);
+        mod16_batch* b = nullptr;
+        OK(a.bind(ctx, true, &b));
+        OK(mod16_static_batch_set_folds(b, labels.data(), 3));
+        size_t live = mod16_stub_live_allocations();
+        EXPECT(a.set(b) == MOD16_ERR_ARG);
+        EXPECT(mod16_stub_live_allocations() == live);
+        EXPECT(mod16_static_batch_destroy(b) == MOD16_OK);
+        OK(a.bind(ctx, true, &b));
+        mod16_mcmc_spec spec = sampler_spec(5, 4);
+        mod16_mcmc* m = nullptr;
+        OK(mod16_mcmc_create(b, &spec, nullptr, &m));
+        live = mod16_stub_live_allocations();
+        EXPECT(a.set(b) == MOD16_ERR_ARG);
+        EXPECT(mod16_stub_live_allocations() == live);
+        spec.constraints = MOD16_CONSTRAINT_ANNUAL_PRECIP;
+        mod16_mcmc* bad = nullptr;
+        EXPECT(mod16_mcmc_create(b, &spec, nullptr, &bad) == MOD16_ERR_ARG && !bad);     // a problem without the constraint
+        EXPECT(mod16_mcmc_destroy(m) == MOD16_OK);
+        EXPECT(mod16_static_batch_destroy(b) == MOD16_OK);
+    }
+    printf("host_asan: annual: done\n");
+}
+
+// ---- the ensemble forward run: the small path, one pixel above it (staged), DEVICE arrays
+template <typename T>
+static int ensemble_call(mod16_ctx* ctx, const mod16_ensemble* e, const uint8_t* cls, const T* const* d, const int64_t* ds, int64_t n,
+                         T* const* out, unsigned flags, int where) {
+    if constexpr (sizeof(T) == 8) return mod16_et_ensemble_f64(ctx, e, cls, d, ds, n, out, flags, where, nullptr);
+    else return mod16_et_ensemble_f32(ctx, e, cls, d, ds, n, out, flags, where, nullptr);
+}
+template <typename T>
+static void ensemble_cases_of(mod16_ctx* ctx, const mod16_ensemble* e) {
+    for (int64_t n : {(int64_t)1, (int64_t)257, (int64_t)65537}) {
+        std::vector<std::vector<T>> drv(14, std::vector<T>(n, T(280))), outs(5, std::vector<T>(n));
+        std::vector<uint8_t> cls(n, 1);
+        const T* dp[14];
+        int64_t ds[14];
+        T one = T(300);
+        for (int k = 0; k < 14; ++k) { dp[k] = k == 5 ? &one : drv[k].data(); ds[k] = k == 5 ? 0 : 1; }
+        T* op[5];
+        for (int k = 0; k < 5; ++k) op[k] = outs[k].data();
+        OK(ensemble_call<T>(ctx, e, cls.data(), dp, ds, n, op, MOD16_MATH_FAST, MOD16_HOST));
+        OK(ensemble_call<T>(ctx, e, cls.data(), dp, ds, n, op, MOD16_MATH_EXACT, MOD16_HOST));
+        op[4] = nullptr;
+        EXPECT(ensemble_call<T>(ctx, e, cls.data(), dp, ds, n, op, MOD16_MATH_FAST, MOD16_HOST) == MOD16_ERR_ARG);
+    }
+    const int64_t n = 257;
+    const size_t per = ((size_t)n * sizeof(T) + 255) / 256 * 256;
+    char* slab = static_cast<char*>(dmalloc(20 * per));
+    const T* dp[14];
+    int64_t ds[14];
+    for (int k = 0; k < 14; ++k) { dp[k] = reinterpret_cast<const T*>(slab + k * per); ds[k] = k == 5 ? 0 : 1; }
+    T* op[5];
+    for (int k = 0; k < 5; ++k) op[k] = reinterpret_cast<T*>(slab + (14 + k) * per);
+    const uint8_t* cls = reinterpret_cast<const uint8_t*>(slab + 19 * per);
+    OK(ensemble_call<T>(ctx, e, cls, dp, ds, n, op, MOD16_MATH_FAST, MOD16_DEVICE));
+    OK(ensemble_call<T>(ctx, e, cls, dp, ds, n, op, MOD16_MATH_EXACT, MOD16_DEVICE));
+    (void)hipFree(slab);
+}
+static void ensemble_cases(mod16_ctx* ctx) {
+    std::vector<double> tables(3 * 13 * 11);
+    for (size_t i = 0; i < tables.size(); ++i) tables[i] = 1.0 + (double)i;
+    mod16_ensemble* bad = nullptr;
+    EXPECT(mod16_ensemble_create(ctx, tables.data(), 0, &bad) == MOD16_ERR_ARG && !bad);
+    for (int64_t members : {(int64_t)1, (int64_t)3}) {
+        mod16_ensemble* e = nullptr;
+        OK(mod16_ensemble_create(ctx, tables.data(), members, &e));
+        ensemble_cases_of<double>(ctx, e);
+        ensemble_cases_of<float>(ctx, e);
+        EXPECT(mod16_ensemble_destroy(e) == MOD16_OK);
+    }
+    printf("host_asan: ensemble: done\n");
+}
+
+// ---- allocation failures. One call of the library under them: allocation k = 1, 2, ... of the call
+// fails (device memory, or with `pinned` page-locked memory) until the call succeeds. Every failing
+// round returns MOD16_ERR_NOMEM or MOD16_ERR_HIP, leaves as many allocations alive as there were, and
+// leaves its object usable: the same call without a failure succeeds, and finish() -- an evaluation
+// under the shadows, then the object's destruction -- runs clean. prepare() makes what the call needs,
+// fresh for every round. HOST_ASAN_SWEEP_REPORT=1 prints a changed count and goes on (a survey of
+// another build of the library) where the test stops.
+template <typename Prepare, typename Call, typename Finish>
+static void sweep(const char* what, bool pinned, Prepare prepare, Call call, Finish finish) {
+    static const bool report = getenv("HOST_ASAN_SWEEP_REPORT") != nullptr;
+    for (int k = 1; k <= 64; ++k) {
+        prepare();
+        const size_t live = mod16_stub_live_allocations();
+        if (pinned) mod16_stub_fail_host_malloc(-k); else mod16_stub_fail_malloc(k);
+        const int rc = call();
+        mod16_stub_fail_host_malloc(0);
+        mod16_stub_fail_malloc(0);
+        ++g_checks;
+        if (rc != MOD16_OK) {
+            if (rc != MOD16_ERR_NOMEM && rc != MOD16_ERR_HIP) { fprintf(stderr, "host_asan: %s, %s allocation %d fails: status %d\n", what, pinned ? "pinned" : "device", k, rc); exit(1); }
+            if (mod16_stub_live_allocations() != live) {
+                fprintf(stderr, "host_asan: %s, %s allocation %d fails: %zu live allocations became %zu\n", what, pinned ? "pinned" : "device", k, live, mod16_stub_live_allocations());
+                if (!report) exit(1);
+            }
+            const int again = call();
+            if (again != MOD16_OK) { fprintf(stderr, "host_asan: %s: the call after a failed %s allocation %d -> %d\n", what, pinned ? "pinned" : "device", k, again); exit(1); }
+        }
+        finish();
+        if (rc == MOD16_OK) {
+            printf("host_asan: %s: %d failing %s allocations\n", what, k - 1, pinned ? "pinned" : "device");
+            return;
+        }
+    }
+    fprintf(stderr, "host_asan: %s: still failing after 64 rounds\n", what);
+    exit(1);
+}
+
+static void failure_cases(mod16_ctx* ctx, const double* lut) {
+    const int64_t n = 300, maxd = 16;
+    Problem<double> p(n);
+    std::vector<double> par(maxd * 11, 1.0), sse(maxd), cnt(maxd), pen(maxd), rows(3 * 7 * n);
+    std::vector<uint8_t> labels(n);
+    std::vector<int32_t> code(maxd);
+    for (int64_t i = 0; i < n; ++i) labels[i] = (uint8_t)(i % 3);
+    for (int64_t d = 0; d < maxd; ++d) code[d] = (int32_t)(d % 3);
+    mod16_batch* b = nullptr;
+    mod16_mcmc* m = nullptr;
+    auto none = [] {};
+    auto bind = [&] { b = nullptr; OK(mod16_static_batch_bind_f64(ctx, p.dp, p.ds, n, p.obs.data(), p.wts.data(), maxd, MOD16_MATH_FAST, MOD16_HOST, &b)); };
+    auto evaluate = [&] { OK(mod16_static_batch_objective(b, par.data(), 7, sse.data(), cnt.data())); };
+    auto unbind = [&] { EXPECT(mod16_static_batch_destroy(b) == MOD16_OK); };
+    for (bool pinned : {false, true}) {
+        mod16_ctx* c2 = nullptr;
+        sweep("mod16_create", pinned, none, [&] { c2 = nullptr; return mod16_create(0, &c2); },
+              [&] { mod16_ctx* ctx = c2; OK(mod16_set_bplut_f64(ctx, lut)); EXPECT(mod16_destroy(c2) == MOD16_OK); });
+        sweep("mod16_static_batch_bind_f64", pinned, none,
+              [&] { b = nullptr; return mod16_static_batch_bind_f64(ctx, p.dp, p.ds, n, p.obs.data(), p.wts.data(), maxd, MOD16_MATH_FAST, MOD16_HOST, &b); },
+              [&] { evaluate(); unbind(); });
+        sweep("mod16_static_batch_set_folds", pinned, bind, [&] { return mod16_static_batch_set_folds(b, labels.data(), 3); },
+              [&] { OK(mod16_static_batch_objective_folds(b, par.data(), 7, code.data(), sse.data(), cnt.data())); evaluate(); unbind(); });
+        AnnualProblem a;
+        sweep("mod16_static_batch_set_annual", pinned, [&] { b = nullptr; OK(a.bind(ctx, true, &b)); }, [&] { return a.set(b); },
+              [&] { OK(mod16_static_batch_objective_annual(b, par.data(), 7, sse.data(), cnt.data(), pen.data())); evaluate(); unbind(); });
+    }
+    mod16_mcmc_spec spec = sampler_spec(5, 4);
+    sweep("mod16_mcmc_create", false, bind, [&] { m = nullptr; return mod16_mcmc_create(b, &spec, nullptr, &m); },
+          [&] { OK(mod16_mcmc_run(m, 3, nullptr)); EXPECT(mod16_mcmc_destroy(m) == MOD16_OK); evaluate(); unbind(); });
+    sweep("mod16_mcmc_run (the trace grows)", false,
+          [&] { bind(); m = nullptr; OK(mod16_mcmc_create(b, &spec, nullptr, &m)); OK(mod16_mcmc_run(m, 5, nullptr)); },
+          [&] { return mod16_mcmc_run(m, 4, nullptr); },
+          [&] { int64_t steps = -1; std::vector<double> x(2 * 5 * 2);
+                OK(mod16_mcmc_read(m, 6, 2, x.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &steps));
+                EXPECT(steps == 9);                      // (a failing round took no step)
+                EXPECT(mod16_mcmc_destroy(m) == MOD16_OK); evaluate(); unbind(); });
+    sweep("mod16_static_batch_objective (first call)", false, bind, [&] { return mod16_static_batch_objective(b, par.data(), 7, sse.data(), cnt.data()); },
+          [&] { evaluate(); unbind(); });
+    sweep("mod16_static_batch_rows (first call)", false, bind,
+          [&] { return mod16_static_batch_rows(b, par.data(), 7, rows.data(), rows.data() + 7 * n, rows.data() + 14 * n); }, [&] { evaluate(); unbind(); });
+    {   // on the caller's device arrays: the captured step, and the unbound call's stream-ordered temporaries
+        const size_t per = ((size_t)n * 8 + 255) / 256 * 256;
+        char* slab = static_cast<char*>(dmalloc(19 * per + 7 * 11 * 8 + 2 * 7 * 8 + 64));
+        const double* dp[14];
+        int64_t ds[14];
+        for (int k = 0; k < 14; ++k) { dp[k] = reinterpret_cast<const double*>(slab + k * per); ds[k] = 1; }
+        double* day = reinterpret_cast<double*>(slab + 14 * per);
+        double* night = reinterpret_cast<double*>(slab + 15 * per);
+        const double* dobs = reinterpret_cast<const double*>(slab + 16 * per);
+        const uint8_t* cls = reinterpret_cast<const uint8_t*>(slab + 17 * per);
+        double* dtotal = reinterpret_cast<double*>(slab + 18 * per);       // (one draw's row)
+        double* dpar = reinterpret_cast<double*>(slab + 19 * per);
+        double* dsse = dpar + 7 * 11;
+        double* ddiag = dsse + 2 * 7;
+        mod16_graph* g = nullptr;
+        sweep("mod16_graph_et_diag_f64", false, none,
+              [&] { g = nullptr; return mod16_graph_et_diag_f64(ctx, cls, dp, ds, n, day, night, MOD16_MATH_FAST, ddiag, &g); },
+              [&] { EXPECT(mod16_graph_launch(g, nullptr) == MOD16_OK); EXPECT(mod16_graph_destroy(g) == MOD16_OK); });
+        sweep("mod16_et_static_batch_f64 (DEVICE)", false, none,
+              [&] { return mod16_et_static_batch_f64(ctx, dp, ds, n, dpar, 1, nullptr, nullptr, dtotal, dobs, nullptr, dsse, dsse + 7, MOD16_MATH_FAST, MOD16_DEVICE, nullptr); },
+              none);
+        (void)hipFree(slab);
+    }
+    {
+        std::vector<double> tables(3 * 13 * 11, 1.0), out(5 * 5);
+        std::vector<uint8_t> cls(5, 1);
+        double* op[5];
+        for (int k = 0; k < 5; ++k) op[k] = out.data() + 5 * k;
+        mod16_ensemble* e = nullptr;
+        sweep("mod16_ensemble_create", false, none, [&] { e = nullptr; return mod16_ensemble_create(ctx, tables.data(), 3, &e); },
+              [&] { OK(mod16_et_ensemble_f64(ctx, e, cls.data(), p.dp, p.ds, 5, op, MOD16_MATH_FAST, MOD16_HOST, nullptr)); EXPECT(mod16_ensemble_destroy(e) == MOD16_OK); });
+    }
+    printf("host_asan: allocation failures: done\n");
+}
+
 // the Sobol entry points in HOST mode: their workspaces and their release (launch shapes only)
 static void sobol_cases(mod16_ctx* ctx) {
     const int d = 3;
@@ -601,7 +836,10 @@ int main(int argc, char** argv) {
                                      cnt.data(), MOD16_MATH_EXACT, MOD16_HOST, nullptr));
     }
     calibration_cases(ctx);
+    annual_cases(ctx);
+    ensemble_cases(ctx);
     sobol_cases(ctx);
+    failure_cases(ctx, lut);
     EXPECT(mod16_destroy(ctx) == MOD16_OK);
     {   // no page-locked memory for the small calls' buffer: the call is staged instead (and the
         // context stops asking), every entry point that has the small path

@@ -16,7 +16,7 @@
 //
 // Compiled as HIP (host only) so that it sees the kernels' own argument structures
 // (StreamArgs, EtArgs, SynthArgs, MethodArgs, RawArgs, StaticArgs, StaticBatchArgs, StaticObjArgs,
-// McmcArgs: mod16_amd/csrc/*.hpp) instead of copies of them.
+// StaticAnnualRedoArgs, McmcArgs, EnsArgs: mod16_amd/csrc/*.hpp) instead of copies of them.
 //
 // Fresh "device" memory is filled with 0xA5. No kernel runs, so that is what the library reads
 // back: as a double 0xA5A5A5A5A5A5A5A5 is finite (about -2e-127), which mod16_mcmc_create's check
@@ -44,6 +44,7 @@
 #include "../../mod16_amd/csrc/mod16_stream.hpp"
 #include "../../mod16_amd/csrc/mod16_methods.hpp"
 #include "../../mod16_amd/csrc/mod16_mcmc.hpp"
+#include "../../mod16_amd/csrc/mod16_ensemble.hpp"
 
 using namespace mod16;
 
@@ -328,6 +329,93 @@ static void shadow_obj(const StaticObjArgs<T>& a, bool fold, dim3 grid, dim3 blo
         need(a.code, sizeof(int32_t) * nd, 4, "fold codes", name);
         need(a.label, (size_t)a.n, 1, "fold labels", name);
     }
+    // the ANNUAL instances: the scale of every pixel, one mass per wave of 64 pixels and draw
+    if (a.scale) need(a.scale, sizeof(double) * (size_t)a.n, 8, "scale", name);
+    if (a.mass) need(a.mass, sizeof(double) * nd * grid.x * (kBlock / 64), 8, "mass", name);
+}
+
+// where the memory of [p, p + count) is real: its largest entry, every entry checked to be >= 0 (-1: not readable)
+static int64_t top_index(const int64_t* p, int64_t count, const char* what, const char* name) {
+    bool fake = true;
+    if (!inside(p, sizeof(int64_t) * (size_t)count, &fake) || fake) return -1;
+    int64_t top = 0;
+    for (int64_t u = 0; u < count; ++u) {
+        if (p[u] < 0) die("%s: %s[%lld] = %lld", name, what, (long long)u, (long long)p[u]);
+        top = std::max(top, p[u]);
+    }
+    return top;
+}
+
+// static_annual_redo_kernel<T>: a block per draw, a thread per site-year over its part of the list
+template <typename T>
+static void shadow_annual_redo(const StaticAnnualRedoArgs<T>& a, dim3 grid, dim3 block, const char* name) {
+    need_block(block, name);
+    if (a.G < 1) die("%s: G = %d", name, a.G);
+    const size_t nd = grid.x;
+    need(a.params, sizeof(T) * 11 * nd, sizeof(T), "params", name);
+    need(a.lstart, sizeof(int64_t) * ((size_t)a.G + 1), 8, "lstart", name);
+    need(a.rmass, sizeof(double) * 2 * nd * (size_t)a.G, 8, "rmass", name);
+    // (the tables are small and real: the site-years' parts of the list are ascending and end where the list ends)
+    for (int g = 0; g < a.G; ++g)
+        if (a.lstart[g] < 0 || a.lstart[g] > a.lstart[g + 1]) die("%s: lstart[%d] = %lld, [%d] = %lld", name, g, (long long)a.lstart[g], g + 1, (long long)a.lstart[g + 1]);
+    const int64_t nlist = a.lstart[a.G];
+    if (nlist <= 0) die("%s: %lld listed pixels", name, (long long)nlist);
+    need(a.list, sizeof(int64_t) * (size_t)nlist, 8, "pixel list", name);
+    const int64_t n = std::max<int64_t>(0, top_index(a.list, nlist, "list", name)) + 1;
+    need(a.scale, sizeof(double) * (size_t)n, 8, "scale", name);
+    for (int k = 0; k < 14; ++k) need_arr(a.drv[k], (a.dense_drv >> k) & 1u, n, "driver", name);
+}
+
+// static_annual_final_kernel(mass, rmass, any_draw, wstart, limit, G, S, ndraw, penalty)
+static void shadow_annual_final(void** args, dim3 grid, dim3 block, const char* name) {
+    const double* mass = *static_cast<const double* const*>(args[0]);
+    const double* rmass = *static_cast<const double* const*>(args[1]);
+    const unsigned* any_draw = *static_cast<const unsigned* const*>(args[2]);
+    const int32_t* wstart = *static_cast<const int32_t* const*>(args[3]);
+    const double* limit = *static_cast<const double* const*>(args[4]);
+    const int G = *static_cast<const int*>(args[5]);
+    const int64_t ndraw = *static_cast<const int64_t*>(args[7]);
+    double* penalty = *static_cast<double* const*>(args[8]);
+    need_block(block, name);
+    need_cover(grid.x, kObjPerBlock, ndraw, "draws", name);
+    if (G < 1) die("%s: G = %d", name, G);
+    const size_t nd = (size_t)ndraw;
+    need(wstart, sizeof(int32_t) * ((size_t)G + 1), 4, "wstart", name);
+    for (int g = 0; g < G; ++g)
+        if (wstart[g] < 0 || wstart[g] >= wstart[g + 1]) die("%s: wstart[%d] = %d, [%d] = %d", name, g, wstart[g], g + 1, wstart[g + 1]);
+    need(mass, sizeof(double) * nd * (size_t)wstart[G], 8, "mass", name);
+    if (rmass) need(rmass, sizeof(double) * 2 * nd * (size_t)G, 8, "rmass", name);
+    need(any_draw, sizeof(unsigned) * nd, 4, "any_draw", name);
+    need(limit, sizeof(double) * (size_t)G, 8, "limit", name);
+    need(penalty, sizeof(double) * nd, 8, "penalty", name);
+}
+
+// static_rows_gather_kernel<T>(in [ndraw][n_in], pos [n], n_in, n, ndraw, out [ndraw][n])
+static void shadow_rows_gather(void** args, size_t el, dim3 block, const char* name) {
+    const void* in = *static_cast<const void* const*>(args[0]);
+    const int64_t* pos = *static_cast<const int64_t* const*>(args[1]);
+    const int64_t n_in = *static_cast<const int64_t*>(args[2]), n = *static_cast<const int64_t*>(args[3]);
+    const int64_t ndraw = *static_cast<const int64_t*>(args[4]);
+    need_block(block, name);
+    if (n_in <= 0 || n <= 0 || ndraw <= 0) die("%s: n_in %lld, n %lld, ndraw %lld", name, (long long)n_in, (long long)n, (long long)ndraw);
+    need(pos, sizeof(int64_t) * (size_t)n, 8, "pos", name);
+    if (top_index(pos, n, "pos", name) >= n_in) die("%s: pos points past the %lld resident pixels", name, (long long)n_in);
+    need(in, el * (size_t)ndraw * (size_t)n_in, el, "resident rows", name);
+    need(*static_cast<void* const*>(args[5]), el * (size_t)ndraw * (size_t)n, el, "gathered rows", name);
+}
+
+// ens_kernel<T, FAST> / ens_redo_kernel<T>: drivers, the class raster, the members' tables, the five outputs
+template <typename T>
+static void shadow_ens(const EnsArgs<T>& a, bool fast, dim3 block, const char* name) {
+    need_block(block, name);
+    if (a.n <= 0) die("%s: n = %lld", name, (long long)a.n);
+    if (a.members < 1 || a.members > kEnsMaxMembers) die("%s: %d members", name, a.members);
+    for (int k = 0; k < 14; ++k) need_arr(a.drv[k], (a.dense_drv >> k) & 1u, a.n, "driver", name);
+    need(a.cls, (size_t)a.n, 1, "class raster", name);
+    need(a.tables, sizeof(double) * kEnsTable * (size_t)a.members, 8, "members' tables", name);
+    if (fast) need(a.tab, sizeof(double) * FastMath<double>::kTabDoubles, 16, "exp / log tables", name);
+    for (int k = 0; k < kEnsOut; ++k) need_arr(a.out[k], true, a.n, "output", name);
+    need(a.status, 4, 4, "status word", name);
 }
 
 // static_obj_redo_kernel<T, FOLD>: a block per draw over the listed pixels
@@ -507,6 +595,19 @@ static void run_shadow(const std::string& name, dim3 grid, dim3 block, void** ar
             need(*static_cast<double* const*>(args[5]), sizeof(double) * nd, 8, "sse", n);
             need(*static_cast<double* const*>(args[6]), sizeof(double) * nd, 8, "count", n);
         }
+    } else if (has(name, "25static_annual_redo_kernelI")) {
+        shadow_annual_redo(*static_cast<const StaticAnnualRedoArgs<double>*>(args[0]), grid, block, n);     // (float64 only)
+    } else if (has(name, "26static_annual_final_kernel")) {
+        shadow_annual_final(args, grid, block, n);
+    } else if (has(name, "25static_rows_gather_kernelI")) {
+        shadow_rows_gather(args, name[after(name, "25static_rows_gather_kernelI")] == 'd' ? 8 : 4, block, n);
+    } else if (has(name, "10ens_kernelI") || has(name, "15ens_redo_kernelI")) {
+        // ...ens_kernelI{d|f}Lb<FAST>EE... / ...ens_redo_kernelI{d|f}E...
+        const bool redo = has(name, "15ens_redo_kernelI");
+        const size_t at = after(name, redo ? "15ens_redo_kernelI" : "10ens_kernelI");
+        const bool fast = !redo && name[at + 3] == '1';
+        if (name[at] == 'd') shadow_ens(*static_cast<const EnsArgs<double>*>(args[0]), fast, block, n);
+        else shadow_ens(*static_cast<const EnsArgs<float>*>(args[0]), fast, block, n);
     } else if (has(name, "20static_domain_kernelI")) {
         uint8_t* skip = *static_cast<uint8_t* const*>(args[1]);
         if (!skip) die("%s: no domain mask", n);
@@ -627,16 +728,23 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_t* p, int) {
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char* hipGetErrorString(hipError_t) { return "stub"; }
 
-hipError_t hipMalloc(void** p, size_t bytes) { *p = stub::alloc(bytes); return *p ? hipSuccess : hipErrorOutOfMemory; }
+static int g_fail_malloc = 0;           // mod16_stub_fail_malloc(k): the k-th next hipMalloc / hipMallocAsync fails, once (0: none)
+extern "C" void mod16_stub_fail_malloc(int k) { g_fail_malloc = k; }
+hipError_t hipMalloc(void** p, size_t bytes) {
+    if (g_fail_malloc > 0 && --g_fail_malloc == 0) { *p = nullptr; return hipErrorOutOfMemory; }
+    *p = stub::alloc(bytes);
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
 hipError_t hipFree(void* p) { return stub::release(p); }
 hipError_t hipMallocAsync(void** p, size_t bytes, hipStream_t) { return hipMalloc(p, bytes); }
 hipError_t hipFreeAsync(void* p, hipStream_t) { return stub::release(p); }
 // page-locked host memory is in the device's address space too (the HOST mode's small calls hand it
 // to their kernels): a tracked block like any other, always real memory
-static int g_fail_host_malloc = 0;      // mod16_stub_fail_host_malloc(k): the next k hipHostMalloc calls fail
+static int g_fail_host_malloc = 0;      // mod16_stub_fail_host_malloc(k): the next k hipHostMalloc calls fail; (-k): the k-th next one, once
 extern "C" void mod16_stub_fail_host_malloc(int k) { g_fail_host_malloc = k; }
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
     if (g_fail_host_malloc > 0) { --g_fail_host_malloc; *p = nullptr; return hipErrorOutOfMemory; }
+    if (g_fail_host_malloc < 0 && ++g_fail_host_malloc == 0) { *p = nullptr; return hipErrorOutOfMemory; }
     if (bytes >= stub::kRealBelow) stub::die("hipHostMalloc of %zu bytes: the library pins small buffers only", bytes);
     *p = stub::alloc(bytes);
     return *p ? hipSuccess : hipErrorOutOfMemory;

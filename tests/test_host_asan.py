@@ -5,9 +5,12 @@ launches = shadows that replay the launch's address arithmetic against the alloc
 driven through the C ABI over ragged sizes, every form and layout, bad layouts, the global grid,
 2^31 + 12344 pixels, graphs, the HOST-mode tiler, and the calibration family: resident problems
 (float64 / float32, FAST / EXACT, HOST / DEVICE) whose workspaces grow under cached graphs, folds,
-DE-MCMC-Z samplers with their own workspace and a growing trace, the Sobol entry points. Clean = no
-sanitizer report, no address outside an allocation, nothing leaked; and a planted fault (a raster one
-tile short) is reported. Sanitizers run on the CPU build only (the GPU pool refuses them)."""
+DE-MCMC-Z samplers with their own workspace and a growing trace, the annual-precipitation constraint
+(the site-year-major layout, its objective, rows gathered back, its sampler), the ensemble run, the
+Sobol entry points; and every call that builds a handle or grows a workspace once per allocation it
+makes, with that allocation failing: the call reports it, frees what it had made and leaves its
+object usable. Clean = no sanitizer report, no address outside an allocation, nothing leaked; and a
+planted fault (a raster one tile short) is reported. Sanitizers run on the CPU build only (the GPU pool refuses them)."""
 import os
 import subprocess
 
@@ -41,6 +44,15 @@ def test_host_half_of_the_library_is_clean_under_asan_and_ubsan(tmp_path):
         assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
         assert not any(kernel in l for l in lines if 'launch shape only' in l), kernel
     assert 'calibration family: done' in out and 'Sobol entry points: done' in out
+    # the constraint's kernels, the gather of its rows and the ensemble's kernels likewise
+    for kernel in ('25static_annual_redo_kernel', '26static_annual_final_kernel', '25static_rows_gather_kernel',
+                   '10ens_kernel', '15ens_redo_kernel'):
+        assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
+        assert not any(kernel in l for l in lines if 'launch shape only' in l), kernel
+    assert 'annual: done' in out and 'ensemble: done' in out and 'allocation failures: done' in out
+    # nothing the library allocated outlives its handles
+    report = [l for l in lines if l.startswith('hip_stub:') and 'live allocations' in l]
+    assert report and report[-1].rstrip().endswith('live allocations 0'), report
     for what in ('tiled rasters, float64', 'tiled rasters, float32', 'plain device arrays, float64',
                  'HOST mode, float64', 'HOST mode, float32'):
         assert what in out, what

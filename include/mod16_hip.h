@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 10
+#define MOD16_ABI_VERSION 11
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -961,6 +961,68 @@ MOD16_API int mod16_et_ensemble_f64(mod16_ctx* ctx, const mod16_ensemble* ensemb
 MOD16_API int mod16_et_ensemble_f32(mod16_ctx* ctx, const mod16_ensemble* ensemble, const uint8_t* cls,
                                     const float* const* drivers, const int64_t* dstride, int64_t n,
                                     float* const* out, unsigned flags, int where, void* stream);
+
+/*
+ * Per-member outputs and per-pixel quantiles of the ensemble run (ABI 11;
+ * mod16_amd.evapotranspiration_ensemble_quantiles, EnsembleRun.quantiles / .run_members). The
+ * definition of the quantiles is the numpy statement mod16_amd.calibration.ensemble_quantile (numpy's
+ * default 'linear' method): with h = q (members - 1) in float64, lo = floor(h), frac = h - lo and s the
+ * members in ascending order, a = s[lo], b = s[min(lo + 1, members - 1)], the value is a where
+ * frac == 0 or a == b, else a + frac (b - a) (multiply, then add; no contraction).
+ *
+ *   function                          what it does
+ *   mod16_et_ensemble_members_f64     every member's day and night total: day[m * pitch + i],
+ *   mod16_et_ensemble_members_f32     night[m * pitch + i] for member m and pixel i, pitch >= n
+ *                                     ("mod16_et_ensemble_members: pitch must be at least n").
+ *                                     MOD16_DEVICE only: device pointers, asynchronous on `stream`.
+ *                                     Row m holds the bits mean_day / mean_night of the one-member
+ *                                     ensemble of table m have.
+ *   mod16_et_ensemble_quantiles_f64   nq quantiles q[0..nq) (HOST doubles) of three series per pixel:
+ *   mod16_et_ensemble_quantiles_f32   the day total, the night total, and day + night (summed per
+ *                                     member in float64 before ordering). out[3 * nq], series-major,
+ *                                     all required, each [n]: out[k] day at q[k], out[nq + k] night,
+ *                                     out[2 nq + k] total.
+ *
+ *   slab        The member values of P pixels at a time pass through a stream-ordered temporary of
+ *               members x P x 2 doubles (never members x n): P = slab_bytes / (16 members) rounded down
+ *               to a multiple of 256, at least 256, at most n rounded up to one. slab_bytes = 0: 128 MiB;
+ *               a slab below one 256-pixel batch is raised to one; slab_bytes < 0 is MOD16_ERR_ARG
+ *               ("mod16_et_ensemble_quantiles: slab_bytes must not be negative"). The result does not
+ *               depend on it. MOD16_HOST: one slab per staging slot, on that slot's stream.
+ *   selection   one pixel per lane, the pixel's members ordered in LDS by a bitonic network (exact
+ *               order statistics, no atomics, two calls give the same bits); LDS is static, one
+ *               instance per capacity of 16, 32, 64, 128, 256 members (8 ... 128 KiB).
+ *   float32     member values, their sum, the ordering and the interpolation in float64, one rounding
+ *               on store.
+ *   NaN         a NaN member makes all nq values of that pixel and series NaN. Infinite members follow
+ *               the rule above: equal infinities stay, a position that falls on a finite member gives
+ *               that member, an interpolation between -inf and a finite value or +inf is NaN.
+ *   flags, class, where (quantiles)   as mod16_et_ensemble_*.
+ *   refused (MOD16_ERR_ARG)
+ *               "mod16_et_ensemble_quantiles: nq must be between 1 and 8"
+ *               "mod16_et_ensemble_quantiles: every q must lie in [0, 1] and not be NaN"
+ *               "mod16_et_ensemble_quantiles: more than 256 members" (mod16_ensemble_create itself
+ *               takes up to 65536; the other calls serve them)
+ *               "MOD16_MATH_MIXED is not available for the ensemble run" and
+ *               "MOD16_DOMAIN_TRUSTED is not available for the ensemble run" (both calls)
+ *               "the ensemble was created on another device than this context's" (both calls)
+ */
+MOD16_API int mod16_et_ensemble_members_f64(mod16_ctx* ctx, const mod16_ensemble* ensemble, const uint8_t* cls,
+                                            const double* const* drivers, const int64_t* dstride, int64_t n,
+                                            double* day, double* night, int64_t pitch, unsigned flags,
+                                            void* stream);
+MOD16_API int mod16_et_ensemble_members_f32(mod16_ctx* ctx, const mod16_ensemble* ensemble, const uint8_t* cls,
+                                            const float* const* drivers, const int64_t* dstride, int64_t n,
+                                            float* day, float* night, int64_t pitch, unsigned flags,
+                                            void* stream);
+MOD16_API int mod16_et_ensemble_quantiles_f64(mod16_ctx* ctx, const mod16_ensemble* ensemble, const uint8_t* cls,
+                                              const double* const* drivers, const int64_t* dstride, int64_t n,
+                                              const double* q, int nq, double* const* out, int64_t slab_bytes,
+                                              unsigned flags, int where, void* stream);
+MOD16_API int mod16_et_ensemble_quantiles_f32(mod16_ctx* ctx, const mod16_ensemble* ensemble, const uint8_t* cls,
+                                              const float* const* drivers, const int64_t* dstride, int64_t n,
+                                              const double* q, int nq, float* const* out, int64_t slab_bytes,
+                                              unsigned flags, int where, void* stream);
 
 #ifdef __cplusplus
 }

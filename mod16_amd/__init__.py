@@ -1404,6 +1404,86 @@ def evapotranspiration_ensemble(
     return EnsembleET(*outs)
 
 
+EnsembleQuantiles = _collections.namedtuple('EnsembleQuantiles', 'q day night total')
+
+
+def evapotranspiration_ensemble_quantiles(
+        tables, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, q=(0.05, 0.5, 0.95), beta=None, math=_lib.MATH_FAST, device=0,
+        out=None, slab_bytes=None):
+    r'''
+    (Extension.) Per-pixel quantiles of ET over an ENSEMBLE of parameter tables: what a loop over
+    ``evapotranspiration_raster(tables[m], cls, *drivers)`` followed by ``np.quantile(..., q, axis=0)``
+    returns -- the median and a credible interval of a calibration posterior per pixel -- without the
+    (D, n) arrays: the member values of a batch of pixels pass through a slab on the device and are
+    ordered there (``mod16_et_ensemble_quantiles_*``). The definition is
+    ``mod16_amd.calibration.ensemble_quantile`` (numpy's default ``'linear'`` method).
+
+    Parameters
+    ----------
+    tables, cls, the 14 drivers, beta, math, device
+        as for ``evapotranspiration_ensemble``; 1 <= D <= 256 here
+    q : float or sequence of float
+        1 to 8 quantiles, each in [0, 1]
+    out : sequence of numpy.ndarray
+        (Optional) three arrays ``(Q,) + shape`` to write day, night and total into
+    slab_bytes : int
+        (Optional) device memory the member values may take at a time (default 128 MiB; at least
+        one batch of 256 pixels is taken); the result does not depend on it
+
+    Returns
+    -------
+    EnsembleQuantiles
+        ``(q, day, night, total)``: ``q`` as a float64 array (Q,); the quantiles of the day total, the
+        night total and of day + night (summed per member), each ``(Q,) + shape`` [kg m-2 s-1].
+        float32 only if every driver array is float32 (members, sum, order and interpolation in
+        float64, rounded once). A NaN in any member makes all Q values of that pixel and series NaN.
+        Pixels broadcast as in numpy; all-scalar input gives ``(Q,)`` arrays.
+    '''
+    from .calibration import quantile_positions
+    stack = _ensemble_stack(tables, beta)
+    qs = np.atleast_1d(np.asarray(q, np.float64))
+    if len(stack):
+        quantile_positions(qs, len(stack))       # ValueError for a bad q
+    nq = qs.size
+    drivers = (
+        lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+        temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+        pressure, fpar, lai)
+    dtype = _result_dtype(drivers)
+    cls = np.asarray(cls)
+    if cls.dtype != np.uint8:
+        if cls.size and (cls.min() < 0 or cls.max() > 255):
+            raise IndexError('class code outside [0, 255]')
+        cls = cls.astype(np.uint8)
+    shape, n = _broadcast([_shape(v) for v in drivers] + [cls.shape])
+    keep, dptr, dstride = _marshal(drivers, shape, dtype)
+    cls = np.ascontiguousarray(np.broadcast_to(cls, shape))
+    full = (nq,) + tuple(shape)
+    if out is not None:
+        outs = list(out)
+        if len(outs) != 3:
+            raise ValueError('out must hold 3 arrays')
+        for o in outs:
+            if not (isinstance(o, np.ndarray) and o.shape == full and o.dtype == dtype
+                    and o.flags.c_contiguous and o.flags.writeable):
+                raise ValueError('out arrays must be writeable C-contiguous %s arrays of shape %s'
+                                 % (dtype, full))
+    else:
+        outs = [_lib.pinned.empty(full, dtype) for _ in range(3)]
+    ens = _lib.Ensemble(_lib.context(device), stack)
+    try:
+        if n:
+            esz = np.dtype(dtype).itemsize
+            optr = [o.ctypes.data + k * n * esz for o in outs for k in range(nq)]
+            ens.quantiles(dtype, cls.ctypes.data, dptr, dstride, n, qs, optr, slab_bytes=slab_bytes,
+                          flags=math, where=_lib.HOST)
+    finally:
+        ens.close()
+    return EnsembleQuantiles(qs, *outs)
+
+
 def evapotranspiration_raw(
         bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
         sw_albedo, temp_day, temp_night, temp_annual, tmin, qv10m_day,

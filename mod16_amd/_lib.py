@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -253,6 +253,18 @@ PROTOTYPES = {
         C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, _PP, C.c_uint, C.c_int, C.c_void_p]),
     'mod16_et_ensemble_f32': (C.c_int, [
         C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, _PP, C.c_uint, C.c_int, C.c_void_p]),
+    'mod16_et_ensemble_members_f64': (C.c_int, [
+        C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+        C.c_uint, C.c_void_p]),
+    'mod16_et_ensemble_members_f32': (C.c_int, [
+        C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+        C.c_uint, C.c_void_p]),
+    'mod16_et_ensemble_quantiles_f64': (C.c_int, [
+        C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, C.POINTER(C.c_double), C.c_int, _PP,
+        C.c_int64, C.c_uint, C.c_int, C.c_void_p]),
+    'mod16_et_ensemble_quantiles_f32': (C.c_int, [
+        C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, C.POINTER(C.c_double), C.c_int, _PP,
+        C.c_int64, C.c_uint, C.c_int, C.c_void_p]),
 }
 
 _lib = None
@@ -476,6 +488,29 @@ class Ensemble:
             else self.ctx.lib.mod16_et_ensemble_f64
         self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers), i64_array(dstride),
                           int(n), ptr_array(outs), int(flags), int(where), stream))
+
+    def run_members(self, dtype, cls, drivers, dstride, n, day, night, pitch, flags=MATH_FAST, stream=None):
+        '''Thin wrapper of mod16_et_ensemble_members_f64 / _f32 (device addresses).'''
+        if not self.handle.value:
+            raise ValueError('the ensemble has been closed')
+        fn = self.ctx.lib.mod16_et_ensemble_members_f32 if np.dtype(dtype) == np.float32 \
+            else self.ctx.lib.mod16_et_ensemble_members_f64
+        self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers), i64_array(dstride),
+                          int(n), day, night, int(pitch), int(flags), stream))
+
+    def quantiles(self, dtype, cls, drivers, dstride, n, q, outs, slab_bytes=None, flags=MATH_FAST,
+                  where=HOST, stream=None):
+        '''Thin wrapper of mod16_et_ensemble_quantiles_f64 / _f32: ``q`` a sequence of floats,
+        ``outs`` the 3 * len(q) addresses, series-major (day, night, total); ``slab_bytes`` None: the
+        library's default.'''
+        if not self.handle.value:
+            raise ValueError('the ensemble has been closed')
+        fn = self.ctx.lib.mod16_et_ensemble_quantiles_f32 if np.dtype(dtype) == np.float32 \
+            else self.ctx.lib.mod16_et_ensemble_quantiles_f64
+        qs = _array_type(C.c_double, len(q))(*[float(v) for v in q])
+        self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers), i64_array(dstride),
+                          int(n), qs, len(q), ptr_array(outs), 0 if slab_bytes is None else int(slab_bytes),
+                          int(flags), int(where), stream))
 
     def close(self):
         if getattr(self, 'handle', None) and self.handle.value:

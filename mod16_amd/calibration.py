@@ -34,7 +34,11 @@ arithmetic is stated in full at the top of ``mod16_amd/csrc/mod16_mcmc.hpp``):
 - ``ensemble_tables(table, posterior, members)``: from posteriors to the parameter tables of an
   ensemble forward run (``mod16_amd.evapotranspiration_ensemble``, ``RasterEngine.ensemble``): joint
   draws without replacement per PFT, host only -- what the reference's ``export_posterior``
-  (calibration.py:633-709) hands on, put onto a raster.
+  (calibration.py:633-709) hands on, put onto a raster;
+- ``quantile_positions(q, members)`` and ``ensemble_quantile(x, q)``: the numpy statement of the
+  per-pixel quantiles over the members of an ensemble run
+  (``mod16_amd.evapotranspiration_ensemble_quantiles``, ``EnsembleRun.quantiles``): the definition
+  the selection kernel follows operation for operation. Host only.
 
   The reference's own k-fold loop does not do what its docstring says, and this port does what the
   docstring says. (1) The restore-and-mask block (``tower_obs[idx] = np.nan`` and the driver filter,
@@ -433,6 +437,61 @@ def ensemble_tables(table, posterior, members, seed=0, burn=0, thin=1):
         pick = np.random.default_rng([int(seed), int(pft)]).choice(pool, size=members, replace=False)
         for name, v in kept.items():
             out[:, int(pft), PARAM_NAMES.index(name)] = v[pick]
+    return out
+
+
+MAX_QUANTILES = 8
+
+
+def quantile_positions(q, members):
+    '''
+    Where the quantiles ``q`` fall among ``members`` ordered values: ``h = q * (members - 1)`` (one
+    float64 multiply), ``lo = floor(h)``, ``frac = h - lo`` -- numpy's default ``'linear'`` method.
+
+    ``q`` is a scalar (a 1-tuple) or a sequence of 1 to 8 values, each in [0, 1] and not NaN; anything
+    else raises ``ValueError``. Returns ``(lo int64 (Q,), frac float64 (Q,))``.
+    '''
+    members = int(members)
+    if members < 1:
+        raise ValueError('members >= 1 needed')
+    q = np.atleast_1d(np.asarray(q, np.float64))
+    if q.ndim != 1 or not 1 <= q.size <= MAX_QUANTILES:
+        raise ValueError('q must be a scalar or a sequence of 1 to %d values' % MAX_QUANTILES)
+    if not ((q >= 0.0) & (q <= 1.0)).all():       # (a NaN compares false)
+        raise ValueError('every q must lie in [0, 1] and not be NaN')
+    h = q * np.float64(members - 1)
+    lo = np.floor(h)
+    return lo.astype(np.int64), h - lo
+
+
+def ensemble_quantile(x, q):
+    '''
+    The quantiles ``q`` over axis 0 of ``x`` (members first, float64): THE definition of what
+    ``mod16_et_ensemble_quantiles_*`` returns; its selection kernel follows this statement operation
+    for operation. With ``lo, frac = quantile_positions(q, D)`` and ``s`` the members in ascending
+    order, ``a = s[lo]``, ``b = s[min(lo + 1, D - 1)]``; the value is ``a`` where ``frac == 0`` or
+    ``a == b``, else ``a + frac * (b - a)`` (a multiply, then an add: two roundings). On finite members
+    this is ``np.quantile(x, q, axis=0)`` to 3.3e-16 max|x_m| (measured, D = 1 ... 256, zeros and ties
+    included). A NaN anywhere along axis 0 makes all Q values of that column NaN. The ``frac == 0`` /
+    ``a == b`` rule defines infinite members: equal infinities stay, a position that falls exactly on
+    a finite member is that member (``np.quantile`` gives NaN in both cases).
+
+    Returns float64 ``(Q,) + x.shape[1:]``.
+    '''
+    x = np.asarray(x, np.float64)
+    if x.ndim < 1 or x.shape[0] < 1:
+        raise ValueError('x must have at least one member along axis 0')
+    D = x.shape[0]
+    lo, frac = quantile_positions(q, D)
+    nan = np.isnan(x).any(axis=0)
+    s = np.sort(np.where(nan, 0.0, x), axis=0)
+    out = np.empty((lo.size,) + x.shape[1:], np.float64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for k in range(lo.size):
+            a, b = s[lo[k]], s[min(lo[k] + 1, D - 1)]
+            t = frac[k] * (b - a)
+            v = np.where((frac[k] == 0.0) | (a == b), a, a + t)
+            out[k] = np.where(nan, np.nan, v)
     return out
 
 

@@ -1,4 +1,4 @@
-// libmod16hip.so -- the ensemble forward run: mod16_ensemble_create / _destroy, mod16_et_ensemble_* (per-pixel mean and spread of ET over D parameter tables)
+// libmod16hip.so -- the ensemble forward run: mod16_ensemble_create / _destroy, mod16_et_ensemble_* (per-pixel mean and spread of ET over D parameter tables), mod16_et_ensemble_members_* (every member's totals), mod16_et_ensemble_quantiles_* (per-pixel quantiles over the members)
 #include "host.hpp"
 #include "../mod16_ensemble.hpp"
 
@@ -132,4 +132,220 @@ extern "C" int mod16_et_ensemble_f32(mod16_ctx* ctx, const mod16_ensemble* ens, 
                                      float* const* out, unsigned flags, int where, void* stream) {
     MOD16_LOCK(ctx);
     return ensemble_entry<float>(ctx, ens, cls, drivers, dstride, n, out, flags, where, stream);
+}
+
+// ---- per-member outputs and per-pixel quantiles (ABI 11)
+
+static int ens_grid(const mod16_ctx* ctx, int64_t n) {
+    const int64_t nbatch = (n + kBlock - 1) / kBlock;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t)ctx->cus * 8));
+}
+
+// The member kernel (and, behind the fast one, the kernel of the flagged pixels) for a.n pixels.
+template <typename T, typename O>
+static void launch_members(mod16_ctx* ctx, const mod16_ensemble* ens, EnsMemArgs<T, O> a, unsigned flags, hipStream_t st) {
+    a.tables = ens->tables.as<double>();
+    a.members = (int)ens->members;
+    a.tab = ctx->tab64.as<double>();
+    a.status = ctx->status.as<unsigned>();
+    const int grid = ens_grid(ctx, a.n);
+    if (flags & MOD16_MATH_EXACT) hipLaunchKernelGGL((ens_members_kernel<T, O, false>), dim3(grid), dim3(kBlock), 0, st, a);
+    else {
+        hipLaunchKernelGGL((ens_members_kernel<T, O, true>), dim3(grid), dim3(kBlock), 0, st, a);
+        hipLaunchKernelGGL((ens_members_redo_kernel<T, O>), dim3(grid), dim3(kBlock), 0, st, a);
+    }
+}
+
+template <typename T, int CAP>
+static void launch_select_cap(const EnsSelArgs<T>& a, hipStream_t st) {
+    const unsigned grid = (unsigned)((a.n + kEnsSelLanes - 1) / kEnsSelLanes);
+    hipLaunchKernelGGL((ens_select_kernel<T, CAP>), dim3(grid), dim3(kEnsSelLanes), 0, st, a);
+}
+// the instance of the smallest capacity (16, 32, 64, 128, 256 members) that holds the ensemble
+template <typename T>
+static void launch_select(const EnsSelArgs<T>& a, hipStream_t st) {
+    if (a.members <= 16) launch_select_cap<T, 16>(a, st);
+    else if (a.members <= 32) launch_select_cap<T, 32>(a, st);
+    else if (a.members <= 64) launch_select_cap<T, 64>(a, st);
+    else if (a.members <= 128) launch_select_cap<T, 128>(a, st);
+    else launch_select_cap<T, 256>(a, st);
+}
+
+// What the entry point has checked: drivers, class raster, positions, outputs (device pointers, or
+// host pointers in front of the staging path).
+template <typename T> struct EnsQuantCall {
+    EnsMemArgs<T, double> mem;     // drv, cls, n, dense_drv
+    EnsSelArgs<T> sel;             // lo, frac, nq, out
+    int64_t slab_bytes;
+};
+
+// Chunks of P pixels through one slab of members x P x 2 doubles, a stream-ordered temporary of the
+// call, reused in stream order: member kernel, redo kernel, selection, next chunk.
+template <typename T>
+static int launch_quantiles(mod16_ctx* ctx, const mod16_ensemble* ens, const EnsQuantCall<T>& q, unsigned flags, hipStream_t st) {
+    const int64_t n = q.mem.n, D = ens->members;
+    if (n <= 0) return MOD16_OK;
+    int64_t P = std::max<int64_t>(256, q.slab_bytes / (16 * D) / 256 * 256);
+    P = std::min(P, (n + 255) / 256 * 256);
+    AsyncMem slab(st);
+    int rc = slab.alloc(ctx, (size_t)P * D * 16, "mod16_et_ensemble_quantiles: device memory for the slab of member values");
+    if (rc != MOD16_OK) return rc;
+    double* day = static_cast<double*>(slab.p);
+    double* night = day + P * D;
+    for (int64_t off = 0; off < n; off += P) {
+        EnsMemArgs<T, double> m = q.mem;
+        EnsSelArgs<T> s = q.sel;
+        m.n = s.n = std::min(P, n - off);
+        for (int k = 0; k < 14; ++k)
+            if ((m.dense_drv >> k) & 1u) m.drv[k] += off;
+        m.cls += off;
+        m.day = day;
+        m.night = night;
+        m.pitch = P;
+        s.day = day;
+        s.night = night;
+        s.pitch = P;
+        s.members = (int)D;
+        for (int k = 0; k < 3 * s.nq; ++k) s.out[k] += off;
+        launch_members<T, double>(ctx, ens, m, flags, st);
+        launch_select<T>(s, st);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return MOD16_OK;
+}
+
+// HOST mode: 14 drivers, the 3 nq outputs, the class raster -- through the shared staging path; each
+// tile's callback has its own slab on its own stream
+template <typename T>
+static int quantiles_host(mod16_ctx* ctx, const mod16_ensemble* ens, const EnsQuantCall<T>& h, unsigned flags) {
+    const int64_t n = h.mem.n;
+    if (n == 0) return MOD16_OK;
+    const int nout = 3 * h.sel.nq;
+    HostPlan p(sizeof(T));
+    for (int k = 0; k < 14; ++k) p.add(((h.mem.dense_drv >> k) & 1u) ? kIn : kScalar, h.mem.drv[k]);
+    for (int k = 0; k < nout; ++k) p.add(kOut, h.sel.out[k]);
+    p.add(kIn, h.mem.cls, true);
+    p.cls = h.mem.cls;
+    auto launch = [&](const HostTile& t) {
+        EnsQuantCall<T> d = h;
+        d.mem.n = t.m;
+        for (int k = 0; k < 14; ++k) d.mem.drv[k] = static_cast<const T*>(t.dev[k]);
+        for (int k = 0; k < nout; ++k) d.sel.out[k] = static_cast<T*>(t.dev[14 + k]);
+        d.mem.cls = static_cast<const uint8_t*>(t.dev[14 + nout]);
+        return launch_quantiles<T>(ctx, ens, d, flags, t.st);
+    };
+    if (n <= ctx->small_pixels) {
+        const int rc = host_small(ctx, p, n, false, launch);
+        if (rc != kSmallUnavailable) return rc;
+    }
+    return host_tiled(ctx, p, n, ctx->host_threads, true, launch);
+}
+
+// The checks the member and the quantile calls share with the ensemble run; fills drv, cls, n.
+template <typename T, typename O>
+static int members_args(mod16_ctx* ctx, const char* name, const mod16_ensemble* ens, const uint8_t* cls,
+                        const T* const* drivers, const int64_t* dstride, int64_t n, unsigned flags, EnsMemArgs<T, O>& a) {
+    char msg[160];
+    auto bad = [&](const char* what) {
+        snprintf(msg, sizeof msg, "%s: %s", name, what);
+        return fail(ctx, MOD16_ERR_ARG, msg);
+    };
+    if (!ens || !cls || !drivers || !dstride || n < 0) return bad("NULL ensemble, class raster, drivers or strides, or n < 0");
+    if (flags & MOD16_MATH_MIXED)
+        return bad("MOD16_MATH_MIXED is not available for the ensemble run (MOD16_MATH_FAST or MOD16_MATH_EXACT)");
+    if (flags & MOD16_DOMAIN_TRUSTED)
+        return bad("MOD16_DOMAIN_TRUSTED is not available for the ensemble run (every launch is guarded)");
+    if (flags & ~(unsigned)MOD16_MATH_EXACT) return bad("unknown flag");
+    if (ens->device != ctx->device) return bad("the ensemble was created on another device than this context's");
+    memset(&a, 0, sizeof a);
+    for (int k = 0; k < 14; ++k) {
+        if (!drivers[k]) return bad("NULL driver array");
+        if (dstride[k] != 0 && dstride[k] != 1) return bad("driver stride must be 0 or 1");
+        a.drv[k] = drivers[k];
+        if (dstride[k] == 1) a.dense_drv |= 1u << k;
+    }
+    a.cls = cls;
+    a.n = n;
+    return MOD16_OK;
+}
+
+template <typename T>
+static int members_entry(mod16_ctx* ctx, const mod16_ensemble* ens, const uint8_t* cls, const T* const* drivers,
+                         const int64_t* dstride, int64_t n, T* day, T* night, int64_t pitch, unsigned flags, void* stream) {
+    if (!ctx) return MOD16_ERR_ARG;
+    EnsMemArgs<T, T> a;
+    int rc = members_args<T, T>(ctx, "mod16_et_ensemble_members", ens, cls, drivers, dstride, n, flags, a);
+    if (rc != MOD16_OK) return rc;
+    if (!day || !night) return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_members: both output arrays are required");
+    if (pitch < n) return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_members: pitch must be at least n");
+    if (n == 0) return MOD16_OK;
+    a.day = day;
+    a.night = night;
+    a.pitch = pitch;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    launch_members<T, T>(ctx, ens, a, flags, static_cast<hipStream_t>(stream));
+    HIPCHK(ctx, hipGetLastError());
+    return MOD16_OK;
+}
+
+template <typename T>
+static int quantiles_entry(mod16_ctx* ctx, const mod16_ensemble* ens, const uint8_t* cls, const T* const* drivers,
+                           const int64_t* dstride, int64_t n, const double* q, int nq, T* const* out,
+                           int64_t slab_bytes, unsigned flags, int where, void* stream) {
+    if (!ctx) return MOD16_ERR_ARG;
+    EnsQuantCall<T> c;
+    memset(&c.sel, 0, sizeof c.sel);
+    int rc = members_args<T, double>(ctx, "mod16_et_ensemble_quantiles", ens, cls, drivers, dstride, n, flags, c.mem);
+    if (rc != MOD16_OK) return rc;
+    if (nq < 1 || nq > kEnsMaxQuantiles) return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_quantiles: nq must be between 1 and 8");
+    if (!q || !out) return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_quantiles: NULL q or outputs");
+    if (ens->members > kEnsSelMaxMembers)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_quantiles: more than 256 members");
+    if (slab_bytes < 0) return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_quantiles: slab_bytes must not be negative");
+    for (int k = 0; k < nq; ++k) {
+        if (!(q[k] >= 0.0 && q[k] <= 1.0))
+            return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_quantiles: every q must lie in [0, 1] and not be NaN");
+        // mod16_amd.calibration.quantile_positions: one float64 multiply, floor, the remainder
+        const double h = q[k] * (double)(ens->members - 1);
+        const double lo = std::floor(h);
+        c.sel.lo[k] = (int)lo;
+        c.sel.frac[k] = h - lo;
+    }
+    c.sel.nq = nq;
+    for (int k = 0; k < 3 * nq; ++k) {
+        if (!out[k]) return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_quantiles: all 3 * nq output arrays are required");
+        c.sel.out[k] = out[k];
+    }
+    c.slab_bytes = slab_bytes ? slab_bytes : (int64_t)128 << 20;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (where == MOD16_DEVICE) return launch_quantiles<T>(ctx, ens, c, flags, static_cast<hipStream_t>(stream));
+    if (where == MOD16_HOST) return quantiles_host<T>(ctx, ens, c, flags);
+    return fail(ctx, MOD16_ERR_ARG, "mod16_et_ensemble_quantiles: `where` must be MOD16_HOST or MOD16_DEVICE");
+}
+
+extern "C" int mod16_et_ensemble_members_f64(mod16_ctx* ctx, const mod16_ensemble* ens, const uint8_t* cls,
+                                             const double* const* drivers, const int64_t* dstride, int64_t n,
+                                             double* day, double* night, int64_t pitch, unsigned flags, void* stream) {
+    MOD16_LOCK(ctx);
+    return members_entry<double>(ctx, ens, cls, drivers, dstride, n, day, night, pitch, flags, stream);
+}
+extern "C" int mod16_et_ensemble_members_f32(mod16_ctx* ctx, const mod16_ensemble* ens, const uint8_t* cls,
+                                             const float* const* drivers, const int64_t* dstride, int64_t n,
+                                             float* day, float* night, int64_t pitch, unsigned flags, void* stream) {
+    MOD16_LOCK(ctx);
+    return members_entry<float>(ctx, ens, cls, drivers, dstride, n, day, night, pitch, flags, stream);
+}
+extern "C" int mod16_et_ensemble_quantiles_f64(mod16_ctx* ctx, const mod16_ensemble* ens, const uint8_t* cls,
+                                               const double* const* drivers, const int64_t* dstride, int64_t n,
+                                               const double* q, int nq, double* const* out, int64_t slab_bytes,
+                                               unsigned flags, int where, void* stream) {
+    MOD16_LOCK(ctx);
+    return quantiles_entry<double>(ctx, ens, cls, drivers, dstride, n, q, nq, out, slab_bytes, flags, where, stream);
+}
+extern "C" int mod16_et_ensemble_quantiles_f32(mod16_ctx* ctx, const mod16_ensemble* ens, const uint8_t* cls,
+                                               const float* const* drivers, const int64_t* dstride, int64_t n,
+                                               const double* q, int nq, float* const* out, int64_t slab_bytes,
+                                               unsigned flags, int where, void* stream) {
+    MOD16_LOCK(ctx);
+    return quantiles_entry<float>(ctx, ens, cls, drivers, dstride, n, q, nq, out, slab_bytes, flags, where, stream);
 }

@@ -11,7 +11,7 @@ namespace {
 constexpr int64_t kTilePixels = int64_t(1) << 21;   // HOST mode: pixels per staged tile
 constexpr size_t kStagger = 33 * 1024;              // see RasterEngine.STAGGER_BYTES
 constexpr int kSmallUnavailable = 1;                // host_small: no page-locked buffer -- the caller stages the call
-constexpr int kHostMaxArrays = 36;
+constexpr int kHostMaxArrays = 40;
 enum HostKind {
     kIn,         // per pixel, staged tile by tile
     kOut,        // per pixel, copied back tile by tile

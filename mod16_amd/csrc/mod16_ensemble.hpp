@@ -396,4 +396,278 @@ __global__ void __launch_bounds__(kBlock, 1) ens_redo_kernel(const EnsArgs<T> a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-member outputs and per-pixel quantiles (mod16_et_ensemble_members_*, _quantiles_*).
+//
+// ens_members_kernel is ens_kernel's body with another sink: instead of EnsAcc::add it stores day_m
+// and night_m to [m * pitch + i] -- a sibling, not an instance of a shared template, so that
+// ens_kernel keeps its code and its registers. O is the type of the member arrays: T for the public
+// ones, double for the slab of the quantile run (float drivers, double slab). The domain guard keeps
+// its shape: the fast kernel writes NO member of a flagged pixel but an EnsMark<O> into member 0's
+// day value, ens_members_redo_kernel behind it computes all members of every marked pixel in the
+// reference's order.
+//
+// ens_select_kernel orders a pixel's members and interpolates the quantiles
+// (mod16_amd.calibration.ensemble_quantile is its definition). One pixel per lane, one wave per
+// block; the pixel's column lives in LDS as doubles laid out [m][lane] (consecutive lanes on
+// consecutive pixels: every global load is coalesced, every LDS access conflict-free), padded with
+// +inf to the capacity CAP (a power of two, 16 ... 256: 8 ... 128 KiB, static). The order is a bitonic
+// network -- data-independent, so the lanes of the wave stay together -- blocked through registers 16
+// elements at a time: runs of 16 are sorted in registers straight from the slab, every later merge
+// does its strides >= 16 in LDS and its strides 8, 4, 2, 1 on 16 registers. A lane touches its own
+// column only: no barrier. The three series (day, night, day + night formed on load) use the same
+// LDS one after the other. A NaN member is replaced by +inf on load and carried as a flag.
+
+template <typename T, typename O> struct EnsMemArgs {
+    const T* drv[14];
+    const uint8_t* cls;
+    const double* tables;
+    const double* tab;
+    O* day;                    // [members][pitch]
+    O* night;
+    int64_t pitch;
+    int64_t n;
+    int members;
+    unsigned* status;
+    uint32_t dense_drv;
+};
+
+template <typename T, typename O>
+__device__ __forceinline__ void ens_exact_members_store(const PixelIn<double>& x, unsigned c,
+                                                        const EnsMemArgs<T, O>& a, int64_t i, bool live) {
+#pragma nounroll
+    for (int m = 0; m < a.members; ++m) {
+        const double* l = a.tables + (int64_t)m * kEnsTable + c;
+        ClassPar<double> p;
+        p.tmin_close = l[0 * kLutCols];
+        p.tmin_open = l[1 * kLutCols];
+        p.vpd_open = l[2 * kLutCols];
+        p.vpd_close = l[3 * kLutCols];
+        p.gl_sh = l[4 * kLutCols];
+        p.gl_wv = l[5 * kLutCols];
+        p.g_cut = l[6 * kLutCols];
+        p.csl = l[7 * kLutCols];
+        p.rbl_min = l[8 * kLutCols];
+        p.rbl_max = l[9 * kLutCols];
+        p.beta = l[10 * kLutCols];
+        const PixelOut<double> o = et_pixel_exact<double, false, true>(x, p);
+        if (live) {
+            a.day[(int64_t)m * a.pitch + i] = (O)((o.canopy_d + o.soil_d) + o.trans_d);
+            a.night[(int64_t)m * a.pitch + i] = (O)((o.canopy_n + o.soil_n) + o.trans_n);
+        }
+    }
+}
+
+template <typename T, typename O, bool FAST>
+__global__ void __launch_bounds__(kBlock, 2) ens_members_kernel(const EnsMemArgs<T, O> a) {
+    constexpr int kTab = FAST ? FastMath<double>::kTabDoubles : 1;
+    constexpr int kLds = FAST ? kEnsChunk * kEnsTable : 1;
+    __shared__ __attribute__((aligned(16))) double lut[kLds];
+    __shared__ __attribute__((aligned(16))) double tab[kTab];
+    const int D = a.members;
+    const bool resident = D <= kEnsChunk;
+    auto stage = [&](int m0, int count) {
+        const double* src = a.tables + (int64_t)m0 * kEnsTable;
+        for (int i = threadIdx.x; i < count * kEnsTable; i += kBlock) lut[i] = src[i];
+    };
+    if constexpr (FAST) {
+        ignore_signalling_nans();
+        for (int i = threadIdx.x; i < kTab; i += kBlock) tab[i] = a.tab[i];
+        if (resident) stage(0, D);
+        __syncthreads();
+    }
+    const int64_t nbatch = (a.n + kBlock - 1) / kBlock;
+    for (int64_t b = blockIdx.x; b < nbatch; b += gridDim.x) {
+        const int64_t i0 = b * kBlock + threadIdx.x;
+        const bool live = i0 < a.n;
+        const int64_t i = live ? i0 : a.n - 1;
+        auto drv = [&](int k) -> double { return (double)a.drv[k][((a.dense_drv >> k) & 1u) ? i : 0]; };
+        auto pixel = [&]() {
+            return PixelIn<double>{drv(0), drv(1), drv(2), drv(3), drv(4), drv(5), drv(6),
+                                   drv(7), drv(8), drv(9), drv(10), drv(11), drv(12), drv(13)};
+        };
+        unsigned c = a.cls[i];
+        if (c >= 13u) {
+            atomicOr(a.status, kStatusClassRange);
+            c = 13u;
+        }
+        if constexpr (FAST) {
+            bool keep;
+            EnsPixel px;
+            {
+                const PixelIn<double> x = pixel();
+                keep = live & !fast_out_of_domain(x);
+                px = ens_pixel_prep(x, tab);
+            }
+            O* day = a.day + i;
+            O* night = a.night + i;
+#pragma nounroll
+            for (int m0 = 0; m0 < D; m0 += kEnsChunk) {
+                const int mc = (D - m0 < kEnsChunk) ? D - m0 : kEnsChunk;
+                if (!resident) {
+                    __syncthreads();
+                    stage(m0, mc);
+                    __syncthreads();
+                }
+#pragma nounroll
+                for (int k = 0; k < mc; ++k) {
+                    const EnsMember m = ens_member(px, lut + k * kEnsTable + c);
+                    const double d = ens_period_eval<true>(px, px.d, m, tab);
+                    const double g = ens_period_eval<false>(px, px.n, m, tab);
+                    if (keep) {
+                        *day = (O)d;
+                        *night = (O)g;
+                    }
+                    day += a.pitch;
+                    night += a.pitch;
+                }
+            }
+            // outside the domain of the strength-reduced arithmetic: the mark for the kernel behind
+            if (live & !keep) a.day[i] = EnsMark<O>::value();
+        } else {
+            ens_exact_members_store(pixel(), c, a, i, live);
+        }
+    }
+}
+
+// Behind ens_members_kernel<T, O, true>: every member of the marked pixels in the reference's order.
+template <typename T, typename O>
+__global__ void __launch_bounds__(kBlock, 1) ens_members_redo_kernel(const EnsMemArgs<T, O> a) {
+    const int64_t step = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += step) {
+        if (!EnsMark<O>::is(a.day[i])) continue;
+        auto drv = [&](int k) -> double { return (double)a.drv[k][((a.dense_drv >> k) & 1u) ? i : 0]; };
+        const PixelIn<double> x = {drv(0), drv(1), drv(2), drv(3), drv(4), drv(5), drv(6),
+                                   drv(7), drv(8), drv(9), drv(10), drv(11), drv(12), drv(13)};
+        unsigned c = a.cls[i];
+        c = c >= 13u ? 13u : c;
+        ens_exact_members_store(x, c, a, i, true);
+    }
+}
+
+constexpr int kEnsMaxQuantiles = 8;
+constexpr int kEnsSelMaxMembers = 256;     // the largest column the selection holds in LDS
+constexpr int kEnsSelLanes = 64;           // one wave per block, one pixel per lane
+constexpr int kEnsSelRun = 16;             // elements a lane orders in registers per LDS pass
+
+template <typename T> struct EnsSelArgs {
+    const double* day;         // the slab: [members][pitch]
+    const double* night;
+    int64_t pitch;
+    int64_t n;                 // pixels of this chunk
+    int members;
+    int nq;
+    int lo[kEnsMaxQuantiles];          // quantile_positions(q, members), computed on the host
+    double frac[kEnsMaxQuantiles];
+    T* out[3 * kEnsMaxQuantiles];      // series-major: day, night, total; nq each
+};
+
+__device__ __forceinline__ void ens_cmpx(double& a, double& b) {    // a <= b afterwards
+    const bool sw = b < a;
+    const double lo = sw ? b : a, hi = sw ? a : b;
+    a = lo;
+    b = hi;
+}
+// bitonic merge of 16 registers whose two halves ... are bitonic already: strides 8, 4, 2, 1
+__device__ __forceinline__ void ens_merge16(double (&v)[kEnsSelRun]) {
+#pragma unroll
+    for (int j = kEnsSelRun / 2; j >= 1; j >>= 1)
+#pragma unroll
+        for (int i = 0; i < kEnsSelRun; ++i)
+            if ((i & j) == 0) ens_cmpx(v[i], v[i | j]);
+}
+// ascending order of 16 registers: the bitonic network, directions resolved at compile time
+__device__ __forceinline__ void ens_sort16(double (&v)[kEnsSelRun]) {
+#pragma unroll
+    for (int k = 2; k <= kEnsSelRun; k <<= 1)
+#pragma unroll
+        for (int j = k >> 1; j >= 1; j >>= 1)
+#pragma unroll
+            for (int i = 0; i < kEnsSelRun; ++i)
+                if ((i & j) == 0) {
+                    if ((i & k) == 0 || k == kEnsSelRun) ens_cmpx(v[i], v[i | j]);
+                    else ens_cmpx(v[i | j], v[i]);
+                }
+}
+
+template <typename T, int CAP>
+__global__ void __launch_bounds__(kEnsSelLanes) ens_select_kernel(const EnsSelArgs<T> a) {
+    static_assert(CAP >= kEnsSelRun && CAP <= kEnsSelMaxMembers && (CAP & (CAP - 1)) == 0, "capacity");
+    constexpr int L = kEnsSelLanes, R = kEnsSelRun;
+    __shared__ __attribute__((aligned(16))) double col[CAP * L];
+    const int lane = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * L + lane;
+    const bool live = i0 < a.n;
+    const int64_t i = live ? i0 : a.n - 1;
+    const int D = a.members;
+    const double inf = __builtin_inf();
+    double* mine = col + lane;
+#pragma nounroll
+    for (int series = 0; series < 3; ++series) {
+        bool nan = false;
+        // runs of 16 straight from the slab, ordered in registers; run r ascending for even r,
+        // descending for odd r: pairs of runs are bitonic
+#pragma nounroll
+        for (int r = 0; r < CAP / R; ++r) {
+            double v[R];
+#pragma unroll
+            for (int e = 0; e < R; ++e) {
+                const int m = r * R + e;
+                double x = inf;
+                if (m < D) {
+                    const int64_t at = (int64_t)m * a.pitch + i;
+                    x = series == 0 ? a.day[at] : series == 1 ? a.night[at] : a.day[at] + a.night[at];
+                }
+                nan |= x != x;
+                v[e] = (x != x) ? inf : x;
+            }
+            ens_sort16(v);
+            const bool up = (r & 1) == 0 || CAP == R;
+#pragma unroll
+            for (int e = 0; e < R; ++e) mine[(r * R + (up ? e : R - 1 - e)) * L] = v[e];
+        }
+        // merges of 32, 64, ... CAP: strides >= 16 in LDS, the rest on registers
+#pragma nounroll
+        for (int k = 2 * R; k <= CAP; k <<= 1) {
+#pragma nounroll
+            for (int j = k >> 1; j >= R; j >>= 1) {
+#pragma nounroll
+                for (int p = 0; p < CAP / 2; ++p) {
+                    const int lo = ((p & ~(j - 1)) << 1) | (p & (j - 1));     // bit j clear
+                    const int hi = lo | j;
+                    const bool up = (lo & k) == 0 || k == CAP;
+                    double x = mine[lo * L], y = mine[hi * L];
+                    if (up) ens_cmpx(x, y);
+                    else ens_cmpx(y, x);
+                    mine[lo * L] = x;
+                    mine[hi * L] = y;
+                }
+            }
+#pragma nounroll
+            for (int r = 0; r < CAP / R; ++r) {
+                double v[R];
+#pragma unroll
+                for (int e = 0; e < R; ++e) v[e] = mine[(r * R + e) * L];
+                ens_merge16(v);
+                const bool up = ((r * R) & k) == 0 || k == CAP;
+#pragma unroll
+                for (int e = 0; e < R; ++e) mine[(r * R + (up ? e : R - 1 - e)) * L] = v[e];
+            }
+        }
+        // the order statistics and their interpolation: ensemble_quantile, operation for operation
+#pragma nounroll
+        for (int q = 0; q < a.nq; ++q) {
+#pragma clang fp contract(off)
+            const int lo = a.lo[q];
+            const int hi = (lo + 1 < D) ? lo + 1 : D - 1;
+            const double frac = a.frac[q];
+            const double x = mine[lo * L], y = mine[hi * L];
+            const double t = frac * (y - x);
+            double val = (frac == 0.0 || x == y) ? x : x + t;
+            val = nan ? __builtin_nan("") : val;
+            if (live) a.out[series * a.nq + q][i] = (T)val;
+        }
+    }
+}
+
 }  // namespace mod16

@@ -149,8 +149,8 @@ class BoundStep(object):
 
 class EnsembleRun(object):
     '''The members of an ensemble forward run resident on an engine's device
-    (``RasterEngine.ensemble``): ``members`` parameter tables uploaded once, ``run`` as often as
-    there are rasters.'''
+    (``RasterEngine.ensemble``): ``members`` parameter tables uploaded once, ``run`` (mean and spread),
+    ``quantiles`` and ``run_members`` as often as there are rasters.'''
 
     def __init__(self, engine, tables):
         from . import _ensemble_stack
@@ -174,6 +174,51 @@ class EnsembleRun(object):
         optr = [eng._check_tensor(t, eng.dtype, n, 'out') for t in out]
         self._ens.run(eng.np_dtype, cptr, dptr, dstride, n, optr, flags=eng.math, where=_lib.DEVICE,
                       stream=eng._stream())
+        return out
+
+    def quantiles(self, cls, drivers, q=(0.05, 0.5, 0.95), out=None, slab_bytes=None):
+        '''Enqueue the quantile run on the current stream: the quantiles ``q`` (1 to 8 values in
+        [0, 1]) over the members of the day total, the night total and day + night per pixel
+        (``mod16_et_ensemble_quantiles_*``, defined by ``mod16_amd.calibration.ensemble_quantile``).
+        Returns three ``(Q, n)`` tensors ``(day, night, total)`` (``out`` may give them). The member
+        values pass through a stream-ordered temporary of at most ``slab_bytes`` (default 128 MiB, at
+        least one batch of 256 pixels). At most 256 members. Asynchronous, ``check()`` as for ``run``.'''
+        from .calibration import quantile_positions
+        eng, torch = self.engine, _torch()
+        n = cls.numel()
+        qs = np.atleast_1d(np.asarray(q, np.float64))
+        quantile_positions(qs, self.members)
+        nq = qs.size
+        cptr = eng._check_tensor(cls, torch.uint8, n, 'cls')
+        keep, dptr, dstride = eng._marshal_drivers(drivers, n)
+        if out is None:
+            out = tuple(torch.empty((nq, n), dtype=eng.dtype, device=eng._dev()) for _ in range(3))
+        out = tuple(out)
+        if len(out) != 3:
+            raise ValueError('out must hold 3 tensors')
+        esz = eng.np_dtype.itemsize
+        optr = [eng._check_tensor(t, eng.dtype, nq * n, 'out') + k * n * esz for t in out for k in range(nq)]
+        self._ens.quantiles(eng.np_dtype, cptr, dptr, dstride, n, qs, optr, slab_bytes=slab_bytes,
+                            flags=eng.math, where=_lib.DEVICE, stream=eng._stream())
+        return out
+
+    def run_members(self, cls, drivers, out=None):
+        '''Enqueue the member kernel on the current stream: every member's day and night total,
+        two ``(members, n)`` tensors ``(day, night)`` (``out`` may give them)
+        (``mod16_et_ensemble_members_*``). Asynchronous, ``check()`` as for ``run``.'''
+        eng, torch = self.engine, _torch()
+        n = cls.numel()
+        D = self.members
+        cptr = eng._check_tensor(cls, torch.uint8, n, 'cls')
+        keep, dptr, dstride = eng._marshal_drivers(drivers, n)
+        if out is None:
+            out = tuple(torch.empty((D, n), dtype=eng.dtype, device=eng._dev()) for _ in range(2))
+        out = tuple(out)
+        if len(out) != 2:
+            raise ValueError('out must hold 2 tensors')
+        optr = [eng._check_tensor(t, eng.dtype, D * n, 'out') for t in out]
+        self._ens.run_members(eng.np_dtype, cptr, dptr, dstride, n, optr[0], optr[1], n, flags=eng.math,
+                              stream=eng._stream())
         return out
 
     def close(self):

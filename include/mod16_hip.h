@@ -58,7 +58,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 11
+#define MOD16_ABI_VERSION 12
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -1023,6 +1023,76 @@ MOD16_API int mod16_et_ensemble_quantiles_f32(mod16_ctx* ctx, const mod16_ensemb
                                               const float* const* drivers, const int64_t* dstride, int64_t n,
                                               const double* q, int nq, float* const* out, int64_t slab_bytes,
                                               unsigned flags, int where, void* stream);
+
+/*
+ * Multi-day ET composites (ABI 12; mod16_amd.evapotranspiration_composite, RasterEngine.composite):
+ * per-pixel period totals [kg m-2 per period] of MOD16.evapotranspiration over `days` days of
+ * drivers in one launch -- MOD16A2 is the 8-day sum of daily ET, MOD16A3 the annual one. The
+ * definition is the numpy statement mod16_amd/composite.py (daily_total, composite_reduce):
+ *
+ *   periods     K = days (1 ... 4096), L = period_days >= 1: period p covers days [p L, min((p + 1) L, K));
+ *               P = ceil(K / L) periods, the last may be short.
+ *   arrays      each of the 14 drivers, and day_hours (hours of daylight), has a pixel stride (1: one
+ *               value per pixel; 0: one value, constant in time), a divisor every >= 1 and a time
+ *               stride in elements: day t reads time slab t / every, which starts time_stride
+ *               elements behind the previous one; ceil(K / every) slabs. An array with one slab
+ *               (every >= K) is constant and its time stride is not looked at.
+ *   daily total v_t = (day_t * h_t * 3600.0) + (night_t * (24.0 - h_t) * 3600.0), left to right, no
+ *               contraction; day_t / night_t are what mod16_et_* gives for day t's drivers [kg m-2 s-1];
+ *               with out_pet the same formula on the potential-ET pair of mod16_et_pet_*.
+ *   result      day t is valid where v_t is not NaN; count_p = valid days of period p (uint16);
+ *               sum_p = the float64 sum in day order of the valid v_t, from +0.0 (infinities take
+ *               part); the result is NaN where count_p < min_valid (1 ... L), else sum_p, or with
+ *               rescale = 1 sum_p * ((double)len_p / (double)count_p). ET and PET have their own counts.
+ *   outputs     out_et[p * out_pitch + i] for period p and pixel i, out_pitch >= n; optional out_pet
+ *               likewise; optional count_et / count_pet (uint16, the same pitch in elements;
+ *               count_pet needs out_pet).
+ *   float32     inputs widened, arithmetic and accumulation in float64, one rounding on store.
+ *   flags       MOD16_MATH_FAST (0) or MOD16_MATH_EXACT; the fast instance tests every pixel-day
+ *               against the domain of its arithmetic and a second kernel behind it recomputes the
+ *               periods of the pixels with a flagged day (the flagged days in the reference's
+ *               operation order): the daily values have the bits of mod16_et_* / mod16_et_pet_*
+ *               with the same flags on that day's drivers. No atomics on results, no workspace:
+ *               two calls give the same bits.
+ *   where       MOD16_DEVICE: device pointers, asynchronous on `stream` (mod16_check_status reports a
+ *               class code >= 13). MOD16_HOST: host pointers; pixel tiles are staged through the
+ *               context's slabs -- every time slab of every array, one copy per slab and tile -- with
+ *               the tile cut so that a slot's slab fits stage_bytes (0: 128 MiB; at least one batch of
+ *               256 pixels is taken). The result does not depend on stage_bytes.
+ *               A year of daily float64 drivers (days = 368, 3900 slabs and periods) gets tiles of 4096
+ *               pixels from the default; more stage_bytes, larger copies.
+ *               every >= days means one slab; it is used as days.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_et_composite: ...")
+ *               "days must be between 1 and 4096", "period_days must be at least 1",
+ *               "min_valid must be between 1 and period_days", "rescale must be 0 or 1",
+ *               "pixel stride must be 0 or 1", "every must be at least 1",
+ *               "time stride must not be negative",
+ *               "a broadcast scalar (pixel stride 0) is constant in time: its every must be at least days",
+ *               "time stride of an array with several slabs must be at least n",
+ *               "out_pitch must be at least n", "count_pet needs out_pet",
+ *               "stage_bytes must not be negative", a NULL array, n < 0, an unknown flag,
+ *               "MOD16_MATH_MIXED is not available for the composite run" and
+ *               "MOD16_DOMAIN_TRUSTED is not available for the composite run".
+ *               n = 0 is MOD16_OK.
+ */
+typedef struct mod16_composite_spec {
+    int64_t n;                                   /* pixels */
+    int32_t days, period_days, min_valid, rescale;
+    int64_t pixel_stride[MOD16_N_DRIVERS];       /* 0 or 1 */
+    int64_t time_stride[MOD16_N_DRIVERS];        /* elements between two time slabs */
+    int32_t every[MOD16_N_DRIVERS];              /* day t reads slab t / every */
+    int64_t hours_pixel_stride, hours_time_stride;   /* the same three for day_hours */
+    int32_t hours_every;
+    int32_t reserved_;
+} mod16_composite_spec;
+MOD16_API int mod16_et_composite_f64(mod16_ctx* ctx, const mod16_composite_spec* spec, const uint8_t* cls,
+                                     const double* const* drivers, const double* day_hours, double* out_et,
+                                     double* out_pet, uint16_t* count_et, uint16_t* count_pet, int64_t out_pitch,
+                                     unsigned flags, int where, void* stream, int64_t stage_bytes);
+MOD16_API int mod16_et_composite_f32(mod16_ctx* ctx, const mod16_composite_spec* spec, const uint8_t* cls,
+                                     const float* const* drivers, const float* day_hours, float* out_et,
+                                     float* out_pet, uint16_t* count_et, uint16_t* count_pet, int64_t out_pitch,
+                                     unsigned flags, int where, void* stream, int64_t stage_bytes);
 
 #ifdef __cplusplus
 }

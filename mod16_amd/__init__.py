@@ -1404,6 +1404,140 @@ def evapotranspiration_ensemble(
     return EnsembleET(*outs)
 
 
+CompositeET = _collections.namedtuple('CompositeET', 'et count')
+CompositeETPET = _collections.namedtuple('CompositeETPET', 'et pet count_et count_pet')
+
+
+def evapotranspiration_composite(
+        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, day_hours, days=None, period_days=8, every=None,
+        pet=False, min_valid=1, rescale=False, beta=None, math=_lib.MATH_FAST, device=0, out=None,
+        stage_bytes=None):
+    r'''
+    (Extension.) Multi-day ET composites over a multi-class raster: per-pixel totals of ET over
+    periods of ``period_days`` days [kg m-2 per period], what a loop over
+    ``evapotranspiration_raster`` per day, ``(day * hours + night * (24 - hours)) * 3600`` and a masked
+    sum return -- MOD16A2 is ``period_days=8``, MOD16A3 the days of the year -- from one kernel that
+    walks the days of a period per pixel and keeps the sums in registers
+    (``mod16_et_composite_*``). The definition is ``mod16_amd.composite`` (``daily_total``,
+    ``composite_reduce``).
+
+    Parameters
+    ----------
+    bplut, beta
+        as for ``evapotranspiration_raster``
+    cls : numpy.ndarray
+        Class raster; its shape is the pixel shape
+    the 14 drivers, day_hours
+        each a scalar, an array of the pixel shape (constant in time) or an array with one more
+        leading axis: its time axis, ``S = ceil(days / every[name])`` slabs of the pixel shape
+        (day ``t`` reads slab ``t // every[name]``). ``day_hours`` are the hours of daylight.
+    days : int
+        1 to 4096 (Default: the slabs of an array with a time axis whose divisor is 1)
+    period_days : int
+        days per period; the last period may be short
+    every : dict
+        divisor per array name (``mod16_amd.composite.ARRAY_NAMES``); default 1, daily
+    pet : bool
+        True to return the potential-ET composite as well
+    min_valid : int
+        a period with fewer valid days (daily total not NaN) is NaN; 1 to ``period_days``
+    rescale : bool
+        True to multiply a period's sum by ``len / count``
+    math : int
+        ``MATH_FAST`` (default) or ``MATH_EXACT``
+    out : sequence of numpy.ndarray
+        (Optional) the 2 (``pet``: 4) arrays ``(P,) + shape`` to write into
+    stage_bytes : int
+        (Optional) device memory a staging slot may take (default 128 MiB); the result does not
+        depend on it
+
+    Returns
+    -------
+    CompositeET or CompositeETPET
+        ``(et, count)`` or ``(et, pet, count_et, count_pet)``, each ``(P,) + shape`` with ``P =
+        ceil(days / period_days)``; counts are uint16. float32 only if every array input is float32
+        (computed in float64, rounded once).
+    '''
+    from . import composite as _c
+    from .utils import bplut_table
+    arrays = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+              temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+              pressure, fpar, lai, day_hours]
+    ev = _c.check_every(every)
+    cls = np.asarray(cls)
+    shape = cls.shape
+    n = int(cls.size)
+    dtype = _result_dtype(arrays)
+    timed = []
+    for name, v in zip(_c.ARRAY_NAMES, arrays):
+        sh = _shape(v)
+        if sh == () or sh == shape:
+            timed.append(False)
+        elif len(sh) == len(shape) + 1 and tuple(sh[1:]) == tuple(shape):
+            timed.append(True)
+        else:
+            raise ValueError('%s has shape %r: expected a scalar, the pixel shape %r or one more leading (time) axis'
+                             % (name, sh, shape))
+    if days is None:
+        daily = [_shape(v)[0] for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed) if t and ev[name] == 1]
+        if not daily:
+            raise ValueError('days is required when no array has a daily time axis')
+        days = int(daily[0])
+    K, L, mv, P = _c.check_periods(days, period_days, min_valid)
+    for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed):
+        if t:
+            _c.check_slabs(name, _shape(v)[0], K, ev[name])
+    if int(math) & ~_lib.MATH_EXACT:
+        raise ValueError('math must be MATH_FAST or MATH_EXACT for the composite run')
+    if stage_bytes is not None and int(stage_bytes) < 0:
+        raise ValueError('stage_bytes must not be negative')
+    if cls.dtype != np.uint8:
+        if cls.size and (cls.min() < 0 or cls.max() > 255):
+            raise IndexError('class code outside [0, 255]')
+        cls = cls.astype(np.uint8)
+    cls = np.ascontiguousarray(cls)
+    full = (P,) + tuple(shape)
+    want = 4 if pet else 2
+    if out is not None:
+        outs = list(out)
+        if len(outs) != want:
+            raise ValueError('out must hold %d arrays' % want)
+        for k, o in enumerate(outs):
+            dt = dtype if k < want // 2 else np.dtype(np.uint16)
+            if not (isinstance(o, np.ndarray) and o.shape == full and o.dtype == dt
+                    and o.flags.c_contiguous and o.flags.writeable):
+                raise ValueError('out[%d] must be a writeable C-contiguous %s array of shape %s' % (k, dt, full))
+    else:
+        outs = [np.empty(full, dtype) for _ in range(want // 2)] + [np.empty(full, np.uint16) for _ in range(want // 2)]
+    if isinstance(bplut, dict):
+        table = bplut_table(bplut, beta=beta)
+    else:
+        table = np.array(bplut, np.float64)
+        if beta is not None:
+            fill = np.isnan(table[:, 10]) & ~np.isnan(table[:, 0])
+            table[fill, 10] = beta
+    keep, ptrs, pstride, tstride, divisor = [], [], [], [], []
+    for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed):
+        scalar = _shape(v) == ()
+        a = np.array(v, dtype).reshape(1) if scalar else np.ascontiguousarray(v, dtype)
+        keep.append(a)
+        pstride.append(0 if scalar else 1)
+        ptrs.append(a.ctypes.data)
+        tstride.append(n if t and a.shape[0] > 1 else 0)
+        divisor.append(ev[name] if t else K)
+    if n:
+        ctx = _lib.context(device)
+        ctx.set_bplut(table)
+        optr = [o.ctypes.data for o in outs]
+        et, pt = (optr[0], optr[1]) if pet else (optr[0], None)
+        c_et, c_pt = (optr[2], optr[3]) if pet else (optr[1], None)
+        ctx.composite(dtype, n, K, L, cls.ctypes.data, ptrs, pstride, tstride, divisor, et, pt, c_et, c_pt, n,
+                      min_valid=mv, rescale=rescale, flags=math, where=_lib.HOST, stage_bytes=stage_bytes)
+    return (CompositeETPET if pet else CompositeET)(*outs)
+
+
 EnsembleQuantiles = _collections.namedtuple('EnsembleQuantiles', 'q day night total')
 
 

@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -82,6 +82,18 @@ class McmcSpec(C.Structure):
                 ('tune_steps', C.c_int64), ('tune_drop_fraction', C.c_double), ('objective', C.c_int32),
                 ('segment', C.c_int32), ('seed', C.c_uint64), ('constraints', C.c_int32),
                 ('reserved_', C.c_int32)]
+
+class CompositeSpec(C.Structure):
+    '''``mod16_composite_spec`` (include/mod16_hip.h): the pixels, days and periods of a composite call
+    and, per driver and for the hours of daylight, a pixel stride, a time stride and a divisor.'''
+    _fields_ = [('n', C.c_int64), ('days', C.c_int32), ('period_days', C.c_int32), ('min_valid', C.c_int32),
+                ('rescale', C.c_int32), ('pixel_stride', C.c_int64 * 14), ('time_stride', C.c_int64 * 14),
+                ('every', C.c_int32 * 14), ('hours_pixel_stride', C.c_int64), ('hours_time_stride', C.c_int64),
+                ('hours_every', C.c_int32), ('reserved_', C.c_int32)]
+
+
+_COMPOSITE_ARGS = [C.c_void_p, C.POINTER(CompositeSpec), C.c_void_p, _PP, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.c_void_p, C.c_void_p, C.c_int64, C.c_uint, C.c_int, C.c_void_p, C.c_int64]
 
 # name -> (restype, argtypes); one entry per function declared in the header
 PROTOTYPES = {
@@ -265,6 +277,8 @@ PROTOTYPES = {
     'mod16_et_ensemble_quantiles_f32': (C.c_int, [
         C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I64P, C.c_int64, C.POINTER(C.c_double), C.c_int, _PP,
         C.c_int64, C.c_uint, C.c_int, C.c_void_p]),
+    'mod16_et_composite_f64': (C.c_int, _COMPOSITE_ARGS),
+    'mod16_et_composite_f32': (C.c_int, _COMPOSITE_ARGS),
 }
 
 _lib = None
@@ -464,6 +478,31 @@ class Context:
 
     def check_status(self, stream=None):
         self.check(self.lib.mod16_check_status(self.handle, stream))
+
+    def composite(self, dtype, n, days, period_days, cls, arrays, pixel_stride, time_stride, every,
+                  out_et, out_pet, count_et, count_pet, out_pitch, min_valid=1, rescale=False,
+                  flags=MATH_FAST, where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_et_composite_f64 / _f32. ``arrays``, ``pixel_stride``, ``time_stride``
+        and ``every`` have 15 entries: the 14 drivers, then the hours of daylight. Every array argument
+        is a raw address (int) or None; ``stage_bytes`` None: the library's default.'''
+        for v in list(every) + [days, period_days, min_valid]:
+            if not 0 <= int(v) < 2 ** 31:
+                raise ValueError('days, period_days, min_valid and every must fit an int32, got %r' % (v,))
+        spec = CompositeSpec()
+        spec.n, spec.days, spec.period_days = int(n), int(days), int(period_days)
+        spec.min_valid, spec.rescale = int(min_valid), 1 if rescale else 0
+        for k in range(N_DRIVERS):
+            spec.pixel_stride[k] = int(pixel_stride[k])
+            spec.time_stride[k] = int(time_stride[k])
+            spec.every[k] = int(every[k])
+        spec.hours_pixel_stride = int(pixel_stride[N_DRIVERS])
+        spec.hours_time_stride = int(time_stride[N_DRIVERS])
+        spec.hours_every = int(every[N_DRIVERS])
+        fn = self.lib.mod16_et_composite_f32 if np.dtype(dtype) == np.float32 \
+            else self.lib.mod16_et_composite_f64
+        self.check(fn(self.handle, C.byref(spec), cls, ptr_array(list(arrays[:N_DRIVERS])), arrays[N_DRIVERS],
+                      out_et, out_pet, count_et, count_pet, int(out_pitch), int(flags), int(where), stream,
+                      0 if stage_bytes is None else int(stage_bytes)))
 
 
 class Ensemble:

@@ -24,19 +24,30 @@ enum HostKind {
 // drivers -- and raw's per-pixel day_hours -- stay equally spaced and the pipeline takes its pitched
 // instance), the byte rasters behind them. An absent optional array keeps its place (host = NULL)
 // and reaches the kernel as NULL.
+// An array may consist of several ROWS of n pixels each (the time slabs of a composite's drivers, the
+// periods of its outputs: composite.hip): `pitch` host elements apart, and in the slab back to back
+// (`row` bytes apart = HostTile::row_bytes, no stagger between them: the stagger separates ARRAYS).
+// Every array of the other families has one row: their offsets are what they were.
 struct HostPlan {
-    struct Array { void* host; void* dev; int elem; int kind; };
+    struct Array { void* host; void* dev; int elem; int kind; int rows; int64_t pitch; int first; };
     Array a[kHostMaxArrays];
     int count = 0, nwide = 0;
+    int wide_rows = 0, byte_rows = 0;  // places of the slab's two regions
     int elem;                          // sizeof(T)
     const uint8_t* cls = nullptr;      // the class raster: the small path checks its codes on the host
     explicit HostPlan(int elem_) : elem(elem_) {}
-    void add(int kind, const void* host, bool bytes = false) {
-        a[count++] = Array{const_cast<void*>(host), nullptr, bytes ? 1 : elem, kind};
+    // elem_size: an array of another element type than T in a T-sized place (0: T, or a byte)
+    void add(int kind, const void* host, bool bytes = false, int rows = 1, int64_t pitch = 0, int elem_size = 0) {
+        int& region = bytes ? byte_rows : wide_rows;
+        a[count++] = Array{const_cast<void*>(host), nullptr, elem_size ? elem_size : (bytes ? 1 : elem), kind, rows, pitch, region};
+        region += rows;
         if (!bytes) ++nwide;
     }
-    size_t offset(int i, size_t per_arr, size_t per_b) const {
-        return i < nwide ? per_arr * i : per_arr * nwide + per_b * (i - nwide);
+    // per_arr: from one T-sized array to the next when both have one row; row: what every further row adds
+    size_t offset(int i, size_t per_arr, size_t per_b, size_t row = 0) const {
+        const size_t wide = per_arr * nwide + row * (wide_rows - nwide);
+        if (i >= count) return wide + per_b * byte_rows;
+        return i < nwide ? per_arr * i + row * (a[i].first - i) : wide + per_b * a[i].first;
     }
     void put_scalars(char* block) const {
         for (int i = 0; i < count; ++i)
@@ -54,6 +65,7 @@ struct HostPlan {
 struct HostTile {
     void* dev[kHostMaxArrays];
     int64_t m, off;      // pixels of the tile, its first pixel in the call
+    size_t row_bytes;    // between two rows of a T-sized array with several (host_tiled)
     hipStream_t st;
     double* diag;        // host_tiled with tile_diag: where this tile's diagnostics vector goes (device)
 };
@@ -115,6 +127,7 @@ static int host_small(mod16_ctx* ctx, const HostPlan& p, int64_t n, bool pad, La
     HostTile t;
     t.m = npad;
     t.off = 0;
+    t.row_bytes = per_arr;
     t.st = ctx->streams[0];
     t.diag = nullptr;
     for (int i = 0; i < p.count; ++i) {
@@ -141,17 +154,20 @@ static int host_small(mod16_ctx* ctx, const HostPlan& p, int64_t n, bool pad, La
 // reserved at its final size before any thread launches, and the status word is read back at the end.
 // tile_diag: one diagnostics vector per tile (host, 8 doubles each), reduced by the callback into
 // HostTile::diag while the tile's outputs are on the device.
+// tile_pixels: a family whose arrays have many rows cuts the tile so that a slot's slab keeps its size.
+// A row of an array is one copy command per tile.
 template <typename Launch>
 static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slots, bool pipeline,
-                      Launch&& launch, double* tile_diag = nullptr) {
-    const int64_t tile = std::min<int64_t>(n, kTilePixels);
+                      Launch&& launch, double* tile_diag = nullptr, int64_t tile_pixels = kTilePixels) {
+    const int64_t tile = std::min<int64_t>(n, tile_pixels);
     const int64_t ntiles = (n + tile - 1) / tile;
     const int nslots = (int)std::min<int64_t>(ntiles, max_slots);
     if (nslots > 1) ctx->ws_multi = true;       // one stream per slot: the launches leave their events (ws_release)
     // successive staged arrays are kStagger bytes apart on top of their size
-    const size_t per_arr = ((size_t)tile * p.elem + 255) / 256 * 256 + kStagger;
+    const size_t row = ((size_t)tile * p.elem + 255) / 256 * 256;
+    const size_t per_arr = row + kStagger;
     const size_t per_b = ((size_t)tile + 255) / 256 * 256;
-    const size_t need = p.offset(p.count, per_arr, per_b) + 256;
+    const size_t need = p.offset(p.count, per_arr, per_b, row) + 256;
     if (ctx->slab_bytes < need) {
         for (int s = 0; s < kSlots; ++s) ctx->slab[s].release();
         ctx->slab_bytes = need;
@@ -178,14 +194,17 @@ static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slot
         HostTile t;
         t.m = std::min(tile, n - off);
         t.off = off;
+        t.row_bytes = row;
         t.st = ctx->streams[slot];
         t.diag = tile_diag ? ctx->hdiag_dev.as<double>() + (size_t)slot * kDiag : nullptr;
         for (int i = 0; i < p.count; ++i) {
             const HostPlan::Array& x = p.a[i];
-            t.dev[i] = p.where(i, base + p.offset(i, per_arr, per_b), dscal);
+            t.dev[i] = p.where(i, base + p.offset(i, per_arr, per_b, row), dscal);
             if (x.host && x.kind == kIn)
-                HIPCHK(ctx, hipMemcpyAsync(t.dev[i], static_cast<const char*>(x.host) + x.elem * off, x.elem * t.m,
-                                           hipMemcpyHostToDevice, t.st));
+                for (int r = 0; r < x.rows; ++r)
+                    HIPCHK(ctx, hipMemcpyAsync(static_cast<char*>(t.dev[i]) + row * r,
+                                               static_cast<const char*>(x.host) + x.elem * (x.pitch * r + off), x.elem * t.m,
+                                               hipMemcpyHostToDevice, t.st));
         }
         {
             std::lock_guard<std::mutex> lock(ctx->launch_mu);
@@ -196,8 +215,10 @@ static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slot
         for (int i = 0; i < p.count; ++i) {
             const HostPlan::Array& x = p.a[i];
             if (x.host && x.kind == kOut)
-                HIPCHK(ctx, hipMemcpyAsync(static_cast<char*>(x.host) + x.elem * off, t.dev[i], x.elem * t.m,
-                                           hipMemcpyDeviceToHost, t.st));
+                for (int r = 0; r < x.rows; ++r)
+                    HIPCHK(ctx, hipMemcpyAsync(static_cast<char*>(x.host) + x.elem * (x.pitch * r + off),
+                                               static_cast<const char*>(t.dev[i]) + row * r, x.elem * t.m,
+                                               hipMemcpyDeviceToHost, t.st));
         }
         if (t.diag) HIPCHK(ctx, hipMemcpyAsync(tile_diag + off / tile * kDiag, t.diag, sizeof(double) * kDiag, hipMemcpyDeviceToHost, t.st));
         HIPCHK(ctx, hipStreamSynchronize(t.st));      // the slab of this slot is free again

@@ -12,3 +12,4 @@
 #include "capi/sensitivity.hip"
 #include "capi/mcmc.hip"
 #include "capi/ensemble.hip"
+#include "capi/composite.hip"

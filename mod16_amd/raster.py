@@ -441,6 +441,91 @@ class RasterEngine(object):
                     flags=self.math, where=_lib.DEVICE, stream=self._stream())
         return out_day, out_night
 
+    def composite(self, cls, drivers, day_hours, days, period_days=8, every=None, pet=False,
+                  min_valid=1, rescale=False, out=None):
+        '''Enqueue the composite kernel on the current stream: per-pixel totals of ET over periods
+        of ``period_days`` days [kg m-2 per period] from ``days`` days of device-resident drivers in
+        one launch (``mod16_et_composite_*``; the definition is ``mod16_amd.composite``) -- ``days=8,
+        period_days=8`` is one MOD16A2 value per pixel, ``days=365, period_days=365`` MOD16A3.
+
+        ``cls`` is the ``(n,)`` class raster. Each of the 14 ``drivers`` and ``day_hours`` (hours of
+        daylight) is a scalar, an ``(n,)`` tensor (constant in time) or an ``(S, n)`` tensor with unit
+        stride in pixels and any stride in time (views of a larger buffer are fine), where ``S =
+        ceil(days / every[name])``: day ``t`` reads row ``t // every[name]``. ``every`` maps names of
+        ``mod16_amd.composite.ARRAY_NAMES`` to divisors (default 1: daily; 8 for 8-day fPAR / LAI /
+        albedo). A day counts where its total is not NaN; a period with fewer than ``min_valid`` such
+        days is NaN; ``rescale`` brings a period with missing days to its full length.
+
+        Returns ``(et, count)``, or with ``pet`` ``(et, pet, count_et, count_pet)``: totals in the
+        engine's dtype and uint16 counts of valid days, each ``(P, n)`` with ``P = ceil(days /
+        period_days)``. ``out`` may give them: rows of unit stride, all with the same distance
+        between rows. The engine's ``math`` must be ``MATH_FAST`` or ``MATH_EXACT``. Asynchronous:
+        call ``check()`` (or synchronise the stream) before trusting the data; a class code >= 13
+        raises IndexError there.'''
+        from . import composite as _c
+        torch = _torch()
+        K, L, mv, P = _c.check_periods(days, period_days, min_valid)
+        ev = _c.check_every(every)
+        if self.math & ~_lib.MATH_EXACT:
+            raise ValueError('composite needs an engine with MATH_FAST or MATH_EXACT (no MATH_MIXED, not trusted)')
+        if len(drivers) != _lib.N_DRIVERS:
+            raise ValueError('expected 14 drivers')
+        n = cls.numel()
+        cptr = self._check_tensor(cls, torch.uint8, n, 'cls')
+        keep, ptrs, pstride, tstride, divisor = [], [], [], [], []
+        for name, d in zip(_c.ARRAY_NAMES, list(drivers) + [day_hours]):
+            if isinstance(d, torch.Tensor) and d.dim() > 0:
+                if not d.is_cuda or d.device.index != self.device or d.dtype != self.dtype:
+                    raise TypeError('%s must be a %s tensor on cuda:%d' % (name, self.dtype, self.device))
+                if d.dim() > 2 or d.shape[-1] != n:
+                    raise ValueError('%s must be a scalar, an (n,) or an (S, n) tensor with n = %d, got %r'
+                                     % (name, n, tuple(d.shape)))
+                if n > 1 and d.stride(-1) != 1:
+                    raise ValueError('%s must have unit stride in pixels' % name)
+                slabs = d.shape[0] if d.dim() == 2 else 1
+                if d.dim() == 2:
+                    _c.check_slabs(name, slabs, K, ev[name])
+                    if slabs > 1 and d.stride(0) < n:
+                        raise ValueError('%s: the stride in time must be at least n' % name)
+                keep.append(d)
+                ptrs.append(d.data_ptr())
+                pstride.append(1)
+                tstride.append(d.stride(0) if slabs > 1 else 0)
+                divisor.append(ev[name] if d.dim() == 2 else K)
+            else:       # broadcast scalar, constant in time
+                sc = torch.as_tensor(d, dtype=self.dtype).reshape(1).to(self._dev())
+                keep.append(sc)
+                ptrs.append(sc.data_ptr())
+                pstride.append(0)
+                tstride.append(0)
+                divisor.append(K)
+        want = 4 if pet else 2
+        if out is None:
+            out = [torch.empty((P, n), dtype=self.dtype, device=self._dev()) for _ in range(want // 2)] + \
+                  [torch.empty((P, n), dtype=torch.uint16, device=self._dev()) for _ in range(want // 2)]
+        out = tuple(out)
+        if len(out) != want:
+            raise ValueError('out must hold %d tensors' % want)
+        pitch = None
+        for k, o in enumerate(out):
+            dt = self.dtype if k < want // 2 else torch.uint16
+            if not isinstance(o, torch.Tensor) or not o.is_cuda or o.device.index != self.device or o.dtype != dt:
+                raise TypeError('out[%d] must be a %s tensor on cuda:%d' % (k, dt, self.device))
+            if tuple(o.shape) != (P, n) or (n > 1 and o.stride(1) != 1):
+                raise ValueError('out[%d] must have shape (%d, %d) and unit stride in pixels' % (k, P, n))
+            row = o.stride(0) if P > 1 else max(n, 1)
+            if row < n or (pitch is not None and row != pitch):
+                raise ValueError('the out tensors must share one distance between rows, at least n')
+            pitch = row
+        if n:
+            optr = [o.data_ptr() for o in out]
+            et, pt = (optr[0], optr[1]) if pet else (optr[0], None)
+            c_et, c_pt = (optr[2], optr[3]) if pet else (optr[1], None)
+            self.ctx.composite(self.np_dtype, n, K, L, cptr, ptrs, pstride, tstride, divisor, et, pt, c_et, c_pt,
+                               pitch, min_valid=mv, rescale=rescale, flags=self.math, where=_lib.DEVICE,
+                               stream=self._stream())
+        return out
+
     def ensemble(self, tables):
         '''The members of an ensemble forward run on this engine's device: ``tables`` is a (D, 13,
         11) array or a sequence of D ``restore_bplut`` dicts (``mod16_amd.calibration.ensemble_tables``

@@ -52,13 +52,14 @@
 #ifndef MOD16_HIP_H
 #define MOD16_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 12
+#define MOD16_ABI_VERSION 13
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -1093,6 +1094,58 @@ MOD16_API int mod16_et_composite_f32(mod16_ctx* ctx, const mod16_composite_spec*
                                      const float* const* drivers, const float* day_hours, float* out_et,
                                      float* out_pet, uint16_t* count_et, uint16_t* count_pet, int64_t out_pitch,
                                      unsigned flags, int where, void* stream, int64_t stage_bytes);
+
+/*
+ * QC-driven temporal gap filling of byte series (ABI 13; mod16_amd.gapfill_series,
+ * RasterEngine.gapfill): the step between MOD15A2H granules and the fPAR / LAI series the raw and
+ * composite entry points take. One launch fills the annual profile of every pixel of one to three
+ * fields. The definition is the numpy statement mod16_amd/gapfill.py (reliable, fill_series, encode):
+ *
+ *   inputs      fields[f][t * in_pitch + i]: the code of field f, slab t (0 ... slabs - 1, slabs
+ *               1 ... 4096), pixel i; optional qc[t * qc_pitch + i], one QC byte shared by the fields;
+ *               optional good256[q]: non-zero where QC byte q is acceptable (NULL: the package's
+ *               default for MOD15A2H's FparLai_QC -- MODLAND good, no dead detector, cloud state clear
+ *               or assumed clear, main algorithm with or without saturation: the codes 0, 2, 24, 26, 32,
+ *               34, 56, 58); optional fallback[f][i] (the array, or any of its entries, may be NULL).
+ *   reliable    slab t of pixel i is reliable for field f where its code is < 249 and, with qc,
+ *               good256[qc] holds: each field has its own reliability.
+ *   result      per field, pixel and slab t, with i the last reliable slab <= t (code a) and j the
+ *               first reliable slab >= t (code b), an exact rational num / den and a source byte:
+ *                 0 observed      t reliable: code / 1
+ *                 1 interpolated  i and j exist, j - i - 1 <= max_gap: (a (j - t) + b (t - i)) / (j - i)
+ *                 2 held          only one of them exists and is at most max_gap slabs away: its code / 1
+ *                 3 fallback      none of these and fallback[f][pixel] < 249: that code / 1
+ *                 4 unfilled      otherwise
+ *               max_gap = -1: no limit.
+ *   outputs     out[f][t * out_pitch + i], of out_type: MOD16_GAPFILL_U8 (2 num + den) / (2 den) in
+ *               integers, round half up, 255 where unfilled; MOD16_GAPFILL_F32 / _F64
+ *               (T)(((double)num / (double)den) * scale[f]), NaN where unfilled (scale is not looked at
+ *               for uint8). Optional source[(f * slabs + t) * source_pitch + i], the source byte.
+ *               Every element [t][0, n) is written exactly once; [t][n, pitch) is not touched.
+ *               Pointers may have any byte alignment and the pitches any value >= n (in elements);
+ *               rows aligned to 16 bytes take vector accesses. No workspace, no atomics: two calls
+ *               give the same bits.
+ *   where       MOD16_DEVICE: device pointers (good256 too), asynchronous on `stream`. MOD16_HOST:
+ *               host pointers; pixel tiles are staged through the context's slabs, every slab of
+ *               every array one copy per tile, the tile cut so that a slot fits stage_bytes (0: 128
+ *               MiB; at least 256 pixels). The result does not depend on stage_bytes.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_gapfill: ...")
+ *               NULL spec, fields, out or one of their first nfields entries; n < 0; "slabs must be
+ *               between 1 and 4096"; "nfields must be between 1 and 3"; an unknown out_type; "max_gap
+ *               must be -1 (none) or at least 0"; a pitch below n; a scale that is not finite;
+ *               `where` other than the two modes; "an output overlaps an input or another output" (in
+ *               place is refused, not supported). n = 0 is MOD16_OK.
+ */
+enum mod16_gapfill_out { MOD16_GAPFILL_U8 = 0, MOD16_GAPFILL_F32 = 1, MOD16_GAPFILL_F64 = 2 };
+typedef struct mod16_gapfill_spec {
+    int64_t n;                                   /* pixels */
+    int32_t slabs, nfields, out_type, max_gap;   /* max_gap: -1 = none */
+    double scale[3];                             /* per field, float outputs only */
+    int64_t in_pitch, qc_pitch, out_pitch, source_pitch;   /* elements between two slabs */
+} mod16_gapfill_spec;
+MOD16_API int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, const uint8_t* const* fields,
+                               const uint8_t* qc, const uint8_t* good256, const uint8_t* const* fallback,
+                               void* const* out, uint8_t* source, int where, void* stream, size_t stage_bytes);
 
 #ifdef __cplusplus
 }

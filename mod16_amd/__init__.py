@@ -1538,6 +1538,84 @@ def evapotranspiration_composite(
     return (CompositeETPET if pet else CompositeET)(*outs)
 
 
+def gapfill_series(fields, qc=None, good=None, max_gap=None, fallback=None, dtype='uint8', scale=None,
+                   source=False, device=0, stage_bytes=None):
+    r'''
+    (Extension.) QC-driven temporal gap filling of one to three 8-day byte series (MOD15A2H fPAR /
+    LAI codes) in one kernel launch per staged tile (``mod16_gapfill_u8``): unreliable slabs are
+    linearly interpolated between the nearest reliable slabs before and after, a gap at either end
+    takes the nearest reliable value, and what ``max_gap`` leaves open takes ``fallback`` or stays
+    unfilled. The definition is ``mod16_amd.gapfill`` (``reliable``, ``fill_series``, ``encode``).
+
+    Parameters
+    ----------
+    fields : numpy.ndarray or tuple of up to three
+        uint8 codes, each ``(S,) + pixel shape`` with ``1 <= S <= 4096``; codes >= 249 are fill values
+    qc : numpy.ndarray
+        (Optional) uint8 QC layer of the same shape, shared by the fields
+    good : sequence of 256 booleans
+        (Optional) which QC bytes are acceptable (Default: ``mod16_amd.gapfill.default_good()``)
+    max_gap : int
+        (Optional) longest run of unreliable slabs that is interpolated, and the furthest a value is
+        held at either end (Default: None, no limit)
+    fallback : numpy.ndarray or tuple
+        (Optional) one uint8 array of the pixel shape (or None) per field, e.g. a climatology
+    dtype : str
+        ``'uint8'`` (codes, rounded half up; 255 where unfilled), ``'float32'`` or ``'float64'``
+        (``code * scale``; NaN where unfilled)
+    scale : float or tuple
+        (Optional) per field, float output only: 0.01 and 0.1 turn fPAR and LAI codes into what the
+        14-driver entry points take (Default: 1)
+    source : bool
+        True to return, per field, the bytes that say where each value came from (0 observed,
+        1 interpolated, 2 held, 3 fallback, 4 unfilled)
+    stage_bytes : int
+        (Optional) device memory a staging slot may take; the result does not depend on it
+
+    Returns
+    -------
+    numpy.ndarray or tuple
+        the filled array (a tuple if ``fields`` was one), and with ``source`` a pair ``(filled,
+        source)`` of the same structure
+    '''
+    from . import gapfill as _g
+    single = isinstance(fields, np.ndarray) or not isinstance(fields, (tuple, list))
+    flds = [np.asarray(f) for f in ([fields] if single else fields)]
+    if fallback is not None and (isinstance(fallback, np.ndarray) or not isinstance(fallback, (tuple, list))):
+        fallback = [fallback]
+    fbs = None if fallback is None else [None if f is None else np.asarray(f) for f in fallback]
+    qc = None if qc is None else np.asarray(qc)
+    S, shape, table, mg, name, scales = _g.check_series(
+        [f.shape for f in flds], None if qc is None else qc.shape, good, max_gap,
+        None if fbs is None else [None if f is None else f.shape for f in fbs], dtype, scale)
+    for what, arrs in (('fields', flds), ('qc', [qc]), ('fallback', fbs or [])):
+        for a in arrs:
+            if a is not None and a.dtype != np.uint8:
+                raise ValueError('%s must be uint8, got %s' % (what, a.dtype))
+    if stage_bytes is not None and int(stage_bytes) < 0:
+        raise ValueError('stage_bytes must not be negative')
+    n = int(np.prod(shape, dtype=np.int64))
+    flds = [np.ascontiguousarray(f).reshape(S, n) for f in flds]
+    qc = None if qc is None else np.ascontiguousarray(qc).reshape(S, n)
+    fbs = None if fbs is None else [None if f is None else np.ascontiguousarray(f).reshape(n) for f in fbs]
+    outs = [np.empty((S, n), name) for _ in flds]
+    src = np.empty((len(flds), S, n), np.uint8) if source else None
+    if n:
+        good8 = np.ascontiguousarray(table, np.uint8)
+        _lib.context(device).gapfill(
+            _g.OUT_TYPES[name], n, S, [f.ctypes.data for f in flds], None if qc is None else qc.ctypes.data,
+            good8.ctypes.data, None if fbs is None else [None if f is None else f.ctypes.data for f in fbs],
+            [o.ctypes.data for o in outs], None if src is None else src.ctypes.data, n, n, n, n,
+            max_gap=mg, scale=scales + [1.0] * (3 - len(scales)), where=_lib.HOST, stage_bytes=stage_bytes)
+    full = (S,) + tuple(shape)
+    filled = [o.reshape(full) for o in outs]
+    filled = filled[0] if single else tuple(filled)
+    if not source:
+        return filled
+    srcs = [src[f].reshape(full) for f in range(len(flds))]
+    return filled, (srcs[0] if single else tuple(srcs))
+
+
 EnsembleQuantiles = _collections.namedtuple('EnsembleQuantiles', 'q day night total')
 
 

@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -94,6 +94,16 @@ class CompositeSpec(C.Structure):
 
 _COMPOSITE_ARGS = [C.c_void_p, C.POINTER(CompositeSpec), C.c_void_p, _PP, C.c_void_p, C.c_void_p, C.c_void_p,
                    C.c_void_p, C.c_void_p, C.c_int64, C.c_uint, C.c_int, C.c_void_p, C.c_int64]
+
+class GapfillSpec(C.Structure):
+    '''``mod16_gapfill_spec`` (include/mod16_hip.h): the pixels, slabs, fields, output type, scales,
+    gap limit and pitches of a gap-filling call.'''
+    _fields_ = [('n', C.c_int64), ('slabs', C.c_int32), ('nfields', C.c_int32), ('out_type', C.c_int32),
+                ('max_gap', C.c_int32), ('scale', C.c_double * 3), ('in_pitch', C.c_int64),
+                ('qc_pitch', C.c_int64), ('out_pitch', C.c_int64), ('source_pitch', C.c_int64)]
+
+
+GAPFILL_U8, GAPFILL_F32, GAPFILL_F64 = 0, 1, 2     # enum mod16_gapfill_out
 
 # name -> (restype, argtypes); one entry per function declared in the header
 PROTOTYPES = {
@@ -279,6 +289,8 @@ PROTOTYPES = {
         C.c_int64, C.c_uint, C.c_int, C.c_void_p]),
     'mod16_et_composite_f64': (C.c_int, _COMPOSITE_ARGS),
     'mod16_et_composite_f32': (C.c_int, _COMPOSITE_ARGS),
+    'mod16_gapfill_u8': (C.c_int, [C.c_void_p, C.POINTER(GapfillSpec), _PP, C.c_void_p, C.c_void_p, _PP, _PP,
+                                   C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
 }
 
 _lib = None
@@ -503,6 +515,25 @@ class Context:
         self.check(fn(self.handle, C.byref(spec), cls, ptr_array(list(arrays[:N_DRIVERS])), arrays[N_DRIVERS],
                       out_et, out_pet, count_et, count_pet, int(out_pitch), int(flags), int(where), stream,
                       0 if stage_bytes is None else int(stage_bytes)))
+
+    def gapfill(self, out_type, n, slabs, fields, qc, good, fallback, out, source, in_pitch, qc_pitch,
+                out_pitch, source_pitch, max_gap=-1, scale=(1.0, 1.0, 1.0), where=HOST, stream=None,
+                stage_bytes=None):
+        '''Thin wrapper of mod16_gapfill_u8. ``fields`` and ``out`` hold one raw address per field,
+        ``fallback`` one address or None per field (or is None); ``qc``, ``good`` (256 bytes) and
+        ``source`` are raw addresses or None; pitches in elements; ``max_gap`` -1: none;
+        ``stage_bytes`` None: the library's default.'''
+        spec = GapfillSpec()
+        spec.n, spec.slabs, spec.nfields = int(n), int(slabs), len(fields)
+        spec.out_type, spec.max_gap = int(out_type), int(max_gap)
+        for f in range(min(len(fields), 3)):
+            spec.scale[f] = float(scale[f])
+        spec.in_pitch, spec.qc_pitch = int(in_pitch), int(qc_pitch)
+        spec.out_pitch, spec.source_pitch = int(out_pitch), int(source_pitch)
+        self.check(self.lib.mod16_gapfill_u8(
+            self.handle, C.byref(spec), ptr_array(list(fields)), qc, good,
+            ptr_array(list(fallback)) if fallback is not None else None, ptr_array(list(out)), source,
+            int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
 
 
 class Ensemble:

@@ -26,7 +26,8 @@ enum HostKind {
 // and reaches the kernel as NULL.
 // An array may consist of several ROWS of n pixels each (the time slabs of a composite's drivers, the
 // periods of its outputs: composite.hip): `pitch` host elements apart, and in the slab back to back
-// (`row` bytes apart = HostTile::row_bytes, no stagger between them: the stagger separates ARRAYS).
+// (`row` bytes apart = HostTile::row_bytes, no stagger between them: the stagger separates ARRAYS;
+// the rows of a byte array HostTile::byte_row_bytes apart: gapfill.hip).
 // Every array of the other families has one row: their offsets are what they were.
 struct HostPlan {
     struct Array { void* host; void* dev; int elem; int kind; int rows; int64_t pitch; int first; };
@@ -66,6 +67,7 @@ struct HostTile {
     void* dev[kHostMaxArrays];
     int64_t m, off;      // pixels of the tile, its first pixel in the call
     size_t row_bytes;    // between two rows of a T-sized array with several (host_tiled)
+    size_t byte_row_bytes;   // ... of a byte array
     hipStream_t st;
     double* diag;        // host_tiled with tile_diag: where this tile's diagnostics vector goes (device)
 };
@@ -128,6 +130,7 @@ static int host_small(mod16_ctx* ctx, const HostPlan& p, int64_t n, bool pad, La
     t.m = npad;
     t.off = 0;
     t.row_bytes = per_arr;
+    t.byte_row_bytes = cap;
     t.st = ctx->streams[0];
     t.diag = nullptr;
     for (int i = 0; i < p.count; ++i) {
@@ -195,14 +198,16 @@ static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slot
         t.m = std::min(tile, n - off);
         t.off = off;
         t.row_bytes = row;
+        t.byte_row_bytes = per_b;
         t.st = ctx->streams[slot];
         t.diag = tile_diag ? ctx->hdiag_dev.as<double>() + (size_t)slot * kDiag : nullptr;
         for (int i = 0; i < p.count; ++i) {
             const HostPlan::Array& x = p.a[i];
             t.dev[i] = p.where(i, base + p.offset(i, per_arr, per_b, row), dscal);
+            const size_t step = i < p.nwide ? row : per_b;      // between the rows of this array in the slab
             if (x.host && x.kind == kIn)
                 for (int r = 0; r < x.rows; ++r)
-                    HIPCHK(ctx, hipMemcpyAsync(static_cast<char*>(t.dev[i]) + row * r,
+                    HIPCHK(ctx, hipMemcpyAsync(static_cast<char*>(t.dev[i]) + step * r,
                                                static_cast<const char*>(x.host) + x.elem * (x.pitch * r + off), x.elem * t.m,
                                                hipMemcpyHostToDevice, t.st));
         }
@@ -214,10 +219,11 @@ static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slot
         }
         for (int i = 0; i < p.count; ++i) {
             const HostPlan::Array& x = p.a[i];
+            const size_t step = i < p.nwide ? row : per_b;
             if (x.host && x.kind == kOut)
                 for (int r = 0; r < x.rows; ++r)
                     HIPCHK(ctx, hipMemcpyAsync(static_cast<char*>(x.host) + x.elem * (x.pitch * r + off),
-                                               static_cast<const char*>(t.dev[i]) + row * r, x.elem * t.m,
+                                               static_cast<const char*>(t.dev[i]) + step * r, x.elem * t.m,
                                                hipMemcpyDeviceToHost, t.st));
         }
         if (t.diag) HIPCHK(ctx, hipMemcpyAsync(tile_diag + off / tile * kDiag, t.diag, sizeof(double) * kDiag, hipMemcpyDeviceToHost, t.st));

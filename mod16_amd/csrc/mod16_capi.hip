@@ -13,3 +13,4 @@
 #include "capi/mcmc.hip"
 #include "capi/ensemble.hip"
 #include "capi/composite.hip"
+#include "capi/gapfill.hip"

@@ -526,6 +526,118 @@ class RasterEngine(object):
                                stream=self._stream())
         return out
 
+    def gapfill(self, fields, qc=None, good=None, max_gap=None, fallback=None, dtype=None, scale=None,
+                source=False, out=None):
+        '''Enqueue the gap-filling kernel on the current stream: the annual profile of every pixel
+        of one to three device-resident byte series (MOD15A2H fPAR / LAI codes) filled in one launch
+        (``mod16_gapfill_u8``; the definition is ``mod16_amd.gapfill``) -- unreliable slabs are
+        interpolated between the nearest reliable ones, held at the ends of the series, and beyond
+        ``max_gap`` take ``fallback`` or stay unfilled.
+
+        ``fields`` is one ``(S, n)`` uint8 tensor or a tuple of up to three, ``qc`` an optional one
+        shared by them, each with unit stride in pixels and any stride >= n in time (views of a
+        larger buffer are fine, at any byte offset); ``good`` a 256-entry table of acceptable QC bytes
+        (default ``mod16_amd.gapfill.default_good()``); ``fallback`` one ``(n,)`` uint8 tensor (or
+        None) per field. ``dtype``: ``'uint8'`` (default: codes, 255 where unfilled -- a row goes into
+        ``run_raw``), ``'float32'`` / ``'float64'``, or ``'engine'``: the engine's type, where
+        ``scale`` defaults to 0.01 and 0.1 for two fields (fPAR, LAI: fractions and m2 m-2, NaN where
+        unfilled -- what ``composite(..., every={'fpar': 8, 'lai': 8})`` takes).
+
+        Returns the filled tensor (a tuple for a tuple of fields), and with ``source`` a pair
+        ``(filled, source)``: per field the ``(S, n)`` bytes 0 observed, 1 interpolated, 2 held, 3
+        fallback, 4 unfilled. ``out`` may give the filled tensors (and, with ``source``, one ``(fields,
+        S, n)`` uint8 tensor behind them); no output may overlap an input. Asynchronous, like
+        ``composite``.'''
+        from . import gapfill as _g
+        torch = _torch()
+        single = isinstance(fields, torch.Tensor)
+        flds = [fields] if single else list(fields)
+        if fallback is not None and isinstance(fallback, torch.Tensor):
+            fallback = [fallback]
+        engine = dtype == 'engine'
+        if dtype is None:
+            dtype = 'uint8'
+        elif engine:
+            dtype = self.np_dtype.name
+            if scale is None and len(flds) == 2:
+                scale = (0.01, 0.1)
+        for what, t in [('fields[%d]' % k, f) for k, f in enumerate(flds)] + [('qc', qc)] + \
+                [('fallback[%d]' % k, f) for k, f in enumerate(fallback or [])]:
+            if t is None and not what.startswith('fields'):
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or t.dtype != torch.uint8:
+                raise TypeError('%s must be a uint8 tensor on cuda:%d' % (what, self.device))
+        S, shape, table, mg, name, scales = _g.check_series(
+            [tuple(f.shape) for f in flds], None if qc is None else tuple(qc.shape), good, max_gap,
+            None if fallback is None else [None if f is None else tuple(f.shape) for f in fallback], dtype, scale)
+        if len(shape) != 1:
+            raise ValueError('fields must be (S, n) tensors, got %r' % (tuple(flds[0].shape),))
+        n = shape[0]
+        tdtype = {'uint8': torch.uint8, 'float32': torch.float32, 'float64': torch.float64}[name]
+
+        def pitch_of(t, what, rows):
+            if n > 1 and t.stride(-1) != 1:
+                raise ValueError('%s must have unit stride in pixels' % what)
+            row = t.stride(-2) if rows > 1 else max(n, 1)
+            if row < n:
+                raise ValueError('%s: the stride in time must be at least n' % what)
+            return row
+        pitches = set(pitch_of(f, 'fields[%d]' % k, S) for k, f in enumerate(flds))
+        if len(pitches) != 1:
+            raise ValueError('the fields must share one stride in time')
+        in_pitch = pitches.pop()
+        qc_pitch = pitch_of(qc, 'qc', S) if qc is not None else n
+        for k, f in enumerate(fallback or []):
+            if f is not None and n > 1 and f.stride(0) != 1:
+                raise ValueError('fallback[%d] must have unit stride' % k)
+        want = len(flds) + (1 if source else 0)
+        if out is None:
+            outs = [torch.empty((S, n), dtype=tdtype, device=self._dev()) for _ in flds]
+            src = torch.empty((len(flds), S, n), dtype=torch.uint8, device=self._dev()) if source else None
+        else:
+            outs = [out] if isinstance(out, torch.Tensor) else list(out)
+            if len(outs) != want:
+                raise ValueError('out must hold %d tensors' % want)
+            src = outs.pop() if source else None
+        for k, o in enumerate(outs):
+            if not isinstance(o, torch.Tensor) or not o.is_cuda or o.device.index != self.device or o.dtype != tdtype:
+                raise TypeError('out[%d] must be a %s tensor on cuda:%d' % (k, tdtype, self.device))
+            if tuple(o.shape) != (S, n):
+                raise ValueError('out[%d] must have shape (%d, %d)' % (k, S, n))
+        opitches = set(pitch_of(o, 'out[%d]' % k, S) for k, o in enumerate(outs))
+        if len(opitches) != 1:
+            raise ValueError('the out tensors must share one distance between rows')
+        out_pitch = opitches.pop()
+        src_pitch = n
+        if src is not None:
+            if not isinstance(src, torch.Tensor) or not src.is_cuda or src.device.index != self.device or \
+                    src.dtype != torch.uint8 or tuple(src.shape) != (len(flds), S, n):
+                raise TypeError('the source tensor must be uint8 of shape (%d, %d, %d) on cuda:%d'
+                                % (len(flds), S, n, self.device))
+            src_pitch = pitch_of(src, 'source', S)
+            if len(flds) > 1 and src.stride(0) != S * src_pitch:
+                raise ValueError('the source tensor must hold its fields back to back')
+        if n:
+            good8 = None
+            if good is not None:       # (the default table is the library's own)
+                good8 = torch.from_numpy(np.ascontiguousarray(table, np.uint8)).to(self._dev())
+            try:
+                self.ctx.gapfill(
+                    _g.OUT_TYPES[name], n, S, [f.data_ptr() for f in flds], None if qc is None else qc.data_ptr(),
+                    None if good8 is None else good8.data_ptr(),
+                    None if fallback is None else [None if f is None else f.data_ptr() for f in fallback],
+                    [o.data_ptr() for o in outs], None if src is None else src.data_ptr(), in_pitch, qc_pitch,
+                    out_pitch, src_pitch, max_gap=mg, scale=scales + [1.0] * (3 - len(scales)),
+                    where=_lib.DEVICE, stream=self._stream())
+            except _lib.Mod16Error as e:
+                if e.status == _lib.ERR_ARG and 'overlaps' in str(e):
+                    raise ValueError(str(e))
+                raise
+        filled = outs[0] if single else tuple(outs)
+        if not source:
+            return filled
+        return filled, (src[0] if single else tuple(src[f] for f in range(len(flds))))
+
     def ensemble(self, tables):
         '''The members of an ensemble forward run on this engine's device: ``tables`` is a (D, 13,
         11) array or a sequence of D ``restore_bplut`` dicts (``mod16_amd.calibration.ensemble_tables``

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 13
+#define MOD16_ABI_VERSION 14
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -1146,6 +1146,93 @@ typedef struct mod16_gapfill_spec {
 MOD16_API int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, const uint8_t* const* fields,
                                const uint8_t* qc, const uint8_t* good256, const uint8_t* const* fallback,
                                void* const* out, uint8_t* source, int where, void* stream, size_t stage_bytes);
+
+/*
+ * Downscaled forward run (ABI 14; mod16_amd.evapotranspiration_downscaled,
+ * RasterEngine.downscale_grid): ET day and night for a contiguous range of pixels of a rows x cols
+ * fine raster, each of the 14 drivers a scalar, a fine array or a COARSE coarse_rows x coarse_cols
+ * array (reanalysis meteorology) interpolated per pixel inside the kernel -- the interpolated values
+ * never touch memory. The definition is the numpy statement mod16_amd/downscale.py (corner_tables,
+ * interpolate):
+ *
+ *   geometry    row_pos[rows], col_pos[cols] (HOST pointers, float64): the position of every fine row
+ *               / column in units of coarse cells, cell centres at the integers. Rectilinear grids
+ *               only. Per axis and entry, two cells and two weights:
+ *                 held edge (rows; columns with wrap_cols = 0): p = min(max(pos, 0), size - 1),
+ *                   i0 = floor(p), f = p - i0, i1 = min(i0 + 1, size - 1);
+ *                 wrap_cols = 1 (the longitude axis of a global grid): p = pos - floor(pos / size) size,
+ *                   0 where that is not in [0, size); i0 = floor(p), f = p - i0, i1 = (i0 + 1) % size;
+ *                 w1 (the far cell's weight; w0 = 1.0 - w1): MOD16_DOWNSCALE_NEAREST 1.0 where
+ *                   f >= 0.5, else 0.0; _BILINEAR f; _COS4 b / (a + b), a = cos(pi/2 f)^4,
+ *                   b = cos(pi/2 (1 - f))^4, and 0.0 where f == 0 -- a separable form of the cosine-to-the-fourth distance
+ *                   weighting, not the great-circle form of the operational algorithm.
+ *               mod16_downscale_create computes the tables on the host (cos and pow of the C
+ *               library); mod16_downscale_create_tables takes tables the caller computed (the Python
+ *               layer passes numpy's, so that device results carry the bits of the numpy definition
+ *               whatever the two cosines round to) and checks them: indices inside the coarse grid,
+ *               finite weights. The handle owns device copies of the tables.
+ *   value       corners in the order (row i0, col i0), (i0, i1), (i1, i0), (i1, i1); a corner's weight
+ *               is wr * wc, its term w * v where w != 0 and +0.0 where w == 0 (a corner without weight
+ *               cannot poison a pixel), the value ((t00 + t01) + t10) + t11 in float64, left to right,
+ *               no contraction. A NaN corner with weight gives NaN; nothing is renormalised.
+ *   run         kinds[k]: 0 a scalar (one value), 1 a fine array, 2 a coarse array. Fine arrays, cls
+ *               and the outputs are addressed from the range's first pixel (element 0 is pixel
+ *               first_pixel of the raster, row-major); coarse arrays are whole
+ *               [coarse_rows][coarse_pitch] planes, coarse_pitch >= coarse_cols in elements. The
+ *               pixel's ET is what mod16_et_* gives on the interpolated drivers, bit for bit, with the
+ *               same flags. float32: inputs widened, interpolation and arithmetic in float64, one
+ *               rounding on store.
+ *   flags       MOD16_MATH_FAST (0) or MOD16_MATH_EXACT; the fast instance tests every interpolated
+ *               pixel against the domain of its arithmetic and a second kernel behind it recomputes
+ *               the flagged pixels in the reference's operation order. No atomics on results, no
+ *               workspace: two calls give the same bits.
+ *   fields      mod16_downscale_fields_*: out[f * out_pitch + i] = the interpolated field f (1 <= F
+ *               <= 16 coarse planes) at pixel first_pixel + i, rounded once to T; [n, out_pitch) of a
+ *               row is not touched.
+ *   where       MOD16_DEVICE: device pointers, asynchronous on `stream` (mod16_check_status reports a
+ *               class code >= 13). MOD16_HOST: host pointers; the coarse planes are uploaded once per
+ *               call, the fine arrays, class raster and outputs are staged tile by tile
+ *               (mod16_host_tile_pixels() pixels). The result does not depend on the tiling.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_downscale_create: ...",
+ *            "mod16_et_downscaled: ...", "mod16_downscale_fields: ...")
+ *               a NULL argument; rows, cols, coarse_rows, coarse_cols outside 1 ... 2^30; wrap_cols
+ *               other than 0 or 1; an unknown method; a position that is not finite; a table index
+ *               outside the coarse grid or a weight that is not finite; a kind other than 0, 1, 2;
+ *               "coarse_pitch must be at least coarse_cols"; "the pixel range [first_pixel,
+ *               first_pixel + n) leaves the raster"; "out_pitch must be at least n"; "F must be between
+ *               1 and 16"; a grid of another device; an unknown flag; "MOD16_MATH_MIXED is not
+ *               available for the downscaled run" and "MOD16_DOMAIN_TRUSTED is not available for the
+ *               downscaled run". n = 0 is MOD16_OK.
+ */
+enum mod16_downscale_method { MOD16_DOWNSCALE_NEAREST = 0, MOD16_DOWNSCALE_BILINEAR = 1, MOD16_DOWNSCALE_COS4 = 2 };
+typedef struct mod16_downscale_spec {
+    int64_t rows, cols;                          /* the fine raster */
+    int64_t coarse_rows, coarse_cols;            /* the coarse grid */
+    int32_t wrap_cols;                           /* 1: the column axis of the coarse grid is periodic */
+    int32_t method;                              /* enum mod16_downscale_method */
+} mod16_downscale_spec;
+typedef struct mod16_downscale mod16_downscale;
+MOD16_API int mod16_downscale_create(mod16_ctx* ctx, const mod16_downscale_spec* spec, const double* row_pos,
+                                     const double* col_pos, mod16_downscale** grid);
+MOD16_API int mod16_downscale_create_tables(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int32_t* row_i0,
+                                            const int32_t* row_i1, const double* row_w0, const double* row_w1,
+                                            const int32_t* col_i0, const int32_t* col_i1, const double* col_w0,
+                                            const double* col_w1, mod16_downscale** grid);
+MOD16_API int mod16_downscale_destroy(mod16_downscale* grid);
+MOD16_API int mod16_et_downscaled_f64(mod16_ctx* ctx, const mod16_downscale* grid, const uint8_t* cls,
+                                      const double* const* drivers, const int32_t* kinds, int64_t coarse_pitch,
+                                      int64_t first_pixel, int64_t n, double* out_day, double* out_night,
+                                      unsigned flags, int where, void* stream);
+MOD16_API int mod16_et_downscaled_f32(mod16_ctx* ctx, const mod16_downscale* grid, const uint8_t* cls,
+                                      const float* const* drivers, const int32_t* kinds, int64_t coarse_pitch,
+                                      int64_t first_pixel, int64_t n, float* out_day, float* out_night,
+                                      unsigned flags, int where, void* stream);
+MOD16_API int mod16_downscale_fields_f64(mod16_ctx* ctx, const mod16_downscale* grid, const double* const* fields,
+                                         int nfields, int64_t coarse_pitch, int64_t first_pixel, int64_t n,
+                                         double* out, int64_t out_pitch, int where, void* stream);
+MOD16_API int mod16_downscale_fields_f32(mod16_ctx* ctx, const mod16_downscale* grid, const float* const* fields,
+                                         int nfields, int64_t coarse_pitch, int64_t first_pixel, int64_t n,
+                                         float* out, int64_t out_pitch, int where, void* stream);
 
 #ifdef __cplusplus
 }

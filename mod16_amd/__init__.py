@@ -36,6 +36,7 @@ import numpy as np
 import threading as _threading
 
 from . import _lib
+from .downscale import MET_DRIVERS as _MET_DRIVERS
 
 # Module constants, same names and values as reference mod16/__init__.py:106-118
 PFT_VALID = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12)
@@ -1536,6 +1537,133 @@ def evapotranspiration_composite(
         ctx.composite(dtype, n, K, L, cls.ctypes.data, ptrs, pstride, tstride, divisor, et, pt, c_et, c_pt, n,
                       min_valid=mv, rescale=rescale, flags=math, where=_lib.HOST, stage_bytes=stage_bytes)
     return (CompositeETPET if pet else CompositeET)(*outs)
+
+
+def evapotranspiration_downscaled(
+        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, row_pos, col_pos, wrap=False, method='bilinear',
+        coarse=_MET_DRIVERS, beta=None, math=_lib.MATH_FAST, device=0, out=None, devices=None):
+    r'''
+    (Extension.) Forward run over a multi-class raster whose reanalysis drivers stay on their own
+    coarse grid: what ``evapotranspiration_raster`` returns on drivers blown up to the fine grid
+    with ``mod16_amd.downscale.interpolate``, bit for bit, without those fine arrays ever existing --
+    the kernel interpolates the four surrounding cells per pixel (``mod16_et_downscaled_*``). The
+    definition is ``mod16_amd.downscale`` (``corner_tables``, ``interpolate``).
+
+    Parameters
+    ----------
+    bplut, beta
+        as for ``evapotranspiration_raster``
+    cls : numpy.ndarray
+        ``(R, C)`` class raster: the fine grid
+    the 14 drivers
+        a driver named in ``coarse`` is an ``(H, W)`` array on the coarse grid, one grid for all of
+        them; any other is an ``(R, C)`` array or a scalar
+    row_pos, col_pos : numpy.ndarray
+        ``(R,)`` and ``(C,)``: the position of every fine row and column in units of coarse cells,
+        cell centres at the integers (``mod16_amd.downscale.positions`` for regular grids)
+    wrap : bool
+        True where the coarse column axis is periodic (the longitude axis of a global grid);
+        otherwise, and always for the rows, the edge value is held outside the grid
+    method : str
+        ``'nearest'``, ``'bilinear'`` (default) or ``'cos4'`` (a separable cosine-to-the-fourth
+        weighting; see ``mod16_amd.downscale.corner_tables`` for what it is not)
+    coarse : sequence of str
+        the names of the coarse drivers (Default: ``mod16_amd.downscale.MET_DRIVERS``, the eleven
+        reanalysis fields; albedo, fPAR and LAI are fine-grid data)
+    math : int
+        ``MATH_FAST`` (default) or ``MATH_EXACT``
+    out : sequence of numpy.ndarray
+        (Optional) the two ``(R, C)`` arrays to write into
+    devices : sequence of int
+        (Optional) several GPUs behind this call: ranges of whole rows dealt over the listed devices
+        (``mod16_amd.multi``), every device with its own copy of the coarse arrays; the same bits
+        whatever the list
+
+    Returns
+    -------
+    tuple
+        ``(day, night)`` [kg m-2 s-1], each ``(R, C)``; float32 only if every array input is float32
+        (interpolated and computed in float64, rounded once). A NaN coarse cell gives NaN at the
+        pixels where it has weight; a class code >= 13 raises IndexError.
+    '''
+    from . import downscale as _d, multi
+    from .utils import bplut_table
+    arrays = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+              temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+              pressure, fpar, lai]
+    devs = multi.device_list(devices)
+    names = _d.check_coarse(coarse)
+    cls = np.asarray(cls)
+    if cls.ndim != 2:
+        raise ValueError('cls must be an (R, C) raster, got shape %r' % (cls.shape,))
+    shape = cls.shape
+    coarse_shape = (1, 1)
+    for name, v in zip(_d.DRIVER_NAMES, arrays):
+        if name in names:
+            coarse_shape = _shape(v)
+            break
+    if len(coarse_shape) != 2:
+        raise ValueError('a coarse driver must be an (H, W) array, got shape %r' % (coarse_shape,))
+    if int(math) & ~_lib.MATH_EXACT:
+        raise ValueError('math must be MATH_FAST or MATH_EXACT for the downscaled run')
+    shapes = [_shape(v) if name in names or np.size(v) != 1 else () for name, v in zip(_d.DRIVER_NAMES, arrays)]
+    kinds, _, n = _d.check_call(shape, coarse_shape, shapes, coarse=names, method=method, cls_size=cls.size,
+                                row_pos=row_pos, col_pos=col_pos)
+    row_tables = _d.corner_tables(row_pos, coarse_shape[0], False, method)
+    col_tables = _d.corner_tables(col_pos, coarse_shape[1], bool(wrap), method)
+    dtype = _result_dtype(arrays)
+    if cls.dtype != np.uint8:
+        if cls.size and (cls.min() < 0 or cls.max() > 255):
+            raise IndexError('class code outside [0, 255]')
+        cls = cls.astype(np.uint8)
+    cls = np.ascontiguousarray(cls)
+    if out is not None:
+        outs = list(out)
+        if len(outs) != 2:
+            raise ValueError('out must hold 2 arrays')
+        for o in outs:
+            if not (isinstance(o, np.ndarray) and o.shape == shape and o.dtype == dtype
+                    and o.flags.c_contiguous and o.flags.writeable):
+                raise ValueError('out arrays must be writeable C-contiguous %s arrays of shape %s' % (dtype, shape))
+    else:
+        outs = [_lib.pinned.empty(shape, dtype) for _ in range(2)]
+    if isinstance(bplut, dict):
+        table = bplut_table(bplut, beta=beta)
+    else:
+        table = np.array(bplut, np.float64)
+        if beta is not None:
+            fill = np.isnan(table[:, 10]) & ~np.isnan(table[:, 0])
+            table[fill, 10] = beta
+    keep, ptrs = [], []
+    for v, kind in zip(arrays, kinds):
+        a = np.array(v, dtype).reshape(1) if kind == _d.KIND_SCALAR else np.ascontiguousarray(v, dtype)
+        keep.append(a)
+        ptrs.append(a.ctypes.data)
+    esz = dtype.itemsize
+    optr = [o.ctypes.data for o in outs]
+
+    def part(ctx, off, m):
+        '''pixels [off, off + m) on the calling thread's context'''
+        ctx.set_bplut(table)
+        if m <= 0:
+            return
+        grid = _lib.Downscale(ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
+                              tables=(row_tables, col_tables))
+        try:
+            d = [p + off * esz if kind == _d.KIND_FINE else p for p, kind in zip(ptrs, kinds)]
+            grid.run(dtype, cls.ctypes.data + off, d, kinds, coarse_shape[1], off, m, optr[0] + off * esz,
+                     optr[1] + off * esz, flags=math, where=_lib.HOST)
+        finally:
+            grid.close()
+
+    if devs is None:
+        part(_lib.context(device), 0, n)
+    else:
+        cuts = multi.shards(n, len(devs), shape[1])         # whole rows per device
+        multi.run(devs, lambda i, ctx: part(ctx, *cuts[i]))
+    return (outs[0], outs[1])
 
 
 def gapfill_series(fields, qc=None, good=None, max_gap=None, fallback=None, dtype='uint8', scale=None,

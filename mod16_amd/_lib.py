@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -104,6 +104,20 @@ class GapfillSpec(C.Structure):
 
 
 GAPFILL_U8, GAPFILL_F32, GAPFILL_F64 = 0, 1, 2     # enum mod16_gapfill_out
+
+
+class DownscaleSpec(C.Structure):
+    '''``mod16_downscale_spec`` (include/mod16_hip.h): the fine raster, the coarse grid, whether its
+    column axis is periodic, the weighting method.'''
+    _fields_ = [('rows', C.c_int64), ('cols', C.c_int64), ('coarse_rows', C.c_int64), ('coarse_cols', C.c_int64),
+                ('wrap_cols', C.c_int32), ('method', C.c_int32)]
+
+
+_I32P = C.POINTER(C.c_int32)
+_DOWNSCALED_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I32P, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                    C.c_void_p, C.c_uint, C.c_int, C.c_void_p]
+_DOWNSCALE_FIELDS_ARGS = [C.c_void_p, C.c_void_p, _PP, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                          C.c_int64, C.c_int, C.c_void_p]
 
 # name -> (restype, argtypes); one entry per function declared in the header
 PROTOTYPES = {
@@ -291,6 +305,15 @@ PROTOTYPES = {
     'mod16_et_composite_f32': (C.c_int, _COMPOSITE_ARGS),
     'mod16_gapfill_u8': (C.c_int, [C.c_void_p, C.POINTER(GapfillSpec), _PP, C.c_void_p, C.c_void_p, _PP, _PP,
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    'mod16_downscale_create': (C.c_int, [C.c_void_p, C.POINTER(DownscaleSpec), C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_void_p)]),
+    'mod16_downscale_create_tables': (C.c_int, [C.c_void_p, C.POINTER(DownscaleSpec)] + [C.c_void_p] * 8 +
+                                      [C.POINTER(C.c_void_p)]),
+    'mod16_downscale_destroy': (C.c_int, [C.c_void_p]),
+    'mod16_et_downscaled_f64': (C.c_int, _DOWNSCALED_ARGS),
+    'mod16_et_downscaled_f32': (C.c_int, _DOWNSCALED_ARGS),
+    'mod16_downscale_fields_f64': (C.c_int, _DOWNSCALE_FIELDS_ARGS),
+    'mod16_downscale_fields_f32': (C.c_int, _DOWNSCALE_FIELDS_ARGS),
 }
 
 _lib = None
@@ -585,6 +608,68 @@ class Ensemble:
     def close(self):
         if getattr(self, 'handle', None) and self.handle.value:
             self.ctx.lib.mod16_ensemble_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Downscale:
+    '''The geometry of a fine raster over a coarse grid on a context's device (``mod16_downscale``):
+    the corner tables of ``mod16_amd.downscale.corner_tables`` for both axes, computed here in numpy
+    and handed to ``mod16_downscale_create_tables``, so that the device's interpolation carries the
+    bits of the numpy definition.'''
+
+    def __init__(self, ctx, shape, coarse_shape, row_pos, col_pos, wrap=False, method='bilinear', tables=None):
+        from . import downscale as _d
+        _d.check_call(shape, coarse_shape, [()] * N_DRIVERS, coarse=(), method=method, row_pos=row_pos,
+                      col_pos=col_pos)
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.coarse_shape = (int(coarse_shape[0]), int(coarse_shape[1]))
+        self.wrap, self.method = bool(wrap), method
+        if tables is not None:          # (another context's grid of the same call: computed once)
+            self.row_tables, self.col_tables = tables
+        else:
+            self.row_tables = _d.corner_tables(row_pos, self.coarse_shape[0], False, method)
+            self.col_tables = _d.corner_tables(col_pos, self.coarse_shape[1], self.wrap, method)
+        rt = _d.check_tables(self.row_tables, self.shape[0], self.coarse_shape[0], 'row')
+        ct = _d.check_tables(self.col_tables, self.shape[1], self.coarse_shape[1], 'column')
+        spec = DownscaleSpec(self.shape[0], self.shape[1], self.coarse_shape[0], self.coarse_shape[1],
+                             1 if self.wrap else 0, _d.method_code(method))
+        self.ctx = ctx                  # keeps the context alive as long as its grid
+        self.handle = C.c_void_p()
+        ctx.check(ctx.lib.mod16_downscale_create_tables(
+            ctx.handle, C.byref(spec), *([t.ctypes.data for t in rt] + [t.ctypes.data for t in ct]),
+            C.byref(self.handle)))
+
+    def _open(self):
+        if not self.handle.value:
+            raise ValueError('the downscale grid has been closed')
+
+    def run(self, dtype, cls, drivers, kinds, coarse_pitch, first_pixel, n, out_day, out_night,
+            flags=MATH_FAST, where=HOST, stream=None):
+        '''Thin wrapper of mod16_et_downscaled_f64 / _f32; every array argument is a raw address.'''
+        self._open()
+        fn = self.ctx.lib.mod16_et_downscaled_f32 if np.dtype(dtype) == np.float32 \
+            else self.ctx.lib.mod16_et_downscaled_f64
+        self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers),
+                          _array_type(C.c_int32, len(kinds))(*[int(k) for k in kinds]), int(coarse_pitch),
+                          int(first_pixel), int(n), out_day, out_night, int(flags), int(where), stream))
+
+    def fields(self, dtype, fields, coarse_pitch, first_pixel, n, out, out_pitch, where=HOST, stream=None):
+        '''Thin wrapper of mod16_downscale_fields_f64 / _f32 (raw addresses; 1 to 16 fields).'''
+        self._open()
+        fn = self.ctx.lib.mod16_downscale_fields_f32 if np.dtype(dtype) == np.float32 \
+            else self.ctx.lib.mod16_downscale_fields_f64
+        self.ctx.check(fn(self.ctx.handle, self.handle, ptr_array(list(fields)), len(fields), int(coarse_pitch),
+                          int(first_pixel), int(n), out, int(out_pitch), int(where), stream))
+
+    def close(self):
+        if getattr(self, 'handle', None) and self.handle.value:
+            self.ctx.lib.mod16_downscale_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -14,3 +14,4 @@
 #include "capi/ensemble.hip"
 #include "capi/composite.hip"
 #include "capi/gapfill.hip"
+#include "capi/downscale.hip"

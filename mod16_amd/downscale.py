@@ -1,0 +1,230 @@
+'''
+Coarse-grid meteorology interpolated inside the forward run: the definition, in numpy, of what
+``mod16_et_downscaled_*`` and ``mod16_downscale_fields_*`` compute (``RasterEngine.downscale_grid``,
+``mod16_amd.evapotranspiration_downscaled``), and the argument checks of those calls. Host only:
+nothing here touches the library or a device; the kernels (``csrc/mod16_downscale.hpp``) follow
+``interpolate`` operation for operation.
+
+A fine raster of ``R x C`` pixels lies over a coarse grid of ``H x W`` cells. The geometry is two
+float64 tables, ``row_pos[R]`` and ``col_pos[C]``: the position of every fine row and column in
+units of coarse cells, cell centres at the integers (``positions`` builds them for regular grids).
+Any rectilinear pair of grids is covered; grids whose column mapping depends on the row (sinusoidal
+tiles) are not. Per axis ``corner_tables`` turns the positions into two cell indices and two weights;
+``interpolate`` forms a pixel's value from the four surrounding cells. All transcendental work
+happens in ``corner_tables``, on the host: the device multiplies and adds only, and its result has
+the bits of ``interpolate``.
+'''
+import numpy as np
+
+#: the 14 drivers in argument order
+DRIVER_NAMES = (
+    'lw_net_day', 'lw_net_night', 'sw_rad_day', 'sw_rad_night', 'sw_albedo',
+    'temp_day', 'temp_night', 'temp_annual', 'tmin', 'vpd_day', 'vpd_night',
+    'pressure', 'fpar', 'lai')
+#: the eleven reanalysis drivers, in driver order: what is coarse unless the caller says otherwise
+#: (albedo, fPAR and LAI are fine-grid data)
+MET_DRIVERS = (
+    'lw_net_day', 'lw_net_night', 'sw_rad_day', 'sw_rad_night',
+    'temp_day', 'temp_night', 'temp_annual', 'tmin', 'vpd_day', 'vpd_night', 'pressure')
+METHODS = ('nearest', 'bilinear', 'cos4')
+#: a scalar, an array on the fine grid, an array on the coarse grid (the ``kinds`` of the C ABI)
+KIND_SCALAR, KIND_FINE, KIND_COARSE = 0, 1, 2
+MAX_EXTENT = 2 ** 30        # rows, columns, coarse rows, coarse columns: the library's limit
+
+
+def positions(fine_first, fine_step, count, coarse_first, coarse_step):
+    '''The position table of one axis of two regular grids: fine coordinate ``fine_first + k *
+    fine_step`` (``k = 0 ... count - 1``) in units of coarse cells, ``(fine_first + k * fine_step -
+    coarse_first) / coarse_step``, where ``coarse_first`` is the coordinate of the centre of coarse
+    cell 0 and ``coarse_step`` the distance between two centres (negative for a north-to-south
+    latitude axis).'''
+    count = int(count)
+    if count < 0:
+        raise ValueError('count must not be negative, got %d' % count)
+    if not np.isfinite(coarse_step) or coarse_step == 0:
+        raise ValueError('coarse_step must be finite and not zero, got %r' % (coarse_step,))
+    k = np.arange(count, dtype=np.float64)
+    return (np.float64(fine_first) + k * np.float64(fine_step) - np.float64(coarse_first)) / np.float64(coarse_step)
+
+
+def method_code(method):
+    '''``'nearest'``, ``'bilinear'``, ``'cos4'`` -> 0, 1, 2 (``enum mod16_downscale_method``).'''
+    if method not in METHODS:
+        raise ValueError('method must be one of %s, got %r' % (', '.join(repr(m) for m in METHODS), method))
+    return METHODS.index(method)
+
+
+def corner_tables(pos, size, wrap=False, method='bilinear'):
+    '''One axis: positions in units of coarse cells -> ``(i0, i1, w0, w1)``, the near and the far
+    cell (int32) and their weights (float64, ``w0 = 1.0 - w1``), for a coarse axis of ``size`` cells.
+
+    Without ``wrap`` the edge value is held outside the grid: ``p = min(max(pos, 0), size - 1)``,
+    ``i0 = floor(p)``, ``f = p - i0``, ``i1 = min(i0 + 1, size - 1)``. With ``wrap`` (the longitude
+    axis of a global grid) ``p = pos - floor(pos / size) * size``, 0 where that rounds up to
+    ``size``; ``i0 = floor(p)``, ``f = p - i0``, ``i1 = (i0 + 1) % size``.
+
+    The far cell's weight ``w1``: ``'nearest'`` 1.0 where ``f >= 0.5``, else 0.0; ``'bilinear'``
+    ``f``; ``'cos4'`` ``b / (a + b)`` with ``a = cos(pi/2 * f)**4`` and ``b = cos(pi/2 * (1 - f))**4``, and
+    exactly 0.0 where ``f == 0``: the float64 cosine of pi/2 is 6e-17, whose fourth power would give the
+    far cell a weight of 1e-65 -- enough for its NaN to reach a pixel that sits on a cell centre.
+
+    ``'cos4'`` is a SEPARABLE form of the cosine-to-the-fourth distance weighting that the
+    operational MOD16 algorithm applies to the four reanalysis cells around a pixel: a weight per
+    axis, multiplied. The operational weighting uses the great-circle distance to each of the four
+    cells, which does not factor into a row and a column term; this is not that, and no equality
+    with the operational product's interpolation is claimed.
+
+    ValueError for a non-finite position, ``size < 1`` or a ``pos`` that is not one-dimensional.'''
+    code = method_code(method)
+    size = int(size)
+    if size < 1:
+        raise ValueError('size must be at least 1, got %d' % size)
+    if size > MAX_EXTENT:
+        raise ValueError('size must be at most %d, got %d' % (MAX_EXTENT, size))
+    pos = np.asarray(pos, np.float64)
+    if pos.ndim != 1:
+        raise ValueError('a position table must be one-dimensional, got shape %r' % (pos.shape,))
+    if not np.all(np.isfinite(pos)):
+        raise ValueError('a position table holds a value that is not finite')
+    with np.errstate(all='ignore'):
+        if wrap:
+            p = pos - np.floor(pos / np.float64(size)) * np.float64(size)
+            p = np.where((p >= size) | (p < 0), 0.0, p)
+            i0 = np.floor(p)
+            f = p - i0
+            i0 = i0.astype(np.int32)
+            i1 = ((i0.astype(np.int64) + 1) % size).astype(np.int32)
+        else:
+            p = np.minimum(np.maximum(pos, 0.0), np.float64(size - 1))
+            i0 = np.floor(p)
+            f = p - i0
+            i0 = i0.astype(np.int32)
+            i1 = np.minimum(i0.astype(np.int64) + 1, size - 1).astype(np.int32)
+        if code == 0:
+            w1 = np.where(f >= 0.5, 1.0, 0.0)
+        elif code == 1:
+            w1 = f
+        else:
+            a = np.cos((np.pi / 2) * f) ** 4
+            b = np.cos((np.pi / 2) * (1.0 - f)) ** 4
+            w1 = np.where(f == 0.0, 0.0, b / (a + b))        # (cos(pi/2) is 6e-17 in float64, not 0)
+        w1 = np.asarray(w1, np.float64)
+        w0 = 1.0 - w1
+    return i0, i1, w0, w1
+
+
+def check_tables(tables, count, size, what):
+    '''``(i0, i1, w0, w1)`` of one axis as contiguous int32 / float64 arrays of ``count`` entries
+    whose indices lie in ``[0, size)`` and whose weights are finite; ValueError otherwise.'''
+    if len(tables) != 4:
+        raise ValueError('%s tables must be (i0, i1, w0, w1)' % what)
+    i0, i1 = (np.ascontiguousarray(t, np.int32) for t in tables[:2])
+    w0, w1 = (np.ascontiguousarray(t, np.float64) for t in tables[2:])
+    for t in (i0, i1, w0, w1):
+        if t.shape != (int(count),):
+            raise ValueError('a %s table has shape %r, expected (%d,)' % (what, t.shape, count))
+    for t in (i0, i1):
+        if t.size and (t.min() < 0 or t.max() >= size):
+            raise ValueError('a %s table holds an index outside [0, %d)' % (what, size))
+    if not (np.all(np.isfinite(w0)) and np.all(np.isfinite(w1))):
+        raise ValueError('a %s table holds a weight that is not finite' % what)
+    return i0, i1, w0, w1
+
+
+def interpolate(field, row_tables, col_tables):
+    '''A coarse ``(H, W)`` field at every pixel of the fine raster -> ``(R, C)`` float64. The field
+    is widened to float64 first. With the corners in the order (row i0, col i0), (i0, i1), (i1, i0),
+    (i1, i1), a corner's weight is ``wr * wc`` (one multiplication), its term ``w * v`` where ``w !=
+    0`` and ``+0.0`` where ``w == 0`` -- a corner without weight cannot poison a pixel with its NaN
+    or infinity -- and the value ``((t00 + t01) + t10) + t11``, left to right, no contraction. A NaN
+    in a corner with weight gives NaN; nothing is renormalised over the valid corners.'''
+    field = np.asarray(field)
+    if field.ndim != 2:
+        raise ValueError('a coarse field must be two-dimensional, got shape %r' % (field.shape,))
+    field = field.astype(np.float64)
+    H, W = field.shape
+    ri0, ri1, rw0, rw1 = check_tables(row_tables, len(row_tables[0]), H, 'row')
+    ci0, ci1, cw0, cw1 = check_tables(col_tables, len(col_tables[0]), W, 'column')
+    with np.errstate(all='ignore'):
+        def term(ri, ci, wr, wc):
+            w = wr[:, None] * wc[None, :]
+            v = field[ri[:, None], ci[None, :]]
+            return np.where(w != 0, w * v, 0.0)
+        t00 = term(ri0, ci0, rw0, cw0)
+        t01 = term(ri0, ci1, rw0, cw1)
+        t10 = term(ri1, ci0, rw1, cw0)
+        t11 = term(ri1, ci1, rw1, cw1)
+        return ((t00 + t01) + t10) + t11
+
+
+def check_coarse(coarse):
+    '''``coarse`` of a downscaled call -> the tuple of driver names it holds, in driver order;
+    ValueError for a name that is no driver or one named twice.'''
+    if isinstance(coarse, str):
+        raise ValueError('coarse must be a sequence of driver names, not a string')
+    names = list(coarse)
+    for name in names:
+        if name not in DRIVER_NAMES:
+            raise ValueError('coarse names %r, which is not one of %s' % (name, ', '.join(DRIVER_NAMES)))
+    if len(set(names)) != len(names):
+        raise ValueError('coarse names a driver twice')
+    return tuple(n for n in DRIVER_NAMES if n in names)
+
+
+def check_range(shape, first_pixel=0, n=None):
+    '''The pixel range ``[first_pixel, first_pixel + n)`` of an ``R x C`` raster -> ``(first, n)``
+    as ints (``n`` None: to the end); ValueError where it leaves the raster.'''
+    total = int(shape[0]) * int(shape[1])
+    first = int(first_pixel)
+    if first < 0 or first > total:
+        raise ValueError('first_pixel must be between 0 and %d, got %d' % (total, first))
+    count = total - first if n is None else int(n)
+    if count < 0 or first + count > total:
+        raise ValueError('the pixel range [%d, %d) leaves the raster of %d pixels' % (first, first + count, total))
+    return first, count
+
+
+def check_call(shape, coarse_shape, driver_shapes, coarse=MET_DRIVERS, first_pixel=0, n=None,
+               method='bilinear', cls_size=None, row_pos=None, col_pos=None):
+    '''The argument checks of every downscaled call, before any device work.
+
+    ``shape`` = ``(R, C)``, ``coarse_shape`` = ``(H, W)``; ``driver_shapes``: the shape of each of
+    the 14 drivers (``()`` for a scalar). A driver named in ``coarse`` must be ``(H, W)``; any other
+    is a scalar, the ``n`` pixels of the range as ``(n,)``, or -- for the whole raster -- ``(R, C)``.
+    ``cls_size``: the elements of the class raster, which must be ``n``. ``row_pos`` / ``col_pos``:
+    the position tables, which must hold ``R`` and ``C`` entries.
+
+    Returns ``(kinds, first, n)``: the 14 kinds (``KIND_SCALAR``, ``KIND_FINE``, ``KIND_COARSE``) and
+    the range as ints. ValueError otherwise.'''
+    method_code(method)
+    if len(shape) != 2 or len(coarse_shape) != 2:
+        raise ValueError('shape and coarse_shape must be (rows, columns)')
+    R, C = int(shape[0]), int(shape[1])
+    H, W = int(coarse_shape[0]), int(coarse_shape[1])
+    for v, what in ((R, 'rows'), (C, 'columns'), (H, 'coarse rows'), (W, 'coarse columns')):
+        if v < 1 or v > MAX_EXTENT:
+            raise ValueError('%s must be between 1 and %d, got %d' % (what, MAX_EXTENT, v))
+    for pos, count, what in ((row_pos, R, 'row_pos'), (col_pos, C, 'col_pos')):
+        if pos is not None and np.shape(pos) != (count,):
+            raise ValueError('%s has shape %r, expected (%d,)' % (what, np.shape(pos), count))
+    names = check_coarse(coarse)
+    first, count = check_range((R, C), first_pixel, n)
+    if len(driver_shapes) != len(DRIVER_NAMES):
+        raise ValueError('expected 14 drivers, got %d' % len(driver_shapes))
+    kinds = []
+    for name, sh in zip(DRIVER_NAMES, driver_shapes):
+        sh = tuple(int(x) for x in sh)
+        if name in names:
+            if sh != (H, W):
+                raise ValueError('%s is a coarse driver: expected shape %r, got %r' % (name, (H, W), sh))
+            kinds.append(KIND_COARSE)
+        elif sh == ():
+            kinds.append(KIND_SCALAR)
+        elif sh == (count,) or (sh == (R, C) and first == 0 and count == R * C):
+            kinds.append(KIND_FINE)
+        else:
+            raise ValueError('%s has shape %r: expected a scalar, the %d pixels of the range or the raster %r'
+                             % (name, sh, count, (R, C)))
+    if cls_size is not None and int(cls_size) != count:
+        raise ValueError('the class raster has %d elements, expected %d' % (cls_size, count))
+    return kinds, first, count

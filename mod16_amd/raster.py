@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .downscale import MET_DRIVERS
 
 #: algorithmic HBM bytes per pixel: 14 driver loads +
 #: 1 class byte + 2 stores
@@ -223,6 +224,123 @@ class EnsembleRun(object):
 
     def close(self):
         self._ens.close()
+
+
+class DownscaleGrid(object):
+    '''The geometry of an ``R x C`` fine raster over an ``H x W`` coarse grid resident on an engine's
+    device (``RasterEngine.downscale_grid``): the corner tables uploaded once, ``run`` (ET with coarse
+    drivers interpolated per pixel inside the kernel) and ``fields`` (the interpolated fields alone)
+    as often as there are days. The definition is ``mod16_amd.downscale``.'''
+
+    def __init__(self, engine, shape, coarse_shape, row_pos, col_pos, wrap=False, method='bilinear'):
+        self.engine = engine
+        self._grid = _lib.Downscale(engine.ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method)
+        self.shape, self.coarse_shape = self._grid.shape, self._grid.coarse_shape
+        self.row_tables, self.col_tables = self._grid.row_tables, self._grid.col_tables
+
+    def _coarse_tensor(self, t, what):
+        '''-> (address, row pitch in elements) of an (H, W) tensor with unit stride in columns'''
+        eng, torch = self.engine, _torch()
+        H, W = self.coarse_shape
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != eng.device or t.dtype != eng.dtype:
+            raise TypeError('%s must be a %s tensor on cuda:%d' % (what, eng.dtype, eng.device))
+        if tuple(t.shape) != (H, W):
+            raise ValueError('%s is a coarse array: expected shape %r, got %r' % (what, (H, W), tuple(t.shape)))
+        if W > 1 and t.stride(1) != 1:
+            raise ValueError('%s must have unit stride in columns' % what)
+        pitch = t.stride(0) if H > 1 else W
+        if pitch < W:
+            raise ValueError('%s: the distance between rows must be at least %d' % (what, W))
+        return t.data_ptr(), pitch
+
+    def run(self, cls, drivers, coarse=MET_DRIVERS, first_pixel=0, out_day=None, out_night=None):
+        '''Enqueue the downscaled forward run on the current stream: ET day and night for the
+        ``n = cls.numel()`` pixels ``[first_pixel, first_pixel + n)`` of the raster (row-major).
+        Each of the 14 ``drivers`` named in ``coarse`` (default ``mod16_amd.downscale.MET_DRIVERS``,
+        the eleven reanalysis fields) is an ``(H, W)`` tensor with unit stride in columns and any
+        row pitch >= W, the same for all of them; every other driver is a scalar or a tensor of
+        the ``n`` pixels of the range. Returns ``(day, night)`` (``out_day`` / ``out_night`` may give
+        them): what ``run`` returns on the drivers ``mod16_amd.downscale.interpolate`` materialises,
+        bit for bit. The engine's ``math`` must be ``MATH_FAST`` or ``MATH_EXACT``. Asynchronous:
+        call the engine's ``check()`` (or synchronise the stream) before trusting the data; a class
+        code >= 13 raises IndexError there.'''
+        from . import downscale as _d
+        eng, torch = self.engine, _torch()
+        if eng.math & ~_lib.MATH_EXACT:
+            raise ValueError('the downscaled run needs an engine with MATH_FAST or MATH_EXACT (no MATH_MIXED, not trusted)')
+        names = _d.check_coarse(coarse)
+        if len(drivers) != _lib.N_DRIVERS:
+            raise ValueError('expected 14 drivers')
+        n = cls.numel()
+        shapes = [tuple(d.shape) if isinstance(d, torch.Tensor) and (name in names or d.numel() != 1) else ()
+                  for name, d in zip(_d.DRIVER_NAMES, drivers)]
+        kinds, first, n = _d.check_call(self.shape, self.coarse_shape, shapes, coarse=names, first_pixel=first_pixel,
+                                        n=n, method=self._grid.method, cls_size=n)
+        cptr = eng._check_tensor(cls, torch.uint8, n, 'cls')
+        keep, ptrs, pitch = [], [], None
+        for name, d, kind in zip(_d.DRIVER_NAMES, drivers, kinds):
+            if kind == _d.KIND_COARSE:
+                ptr, row = self._coarse_tensor(d, name)
+                if pitch is not None and row != pitch:
+                    raise ValueError('the coarse drivers must share one distance between rows')
+                pitch = row
+                keep.append(d)
+            elif kind == _d.KIND_FINE:
+                ptr = eng._check_tensor(d, eng.dtype, n, name)
+                keep.append(d)
+            else:
+                sc = torch.as_tensor(d, dtype=eng.dtype).reshape(1).to(eng._dev())
+                keep.append(sc)
+                ptr = sc.data_ptr()
+            ptrs.append(ptr)
+        if out_day is None:
+            out_day = eng.empty(n)[0]
+        if out_night is None:
+            out_night = eng.empty(n)[0]
+        pd = eng._check_tensor(out_day, eng.dtype, n, 'out_day')
+        pn = eng._check_tensor(out_night, eng.dtype, n, 'out_night')
+        if n:
+            self._grid.run(eng.np_dtype, cptr, ptrs, kinds, pitch or self.coarse_shape[1], first, n, pd, pn,
+                           flags=eng.math, where=_lib.DEVICE, stream=eng._stream())
+        return out_day, out_night
+
+    def fields(self, coarse_fields, first_pixel=0, n=None, out=None):
+        '''Enqueue the interpolation alone on the current stream: the ``F`` coarse ``(H, W)`` tensors
+        ``coarse_fields`` (one row pitch for all) at the pixels ``[first_pixel, first_pixel + n)``
+        (``n`` None: to the end) as an ``(F, n)`` tensor in the engine's dtype -- the float64
+        interpolant of ``mod16_amd.downscale.interpolate``, rounded once. ``out`` may give it: rows of
+        unit stride, any distance >= n between them; what lies between the rows is not touched.'''
+        from . import downscale as _d
+        eng, torch = self.engine, _torch()
+        fields = list(coarse_fields)
+        if not fields:
+            raise ValueError('fields needs at least one coarse field')
+        first, n = _d.check_range(self.shape, first_pixel, n)
+        ptrs, pitch = [], None
+        for k, t in enumerate(fields):
+            ptr, row = self._coarse_tensor(t, 'field %d' % k)
+            if pitch is not None and row != pitch:
+                raise ValueError('the coarse fields must share one distance between rows')
+            pitch = row
+            ptrs.append(ptr)
+        F = len(fields)
+        if out is None:
+            out = torch.empty((F, n), dtype=eng.dtype, device=eng._dev())
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != eng.device or out.dtype != eng.dtype:
+            raise TypeError('out must be a %s tensor on cuda:%d' % (eng.dtype, eng.device))
+        if tuple(out.shape) != (F, n) or (n > 1 and out.stride(1) != 1):
+            raise ValueError('out must have shape (%d, %d) and unit stride in pixels' % (F, n))
+        opitch = out.stride(0) if F > 1 else max(n, 1)
+        if opitch < n:
+            raise ValueError('the distance between the rows of out must be at least n')
+        esz = eng.np_dtype.itemsize
+        for f0 in range(0, F if n else 0, 16):       # the library takes 16 fields a call
+            self._grid.fields(eng.np_dtype, ptrs[f0:f0 + 16], pitch, first, n, out.data_ptr() + f0 * opitch * esz,
+                              opitch, where=_lib.DEVICE, stream=eng._stream())
+        return out
+
+    def close(self):
+        self._grid.close()
 
 
 class RasterEngine(object):
@@ -525,6 +643,15 @@ class RasterEngine(object):
                                pitch, min_valid=mv, rescale=rescale, flags=self.math, where=_lib.DEVICE,
                                stream=self._stream())
         return out
+
+    def downscale_grid(self, shape, coarse_shape, row_pos, col_pos, wrap=False, method='bilinear'):
+        '''The geometry of an ``R x C`` fine raster (``shape``) over an ``H x W`` coarse grid
+        (``coarse_shape``) on this engine's device -> ``DownscaleGrid``. ``row_pos[R]`` and
+        ``col_pos[C]`` are the positions of the fine rows and columns in units of coarse cells, cell
+        centres at the integers (``mod16_amd.downscale.positions`` builds them for regular grids);
+        ``wrap``: the coarse column axis is periodic (a global longitude axis); ``method``:
+        ``'nearest'``, ``'bilinear'`` or ``'cos4'`` (``mod16_amd.downscale.corner_tables``).'''
+        return DownscaleGrid(self, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method)
 
     def gapfill(self, fields, qc=None, good=None, max_gap=None, fallback=None, dtype=None, scale=None,
                 source=False, out=None):

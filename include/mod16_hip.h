@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 14
+#define MOD16_ABI_VERSION 15
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -1233,6 +1233,83 @@ MOD16_API int mod16_downscale_fields_f64(mod16_ctx* ctx, const mod16_downscale* 
 MOD16_API int mod16_downscale_fields_f32(mod16_ctx* ctx, const mod16_downscale* grid, const float* const* fields,
                                          int nfields, int64_t coarse_pitch, int64_t first_pixel, int64_t n,
                                          float* out, int64_t out_pitch, int where, void* stream);
+
+/*
+ * Zonal statistics (ABI 15; mod16_amd.zonal_statistics, RasterEngine.zonal): exact weighted totals per
+ * zone and layer -- ET in km3 per basin, country, biome or climate-grid cell -- in one pass over the
+ * raster, with sums that do not depend on the order of arrival: one launch, a call staged in tiles,
+ * several calls that accumulate tile after tile and the sum of several devices' partial results give
+ * the same words. The definition is the numpy statement mod16_amd/zonal.py (classify, quantise,
+ * accumulate):
+ *
+ *   inputs      values[k * value_pitch + i]: layer k (0 ... layers - 1), pixel i; zones[i] of zone_type
+ *               (MOD16_ZONE_U8 / _U16 / _I32); a weight w per pixel by weight_kind:
+ *               MOD16_ZONAL_WEIGHT_NONE w = 1 (weights is not looked at); _ROW weights is float64, one
+ *               entry per raster row, and pixel i takes weights[(first_pixel + i) / cols] (the area of
+ *               a latitude row; the vector must reach the row of the last pixel); _PIXEL weights[i]
+ *               of the values' type. float32 inputs are widened; all arithmetic is float64.
+ *   bounds      0 < wmax <= 2^ew and 0 < xmax <= 2^ex (ew, ex the smallest such exponents when the
+ *               call comes from the Python layer). The three sums carry F0 = 62 - ew, F1 = 62 - ew - ex
+ *               and F2 = 62 - ew - 2 ex fractional bits.
+ *   per pixel and layer, in this order
+ *               a zone id outside [0, nzones): ignored; x NaN or w NaN: ignored (masked);
+ *               !(|x| <= xmax) or !(0 <= w <= wmax): rejected += 1, nothing else (infinities land
+ *               here); otherwise count += 1 and, for t = w, w x, (w x) x (one rounded multiply each),
+ *               q = (int64)rint(ldexp(t, F)) (|q| <= 2^62), hi += q >> 32, lo += q & 0xffffffff; the
+ *               min and max words take key(x), the bits of the double with the low 63 flipped where
+ *               the sign is set (an order-preserving int64; -0.0 < +0.0).
+ *   acc         int64 [layers][nzones][10]: count, rejected, w_hi, w_lo, wx_hi, wx_lo, wxx_hi, wxx_lo,
+ *               min_key, max_key. The call ADDS into it: the caller starts it with min_key =
+ *               INT64_MAX, max_key = INT64_MIN, the rest 0. A sum is (hi * 2^32 + lo) / 2^F. Valid
+ *               while a zone and layer holds fewer than 2^31 valid pixels over everything accumulated
+ *               into it (every lo word then stays below 2^63). Two accumulators with the same
+ *               exponents add word by word (min / max of the last two).
+ *   kernel      a lane merges runs of equal zone id in registers; up to mod16_zonal_lds_zones() zones
+ *               a block accumulates in an LDS table with 64-bit LDS integer atomics and flushes the
+ *               entries it touched with global 64-bit integer atomics; above that the runs go straight
+ *               to the accumulator, those of a wave's neighbouring lanes that hold the same zone merged
+ *               first -- right for any zone map, slow for one without runs. No float atomics anywhere:
+ *               the words of two calls are identical.
+ *   where       MOD16_DEVICE: device pointers, asynchronous on `stream`; stage_bytes is not looked at.
+ *               MOD16_HOST: host pointers; values, zones and per-pixel weights are staged tile by tile
+ *               through the context's slabs, the tile cut so that a slot fits stage_bytes (0: 128 MiB;
+ *               at least 256 pixels); acc is uploaded once, added into by every tile and downloaded
+ *               once; the per-row weights are uploaded once. The result does not depend on stage_bytes.
+ *   bounds pre-pass
+ *               mod16_zonal_bounds_*: *xmax = max |x| over the finite values of all layers (0 if
+ *               none), *wmax = max w over the finite weights >= 0 of the pixels' range (1 without
+ *               weights), by integer maxima of the bit patterns; synchronous in both modes. Looks at
+ *               n, layers, weight_kind, cols, first_pixel and value_pitch of the spec only.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_zonal: ...", "mod16_zonal_bounds: ...")
+ *               a NULL argument; n < 0 or n > 2^30; layers outside 1 ... 65535; nzones outside 1 ...
+ *               2^24; an unknown zone_type, weight_kind or `where`; per-row weights with cols < 1 or
+ *               first_pixel outside 0 ... 2^50; value_pitch < n; exponents for which an F leaves
+ *               [-900, 900]; bounds that are not positive or exceed 2^ew / 2^ex; "acc overlaps an
+ *               input". Memory that cannot be had is MOD16_ERR_NOMEM. n = 0 is MOD16_OK and leaves
+ *               acc untouched.
+ */
+enum mod16_zone_type { MOD16_ZONE_U8 = 0, MOD16_ZONE_U16 = 1, MOD16_ZONE_I32 = 2 };
+enum mod16_zonal_weight { MOD16_ZONAL_WEIGHT_NONE = 0, MOD16_ZONAL_WEIGHT_ROW = 1, MOD16_ZONAL_WEIGHT_PIXEL = 2 };
+typedef struct mod16_zonal_spec {
+    int64_t n;                                   /* pixels */
+    int32_t layers, nzones;
+    int32_t zone_type, weight_kind;              /* enum mod16_zone_type, enum mod16_zonal_weight */
+    int64_t cols, first_pixel;                   /* per-row weights: raster columns, raster index of pixel 0 */
+    int64_t value_pitch;                         /* elements between two layers */
+    int32_t ew, ex;                              /* wmax <= 2^ew, xmax <= 2^ex */
+    double wmax, xmax;                           /* what a pixel is tested against */
+} mod16_zonal_spec;
+MOD16_API int mod16_zonal_f64(mod16_ctx* ctx, const mod16_zonal_spec* spec, const double* values, const void* zones,
+                              const void* weights, int64_t* acc, int where, void* stream, size_t stage_bytes);
+MOD16_API int mod16_zonal_f32(mod16_ctx* ctx, const mod16_zonal_spec* spec, const float* values, const void* zones,
+                              const void* weights, int64_t* acc, int where, void* stream, size_t stage_bytes);
+MOD16_API int mod16_zonal_bounds_f64(mod16_ctx* ctx, const mod16_zonal_spec* spec, const double* values,
+                                     const void* weights, double* wmax, double* xmax, int where, void* stream,
+                                     size_t stage_bytes);
+MOD16_API int mod16_zonal_bounds_f32(mod16_ctx* ctx, const mod16_zonal_spec* spec, const float* values,
+                                     const void* weights, double* wmax, double* xmax, int where, void* stream,
+                                     size_t stage_bytes);
+MOD16_API int mod16_zonal_lds_zones(void);
 
 #ifdef __cplusplus
 }

@@ -1744,6 +1744,124 @@ def gapfill_series(fields, qc=None, good=None, max_gap=None, fallback=None, dtyp
     return filled, (srcs[0] if single else tuple(srcs))
 
 
+def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=None, device=0, stage_bytes=None):
+    r'''
+    (Extension.) Zonal statistics of a raster: per zone (river basin, country, biome, climate-grid
+    cell) and layer (composite period) the exact weighted totals ``sum w``, ``sum w x`` and ``sum w x
+    x``, the count, minimum and maximum of the valid pixels, in one pass over the values
+    (``mod16_zonal_*``). The sums are order-independent by construction -- every term is quantised
+    once to a 62-bit fixed point and added as an integer -- so the result does not depend on
+    ``stage_bytes``, on how a raster is cut into calls that accumulate (``acc=``), or on the device
+    that ran a part (``ZonalResult.merge``). The definition is ``mod16_amd.zonal`` (``accumulate``).
+
+    Parameters
+    ----------
+    values : numpy.ndarray
+        float32 or float64, ``shape`` or ``(K,) + shape``; NaN masks a pixel
+    zones : numpy.ndarray
+        integer zone ids of ``shape``; ids outside ``[0, nzones)`` are ignored (uint8, uint16 and
+        int32 are taken as they are, other integer types are range-checked and cast to int32)
+    nzones : int
+        (Optional) the number of zones (Default: ``zones.max() + 1``)
+    area : None, float or numpy.ndarray
+        (Optional) the weight of a pixel: None (1), a scalar, ``(R,)`` for a 2-D ``shape`` with R
+        rows (the area of a latitude row, float64) or an array of ``shape`` (a land fraction; taken
+        in the values' dtype); NaN masks a pixel
+    bounds : (float, float)
+        (Optional) ``(wmax, xmax)``: the largest weight and the largest ``|value|`` the call accepts;
+        a pixel beyond them raises ValueError. They fix the fixed-point scale, so calls that are to
+        be accumulated or merged must share their exponents (``zonal.exponent``). Default: a
+        pre-pass over the inputs finds them (infinities are then counted in ``rejected``)
+    acc : ZonalResult
+        (Optional) a result to add into (it is not modified); needs ``bounds`` with its exponents
+    stage_bytes : int
+        (Optional) device memory a staging slot may take; the result does not depend on it
+
+    Returns
+    -------
+    mod16_amd.zonal.ZonalResult
+        ``count``, ``rejected``, ``sum_w``, ``sum_wx``, ``sum_wxx``, ``mean``, ``var``, ``std``,
+        ``min``, ``max``, each ``(K, Z)`` (``(Z,)`` for values without a layer axis); ``words``, the
+        ``(K, Z, 10)`` int64 accumulator; ``merge(other)``
+    '''
+    from . import zonal as _z
+    values, zones = np.asarray(values), np.asarray(zones)
+    if values.dtype not in (np.float32, np.float64):
+        raise ValueError('values must be float32 or float64, got %s' % values.dtype)
+    if zones.dtype.kind not in 'iu':
+        raise ValueError('zones must be integers, got %s' % zones.dtype)
+    shape = zones.shape
+    if values.shape == shape:
+        layered, K = False, 1
+    elif values.ndim == zones.ndim + 1 and values.shape[1:] == shape:
+        layered, K = True, values.shape[0]
+    else:
+        raise ValueError('values must have the shape of zones %r or (K,) + that shape, got %r' % (shape, values.shape))
+    n = int(np.prod(shape, dtype=np.int64))
+    if n > _z.MAX_PIXELS:
+        raise ValueError('a call takes at most 2**30 pixels (accumulate parts with acc=), got %d' % n)
+    if not 1 <= K <= _z.MAX_LAYERS:
+        raise ValueError('between 1 and %d layers, got %d' % (_z.MAX_LAYERS, K))
+    if nzones is None:
+        nzones = max(int(zones.max()) + 1, 1) if n else 1
+    if isinstance(nzones, (bool, np.bool_)) or not isinstance(nzones, (int, np.integer)) or not 1 <= nzones <= _z.MAX_ZONES:
+        raise ValueError('nzones must be an integer between 1 and 2**24, got %r' % (nzones,))
+    nzones = int(nzones)
+    if zones.dtype.name not in _z.ZONE_TYPES:
+        if n and (int(zones.min()) < -2 ** 31 or int(zones.max()) >= 2 ** 31):
+            raise ValueError('zone ids must fit an int32')
+        zones = zones.astype(np.int32)
+    zones = np.ascontiguousarray(zones).reshape(n)
+    values = np.ascontiguousarray(values).reshape(K, n)
+    kind, cols, weights = _lib.ZONAL_WEIGHT_NONE, 1, None
+    if area is not None:
+        area = np.asarray(area)
+        if area.dtype.kind not in 'fiu':
+            raise ValueError('area must be numeric, got %s' % area.dtype)
+        if area.ndim == 0:               # one weight for every pixel: one "row" that holds them all
+            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(n, 1), np.array([area], np.float64)
+        elif len(shape) == 2 and area.shape == (shape[0],):
+            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(shape[1], 1), np.ascontiguousarray(area, np.float64)
+        elif area.shape == shape:
+            kind, weights = _lib.ZONAL_WEIGHT_PIXEL, np.ascontiguousarray(area, values.dtype).reshape(n)
+        else:
+            raise ValueError('area must be a scalar, (rows,) for a 2-D raster or of the shape of zones %r, got %r'
+                             % (shape, area.shape))
+    if stage_bytes is not None and int(stage_bytes) < 0:
+        raise ValueError('stage_bytes must not be negative')
+    explicit = bounds is not None
+    if acc is not None:
+        if not isinstance(acc, _z.ZonalResult):
+            raise ValueError('acc must be a ZonalResult')
+        if not explicit:
+            raise ValueError('acc= needs explicit bounds: their exponents are the scale of the accumulator')
+        if acc.words.shape != (K, nzones, _z.NWORDS):
+            raise ValueError('acc holds %r words, this call needs %r' % (acc.words.shape, (K, nzones, _z.NWORDS)))
+    if explicit:
+        bounds = _z.check_bounds(bounds)
+        if acc is not None and (acc.ew, acc.ex) != bounds[2:]:
+            raise ValueError('the exponents of bounds %r differ from the accumulator\'s %r' % (bounds[2:], (acc.ew, acc.ex)))
+    wptr = None if weights is None else weights.ctypes.data
+    ztype = _z.ZONE_TYPES[zones.dtype.name]
+    ctx = _lib.context(device)
+    if not explicit:
+        wmax, xmax = ctx.zonal_bounds(values.dtype, n, K, values.ctypes.data, wptr, weight_kind=kind, cols=cols,
+                                      where=_lib.HOST, stage_bytes=stage_bytes) if n else (1.0, 1.0)
+        bounds = _z.check_bounds((wmax if wmax > 0 else 1.0, xmax if xmax > 0 else 1.0))
+    words = _z.empty(K, nzones) if acc is None else acc.words.copy()
+    before = words[..., _z.REJECTED].copy()
+    if n:
+        ctx.zonal(values.dtype, n, K, nzones, ztype, values.ctypes.data, zones.ctypes.data, wptr, words.ctypes.data,
+                  bounds, weight_kind=kind, cols=cols, where=_lib.HOST, stage_bytes=stage_bytes)
+    if explicit:
+        bad = np.argwhere(words[..., _z.REJECTED] != before)
+        if len(bad):
+            k, z = (int(v) for v in bad[0])
+            raise ValueError('%d pixels of zone %d, layer %d lie outside the bounds (wmax %r, xmax %r)'
+                             % (words[k, z, _z.REJECTED] - before[k, z], z, k, bounds[0], bounds[1]))
+    return _z.ZonalResult(words, bounds[2], bounds[3], squeeze=not layered)
+
+
 EnsembleQuantiles = _collections.namedtuple('EnsembleQuantiles', 'q day night total')
 
 

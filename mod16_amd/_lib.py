@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -112,6 +112,23 @@ class DownscaleSpec(C.Structure):
     _fields_ = [('rows', C.c_int64), ('cols', C.c_int64), ('coarse_rows', C.c_int64), ('coarse_cols', C.c_int64),
                 ('wrap_cols', C.c_int32), ('method', C.c_int32)]
 
+
+class ZonalSpec(C.Structure):
+    '''``mod16_zonal_spec`` (include/mod16_hip.h): the pixels, layers and zones of a zonal call, the
+    types of its zone ids and weights, the raster geometry of per-row weights, the value pitch, and
+    the bounds with their exponents.'''
+    _fields_ = [('n', C.c_int64), ('layers', C.c_int32), ('nzones', C.c_int32), ('zone_type', C.c_int32),
+                ('weight_kind', C.c_int32), ('cols', C.c_int64), ('first_pixel', C.c_int64),
+                ('value_pitch', C.c_int64), ('ew', C.c_int32), ('ex', C.c_int32), ('wmax', C.c_double),
+                ('xmax', C.c_double)]
+
+
+ZONE_U8, ZONE_U16, ZONE_I32 = 0, 1, 2                           # enum mod16_zone_type
+ZONAL_WEIGHT_NONE, ZONAL_WEIGHT_ROW, ZONAL_WEIGHT_PIXEL = 0, 1, 2     # enum mod16_zonal_weight
+_ZONAL_ARGS = [C.c_void_p, C.POINTER(ZonalSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+               C.c_void_p, C.c_size_t]
+_ZONAL_BOUNDS_ARGS = [C.c_void_p, C.POINTER(ZonalSpec), C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                      C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_size_t]
 
 _I32P = C.POINTER(C.c_int32)
 _DOWNSCALED_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I32P, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
@@ -314,6 +331,11 @@ PROTOTYPES = {
     'mod16_et_downscaled_f32': (C.c_int, _DOWNSCALED_ARGS),
     'mod16_downscale_fields_f64': (C.c_int, _DOWNSCALE_FIELDS_ARGS),
     'mod16_downscale_fields_f32': (C.c_int, _DOWNSCALE_FIELDS_ARGS),
+    'mod16_zonal_f64': (C.c_int, _ZONAL_ARGS),
+    'mod16_zonal_f32': (C.c_int, _ZONAL_ARGS),
+    'mod16_zonal_bounds_f64': (C.c_int, _ZONAL_BOUNDS_ARGS),
+    'mod16_zonal_bounds_f32': (C.c_int, _ZONAL_BOUNDS_ARGS),
+    'mod16_zonal_lds_zones': (C.c_int, []),
 }
 
 _lib = None
@@ -557,6 +579,47 @@ class Context:
             self.handle, C.byref(spec), ptr_array(list(fields)), qc, good,
             ptr_array(list(fallback)) if fallback is not None else None, ptr_array(list(out)), source,
             int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
+
+    @staticmethod
+    def _zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch, bounds=None):
+        for what, v in (('layers', layers), ('nzones', nzones), ('zone_type', zone_type), ('weight_kind', weight_kind)):
+            if not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError('%s must fit an int32, got %r' % (what, v))
+        spec = ZonalSpec()
+        spec.n, spec.layers, spec.nzones = int(n), int(layers), int(nzones)
+        spec.zone_type, spec.weight_kind = int(zone_type), int(weight_kind)
+        spec.cols, spec.first_pixel, spec.value_pitch = int(cols), int(first_pixel), int(value_pitch)
+        if bounds is not None:
+            spec.wmax, spec.xmax, spec.ew, spec.ex = float(bounds[0]), float(bounds[1]), int(bounds[2]), int(bounds[3])
+        return spec
+
+    def zonal(self, dtype, n, layers, nzones, zone_type, values, zones, weights, acc, bounds, weight_kind=0,
+              cols=1, first_pixel=0, value_pitch=None, where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_zonal_f64 / _f32. ``values``, ``zones``, ``weights`` (or None) and
+        ``acc`` are raw addresses; ``bounds`` is ``(wmax, xmax, ew, ex)`` (``zonal.check_bounds``);
+        ``value_pitch`` None: ``n``; ``stage_bytes`` None: the library's default.'''
+        spec = self._zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel,
+                                n if value_pitch is None else value_pitch, bounds)
+        fn = self.lib.mod16_zonal_f32 if np.dtype(dtype) == np.float32 else self.lib.mod16_zonal_f64
+        self.check(fn(self.handle, C.byref(spec), values, zones, weights, acc, int(where), stream,
+                      0 if stage_bytes is None else int(stage_bytes)))
+
+    def zonal_bounds(self, dtype, n, layers, values, weights, weight_kind=0, cols=1, first_pixel=0,
+                     value_pitch=None, where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_zonal_bounds_f64 / _f32 (raw addresses): ``(wmax, xmax)``, the
+        largest finite weight >= 0 (1.0 without weights) and the largest finite ``|x|`` of a call's
+        inputs; synchronous.'''
+        spec = self._zonal_spec(n, layers, 1, 0, weight_kind, cols, first_pixel, n if value_pitch is None else value_pitch)
+        fn = self.lib.mod16_zonal_bounds_f32 if np.dtype(dtype) == np.float32 else self.lib.mod16_zonal_bounds_f64
+        wmax, xmax = C.c_double(0.0), C.c_double(0.0)
+        self.check(fn(self.handle, C.byref(spec), values, weights, C.byref(wmax), C.byref(xmax), int(where), stream,
+                      0 if stage_bytes is None else int(stage_bytes)))
+        return wmax.value, xmax.value
+
+
+def zonal_lds_zones():
+    '''``mod16_zonal_lds_zones()``: the zone count up to which a block accumulates in LDS.'''
+    return int(load().mod16_zonal_lds_zones())
 
 
 class Ensemble:

@@ -15,3 +15,4 @@
 #include "capi/composite.hip"
 #include "capi/gapfill.hip"
 #include "capi/downscale.hip"
+#include "capi/zonal.hip"

@@ -765,6 +765,109 @@ class RasterEngine(object):
             return filled
         return filled, (src[0] if single else tuple(src[f] for f in range(len(flds))))
 
+    def _zonal_args(self, values, zones, area, cols, first_pixel):
+        '''The checks ``zonal`` and ``zonal_bounds`` share: -> (K, n, value pitch, weight kind, address
+        of the weights or None, cols, first_pixel).'''
+        torch = _torch()
+        if not isinstance(values, torch.Tensor) or not values.is_cuda or values.device.index != self.device or \
+                values.dtype != self.dtype:
+            raise TypeError('values must be a %s tensor on cuda:%d' % (self.dtype, self.device))
+        if values.dim() != 2:
+            raise ValueError('values must be a (K, n) tensor, got %r' % (tuple(values.shape),))
+        K, n = values.shape
+        if n > 1 and values.stride(1) != 1:
+            raise ValueError('values must have unit stride in pixels')
+        pitch = values.stride(0) if K > 1 else max(n, 1)
+        if pitch < n:
+            raise ValueError('the distance between the layers of values must be at least n')
+        if zones is not None:
+            if not isinstance(zones, torch.Tensor) or not zones.is_cuda or zones.device.index != self.device or \
+                    zones.dtype not in (torch.uint8, torch.int32):
+                raise TypeError('zones must be a uint8 or int32 tensor on cuda:%d' % self.device)
+            if tuple(zones.shape) != (n,) or (n > 1 and zones.stride(0) != 1):
+                raise ValueError('zones must have shape (%d,) and unit stride' % n)
+        if area is None:
+            return K, n, pitch, _lib.ZONAL_WEIGHT_NONE, None, 1, 0
+        if not isinstance(area, torch.Tensor) or not area.is_cuda or area.device.index != self.device:
+            raise TypeError('area must be a tensor on cuda:%d' % self.device)
+        if area.dim() != 1 or (area.numel() > 1 and area.stride(0) != 1):
+            raise ValueError('area must be a vector with unit stride')
+        if cols is None:
+            if area.dtype != self.dtype or area.numel() != n:
+                raise TypeError('per-pixel area must be a %s tensor of %d elements' % (self.dtype, n))
+            return K, n, pitch, _lib.ZONAL_WEIGHT_PIXEL, area.data_ptr(), 1, 0
+        cols, first_pixel = int(cols), int(first_pixel)
+        if cols < 1 or first_pixel < 0:
+            raise ValueError('cols must be at least 1 and first_pixel at least 0')
+        if area.dtype != torch.float64:
+            raise TypeError('per-row area must be a float64 tensor')
+        if n and area.numel() < (first_pixel + n - 1) // cols + 1:
+            raise ValueError('area holds %d rows, the pixel range reaches row %d'
+                             % (area.numel(), (first_pixel + n - 1) // cols))
+        return K, n, pitch, _lib.ZONAL_WEIGHT_ROW, area.data_ptr(), cols, first_pixel
+
+    def zonal_bounds(self, values, area=None, cols=None, first_pixel=0):
+        '''``(wmax, xmax)`` of a ``zonal`` call's inputs (``mod16_zonal_bounds_*``): the largest finite
+        weight >= 0 and the largest finite ``|value|``; waits for the result.'''
+        K, n, pitch, kind, wptr, cols, first_pixel = self._zonal_args(values, None, area, cols, first_pixel)
+        if not n:
+            return 1.0, 1.0
+        return self.ctx.zonal_bounds(self.np_dtype, n, K, values.data_ptr(), wptr, weight_kind=kind, cols=cols,
+                                     first_pixel=first_pixel, value_pitch=pitch, where=_lib.DEVICE, stream=self._stream())
+
+    def zonal(self, values, zones, nzones, area=None, cols=None, first_pixel=0, bounds=None, acc=None):
+        '''Enqueue the zonal reduction on the current stream: per zone and layer the exact weighted
+        totals, count, minimum and maximum of device-resident values in one launch (``mod16_zonal_*``;
+        the definition is ``mod16_amd.zonal``). The sums are integers: they do not depend on the order
+        in which the pixels arrive, so calls that add parts of a raster into one ``acc`` give the
+        words of one call over the whole.
+
+        ``values`` is ``(K, n)`` in the engine's dtype with unit stride in pixels and any distance >= n
+        between layers; ``zones`` ``(n,)`` uint8 or int32 (ids outside ``[0, nzones)`` are ignored);
+        ``area`` None, a float64 vector with one weight per raster row (with ``cols``; pixel ``p``
+        takes ``area[(first_pixel + p) // cols]``) or ``(n,)`` in the engine's dtype (``cols`` None).
+        ``bounds``: ``(wmax, xmax)``; None runs the pre-pass (``zonal_bounds``, which waits for its
+        result). ``acc``: a ``(K, nzones, 10)`` int64 tensor to add into (then ``bounds`` is
+        mandatory, with the exponents the accumulator was started with); default a fresh one.
+
+        Returns the accumulator tensor, with the exponents of the bounds recorded on it as
+        ``.exponents``; ``mod16_amd.zonal.ZonalResult.from_tensor(acc)`` downloads it. Pixels beyond
+        the bounds are counted in the ``rejected`` word. Asynchronous, like ``composite``.'''
+        from . import zonal as _z
+        torch = _torch()
+        K, n, pitch, kind, wptr, cols, first_pixel = self._zonal_args(values, zones, area, cols, first_pixel)
+        if isinstance(nzones, bool) or not isinstance(nzones, (int, np.integer)) or not 1 <= nzones <= _z.MAX_ZONES:
+            raise ValueError('nzones must be an integer between 1 and 2**24, got %r' % (nzones,))
+        nzones = int(nzones)
+        if acc is not None:
+            if bounds is None:
+                raise ValueError('acc= needs explicit bounds: their exponents are the scale of the accumulator')
+            if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.device.index != self.device or \
+                    acc.dtype != torch.int64 or not acc.is_contiguous():
+                raise TypeError('acc must be a contiguous int64 tensor on cuda:%d' % self.device)
+            if tuple(acc.shape) != (K, nzones, _z.NWORDS):
+                raise ValueError('acc must have shape %r, got %r' % ((K, nzones, _z.NWORDS), tuple(acc.shape)))
+        if bounds is None:
+            wmax, xmax = self.zonal_bounds(values, area, cols if kind == _lib.ZONAL_WEIGHT_ROW else None, first_pixel)
+            bounds = (wmax if wmax > 0 else 1.0, xmax if xmax > 0 else 1.0)
+        bounds = _z.check_bounds(bounds)
+        if acc is not None and getattr(acc, 'exponents', bounds[2:]) != bounds[2:]:
+            raise ValueError('the exponents of bounds %r differ from the accumulator\'s %r' % (bounds[2:], acc.exponents))
+        if acc is None:
+            acc = torch.from_numpy(_z.empty(K, nzones)).to(self._dev())
+        acc.exponents = bounds[2:]
+        if n:
+            try:
+                self.ctx.zonal(self.np_dtype, n, K, nzones, _z.ZONE_U8 if zones.dtype == torch.uint8 else _z.ZONE_I32,
+                               values.data_ptr(), zones.data_ptr(), wptr, acc.data_ptr(), bounds, weight_kind=kind,
+                               cols=cols, first_pixel=first_pixel, value_pitch=pitch, where=_lib.DEVICE,
+                               stream=self._stream())
+            except _lib.Mod16Error as e:
+                if e.status == _lib.ERR_ARG and 'overlaps' in str(e):
+                    raise ValueError(str(e))
+                raise
+        return acc
+
     def ensemble(self, tables):
         '''The members of an ensemble forward run on this engine's device: ``tables`` is a (D, 13,
         11) array or a sequence of D ``restore_bplut`` dicts (``mod16_amd.calibration.ensemble_tables``

@@ -29,14 +29,19 @@ Two ways in:
 
 __version__ = 'v1.2.0+mi355x.r1'
 
-import collections as _collections
 import ctypes as _ctypes
 
 import numpy as np
 import threading as _threading
 
 from . import _lib
-from .downscale import MET_DRIVERS as _MET_DRIVERS
+from ._args import (_F32, _F64, _address, _as_uint8, _broadcast, _broadcast_kind, _marshal, _outputs,
+                    _result_dtype, _shape, _shift)
+# the entry points the reference does not have, under the names they have always had here
+from .extensions import (
+    CompositeET, CompositeETPET, EnsembleET, EnsembleQuantiles, _ensemble_stack, evapotranspiration_composite,
+    evapotranspiration_downscaled, evapotranspiration_ensemble, evapotranspiration_ensemble_quantiles,
+    evapotranspiration_raw, gapfill_series, zonal_statistics)
 
 # Module constants, same names and values as reference mod16/__init__.py:106-118
 PFT_VALID = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12)
@@ -72,135 +77,6 @@ def pinned_empty(shape, dtype=np.float64):
     return _lib.pinned.empty(tuple(np.atleast_1d(shape)) if not isinstance(shape, tuple) else shape, np.dtype(dtype))
 
 
-def _result_dtype(values):
-    '''float32 only if every array-like input is float32 (numpy's own rule
-    for the reference code); Python scalars are weak.'''
-    seen32, others = False, None
-    for v in values:
-        t = type(v)
-        if t is float or t is int:
-            continue
-        if isinstance(v, (np.ndarray, np.generic)):
-            if v.dtype == _F32:
-                seen32 = True
-            elif others is None:
-                others = [v.dtype]
-            else:
-                others.append(v.dtype)
-    if others is None:
-        return _F32 if seen32 else _F64
-    if seen32:
-        others.append(_F32)
-    return _F32 if np.result_type(*others) == _F32 else _F64
-
-
-_F32, _F64 = np.dtype(np.float32), np.dtype(np.float64)
-
-
-def _address(a):
-    '''Address of a C-contiguous array's first element (the buffer protocol is a third of
-    the cost of ``a.ctypes.data``, but wants a writeable, non-empty array).'''
-    if a.flags.writeable and a.size:
-        return _ctypes.addressof(_ctypes.c_char.from_buffer(a))
-    return a.__array_interface__['data'][0]
-
-
-def _broadcast(shapes):
-    '''-> (broadcast shape, number of elements); equal shapes -- the usual call -- without numpy.'''
-    shape = shapes[0]
-    for sh in shapes:
-        if sh != shape:
-            shape = np.broadcast_shapes(*shapes)
-            break
-    n = 1
-    for extent in shape:
-        n *= int(extent)
-    return shape, n
-
-
-def _shape(v):
-    '''``np.shape`` without its detour through ``asarray`` for the two common cases.'''
-    t = type(v)
-    if t is float or t is int:
-        return ()
-    if t is np.ndarray:
-        return v.shape
-    return np.shape(v)
-
-
-def _broadcast_kind(a_shape, size, shape):
-    '''How an input of shape ``a_shape`` broadcasts against the full ``shape``,
-    as one of the kinds the C ABI takes without making it dense (``mod16_et2_*``):
-    scalar, dense, an (N,) row against (..., N), or a (..., 1) column. ``None``:
-    another pattern (made dense by the caller).'''
-    if size == 1:
-        return _lib.BC_SCALAR
-    padded = (1,) * (len(shape) - len(a_shape)) + tuple(a_shape)
-    if padded == tuple(shape):
-        return _lib.BC_DENSE
-    if len(shape) >= 2:
-        if padded[-1] == shape[-1] and all(x == 1 for x in padded[:-1]):
-            return _lib.BC_ROW
-        if padded[-1] == 1 and padded[:-1] == tuple(shape[:-1]):
-            return _lib.BC_COL
-    return None
-
-
-def _marshal(values, shape, dtype, kinds=False):
-    '''-> (keepalive arrays, addresses, element strides) for the C ABI: a
-    size-1 input is passed as a broadcast scalar (stride 0), anything else is
-    made dense over ``shape`` (stride 1). With ``kinds`` the third list holds
-    broadcast kinds (``_lib.BC_*``) and (N,) rows / (..., 1) columns stay as
-    small as they are. (The size-1 inputs share ONE small array: a call on the
-    scalars of a flux-tower site costs a handful of numpy operations, not 25
-    times three.)'''
-    keep, ptrs, strides = [], [], []
-    scal = base = None
-    dtype = np.dtype(dtype)
-    esz = dtype.itemsize
-    for i, v in enumerate(values):
-        t = type(v)
-        if t is float or t is int:
-            a = None
-        else:
-            a = v if (t is np.ndarray and v.dtype == dtype) else np.asarray(v, dtype=dtype)
-            if a.size == 1:
-                v = a.reshape(-1)[0]
-                a = None
-        if a is None:
-            if scal is None:
-                scal = np.empty(len(values), dtype)
-                base = _address(scal)
-                keep.append(scal)
-            scal[i] = v
-            ptrs.append(base + i * esz)
-            strides.append(0)
-            continue
-        kind = _broadcast_kind(a.shape, a.size, shape) if kinds else None
-        if kind in (_lib.BC_ROW, _lib.BC_COL):
-            a = np.ascontiguousarray(a.reshape(-1))
-            strides.append(kind)
-        else:
-            if a.shape != shape:
-                a = np.broadcast_to(a, shape)
-            if not a.flags.c_contiguous:
-                a = np.ascontiguousarray(a)
-            strides.append(1)
-        keep.append(a)
-        ptrs.append(_address(a))
-    return keep, ptrs, strides
-
-
-def _shift(ptrs, kinds, off, inner, itemsize):
-    '''The addresses of pixel ``off`` onwards: dense arrays move by ``off``
-    elements, (T, 1) columns by ``off // inner`` (``off`` is then a multiple of
-    ``inner``), scalars and (N,) rows stay.'''
-    if ptrs is None or off == 0:
-        return ptrs
-    step = {_lib.BC_SCALAR: 0, _lib.BC_DENSE: off, _lib.BC_ROW: 0, _lib.BC_COL: off // max(inner, 1)}
-    return [p + step[k] * itemsize if p is not None else None for p, k in zip(ptrs, kinds)]
-
-
 def _forward(cls, drivers, params, separate, flags, device, pet=False, out=None,
              devices=None, table=None, diagnostics=False):
     '''Shared host path of MOD16.evapotranspiration and
@@ -217,11 +93,7 @@ def _forward(cls, drivers, params, separate, flags, device, pet=False, out=None,
     dtype = _result_dtype(values)
     shapes = [_shape(v) for v in values]
     if cls is not None:
-        cls = np.asarray(cls)
-        if cls.dtype != np.uint8:
-            if cls.size and (cls.min() < 0 or cls.max() > 255):
-                raise IndexError('class code outside [0, 255]')
-            cls = cls.astype(np.uint8)
+        cls = _as_uint8(cls)
         shapes.append(cls.shape)
     shape, n = _broadcast(shapes)
     if diagnostics and (pet or separate):
@@ -245,17 +117,7 @@ def _forward(cls, drivers, params, separate, flags, device, pet=False, out=None,
                                (pstride is not None and max(pstride) > 1))
     inner = shape[-1] if two_level else 1
     nout = 4 if pet else (6 if separate else 2)
-    if out is not None:      # caller's arrays (e.g. memory-mapped files), written in place
-        outs = list(out)
-        if len(outs) != nout:
-            raise ValueError('out must hold %d arrays' % nout)
-        for o in outs:
-            if not (isinstance(o, np.ndarray) and o.shape == shape and o.dtype == dtype
-                    and o.flags.c_contiguous and o.flags.writeable):
-                raise ValueError('out arrays must be writeable C-contiguous %s arrays of shape %s'
-                                 % (dtype, shape))
-    else:
-        outs = [_lib.pinned.empty(shape, dtype) for _ in range(nout)]
+    outs = _outputs(out, shape, [dtype] * nout)      # the caller's arrays (e.g. memory-mapped files) are written in place
     optr = [o.ctypes.data for o in outs]
     esz = dtype.itemsize
     tile = multi.host_tile()
@@ -272,16 +134,14 @@ def _forward(cls, drivers, params, separate, flags, device, pet=False, out=None,
         c = _shift([cptr], [ckind], off, inner, 1)[0]
         o = [a + off * esz for a in optr]
         if pet:
-            fn = ctx.lib.mod16_et_pet_f32 if dtype == np.float32 else ctx.lib.mod16_et_pet_f64
-            ctx.check(fn(
+            ctx.check(_lib.typed(ctx.lib, 'mod16_et_pet', dtype)(
                 ctx.handle, c, _lib.ptr_array(d), _lib.i64_array(dstride),
                 _lib.ptr_array(p) if p is not None else None,
                 _lib.i64_array(pstride) if pstride is not None else None, m,
                 o[0], o[1], o[2], o[3], int(flags), _lib.HOST, None))
             return
         if diagnostics:
-            fn = ctx.lib.mod16_et_hdiag_f32 if dtype == np.float32 else ctx.lib.mod16_et_hdiag_f64
-            ctx.check(fn(
+            ctx.check(_lib.typed(ctx.lib, 'mod16_et_hdiag', dtype)(
                 ctx.handle, c, _lib.ptr_array(d), _lib.i64_array(dstride),
                 _lib.ptr_array(p) if p is not None else None,
                 _lib.i64_array(pstride) if pstride is not None else None, m,
@@ -295,13 +155,9 @@ def _forward(cls, drivers, params, separate, flags, device, pet=False, out=None,
             ctx.et(dtype, c, d, dstride, p, pstride, m, day, night, sep,
                    flags=flags, where=_lib.HOST)
 
-    if devs is None:
-        part(_lib.context(device), 0, n)
-    else:
-        # whole staging tiles per device (two-level shapes: whole rows), so every tile is the
-        # tile of the undivided call
-        cuts = multi.shards(n, len(devs), inner if two_level else tile)
-        multi.run(devs, lambda i, ctx: part(ctx, *cuts[i]))
+    # whole staging tiles per device (two-level shapes: whole rows), so every tile is the tile of
+    # the undivided call
+    multi.deal(devs, device, n, part, unit=inner if two_level else tile)
     if not shape:
         # all-scalar input, as the reference returns it: the totals (sums, :792) and the soil component
         # (e / lhv, :864) are numpy scalars, the canopy and transpiration components -- np.where
@@ -430,7 +286,7 @@ def _gathered_classes(torch, dev, index, values, shape, n, dtype, np_dtype, cach
         rows = rows.view(dtype).cpu().numpy()                       # (r, 11), the sample's distinct rows
         cls = torch.empty(n, dtype=torch.uint8, device=dev)
         ctx = _lib.context(index)
-        fn = ctx.lib.mod16_classify_f32 if np_dtype == _F32 else ctx.lib.mod16_classify_f64
+        fn = _lib.typed(ctx.lib, 'mod16_classify', np_dtype)
         stream = _ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         ptrs = _lib.ptr_array([t.data_ptr() for t in flat])
         strides = _lib.i64_array([1 if t.numel() > 1 else 0 for t in flat])
@@ -543,7 +399,7 @@ def _forward_device(drivers, params, separate, flags, pet=False, cache=None):
                 cptr = _class_of_ones(torch, dev, index, n).data_ptr()
                 pptr = pstr = None
             if pet:
-                fn = ctx.lib.mod16_et_pet_f32 if f32 else ctx.lib.mod16_et_pet_f64
+                fn = _lib.typed(ctx.lib, 'mod16_et_pet', np_dtype)
                 ctx.check(fn(ctx.handle, cptr, _lib.ptr_array(dptr), _lib.i64_array(dstr),
                              _lib.ptr_array(pptr) if pptr is not None else None,
                              _lib.i64_array(pstr) if pstr is not None else None,
@@ -771,8 +627,7 @@ class MOD16(object):
         day, night = np.empty(shape, dtype), np.empty(shape, dtype)
         ctx = _lib.context(0)
         if n:
-            fn = ctx.lib.mod16_et_static_f32 if dtype == np.float32 \
-                else ctx.lib.mod16_et_static_f64
+            fn = _lib.typed(ctx.lib, 'mod16_et_static', dtype)
             ctx.check(fn(
                 ctx.handle, _lib.ptr_array(dptr), _lib.i64_array(dstr),
                 _lib.ptr_array(pptr), _lib.i64_array(pstr),
@@ -842,8 +697,7 @@ class MOD16(object):
         if weights is not None and observed is None:
             raise ValueError('weights need observed')
         ctx = _lib.context(0)
-        fn = ctx.lib.mod16_et_static_batch_f32 if dtype == np.float32 \
-            else ctx.lib.mod16_et_static_batch_f64
+        fn = _lib.typed(ctx.lib, 'mod16_et_static_batch', dtype)
         adr = lambda a: a.ctypes.data if a is not None else None
         if obs is not None:
             sse, count = np.zeros(ndraw), np.zeros(ndraw)
@@ -1034,8 +888,7 @@ class BoundCalibration(object):
         obs = full(observed) if observed is not None else None
         wts = full(weights) if weights is not None else None
         self.has_observed = obs is not None
-        fn = self._ctx.lib.mod16_static_batch_bind_f32 if self.dtype == np.float32 \
-            else self._ctx.lib.mod16_static_batch_bind_f64
+        fn = _lib.typed(self._ctx.lib, 'mod16_static_batch_bind', self.dtype)
         self._handle = C.c_void_p()
         self._ctx.check(fn(self._ctx.handle, _lib.ptr_array(dptr), _lib.i64_array(dstr), self.n,
                            obs.ctypes.data if obs is not None else None,
@@ -1298,717 +1151,11 @@ def evapotranspiration_raster(
     tuple
         As ``MOD16.evapotranspiration``
     '''
-    from .utils import bplut_table
-    if isinstance(bplut, dict):
-        table = bplut_table(bplut, beta=beta)
-    else:
-        table = np.array(bplut, np.float64)
-        if beta is not None:
-            fill = np.isnan(table[:, 10]) & ~np.isnan(table[:, 0])
-            table[fill, 10] = beta
+    from .utils import as_bplut_table
+    table = as_bplut_table(bplut, beta)
     drivers = (
         lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
         temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
         pressure, fpar, lai)
     return _forward(cls, drivers, None, separate, math, device, pet=pet, out=out,
                     devices=devices, table=table, diagnostics=diagnostics)
-
-
-EnsembleET = _collections.namedtuple('EnsembleET', 'mean_day mean_night std_day std_night std_total')
-
-
-def _ensemble_stack(tables, beta=None):
-    '''``tables`` of the ensemble entry points -> float64 (D, 13, 11): a (D, 13, 11) array, or a
-    sequence of D ``restore_bplut`` dicts; ``beta`` fills the ``beta`` column where a table has none.'''
-    from .utils import bplut_table
-    if isinstance(tables, np.ndarray) or not len(tables) or not isinstance(tables[0], dict):
-        stack = np.array(tables, np.float64)
-        if stack.ndim != 3 or stack.shape[1:] != (_lib.N_CLASSES, _lib.N_PARAMS):
-            raise ValueError('tables must have shape (members, 13, 11), got %r' % (stack.shape,))
-        if beta is not None:
-            fill = np.isnan(stack[:, :, 10]) & ~np.isnan(stack[:, :, 0])
-            stack[:, :, 10][fill] = beta
-        return stack
-    return np.stack([bplut_table(t, beta=beta) for t in tables])
-
-
-def evapotranspiration_ensemble(
-        tables, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
-        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
-        vpd_night, pressure, fpar, lai, beta=None, math=_lib.MATH_FAST, device=0, out=None):
-    r'''
-    (Extension.) Forward run of an ENSEMBLE of parameter tables over a multi-class raster: what a
-    loop over ``evapotranspiration_raster(tables[m], cls, *drivers)`` followed by ``np.mean`` /
-    ``np.std`` over the members returns, from one kernel that reads each pixel's drivers once,
-    evaluates every member and keeps only the running sums (``mod16_et_ensemble_*``): the posterior
-    of a calibration (``mod16_amd.calibration.ensemble_tables``) as an ET map with its parameter
-    uncertainty.
-
-    Parameters
-    ----------
-    tables : numpy.ndarray or sequence of dict
-        (D, 13, 11) parameter tables (``MOD16.required_parameters`` column order), or D dicts as
-        ``restore_bplut`` returns them; 1 <= D <= 65536
-    cls : numpy.ndarray
-        Class raster as for ``evapotranspiration_raster``: a pixel's class picks its row in EVERY
-        table; codes without parameters give NaN, a code >= 13 raises IndexError
-    beta : float
-        (Optional) value for the ``beta`` column where a table has none
-    math : int
-        ``MATH_FAST`` (default) or ``MATH_EXACT``; the mixed and the trusted forms are refused
-    out : sequence of numpy.ndarray
-        (Optional) the five output arrays to write into
-
-    Returns
-    -------
-    EnsembleET
-        ``(mean_day, mean_night, std_day, std_night, std_total)`` [kg m-2 s-1]: mean and standard
-        deviation (``ddof = 0``) over the members of the day and night totals, and the standard
-        deviation of their sum (whose mean is ``mean_day + mean_night``). float32 only if every
-        driver array is float32 (computed in float64, rounded once). A NaN in any member makes that
-        period's mean and spread NaN. Pixels broadcast as in numpy; scalars stay scalars.
-    '''
-    stack = _ensemble_stack(tables, beta)
-    drivers = (
-        lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
-        temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
-        pressure, fpar, lai)
-    dtype = _result_dtype(drivers)
-    cls = np.asarray(cls)
-    if cls.dtype != np.uint8:
-        if cls.size and (cls.min() < 0 or cls.max() > 255):
-            raise IndexError('class code outside [0, 255]')
-        cls = cls.astype(np.uint8)
-    shape, n = _broadcast([_shape(v) for v in drivers] + [cls.shape])
-    keep, dptr, dstride = _marshal(drivers, shape, dtype)
-    cls = np.ascontiguousarray(np.broadcast_to(cls, shape))
-    if out is not None:
-        outs = list(out)
-        if len(outs) != 5:
-            raise ValueError('out must hold 5 arrays')
-        for o in outs:
-            if not (isinstance(o, np.ndarray) and o.shape == shape and o.dtype == dtype
-                    and o.flags.c_contiguous and o.flags.writeable):
-                raise ValueError('out arrays must be writeable C-contiguous %s arrays of shape %s'
-                                 % (dtype, shape))
-    else:
-        outs = [_lib.pinned.empty(shape, dtype) for _ in range(5)]
-    ens = _lib.Ensemble(_lib.context(device), stack)
-    try:
-        if n:
-            ens.run(dtype, cls.ctypes.data, dptr, dstride, n, [o.ctypes.data for o in outs],
-                    flags=math, where=_lib.HOST)
-    finally:
-        ens.close()
-    if not shape:
-        outs = [o[()] for o in outs]
-    return EnsembleET(*outs)
-
-
-CompositeET = _collections.namedtuple('CompositeET', 'et count')
-CompositeETPET = _collections.namedtuple('CompositeETPET', 'et pet count_et count_pet')
-
-
-def evapotranspiration_composite(
-        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
-        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
-        vpd_night, pressure, fpar, lai, day_hours, days=None, period_days=8, every=None,
-        pet=False, min_valid=1, rescale=False, beta=None, math=_lib.MATH_FAST, device=0, out=None,
-        stage_bytes=None):
-    r'''
-    (Extension.) Multi-day ET composites over a multi-class raster: per-pixel totals of ET over
-    periods of ``period_days`` days [kg m-2 per period], what a loop over
-    ``evapotranspiration_raster`` per day, ``(day * hours + night * (24 - hours)) * 3600`` and a masked
-    sum return -- MOD16A2 is ``period_days=8``, MOD16A3 the days of the year -- from one kernel that
-    walks the days of a period per pixel and keeps the sums in registers
-    (``mod16_et_composite_*``). The definition is ``mod16_amd.composite`` (``daily_total``,
-    ``composite_reduce``).
-
-    Parameters
-    ----------
-    bplut, beta
-        as for ``evapotranspiration_raster``
-    cls : numpy.ndarray
-        Class raster; its shape is the pixel shape
-    the 14 drivers, day_hours
-        each a scalar, an array of the pixel shape (constant in time) or an array with one more
-        leading axis: its time axis, ``S = ceil(days / every[name])`` slabs of the pixel shape
-        (day ``t`` reads slab ``t // every[name]``). ``day_hours`` are the hours of daylight.
-    days : int
-        1 to 4096 (Default: the slabs of an array with a time axis whose divisor is 1)
-    period_days : int
-        days per period; the last period may be short
-    every : dict
-        divisor per array name (``mod16_amd.composite.ARRAY_NAMES``); default 1, daily
-    pet : bool
-        True to return the potential-ET composite as well
-    min_valid : int
-        a period with fewer valid days (daily total not NaN) is NaN; 1 to ``period_days``
-    rescale : bool
-        True to multiply a period's sum by ``len / count``
-    math : int
-        ``MATH_FAST`` (default) or ``MATH_EXACT``
-    out : sequence of numpy.ndarray
-        (Optional) the 2 (``pet``: 4) arrays ``(P,) + shape`` to write into
-    stage_bytes : int
-        (Optional) device memory a staging slot may take (default 128 MiB); the result does not
-        depend on it
-
-    Returns
-    -------
-    CompositeET or CompositeETPET
-        ``(et, count)`` or ``(et, pet, count_et, count_pet)``, each ``(P,) + shape`` with ``P =
-        ceil(days / period_days)``; counts are uint16. float32 only if every array input is float32
-        (computed in float64, rounded once).
-    '''
-    from . import composite as _c
-    from .utils import bplut_table
-    arrays = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
-              temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
-              pressure, fpar, lai, day_hours]
-    ev = _c.check_every(every)
-    cls = np.asarray(cls)
-    shape = cls.shape
-    n = int(cls.size)
-    dtype = _result_dtype(arrays)
-    timed = []
-    for name, v in zip(_c.ARRAY_NAMES, arrays):
-        sh = _shape(v)
-        if sh == () or sh == shape:
-            timed.append(False)
-        elif len(sh) == len(shape) + 1 and tuple(sh[1:]) == tuple(shape):
-            timed.append(True)
-        else:
-            raise ValueError('%s has shape %r: expected a scalar, the pixel shape %r or one more leading (time) axis'
-                             % (name, sh, shape))
-    if days is None:
-        daily = [_shape(v)[0] for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed) if t and ev[name] == 1]
-        if not daily:
-            raise ValueError('days is required when no array has a daily time axis')
-        days = int(daily[0])
-    K, L, mv, P = _c.check_periods(days, period_days, min_valid)
-    for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed):
-        if t:
-            _c.check_slabs(name, _shape(v)[0], K, ev[name])
-    if int(math) & ~_lib.MATH_EXACT:
-        raise ValueError('math must be MATH_FAST or MATH_EXACT for the composite run')
-    if stage_bytes is not None and int(stage_bytes) < 0:
-        raise ValueError('stage_bytes must not be negative')
-    if cls.dtype != np.uint8:
-        if cls.size and (cls.min() < 0 or cls.max() > 255):
-            raise IndexError('class code outside [0, 255]')
-        cls = cls.astype(np.uint8)
-    cls = np.ascontiguousarray(cls)
-    full = (P,) + tuple(shape)
-    want = 4 if pet else 2
-    if out is not None:
-        outs = list(out)
-        if len(outs) != want:
-            raise ValueError('out must hold %d arrays' % want)
-        for k, o in enumerate(outs):
-            dt = dtype if k < want // 2 else np.dtype(np.uint16)
-            if not (isinstance(o, np.ndarray) and o.shape == full and o.dtype == dt
-                    and o.flags.c_contiguous and o.flags.writeable):
-                raise ValueError('out[%d] must be a writeable C-contiguous %s array of shape %s' % (k, dt, full))
-    else:
-        outs = [np.empty(full, dtype) for _ in range(want // 2)] + [np.empty(full, np.uint16) for _ in range(want // 2)]
-    if isinstance(bplut, dict):
-        table = bplut_table(bplut, beta=beta)
-    else:
-        table = np.array(bplut, np.float64)
-        if beta is not None:
-            fill = np.isnan(table[:, 10]) & ~np.isnan(table[:, 0])
-            table[fill, 10] = beta
-    keep, ptrs, pstride, tstride, divisor = [], [], [], [], []
-    for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed):
-        scalar = _shape(v) == ()
-        a = np.array(v, dtype).reshape(1) if scalar else np.ascontiguousarray(v, dtype)
-        keep.append(a)
-        pstride.append(0 if scalar else 1)
-        ptrs.append(a.ctypes.data)
-        tstride.append(n if t and a.shape[0] > 1 else 0)
-        divisor.append(ev[name] if t else K)
-    if n:
-        ctx = _lib.context(device)
-        ctx.set_bplut(table)
-        optr = [o.ctypes.data for o in outs]
-        et, pt = (optr[0], optr[1]) if pet else (optr[0], None)
-        c_et, c_pt = (optr[2], optr[3]) if pet else (optr[1], None)
-        ctx.composite(dtype, n, K, L, cls.ctypes.data, ptrs, pstride, tstride, divisor, et, pt, c_et, c_pt, n,
-                      min_valid=mv, rescale=rescale, flags=math, where=_lib.HOST, stage_bytes=stage_bytes)
-    return (CompositeETPET if pet else CompositeET)(*outs)
-
-
-def evapotranspiration_downscaled(
-        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
-        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
-        vpd_night, pressure, fpar, lai, row_pos, col_pos, wrap=False, method='bilinear',
-        coarse=_MET_DRIVERS, beta=None, math=_lib.MATH_FAST, device=0, out=None, devices=None):
-    r'''
-    (Extension.) Forward run over a multi-class raster whose reanalysis drivers stay on their own
-    coarse grid: what ``evapotranspiration_raster`` returns on drivers blown up to the fine grid
-    with ``mod16_amd.downscale.interpolate``, bit for bit, without those fine arrays ever existing --
-    the kernel interpolates the four surrounding cells per pixel (``mod16_et_downscaled_*``). The
-    definition is ``mod16_amd.downscale`` (``corner_tables``, ``interpolate``).
-
-    Parameters
-    ----------
-    bplut, beta
-        as for ``evapotranspiration_raster``
-    cls : numpy.ndarray
-        ``(R, C)`` class raster: the fine grid
-    the 14 drivers
-        a driver named in ``coarse`` is an ``(H, W)`` array on the coarse grid, one grid for all of
-        them; any other is an ``(R, C)`` array or a scalar
-    row_pos, col_pos : numpy.ndarray
-        ``(R,)`` and ``(C,)``: the position of every fine row and column in units of coarse cells,
-        cell centres at the integers (``mod16_amd.downscale.positions`` for regular grids)
-    wrap : bool
-        True where the coarse column axis is periodic (the longitude axis of a global grid);
-        otherwise, and always for the rows, the edge value is held outside the grid
-    method : str
-        ``'nearest'``, ``'bilinear'`` (default) or ``'cos4'`` (a separable cosine-to-the-fourth
-        weighting; see ``mod16_amd.downscale.corner_tables`` for what it is not)
-    coarse : sequence of str
-        the names of the coarse drivers (Default: ``mod16_amd.downscale.MET_DRIVERS``, the eleven
-        reanalysis fields; albedo, fPAR and LAI are fine-grid data)
-    math : int
-        ``MATH_FAST`` (default) or ``MATH_EXACT``
-    out : sequence of numpy.ndarray
-        (Optional) the two ``(R, C)`` arrays to write into
-    devices : sequence of int
-        (Optional) several GPUs behind this call: ranges of whole rows dealt over the listed devices
-        (``mod16_amd.multi``), every device with its own copy of the coarse arrays; the same bits
-        whatever the list
-
-    Returns
-    -------
-    tuple
-        ``(day, night)`` [kg m-2 s-1], each ``(R, C)``; float32 only if every array input is float32
-        (interpolated and computed in float64, rounded once). A NaN coarse cell gives NaN at the
-        pixels where it has weight; a class code >= 13 raises IndexError.
-    '''
-    from . import downscale as _d, multi
-    from .utils import bplut_table
-    arrays = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
-              temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
-              pressure, fpar, lai]
-    devs = multi.device_list(devices)
-    names = _d.check_coarse(coarse)
-    cls = np.asarray(cls)
-    if cls.ndim != 2:
-        raise ValueError('cls must be an (R, C) raster, got shape %r' % (cls.shape,))
-    shape = cls.shape
-    coarse_shape = (1, 1)
-    for name, v in zip(_d.DRIVER_NAMES, arrays):
-        if name in names:
-            coarse_shape = _shape(v)
-            break
-    if len(coarse_shape) != 2:
-        raise ValueError('a coarse driver must be an (H, W) array, got shape %r' % (coarse_shape,))
-    if int(math) & ~_lib.MATH_EXACT:
-        raise ValueError('math must be MATH_FAST or MATH_EXACT for the downscaled run')
-    shapes = [_shape(v) if name in names or np.size(v) != 1 else () for name, v in zip(_d.DRIVER_NAMES, arrays)]
-    kinds, _, n = _d.check_call(shape, coarse_shape, shapes, coarse=names, method=method, cls_size=cls.size,
-                                row_pos=row_pos, col_pos=col_pos)
-    row_tables = _d.corner_tables(row_pos, coarse_shape[0], False, method)
-    col_tables = _d.corner_tables(col_pos, coarse_shape[1], bool(wrap), method)
-    dtype = _result_dtype(arrays)
-    if cls.dtype != np.uint8:
-        if cls.size and (cls.min() < 0 or cls.max() > 255):
-            raise IndexError('class code outside [0, 255]')
-        cls = cls.astype(np.uint8)
-    cls = np.ascontiguousarray(cls)
-    if out is not None:
-        outs = list(out)
-        if len(outs) != 2:
-            raise ValueError('out must hold 2 arrays')
-        for o in outs:
-            if not (isinstance(o, np.ndarray) and o.shape == shape and o.dtype == dtype
-                    and o.flags.c_contiguous and o.flags.writeable):
-                raise ValueError('out arrays must be writeable C-contiguous %s arrays of shape %s' % (dtype, shape))
-    else:
-        outs = [_lib.pinned.empty(shape, dtype) for _ in range(2)]
-    if isinstance(bplut, dict):
-        table = bplut_table(bplut, beta=beta)
-    else:
-        table = np.array(bplut, np.float64)
-        if beta is not None:
-            fill = np.isnan(table[:, 10]) & ~np.isnan(table[:, 0])
-            table[fill, 10] = beta
-    keep, ptrs = [], []
-    for v, kind in zip(arrays, kinds):
-        a = np.array(v, dtype).reshape(1) if kind == _d.KIND_SCALAR else np.ascontiguousarray(v, dtype)
-        keep.append(a)
-        ptrs.append(a.ctypes.data)
-    esz = dtype.itemsize
-    optr = [o.ctypes.data for o in outs]
-
-    def part(ctx, off, m):
-        '''pixels [off, off + m) on the calling thread's context'''
-        ctx.set_bplut(table)
-        if m <= 0:
-            return
-        grid = _lib.Downscale(ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
-                              tables=(row_tables, col_tables))
-        try:
-            d = [p + off * esz if kind == _d.KIND_FINE else p for p, kind in zip(ptrs, kinds)]
-            grid.run(dtype, cls.ctypes.data + off, d, kinds, coarse_shape[1], off, m, optr[0] + off * esz,
-                     optr[1] + off * esz, flags=math, where=_lib.HOST)
-        finally:
-            grid.close()
-
-    if devs is None:
-        part(_lib.context(device), 0, n)
-    else:
-        cuts = multi.shards(n, len(devs), shape[1])         # whole rows per device
-        multi.run(devs, lambda i, ctx: part(ctx, *cuts[i]))
-    return (outs[0], outs[1])
-
-
-def gapfill_series(fields, qc=None, good=None, max_gap=None, fallback=None, dtype='uint8', scale=None,
-                   source=False, device=0, stage_bytes=None):
-    r'''
-    (Extension.) QC-driven temporal gap filling of one to three 8-day byte series (MOD15A2H fPAR /
-    LAI codes) in one kernel launch per staged tile (``mod16_gapfill_u8``): unreliable slabs are
-    linearly interpolated between the nearest reliable slabs before and after, a gap at either end
-    takes the nearest reliable value, and what ``max_gap`` leaves open takes ``fallback`` or stays
-    unfilled. The definition is ``mod16_amd.gapfill`` (``reliable``, ``fill_series``, ``encode``).
-
-    Parameters
-    ----------
-    fields : numpy.ndarray or tuple of up to three
-        uint8 codes, each ``(S,) + pixel shape`` with ``1 <= S <= 4096``; codes >= 249 are fill values
-    qc : numpy.ndarray
-        (Optional) uint8 QC layer of the same shape, shared by the fields
-    good : sequence of 256 booleans
-        (Optional) which QC bytes are acceptable (Default: ``mod16_amd.gapfill.default_good()``)
-    max_gap : int
-        (Optional) longest run of unreliable slabs that is interpolated, and the furthest a value is
-        held at either end (Default: None, no limit)
-    fallback : numpy.ndarray or tuple
-        (Optional) one uint8 array of the pixel shape (or None) per field, e.g. a climatology
-    dtype : str
-        ``'uint8'`` (codes, rounded half up; 255 where unfilled), ``'float32'`` or ``'float64'``
-        (``code * scale``; NaN where unfilled)
-    scale : float or tuple
-        (Optional) per field, float output only: 0.01 and 0.1 turn fPAR and LAI codes into what the
-        14-driver entry points take (Default: 1)
-    source : bool
-        True to return, per field, the bytes that say where each value came from (0 observed,
-        1 interpolated, 2 held, 3 fallback, 4 unfilled)
-    stage_bytes : int
-        (Optional) device memory a staging slot may take; the result does not depend on it
-
-    Returns
-    -------
-    numpy.ndarray or tuple
-        the filled array (a tuple if ``fields`` was one), and with ``source`` a pair ``(filled,
-        source)`` of the same structure
-    '''
-    from . import gapfill as _g
-    single = isinstance(fields, np.ndarray) or not isinstance(fields, (tuple, list))
-    flds = [np.asarray(f) for f in ([fields] if single else fields)]
-    if fallback is not None and (isinstance(fallback, np.ndarray) or not isinstance(fallback, (tuple, list))):
-        fallback = [fallback]
-    fbs = None if fallback is None else [None if f is None else np.asarray(f) for f in fallback]
-    qc = None if qc is None else np.asarray(qc)
-    S, shape, table, mg, name, scales = _g.check_series(
-        [f.shape for f in flds], None if qc is None else qc.shape, good, max_gap,
-        None if fbs is None else [None if f is None else f.shape for f in fbs], dtype, scale)
-    for what, arrs in (('fields', flds), ('qc', [qc]), ('fallback', fbs or [])):
-        for a in arrs:
-            if a is not None and a.dtype != np.uint8:
-                raise ValueError('%s must be uint8, got %s' % (what, a.dtype))
-    if stage_bytes is not None and int(stage_bytes) < 0:
-        raise ValueError('stage_bytes must not be negative')
-    n = int(np.prod(shape, dtype=np.int64))
-    flds = [np.ascontiguousarray(f).reshape(S, n) for f in flds]
-    qc = None if qc is None else np.ascontiguousarray(qc).reshape(S, n)
-    fbs = None if fbs is None else [None if f is None else np.ascontiguousarray(f).reshape(n) for f in fbs]
-    outs = [np.empty((S, n), name) for _ in flds]
-    src = np.empty((len(flds), S, n), np.uint8) if source else None
-    if n:
-        good8 = np.ascontiguousarray(table, np.uint8)
-        _lib.context(device).gapfill(
-            _g.OUT_TYPES[name], n, S, [f.ctypes.data for f in flds], None if qc is None else qc.ctypes.data,
-            good8.ctypes.data, None if fbs is None else [None if f is None else f.ctypes.data for f in fbs],
-            [o.ctypes.data for o in outs], None if src is None else src.ctypes.data, n, n, n, n,
-            max_gap=mg, scale=scales + [1.0] * (3 - len(scales)), where=_lib.HOST, stage_bytes=stage_bytes)
-    full = (S,) + tuple(shape)
-    filled = [o.reshape(full) for o in outs]
-    filled = filled[0] if single else tuple(filled)
-    if not source:
-        return filled
-    srcs = [src[f].reshape(full) for f in range(len(flds))]
-    return filled, (srcs[0] if single else tuple(srcs))
-
-
-def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=None, device=0, stage_bytes=None):
-    r'''
-    (Extension.) Zonal statistics of a raster: per zone (river basin, country, biome, climate-grid
-    cell) and layer (composite period) the exact weighted totals ``sum w``, ``sum w x`` and ``sum w x
-    x``, the count, minimum and maximum of the valid pixels, in one pass over the values
-    (``mod16_zonal_*``). The sums are order-independent by construction -- every term is quantised
-    once to a 62-bit fixed point and added as an integer -- so the result does not depend on
-    ``stage_bytes``, on how a raster is cut into calls that accumulate (``acc=``), or on the device
-    that ran a part (``ZonalResult.merge``). The definition is ``mod16_amd.zonal`` (``accumulate``).
-
-    Parameters
-    ----------
-    values : numpy.ndarray
-        float32 or float64, ``shape`` or ``(K,) + shape``; NaN masks a pixel
-    zones : numpy.ndarray
-        integer zone ids of ``shape``; ids outside ``[0, nzones)`` are ignored (uint8, uint16 and
-        int32 are taken as they are, other integer types are range-checked and cast to int32)
-    nzones : int
-        (Optional) the number of zones (Default: ``zones.max() + 1``)
-    area : None, float or numpy.ndarray
-        (Optional) the weight of a pixel: None (1), a scalar, ``(R,)`` for a 2-D ``shape`` with R
-        rows (the area of a latitude row, float64) or an array of ``shape`` (a land fraction; taken
-        in the values' dtype); NaN masks a pixel
-    bounds : (float, float)
-        (Optional) ``(wmax, xmax)``: the largest weight and the largest ``|value|`` the call accepts;
-        a pixel beyond them raises ValueError. They fix the fixed-point scale, so calls that are to
-        be accumulated or merged must share their exponents (``zonal.exponent``). Default: a
-        pre-pass over the inputs finds them (infinities are then counted in ``rejected``)
-    acc : ZonalResult
-        (Optional) a result to add into (it is not modified); needs ``bounds`` with its exponents
-    stage_bytes : int
-        (Optional) device memory a staging slot may take; the result does not depend on it
-
-    Returns
-    -------
-    mod16_amd.zonal.ZonalResult
-        ``count``, ``rejected``, ``sum_w``, ``sum_wx``, ``sum_wxx``, ``mean``, ``var``, ``std``,
-        ``min``, ``max``, each ``(K, Z)`` (``(Z,)`` for values without a layer axis); ``words``, the
-        ``(K, Z, 10)`` int64 accumulator; ``merge(other)``
-    '''
-    from . import zonal as _z
-    values, zones = np.asarray(values), np.asarray(zones)
-    if values.dtype not in (np.float32, np.float64):
-        raise ValueError('values must be float32 or float64, got %s' % values.dtype)
-    if zones.dtype.kind not in 'iu':
-        raise ValueError('zones must be integers, got %s' % zones.dtype)
-    shape = zones.shape
-    if values.shape == shape:
-        layered, K = False, 1
-    elif values.ndim == zones.ndim + 1 and values.shape[1:] == shape:
-        layered, K = True, values.shape[0]
-    else:
-        raise ValueError('values must have the shape of zones %r or (K,) + that shape, got %r' % (shape, values.shape))
-    n = int(np.prod(shape, dtype=np.int64))
-    if n > _z.MAX_PIXELS:
-        raise ValueError('a call takes at most 2**30 pixels (accumulate parts with acc=), got %d' % n)
-    if not 1 <= K <= _z.MAX_LAYERS:
-        raise ValueError('between 1 and %d layers, got %d' % (_z.MAX_LAYERS, K))
-    if nzones is None:
-        nzones = max(int(zones.max()) + 1, 1) if n else 1
-    if isinstance(nzones, (bool, np.bool_)) or not isinstance(nzones, (int, np.integer)) or not 1 <= nzones <= _z.MAX_ZONES:
-        raise ValueError('nzones must be an integer between 1 and 2**24, got %r' % (nzones,))
-    nzones = int(nzones)
-    if zones.dtype.name not in _z.ZONE_TYPES:
-        if n and (int(zones.min()) < -2 ** 31 or int(zones.max()) >= 2 ** 31):
-            raise ValueError('zone ids must fit an int32')
-        zones = zones.astype(np.int32)
-    zones = np.ascontiguousarray(zones).reshape(n)
-    values = np.ascontiguousarray(values).reshape(K, n)
-    kind, cols, weights = _lib.ZONAL_WEIGHT_NONE, 1, None
-    if area is not None:
-        area = np.asarray(area)
-        if area.dtype.kind not in 'fiu':
-            raise ValueError('area must be numeric, got %s' % area.dtype)
-        if area.ndim == 0:               # one weight for every pixel: one "row" that holds them all
-            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(n, 1), np.array([area], np.float64)
-        elif len(shape) == 2 and area.shape == (shape[0],):
-            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(shape[1], 1), np.ascontiguousarray(area, np.float64)
-        elif area.shape == shape:
-            kind, weights = _lib.ZONAL_WEIGHT_PIXEL, np.ascontiguousarray(area, values.dtype).reshape(n)
-        else:
-            raise ValueError('area must be a scalar, (rows,) for a 2-D raster or of the shape of zones %r, got %r'
-                             % (shape, area.shape))
-    if stage_bytes is not None and int(stage_bytes) < 0:
-        raise ValueError('stage_bytes must not be negative')
-    explicit = bounds is not None
-    if acc is not None:
-        if not isinstance(acc, _z.ZonalResult):
-            raise ValueError('acc must be a ZonalResult')
-        if not explicit:
-            raise ValueError('acc= needs explicit bounds: their exponents are the scale of the accumulator')
-        if acc.words.shape != (K, nzones, _z.NWORDS):
-            raise ValueError('acc holds %r words, this call needs %r' % (acc.words.shape, (K, nzones, _z.NWORDS)))
-    if explicit:
-        bounds = _z.check_bounds(bounds)
-        if acc is not None and (acc.ew, acc.ex) != bounds[2:]:
-            raise ValueError('the exponents of bounds %r differ from the accumulator\'s %r' % (bounds[2:], (acc.ew, acc.ex)))
-    wptr = None if weights is None else weights.ctypes.data
-    ztype = _z.ZONE_TYPES[zones.dtype.name]
-    ctx = _lib.context(device)
-    if not explicit:
-        wmax, xmax = ctx.zonal_bounds(values.dtype, n, K, values.ctypes.data, wptr, weight_kind=kind, cols=cols,
-                                      where=_lib.HOST, stage_bytes=stage_bytes) if n else (1.0, 1.0)
-        bounds = _z.check_bounds((wmax if wmax > 0 else 1.0, xmax if xmax > 0 else 1.0))
-    words = _z.empty(K, nzones) if acc is None else acc.words.copy()
-    before = words[..., _z.REJECTED].copy()
-    if n:
-        ctx.zonal(values.dtype, n, K, nzones, ztype, values.ctypes.data, zones.ctypes.data, wptr, words.ctypes.data,
-                  bounds, weight_kind=kind, cols=cols, where=_lib.HOST, stage_bytes=stage_bytes)
-    if explicit:
-        bad = np.argwhere(words[..., _z.REJECTED] != before)
-        if len(bad):
-            k, z = (int(v) for v in bad[0])
-            raise ValueError('%d pixels of zone %d, layer %d lie outside the bounds (wmax %r, xmax %r)'
-                             % (words[k, z, _z.REJECTED] - before[k, z], z, k, bounds[0], bounds[1]))
-    return _z.ZonalResult(words, bounds[2], bounds[3], squeeze=not layered)
-
-
-EnsembleQuantiles = _collections.namedtuple('EnsembleQuantiles', 'q day night total')
-
-
-def evapotranspiration_ensemble_quantiles(
-        tables, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
-        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
-        vpd_night, pressure, fpar, lai, q=(0.05, 0.5, 0.95), beta=None, math=_lib.MATH_FAST, device=0,
-        out=None, slab_bytes=None):
-    r'''
-    (Extension.) Per-pixel quantiles of ET over an ENSEMBLE of parameter tables: what a loop over
-    ``evapotranspiration_raster(tables[m], cls, *drivers)`` followed by ``np.quantile(..., q, axis=0)``
-    returns -- the median and a credible interval of a calibration posterior per pixel -- without the
-    (D, n) arrays: the member values of a batch of pixels pass through a slab on the device and are
-    ordered there (``mod16_et_ensemble_quantiles_*``). The definition is
-    ``mod16_amd.calibration.ensemble_quantile`` (numpy's default ``'linear'`` method).
-
-    Parameters
-    ----------
-    tables, cls, the 14 drivers, beta, math, device
-        as for ``evapotranspiration_ensemble``; 1 <= D <= 256 here
-    q : float or sequence of float
-        1 to 8 quantiles, each in [0, 1]
-    out : sequence of numpy.ndarray
-        (Optional) three arrays ``(Q,) + shape`` to write day, night and total into
-    slab_bytes : int
-        (Optional) device memory the member values may take at a time (default 128 MiB; at least
-        one batch of 256 pixels is taken); the result does not depend on it
-
-    Returns
-    -------
-    EnsembleQuantiles
-        ``(q, day, night, total)``: ``q`` as a float64 array (Q,); the quantiles of the day total, the
-        night total and of day + night (summed per member), each ``(Q,) + shape`` [kg m-2 s-1].
-        float32 only if every driver array is float32 (members, sum, order and interpolation in
-        float64, rounded once). A NaN in any member makes all Q values of that pixel and series NaN.
-        Pixels broadcast as in numpy; all-scalar input gives ``(Q,)`` arrays.
-    '''
-    from .calibration import quantile_positions
-    stack = _ensemble_stack(tables, beta)
-    qs = np.atleast_1d(np.asarray(q, np.float64))
-    if len(stack):
-        quantile_positions(qs, len(stack))       # ValueError for a bad q
-    nq = qs.size
-    drivers = (
-        lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
-        temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
-        pressure, fpar, lai)
-    dtype = _result_dtype(drivers)
-    cls = np.asarray(cls)
-    if cls.dtype != np.uint8:
-        if cls.size and (cls.min() < 0 or cls.max() > 255):
-            raise IndexError('class code outside [0, 255]')
-        cls = cls.astype(np.uint8)
-    shape, n = _broadcast([_shape(v) for v in drivers] + [cls.shape])
-    keep, dptr, dstride = _marshal(drivers, shape, dtype)
-    cls = np.ascontiguousarray(np.broadcast_to(cls, shape))
-    full = (nq,) + tuple(shape)
-    if out is not None:
-        outs = list(out)
-        if len(outs) != 3:
-            raise ValueError('out must hold 3 arrays')
-        for o in outs:
-            if not (isinstance(o, np.ndarray) and o.shape == full and o.dtype == dtype
-                    and o.flags.c_contiguous and o.flags.writeable):
-                raise ValueError('out arrays must be writeable C-contiguous %s arrays of shape %s'
-                                 % (dtype, full))
-    else:
-        outs = [_lib.pinned.empty(full, dtype) for _ in range(3)]
-    ens = _lib.Ensemble(_lib.context(device), stack)
-    try:
-        if n:
-            esz = np.dtype(dtype).itemsize
-            optr = [o.ctypes.data + k * n * esz for o in outs for k in range(nq)]
-            ens.quantiles(dtype, cls.ctypes.data, dptr, dstride, n, qs, optr, slab_bytes=slab_bytes,
-                          flags=math, where=_lib.HOST)
-    finally:
-        ens.close()
-    return EnsembleQuantiles(qs, *outs)
-
-
-def evapotranspiration_raw(
-        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
-        sw_albedo, temp_day, temp_night, temp_annual, tmin, qv10m_day,
-        qv10m_night, ps_day, ps_night, elevation, fpar_pct, lai_x10,
-        day_hours=None, beta=None, math=_lib.MATH_FAST, device=0, devices=None):
-    r'''
-    (Extension) Forward run on raw drivers: the
-    pre-processing the reference does in front of ``evapotranspiration()``
-    (mod16/calibration.py:380-423) is folded into the kernel --
-
-    - ``vpd_day = MOD16.vpd(qv10m_day, ps_day, temp_day)``,
-      ``vpd_night = max(MOD16.vpd(qv10m_night, ps_night, temp_night), 0)``;
-    - ``pressure = MOD16.air_pressure(elevation)``;
-    - ``fpar = fpar_pct / 100``, ``lai = lai_x10 / 10`` with ``fpar_pct`` and
-      ``lai_x10`` as uint8 rasters in the MODIS encodings (codes >= 249 are
-      fill values and give NaN).
-
-    Returns ``(day, night)`` [kg m-2 s-1] or, with ``day_hours`` (hours of
-    daylight), ``(day, night, total8)`` where ``total8 = (day h + night (24 -
-    h)) * 8 * 3600`` [kg m-2 (8 d)-1], the MOD16A2 unit
-    (tests/verification/verify2.py:113-115). ``devices``: several GPUs behind the
-    one call, as for ``evapotranspiration_raster``.
-    '''
-    from . import multi
-    from .utils import bplut_table
-    table = bplut_table(bplut, beta=beta) if isinstance(bplut, dict) else np.array(bplut, np.float64)
-    if not isinstance(bplut, dict) and beta is not None:
-        fill = np.isnan(table[:, 10]) & ~np.isnan(table[:, 0])
-        table[fill, 10] = beta
-    devs = multi.device_list(devices)
-    raw = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
-           temp_day, temp_night, temp_annual, tmin, qv10m_day, qv10m_night,
-           ps_day, ps_night, elevation]
-    hours = [day_hours] if day_hours is not None else []
-    dtype = _result_dtype(raw + hours)
-    u8 = [np.asarray(v) for v in (cls, fpar_pct, lai_x10)]
-    shape = np.broadcast_shapes(*[np.shape(v) for v in raw + hours + u8])
-    n = int(np.prod(shape, dtype=np.int64))
-    keep, rptr, rstr = _marshal(raw, shape, dtype)
-    hkeep, hptr, hstr = _marshal(hours, shape, dtype) if hours else (None, [None], [0])
-    bytes_ = []
-    for a in u8:
-        if a.dtype != np.uint8:
-            if a.size and (a.min() < 0 or a.max() > 255):
-                raise IndexError('uint8 raster value outside [0, 255]')
-            a = a.astype(np.uint8)
-        bytes_.append(np.ascontiguousarray(np.broadcast_to(a, shape)))
-    outs = [_lib.pinned.empty(shape, dtype) for _ in range(3 if hours else 2)]
-    esz = dtype.itemsize
-
-    def part(ctx, off, m):
-        ctx.set_bplut(table)
-        if m <= 0:
-            return
-        fn = ctx.lib.mod16_et_raw_f32 if dtype == np.float32 else ctx.lib.mod16_et_raw_f64
-        ctx.check(fn(
-            ctx.handle, bytes_[0].ctypes.data + off, _lib.ptr_array(_shift(rptr, rstr, off, 1, esz)),
-            _lib.i64_array(rstr), bytes_[1].ctypes.data + off, bytes_[2].ctypes.data + off,
-            _shift(hptr, hstr, off, 1, esz)[0], int(hstr[0]), m,
-            outs[0].ctypes.data + off * esz, outs[1].ctypes.data + off * esz,
-            outs[2].ctypes.data + off * esz if hours else None, int(math), _lib.HOST, None))
-
-    if devs is None:
-        part(_lib.context(device), 0, n)
-    else:
-        cuts = multi.shards(n, len(devs), multi.host_tile())
-        multi.run(devs, lambda i, ctx: part(ctx, *cuts[i]))
-    if not shape:
-        outs = [o[()] for o in outs]
-    return tuple(outs)

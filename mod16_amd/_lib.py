@@ -432,6 +432,15 @@ def _array_type(base, n):
     return t
 
 
+_F32 = np.dtype(np.float32)
+
+
+def typed(lib, stem, dtype):
+    '''The float32 or the float64 form of an entry point: ``lib.<stem>_f32`` for float32 (a dtype,
+    a scalar type or a name), ``lib.<stem>_f64`` for anything else.'''
+    return getattr(lib, stem + ('_f32' if dtype == _F32 else '_f64'))
+
+
 def ptr_array(ptrs):
     '''Python ints / None -> void*[len]'''
     return _array_type(C.c_void_p, len(ptrs))(*ptrs)
@@ -498,8 +507,7 @@ class Context:
            out_night, out_sep, flags=MATH_FAST, where=HOST, stream=None):
         '''Thin wrapper of mod16_et_f64 / mod16_et_f32; every array argument
         is a raw address (int) or None.'''
-        fn = self.lib.mod16_et_f32 if dtype == np.float32 \
-            else self.lib.mod16_et_f64
+        fn = typed(self.lib, 'mod16_et', dtype)
         self.check(fn(
             self.handle, cls, ptr_array(drivers), i64_array(dstride),
             ptr_array(params) if params is not None else None,
@@ -512,8 +520,7 @@ class Context:
             out_day, out_night, out_sep, flags=MATH_FAST, where=HOST, stream=None):
         '''mod16_et2_f64 / mod16_et2_f32: as ``et`` with a broadcast kind
         (``BC_*``) per input instead of a 0 / 1 stride.'''
-        fn = self.lib.mod16_et2_f32 if np.dtype(dtype) == np.float32 \
-            else self.lib.mod16_et2_f64
+        fn = typed(self.lib, 'mod16_et2', dtype)
         self.check(fn(
             self.handle, cls, int(cls_kind), ptr_array(drivers), i64_array(dkind),
             ptr_array(params) if params is not None else None,
@@ -525,8 +532,7 @@ class Context:
     def method(self, dtype, method, inputs, istride, params, pstride, n, outs,
                alpha=1.26, tiny=1e-7, where=HOST, stream=None):
         '''Thin wrapper of mod16_method_f64 / _f32 (raw addresses or None).'''
-        fn = self.lib.mod16_method_f32 if np.dtype(dtype) == np.float32 \
-            else self.lib.mod16_method_f64
+        fn = typed(self.lib, 'mod16_method', dtype)
         self.check(fn(
             self.handle, int(method), ptr_array(inputs), i64_array(istride),
             ptr_array(params) if params is not None else None,
@@ -555,8 +561,7 @@ class Context:
         spec.hours_pixel_stride = int(pixel_stride[N_DRIVERS])
         spec.hours_time_stride = int(time_stride[N_DRIVERS])
         spec.hours_every = int(every[N_DRIVERS])
-        fn = self.lib.mod16_et_composite_f32 if np.dtype(dtype) == np.float32 \
-            else self.lib.mod16_et_composite_f64
+        fn = typed(self.lib, 'mod16_et_composite', dtype)
         self.check(fn(self.handle, C.byref(spec), cls, ptr_array(list(arrays[:N_DRIVERS])), arrays[N_DRIVERS],
                       out_et, out_pet, count_et, count_pet, int(out_pitch), int(flags), int(where), stream,
                       0 if stage_bytes is None else int(stage_bytes)))
@@ -600,7 +605,7 @@ class Context:
         ``value_pitch`` None: ``n``; ``stage_bytes`` None: the library's default.'''
         spec = self._zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel,
                                 n if value_pitch is None else value_pitch, bounds)
-        fn = self.lib.mod16_zonal_f32 if np.dtype(dtype) == np.float32 else self.lib.mod16_zonal_f64
+        fn = typed(self.lib, 'mod16_zonal', dtype)
         self.check(fn(self.handle, C.byref(spec), values, zones, weights, acc, int(where), stream,
                       0 if stage_bytes is None else int(stage_bytes)))
 
@@ -610,7 +615,7 @@ class Context:
         largest finite weight >= 0 (1.0 without weights) and the largest finite ``|x|`` of a call's
         inputs; synchronous.'''
         spec = self._zonal_spec(n, layers, 1, 0, weight_kind, cols, first_pixel, n if value_pitch is None else value_pitch)
-        fn = self.lib.mod16_zonal_bounds_f32 if np.dtype(dtype) == np.float32 else self.lib.mod16_zonal_bounds_f64
+        fn = typed(self.lib, 'mod16_zonal_bounds', dtype)
         wmax, xmax = C.c_double(0.0), C.c_double(0.0)
         self.check(fn(self.handle, C.byref(spec), values, weights, C.byref(wmax), C.byref(xmax), int(where), stream,
                       0 if stage_bytes is None else int(stage_bytes)))
@@ -640,8 +645,7 @@ class Ensemble:
         '''Thin wrapper of mod16_et_ensemble_f64 / _f32; every array argument is a raw address.'''
         if not self.handle.value:
             raise ValueError('the ensemble has been closed')
-        fn = self.ctx.lib.mod16_et_ensemble_f32 if np.dtype(dtype) == np.float32 \
-            else self.ctx.lib.mod16_et_ensemble_f64
+        fn = typed(self.ctx.lib, 'mod16_et_ensemble', dtype)
         self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers), i64_array(dstride),
                           int(n), ptr_array(outs), int(flags), int(where), stream))
 
@@ -649,8 +653,7 @@ class Ensemble:
         '''Thin wrapper of mod16_et_ensemble_members_f64 / _f32 (device addresses).'''
         if not self.handle.value:
             raise ValueError('the ensemble has been closed')
-        fn = self.ctx.lib.mod16_et_ensemble_members_f32 if np.dtype(dtype) == np.float32 \
-            else self.ctx.lib.mod16_et_ensemble_members_f64
+        fn = typed(self.ctx.lib, 'mod16_et_ensemble_members', dtype)
         self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers), i64_array(dstride),
                           int(n), day, night, int(pitch), int(flags), stream))
 
@@ -661,8 +664,7 @@ class Ensemble:
         library's default.'''
         if not self.handle.value:
             raise ValueError('the ensemble has been closed')
-        fn = self.ctx.lib.mod16_et_ensemble_quantiles_f32 if np.dtype(dtype) == np.float32 \
-            else self.ctx.lib.mod16_et_ensemble_quantiles_f64
+        fn = typed(self.ctx.lib, 'mod16_et_ensemble_quantiles', dtype)
         qs = _array_type(C.c_double, len(q))(*[float(v) for v in q])
         self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers), i64_array(dstride),
                           int(n), qs, len(q), ptr_array(outs), 0 if slab_bytes is None else int(slab_bytes),
@@ -716,8 +718,7 @@ class Downscale:
             flags=MATH_FAST, where=HOST, stream=None):
         '''Thin wrapper of mod16_et_downscaled_f64 / _f32; every array argument is a raw address.'''
         self._open()
-        fn = self.ctx.lib.mod16_et_downscaled_f32 if np.dtype(dtype) == np.float32 \
-            else self.ctx.lib.mod16_et_downscaled_f64
+        fn = typed(self.ctx.lib, 'mod16_et_downscaled', dtype)
         self.ctx.check(fn(self.ctx.handle, self.handle, cls, ptr_array(drivers),
                           _array_type(C.c_int32, len(kinds))(*[int(k) for k in kinds]), int(coarse_pitch),
                           int(first_pixel), int(n), out_day, out_night, int(flags), int(where), stream))
@@ -725,8 +726,7 @@ class Downscale:
     def fields(self, dtype, fields, coarse_pitch, first_pixel, n, out, out_pitch, where=HOST, stream=None):
         '''Thin wrapper of mod16_downscale_fields_f64 / _f32 (raw addresses; 1 to 16 fields).'''
         self._open()
-        fn = self.ctx.lib.mod16_downscale_fields_f32 if np.dtype(dtype) == np.float32 \
-            else self.ctx.lib.mod16_downscale_fields_f64
+        fn = typed(self.ctx.lib, 'mod16_downscale_fields', dtype)
         self.ctx.check(fn(self.ctx.handle, self.handle, ptr_array(list(fields)), len(fields), int(coarse_pitch),
                           int(first_pixel), int(n), out, int(out_pitch), int(where), stream))
 

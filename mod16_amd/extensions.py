@@ -1,0 +1,628 @@
+'''
+The extension entry points of the numpy surface -- what the reference package does not have: the
+ensemble forward run and its quantiles, multi-day composites, the downscaled forward run, gap
+filling of the 8-day series, zonal statistics and the forward run on raw drivers. numpy in, numpy
+out, as ``evapotranspiration_raster``; ``mod16_amd`` re-exports every name here. The definitions
+they are checked against live in ``mod16_amd.composite``, ``.downscale``, ``.gapfill``, ``.zonal``
+and ``.calibration``; the argument rules they share with the package root in ``mod16_amd._args``.
+'''
+import collections as _collections
+
+import numpy as np
+
+from . import _lib
+from ._args import _U16, _as_uint8, _broadcast, _check_stage_bytes, _marshal, _outputs, _result_dtype, _shape, _shift
+from .downscale import MET_DRIVERS as _MET_DRIVERS
+
+
+EnsembleET = _collections.namedtuple('EnsembleET', 'mean_day mean_night std_day std_night std_total')
+
+
+def _ensemble_stack(tables, beta=None):
+    '''``tables`` of the ensemble entry points -> float64 (D, 13, 11): a (D, 13, 11) array, or a
+    sequence of D ``restore_bplut`` dicts; ``beta`` fills the ``beta`` column where a table has none.'''
+    from .utils import bplut_table
+    if isinstance(tables, np.ndarray) or not len(tables) or not isinstance(tables[0], dict):
+        stack = np.array(tables, np.float64)
+        if stack.ndim != 3 or stack.shape[1:] != (_lib.N_CLASSES, _lib.N_PARAMS):
+            raise ValueError('tables must have shape (members, 13, 11), got %r' % (stack.shape,))
+        if beta is not None:
+            fill = np.isnan(stack[:, :, 10]) & ~np.isnan(stack[:, :, 0])
+            stack[:, :, 10][fill] = beta
+        return stack
+    return np.stack([bplut_table(t, beta=beta) for t in tables])
+
+
+def evapotranspiration_ensemble(
+        tables, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, beta=None, math=_lib.MATH_FAST, device=0, out=None):
+    r'''
+    (Extension.) Forward run of an ENSEMBLE of parameter tables over a multi-class raster: what a
+    loop over ``evapotranspiration_raster(tables[m], cls, *drivers)`` followed by ``np.mean`` /
+    ``np.std`` over the members returns, from one kernel that reads each pixel's drivers once,
+    evaluates every member and keeps only the running sums (``mod16_et_ensemble_*``): the posterior
+    of a calibration (``mod16_amd.calibration.ensemble_tables``) as an ET map with its parameter
+    uncertainty.
+
+    Parameters
+    ----------
+    tables : numpy.ndarray or sequence of dict
+        (D, 13, 11) parameter tables (``MOD16.required_parameters`` column order), or D dicts as
+        ``restore_bplut`` returns them; 1 <= D <= 65536
+    cls : numpy.ndarray
+        Class raster as for ``evapotranspiration_raster``: a pixel's class picks its row in EVERY
+        table; codes without parameters give NaN, a code >= 13 raises IndexError
+    beta : float
+        (Optional) value for the ``beta`` column where a table has none
+    math : int
+        ``MATH_FAST`` (default) or ``MATH_EXACT``; the mixed and the trusted forms are refused
+    out : sequence of numpy.ndarray
+        (Optional) the five output arrays to write into
+
+    Returns
+    -------
+    EnsembleET
+        ``(mean_day, mean_night, std_day, std_night, std_total)`` [kg m-2 s-1]: mean and standard
+        deviation (``ddof = 0``) over the members of the day and night totals, and the standard
+        deviation of their sum (whose mean is ``mean_day + mean_night``). float32 only if every
+        driver array is float32 (computed in float64, rounded once). A NaN in any member makes that
+        period's mean and spread NaN. Pixels broadcast as in numpy; scalars stay scalars.
+    '''
+    stack = _ensemble_stack(tables, beta)
+    drivers = (
+        lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+        temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+        pressure, fpar, lai)
+    dtype = _result_dtype(drivers)
+    cls = _as_uint8(cls)
+    shape, n = _broadcast([_shape(v) for v in drivers] + [cls.shape])
+    keep, dptr, dstride = _marshal(drivers, shape, dtype)
+    cls = np.ascontiguousarray(np.broadcast_to(cls, shape))
+    outs = _outputs(out, shape, [dtype] * 5)
+    ens = _lib.Ensemble(_lib.context(device), stack)
+    try:
+        if n:
+            ens.run(dtype, cls.ctypes.data, dptr, dstride, n, [o.ctypes.data for o in outs],
+                    flags=math, where=_lib.HOST)
+    finally:
+        ens.close()
+    if not shape:
+        outs = [o[()] for o in outs]
+    return EnsembleET(*outs)
+
+
+CompositeET = _collections.namedtuple('CompositeET', 'et count')
+CompositeETPET = _collections.namedtuple('CompositeETPET', 'et pet count_et count_pet')
+
+
+def evapotranspiration_composite(
+        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, day_hours, days=None, period_days=8, every=None,
+        pet=False, min_valid=1, rescale=False, beta=None, math=_lib.MATH_FAST, device=0, out=None,
+        stage_bytes=None):
+    r'''
+    (Extension.) Multi-day ET composites over a multi-class raster: per-pixel totals of ET over
+    periods of ``period_days`` days [kg m-2 per period], what a loop over
+    ``evapotranspiration_raster`` per day, ``(day * hours + night * (24 - hours)) * 3600`` and a masked
+    sum return -- MOD16A2 is ``period_days=8``, MOD16A3 the days of the year -- from one kernel that
+    walks the days of a period per pixel and keeps the sums in registers
+    (``mod16_et_composite_*``). The definition is ``mod16_amd.composite`` (``daily_total``,
+    ``composite_reduce``).
+
+    Parameters
+    ----------
+    bplut, beta
+        as for ``evapotranspiration_raster``
+    cls : numpy.ndarray
+        Class raster; its shape is the pixel shape
+    the 14 drivers, day_hours
+        each a scalar, an array of the pixel shape (constant in time) or an array with one more
+        leading axis: its time axis, ``S = ceil(days / every[name])`` slabs of the pixel shape
+        (day ``t`` reads slab ``t // every[name]``). ``day_hours`` are the hours of daylight.
+    days : int
+        1 to 4096 (Default: the slabs of an array with a time axis whose divisor is 1)
+    period_days : int
+        days per period; the last period may be short
+    every : dict
+        divisor per array name (``mod16_amd.composite.ARRAY_NAMES``); default 1, daily
+    pet : bool
+        True to return the potential-ET composite as well
+    min_valid : int
+        a period with fewer valid days (daily total not NaN) is NaN; 1 to ``period_days``
+    rescale : bool
+        True to multiply a period's sum by ``len / count``
+    math : int
+        ``MATH_FAST`` (default) or ``MATH_EXACT``
+    out : sequence of numpy.ndarray
+        (Optional) the 2 (``pet``: 4) arrays ``(P,) + shape`` to write into
+    stage_bytes : int
+        (Optional) device memory a staging slot may take (default 128 MiB); the result does not
+        depend on it
+
+    Returns
+    -------
+    CompositeET or CompositeETPET
+        ``(et, count)`` or ``(et, pet, count_et, count_pet)``, each ``(P,) + shape`` with ``P =
+        ceil(days / period_days)``; counts are uint16. float32 only if every array input is float32
+        (computed in float64, rounded once).
+    '''
+    from . import composite as _c
+    from .utils import as_bplut_table
+    arrays = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+              temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+              pressure, fpar, lai, day_hours]
+    ev = _c.check_every(every)
+    cls = np.asarray(cls)
+    shape = cls.shape
+    n = int(cls.size)
+    dtype = _result_dtype(arrays)
+    timed = []
+    for name, v in zip(_c.ARRAY_NAMES, arrays):
+        sh = _shape(v)
+        if sh == () or sh == shape:
+            timed.append(False)
+        elif len(sh) == len(shape) + 1 and tuple(sh[1:]) == tuple(shape):
+            timed.append(True)
+        else:
+            raise ValueError('%s has shape %r: expected a scalar, the pixel shape %r or one more leading (time) axis'
+                             % (name, sh, shape))
+    if days is None:
+        daily = [_shape(v)[0] for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed) if t and ev[name] == 1]
+        if not daily:
+            raise ValueError('days is required when no array has a daily time axis')
+        days = int(daily[0])
+    K, L, mv, P = _c.check_periods(days, period_days, min_valid)
+    for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed):
+        if t:
+            _c.check_slabs(name, _shape(v)[0], K, ev[name])
+    if int(math) & ~_lib.MATH_EXACT:
+        raise ValueError('math must be MATH_FAST or MATH_EXACT for the composite run')
+    _check_stage_bytes(stage_bytes)
+    cls = np.ascontiguousarray(_as_uint8(cls))
+    full = (P,) + tuple(shape)
+    half = 2 if pet else 1
+    outs = _outputs(out, full, [dtype] * half + [_U16] * half, pinned=False, indexed=True)
+    table = as_bplut_table(bplut, beta)
+    keep, ptrs, pstride, tstride, divisor = [], [], [], [], []
+    for name, v, t in zip(_c.ARRAY_NAMES, arrays, timed):
+        scalar = _shape(v) == ()
+        a = np.array(v, dtype).reshape(1) if scalar else np.ascontiguousarray(v, dtype)
+        keep.append(a)
+        pstride.append(0 if scalar else 1)
+        ptrs.append(a.ctypes.data)
+        tstride.append(n if t and a.shape[0] > 1 else 0)
+        divisor.append(ev[name] if t else K)
+    if n:
+        ctx = _lib.context(device)
+        ctx.set_bplut(table)
+        optr = [o.ctypes.data for o in outs]
+        et, pt = (optr[0], optr[1]) if pet else (optr[0], None)
+        c_et, c_pt = (optr[2], optr[3]) if pet else (optr[1], None)
+        ctx.composite(dtype, n, K, L, cls.ctypes.data, ptrs, pstride, tstride, divisor, et, pt, c_et, c_pt, n,
+                      min_valid=mv, rescale=rescale, flags=math, where=_lib.HOST, stage_bytes=stage_bytes)
+    return (CompositeETPET if pet else CompositeET)(*outs)
+
+
+def evapotranspiration_downscaled(
+        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, row_pos, col_pos, wrap=False, method='bilinear',
+        coarse=_MET_DRIVERS, beta=None, math=_lib.MATH_FAST, device=0, out=None, devices=None):
+    r'''
+    (Extension.) Forward run over a multi-class raster whose reanalysis drivers stay on their own
+    coarse grid: what ``evapotranspiration_raster`` returns on drivers blown up to the fine grid
+    with ``mod16_amd.downscale.interpolate``, bit for bit, without those fine arrays ever existing --
+    the kernel interpolates the four surrounding cells per pixel (``mod16_et_downscaled_*``). The
+    definition is ``mod16_amd.downscale`` (``corner_tables``, ``interpolate``).
+
+    Parameters
+    ----------
+    bplut, beta
+        as for ``evapotranspiration_raster``
+    cls : numpy.ndarray
+        ``(R, C)`` class raster: the fine grid
+    the 14 drivers
+        a driver named in ``coarse`` is an ``(H, W)`` array on the coarse grid, one grid for all of
+        them; any other is an ``(R, C)`` array or a scalar
+    row_pos, col_pos : numpy.ndarray
+        ``(R,)`` and ``(C,)``: the position of every fine row and column in units of coarse cells,
+        cell centres at the integers (``mod16_amd.downscale.positions`` for regular grids)
+    wrap : bool
+        True where the coarse column axis is periodic (the longitude axis of a global grid);
+        otherwise, and always for the rows, the edge value is held outside the grid
+    method : str
+        ``'nearest'``, ``'bilinear'`` (default) or ``'cos4'`` (a separable cosine-to-the-fourth
+        weighting; see ``mod16_amd.downscale.corner_tables`` for what it is not)
+    coarse : sequence of str
+        the names of the coarse drivers (Default: ``mod16_amd.downscale.MET_DRIVERS``, the eleven
+        reanalysis fields; albedo, fPAR and LAI are fine-grid data)
+    math : int
+        ``MATH_FAST`` (default) or ``MATH_EXACT``
+    out : sequence of numpy.ndarray
+        (Optional) the two ``(R, C)`` arrays to write into
+    devices : sequence of int
+        (Optional) several GPUs behind this call: ranges of whole rows dealt over the listed devices
+        (``mod16_amd.multi``), every device with its own copy of the coarse arrays; the same bits
+        whatever the list
+
+    Returns
+    -------
+    tuple
+        ``(day, night)`` [kg m-2 s-1], each ``(R, C)``; float32 only if every array input is float32
+        (interpolated and computed in float64, rounded once). A NaN coarse cell gives NaN at the
+        pixels where it has weight; a class code >= 13 raises IndexError.
+    '''
+    from . import downscale as _d, multi
+    from .utils import as_bplut_table
+    arrays = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+              temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+              pressure, fpar, lai]
+    devs = multi.device_list(devices)
+    names = _d.check_coarse(coarse)
+    cls = np.asarray(cls)
+    if cls.ndim != 2:
+        raise ValueError('cls must be an (R, C) raster, got shape %r' % (cls.shape,))
+    shape = cls.shape
+    coarse_shape = (1, 1)
+    for name, v in zip(_d.DRIVER_NAMES, arrays):
+        if name in names:
+            coarse_shape = _shape(v)
+            break
+    if len(coarse_shape) != 2:
+        raise ValueError('a coarse driver must be an (H, W) array, got shape %r' % (coarse_shape,))
+    if int(math) & ~_lib.MATH_EXACT:
+        raise ValueError('math must be MATH_FAST or MATH_EXACT for the downscaled run')
+    shapes = [_shape(v) if name in names or np.size(v) != 1 else () for name, v in zip(_d.DRIVER_NAMES, arrays)]
+    kinds, _, n = _d.check_call(shape, coarse_shape, shapes, coarse=names, method=method, cls_size=cls.size,
+                                row_pos=row_pos, col_pos=col_pos)
+    row_tables = _d.corner_tables(row_pos, coarse_shape[0], False, method)
+    col_tables = _d.corner_tables(col_pos, coarse_shape[1], bool(wrap), method)
+    dtype = _result_dtype(arrays)
+    cls = np.ascontiguousarray(_as_uint8(cls))
+    outs = _outputs(out, shape, [dtype] * 2)
+    table = as_bplut_table(bplut, beta)
+    keep, ptrs = [], []
+    for v, kind in zip(arrays, kinds):
+        a = np.array(v, dtype).reshape(1) if kind == _d.KIND_SCALAR else np.ascontiguousarray(v, dtype)
+        keep.append(a)
+        ptrs.append(a.ctypes.data)
+    esz = dtype.itemsize
+    optr = [o.ctypes.data for o in outs]
+
+    def part(ctx, off, m):
+        '''pixels [off, off + m) on the calling thread's context'''
+        ctx.set_bplut(table)
+        if m <= 0:
+            return
+        grid = _lib.Downscale(ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
+                              tables=(row_tables, col_tables))
+        try:
+            d = [p + off * esz if kind == _d.KIND_FINE else p for p, kind in zip(ptrs, kinds)]
+            grid.run(dtype, cls.ctypes.data + off, d, kinds, coarse_shape[1], off, m, optr[0] + off * esz,
+                     optr[1] + off * esz, flags=math, where=_lib.HOST)
+        finally:
+            grid.close()
+
+    multi.deal(devs, device, n, part, unit=shape[1])        # whole rows per device
+    return (outs[0], outs[1])
+
+
+def gapfill_series(fields, qc=None, good=None, max_gap=None, fallback=None, dtype='uint8', scale=None,
+                   source=False, device=0, stage_bytes=None):
+    r'''
+    (Extension.) QC-driven temporal gap filling of one to three 8-day byte series (MOD15A2H fPAR /
+    LAI codes) in one kernel launch per staged tile (``mod16_gapfill_u8``): unreliable slabs are
+    linearly interpolated between the nearest reliable slabs before and after, a gap at either end
+    takes the nearest reliable value, and what ``max_gap`` leaves open takes ``fallback`` or stays
+    unfilled. The definition is ``mod16_amd.gapfill`` (``reliable``, ``fill_series``, ``encode``).
+
+    Parameters
+    ----------
+    fields : numpy.ndarray or tuple of up to three
+        uint8 codes, each ``(S,) + pixel shape`` with ``1 <= S <= 4096``; codes >= 249 are fill values
+    qc : numpy.ndarray
+        (Optional) uint8 QC layer of the same shape, shared by the fields
+    good : sequence of 256 booleans
+        (Optional) which QC bytes are acceptable (Default: ``mod16_amd.gapfill.default_good()``)
+    max_gap : int
+        (Optional) longest run of unreliable slabs that is interpolated, and the furthest a value is
+        held at either end (Default: None, no limit)
+    fallback : numpy.ndarray or tuple
+        (Optional) one uint8 array of the pixel shape (or None) per field, e.g. a climatology
+    dtype : str
+        ``'uint8'`` (codes, rounded half up; 255 where unfilled), ``'float32'`` or ``'float64'``
+        (``code * scale``; NaN where unfilled)
+    scale : float or tuple
+        (Optional) per field, float output only: 0.01 and 0.1 turn fPAR and LAI codes into what the
+        14-driver entry points take (Default: 1)
+    source : bool
+        True to return, per field, the bytes that say where each value came from (0 observed,
+        1 interpolated, 2 held, 3 fallback, 4 unfilled)
+    stage_bytes : int
+        (Optional) device memory a staging slot may take; the result does not depend on it
+
+    Returns
+    -------
+    numpy.ndarray or tuple
+        the filled array (a tuple if ``fields`` was one), and with ``source`` a pair ``(filled,
+        source)`` of the same structure
+    '''
+    from . import gapfill as _g
+    single = isinstance(fields, np.ndarray) or not isinstance(fields, (tuple, list))
+    flds = [np.asarray(f) for f in ([fields] if single else fields)]
+    if fallback is not None and (isinstance(fallback, np.ndarray) or not isinstance(fallback, (tuple, list))):
+        fallback = [fallback]
+    fbs = None if fallback is None else [None if f is None else np.asarray(f) for f in fallback]
+    qc = None if qc is None else np.asarray(qc)
+    S, shape, table, mg, name, scales = _g.check_series(
+        [f.shape for f in flds], None if qc is None else qc.shape, good, max_gap,
+        None if fbs is None else [None if f is None else f.shape for f in fbs], dtype, scale)
+    for what, arrs in (('fields', flds), ('qc', [qc]), ('fallback', fbs or [])):
+        for a in arrs:
+            if a is not None and a.dtype != np.uint8:
+                raise ValueError('%s must be uint8, got %s' % (what, a.dtype))
+    _check_stage_bytes(stage_bytes)
+    n = int(np.prod(shape, dtype=np.int64))
+    flds = [np.ascontiguousarray(f).reshape(S, n) for f in flds]
+    qc = None if qc is None else np.ascontiguousarray(qc).reshape(S, n)
+    fbs = None if fbs is None else [None if f is None else np.ascontiguousarray(f).reshape(n) for f in fbs]
+    outs = [np.empty((S, n), name) for _ in flds]
+    src = np.empty((len(flds), S, n), np.uint8) if source else None
+    if n:
+        good8 = np.ascontiguousarray(table, np.uint8)
+        _lib.context(device).gapfill(
+            _g.OUT_TYPES[name], n, S, [f.ctypes.data for f in flds], None if qc is None else qc.ctypes.data,
+            good8.ctypes.data, None if fbs is None else [None if f is None else f.ctypes.data for f in fbs],
+            [o.ctypes.data for o in outs], None if src is None else src.ctypes.data, n, n, n, n,
+            max_gap=mg, scale=scales + [1.0] * (3 - len(scales)), where=_lib.HOST, stage_bytes=stage_bytes)
+    full = (S,) + tuple(shape)
+    filled = [o.reshape(full) for o in outs]
+    filled = filled[0] if single else tuple(filled)
+    if not source:
+        return filled
+    srcs = [src[f].reshape(full) for f in range(len(flds))]
+    return filled, (srcs[0] if single else tuple(srcs))
+
+
+def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=None, device=0, stage_bytes=None):
+    r'''
+    (Extension.) Zonal statistics of a raster: per zone (river basin, country, biome, climate-grid
+    cell) and layer (composite period) the exact weighted totals ``sum w``, ``sum w x`` and ``sum w x
+    x``, the count, minimum and maximum of the valid pixels, in one pass over the values
+    (``mod16_zonal_*``). The sums are order-independent by construction -- every term is quantised
+    once to a 62-bit fixed point and added as an integer -- so the result does not depend on
+    ``stage_bytes``, on how a raster is cut into calls that accumulate (``acc=``), or on the device
+    that ran a part (``ZonalResult.merge``). The definition is ``mod16_amd.zonal`` (``accumulate``).
+
+    Parameters
+    ----------
+    values : numpy.ndarray
+        float32 or float64, ``shape`` or ``(K,) + shape``; NaN masks a pixel
+    zones : numpy.ndarray
+        integer zone ids of ``shape``; ids outside ``[0, nzones)`` are ignored (uint8, uint16 and
+        int32 are taken as they are, other integer types are range-checked and cast to int32)
+    nzones : int
+        (Optional) the number of zones (Default: ``zones.max() + 1``)
+    area : None, float or numpy.ndarray
+        (Optional) the weight of a pixel: None (1), a scalar, ``(R,)`` for a 2-D ``shape`` with R
+        rows (the area of a latitude row, float64) or an array of ``shape`` (a land fraction; taken
+        in the values' dtype); NaN masks a pixel
+    bounds : (float, float)
+        (Optional) ``(wmax, xmax)``: the largest weight and the largest ``|value|`` the call accepts;
+        a pixel beyond them raises ValueError. They fix the fixed-point scale, so calls that are to
+        be accumulated or merged must share their exponents (``zonal.exponent``). Default: a
+        pre-pass over the inputs finds them (infinities are then counted in ``rejected``)
+    acc : ZonalResult
+        (Optional) a result to add into (it is not modified); needs ``bounds`` with its exponents
+    stage_bytes : int
+        (Optional) device memory a staging slot may take; the result does not depend on it
+
+    Returns
+    -------
+    mod16_amd.zonal.ZonalResult
+        ``count``, ``rejected``, ``sum_w``, ``sum_wx``, ``sum_wxx``, ``mean``, ``var``, ``std``,
+        ``min``, ``max``, each ``(K, Z)`` (``(Z,)`` for values without a layer axis); ``words``, the
+        ``(K, Z, 10)`` int64 accumulator; ``merge(other)``
+    '''
+    from . import zonal as _z
+    values, zones = np.asarray(values), np.asarray(zones)
+    if values.dtype not in (np.float32, np.float64):
+        raise ValueError('values must be float32 or float64, got %s' % values.dtype)
+    if zones.dtype.kind not in 'iu':
+        raise ValueError('zones must be integers, got %s' % zones.dtype)
+    shape = zones.shape
+    if values.shape == shape:
+        layered, K = False, 1
+    elif values.ndim == zones.ndim + 1 and values.shape[1:] == shape:
+        layered, K = True, values.shape[0]
+    else:
+        raise ValueError('values must have the shape of zones %r or (K,) + that shape, got %r' % (shape, values.shape))
+    n = int(np.prod(shape, dtype=np.int64))
+    if n > _z.MAX_PIXELS:
+        raise ValueError('a call takes at most 2**30 pixels (accumulate parts with acc=), got %d' % n)
+    if not 1 <= K <= _z.MAX_LAYERS:
+        raise ValueError('between 1 and %d layers, got %d' % (_z.MAX_LAYERS, K))
+    if nzones is None:
+        nzones = max(int(zones.max()) + 1, 1) if n else 1
+    if isinstance(nzones, (bool, np.bool_)) or not isinstance(nzones, (int, np.integer)) or not 1 <= nzones <= _z.MAX_ZONES:
+        raise ValueError('nzones must be an integer between 1 and 2**24, got %r' % (nzones,))
+    nzones = int(nzones)
+    if zones.dtype.name not in _z.ZONE_TYPES:
+        if n and (int(zones.min()) < -2 ** 31 or int(zones.max()) >= 2 ** 31):
+            raise ValueError('zone ids must fit an int32')
+        zones = zones.astype(np.int32)
+    zones = np.ascontiguousarray(zones).reshape(n)
+    values = np.ascontiguousarray(values).reshape(K, n)
+    kind, cols, weights = _lib.ZONAL_WEIGHT_NONE, 1, None
+    if area is not None:
+        area = np.asarray(area)
+        if area.dtype.kind not in 'fiu':
+            raise ValueError('area must be numeric, got %s' % area.dtype)
+        if area.ndim == 0:               # one weight for every pixel: one "row" that holds them all
+            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(n, 1), np.array([area], np.float64)
+        elif len(shape) == 2 and area.shape == (shape[0],):
+            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(shape[1], 1), np.ascontiguousarray(area, np.float64)
+        elif area.shape == shape:
+            kind, weights = _lib.ZONAL_WEIGHT_PIXEL, np.ascontiguousarray(area, values.dtype).reshape(n)
+        else:
+            raise ValueError('area must be a scalar, (rows,) for a 2-D raster or of the shape of zones %r, got %r'
+                             % (shape, area.shape))
+    _check_stage_bytes(stage_bytes)
+    explicit = bounds is not None
+    if acc is not None:
+        if not isinstance(acc, _z.ZonalResult):
+            raise ValueError('acc must be a ZonalResult')
+        if not explicit:
+            raise ValueError('acc= needs explicit bounds: their exponents are the scale of the accumulator')
+        if acc.words.shape != (K, nzones, _z.NWORDS):
+            raise ValueError('acc holds %r words, this call needs %r' % (acc.words.shape, (K, nzones, _z.NWORDS)))
+    if explicit:
+        bounds = _z.check_bounds(bounds)
+        if acc is not None and (acc.ew, acc.ex) != bounds[2:]:
+            raise ValueError('the exponents of bounds %r differ from the accumulator\'s %r' % (bounds[2:], (acc.ew, acc.ex)))
+    wptr = None if weights is None else weights.ctypes.data
+    ztype = _z.ZONE_TYPES[zones.dtype.name]
+    ctx = _lib.context(device)
+    if not explicit:
+        wmax, xmax = ctx.zonal_bounds(values.dtype, n, K, values.ctypes.data, wptr, weight_kind=kind, cols=cols,
+                                      where=_lib.HOST, stage_bytes=stage_bytes) if n else (1.0, 1.0)
+        bounds = _z.check_bounds((wmax if wmax > 0 else 1.0, xmax if xmax > 0 else 1.0))
+    words = _z.empty(K, nzones) if acc is None else acc.words.copy()
+    before = words[..., _z.REJECTED].copy()
+    if n:
+        ctx.zonal(values.dtype, n, K, nzones, ztype, values.ctypes.data, zones.ctypes.data, wptr, words.ctypes.data,
+                  bounds, weight_kind=kind, cols=cols, where=_lib.HOST, stage_bytes=stage_bytes)
+    if explicit:
+        bad = np.argwhere(words[..., _z.REJECTED] != before)
+        if len(bad):
+            k, z = (int(v) for v in bad[0])
+            raise ValueError('%d pixels of zone %d, layer %d lie outside the bounds (wmax %r, xmax %r)'
+                             % (words[k, z, _z.REJECTED] - before[k, z], z, k, bounds[0], bounds[1]))
+    return _z.ZonalResult(words, bounds[2], bounds[3], squeeze=not layered)
+
+
+EnsembleQuantiles = _collections.namedtuple('EnsembleQuantiles', 'q day night total')
+
+
+def evapotranspiration_ensemble_quantiles(
+        tables, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, q=(0.05, 0.5, 0.95), beta=None, math=_lib.MATH_FAST, device=0,
+        out=None, slab_bytes=None):
+    r'''
+    (Extension.) Per-pixel quantiles of ET over an ENSEMBLE of parameter tables: what a loop over
+    ``evapotranspiration_raster(tables[m], cls, *drivers)`` followed by ``np.quantile(..., q, axis=0)``
+    returns -- the median and a credible interval of a calibration posterior per pixel -- without the
+    (D, n) arrays: the member values of a batch of pixels pass through a slab on the device and are
+    ordered there (``mod16_et_ensemble_quantiles_*``). The definition is
+    ``mod16_amd.calibration.ensemble_quantile`` (numpy's default ``'linear'`` method).
+
+    Parameters
+    ----------
+    tables, cls, the 14 drivers, beta, math, device
+        as for ``evapotranspiration_ensemble``; 1 <= D <= 256 here
+    q : float or sequence of float
+        1 to 8 quantiles, each in [0, 1]
+    out : sequence of numpy.ndarray
+        (Optional) three arrays ``(Q,) + shape`` to write day, night and total into
+    slab_bytes : int
+        (Optional) device memory the member values may take at a time (default 128 MiB; at least
+        one batch of 256 pixels is taken); the result does not depend on it
+
+    Returns
+    -------
+    EnsembleQuantiles
+        ``(q, day, night, total)``: ``q`` as a float64 array (Q,); the quantiles of the day total, the
+        night total and of day + night (summed per member), each ``(Q,) + shape`` [kg m-2 s-1].
+        float32 only if every driver array is float32 (members, sum, order and interpolation in
+        float64, rounded once). A NaN in any member makes all Q values of that pixel and series NaN.
+        Pixels broadcast as in numpy; all-scalar input gives ``(Q,)`` arrays.
+    '''
+    from .calibration import quantile_positions
+    stack = _ensemble_stack(tables, beta)
+    qs = np.atleast_1d(np.asarray(q, np.float64))
+    if len(stack):
+        quantile_positions(qs, len(stack))       # ValueError for a bad q
+    nq = qs.size
+    drivers = (
+        lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+        temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+        pressure, fpar, lai)
+    dtype = _result_dtype(drivers)
+    cls = _as_uint8(cls)
+    shape, n = _broadcast([_shape(v) for v in drivers] + [cls.shape])
+    keep, dptr, dstride = _marshal(drivers, shape, dtype)
+    cls = np.ascontiguousarray(np.broadcast_to(cls, shape))
+    full = (nq,) + tuple(shape)
+    outs = _outputs(out, full, [dtype] * 3)
+    ens = _lib.Ensemble(_lib.context(device), stack)
+    try:
+        if n:
+            esz = np.dtype(dtype).itemsize
+            optr = [o.ctypes.data + k * n * esz for o in outs for k in range(nq)]
+            ens.quantiles(dtype, cls.ctypes.data, dptr, dstride, n, qs, optr, slab_bytes=slab_bytes,
+                          flags=math, where=_lib.HOST)
+    finally:
+        ens.close()
+    return EnsembleQuantiles(qs, *outs)
+
+
+def evapotranspiration_raw(
+        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, qv10m_day,
+        qv10m_night, ps_day, ps_night, elevation, fpar_pct, lai_x10,
+        day_hours=None, beta=None, math=_lib.MATH_FAST, device=0, devices=None):
+    r'''
+    (Extension) Forward run on raw drivers: the
+    pre-processing the reference does in front of ``evapotranspiration()``
+    (mod16/calibration.py:380-423) is folded into the kernel --
+
+    - ``vpd_day = MOD16.vpd(qv10m_day, ps_day, temp_day)``,
+      ``vpd_night = max(MOD16.vpd(qv10m_night, ps_night, temp_night), 0)``;
+    - ``pressure = MOD16.air_pressure(elevation)``;
+    - ``fpar = fpar_pct / 100``, ``lai = lai_x10 / 10`` with ``fpar_pct`` and
+      ``lai_x10`` as uint8 rasters in the MODIS encodings (codes >= 249 are
+      fill values and give NaN).
+
+    Returns ``(day, night)`` [kg m-2 s-1] or, with ``day_hours`` (hours of
+    daylight), ``(day, night, total8)`` where ``total8 = (day h + night (24 -
+    h)) * 8 * 3600`` [kg m-2 (8 d)-1], the MOD16A2 unit
+    (tests/verification/verify2.py:113-115). ``devices``: several GPUs behind the
+    one call, as for ``evapotranspiration_raster``.
+    '''
+    from . import multi
+    from .utils import as_bplut_table
+    table = as_bplut_table(bplut, beta)
+    devs = multi.device_list(devices)
+    raw = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+           temp_day, temp_night, temp_annual, tmin, qv10m_day, qv10m_night,
+           ps_day, ps_night, elevation]
+    hours = [day_hours] if day_hours is not None else []
+    dtype = _result_dtype(raw + hours)
+    u8 = [np.asarray(v) for v in (cls, fpar_pct, lai_x10)]
+    shape = np.broadcast_shapes(*[np.shape(v) for v in raw + hours + u8])
+    n = int(np.prod(shape, dtype=np.int64))
+    keep, rptr, rstr = _marshal(raw, shape, dtype)
+    hkeep, hptr, hstr = _marshal(hours, shape, dtype) if hours else (None, [None], [0])
+    bytes_ = [np.ascontiguousarray(np.broadcast_to(_as_uint8(a, 'uint8 raster value outside [0, 255]'), shape))
+              for a in u8]
+    outs = [_lib.pinned.empty(shape, dtype) for _ in range(3 if hours else 2)]
+    esz = dtype.itemsize
+
+    def part(ctx, off, m):
+        ctx.set_bplut(table)
+        if m <= 0:
+            return
+        ctx.check(_lib.typed(ctx.lib, 'mod16_et_raw', dtype)(
+            ctx.handle, bytes_[0].ctypes.data + off, _lib.ptr_array(_shift(rptr, rstr, off, 1, esz)),
+            _lib.i64_array(rstr), bytes_[1].ctypes.data + off, bytes_[2].ctypes.data + off,
+            _shift(hptr, hstr, off, 1, esz)[0], int(hstr[0]), m,
+            outs[0].ctypes.data + off * esz, outs[1].ctypes.data + off * esz,
+            outs[2].ctypes.data + off * esz if hours else None, int(math), _lib.HOST, None))
+
+    multi.deal(devs, device, n, part)
+    if not shape:
+        outs = [o[()] for o in outs]
+    return tuple(outs)

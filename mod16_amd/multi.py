@@ -128,6 +128,20 @@ def run(devices, fn):
     return [value for _, value in results]
 
 
+def deal(devices, device, n, part, unit=None):
+    '''Runs ``part(ctx, offset, count)`` over the pixels [0, n) of a numpy entry point. ``devices``
+    None (``device_list``): all of them on the calling thread's context on ``device``. Else they
+    are dealt over the listed devices, in ranges cut at multiples of ``unit`` (``shards``; None: the
+    staging tile, so that every tile is a tile of the undivided call), one worker thread and
+    context each (``run``). ``part`` is called for every listed device, also for one whose range is
+    empty -- what a context must be given whether or not it has pixels is ``part``'s business.'''
+    if devices is None:
+        part(_lib.context(device), 0, n)
+    else:
+        cuts = shards(n, len(devices), host_tile() if unit is None else unit)
+        run(devices, lambda i, ctx: part(ctx, *cuts[i]))
+
+
 def shutdown():
     '''Ends the worker threads of the sharded calls and frees what they hold -- per (list position,
     device) a library context with up to ~4.7 GB of staging slabs in HBM and its page-locked

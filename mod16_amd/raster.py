@@ -517,8 +517,7 @@ class RasterEngine(object):
             drivers = self.empty(n, _lib.N_DRIVERS)
         else:
             cls, drivers = out
-        fn = self.ctx.lib.mod16_synth_f32 if self.np_dtype == np.float32 \
-            else self.ctx.lib.mod16_synth_f64
+        fn = _lib.typed(self.ctx.lib, 'mod16_synth', self.np_dtype)
         ptrs = [self._check_tensor(d, self.dtype, n, 'driver') for d in drivers]
         self.ctx.check(fn(
             self.ctx.handle, int(seed), int(step), int(pixel_offset), int(n),
@@ -544,8 +543,7 @@ class RasterEngine(object):
         if diag is not None:
             if out_sep is not None:
                 raise ValueError('diag and out_sep cannot be combined')
-            fn = self.ctx.lib.mod16_et_diag_f32 if self.np_dtype == np.float32 \
-                else self.ctx.lib.mod16_et_diag_f64
+            fn = _lib.typed(self.ctx.lib, 'mod16_et_diag', self.np_dtype)
             self.ctx.check(fn(
                 self.ctx.handle, cptr, _lib.ptr_array(dptr), _lib.i64_array(dstride), n,
                 pd, pn, int(self.math),
@@ -888,8 +886,7 @@ class RasterEngine(object):
         keep, dptr, dstride = self._marshal_drivers(drivers, n)
         out = tuple(out) if out is not None else tuple(self.empty(n, 4))
         optr = [self._check_tensor(t, self.dtype, n, 'out') for t in out]
-        fn = self.ctx.lib.mod16_et_pet_f32 if self.np_dtype == np.float32 \
-            else self.ctx.lib.mod16_et_pet_f64
+        fn = _lib.typed(self.ctx.lib, 'mod16_et_pet', self.np_dtype)
         self.ctx.check(fn(
             self.ctx.handle, cptr, _lib.ptr_array(dptr), _lib.i64_array(dstride), None, None,
             n, optr[0], optr[1], optr[2], optr[3], int(self.math), _lib.DEVICE, self._stream()))
@@ -973,8 +970,7 @@ class RasterEngine(object):
             if day_hours is not None:
                 out_total8 = self.empty(n, 1)[0]
         ptr = lambda t, what: self._check_tensor(t, self.dtype, n, what) if t is not None else None
-        fn = self.ctx.lib.mod16_et_raw_f32 if self.np_dtype == np.float32 \
-            else self.ctx.lib.mod16_et_raw_f64
+        fn = _lib.typed(self.ctx.lib, 'mod16_et_raw', self.np_dtype)
         self.ctx.check(fn(
             self.ctx.handle, self._check_tensor(cls, torch.uint8, n, 'cls'),
             _lib.ptr_array(rptr), _lib.i64_array(rstr),
@@ -1003,12 +999,11 @@ class RasterEngine(object):
                 self._check_tensor(out_day, self.dtype, n, 'out_day'),
                 self._check_tensor(out_night, self.dtype, n, 'out_night'), int(self.math),
                 self._check_tensor(diag, torch.float64, 8, 'diag'))
-        f32 = self.np_dtype == np.float32
         check, device, lib = self.ctx.check, self.device, self.ctx.lib
         keepalive = (keep, cls, out_day, out_night, diag)
         if graph:
             handle = C.c_void_p()
-            make = lib.mod16_graph_et_diag_f32 if f32 else lib.mod16_graph_et_diag_f64
+            make = _lib.typed(lib, 'mod16_graph_et_diag', self.np_dtype)
             rc = make(*args, C.byref(handle))
             if rc == _lib.OK:
                 owner = _GraphHandle(lib, handle, self.ctx)
@@ -1023,7 +1018,7 @@ class RasterEngine(object):
             import warnings
             warnings.warn('HIP graph capture failed (%s); the bound launch enqueues its kernels one by one'
                           % self.ctx.lib.mod16_last_error(self.ctx.handle).decode())
-        fn = lib.mod16_et_diag_f32 if f32 else lib.mod16_et_diag_f64
+        fn = _lib.typed(lib, 'mod16_et_diag', self.np_dtype)
 
         def launch():
             check(fn(*args, torch.cuda.current_stream(device).cuda_stream))
@@ -1045,8 +1040,7 @@ class RasterEngine(object):
         from ``r.wide[14]``). Asynchronous on the current stream; returns ``r.outs``.'''
         if r.form == _lib.FORM_RAW_TOTAL8 and day_hours is None:
             raise ValueError('FORM_RAW_TOTAL8 needs day_hours')
-        fn = self.ctx.lib.mod16_et_form_tiled_f32 if self.np_dtype == np.float32 \
-            else self.ctx.lib.mod16_et_form_tiled_f64
+        fn = _lib.typed(self.ctx.lib, 'mod16_et_form_tiled', self.np_dtype)
         self.ctx.check(fn(
             self.ctx.handle, C.byref(r.layout), r.form,
             _lib.ptr_array([b.data_ptr() for b in r.bytes]),
@@ -1064,8 +1058,7 @@ class RasterEngine(object):
     def synth_tiled(self, r, seed=16, step=0, pixel_offset=0):
         '''The synthetic drivers of ``synth`` written straight into the tiled
         raster ``r`` (``mod16_synth_tiled_*``): same field, pixel for pixel.'''
-        fn = self.ctx.lib.mod16_synth_tiled_f32 if self.np_dtype == np.float32 \
-            else self.ctx.lib.mod16_synth_tiled_f64
+        fn = _lib.typed(self.ctx.lib, 'mod16_synth_tiled', self.np_dtype)
         self.ctx.check(fn(
             self.ctx.handle, C.byref(r.layout), int(seed), int(step), int(pixel_offset), r.n,
             r.cls.data_ptr(), _lib.ptr_array([d.data_ptr() for d in r.drivers]), self._stream()))
@@ -1086,8 +1079,7 @@ class RasterEngine(object):
         asynchronous on the current stream; outputs in ``r.day`` / ``r.night``,
         with ``diag`` (float64 tensor of 8 on the device) the diagnostics too.'''
         torch = _torch()
-        fn = self.ctx.lib.mod16_et_tiled_f32 if self.np_dtype == np.float32 \
-            else self.ctx.lib.mod16_et_tiled_f64
+        fn = _lib.typed(self.ctx.lib, 'mod16_et_tiled', self.np_dtype)
         dptr = self._check_tensor(diag, torch.float64, 8, 'diag') if diag is not None else None
         self.ctx.check(fn(self.ctx.handle, *self._tiled_args(r), dptr, self._stream()))
         return r.day, r.night
@@ -1111,8 +1103,7 @@ class RasterEngine(object):
         torch = _torch()
         handle = C.c_void_p()
         lib, check, device = self.ctx.lib, self.ctx.check, self.device
-        make = lib.mod16_graph_et_tiled_f32 if self.np_dtype == np.float32 \
-            else lib.mod16_graph_et_tiled_f64
+        make = _lib.typed(lib, 'mod16_graph_et_tiled', self.np_dtype)
         check(make(self.ctx.handle, *self._tiled_args(r),
                    self._check_tensor(diag, torch.float64, 8, 'diag'), C.byref(handle)))
         owner = _GraphHandle(lib, handle, self.ctx)
@@ -1239,8 +1230,7 @@ class RasterEngine(object):
         n = day.numel()
         if out is None:
             out = torch.empty(8, dtype=torch.float64, device=self._dev())
-        fn = self.ctx.lib.mod16_reduce_diag_f32 if self.np_dtype == np.float32 \
-            else self.ctx.lib.mod16_reduce_diag_f64
+        fn = _lib.typed(self.ctx.lib, 'mod16_reduce_diag', self.np_dtype)
         self.ctx.check(fn(
             self.ctx.handle, self._check_tensor(day, self.dtype, n, 'day'),
             self._check_tensor(night, self.dtype, n, 'night'), n, None,

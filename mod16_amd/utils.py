@@ -134,8 +134,24 @@ def bplut_table(bplut, beta=None):
         axis=1)
     if table.shape != (13, 11):
         raise ValueError('BPLUT arrays must have 13 entries each')
-    if beta is not None:
-        col = MOD16.required_parameters.index('beta')
-        fill = np.isnan(table[:, col]) & ~np.isnan(table[:, 0])
-        table[fill, col] = beta
+    _fill_beta(table, beta)
     return np.ascontiguousarray(table)
+
+
+def _fill_beta(table, beta):
+    '''``beta`` (unless None) into the ``beta`` column -- the last -- of a [13][11] table, in place,
+    for the classes that have parameters but no ``beta``.'''
+    if beta is not None:
+        fill = np.isnan(table[:, 10]) & ~np.isnan(table[:, 0])
+        table[fill, 10] = beta
+
+
+def as_bplut_table(bplut, beta=None):
+    '''The ``bplut`` argument of the raster entry points -> float64 [13][11] table: a dict goes
+    through ``bplut_table``, anything else is copied as a table in ``MOD16.required_parameters``
+    column order; ``beta`` fills the ``beta`` column of either as ``bplut_table`` does.'''
+    if isinstance(bplut, dict):
+        return bplut_table(bplut, beta=beta)
+    table = np.array(bplut, np.float64)
+    _fill_beta(table, beta)
+    return table

@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define MOD16_ABI_VERSION 15
+#define MOD16_ABI_VERSION 16
 
 #if defined(__GNUC__)
 #define MOD16_API __attribute__((visibility("default")))
@@ -1310,6 +1310,67 @@ MOD16_API int mod16_zonal_bounds_f32(mod16_ctx* ctx, const mod16_zonal_spec* spe
                                      const void* weights, double* wmax, double* xmax, int where, void* stream,
                                      size_t stage_bytes);
 MOD16_API int mod16_zonal_lds_zones(void);
+
+/*
+ * Composites over coarse-grid meteorology (ABI 16; mod16_amd.evapotranspiration_composite_downscaled,
+ * DownscaleGrid.composite): the period totals of mod16_et_composite_* for a contiguous range of pixels
+ * of a grid handle's fine raster, with any of the 15 arrays (the 14 drivers and day_hours) a series
+ * of COARSE planes interpolated per pixel inside the kernel -- a year of daily reanalysis stays on its
+ * own grid, the interpolated values never touch memory. No new numerics: the result is what
+ * mod16_et_composite_* gives on the arrays the "value" rule of mod16_et_downscaled_* materialises
+ * slab by slab, bit for bit (counts included), with the same flags.
+ *
+ *   spec        `composite`: as for mod16_et_composite_* -- n is the number of pixels of the range;
+ *               fine arrays, cls and the outputs are addressed from the range's first pixel (element 0
+ *               is pixel first_pixel of the raster, row-major). coarse_mask: bit k set = driver k is
+ *               coarse, bit 14 = day_hours (they are a function of latitude and day). A coarse array
+ *               is ceil(days / every) planes [coarse_rows][coarse_pitch], time_stride elements apart
+ *               (one plane where every >= days: constant in time); its pixel stride is not looked at.
+ *               All coarse arrays share the grid and coarse_pitch >= coarse_cols; each has its own time
+ *               stride. A NaN cell makes the interpolant NaN where it has weight: that day is not
+ *               counted (see "result" of mod16_et_composite_*); nothing is renormalised.
+ *   float32     coarse and fine values widened; interpolation, pixel function and accumulation in
+ *               float64; one rounding on store.
+ *   flags       MOD16_MATH_FAST (0) or MOD16_MATH_EXACT; guarded as mod16_et_composite_*: a second
+ *               kernel recomputes all periods of the pixels with a flagged day. No atomics on results,
+ *               no workspace: two calls give the same bits.
+ *   where       MOD16_DEVICE: device pointers, asynchronous on `stream` (mod16_check_status reports a
+ *               class code >= 13). MOD16_HOST: host pointers; the coarse series are uploaded whole,
+ *               once per call, before the first pixel tile (MOD16_ERR_NOMEM where there is no room:
+ *               11 x 365 planes of 361 x 576 float64 are 6.7 GB); the fine arrays, the class raster
+ *               and the outputs go through the tile staging of mod16_et_composite_* (stage_bytes as
+ *               there), each tile launched with its own first pixel. The result does not depend on
+ *               stage_bytes.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_et_composite_downscaled: ...")
+ *               everything mod16_et_composite_* refuses, with its texts (a coarse array's pixel stride
+ *               apart); "the grid was created on another device than this context's"; "the pixel
+ *               range [first_pixel, first_pixel + n) leaves the raster"; "coarse_mask has a bit above
+ *               14"; "coarse_pitch must be at least coarse_cols"; "a coarse plane with its pitch must
+ *               hold at most 2^31 - 1 elements" (this entry only: the kernel's cell offsets are
+ *               32-bit); "time stride of a coarse array with several slabs must be at least a plane"
+ *               ((coarse_rows - 1) coarse_pitch + coarse_cols elements); a NULL grid or spec;
+ *               "MOD16_MATH_MIXED is not available for the composite run" and "MOD16_DOMAIN_TRUSTED is
+ *               not available for the composite run". n = 0 is MOD16_OK.
+ */
+typedef struct mod16_composite_downscaled_spec {
+    mod16_composite_spec composite;              /* n: the pixels of the range */
+    uint32_t coarse_mask;                        /* bit k: driver k is coarse; bit 14: day_hours */
+    uint32_t reserved_;
+    int64_t coarse_pitch;                        /* elements between two rows of a coarse plane */
+    int64_t first_pixel;                         /* the range's first pixel in the raster */
+} mod16_composite_downscaled_spec;
+MOD16_API int mod16_et_composite_downscaled_f64(mod16_ctx* ctx, const mod16_downscale* grid,
+                                                const mod16_composite_downscaled_spec* spec, const uint8_t* cls,
+                                                const double* const* drivers, const double* day_hours, double* out_et,
+                                                double* out_pet, uint16_t* count_et, uint16_t* count_pet,
+                                                int64_t out_pitch, unsigned flags, int where, void* stream,
+                                                int64_t stage_bytes);
+MOD16_API int mod16_et_composite_downscaled_f32(mod16_ctx* ctx, const mod16_downscale* grid,
+                                                const mod16_composite_downscaled_spec* spec, const uint8_t* cls,
+                                                const float* const* drivers, const float* day_hours, float* out_et,
+                                                float* out_pet, uint16_t* count_et, uint16_t* count_pet,
+                                                int64_t out_pitch, unsigned flags, int where, void* stream,
+                                                int64_t stage_bytes);
 
 #ifdef __cplusplus
 }

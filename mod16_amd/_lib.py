@@ -36,7 +36,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_CLASS_RANGE, ERR_NOMEM, ERR_NO_DEVICE, ERR_NO_BPLUT = \
     -1, -2, -3, -4, -5, -6
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 LIB_NAME = 'libmod16hip.so'
 # MOD16_LIB: alternative build of the same library (kernel experiments only)
 LIB_PATH = os.environ.get('MOD16_LIB') or os.path.join(
@@ -135,6 +135,19 @@ _DOWNSCALED_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I32P, C.c_int64, C
                     C.c_void_p, C.c_uint, C.c_int, C.c_void_p]
 _DOWNSCALE_FIELDS_ARGS = [C.c_void_p, C.c_void_p, _PP, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                           C.c_int64, C.c_int, C.c_void_p]
+
+
+class CompositeDownscaledSpec(C.Structure):
+    '''``mod16_composite_downscaled_spec`` (include/mod16_hip.h): a composite call's spec, which of its
+    15 arrays are series of coarse planes (bit 14: the hours of daylight), their row pitch, and the
+    first pixel of the range.'''
+    _fields_ = [('composite', CompositeSpec), ('coarse_mask', C.c_uint32), ('reserved_', C.c_uint32),
+                ('coarse_pitch', C.c_int64), ('first_pixel', C.c_int64)]
+
+
+_COMPOSITE_DOWNSCALED_ARGS = [C.c_void_p, C.c_void_p, C.POINTER(CompositeDownscaledSpec), C.c_void_p, _PP, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint, C.c_int, C.c_void_p,
+                              C.c_int64]
 
 # name -> (restype, argtypes); one entry per function declared in the header
 PROTOTYPES = {
@@ -336,6 +349,8 @@ PROTOTYPES = {
     'mod16_zonal_bounds_f64': (C.c_int, _ZONAL_BOUNDS_ARGS),
     'mod16_zonal_bounds_f32': (C.c_int, _ZONAL_BOUNDS_ARGS),
     'mod16_zonal_lds_zones': (C.c_int, []),
+    'mod16_et_composite_downscaled_f64': (C.c_int, _COMPOSITE_DOWNSCALED_ARGS),
+    'mod16_et_composite_downscaled_f32': (C.c_int, _COMPOSITE_DOWNSCALED_ARGS),
 }
 
 _lib = None
@@ -548,19 +563,8 @@ class Context:
         '''Thin wrapper of mod16_et_composite_f64 / _f32. ``arrays``, ``pixel_stride``, ``time_stride``
         and ``every`` have 15 entries: the 14 drivers, then the hours of daylight. Every array argument
         is a raw address (int) or None; ``stage_bytes`` None: the library's default.'''
-        for v in list(every) + [days, period_days, min_valid]:
-            if not 0 <= int(v) < 2 ** 31:
-                raise ValueError('days, period_days, min_valid and every must fit an int32, got %r' % (v,))
         spec = CompositeSpec()
-        spec.n, spec.days, spec.period_days = int(n), int(days), int(period_days)
-        spec.min_valid, spec.rescale = int(min_valid), 1 if rescale else 0
-        for k in range(N_DRIVERS):
-            spec.pixel_stride[k] = int(pixel_stride[k])
-            spec.time_stride[k] = int(time_stride[k])
-            spec.every[k] = int(every[k])
-        spec.hours_pixel_stride = int(pixel_stride[N_DRIVERS])
-        spec.hours_time_stride = int(time_stride[N_DRIVERS])
-        spec.hours_every = int(every[N_DRIVERS])
+        fill_composite_spec(spec, n, days, period_days, pixel_stride, time_stride, every, min_valid, rescale)
         fn = typed(self.lib, 'mod16_et_composite', dtype)
         self.check(fn(self.handle, C.byref(spec), cls, ptr_array(list(arrays[:N_DRIVERS])), arrays[N_DRIVERS],
                       out_et, out_pet, count_et, count_pet, int(out_pitch), int(flags), int(where), stream,
@@ -620,6 +624,23 @@ class Context:
         self.check(fn(self.handle, C.byref(spec), values, weights, C.byref(wmax), C.byref(xmax), int(where), stream,
                       0 if stage_bytes is None else int(stage_bytes)))
         return wmax.value, xmax.value
+
+
+def fill_composite_spec(spec, n, days, period_days, pixel_stride, time_stride, every, min_valid, rescale):
+    '''Fills a ``CompositeSpec``; ``pixel_stride``, ``time_stride`` and ``every`` have 15 entries: the 14
+    drivers, then the hours of daylight.'''
+    for v in list(every) + [days, period_days, min_valid]:
+        if not 0 <= int(v) < 2 ** 31:
+            raise ValueError('days, period_days, min_valid and every must fit an int32, got %r' % (v,))
+    spec.n, spec.days, spec.period_days = int(n), int(days), int(period_days)
+    spec.min_valid, spec.rescale = int(min_valid), 1 if rescale else 0
+    for k in range(N_DRIVERS):
+        spec.pixel_stride[k] = int(pixel_stride[k])
+        spec.time_stride[k] = int(time_stride[k])
+        spec.every[k] = int(every[k])
+    spec.hours_pixel_stride = int(pixel_stride[N_DRIVERS])
+    spec.hours_time_stride = int(time_stride[N_DRIVERS])
+    spec.hours_every = int(every[N_DRIVERS])
 
 
 def zonal_lds_zones():
@@ -729,6 +750,21 @@ class Downscale:
         fn = typed(self.ctx.lib, 'mod16_downscale_fields', dtype)
         self.ctx.check(fn(self.ctx.handle, self.handle, ptr_array(list(fields)), len(fields), int(coarse_pitch),
                           int(first_pixel), int(n), out, int(out_pitch), int(where), stream))
+
+    def composite(self, dtype, n, days, period_days, cls, arrays, pixel_stride, time_stride, every, coarse_mask,
+                  coarse_pitch, first_pixel, out_et, out_pet, count_et, count_pet, out_pitch, min_valid=1,
+                  rescale=False, flags=MATH_FAST, where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_et_composite_downscaled_f64 / _f32: the arguments of ``Context.composite``
+        (15 entries per list; raw addresses) and the coarse mask (bit k: array k is a series of coarse
+        planes), their row pitch and the range's first pixel.'''
+        self._open()
+        spec = CompositeDownscaledSpec()
+        fill_composite_spec(spec.composite, n, days, period_days, pixel_stride, time_stride, every, min_valid, rescale)
+        spec.coarse_mask, spec.coarse_pitch, spec.first_pixel = int(coarse_mask), int(coarse_pitch), int(first_pixel)
+        fn = typed(self.ctx.lib, 'mod16_et_composite_downscaled', dtype)
+        self.ctx.check(fn(self.ctx.handle, self.handle, C.byref(spec), cls, ptr_array(list(arrays[:N_DRIVERS])),
+                          arrays[N_DRIVERS], out_et, out_pet, count_et, count_pet, int(out_pitch), int(flags),
+                          int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
 
     def close(self):
         if getattr(self, 'handle', None) and self.handle.value:

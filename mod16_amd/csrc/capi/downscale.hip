@@ -1,14 +1,5 @@
 // libmod16hip.so -- the downscaled forward run: mod16_downscale_create / _create_tables / _destroy (the geometry of a fine raster over a coarse grid), mod16_et_downscaled_* (ET with coarse drivers interpolated per pixel inside the kernel), mod16_downscale_fields_* (the interpolated fields alone)
-#include "host.hpp"
-#include "../mod16_downscale.hpp"
-
-// The corner tables of both axes on the device (mod16_amd/downscale.py: corner_tables).
-struct mod16_downscale {
-    int device = 0;
-    mod16_downscale_spec spec = {};
-    DevMem tables;               // ri0, ri1 (int32 [R]), rw0, rw1 (double [R]), the same four for the columns
-    DsGrid g = {};               // views into `tables`
-};
+#include "downscale_grid.hpp"
 
 namespace {
 constexpr int64_t kDsMaxExtent = int64_t(1) << 30;

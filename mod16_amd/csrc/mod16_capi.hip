@@ -15,4 +15,5 @@
 #include "capi/composite.hip"
 #include "capi/gapfill.hip"
 #include "capi/downscale.hip"
+#include "capi/composite_downscale.hip"
 #include "capi/zonal.hip"

@@ -228,3 +228,114 @@ def check_call(shape, coarse_shape, driver_shapes, coarse=MET_DRIVERS, first_pix
     if cls_size is not None and int(cls_size) != count:
         raise ValueError('the class raster has %d elements, expected %d' % (cls_size, count))
     return kinds, first, count
+
+
+# ---- composites over coarse drivers (``mod16_et_composite_downscaled_*``, ``DownscaleGrid.composite``,
+# ``mod16_amd.evapotranspiration_composite_downscaled``): any of the 15 arrays of
+# ``mod16_amd.composite.ARRAY_NAMES`` -- the 14 drivers and the hours of daylight -- a scalar, a fine
+# array or a coarse array, the last two with or without a time axis
+
+#: a fine array with a leading time axis, a coarse array with one (after KIND_SCALAR, KIND_FINE, KIND_COARSE)
+KIND_FINE_TIME, KIND_COARSE_TIME = 3, 4
+
+
+def check_coarse_arrays(coarse):
+    '''``coarse`` of a composite call over coarse drivers -> the tuple of array names it holds, in the
+    order of ``mod16_amd.composite.ARRAY_NAMES`` (``'day_hours'`` may be among them: the hours of
+    daylight are a function of latitude and day); ValueError for a name that is no array of the
+    call or one named twice.'''
+    from .composite import ARRAY_NAMES
+    if isinstance(coarse, str):
+        raise ValueError('coarse must be a sequence of array names, not a string')
+    names = list(coarse)
+    for name in names:
+        if name not in ARRAY_NAMES:
+            raise ValueError('coarse names %r, which is not one of %s' % (name, ', '.join(ARRAY_NAMES)))
+    if len(set(names)) != len(names):
+        raise ValueError('coarse names an array twice')
+    return tuple(n for n in ARRAY_NAMES if n in names)
+
+
+def coarse_mask(names):
+    '''The C ABI's ``coarse_mask`` of the names ``check_coarse_arrays`` returned: bit k for array k
+    of ``ARRAY_NAMES`` (bit 14: the hours of daylight).'''
+    from .composite import ARRAY_NAMES
+    return sum(1 << ARRAY_NAMES.index(n) for n in names)
+
+
+def coarse_grid_shape(names, array_shapes):
+    '''``(H, W)`` of the coarse grid of a composite call: the last two extents of the arrays named
+    coarse (``array_shapes``: the 15 shapes in ``ARRAY_NAMES`` order), which must be ``(H, W)`` or
+    ``(S, H, W)`` and agree; ``(1, 1)`` where nothing is coarse. ValueError otherwise.'''
+    from .composite import ARRAY_NAMES
+    grid, owner = None, None
+    for name, sh in zip(ARRAY_NAMES, array_shapes):
+        if name not in names:
+            continue
+        sh = tuple(int(x) for x in sh)
+        if len(sh) not in (2, 3):
+            raise ValueError('%s is a coarse array: expected shape (H, W) or (S, H, W), got %r' % (name, sh))
+        if grid is not None and sh[-2:] != grid:
+            raise ValueError('the coarse arrays must share one grid: %s is %r, %s is %r' % (owner, grid, name, sh[-2:]))
+        if grid is None:
+            grid, owner = sh[-2:], name
+    return grid if grid is not None else (1, 1)
+
+
+def check_composite_call(shape, coarse_shape, array_shapes, days, every=None, coarse=MET_DRIVERS, first_pixel=0,
+                         n=None, cls_size=None):
+    '''The shape checks of every composite call over coarse drivers, before any device work.
+
+    ``shape`` = ``(R, C)``, ``coarse_shape`` = ``(H, W)``; ``array_shapes``: the shape of each of the
+    15 arrays of ``ARRAY_NAMES`` (``()`` for a scalar); ``days`` and ``every`` as for the composite
+    (``mod16_amd.composite.check_every``). With ``S = ceil(days / every[name])``, an array named in
+    ``coarse`` must be ``(H, W)`` (constant in time) or ``(S, H, W)``; any other is a scalar, the
+    ``n`` pixels of the range as ``(n,)`` or ``(S, n)``, or -- for the whole raster -- ``(R, C)`` or
+    ``(S, R, C)``. ``cls_size``: the elements of the class raster, which must be ``n``.
+
+    Returns ``(kinds, slabs, first, n)``: per array its kind (``KIND_SCALAR``, ``KIND_FINE``,
+    ``KIND_FINE_TIME``, ``KIND_COARSE``, ``KIND_COARSE_TIME``) and its time slabs (1 without a
+    time axis), and the range as ints. ValueError otherwise.'''
+    from . import composite as _c
+    if len(shape) != 2 or len(coarse_shape) != 2:
+        raise ValueError('shape and coarse_shape must be (rows, columns)')
+    R, C = int(shape[0]), int(shape[1])
+    H, W = int(coarse_shape[0]), int(coarse_shape[1])
+    for v, what in ((R, 'rows'), (C, 'columns'), (H, 'coarse rows'), (W, 'coarse columns')):
+        if v < 1 or v > MAX_EXTENT:
+            raise ValueError('%s must be between 1 and %d, got %d' % (what, MAX_EXTENT, v))
+    names = check_coarse_arrays(coarse)
+    ev = _c.check_every(every)
+    K = _c.check_periods(days, 1)[0]
+    first, count = check_range((R, C), first_pixel, n)
+    whole = first == 0 and count == R * C
+    if len(array_shapes) != len(_c.ARRAY_NAMES):
+        raise ValueError('expected 15 arrays (14 drivers and day_hours), got %d' % len(array_shapes))
+    kinds, slabs = [], []
+    for name, sh in zip(_c.ARRAY_NAMES, array_shapes):
+        sh = tuple(int(x) for x in sh)
+        timed = None
+        if name in names:
+            if sh == (H, W):
+                kinds.append(KIND_COARSE)
+            elif len(sh) == 3 and sh[1:] == (H, W):
+                kinds.append(KIND_COARSE_TIME)
+                timed = sh[0]
+            else:
+                raise ValueError('%s is a coarse array: expected shape %r or (S, %d, %d), got %r' % (name, (H, W), H, W, sh))
+        elif sh == ():
+            kinds.append(KIND_SCALAR)
+        elif sh == (count,) or (sh == (R, C) and whole):
+            kinds.append(KIND_FINE)
+        elif (len(sh) == 2 and sh[1] == count) or (len(sh) == 3 and sh[1:] == (R, C) and whole):
+            kinds.append(KIND_FINE_TIME)
+            timed = sh[0]
+        else:
+            raise ValueError('%s has shape %r: expected a scalar, the %d pixels of the range or the raster %r, '
+                             'each with or without a leading time axis' % (name, sh, count, (R, C)))
+        if timed is not None:
+            _c.check_slabs(name, timed, K, ev[name])
+        slabs.append(1 if timed is None else timed)
+    if cls_size is not None and int(cls_size) != count:
+        raise ValueError('the class raster has %d elements, expected %d' % (cls_size, count))
+    return kinds, slabs, first, count

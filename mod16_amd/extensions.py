@@ -309,6 +309,116 @@ def evapotranspiration_downscaled(
     return (outs[0], outs[1])
 
 
+def evapotranspiration_composite_downscaled(
+        bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
+        sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
+        vpd_night, pressure, fpar, lai, day_hours, row_pos, col_pos, days=None, period_days=8, every=None,
+        wrap=False, method='bilinear', coarse=_MET_DRIVERS, pet=False, min_valid=1, rescale=False, beta=None,
+        math=_lib.MATH_FAST, device=0, out=None, stage_bytes=None):
+    r'''
+    (Extension.) Multi-day ET composites over a multi-class raster whose reanalysis drivers stay on
+    their own coarse grid: what ``evapotranspiration_composite`` returns on arrays blown up to the
+    fine grid slab by slab with ``mod16_amd.downscale.interpolate``, bit for bit, counts included,
+    without those arrays ever existing -- a year of daily reanalysis is 11 x 365 coarse planes, not
+    88 bytes per pixel and day (``mod16_et_composite_downscaled_*``). The definitions are
+    ``mod16_amd.composite`` and ``mod16_amd.downscale``.
+
+    Parameters
+    ----------
+    bplut, beta
+        as for ``evapotranspiration_raster``
+    cls : numpy.ndarray
+        ``(R, C)`` class raster: the fine grid
+    the 14 drivers, day_hours
+        an array named in ``coarse`` is an ``(H, W)`` array on the coarse grid (constant in time) or
+        an ``(S, H, W)`` array, one grid for all of them; any other is a scalar, an ``(R, C)`` array
+        or an ``(S, R, C)`` array. ``S = ceil(days / every[name])``: day ``t`` reads slab
+        ``t // every[name]``
+    row_pos, col_pos, wrap, method
+        the geometry, as for ``evapotranspiration_downscaled``
+    days, period_days, every, pet, min_valid, rescale
+        as for ``evapotranspiration_composite``
+    coarse : sequence of str
+        the names of the coarse arrays (Default: ``mod16_amd.downscale.MET_DRIVERS``);
+        ``'day_hours'`` may be among them
+    math : int
+        ``MATH_FAST`` (default) or ``MATH_EXACT``
+    out : sequence of numpy.ndarray
+        (Optional) the 2 (``pet``: 4) arrays ``(P, R, C)`` to write into
+    stage_bytes : int
+        (Optional) device memory a staging slot of the fine arrays may take (default 128 MiB); the
+        result does not depend on it. The coarse arrays are uploaded whole, once
+
+    Returns
+    -------
+    CompositeET or CompositeETPET
+        ``(et, count)`` or ``(et, pet, count_et, count_pet)``, each ``(P, R, C)`` with ``P =
+        ceil(days / period_days)``; counts are uint16. float32 only if every array input is float32
+        (interpolated, computed and summed in float64, rounded once). A NaN coarse cell makes that
+        day invalid at the pixels where the cell has weight; a class code >= 13 raises IndexError.
+    '''
+    from . import composite as _c, downscale as _d
+    from .utils import as_bplut_table
+    arrays = [lw_net_day, lw_net_night, sw_rad_day, sw_rad_night, sw_albedo,
+              temp_day, temp_night, temp_annual, tmin, vpd_day, vpd_night,
+              pressure, fpar, lai, day_hours]
+    ev = _c.check_every(every)
+    names = _d.check_coarse_arrays(coarse)
+    _d.method_code(method)
+    cls = np.asarray(cls)
+    if cls.ndim != 2:
+        raise ValueError('cls must be an (R, C) raster, got shape %r' % (cls.shape,))
+    shape = cls.shape
+    shapes = [_shape(v) if name in names or np.size(v) != 1 else () for name, v in zip(_c.ARRAY_NAMES, arrays)]
+    coarse_shape = _d.coarse_grid_shape(names, shapes)
+    for pos, count, what in ((row_pos, shape[0], 'row_pos'), (col_pos, shape[1], 'col_pos')):
+        if np.shape(pos) != (count,):
+            raise ValueError('%s has shape %r, expected (%d,)' % (what, np.shape(pos), count))
+    if days is None:
+        daily = [sh[0] for name, sh in zip(_c.ARRAY_NAMES, shapes)
+                 if ev[name] == 1 and len(sh) == 3 and (name in names or tuple(sh[1:]) == tuple(shape))]
+        if not daily:
+            raise ValueError('days is required when no array has a daily time axis')
+        days = int(daily[0])
+    K, L, mv, P = _c.check_periods(days, period_days, min_valid)
+    kinds, slabs, _, n = _d.check_composite_call(shape, coarse_shape, shapes, K, ev, coarse=names, cls_size=cls.size)
+    if int(math) & ~_lib.MATH_EXACT:
+        raise ValueError('math must be MATH_FAST or MATH_EXACT for the composite run')
+    _check_stage_bytes(stage_bytes)
+    row_tables = _d.corner_tables(row_pos, coarse_shape[0], False, method)
+    col_tables = _d.corner_tables(col_pos, coarse_shape[1], bool(wrap), method)
+    dtype = _result_dtype(arrays)
+    cls = np.ascontiguousarray(_as_uint8(cls))
+    full = (P,) + tuple(shape)
+    half = 2 if pet else 1
+    outs = _outputs(out, full, [dtype] * half + [_U16] * half, pinned=False, indexed=True)
+    table = as_bplut_table(bplut, beta)
+    plane = coarse_shape[0] * coarse_shape[1]
+    keep, ptrs, pstride, tstride, divisor = [], [], [], [], []
+    for name, v, kind, S in zip(_c.ARRAY_NAMES, arrays, kinds, slabs):
+        a = np.array(v, dtype).reshape(1) if kind == _d.KIND_SCALAR else np.ascontiguousarray(v, dtype)
+        keep.append(a)
+        ptrs.append(a.ctypes.data)
+        pstride.append(1 if kind in (_d.KIND_FINE, _d.KIND_FINE_TIME) else 0)
+        timed = kind in (_d.KIND_FINE_TIME, _d.KIND_COARSE_TIME)
+        tstride.append(0 if S <= 1 else plane if kind == _d.KIND_COARSE_TIME else n)
+        divisor.append(ev[name] if timed else K)
+    ctx = _lib.context(device)
+    ctx.set_bplut(table)
+    grid = _lib.Downscale(ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
+                          tables=(row_tables, col_tables))
+    try:
+        optr = [o.ctypes.data for o in outs]
+        et, pt = (optr[0], optr[1]) if pet else (optr[0], None)
+        c_et, c_pt = (optr[2], optr[3]) if pet else (optr[1], None)
+        grid.composite(dtype, n, K, L, cls.ctypes.data, ptrs, pstride, tstride, divisor, _d.coarse_mask(names),
+                       coarse_shape[1], 0, et, pt, c_et, c_pt, n, min_valid=mv, rescale=rescale, flags=math,
+                       where=_lib.HOST, stage_bytes=stage_bytes)
+    finally:
+        grid.close()
+    return (CompositeETPET if pet else CompositeET)(*outs)
+
+
 def gapfill_series(fields, qc=None, good=None, max_gap=None, fallback=None, dtype='uint8', scale=None,
                    source=False, device=0, stage_bytes=None):
     r'''

@@ -339,6 +339,100 @@ class DownscaleGrid(object):
                               opitch, where=_lib.DEVICE, stream=eng._stream())
         return out
 
+    def _coarse_series(self, t, what):
+        '''-> (address, row pitch, time stride in elements, slabs) of an (H, W) or (S, H, W) tensor with
+        unit stride in columns'''
+        eng, torch = self.engine, _torch()
+        H, W = self.coarse_shape
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != eng.device or t.dtype != eng.dtype:
+            raise TypeError('%s must be a %s tensor on cuda:%d' % (what, eng.dtype, eng.device))
+        if t.dim() == 2:
+            ptr, pitch = self._coarse_tensor(t, what)
+            return ptr, pitch, 0, 1
+        if t.dim() != 3 or tuple(t.shape[1:]) != (H, W):
+            raise ValueError('%s is a coarse array: expected shape %r or (S, %d, %d), got %r'
+                             % (what, (H, W), H, W, tuple(t.shape)))
+        ptr, pitch = self._coarse_tensor(t[0], what)
+        slabs = t.shape[0]
+        if slabs > 1 and t.stride(0) < (H - 1) * pitch + W:
+            raise ValueError('%s: the stride in time must be at least a plane (%d elements)' % (what, (H - 1) * pitch + W))
+        return ptr, pitch, t.stride(0) if slabs > 1 else 0, slabs
+
+    def composite(self, cls, drivers, day_hours, days, period_days=8, every=None, coarse=MET_DRIVERS, first_pixel=0,
+                  pet=False, min_valid=1, rescale=False, out=None):
+        '''Enqueue the composite over coarse drivers on the current stream: what
+        ``RasterEngine.composite`` returns for the ``n = cls.numel()`` pixels ``[first_pixel,
+        first_pixel + n)`` of the raster (row-major) when each array named in ``coarse`` is
+        materialised slab by slab with ``mod16_amd.downscale.interpolate`` -- bit for bit, counts
+        included, without those ``(S, n)`` arrays ever existing (``mod16_et_composite_downscaled_*``).
+
+        ``coarse`` names arrays of ``mod16_amd.composite.ARRAY_NAMES`` (default: the eleven reanalysis
+        drivers; ``'day_hours'`` may be among them). A coarse array is an ``(H, W)`` tensor (constant in
+        time) or an ``(S, H, W)`` tensor with ``S = ceil(days / every[name])``, unit stride in columns,
+        one row pitch >= W for all of them and any stride in time of at least a plane (views of
+        larger tensors are fine). Every other array is what ``RasterEngine.composite`` takes: a
+        scalar, an ``(n,)`` or an ``(S, n)`` tensor of the range's pixels. ``days``, ``period_days``,
+        ``every``, ``pet``, ``min_valid``, ``rescale`` and ``out`` as there; returns what it returns.
+        Asynchronous: call the engine's ``check()`` before trusting the data; a class code >= 13
+        raises IndexError there.'''
+        from . import composite as _c, downscale as _d
+        eng, torch = self.engine, _torch()
+        K, L, mv, P = _c.check_periods(days, period_days, min_valid)
+        ev = _c.check_every(every)
+        if eng.math & ~_lib.MATH_EXACT:
+            raise ValueError('composite needs an engine with MATH_FAST or MATH_EXACT (no MATH_MIXED, not trusted)')
+        names = _d.check_coarse_arrays(coarse)
+        if len(drivers) != _lib.N_DRIVERS:
+            raise ValueError('expected 14 drivers')
+        arrays = list(drivers) + [day_hours]
+        n = cls.numel()
+        shapes = [tuple(d.shape) if isinstance(d, torch.Tensor) and (name in names or d.dim() > 0) else ()
+                  for name, d in zip(_c.ARRAY_NAMES, arrays)]
+        kinds, slabs, first, n = _d.check_composite_call(self.shape, self.coarse_shape, shapes, K, ev, coarse=names,
+                                                         first_pixel=first_pixel, n=n, cls_size=n)
+        cptr = eng._check_tensor(cls, torch.uint8, n, 'cls')
+        keep, ptrs, pstride, tstride, divisor, cpitch = [], [], [], [], [], None
+        for name, d, kind, S in zip(_c.ARRAY_NAMES, arrays, kinds, slabs):
+            timed = kind in (_d.KIND_FINE_TIME, _d.KIND_COARSE_TIME)
+            if kind in (_d.KIND_COARSE, _d.KIND_COARSE_TIME):
+                ptr, row, ts, _ = self._coarse_series(d, name)
+                if cpitch is not None and row != cpitch:
+                    raise ValueError('the coarse arrays must share one distance between rows')
+                cpitch = row
+                pstride.append(0)
+            elif kind == _d.KIND_SCALAR:
+                d = torch.as_tensor(d, dtype=eng.dtype).reshape(1).to(eng._dev())
+                ptr, ts = d.data_ptr(), 0
+                pstride.append(0)
+            elif kind == _d.KIND_FINE:
+                ptr, ts = eng._check_tensor(d, eng.dtype, n, name), 0
+                pstride.append(1)
+            else:
+                if not d.is_cuda or d.device.index != eng.device or d.dtype != eng.dtype:
+                    raise TypeError('%s must be a %s tensor on cuda:%d' % (name, eng.dtype, eng.device))
+                if d.dim() > 2:
+                    raise ValueError('%s must be a scalar, an (n,) or an (S, n) tensor with n = %d, got %r'
+                                     % (name, n, tuple(d.shape)))
+                if n > 1 and d.stride(-1) != 1:
+                    raise ValueError('%s must have unit stride in pixels' % name)
+                if S > 1 and d.stride(0) < n:
+                    raise ValueError('%s: the stride in time must be at least n' % name)
+                ptr, ts = d.data_ptr(), (d.stride(0) if S > 1 else 0)
+                pstride.append(1)
+            keep.append(d)
+            ptrs.append(ptr)
+            tstride.append(ts)
+            divisor.append(ev[name] if timed else K)
+        out, pitch = eng._composite_outputs(out, P, n, pet)
+        if n:
+            optr = [o.data_ptr() for o in out]
+            et, pt = (optr[0], optr[1]) if pet else (optr[0], None)
+            c_et, c_pt = (optr[2], optr[3]) if pet else (optr[1], None)
+            self._grid.composite(eng.np_dtype, n, K, L, cptr, ptrs, pstride, tstride, divisor, _d.coarse_mask(names),
+                                 cpitch or self.coarse_shape[1], first, et, pt, c_et, c_pt, pitch, min_valid=mv,
+                                 rescale=rescale, flags=eng.math, where=_lib.DEVICE, stream=eng._stream())
+        return out
+
     def close(self):
         self._grid.close()
 
@@ -615,6 +709,20 @@ class RasterEngine(object):
                 pstride.append(0)
                 tstride.append(0)
                 divisor.append(K)
+        out, pitch = self._composite_outputs(out, P, n, pet)
+        if n:
+            optr = [o.data_ptr() for o in out]
+            et, pt = (optr[0], optr[1]) if pet else (optr[0], None)
+            c_et, c_pt = (optr[2], optr[3]) if pet else (optr[1], None)
+            self.ctx.composite(self.np_dtype, n, K, L, cptr, ptrs, pstride, tstride, divisor, et, pt, c_et, c_pt,
+                               pitch, min_valid=mv, rescale=rescale, flags=self.math, where=_lib.DEVICE,
+                               stream=self._stream())
+        return out
+
+    def _composite_outputs(self, out, P, n, pet):
+        '''The 2 (``pet``: 4) ``(P, n)`` result tensors of a composite call -- new ones, or the caller's
+        ``out`` after a check -- and their common distance between rows.'''
+        torch = _torch()
         want = 4 if pet else 2
         if out is None:
             out = [torch.empty((P, n), dtype=self.dtype, device=self._dev()) for _ in range(want // 2)] + \
@@ -633,14 +741,7 @@ class RasterEngine(object):
             if row < n or (pitch is not None and row != pitch):
                 raise ValueError('the out tensors must share one distance between rows, at least n')
             pitch = row
-        if n:
-            optr = [o.data_ptr() for o in out]
-            et, pt = (optr[0], optr[1]) if pet else (optr[0], None)
-            c_et, c_pt = (optr[2], optr[3]) if pet else (optr[1], None)
-            self.ctx.composite(self.np_dtype, n, K, L, cptr, ptrs, pstride, tstride, divisor, et, pt, c_et, c_pt,
-                               pitch, min_valid=mv, rescale=rescale, flags=self.math, where=_lib.DEVICE,
-                               stream=self._stream())
-        return out
+        return out, pitch
 
     def downscale_grid(self, shape, coarse_shape, row_pos, col_pos, wrap=False, method='bilinear'):
         '''The geometry of an ``R x C`` fine raster (``shape``) over an ``H x W`` coarse grid

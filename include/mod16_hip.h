@@ -1157,7 +1157,7 @@ MOD16_API int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, c
  *
  *   geometry    row_pos[rows], col_pos[cols] (HOST pointers, float64): the position of every fine row
  *               / column in units of coarse cells, cell centres at the integers. Rectilinear grids
- *               only. Per axis and entry, two cells and two weights:
+ *               (row-affine columns: below). Per axis and entry, two cells and two weights:
  *                 held edge (rows; columns with wrap_cols = 0): p = min(max(pos, 0), size - 1),
  *                   i0 = floor(p), f = p - i0, i1 = min(i0 + 1, size - 1);
  *                 wrap_cols = 1 (the longitude axis of a global grid): p = pos - floor(pos / size) size,
@@ -1203,6 +1203,31 @@ MOD16_API int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, c
  *               1 and 16"; a grid of another device; an unknown flag; "MOD16_MATH_MIXED is not
  *               available for the downscaled run" and "MOD16_DOMAIN_TRUSTED is not available for the
  *               downscaled run". n = 0 is MOD16_OK.
+ *
+ * Row-affine columns (additive in ABI 16; mod16_amd.downscale.corner_tables_rows, sinusoidal_positions;
+ * `col_affine` of the Python layer): a second geometry of the same handle for fine grids whose column
+ * mapping depends on the row -- MODIS sinusoidal tiles, where the longitude of column c is
+ * x / (R cos(lat_row)). The column position of pixel (r, c) is
+ *
+ *     col_pos(r, c) = col_origin[r] + col_scale[r] * c        (one multiplication, one addition, each rounded)
+ *
+ *   geometry    mod16_downscale_create_rows(row_pos[rows], col_origin[rows], col_scale[rows]) computes the
+ *               row tables on the host as mod16_downscale_create does; mod16_downscale_create_rows_tables
+ *               takes the caller's row tables as mod16_downscale_create_tables does. The handle owns
+ *               device copies of the row tables and of the two float64 per row; the column cell pair and
+ *               its weights are formed per pixel inside the kernel by the formulas of "geometry" above
+ *               (wrap_cols and method of the spec govern them), in float64 with multiply, add, a correctly
+ *               rounded division, floor and compare, no contraction: the bits of the numpy definition.
+ *   use         mod16_et_downscaled_*, mod16_downscale_fields_* and mod16_et_composite_downscaled_* accept
+ *               a handle of either geometry and pick their kernel instances by it; everything said of
+ *               them above and below holds unchanged (ranges, pitches, HOST and DEVICE).
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_downscale_create: ...")
+ *               a NULL argument; the spec as above; MOD16_DOWNSCALE_COS4 (its weights need a cosine, which
+ *               the device would not reproduce bit for bit); a row position that is not finite, a row
+ *               table index outside the coarse grid or a weight that is not finite; a row r whose
+ *               col_origin[r], col_scale[r] or col_origin[r] + col_scale[r] * (cols - 1) is not finite
+ *               (finite end points make every position of the row finite). Whatever the arithmetic
+ *               gives, the kernels clamp the computed cell index into [0, coarse_cols).
  */
 enum mod16_downscale_method { MOD16_DOWNSCALE_NEAREST = 0, MOD16_DOWNSCALE_BILINEAR = 1, MOD16_DOWNSCALE_COS4 = 2 };
 typedef struct mod16_downscale_spec {
@@ -1218,6 +1243,12 @@ MOD16_API int mod16_downscale_create_tables(mod16_ctx* ctx, const mod16_downscal
                                             const int32_t* row_i1, const double* row_w0, const double* row_w1,
                                             const int32_t* col_i0, const int32_t* col_i1, const double* col_w0,
                                             const double* col_w1, mod16_downscale** grid);
+MOD16_API int mod16_downscale_create_rows(mod16_ctx* ctx, const mod16_downscale_spec* spec, const double* row_pos,
+                                          const double* col_origin, const double* col_scale, mod16_downscale** grid);
+MOD16_API int mod16_downscale_create_rows_tables(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int32_t* row_i0,
+                                                 const int32_t* row_i1, const double* row_w0, const double* row_w1,
+                                                 const double* col_origin, const double* col_scale,
+                                                 mod16_downscale** grid);
 MOD16_API int mod16_downscale_destroy(mod16_downscale* grid);
 MOD16_API int mod16_et_downscaled_f64(mod16_ctx* ctx, const mod16_downscale* grid, const uint8_t* cls,
                                       const double* const* drivers, const int32_t* kinds, int64_t coarse_pitch,

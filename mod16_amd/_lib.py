@@ -339,6 +339,10 @@ PROTOTYPES = {
                                          C.POINTER(C.c_void_p)]),
     'mod16_downscale_create_tables': (C.c_int, [C.c_void_p, C.POINTER(DownscaleSpec)] + [C.c_void_p] * 8 +
                                       [C.POINTER(C.c_void_p)]),
+    'mod16_downscale_create_rows': (C.c_int, [C.c_void_p, C.POINTER(DownscaleSpec)] + [C.c_void_p] * 3 +
+                                    [C.POINTER(C.c_void_p)]),
+    'mod16_downscale_create_rows_tables': (C.c_int, [C.c_void_p, C.POINTER(DownscaleSpec)] + [C.c_void_p] * 6 +
+                                           [C.POINTER(C.c_void_p)]),
     'mod16_downscale_destroy': (C.c_int, [C.c_void_p]),
     'mod16_et_downscaled_f64': (C.c_int, _DOWNSCALED_ARGS),
     'mod16_et_downscaled_f32': (C.c_int, _DOWNSCALED_ARGS),
@@ -707,26 +711,40 @@ class Downscale:
     '''The geometry of a fine raster over a coarse grid on a context's device (``mod16_downscale``):
     the corner tables of ``mod16_amd.downscale.corner_tables`` for both axes, computed here in numpy
     and handed to ``mod16_downscale_create_tables``, so that the device's interpolation carries the
-    bits of the numpy definition.'''
+    bits of the numpy definition. With ``col_affine = (col_origin, col_scale)`` in place of ``col_pos``
+    (row-affine columns: ``mod16_amd.downscale.corner_tables_rows``) the rows keep their numpy tables,
+    ``col_tables`` is None and the handle comes from ``mod16_downscale_create_rows_tables``.'''
 
-    def __init__(self, ctx, shape, coarse_shape, row_pos, col_pos, wrap=False, method='bilinear', tables=None):
+    def __init__(self, ctx, shape, coarse_shape, row_pos, col_pos=None, wrap=False, method='bilinear', tables=None,
+                 col_affine=None):
         from . import downscale as _d
+        if (col_pos is None) == (col_affine is None):
+            raise ValueError('exactly one of col_pos and col_affine must be given')
         _d.check_call(shape, coarse_shape, [()] * N_DRIVERS, coarse=(), method=method, row_pos=row_pos,
                       col_pos=col_pos)
         self.shape = (int(shape[0]), int(shape[1]))
         self.coarse_shape = (int(coarse_shape[0]), int(coarse_shape[1]))
         self.wrap, self.method = bool(wrap), method
+        self.col_affine = None
+        if col_affine is not None:      # row-affine columns: the device forms the column pair per pixel
+            self.col_affine = _d.check_affine(self.shape, col_affine[0], col_affine[1], method)
         if tables is not None:          # (another context's grid of the same call: computed once)
             self.row_tables, self.col_tables = tables
         else:
             self.row_tables = _d.corner_tables(row_pos, self.coarse_shape[0], False, method)
-            self.col_tables = _d.corner_tables(col_pos, self.coarse_shape[1], self.wrap, method)
+            self.col_tables = None if col_affine is not None else \
+                _d.corner_tables(col_pos, self.coarse_shape[1], self.wrap, method)
         rt = _d.check_tables(self.row_tables, self.shape[0], self.coarse_shape[0], 'row')
-        ct = _d.check_tables(self.col_tables, self.shape[1], self.coarse_shape[1], 'column')
         spec = DownscaleSpec(self.shape[0], self.shape[1], self.coarse_shape[0], self.coarse_shape[1],
                              1 if self.wrap else 0, _d.method_code(method))
         self.ctx = ctx                  # keeps the context alive as long as its grid
         self.handle = C.c_void_p()
+        if self.col_affine is not None:
+            ctx.check(ctx.lib.mod16_downscale_create_rows_tables(
+                ctx.handle, C.byref(spec), *([t.ctypes.data for t in rt] + [t.ctypes.data for t in self.col_affine]),
+                C.byref(self.handle)))
+            return
+        ct = _d.check_tables(self.col_tables, self.shape[1], self.coarse_shape[1], 'column')
         ctx.check(ctx.lib.mod16_downscale_create_tables(
             ctx.handle, C.byref(spec), *([t.ctypes.data for t in rt] + [t.ctypes.data for t in ct]),
             C.byref(self.handle)))

@@ -12,29 +12,42 @@ template <typename T> struct CdCall {
     int64_t stage_bytes;
 };
 
-// All pointers are device pointers here.
+// the kernels of one geometry (G: DsGrid or DsRowsGrid)
+template <typename T, typename G>
+static void launch_composite_downscaled_on(const CdArgs<T>& a, const G& g, int blocks, bool pet, unsigned flags, hipStream_t st) {
+    CdArgs<T, G> b;
+    memset(&b, 0, sizeof b);
+    b.c = a.c;
+    b.coarse = a.coarse;
+    b.g = g;
+    b.cpitch = a.cpitch;
+    b.first = a.first;
+    if (flags & MOD16_MATH_EXACT) {
+        if (pet) hipLaunchKernelGGL((cd_kernel<T, false, true, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+        else hipLaunchKernelGGL((cd_kernel<T, false, false, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+    } else if (pet) {
+        hipLaunchKernelGGL((cd_kernel<T, true, true, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+        // pixels with a day outside the domain of the fast arithmetic: the kernel above left a mark
+        // in period 0 of their out_et, this one computes all their periods
+        hipLaunchKernelGGL((cd_redo_kernel<T, true, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+    } else {
+        hipLaunchKernelGGL((cd_kernel<T, true, false, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+        hipLaunchKernelGGL((cd_redo_kernel<T, false, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+    }
+}
+
+// All pointers are device pointers here. The handle's geometry picks the instances.
 template <typename T>
 static int launch_composite_downscaled(mod16_ctx* ctx, const mod16_downscale* grid, CdArgs<T> a, bool pet, unsigned flags,
                                        hipStream_t st) {
     if (a.c.n <= 0) return MOD16_OK;
-    a.g = grid->g;
     a.c.lut64 = ctx->lut64.as<double>();
     a.c.tab = ctx->tab64.as<double>();
     a.c.status = ctx->status.as<unsigned>();
     const int64_t nbatch = (a.c.n + kBlock - 1) / kBlock;
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t)ctx->cus * 8));
-    if (flags & MOD16_MATH_EXACT) {
-        if (pet) hipLaunchKernelGGL((cd_kernel<T, false, true>), dim3(blocks), dim3(kBlock), 0, st, a);
-        else hipLaunchKernelGGL((cd_kernel<T, false, false>), dim3(blocks), dim3(kBlock), 0, st, a);
-    } else if (pet) {
-        hipLaunchKernelGGL((cd_kernel<T, true, true>), dim3(blocks), dim3(kBlock), 0, st, a);
-        // pixels with a day outside the domain of the fast arithmetic: the kernel above left a mark
-        // in period 0 of their out_et, this one computes all their periods
-        hipLaunchKernelGGL((cd_redo_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((cd_kernel<T, true, false>), dim3(blocks), dim3(kBlock), 0, st, a);
-        hipLaunchKernelGGL((cd_redo_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, st, a);
-    }
+    if (grid->affine) launch_composite_downscaled_on<T, DsRowsGrid>(a, grid->gr, blocks, pet, flags, st);
+    else launch_composite_downscaled_on<T, DsGrid>(a, grid->g, blocks, pet, flags, st);
     HIPCHK(ctx, hipGetLastError());
     return MOD16_OK;
 }

@@ -1,4 +1,4 @@
-// libmod16hip.so -- the downscaled forward run: mod16_downscale_create / _create_tables / _destroy (the geometry of a fine raster over a coarse grid), mod16_et_downscaled_* (ET with coarse drivers interpolated per pixel inside the kernel), mod16_downscale_fields_* (the interpolated fields alone)
+// libmod16hip.so -- the downscaled forward run: mod16_downscale_create / _create_tables / _create_rows / _create_rows_tables / _destroy (the geometry of a fine raster over a coarse grid), mod16_et_downscaled_* (ET with coarse drivers interpolated per pixel inside the kernel), mod16_downscale_fields_* (the interpolated fields alone)
 #include "downscale_grid.hpp"
 
 namespace {
@@ -167,27 +167,136 @@ extern "C" int mod16_downscale_create_tables(mod16_ctx* ctx, const mod16_downsca
     return ds_build(ctx, spec, ri, rw, ci, cw, out);
 }
 
+// The row-affine geometry: validated row tables and per-row (origin, scale) -> a handle with their
+// device copies. Every check runs before any device work.
+static int ds_build_rows(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int32_t* const* ri, const double* const* rw,
+                         const double* origin, const double* scale, mod16_downscale** out) {
+#pragma clang fp contract(off)
+    auto bad = [&](const char* what) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
+        return fail(ctx, MOD16_ERR_ARG, msg);
+    };
+    const int64_t R = spec->rows, C = spec->cols;
+    if (!ds_tables_valid(ri[0], ri[1], rw[0], rw[1], R, spec->coarse_rows))
+        return bad("a row table holds an index outside the coarse grid or a weight that is not finite");
+    const double far = (double)(C - 1);
+    for (int64_t r = 0; r < R; ++r) {
+        if (!std::isfinite(origin[r])) return bad("col_origin holds a value that is not finite");
+        if (!std::isfinite(scale[r])) return bad("col_scale holds a value that is not finite");
+        const double step = scale[r] * far;
+        const double end = origin[r] + step;
+        if (!std::isfinite(end)) return bad("col_origin + col_scale * (cols - 1) is not finite in some row");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    mod16_downscale* g = new (std::nothrow) mod16_downscale;
+    if (!g) return MOD16_ERR_NOMEM;
+    g->device = ctx->device;
+    g->spec = *spec;
+    g->affine = true;
+    const size_t ib = align256((size_t)R * sizeof(int32_t)), wb = align256((size_t)R * sizeof(double));
+    int rc = g->tables.alloc(ctx, 2 * ib + 4 * wb, "mod16_downscale_create: device memory for the corner tables");
+    if (rc == MOD16_OK) {
+        char* base = g->tables.as<char>();
+        char* at[6] = {base, base + ib, base + 2 * ib, base + 2 * ib + wb, base + 2 * ib + 2 * wb, base + 2 * ib + 3 * wb};
+        const void* src[6] = {ri[0], ri[1], rw[0], rw[1], origin, scale};
+        const size_t bytes[6] = {(size_t)R * 4, (size_t)R * 4, (size_t)R * 8, (size_t)R * 8, (size_t)R * 8, (size_t)R * 8};
+        for (int k = 0; k < 6 && rc == MOD16_OK; ++k)
+            if (hipMemcpy(at[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess)
+                rc = fail(ctx, MOD16_ERR_HIP, "mod16_downscale_create: upload of the corner tables failed");
+        g->gr.ri0 = reinterpret_cast<const int32_t*>(at[0]);
+        g->gr.ri1 = reinterpret_cast<const int32_t*>(at[1]);
+        g->gr.rw0 = reinterpret_cast<const double*>(at[2]);
+        g->gr.rw1 = reinterpret_cast<const double*>(at[3]);
+        g->gr.origin = reinterpret_cast<const double*>(at[4]);
+        g->gr.scale = reinterpret_cast<const double*>(at[5]);
+        g->gr.cols = (int32_t)C;
+        g->gr.width = (int32_t)spec->coarse_cols;
+        g->gr.wrap = spec->wrap_cols != 0;
+        g->gr.nearest = spec->method == MOD16_DOWNSCALE_NEAREST;
+    }
+    if (rc != MOD16_OK) {
+        mod16_downscale_destroy(g);
+        return rc;
+    }
+    *out = g;
+    return MOD16_OK;
+}
+
+// the spec of a row-affine grid: as ds_check_spec, and no 'cos4' (its weights need a cosine; the
+// device forms this geometry's column weights with multiply, add, divide, floor and compare)
+static const char* ds_check_spec_rows(const mod16_downscale_spec* s) {
+    if (const char* what = ds_check_spec(s)) return what;
+    if (s->method == MOD16_DOWNSCALE_COS4)
+        return "MOD16_DOWNSCALE_COS4 is not available with row-affine columns (MOD16_DOWNSCALE_NEAREST or MOD16_DOWNSCALE_BILINEAR)";
+    return nullptr;
+}
+
+extern "C" int mod16_downscale_create_rows(mod16_ctx* ctx, const mod16_downscale_spec* spec, const double* row_pos,
+                                           const double* col_origin, const double* col_scale, mod16_downscale** out) {
+    MOD16_LOCK(ctx);
+    if (!ctx) return MOD16_ERR_ARG;
+    if (out) *out = nullptr;
+    auto bad = [&](const char* what) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
+        return fail(ctx, MOD16_ERR_ARG, msg);
+    };
+    if (!row_pos || !col_origin || !col_scale || !out) return bad("NULL argument");
+    if (const char* what = ds_check_spec_rows(spec)) return bad(what);
+    DsAxis r;
+    if (!ds_axis_tables(row_pos, spec->rows, spec->coarse_rows, false, spec->method, r)) return bad("row_pos holds a value that is not finite");
+    const int32_t* ri[2] = {r.i0.data(), r.i1.data()};
+    const double* rw[2] = {r.w0.data(), r.w1.data()};
+    return ds_build_rows(ctx, spec, ri, rw, col_origin, col_scale, out);
+}
+
+extern "C" int mod16_downscale_create_rows_tables(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int32_t* row_i0,
+                                                  const int32_t* row_i1, const double* row_w0, const double* row_w1,
+                                                  const double* col_origin, const double* col_scale,
+                                                  mod16_downscale** out) {
+    MOD16_LOCK(ctx);
+    if (!ctx) return MOD16_ERR_ARG;
+    if (out) *out = nullptr;
+    if (!row_i0 || !row_i1 || !row_w0 || !row_w1 || !col_origin || !col_scale || !out)
+        return fail(ctx, MOD16_ERR_ARG, "mod16_downscale_create: NULL argument");
+    if (const char* what = ds_check_spec_rows(spec)) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
+        return fail(ctx, MOD16_ERR_ARG, msg);
+    }
+    const int32_t* ri[2] = {row_i0, row_i1};
+    const double* rw[2] = {row_w0, row_w1};
+    return ds_build_rows(ctx, spec, ri, rw, col_origin, col_scale, out);
+}
+
 static int ds_grid_size(const mod16_ctx* ctx, int64_t n) {
     const int64_t nbatch = (n + kBlock - 1) / kBlock;
     return (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t)ctx->cus * 8));
 }
 
-// All pointers are device pointers here.
+// the kernels of one geometry (G: DsGrid or DsRowsGrid)
+template <typename T, typename G>
+static void launch_downscaled_on(const DsArgs<T, G>& a, int blocks, unsigned flags, hipStream_t st) {
+    if (flags & MOD16_MATH_EXACT) hipLaunchKernelGGL((ds_kernel<T, false, G>), dim3(blocks), dim3(kBlock), 0, st, a);
+    else {
+        hipLaunchKernelGGL((ds_kernel<T, true, G>), dim3(blocks), dim3(kBlock), 0, st, a);
+        // pixels outside the domain of the fast arithmetic: the kernel above left a mark in their
+        // out_night, this one computes them in the reference's operation order
+        hipLaunchKernelGGL((ds_redo_kernel<T, G>), dim3(blocks), dim3(kBlock), 0, st, a);
+    }
+}
+
+// All pointers are device pointers here. The handle's geometry picks the instances.
 template <typename T>
 static int launch_downscaled(mod16_ctx* ctx, const mod16_downscale* grid, DsArgs<T> a, unsigned flags, hipStream_t st) {
     if (a.n <= 0) return MOD16_OK;
-    a.g = grid->g;
     a.lut64 = ctx->lut64.as<double>();
     a.tab = ctx->tab64.as<double>();
     a.status = ctx->status.as<unsigned>();
     const int blocks = ds_grid_size(ctx, a.n);
-    if (flags & MOD16_MATH_EXACT) hipLaunchKernelGGL((ds_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, st, a);
-    else {
-        hipLaunchKernelGGL((ds_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, st, a);
-        // pixels outside the domain of the fast arithmetic: the kernel above left a mark in their
-        // out_night, this one computes them in the reference's operation order
-        hipLaunchKernelGGL((ds_redo_kernel<T>), dim3(blocks), dim3(kBlock), 0, st, a);
-    }
+    if (grid->affine) launch_downscaled_on<T, DsRowsGrid>(ds_with_grid<T, DsRowsGrid>(a, grid->gr), blocks, flags, st);
+    else launch_downscaled_on<T, DsGrid>(ds_with_grid<T, DsGrid>(a, grid->g), blocks, flags, st);
     HIPCHK(ctx, hipGetLastError());
     return MOD16_OK;
 }
@@ -195,8 +304,23 @@ static int launch_downscaled(mod16_ctx* ctx, const mod16_downscale* grid, DsArgs
 template <typename T>
 static int launch_fields(mod16_ctx* ctx, const mod16_downscale* grid, DsFieldArgs<T> a, hipStream_t st) {
     if (a.n <= 0) return MOD16_OK;
-    a.g = grid->g;
-    hipLaunchKernelGGL((ds_fields_kernel<T>), dim3(ds_grid_size(ctx, a.n)), dim3(kBlock), 0, st, a);
+    const int blocks = ds_grid_size(ctx, a.n);
+    if (grid->affine) {
+        DsFieldArgs<T, DsRowsGrid> b;
+        memset(&b, 0, sizeof b);
+        for (int f = 0; f < kDsMaxFields; ++f) b.field[f] = a.field[f];
+        b.out = a.out;
+        b.nfields = a.nfields;
+        b.g = grid->gr;
+        b.cpitch = a.cpitch;
+        b.first = a.first;
+        b.n = a.n;
+        b.out_pitch = a.out_pitch;
+        hipLaunchKernelGGL((ds_fields_kernel<T, DsRowsGrid>), dim3(blocks), dim3(kBlock), 0, st, b);
+    } else {
+        a.g = grid->g;
+        hipLaunchKernelGGL((ds_fields_kernel<T>), dim3(blocks), dim3(kBlock), 0, st, a);
+    }
     HIPCHK(ctx, hipGetLastError());
     return MOD16_OK;
 }

@@ -30,7 +30,9 @@
 // Index safety: as in ds_kernel. Coarse indices come from the handle's tables (validated against H
 // and W on the host; (H - 1) x pitch + W <= 2^31 - 1 for this entry), time offsets from validated
 // strides and `every`, fine indices from the pixel range (validated against R x C); no driver value
-// steers an address.
+// steers an address. In the row-affine geometry the lane computes its column pair; ds_corners
+// (DsRowsGrid) clamps the cell index to [0, W - 1] whatever the arithmetic gave, a NaN included, so
+// the narrowed offsets stay inside the plane the entry point has measured.
 #pragma once
 #include "mod16_downscale.hpp"
 
@@ -38,11 +40,11 @@ namespace mod16 {
 
 constexpr int kCdGroup = 3;         // coarse arrays whose cells are in flight together at a day boundary
 
-template <typename T> struct CdArgs {
+template <typename T, typename G = DsGrid> struct CdArgs {
     CompArgs<T> c;                  // arr[k]: scalar: one value; fine: from the range's first pixel (`dense`);
                                     // coarse: the plane of time slab 0 -- tstride[k] elements between two planes
     uint32_t coarse;                // bit k set: array k is a series of coarse planes (bit 14: the hours)
-    DsGrid g;
+    G g;                            // DsGrid (column tables) or DsRowsGrid (row-affine columns)
     int64_t cpitch;                 // elements between two rows of a coarse plane
     int64_t first;                  // the range's first pixel in the raster
 };
@@ -55,7 +57,8 @@ struct CdCorners {
 
 // the corners of pixel `pixel + lane` of the raster (one 64-bit division: block-uniform where
 // `pixel` is a batch's first, the lane adds its carry: ds_corners)
-__device__ __forceinline__ CdCorners cd_corners(const DsGrid& g, int64_t cpitch, int64_t pixel, uint32_t lane) {
+template <typename G>
+__device__ __forceinline__ CdCorners cd_corners(const G& g, int64_t cpitch, int64_t pixel, uint32_t lane) {
     const int64_t row0 = pixel / g.cols;
     const DsCorners k = ds_corners(g, cpitch, row0, (uint32_t)(pixel - row0 * g.cols), lane);
     CdCorners c;
@@ -123,8 +126,8 @@ __device__ __forceinline__ int cd_keep_in_loop(int64_t& i, CdCorners& cn) {
 
 // 256-thread blocks over batches of 256 pixels; the threads past the range's end compute on its last
 // pixel and store nothing. Launch bounds as comp_kernel's.
-template <typename T, bool FAST, bool PET>
-__global__ void __launch_bounds__(kBlock, FAST ? 2 : 1) cd_kernel(const CdArgs<T> a) {
+template <typename T, bool FAST, bool PET, typename G = DsGrid>
+__global__ void __launch_bounds__(kBlock, FAST ? 2 : 1) cd_kernel(const CdArgs<T, G> a) {
     constexpr int kTab = FAST ? FastMath<double>::kTabDoubles : 1;
     __shared__ __attribute__((aligned(16))) double lut[MOD16_LUT_ROWS * kLutCols];
     __shared__ __attribute__((aligned(16))) double tab[kTab];
@@ -240,8 +243,8 @@ __global__ void __launch_bounds__(kBlock, FAST ? 2 : 1) cd_kernel(const CdArgs<T
 
 // Behind cd_kernel<T, true, PET>: all periods of the marked pixels; a day outside the domain in the
 // reference's operation order, every other day by the fast pixel function.
-template <typename T, bool PET>
-__global__ void __launch_bounds__(kBlock, 1) cd_redo_kernel(const CdArgs<T> a) {
+template <typename T, bool PET, typename G = DsGrid>
+__global__ void __launch_bounds__(kBlock, 1) cd_redo_kernel(const CdArgs<T, G> a) {
     constexpr int kTab = FastMath<double>::kTabDoubles;
     __shared__ __attribute__((aligned(16))) double lut[MOD16_LUT_ROWS * kLutCols];
     __shared__ __attribute__((aligned(16))) double tab[kTab];

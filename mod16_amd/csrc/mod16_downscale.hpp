@@ -26,7 +26,13 @@
 //
 // Index safety: every coarse index comes from the handle's tables (validated against H and W on
 // the host), every fine index from the pixel range (validated against R x C); no driver value
-// steers an address.
+// steers an address. In the row-affine geometry (DsRowsGrid) the column pair is computed by the
+// lane from the row's (origin, scale), which the host has validated as finite with a finite far
+// end, so every position is finite. The argument does not lean on that: the clamped position is
+// the result of min / max against 0 and W - 1, the wrapped one is replaced by 0 unless
+// 0 <= p < W holds (a comparison that a NaN fails), and the converted cell index is clamped to
+// [0, W - 1] as an integer once more, so no computed value, NaN and infinity included, steers an
+// address outside [0, W); i1 is formed from i0 by integer arithmetic alone.
 #pragma once
 #include "mod16_composite.hpp"
 
@@ -47,11 +53,27 @@ struct DsGrid {
     int32_t cols;            // C
 };
 
-template <typename T> struct DsArgs {
+// The row-affine geometry (mod16_amd/downscale.py: corner_tables_rows): the rows keep their tables,
+// the column position of pixel (r, c) is origin[r] + scale[r] * c and its cell pair and weights are
+// formed by the lane (sinusoidal tiles: the longitude of a column depends on the row)
+struct DsRowsGrid {
+    const int32_t* ri0;      // [R] as in DsGrid
+    const int32_t* ri1;
+    const double* rw0;
+    const double* rw1;
+    const double* origin;    // [R] position of column 0 in units of coarse cells
+    const double* scale;     // [R] coarse cells per fine column
+    int32_t cols;            // C
+    int32_t width;           // W: the coarse grid's columns
+    int32_t wrap;            // 1: the coarse column axis is periodic
+    int32_t nearest;         // 1: 'nearest', 0: 'bilinear'
+};
+
+template <typename T, typename G = DsGrid> struct DsArgs {
     const T* drv[14];               // scalar: one value; fine: from the range's first pixel; coarse: a whole plane
     uint32_t dense;                 // bit k set: driver k is a fine array
     uint32_t coarse;                // bit k set: driver k is a coarse plane
-    DsGrid g;
+    G g;
     int64_t cpitch;                 // elements between two rows of a coarse plane
     int64_t first, n;               // the pixel range [first, first + n) of the raster
     const uint8_t* cls;
@@ -62,11 +84,11 @@ template <typename T> struct DsArgs {
     unsigned* status;
 };
 
-template <typename T> struct DsFieldArgs {
+template <typename T, typename G = DsGrid> struct DsFieldArgs {
     const T* field[kDsMaxFields];   // coarse planes
     T* out;                         // [nfields][out_pitch]
     int nfields;
-    DsGrid g;
+    G g;
     int64_t cpitch, first, n, out_pitch;
 };
 
@@ -115,6 +137,53 @@ __device__ __forceinline__ DsCorners ds_corners(const DsGrid& g, int64_t cpitch,
     return k;
 }
 
+// The same in the row-affine geometry: the row's table entry as above, the column pair and its
+// weights from the row's (origin, scale) -- downscale.corner_tables on origin + scale * c, operation
+// for operation, no contraction: one multiplication and one addition (each rounded), clamp or wrap
+// (the quotient of pos / W is the correctly rounded one: the compiler's IEEE float64 division),
+// floor, f, the far cell, w1, w0 = 1.0 - w1. `wrap` and `nearest` are wave-uniform. Some fifteen
+// float64 operations per pixel (the division's refinement steps among them), once per pixel and
+// outside every day loop.
+__device__ __forceinline__ DsCorners ds_corners(const DsRowsGrid& g, int64_t cpitch, int64_t row0, uint32_t col0, uint32_t lane) {
+#pragma clang fp contract(off)
+    const uint32_t cc = col0 + lane;
+    const uint32_t q = cc / (uint32_t)g.cols;
+    const uint32_t c = cc - q * (uint32_t)g.cols;
+    const int64_t r = row0 + q;
+    const int64_t r0 = (int64_t)g.ri0[r] * cpitch, r1 = (int64_t)g.ri1[r] * cpitch;
+    const double wr0 = g.rw0[r], wr1 = g.rw1[r];
+    const double step = g.scale[r] * (double)c;
+    const double pos = g.origin[r] + step;
+    const int32_t W = g.width;
+    const double size = (double)W;
+    double p;
+    if (g.wrap) {
+        const double turns = floor(pos / size) * size;
+        p = pos - turns;
+        p = (p >= 0.0 && p < size) ? p : 0.0;        // (a NaN fails the comparison and lands on 0 too)
+    } else {
+        p = fmin(fmax(pos, 0.0), (double)(W - 1));
+    }
+    const double fl = floor(p);
+    const double f = p - fl;
+    int32_t i0 = (int32_t)fl;
+    i0 = i0 < 0 ? 0 : (i0 > W - 1 ? W - 1 : i0);         // (never taken for a validated handle: index safety)
+    const int32_t i1 = g.wrap ? (i0 + 1 == W ? 0 : i0 + 1) : (i0 + 1 < W - 1 ? i0 + 1 : W - 1);
+    const double wc1 = g.nearest ? (f >= 0.5 ? 1.0 : 0.0) : f;
+    const double wc0 = 1.0 - wc1;
+    const int64_t c0 = i0, c1 = i1;
+    DsCorners k;
+    k.o[0] = r0 + c0;
+    k.o[1] = r0 + c1;
+    k.o[2] = r1 + c0;
+    k.o[3] = r1 + c1;
+    k.w[0] = wr0 * wc0;
+    k.w[1] = wr0 * wc1;
+    k.w[2] = wr1 * wc0;
+    k.w[3] = wr1 * wc1;
+    return k;
+}
+
 // downscale.interpolate for one pixel from its four cell values: a corner without weight gives
 // +0.0 whatever its cell holds; left to right, no contraction
 __device__ __forceinline__ double ds_interp(const DsCorners& k, double v00, double v01, double v10, double v11) {
@@ -134,8 +203,8 @@ __device__ __forceinline__ double ds_total(double canopy, double soil, double tr
 
 // The 14 driver values of pixel i of the range (its corners in k): every load first, in the storage
 // type, under wave-uniform branches; the arithmetic behind them
-template <typename T>
-__device__ __forceinline__ PixelIn<double> ds_pixel(const DsArgs<T>& a, int64_t i, const DsCorners& k) {
+template <typename T, typename G>
+__device__ __forceinline__ PixelIn<double> ds_pixel(const DsArgs<T, G>& a, int64_t i, const DsCorners& k) {
     T raw[14][4];
 #pragma unroll
     for (int d = 0; d < 14; ++d) {
@@ -159,9 +228,10 @@ __device__ __forceinline__ PixelIn<double> ds_pixel(const DsArgs<T>& a, int64_t 
 }
 
 // 256-thread blocks over batches of 256 pixels; the batch loop is block-uniform, the threads past
-// the range's end compute on its last pixel and store nothing.
-template <typename T, bool FAST>
-__global__ void __launch_bounds__(kBlock, FAST ? 2 : 1) ds_kernel(const DsArgs<T> a) {
+// the range's end compute on its last pixel and store nothing. G: the geometry, DsGrid (column
+// tables) or DsRowsGrid (row-affine columns).
+template <typename T, bool FAST, typename G = DsGrid>
+__global__ void __launch_bounds__(kBlock, FAST ? 2 : 1) ds_kernel(const DsArgs<T, G> a) {
     constexpr int kTab = FAST ? FastMath<double>::kTabDoubles : 1;
     __shared__ __attribute__((aligned(16))) double lut[MOD16_LUT_ROWS * kLutCols];
     __shared__ __attribute__((aligned(16))) double tab[kTab];
@@ -217,8 +287,8 @@ __global__ void __launch_bounds__(kBlock, FAST ? 2 : 1) ds_kernel(const DsArgs<T
 }
 
 // Behind ds_kernel<T, true>: the marked pixels in the reference's operation order.
-template <typename T>
-__global__ void __launch_bounds__(kBlock, 1) ds_redo_kernel(const DsArgs<T> a) {
+template <typename T, typename G = DsGrid>
+__global__ void __launch_bounds__(kBlock, 1) ds_redo_kernel(const DsArgs<T, G> a) {
     __shared__ __attribute__((aligned(16))) double lut[MOD16_LUT_ROWS * kLutCols];
     for (int i = threadIdx.x; i < MOD16_LUT_ROWS * kLutCols; i += kBlock) lut[i] = a.lut64[i];
     __syncthreads();
@@ -238,8 +308,8 @@ __global__ void __launch_bounds__(kBlock, 1) ds_redo_kernel(const DsArgs<T> a) {
 }
 
 // The interpolated fields alone: out[f][i] for the pixels of the range, through ds_interp.
-template <typename T>
-__global__ void __launch_bounds__(kBlock) ds_fields_kernel(const DsFieldArgs<T> a) {
+template <typename T, typename G = DsGrid>
+__global__ void __launch_bounds__(kBlock) ds_fields_kernel(const DsFieldArgs<T, G> a) {
     const int64_t nbatch = (a.n + kBlock - 1) / kBlock;
     for (int64_t b = blockIdx.x; b < nbatch; b += gridDim.x) {
         const int64_t i = b * kBlock + threadIdx.x;

@@ -8,11 +8,20 @@ nothing here touches the library or a device; the kernels (``csrc/mod16_downscal
 A fine raster of ``R x C`` pixels lies over a coarse grid of ``H x W`` cells. The geometry is two
 float64 tables, ``row_pos[R]`` and ``col_pos[C]``: the position of every fine row and column in
 units of coarse cells, cell centres at the integers (``positions`` builds them for regular grids).
-Any rectilinear pair of grids is covered; grids whose column mapping depends on the row (sinusoidal
-tiles) are not. Per axis ``corner_tables`` turns the positions into two cell indices and two weights;
-``interpolate`` forms a pixel's value from the four surrounding cells. All transcendental work
-happens in ``corner_tables``, on the host: the device multiplies and adds only, and its result has
-the bits of ``interpolate``.
+Any rectilinear pair of grids is covered. Per axis ``corner_tables`` turns the positions into two
+cell indices and two weights; ``interpolate`` forms a pixel's value from the four surrounding cells.
+All transcendental work happens in ``corner_tables``, on the host: the device multiplies and adds
+only, and its result has the bits of ``interpolate``.
+
+A second geometry, "row-affine columns", covers fine grids whose column mapping depends on the row
+-- MODIS sinusoidal tiles, where ``lon = x / (R_earth cos(lat_row))``: the column position of pixel
+``(r, c)`` is ``col_origin[r] + col_scale[r] * c``, two float64 per row (``sinusoidal_positions``
+builds them for a tile). The rows keep their table; ``corner_tables_rows`` is ``corner_tables`` on
+those ``(R, C)`` positions and ``interpolate_rows`` is ``interpolate`` with its tables. The device
+forms the column pair per pixel with multiply, add, divide, floor and compare and reproduces these
+bits. Out of scope in this geometry: ``'cos4'`` (its weights need a cosine), arbitrary per-pixel
+positions, projections whose columns are not affine in ``c`` within a row, and the masking of
+off-globe pixels of edge tiles (the class raster's job).
 '''
 import numpy as np
 
@@ -155,6 +164,162 @@ def interpolate(field, row_tables, col_tables):
         t10 = term(ri1, ci0, rw1, cw0)
         t11 = term(ri1, ci1, rw1, cw1)
         return ((t00 + t01) + t10) + t11
+
+
+# ---- row-affine columns: fine grids whose column mapping depends on the row (MODIS sinusoidal tiles).
+# The column position of pixel (r, c) is ``col_origin[r] + col_scale[r] * c``; the rows keep their table.
+
+#: the methods of the row-affine geometry (no ``'cos4'``)
+AFFINE_METHODS = ('nearest', 'bilinear')
+#: the MODIS sinusoidal grid: radius of its sphere [m], tiles across and down, the edge of a tile [m]
+SINUSOIDAL_RADIUS = 6371007.181
+SINUSOIDAL_TILES = (36, 18)
+SINUSOIDAL_TILE_EDGE = 2 * np.pi * SINUSOIDAL_RADIUS / 36
+
+
+def check_affine(shape, col_origin, col_scale, method=None):
+    '''The row-affine column geometry of an ``R x C`` raster -> ``(col_origin, col_scale)`` as
+    contiguous float64 arrays of ``R`` entries. ValueError unless both are one-dimensional with
+    ``R`` entries and, for every row, ``col_origin[r]``, ``col_scale[r]`` and ``col_origin[r] +
+    col_scale[r] * (C - 1)`` are finite (finite end points make every position of the row finite),
+    or where ``method`` is given and is ``'cos4'``: its weights need a cosine, and the contract of
+    this geometry is that the device reproduces the definition's bits with multiply, add, divide,
+    floor and compare only.'''
+    if method is not None:
+        method_code(method)
+        if method not in AFFINE_METHODS:
+            raise ValueError("method 'cos4' is not available with row-affine columns (col_affine): its weights need a "
+                             "cosine, which the device would not reproduce bit for bit; use 'nearest' or 'bilinear'")
+    R, C = int(shape[0]), int(shape[1])
+    column_positions(col_origin, col_scale, C, _check_only=True)
+    origin = np.ascontiguousarray(col_origin, np.float64)
+    scale = np.ascontiguousarray(col_scale, np.float64)
+    if origin.shape != (R,):
+        raise ValueError('col_origin and col_scale have shape %r, expected (%d,)' % (origin.shape, R))
+    return origin, scale
+
+
+def column_positions(col_origin, col_scale, cols, _check_only=False):
+    '''The column position of every pixel of a raster with row-affine columns -> ``(R, C)`` float64:
+    ``col_origin[:, None] + col_scale[:, None] * arange(C)``, one multiplication and one addition,
+    each rounded. ValueError unless both inputs are one-dimensional with equal length and, for every
+    row, ``col_origin[r]``, ``col_scale[r]`` and ``col_origin[r] + col_scale[r] * (C - 1)`` are finite.'''
+    origin = np.asarray(col_origin, np.float64)
+    scale = np.asarray(col_scale, np.float64)
+    cols = int(cols)
+    if cols < 1 or cols > MAX_EXTENT:
+        raise ValueError('cols must be between 1 and %d, got %d' % (MAX_EXTENT, cols))
+    if origin.ndim != 1 or scale.ndim != 1:
+        raise ValueError('col_origin and col_scale must be one-dimensional, got shapes %r and %r'
+                         % (origin.shape, scale.shape))
+    if origin.shape != scale.shape:
+        raise ValueError('col_origin and col_scale must have equal length, got %d and %d' % (origin.size, scale.size))
+    if not np.all(np.isfinite(origin)):
+        raise ValueError('col_origin holds a value that is not finite')
+    if not np.all(np.isfinite(scale)):
+        raise ValueError('col_scale holds a value that is not finite')
+    with np.errstate(all='ignore'):
+        far = origin + scale * np.float64(cols - 1)
+        if not np.all(np.isfinite(far)):
+            raise ValueError('col_origin + col_scale * (cols - 1) is not finite in some row')
+        if _check_only:
+            return None
+        return origin[:, None] + scale[:, None] * np.arange(cols, dtype=np.float64)[None, :]
+
+
+def corner_tables_rows(col_origin, col_scale, cols, size, wrap=False, method='bilinear'):
+    '''The column tables of a raster with row-affine columns -> ``(i0, i1, w0, w1)``, each ``(R, C)``:
+    ``corner_tables`` applied to ``column_positions(col_origin, col_scale, cols)``, with the same
+    formulas (clamp or wrap, ``floor``, ``f``, ``i1``, ``w1``, ``w0 = 1.0 - w1``). This is what the
+    kernels form per pixel from the two float64 of the pixel's row.
+
+    ``method`` is ``'nearest'`` or ``'bilinear'``. ``'cos4'`` raises ValueError for this geometry: its
+    weights need a cosine, and the contract here is that the device reproduces the definition's bits
+    with multiply, add, divide, floor and compare only.'''
+    method_code(method)
+    if method not in AFFINE_METHODS:
+        raise ValueError("method 'cos4' is not available with row-affine columns: its weights need a cosine, which "
+                         "the device would not reproduce bit for bit; use 'nearest' or 'bilinear'")
+    pos = column_positions(col_origin, col_scale, cols)
+    i0, i1, w0, w1 = corner_tables(pos.reshape(-1), size, wrap, method)
+    return tuple(t.reshape(pos.shape) for t in (i0, i1, w0, w1))
+
+
+def interpolate_rows(field, row_tables, col_tables_2d):
+    '''``interpolate`` with ``(R, C)`` column tables (``corner_tables_rows``): the same corner order,
+    the same ``w != 0`` rule and the same left-to-right sum without contraction -> ``(R, C)`` float64.'''
+    field = np.asarray(field)
+    if field.ndim != 2:
+        raise ValueError('a coarse field must be two-dimensional, got shape %r' % (field.shape,))
+    field = field.astype(np.float64)
+    H, W = field.shape
+    ri0, ri1, rw0, rw1 = check_tables(row_tables, len(row_tables[0]), H, 'row')
+    if len(col_tables_2d) != 4:
+        raise ValueError('column tables must be (i0, i1, w0, w1)')
+    R = len(ri0)
+    ci0, ci1 = (np.asarray(t, np.int32) for t in col_tables_2d[:2])
+    cw0, cw1 = (np.asarray(t, np.float64) for t in col_tables_2d[2:])
+    for t in (ci0, ci1, cw0, cw1):
+        if t.ndim != 2 or t.shape[0] != R or t.shape != ci0.shape:
+            raise ValueError('a column table has shape %r, expected (%d, C)' % (t.shape, R))
+    for t in (ci0, ci1):
+        if t.size and (t.min() < 0 or t.max() >= W):
+            raise ValueError('a column table holds an index outside [0, %d)' % W)
+    if not (np.all(np.isfinite(cw0)) and np.all(np.isfinite(cw1))):
+        raise ValueError('a column table holds a weight that is not finite')
+    with np.errstate(all='ignore'):
+        def term(ri, ci, wr, wc):
+            w = wr[:, None] * wc
+            v = field[ri[:, None], ci]
+            return np.where(w != 0, w * v, 0.0)
+        t00 = term(ri0, ci0, rw0, cw0)
+        t01 = term(ri0, ci1, rw0, cw1)
+        t10 = term(ri1, ci0, rw1, cw0)
+        t11 = term(ri1, ci1, rw1, cw1)
+        return ((t00 + t01) + t10) + t11
+
+
+def sinusoidal_positions(h, v, size, coarse_lat_first, coarse_lat_step, coarse_lon_first, coarse_lon_step):
+    '''The geometry of MODIS sinusoidal tile ``(h, v)`` with ``size`` pixels per side (1200, 2400, 4800,
+    or any positive int) over a regular latitude / longitude grid -> ``(row_pos[size],
+    col_origin[size], col_scale[size])``: ``row_pos`` for ``corner_tables``, the other two for
+    ``col_affine`` / ``corner_tables_rows``.
+
+    The grid's public constants: a sphere of radius 6371007.181 m, 36 x 18 tiles of edge ``T = 2 pi R
+    / 36``. The tile's upper-left corner is ``((h - 18) T, (9 - v) T)``; pixel centres lie at +0.5
+    pixel; ``lat = y / R`` and ``lon = x / (R cos(lat))``. The coarse coordinates are in degrees, cell
+    centres at the integers as in ``positions``: ``coarse_lat_first`` / ``coarse_lon_first`` are the
+    centre of cell 0, the steps the distance between two centres (negative for north to south).
+
+    On edge tiles the pixels beyond the globe's outline (``|lon| > 180`` degrees) get finite positions
+    that wrap around the coarse grid like any other; masking them is the class raster's job. The
+    sinusoidal grid is equal-area, so ``zonal`` needs no per-row ``area`` on it.
+
+    ValueError for ``h`` outside 0..35, ``v`` outside 0..17, ``size < 1``, or a zero or non-finite step.'''
+    h, v, size = int(h), int(v), int(size)
+    if h < 0 or h >= SINUSOIDAL_TILES[0]:
+        raise ValueError('h must be between 0 and 35, got %d' % h)
+    if v < 0 or v >= SINUSOIDAL_TILES[1]:
+        raise ValueError('v must be between 0 and 17, got %d' % v)
+    if size < 1 or size > MAX_EXTENT:
+        raise ValueError('size must be between 1 and %d, got %d' % (MAX_EXTENT, size))
+    for step, what in ((coarse_lat_step, 'coarse_lat_step'), (coarse_lon_step, 'coarse_lon_step')):
+        if not np.isfinite(step) or step == 0:
+            raise ValueError('%s must be finite and not zero, got %r' % (what, step))
+    for first, what in ((coarse_lat_first, 'coarse_lat_first'), (coarse_lon_first, 'coarse_lon_first')):
+        if not np.isfinite(first):
+            raise ValueError('%s must be finite, got %r' % (what, first))
+    radius, edge = np.float64(SINUSOIDAL_RADIUS), np.float64(SINUSOIDAL_TILE_EDGE)
+    pixel = edge / np.float64(size)
+    k = np.arange(size, dtype=np.float64)
+    y = np.float64(9 - v) * edge - (k + 0.5) * pixel
+    lat = y / radius                                   # radians
+    x0 = np.float64(h - 18) * edge + 0.5 * pixel       # the centre of column 0
+    across = radius * np.cos(lat)                      # metres per radian of longitude in every row: > 0
+    row_pos = (np.degrees(lat) - np.float64(coarse_lat_first)) / np.float64(coarse_lat_step)
+    col_origin = (np.degrees(x0 / across) - np.float64(coarse_lon_first)) / np.float64(coarse_lon_step)
+    col_scale = np.degrees(pixel / across) / np.float64(coarse_lon_step)
+    return row_pos, col_origin, col_scale
 
 
 def check_coarse(coarse):

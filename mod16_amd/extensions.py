@@ -209,7 +209,7 @@ def evapotranspiration_downscaled(
         bplut, cls, lw_net_day, lw_net_night, sw_rad_day, sw_rad_night,
         sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
         vpd_night, pressure, fpar, lai, row_pos, col_pos, wrap=False, method='bilinear',
-        coarse=_MET_DRIVERS, beta=None, math=_lib.MATH_FAST, device=0, out=None, devices=None):
+        coarse=_MET_DRIVERS, beta=None, math=_lib.MATH_FAST, device=0, out=None, devices=None, col_affine=None):
     r'''
     (Extension.) Forward run over a multi-class raster whose reanalysis drivers stay on their own
     coarse grid: what ``evapotranspiration_raster`` returns on drivers blown up to the fine grid
@@ -229,6 +229,12 @@ def evapotranspiration_downscaled(
     row_pos, col_pos : numpy.ndarray
         ``(R,)`` and ``(C,)``: the position of every fine row and column in units of coarse cells,
         cell centres at the integers (``mod16_amd.downscale.positions`` for regular grids)
+    col_affine : tuple of numpy.ndarray
+        (Optional) ``(col_origin, col_scale)``, each ``(R,)``, in place of ``col_pos`` (pass
+        ``col_pos=None``): row-affine columns, the column position of pixel ``(r, c)`` being
+        ``col_origin[r] + col_scale[r] * c`` (a MODIS sinusoidal tile:
+        ``mod16_amd.downscale.sinusoidal_positions``; ``'nearest'`` or ``'bilinear'``). The result is
+        then that on drivers materialised with ``mod16_amd.downscale.interpolate_rows``
     wrap : bool
         True where the coarse column axis is periodic (the longitude axis of a global grid);
         otherwise, and always for the rows, the edge value is held outside the grid
@@ -275,10 +281,15 @@ def evapotranspiration_downscaled(
     if int(math) & ~_lib.MATH_EXACT:
         raise ValueError('math must be MATH_FAST or MATH_EXACT for the downscaled run')
     shapes = [_shape(v) if name in names or np.size(v) != 1 else () for name, v in zip(_d.DRIVER_NAMES, arrays)]
+    if (col_pos is None) == (col_affine is None):
+        raise ValueError('exactly one of col_pos and col_affine must be given')
     kinds, _, n = _d.check_call(shape, coarse_shape, shapes, coarse=names, method=method, cls_size=cls.size,
                                 row_pos=row_pos, col_pos=col_pos)
+    if col_affine is not None:
+        col_affine = _d.check_affine(shape, col_affine[0], col_affine[1], method)
     row_tables = _d.corner_tables(row_pos, coarse_shape[0], False, method)
-    col_tables = _d.corner_tables(col_pos, coarse_shape[1], bool(wrap), method)
+    col_tables = None if col_affine is not None else _d.corner_tables(col_pos, coarse_shape[1], bool(wrap), method)
+    geometry = {} if col_affine is None else {'col_affine': col_affine}       # (rectilinear calls are made as before)
     dtype = _result_dtype(arrays)
     cls = np.ascontiguousarray(_as_uint8(cls))
     outs = _outputs(out, shape, [dtype] * 2)
@@ -297,7 +308,7 @@ def evapotranspiration_downscaled(
         if m <= 0:
             return
         grid = _lib.Downscale(ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
-                              tables=(row_tables, col_tables))
+                              tables=(row_tables, col_tables), **geometry)
         try:
             d = [p + off * esz if kind == _d.KIND_FINE else p for p, kind in zip(ptrs, kinds)]
             grid.run(dtype, cls.ctypes.data + off, d, kinds, coarse_shape[1], off, m, optr[0] + off * esz,
@@ -314,7 +325,7 @@ def evapotranspiration_composite_downscaled(
         sw_albedo, temp_day, temp_night, temp_annual, tmin, vpd_day,
         vpd_night, pressure, fpar, lai, day_hours, row_pos, col_pos, days=None, period_days=8, every=None,
         wrap=False, method='bilinear', coarse=_MET_DRIVERS, pet=False, min_valid=1, rescale=False, beta=None,
-        math=_lib.MATH_FAST, device=0, out=None, stage_bytes=None):
+        math=_lib.MATH_FAST, device=0, out=None, stage_bytes=None, col_affine=None):
     r'''
     (Extension.) Multi-day ET composites over a multi-class raster whose reanalysis drivers stay on
     their own coarse grid: what ``evapotranspiration_composite`` returns on arrays blown up to the
@@ -334,8 +345,8 @@ def evapotranspiration_composite_downscaled(
         an ``(S, H, W)`` array, one grid for all of them; any other is a scalar, an ``(R, C)`` array
         or an ``(S, R, C)`` array. ``S = ceil(days / every[name])``: day ``t`` reads slab
         ``t // every[name]``
-    row_pos, col_pos, wrap, method
-        the geometry, as for ``evapotranspiration_downscaled``
+    row_pos, col_pos, wrap, method, col_affine
+        the geometry, as for ``evapotranspiration_downscaled`` (``col_pos=None`` with ``col_affine``)
     days, period_days, every, pet, min_valid, rescale
         as for ``evapotranspiration_composite``
     coarse : sequence of str
@@ -371,9 +382,13 @@ def evapotranspiration_composite_downscaled(
     shape = cls.shape
     shapes = [_shape(v) if name in names or np.size(v) != 1 else () for name, v in zip(_c.ARRAY_NAMES, arrays)]
     coarse_shape = _d.coarse_grid_shape(names, shapes)
+    if (col_pos is None) == (col_affine is None):
+        raise ValueError('exactly one of col_pos and col_affine must be given')
     for pos, count, what in ((row_pos, shape[0], 'row_pos'), (col_pos, shape[1], 'col_pos')):
-        if np.shape(pos) != (count,):
+        if pos is not None and np.shape(pos) != (count,):
             raise ValueError('%s has shape %r, expected (%d,)' % (what, np.shape(pos), count))
+    if col_affine is not None:
+        col_affine = _d.check_affine(shape, col_affine[0], col_affine[1], method)
     if days is None:
         daily = [sh[0] for name, sh in zip(_c.ARRAY_NAMES, shapes)
                  if ev[name] == 1 and len(sh) == 3 and (name in names or tuple(sh[1:]) == tuple(shape))]
@@ -386,7 +401,8 @@ def evapotranspiration_composite_downscaled(
         raise ValueError('math must be MATH_FAST or MATH_EXACT for the composite run')
     _check_stage_bytes(stage_bytes)
     row_tables = _d.corner_tables(row_pos, coarse_shape[0], False, method)
-    col_tables = _d.corner_tables(col_pos, coarse_shape[1], bool(wrap), method)
+    col_tables = None if col_affine is not None else _d.corner_tables(col_pos, coarse_shape[1], bool(wrap), method)
+    geometry = {} if col_affine is None else {'col_affine': col_affine}       # (rectilinear calls are made as before)
     dtype = _result_dtype(arrays)
     cls = np.ascontiguousarray(_as_uint8(cls))
     full = (P,) + tuple(shape)
@@ -406,7 +422,7 @@ def evapotranspiration_composite_downscaled(
     ctx = _lib.context(device)
     ctx.set_bplut(table)
     grid = _lib.Downscale(ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
-                          tables=(row_tables, col_tables))
+                          tables=(row_tables, col_tables), **geometry)
     try:
         optr = [o.ctypes.data for o in outs]
         et, pt = (optr[0], optr[1]) if pet else (optr[0], None)

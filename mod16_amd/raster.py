@@ -230,13 +230,19 @@ class DownscaleGrid(object):
     '''The geometry of an ``R x C`` fine raster over an ``H x W`` coarse grid resident on an engine's
     device (``RasterEngine.downscale_grid``): the corner tables uploaded once, ``run`` (ET with coarse
     drivers interpolated per pixel inside the kernel) and ``fields`` (the interpolated fields alone)
-    as often as there are days. The definition is ``mod16_amd.downscale``.'''
+    as often as there are days. The definition is ``mod16_amd.downscale``. Exactly one of ``col_pos``
+    (column tables) and ``col_affine = (col_origin, col_scale)`` (row-affine columns, e.g. a sinusoidal
+    tile: the kernels form the column pair per pixel, ``col_tables`` is None) gives the columns;
+    ``run``, ``fields`` and ``composite`` are the same for both.'''
 
-    def __init__(self, engine, shape, coarse_shape, row_pos, col_pos, wrap=False, method='bilinear'):
+    def __init__(self, engine, shape, coarse_shape, row_pos, col_pos=None, wrap=False, method='bilinear',
+                 col_affine=None):
         self.engine = engine
-        self._grid = _lib.Downscale(engine.ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method)
+        self._grid = _lib.Downscale(engine.ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
+                                    col_affine=col_affine)
         self.shape, self.coarse_shape = self._grid.shape, self._grid.coarse_shape
         self.row_tables, self.col_tables = self._grid.row_tables, self._grid.col_tables
+        self.col_affine = self._grid.col_affine      # (col_origin, col_scale) of row-affine columns, else None
 
     def _coarse_tensor(self, t, what):
         '''-> (address, row pitch in elements) of an (H, W) tensor with unit stride in columns'''
@@ -743,14 +749,23 @@ class RasterEngine(object):
             pitch = row
         return out, pitch
 
-    def downscale_grid(self, shape, coarse_shape, row_pos, col_pos, wrap=False, method='bilinear'):
+    def downscale_grid(self, shape, coarse_shape, row_pos, col_pos=None, wrap=False, method='bilinear',
+                       col_affine=None):
         '''The geometry of an ``R x C`` fine raster (``shape``) over an ``H x W`` coarse grid
         (``coarse_shape``) on this engine's device -> ``DownscaleGrid``. ``row_pos[R]`` and
         ``col_pos[C]`` are the positions of the fine rows and columns in units of coarse cells, cell
         centres at the integers (``mod16_amd.downscale.positions`` builds them for regular grids);
         ``wrap``: the coarse column axis is periodic (a global longitude axis); ``method``:
-        ``'nearest'``, ``'bilinear'`` or ``'cos4'`` (``mod16_amd.downscale.corner_tables``).'''
-        return DownscaleGrid(self, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method)
+        ``'nearest'``, ``'bilinear'`` or ``'cos4'`` (``mod16_amd.downscale.corner_tables``).
+
+        For a fine grid whose column mapping depends on the row (a MODIS sinusoidal tile:
+        ``mod16_amd.downscale.sinusoidal_positions``) give ``col_affine = (col_origin[R],
+        col_scale[R])`` instead of ``col_pos``: the column position of pixel ``(r, c)`` is
+        ``col_origin[r] + col_scale[r] * c`` and the kernels form its cell pair and weights per
+        pixel (``mod16_amd.downscale.corner_tables_rows``; ``'nearest'`` or ``'bilinear'``). Exactly
+        one of the two must be given.'''
+        return DownscaleGrid(self, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
+                             col_affine=col_affine)
 
     def gapfill(self, fields, qc=None, good=None, max_gap=None, fallback=None, dtype=None, scale=None,
                 source=False, out=None):

@@ -63,15 +63,13 @@ static int static_entry(mod16_ctx* ctx, const T* const* drivers, const int64_t* 
         if (rc != MOD16_OK) return rc;
     }
     a.flag = ctx->static_flag.as<unsigned>();
-    auto grid_of = [&](int64_t m) {
-        return (int)std::max<int64_t>(1, std::min<int64_t>((m + kBlock - 1) / kBlock, (int64_t)ctx->cus * 8));
-    };
+    const int grid = batch_blocks(ctx, n);
     // the flag word cleared, any(g_surf > 0) over the whole array, then the pixels
     auto enqueue = [&](const StaticArgs<T>& d, hipStream_t st) -> hipError_t {
         hipError_t e = hipMemsetAsync(d.flag, 0, sizeof(unsigned), st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((static_flag_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, d);
-        hipLaunchKernelGGL((static_kernel<T>), dim3(grid_of(n)), dim3(kBlock), 0, st, d);
+        hipLaunchKernelGGL((static_flag_kernel<T>), dim3(grid), dim3(kBlock), 0, st, d);
+        hipLaunchKernelGGL((static_kernel<T>), dim3(grid), dim3(kBlock), 0, st, d);
         return hipSuccess;
     };
     if (where == MOD16_DEVICE) {
@@ -173,7 +171,7 @@ static int static_batch_rows(mod16_ctx* ctx, StaticBatchArgs<T> d, int64_t ndraw
     const bool fast = (flags & MOD16_MATH_EXACT) == 0;
     d.skip = fast ? dskip : nullptr;
     hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)((ndraw + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, dflags, ndraw);
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)ctx->cus * 8));
+    const int gx = batch_blocks(ctx, n);
     if (fast && !skip_ready)
         hipLaunchKernelGGL((static_domain_kernel<T>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d, dskip);
     for (int64_t d0 = 0; d0 < ndraw; d0 += 32768 * (int64_t)kBatchDraws) {

@@ -5,9 +5,18 @@ namespace {
 constexpr int64_t kDsMaxExtent = int64_t(1) << 30;
 enum { kDsScalar = 0, kDsFine = 1, kDsCoarse = 2 };
 
+// an axis' corner tables: the caller's, or a DsAxis' own
+struct DsTables {
+    const int32_t* i0;
+    const int32_t* i1;
+    const double* w0;
+    const double* w1;
+};
+
 struct DsAxis {
     std::vector<int32_t> i0, i1;
     std::vector<double> w0, w1;
+    DsTables view() const { return DsTables{i0.data(), i1.data(), w0.data(), w1.data()}; }
 };
 
 // downscale.corner_tables, formula for formula -> false: a position that is not finite
@@ -46,22 +55,10 @@ bool ds_axis_tables(const double* pos, int64_t count, int64_t size, bool wrap, i
     return true;
 }
 
-const char* ds_check_spec(const mod16_downscale_spec* s) {
-    if (!s) return "NULL spec";
-    if (s->rows < 1 || s->rows > kDsMaxExtent || s->cols < 1 || s->cols > kDsMaxExtent)
-        return "rows and cols must be between 1 and 2^30";
-    if (s->coarse_rows < 1 || s->coarse_rows > kDsMaxExtent || s->coarse_cols < 1 || s->coarse_cols > kDsMaxExtent)
-        return "coarse_rows and coarse_cols must be between 1 and 2^30";
-    if (s->wrap_cols != 0 && s->wrap_cols != 1) return "wrap_cols must be 0 or 1";
-    if (s->method != MOD16_DOWNSCALE_NEAREST && s->method != MOD16_DOWNSCALE_BILINEAR && s->method != MOD16_DOWNSCALE_COS4)
-        return "unknown method";
-    return nullptr;
-}
-
 // every index inside its axis, every weight finite: what the kernels rely on
-bool ds_tables_valid(const int32_t* i0, const int32_t* i1, const double* w0, const double* w1, int64_t count, int64_t size) {
+bool ds_tables_valid(const DsTables& t, int64_t count, int64_t size) {
     for (int64_t k = 0; k < count; ++k)
-        if (i0[k] < 0 || i0[k] >= size || i1[k] < 0 || i1[k] >= size || !std::isfinite(w0[k]) || !std::isfinite(w1[k]))
+        if (t.i0[k] < 0 || t.i0[k] >= size || t.i1[k] < 0 || t.i1[k] >= size || !std::isfinite(t.w0[k]) || !std::isfinite(t.w1[k]))
             return false;
     return true;
 }
@@ -74,46 +71,86 @@ extern "C" int mod16_downscale_destroy(mod16_downscale* grid) {
     return MOD16_OK;
 }
 
-// validated host tables -> a handle with their device copies
-static int ds_build(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int32_t* const* ri, const double* const* rw,
-                    const int32_t* const* ci, const double* const* cw, mod16_downscale** out) {
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
+static int ds_bad(mod16_ctx* ctx, const char* what) { return fail(ctx, MOD16_ERR_ARG, "mod16_downscale_create: ", what); }
+
+// What every create entry point begins with: *out cleared, its pointer arguments present (`given`),
+// the spec. A row-affine grid has no 'cos4' (its weights need a cosine; the device forms this
+// geometry's column weights with multiply, add, divide, floor and compare).
+static int ds_create_begin(mod16_ctx* ctx, const mod16_downscale_spec* s, bool affine, bool given, mod16_downscale** out) {
+    if (!ctx) return MOD16_ERR_ARG;
+    if (out) *out = nullptr;
+    if (!given || !out) return ds_bad(ctx, "NULL argument");
+    if (!s) return ds_bad(ctx, "NULL spec");
+    if (s->rows < 1 || s->rows > kDsMaxExtent || s->cols < 1 || s->cols > kDsMaxExtent)
+        return ds_bad(ctx, "rows and cols must be between 1 and 2^30");
+    if (s->coarse_rows < 1 || s->coarse_rows > kDsMaxExtent || s->coarse_cols < 1 || s->coarse_cols > kDsMaxExtent)
+        return ds_bad(ctx, "coarse_rows and coarse_cols must be between 1 and 2^30");
+    if (s->wrap_cols != 0 && s->wrap_cols != 1) return ds_bad(ctx, "wrap_cols must be 0 or 1");
+    if (s->method != MOD16_DOWNSCALE_NEAREST && s->method != MOD16_DOWNSCALE_BILINEAR && s->method != MOD16_DOWNSCALE_COS4)
+        return ds_bad(ctx, "unknown method");
+    if (affine && s->method == MOD16_DOWNSCALE_COS4)
+        return ds_bad(ctx, "MOD16_DOWNSCALE_COS4 is not available with row-affine columns (MOD16_DOWNSCALE_NEAREST or MOD16_DOWNSCALE_BILINEAR)");
+    return MOD16_OK;
+}
+
+// The row tables and the columns' geometry -- their tables (cols), or the per-row (origin, scale) of
+// row-affine columns (cols NULL) -- validated, then a handle with their device copies. Every check
+// runs before any device work.
+static int ds_build(mod16_ctx* ctx, const mod16_downscale_spec* spec, const DsTables& rows, const DsTables* cols,
+                    const double* origin, const double* scale, mod16_downscale** out) {
     const int64_t R = spec->rows, C = spec->cols;
-    if (!ds_tables_valid(ri[0], ri[1], rw[0], rw[1], R, spec->coarse_rows))
-        return bad("a row table holds an index outside the coarse grid or a weight that is not finite");
-    if (!ds_tables_valid(ci[0], ci[1], cw[0], cw[1], C, spec->coarse_cols))
-        return bad("a column table holds an index outside the coarse grid or a weight that is not finite");
+    if (!ds_tables_valid(rows, R, spec->coarse_rows))
+        return ds_bad(ctx, "a row table holds an index outside the coarse grid or a weight that is not finite");
+    if (cols) {
+        if (!ds_tables_valid(*cols, C, spec->coarse_cols))
+            return ds_bad(ctx, "a column table holds an index outside the coarse grid or a weight that is not finite");
+    } else {
+#pragma clang fp contract(off)
+        const double far = (double)(C - 1);
+        for (int64_t r = 0; r < R; ++r) {
+            if (!std::isfinite(origin[r])) return ds_bad(ctx, "col_origin holds a value that is not finite");
+            if (!std::isfinite(scale[r])) return ds_bad(ctx, "col_scale holds a value that is not finite");
+            const double step = scale[r] * far;
+            const double end = origin[r] + step;
+            if (!std::isfinite(end)) return ds_bad(ctx, "col_origin + col_scale * (cols - 1) is not finite in some row");
+        }
+    }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     mod16_downscale* g = new (std::nothrow) mod16_downscale;
     if (!g) return MOD16_ERR_NOMEM;
     g->device = ctx->device;
     g->spec = *spec;
-    const size_t ib = align256((size_t)R * sizeof(int32_t)), wb = align256((size_t)R * sizeof(double));
-    const size_t jb = align256((size_t)C * sizeof(int32_t)), vb = align256((size_t)C * sizeof(double));
-    int rc = g->tables.alloc(ctx, 2 * (ib + wb + jb + vb), "mod16_downscale_create: device memory for the corner tables");
+    g->affine = !cols;
+    // The device block: the arrays in this order, each in whole 256-byte lines. Walked once without
+    // a block for its size, once with it for the uploads and the views into it.
+    struct Piece { const void* src; size_t bytes; };
+    const size_t ib = (size_t)R * sizeof(int32_t), wb = (size_t)R * sizeof(double);
+    const size_t jb = (size_t)C * sizeof(int32_t), vb = (size_t)C * sizeof(double);
+    const Piece tables[8] = {{rows.i0, ib}, {rows.i1, ib}, {rows.w0, wb}, {rows.w1, wb},
+                             {cols ? cols->i0 : nullptr, jb}, {cols ? cols->i1 : nullptr, jb},
+                             {cols ? cols->w0 : nullptr, vb}, {cols ? cols->w1 : nullptr, vb}};
+    const Piece affine[6] = {{rows.i0, ib}, {rows.i1, ib}, {rows.w0, wb}, {rows.w1, wb}, {origin, wb}, {scale, wb}};
+    const Piece* pieces = cols ? tables : affine;
+    const int count = cols ? 8 : 6;
+    Carver size;
+    for (int k = 0; k < count; ++k) size.take<char>(pieces[k].bytes);
+    int rc = g->tables.alloc(ctx, size.used, "mod16_downscale_create: device memory for the corner tables");
     if (rc == MOD16_OK) {
-        char* base = g->tables.as<char>();
-        char* at[8] = {base, base + ib, base + 2 * ib, base + 2 * ib + wb,
-                       base + 2 * (ib + wb), base + 2 * (ib + wb) + jb, base + 2 * (ib + wb + jb), base + 2 * (ib + wb + jb) + vb};
-        const void* src[8] = {ri[0], ri[1], rw[0], rw[1], ci[0], ci[1], cw[0], cw[1]};
-        const size_t bytes[8] = {(size_t)R * 4, (size_t)R * 4, (size_t)R * 8, (size_t)R * 8,
-                                 (size_t)C * 4, (size_t)C * 4, (size_t)C * 8, (size_t)C * 8};
-        for (int k = 0; k < 8 && rc == MOD16_OK; ++k)
-            if (hipMemcpy(at[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess)
+        Carver block(g->tables.get());
+        const char* at[8];
+        for (int k = 0; k < count; ++k) {
+            at[k] = block.take<char>(pieces[k].bytes);
+            if (rc == MOD16_OK && hipMemcpy(const_cast<char*>(at[k]), pieces[k].src, pieces[k].bytes, hipMemcpyHostToDevice) != hipSuccess)
                 rc = fail(ctx, MOD16_ERR_HIP, "mod16_downscale_create: upload of the corner tables failed");
-        g->g.ri0 = reinterpret_cast<const int32_t*>(at[0]);
-        g->g.ri1 = reinterpret_cast<const int32_t*>(at[1]);
-        g->g.rw0 = reinterpret_cast<const double*>(at[2]);
-        g->g.rw1 = reinterpret_cast<const double*>(at[3]);
-        g->g.ci0 = reinterpret_cast<const int32_t*>(at[4]);
-        g->g.ci1 = reinterpret_cast<const int32_t*>(at[5]);
-        g->g.cw0 = reinterpret_cast<const double*>(at[6]);
-        g->g.cw1 = reinterpret_cast<const double*>(at[7]);
-        g->g.cols = (int32_t)C;
+        }
+        auto i32 = [&](int k) { return reinterpret_cast<const int32_t*>(at[k]); };
+        auto f64 = [&](int k) { return reinterpret_cast<const double*>(at[k]); };
+        if (cols) {
+            g->g = DsGrid{i32(0), i32(1), f64(2), f64(3), i32(4), i32(5), f64(6), f64(7), (int32_t)C};
+        } else {
+            g->gr = DsRowsGrid{i32(0), i32(1), f64(2), f64(3), f64(4), f64(5), (int32_t)C, (int32_t)spec->coarse_cols,
+                               spec->wrap_cols != 0, spec->method == MOD16_DOWNSCALE_NEAREST};
+        }
     }
     if (rc != MOD16_OK) {
         mod16_downscale_destroy(g);
@@ -126,24 +163,13 @@ static int ds_build(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int3
 extern "C" int mod16_downscale_create(mod16_ctx* ctx, const mod16_downscale_spec* spec, const double* row_pos,
                                       const double* col_pos, mod16_downscale** out) {
     MOD16_LOCK(ctx);
-    if (!ctx) return MOD16_ERR_ARG;
-    if (out) *out = nullptr;
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
-    if (!row_pos || !col_pos || !out) return bad("NULL argument");
-    if (const char* what = ds_check_spec(spec)) return bad(what);
+    if (int rc = ds_create_begin(ctx, spec, false, row_pos && col_pos, out)) return rc;
     DsAxis r, c;
-    if (!ds_axis_tables(row_pos, spec->rows, spec->coarse_rows, false, spec->method, r)) return bad("row_pos holds a value that is not finite");
+    if (!ds_axis_tables(row_pos, spec->rows, spec->coarse_rows, false, spec->method, r)) return ds_bad(ctx, "row_pos holds a value that is not finite");
     if (!ds_axis_tables(col_pos, spec->cols, spec->coarse_cols, spec->wrap_cols != 0, spec->method, c))
-        return bad("col_pos holds a value that is not finite");
-    const int32_t* ri[2] = {r.i0.data(), r.i1.data()};
-    const double* rw[2] = {r.w0.data(), r.w1.data()};
-    const int32_t* ci[2] = {c.i0.data(), c.i1.data()};
-    const double* cw[2] = {c.w0.data(), c.w1.data()};
-    return ds_build(ctx, spec, ri, rw, ci, cw, out);
+        return ds_bad(ctx, "col_pos holds a value that is not finite");
+    const DsTables cols = c.view();
+    return ds_build(ctx, spec, r.view(), &cols, nullptr, nullptr, out);
 }
 
 extern "C" int mod16_downscale_create_tables(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int32_t* row_i0,
@@ -151,104 +177,19 @@ extern "C" int mod16_downscale_create_tables(mod16_ctx* ctx, const mod16_downsca
                                              const int32_t* col_i0, const int32_t* col_i1, const double* col_w0,
                                              const double* col_w1, mod16_downscale** out) {
     MOD16_LOCK(ctx);
-    if (!ctx) return MOD16_ERR_ARG;
-    if (out) *out = nullptr;
-    if (!row_i0 || !row_i1 || !row_w0 || !row_w1 || !col_i0 || !col_i1 || !col_w0 || !col_w1 || !out)
-        return fail(ctx, MOD16_ERR_ARG, "mod16_downscale_create: NULL argument");
-    if (const char* what = ds_check_spec(spec)) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    }
-    const int32_t* ri[2] = {row_i0, row_i1};
-    const double* rw[2] = {row_w0, row_w1};
-    const int32_t* ci[2] = {col_i0, col_i1};
-    const double* cw[2] = {col_w0, col_w1};
-    return ds_build(ctx, spec, ri, rw, ci, cw, out);
-}
-
-// The row-affine geometry: validated row tables and per-row (origin, scale) -> a handle with their
-// device copies. Every check runs before any device work.
-static int ds_build_rows(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int32_t* const* ri, const double* const* rw,
-                         const double* origin, const double* scale, mod16_downscale** out) {
-#pragma clang fp contract(off)
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
-    const int64_t R = spec->rows, C = spec->cols;
-    if (!ds_tables_valid(ri[0], ri[1], rw[0], rw[1], R, spec->coarse_rows))
-        return bad("a row table holds an index outside the coarse grid or a weight that is not finite");
-    const double far = (double)(C - 1);
-    for (int64_t r = 0; r < R; ++r) {
-        if (!std::isfinite(origin[r])) return bad("col_origin holds a value that is not finite");
-        if (!std::isfinite(scale[r])) return bad("col_scale holds a value that is not finite");
-        const double step = scale[r] * far;
-        const double end = origin[r] + step;
-        if (!std::isfinite(end)) return bad("col_origin + col_scale * (cols - 1) is not finite in some row");
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    mod16_downscale* g = new (std::nothrow) mod16_downscale;
-    if (!g) return MOD16_ERR_NOMEM;
-    g->device = ctx->device;
-    g->spec = *spec;
-    g->affine = true;
-    const size_t ib = align256((size_t)R * sizeof(int32_t)), wb = align256((size_t)R * sizeof(double));
-    int rc = g->tables.alloc(ctx, 2 * ib + 4 * wb, "mod16_downscale_create: device memory for the corner tables");
-    if (rc == MOD16_OK) {
-        char* base = g->tables.as<char>();
-        char* at[6] = {base, base + ib, base + 2 * ib, base + 2 * ib + wb, base + 2 * ib + 2 * wb, base + 2 * ib + 3 * wb};
-        const void* src[6] = {ri[0], ri[1], rw[0], rw[1], origin, scale};
-        const size_t bytes[6] = {(size_t)R * 4, (size_t)R * 4, (size_t)R * 8, (size_t)R * 8, (size_t)R * 8, (size_t)R * 8};
-        for (int k = 0; k < 6 && rc == MOD16_OK; ++k)
-            if (hipMemcpy(at[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess)
-                rc = fail(ctx, MOD16_ERR_HIP, "mod16_downscale_create: upload of the corner tables failed");
-        g->gr.ri0 = reinterpret_cast<const int32_t*>(at[0]);
-        g->gr.ri1 = reinterpret_cast<const int32_t*>(at[1]);
-        g->gr.rw0 = reinterpret_cast<const double*>(at[2]);
-        g->gr.rw1 = reinterpret_cast<const double*>(at[3]);
-        g->gr.origin = reinterpret_cast<const double*>(at[4]);
-        g->gr.scale = reinterpret_cast<const double*>(at[5]);
-        g->gr.cols = (int32_t)C;
-        g->gr.width = (int32_t)spec->coarse_cols;
-        g->gr.wrap = spec->wrap_cols != 0;
-        g->gr.nearest = spec->method == MOD16_DOWNSCALE_NEAREST;
-    }
-    if (rc != MOD16_OK) {
-        mod16_downscale_destroy(g);
-        return rc;
-    }
-    *out = g;
-    return MOD16_OK;
-}
-
-// the spec of a row-affine grid: as ds_check_spec, and no 'cos4' (its weights need a cosine; the
-// device forms this geometry's column weights with multiply, add, divide, floor and compare)
-static const char* ds_check_spec_rows(const mod16_downscale_spec* s) {
-    if (const char* what = ds_check_spec(s)) return what;
-    if (s->method == MOD16_DOWNSCALE_COS4)
-        return "MOD16_DOWNSCALE_COS4 is not available with row-affine columns (MOD16_DOWNSCALE_NEAREST or MOD16_DOWNSCALE_BILINEAR)";
-    return nullptr;
+    const bool given = row_i0 && row_i1 && row_w0 && row_w1 && col_i0 && col_i1 && col_w0 && col_w1;
+    if (int rc = ds_create_begin(ctx, spec, false, given, out)) return rc;
+    const DsTables cols = {col_i0, col_i1, col_w0, col_w1};
+    return ds_build(ctx, spec, DsTables{row_i0, row_i1, row_w0, row_w1}, &cols, nullptr, nullptr, out);
 }
 
 extern "C" int mod16_downscale_create_rows(mod16_ctx* ctx, const mod16_downscale_spec* spec, const double* row_pos,
                                            const double* col_origin, const double* col_scale, mod16_downscale** out) {
     MOD16_LOCK(ctx);
-    if (!ctx) return MOD16_ERR_ARG;
-    if (out) *out = nullptr;
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
-    if (!row_pos || !col_origin || !col_scale || !out) return bad("NULL argument");
-    if (const char* what = ds_check_spec_rows(spec)) return bad(what);
+    if (int rc = ds_create_begin(ctx, spec, true, row_pos && col_origin && col_scale, out)) return rc;
     DsAxis r;
-    if (!ds_axis_tables(row_pos, spec->rows, spec->coarse_rows, false, spec->method, r)) return bad("row_pos holds a value that is not finite");
-    const int32_t* ri[2] = {r.i0.data(), r.i1.data()};
-    const double* rw[2] = {r.w0.data(), r.w1.data()};
-    return ds_build_rows(ctx, spec, ri, rw, col_origin, col_scale, out);
+    if (!ds_axis_tables(row_pos, spec->rows, spec->coarse_rows, false, spec->method, r)) return ds_bad(ctx, "row_pos holds a value that is not finite");
+    return ds_build(ctx, spec, r.view(), nullptr, col_origin, col_scale, out);
 }
 
 extern "C" int mod16_downscale_create_rows_tables(mod16_ctx* ctx, const mod16_downscale_spec* spec, const int32_t* row_i0,
@@ -256,35 +197,30 @@ extern "C" int mod16_downscale_create_rows_tables(mod16_ctx* ctx, const mod16_do
                                                   const double* col_origin, const double* col_scale,
                                                   mod16_downscale** out) {
     MOD16_LOCK(ctx);
-    if (!ctx) return MOD16_ERR_ARG;
-    if (out) *out = nullptr;
-    if (!row_i0 || !row_i1 || !row_w0 || !row_w1 || !col_origin || !col_scale || !out)
-        return fail(ctx, MOD16_ERR_ARG, "mod16_downscale_create: NULL argument");
-    if (const char* what = ds_check_spec_rows(spec)) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_downscale_create: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    }
-    const int32_t* ri[2] = {row_i0, row_i1};
-    const double* rw[2] = {row_w0, row_w1};
-    return ds_build_rows(ctx, spec, ri, rw, col_origin, col_scale, out);
+    if (int rc = ds_create_begin(ctx, spec, true, row_i0 && row_i1 && row_w0 && row_w1 && col_origin && col_scale, out)) return rc;
+    return ds_build(ctx, spec, DsTables{row_i0, row_i1, row_w0, row_w1}, nullptr, col_origin, col_scale, out);
 }
 
-static int ds_grid_size(const mod16_ctx* ctx, int64_t n) {
-    const int64_t nbatch = (n + kBlock - 1) / kBlock;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t)ctx->cus * 8));
-}
-
-// the kernels of one geometry (G: DsGrid or DsRowsGrid)
-template <typename T, typename G>
-static void launch_downscaled_on(const DsArgs<T, G>& a, int blocks, unsigned flags, hipStream_t st) {
-    if (flags & MOD16_MATH_EXACT) hipLaunchKernelGGL((ds_kernel<T, false, G>), dim3(blocks), dim3(kBlock), 0, st, a);
-    else {
-        hipLaunchKernelGGL((ds_kernel<T, true, G>), dim3(blocks), dim3(kBlock), 0, st, a);
-        // pixels outside the domain of the fast arithmetic: the kernel above left a mark in their
-        // out_night, this one computes them in the reference's operation order
-        hipLaunchKernelGGL((ds_redo_kernel<T, G>), dim3(blocks), dim3(kBlock), 0, st, a);
-    }
+// The arguments of a launch of the run with the handle's geometry in place (G: DsGrid or DsRowsGrid).
+// DsArgs keeps the geometry between its other members, member by member: with `g` behind them, as in
+// DsFieldArgs and CdArgs, ds_redo_kernel<double, DsRowsGrid> takes 193 vector registers for 191.
+template <typename T, typename G> static DsArgs<T, G> ds_with_grid(const DsArgs<T>& a, const G& g) {
+    DsArgs<T, G> b;
+    memset(&b, 0, sizeof b);
+    for (int k = 0; k < 14; ++k) b.drv[k] = a.drv[k];
+    b.dense = a.dense;
+    b.coarse = a.coarse;
+    b.g = g;
+    b.cpitch = a.cpitch;
+    b.first = a.first;
+    b.n = a.n;
+    b.cls = a.cls;
+    b.lut64 = a.lut64;
+    b.tab = a.tab;
+    b.out_day = a.out_day;
+    b.out_night = a.out_night;
+    b.status = a.status;
+    return b;
 }
 
 // All pointers are device pointers here. The handle's geometry picks the instances.
@@ -294,58 +230,31 @@ static int launch_downscaled(mod16_ctx* ctx, const mod16_downscale* grid, DsArgs
     a.lut64 = ctx->lut64.as<double>();
     a.tab = ctx->tab64.as<double>();
     a.status = ctx->status.as<unsigned>();
-    const int blocks = ds_grid_size(ctx, a.n);
-    if (grid->affine) launch_downscaled_on<T, DsRowsGrid>(ds_with_grid<T, DsRowsGrid>(a, grid->gr), blocks, flags, st);
-    else launch_downscaled_on<T, DsGrid>(ds_with_grid<T, DsGrid>(a, grid->g), blocks, flags, st);
+    const int blocks = batch_blocks(ctx, a.n);
+    ds_dispatch(grid, [&](const auto& g) {
+        using G = std::decay_t<decltype(g)>;
+        const DsArgs<T, G> b = ds_with_grid<T, G>(a, g);
+        if (flags & MOD16_MATH_EXACT) hipLaunchKernelGGL((ds_kernel<T, false, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+        else {
+            hipLaunchKernelGGL((ds_kernel<T, true, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+            // pixels outside the domain of the fast arithmetic: the kernel above left a mark in their
+            // out_night, this one computes them in the reference's operation order
+            hipLaunchKernelGGL((ds_redo_kernel<T, G>), dim3(blocks), dim3(kBlock), 0, st, b);
+        }
+    });
     HIPCHK(ctx, hipGetLastError());
     return MOD16_OK;
 }
 
 template <typename T>
-static int launch_fields(mod16_ctx* ctx, const mod16_downscale* grid, DsFieldArgs<T> a, hipStream_t st) {
+static int launch_fields(mod16_ctx* ctx, const mod16_downscale* grid, const DsFields<T>& a, hipStream_t st) {
     if (a.n <= 0) return MOD16_OK;
-    const int blocks = ds_grid_size(ctx, a.n);
-    if (grid->affine) {
-        DsFieldArgs<T, DsRowsGrid> b;
-        memset(&b, 0, sizeof b);
-        for (int f = 0; f < kDsMaxFields; ++f) b.field[f] = a.field[f];
-        b.out = a.out;
-        b.nfields = a.nfields;
-        b.g = grid->gr;
-        b.cpitch = a.cpitch;
-        b.first = a.first;
-        b.n = a.n;
-        b.out_pitch = a.out_pitch;
-        hipLaunchKernelGGL((ds_fields_kernel<T, DsRowsGrid>), dim3(blocks), dim3(kBlock), 0, st, b);
-    } else {
-        a.g = grid->g;
-        hipLaunchKernelGGL((ds_fields_kernel<T>), dim3(blocks), dim3(kBlock), 0, st, a);
-    }
+    ds_dispatch(grid, [&](const auto& g) {
+        using G = std::decay_t<decltype(g)>;
+        const DsFieldArgs<T, G> b = {a, g};
+        hipLaunchKernelGGL((ds_fields_kernel<T, G>), dim3(batch_blocks(ctx, a.n)), dim3(kBlock), 0, st, b);
+    });
     HIPCHK(ctx, hipGetLastError());
-    return MOD16_OK;
-}
-
-// HOST mode: `count` coarse planes of the call uploaded whole, once, rows back to back (pitch =
-// coarse_cols), into the context's buffer for resident inputs; dev[k] receives their addresses
-template <typename T>
-static int ds_upload_planes(mod16_ctx* ctx, const mod16_downscale* grid, const T* const* host, int count, int64_t cpitch,
-                            const T** dev) {
-    const size_t H = (size_t)grid->spec.coarse_rows, W = (size_t)grid->spec.coarse_cols;
-    const size_t plane = align256(H * W * sizeof(T));
-    int rc = ctx->bc_buf.reserve(ctx, 256 + plane * (size_t)count, "HOST mode: device memory for the coarse planes");
-    if (rc != MOD16_OK) return rc;
-    char* cur = ctx->bc_buf.as<char>();
-    for (int k = 0; k < count; ++k) {
-        dev[k] = nullptr;
-        if (!host[k]) continue;
-        // (one copy where the rows lie back to back, else one per row: a plane has a few hundred)
-        const size_t rows = (size_t)cpitch == W ? 1 : H, row_bytes = ((size_t)cpitch == W ? H : 1) * W * sizeof(T);
-        for (size_t r = 0; r < rows; ++r)
-            if (hipMemcpy(cur + r * W * sizeof(T), host[k] + r * (size_t)cpitch, row_bytes, hipMemcpyHostToDevice) != hipSuccess)
-                return fail(ctx, MOD16_ERR_HIP, "HOST mode: upload of a coarse plane failed");
-        dev[k] = reinterpret_cast<const T*>(cur);
-        cur += plane;
-    }
     return MOD16_OK;
 }
 
@@ -356,7 +265,7 @@ static int downscaled_host(mod16_ctx* ctx, const mod16_downscale* grid, const Ds
     const T* planes[14];
     const T* dev[14];
     for (int k = 0; k < 14; ++k) planes[k] = ((h.coarse >> k) & 1u) ? h.drv[k] : nullptr;
-    int rc = ds_upload_planes<T>(ctx, grid, planes, 14, h.cpitch, dev);
+    int rc = upload_coarse<T>(ctx, grid, planes, nullptr, nullptr, h.cpitch, 14, "coarse planes", dev);
     if (rc != MOD16_OK) return rc;
     HostPlan p(sizeof(T));
     for (int k = 0; k < 14; ++k) {
@@ -390,11 +299,8 @@ static int downscaled_entry(mod16_ctx* ctx, const mod16_downscale* grid, const u
                             const int32_t* kinds, int64_t coarse_pitch, int64_t first_pixel, int64_t n, T* out_day,
                             T* out_night, unsigned flags, int where, void* stream) {
     if (!ctx) return MOD16_ERR_ARG;
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_et_downscaled: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
+    const char* const prefix = "mod16_et_downscaled: ";
+    auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, prefix, what); };
     if (!grid || !cls || !drivers || !kinds || !out_day || !out_night) return bad("NULL grid, class raster, drivers, kinds or outputs");
     if (flags & MOD16_MATH_MIXED)
         return bad("MOD16_MATH_MIXED is not available for the downscaled run (MOD16_MATH_FAST or MOD16_MATH_EXACT)");
@@ -416,7 +322,7 @@ static int downscaled_entry(mod16_ctx* ctx, const mod16_downscale* grid, const u
         if (kinds[k] == kDsCoarse) a.coarse |= 1u << k;
     }
     if (a.coarse && coarse_pitch < grid->spec.coarse_cols) return bad("coarse_pitch must be at least coarse_cols");
-    if (!ctx->have_lut) return fail(ctx, MOD16_ERR_NO_BPLUT, "mod16_et_downscaled: mod16_set_bplut_f64 was not called");
+    if (!ctx->have_lut) return fail(ctx, MOD16_ERR_NO_BPLUT, prefix, "mod16_set_bplut_f64 was not called");
     if (n == 0) return MOD16_OK;
     a.cpitch = coarse_pitch;
     a.first = first_pixel;
@@ -448,9 +354,9 @@ extern "C" int mod16_et_downscaled_f32(mod16_ctx* ctx, const mod16_downscale* gr
 
 // HOST mode of the fields: the planes resident, the F output rows tile by tile
 template <typename T>
-static int fields_host(mod16_ctx* ctx, const mod16_downscale* grid, const DsFieldArgs<T>& h, const T* const* fields) {
+static int fields_host(mod16_ctx* ctx, const mod16_downscale* grid, const DsFields<T>& h) {
     const T* dev[kDsMaxFields];
-    int rc = ds_upload_planes<T>(ctx, grid, fields, h.nfields, h.cpitch, dev);
+    int rc = upload_coarse<T>(ctx, grid, h.field, nullptr, nullptr, h.cpitch, h.nfields, "coarse planes", dev);
     if (rc != MOD16_OK) return rc;
     HostPlan p(sizeof(T));
     p.add(kOut, h.out, false, h.nfields, h.out_pitch);
@@ -458,7 +364,7 @@ static int fields_host(mod16_ctx* ctx, const mod16_downscale* grid, const DsFiel
     int64_t tile = ((int64_t)32 << 20) / ((int64_t)h.nfields * (int64_t)sizeof(T)) / kBlock * kBlock;
     tile = std::max<int64_t>(kBlock, std::min<int64_t>(tile, kTilePixels));
     auto launch = [&](const HostTile& t) {
-        DsFieldArgs<T> d = h;
+        DsFields<T> d = h;
         d.n = t.m;
         d.first = h.first + t.off;
         d.cpitch = grid->spec.coarse_cols;
@@ -475,11 +381,7 @@ static int fields_entry(mod16_ctx* ctx, const mod16_downscale* grid, const T* co
                         int64_t coarse_pitch, int64_t first_pixel, int64_t n, T* out, int64_t out_pitch, int where,
                         void* stream) {
     if (!ctx) return MOD16_ERR_ARG;
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_downscale_fields: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
+    auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, "mod16_downscale_fields: ", what); };
     if (!grid || !fields || !out) return bad("NULL grid, fields or out");
     if (nfields < 1 || nfields > kDsMaxFields) return bad("F must be between 1 and 16");
     if (where != MOD16_DEVICE && where != MOD16_HOST) return bad("`where` must be MOD16_HOST or MOD16_DEVICE");
@@ -489,7 +391,7 @@ static int fields_entry(mod16_ctx* ctx, const mod16_downscale* grid, const T* co
         return bad("the pixel range [first_pixel, first_pixel + n) leaves the raster");
     if (coarse_pitch < grid->spec.coarse_cols) return bad("coarse_pitch must be at least coarse_cols");
     if (out_pitch < n) return bad("out_pitch must be at least n");
-    DsFieldArgs<T> a;
+    DsFields<T> a;
     memset(&a, 0, sizeof a);
     for (int f = 0; f < nfields; ++f) {
         if (!fields[f]) return bad("NULL field");
@@ -504,7 +406,7 @@ static int fields_entry(mod16_ctx* ctx, const mod16_downscale* grid, const T* co
     a.out_pitch = out_pitch;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (where == MOD16_DEVICE) return launch_fields<T>(ctx, grid, a, static_cast<hipStream_t>(stream));
-    return fields_host<T>(ctx, grid, a, fields);
+    return fields_host<T>(ctx, grid, a);
 }
 
 extern "C" int mod16_downscale_fields_f64(mod16_ctx* ctx, const mod16_downscale* grid, const double* const* fields,

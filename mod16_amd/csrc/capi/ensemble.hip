@@ -50,8 +50,7 @@ static int launch_ensemble(mod16_ctx* ctx, const mod16_ensemble* ens, EnsArgs<T>
     a.members = (int)ens->members;
     a.tab = ctx->tab64.as<double>();
     a.status = ctx->status.as<unsigned>();
-    const int64_t nbatch = (a.n + kBlock - 1) / kBlock;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t)ctx->cus * 8));
+    const int grid = batch_blocks(ctx, a.n);
     if (flags & MOD16_MATH_EXACT) hipLaunchKernelGGL((ens_kernel<T, false>), dim3(grid), dim3(kBlock), 0, st, a);
     else {
         hipLaunchKernelGGL((ens_kernel<T, true>), dim3(grid), dim3(kBlock), 0, st, a);
@@ -136,11 +135,6 @@ extern "C" int mod16_et_ensemble_f32(mod16_ctx* ctx, const mod16_ensemble* ens, 
 
 // ---- per-member outputs and per-pixel quantiles (ABI 11)
 
-static int ens_grid(const mod16_ctx* ctx, int64_t n) {
-    const int64_t nbatch = (n + kBlock - 1) / kBlock;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(nbatch, (int64_t)ctx->cus * 8));
-}
-
 // The member kernel (and, behind the fast one, the kernel of the flagged pixels) for a.n pixels.
 template <typename T, typename O>
 static void launch_members(mod16_ctx* ctx, const mod16_ensemble* ens, EnsMemArgs<T, O> a, unsigned flags, hipStream_t st) {
@@ -148,7 +142,7 @@ static void launch_members(mod16_ctx* ctx, const mod16_ensemble* ens, EnsMemArgs
     a.members = (int)ens->members;
     a.tab = ctx->tab64.as<double>();
     a.status = ctx->status.as<unsigned>();
-    const int grid = ens_grid(ctx, a.n);
+    const int grid = batch_blocks(ctx, a.n);
     if (flags & MOD16_MATH_EXACT) hipLaunchKernelGGL((ens_members_kernel<T, O, false>), dim3(grid), dim3(kBlock), 0, st, a);
     else {
         hipLaunchKernelGGL((ens_members_kernel<T, O, true>), dim3(grid), dim3(kBlock), 0, st, a);

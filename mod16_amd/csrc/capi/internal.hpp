@@ -129,6 +129,12 @@ static int fail(mod16_ctx* ctx, int code, const char* msg) {
     if (ctx) ctx->err = msg;
     return code;
 }
+// ... with the message in two parts: prefix ("<entry point>: "), then what is wrong
+static int fail(mod16_ctx* ctx, int code, const char* prefix, const char* what) {
+    char msg[240];
+    snprintf(msg, sizeof msg, "%s%s", prefix, what);
+    return fail(ctx, code, msg);
+}
 
 // A workspace for `blocks` partials + the (zeroed) counter behind them
 static int ws_alloc(mod16_ctx* ctx, DiagWs& ws, int64_t blocks) {
@@ -255,6 +261,10 @@ static int grid_for(const mod16_ctx* ctx, int64_t nvec) {
     int64_t need = (nvec + kBlock - 1) / kBlock;
     int64_t cap = (int64_t)ctx->cus * ctx->grid_mult;
     return (int)std::max<int64_t>(1, std::min(need, cap));
+}
+// ... of the kernels that walk batches of kBlock items block by block: a block per batch, at most 8 per CU
+static int batch_blocks(const mod16_ctx* ctx, int64_t n) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)ctx->cus * 8));
 }
 
 // All pointers are device pointers here.
@@ -443,14 +453,13 @@ static int launch_stream(mod16_ctx* ctx, StreamArgs<T> s, hipStream_t st, double
 #ifndef MOD16_NO_REDO_LAUNCH
     if constexpr (GUARD) if (!g.static_sched) {
         const int64_t groups = (nruns + 63) / 64;
+        // a group of 64 runs per wave: both kernels get a block per kBlock runs, the first at most
+        // 8 blocks per CU, the second at most 4
+        const int cgrid = batch_blocks(ctx, groups * 64);
+        const int rgrid = std::min(cgrid, ctx->cus * 4);
         // mixed-precision forms: first the runs' cancellation lists (mod16_mixed.hpp, period_mixed)
-        if constexpr (stream_is_mixed(MODE)) {
-            const int cgrid = (int)std::max<int64_t>(1, std::min<int64_t>((groups + kBlock / 64 - 1) / (kBlock / 64),
-                                                                          (int64_t)ctx->cus * 8));
+        if constexpr (stream_is_mixed(MODE))
             hipLaunchKernelGGL((et_stream_cancel_kernel<T, MODE>), dim3(cgrid), dim3(kBlock), 0, st, s);
-        }
-        const int rgrid = (int)std::max<int64_t>(1, std::min<int64_t>((groups + kBlock / 64 - 1) / (kBlock / 64),
-                                                                      (int64_t)ctx->cus * 4));
         hipLaunchKernelGGL((et_stream_redo_kernel<T, MODE>), dim3(rgrid), dim3(kBlock), 0, st, s);
     }
 #endif

@@ -33,8 +33,7 @@ static int method_entry(mod16_ctx* ctx, int method, const T* const* in, const in
     if (n == 0) return MOD16_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     auto launch = [&](const MethodArgs<T>& d, hipStream_t st) {
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((d.n + kBlock - 1) / kBlock, (int64_t)ctx->cus * 8));
-        hipLaunchKernelGGL((method_kernel<T>), dim3(grid), dim3(kBlock), 0, st, d);
+        hipLaunchKernelGGL((method_kernel<T>), dim3(batch_blocks(ctx, d.n)), dim3(kBlock), 0, st, d);
     };
     if (where == MOD16_DEVICE) {
         // absent parameters read as NaN scalars from the ctx scratch

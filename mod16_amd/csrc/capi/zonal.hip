@@ -55,7 +55,7 @@ static int launch_zonal(mod16_ctx* ctx, ZonalArgs a, const mod16_zonal_spec& s, 
 template <typename T>
 static int launch_zonal_bounds(mod16_ctx* ctx, const ZonalArgs& a, int wk, int layers, hipStream_t st) {
     const int64_t most = std::max(a.n, wk == MOD16_ZONAL_WEIGHT_ROW ? a.rows : (int64_t)0);
-    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((most + kBlock - 1) / kBlock, (int64_t)ctx->cus * 8)), (unsigned)layers);
+    const dim3 grid((unsigned)batch_blocks(ctx, most), (unsigned)layers);
     if (wk == MOD16_ZONAL_WEIGHT_NONE) hipLaunchKernelGGL((zonal_bounds_kernel<T, kZonalWeightNone>), grid, dim3(kBlock), 0, st, a);
     else if (wk == MOD16_ZONAL_WEIGHT_ROW) hipLaunchKernelGGL((zonal_bounds_kernel<T, kZonalWeightRow>), grid, dim3(kBlock), 0, st, a);
     else hipLaunchKernelGGL((zonal_bounds_kernel<T, kZonalWeightPixel>), grid, dim3(kBlock), 0, st, a);

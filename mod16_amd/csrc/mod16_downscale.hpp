@@ -84,12 +84,16 @@ template <typename T, typename G = DsGrid> struct DsArgs {
     unsigned* status;
 };
 
-template <typename T, typename G = DsGrid> struct DsFieldArgs {
+// What a launch of the fields is given apart from the geometry (CdArgs has the same shape: `c`, then `g`)
+template <typename T> struct DsFields {
     const T* field[kDsMaxFields];   // coarse planes
     T* out;                         // [nfields][out_pitch]
     int nfields;
-    G g;
     int64_t cpitch, first, n, out_pitch;
+};
+template <typename T, typename G = DsGrid> struct DsFieldArgs {
+    DsFields<T> c;
+    G g;                            // DsGrid (column tables) or DsRowsGrid (row-affine columns)
 };
 
 // What ds_kernel leaves in out_night of a pixel outside the domain of the fast arithmetic (a quiet
@@ -310,18 +314,18 @@ __global__ void __launch_bounds__(kBlock, 1) ds_redo_kernel(const DsArgs<T, G> a
 // The interpolated fields alone: out[f][i] for the pixels of the range, through ds_interp.
 template <typename T, typename G = DsGrid>
 __global__ void __launch_bounds__(kBlock) ds_fields_kernel(const DsFieldArgs<T, G> a) {
-    const int64_t nbatch = (a.n + kBlock - 1) / kBlock;
+    const int64_t nbatch = (a.c.n + kBlock - 1) / kBlock;
     for (int64_t b = blockIdx.x; b < nbatch; b += gridDim.x) {
         const int64_t i = b * kBlock + threadIdx.x;
-        if (i >= a.n) continue;
-        const int64_t p0 = a.first + b * kBlock;
+        if (i >= a.c.n) continue;
+        const int64_t p0 = a.c.first + b * kBlock;
         const int64_t row0 = p0 / a.g.cols;
-        const DsCorners k = ds_corners(a.g, a.cpitch, row0, (uint32_t)(p0 - row0 * a.g.cols), threadIdx.x);
+        const DsCorners k = ds_corners(a.g, a.c.cpitch, row0, (uint32_t)(p0 - row0 * a.g.cols), threadIdx.x);
 #pragma nounroll
-        for (int f = 0; f < a.nfields; ++f) {
-            const T* src = a.field[f];
+        for (int f = 0; f < a.c.nfields; ++f) {
+            const T* src = a.c.field[f];
             const double v = ds_interp(k, (double)src[k.o[0]], (double)src[k.o[1]], (double)src[k.o[2]], (double)src[k.o[3]]);
-            a.out[(int64_t)f * a.out_pitch + i] = (T)v;
+            a.c.out[(int64_t)f * a.c.out_pitch + i] = (T)v;
         }
     }
 }

@@ -464,3 +464,55 @@ def test_numpy_entry_point(env):
     for math in (_lib.MATH_MIXED, _lib.DOMAIN_TRUSTED):
         with pytest.raises(ValueError, match='MATH_FAST or MATH_EXACT'):
             call(table(), cls.reshape(R, C), *shaped(arrays, names, cp), row_pos, col_pos, every=EVERY, math=math)
+
+
+def test_host_call_with_pitched_coarse_series(env):
+    """_lib.Downscale.composite, where=HOST, numpy addresses: fine 6 x 10 over coarse 5 x 7, three days in
+    periods of two. Every coarse series with its rows 9 elements apart and its planes a plane's span
+    ((H - 1) 9 + W) apart, NaN in between -- the upload's copy per row -- against the same call on packed
+    planes, bit for bit, counts included. temp_annual is one coarse plane, sw_rad_night a scalar, albedo,
+    fPAR and LAI fine daily arrays."""
+    torch, mod16_amd, _lib, cp, ds = env
+    shape, days, period, pitch = (6, 10), 3, 2, 9
+    n, periods = shape[0] * shape[1], 2
+    cls3, fine = synth.drivers((days, n), seed=91, special=True)
+    planes = [synth.drivers((H, W), seed=92 + t, special=False)[1] for t in range(days)]
+    names = tuple(name for name in ds.MET_DRIVERS if name != 'sw_rad_night') + ('day_hours',)
+    series = {name: np.stack([planes[t][k] for t in range(days)]) for k, name in enumerate(cp.ARRAY_NAMES[:14]) if name in names}
+    series['day_hours'] = np.random.default_rng(95).uniform(6, 18, (days, H, W))
+    series['temp_annual'] = series['temp_annual'][:1]
+    cls = np.ascontiguousarray(cls3[0])
+    row_pos, col_pos = ds.positions(-0.8, 0.9, shape[0], 0.0, 1.0), ds.positions(-9.3, 2.1, shape[1], 0.0, 1.0)
+    eng = engine()
+    torch.cuda.synchronize()
+
+    def call(cpitch):
+        span = (H - 1) * cpitch + W
+        keep, ptrs, pstride, tstride, every = [], [], [], [], []
+        for k, name in enumerate(cp.ARRAY_NAMES):
+            if name in names:
+                a = series[name]
+                mem = np.full((len(a) - 1) * span + span, np.nan)
+                view = np.lib.stride_tricks.as_strided(mem, a.shape, (span * 8, cpitch * 8, 8))
+                view[...] = a
+                assert np.isnan(mem).sum() == len(a) * (H - 1) * (cpitch - W) + np.isnan(a).sum()
+                pstride.append(0); tstride.append(span if len(a) > 1 else 0); every.append(1 if len(a) > 1 else days)
+            elif name == 'sw_rad_night':
+                mem = np.zeros(1)
+                pstride.append(0); tstride.append(0); every.append(days)
+            else:
+                mem = np.ascontiguousarray(fine[k])
+                pstride.append(1); tstride.append(n); every.append(1)
+            keep.append(mem)
+            ptrs.append(mem.ctypes.data)
+        outs = [np.full((periods, n), -7.0) for _ in range(2)] + [np.full((periods, n), 7, np.uint16) for _ in range(2)]
+        low = _lib.Downscale(eng.ctx, shape, (H, W), row_pos, col_pos, wrap=True, method='bilinear')
+        low.composite('float64', n, days, period, cls.ctypes.data, ptrs, pstride, tstride, every, ds.coarse_mask(names),
+                      cpitch, 0, outs[0].ctypes.data, outs[1].ctypes.data, outs[2].ctypes.data, outs[3].ctypes.data, n,
+                      flags=_lib.MATH_FAST, where=_lib.HOST)
+        low.close()
+        return outs
+
+    packed, pitched = call(W), call(pitch)
+    same_results(pitched, packed, 'pitched coarse series')
+    assert 0.5 < np.isfinite(packed[0]).mean() and (packed[2] <= period).all() and (packed[2] > 0).any()

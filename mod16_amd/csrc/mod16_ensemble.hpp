@@ -85,9 +85,8 @@ __device__ __forceinline__ EnsPeriod ens_period_prep(const PixelIn<double>& x, d
     double avp = esat - vpd;
     double resat = M::rcp(esat);
     double rh = avp * resat;
-    rh = __builtin_fma(__builtin_fma(-rh, esat, avp), resat, rh);
-    rh = (rh > 1.0) ? 1.0 : rh;
-    rh = (avp < 0.0) ? 0.0 : rh;                                   // :670-673
+    rh = M::fma_unit(__builtin_fma(-rh, esat, avp), resat, rh);    // :670-673, as period_fast has it
+    rh = __builtin_fma(avp, 0.0, rh);
     double rh2 = rh * rh;
     c.dry = rh < 0.7;                                              // :764 (NaN compares false)
     c.fwet = c.dry ? 0.0 : rh2 * rh2;
@@ -162,7 +161,7 @@ struct EnsMember {
 __device__ __forceinline__ EnsMember ens_member(const EnsPixel& px, const double* l) {
 #pragma clang fp contract(off)
     EnsMember m;
-    const double tmin_close = l[0 * kLutCols], tmin_open = l[1 * kLutCols];
+    const double tmin_close = l[0 * kLutCols];
     m.vpd_open = l[2 * kLutCols];
     m.gl_sh = l[4 * kLutCols];
     const double gl_wv = l[5 * kLutCols];
@@ -177,10 +176,8 @@ __device__ __forceinline__ EnsMember ens_member(const EnsPixel& px, const double
     m.glsh_lai = m.gl_sh * px.lai;
     m.glwv_lai = gl_wv * px.lai;
     m.drbl = rbl_max - m.rbl_min;
-    double m_tmin = (px.tm - tmin_close) * inv_dtmin;
-    m_tmin = (px.tm < tmin_close) ? 0.0 : m_tmin;
-    m_tmin = (px.tm >= tmin_open) ? 1.0 : m_tmin;
-    m.csl_mt = csl * m_tmin;
+    typedef FastMath<double> M;
+    m.csl_mt = csl * M::nan_from(M::mul_unit(px.tm - tmin_close, inv_dtmin), px.tm);   // as et_pixel_fast has it
     return m;
 }
 
@@ -191,7 +188,7 @@ __device__ __forceinline__ double ens_period_eval(const EnsPixel& px, const EnsP
 #pragma clang fp contract(off)
     typedef FastMath<double> M;
     const double tiny = 1e-7;
-    const double vramp = M::clamp01((c.vpd - m.vpd_open) * m.inv_dvpd);
+    const double vramp = M::mul_unit(c.vpd - m.vpd_open, m.inv_dvpd);
     double canopy, soil, trans;
     {   // wet canopy, :866-961
         const double g_e = m.glwv_lai * c.fwet;

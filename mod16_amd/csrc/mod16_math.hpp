@@ -102,11 +102,26 @@ template <> struct FastMath<double> {
         return d;
     }
 
-    // min(max(x, 0), 1) as v_max_f64 + v_min_f64 (a NaN x gives 0: v_max passes it over)
-    static __device__ __forceinline__ T clamp01(T x) {
+    // a * b and a * b + c forced into [0, 1] by the VOP3 `clamp` output modifier of the instruction
+    // that produces the value: nothing behind it -- no v_max / v_min pair, no compares and 64-bit
+    // selects. Waves run with MODE.DX10_CLAMP = 1 (what the kernel descriptor starts them with; no
+    // kernel here changes that bit), where the modifier makes a NaN +0 (as the v_max_f64 / v_min_f64 pair of round 6 did, which passed a NaN over); -0 and
+    // everything below become +0, everything above 1 (inf too) becomes 1
+    // (tools/probe_clamp.hip, profiles/r07_probe_clamp.txt). Where the NaN has to stay: nan_from.
+    static __device__ __forceinline__ T mul_unit(T a, T b) {
         T d;
-        asm("v_max_f64 %0, %1, 0\n\tv_min_f64 %0, %0, 1.0" : "=&v"(d) : "v"(x));
+        asm("v_mul_f64 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(b));
         return d;
+    }
+    static __device__ __forceinline__ T fma_unit(T a, T b, T c) {
+        T d;
+        asm("v_fma_f64 %0, %1, %2, %3 clamp" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+        return d;
+    }
+    // x, or the NaN that `src` is (src: a result of arithmetic, so a quiet NaN -- its high word
+    // alone says so): one v_cmp_u_f64 and ONE v_cndmask_b32
+    static __device__ __forceinline__ T nan_from(T x, T src) {
+        return __hiloint2double((src != src) ? __double2hiint(src) : __double2hiint(x), __double2loint(x));
     }
 
     // 1/x: v_rcp_f64 (about 2^-23 relative) + one Newton step -> ~2^-45.

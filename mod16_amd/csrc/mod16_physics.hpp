@@ -653,11 +653,15 @@ __device__ __forceinline__ void period_fast(const PixelIn<T>& x, const ClassPar<
     // finished like an IEEE division (residual correction): x / x = 1 exactly
     T resat = M::rcp(esat);
     T rh = avp * resat;
-    rh = __builtin_fma(__builtin_fma(-rh, esat, avp), resat, rh);
-    // flat selects, innermost first: hipcc turns a NESTED conditional into exec-masked
-    // branches (s_and_saveexec / s_cbranch / v_mov / s_or: ~8 instructions a level)
-    rh = (rh > T(1)) ? T(1) : rh;
-    rh = (avp < T(0)) ? T(0) : rh;                                 // :670-673
+    // ... and clamped to [0, 1] (:670-673) by the correction's own output modifier (round 7; two
+    // compares and four v_cndmask before): avp < 0 <=> rh < 0 for esat > 0, and where esat has
+    // underflowed to 0 (below 41.5 K) the quotient is NaN and the modifier makes it the 0 that
+    // avp = -vpd < 0 asked for. The modifier makes EVERY NaN 0, so the NaN of avp (a NaN temperature
+    // or vpd) is put back: avp * 0 is -0, +0 or NaN, and nothing else since the guard admits no
+    // infinite vpd. (Bit-identical to the selects but for vpd <= 0 below 41.5 K: 0 now, NaN before,
+    // 1 in the reference.)
+    rh = M::fma_unit(__builtin_fma(-rh, esat, avp), resat, rh);
+    rh = __builtin_fma(avp, T(0), rh);
     T rh2 = rh * rh;
     const bool dry = rh < T(0.7);                                  // :764 (NaN compares false)
     T fwet = dry ? T(0) : rh2 * rh2;
@@ -680,7 +684,7 @@ __device__ __forceinline__ void period_fast(const PixelIn<T>& x, const ClassPar<
     T g_rr = (K<T>::sigma4 * (t2 * t2)) * M::rcp(nn);
     T rcfv = rho_cp * vpd;             // rho Cp vpd
 #if MOD16_F64_CAND >= 2
-    T vramp = M::clamp01((vpd - p.vpd_open) * p.inv_dvpd);
+    T vramp = M::mul_unit(vpd - p.vpd_open, p.inv_dvpd);           // (round 7: the product's own clamp)
 #endif
 
     // -- wet canopy, :866-961 in conductances:
@@ -705,7 +709,7 @@ __device__ __forceinline__ void period_fast(const PixelIn<T>& x, const ClassPar<
 #if MOD16_F64_CAND >= 2
         // rbl_min + (rbl_max - rbl_min) clamp01((vpd - vpd_open) / (vpd_close - vpd_open)), :527-531:
         // exactly rbl_min up to vpd_open, rbl_max to an ulp from vpd_close on. A NaN vpd leaves the
-        // clamp as 0 (v_max_f64 passes a NaN over) -- and the period as NaN through rho Cp vpd.
+        // clamp as 0 (the `clamp` modifier under DX10_CLAMP) -- and the period as NaN through rho Cp vpd.
         T r0 = __builtin_fma(vramp, sh.drbl, p.rbl_min);
 #else
         T r0 = __builtin_fma(-(p.vpd_close - vpd), p.rbl_slope, p.rbl_max);   // :527-531
@@ -817,9 +821,11 @@ __device__ __forceinline__ PixelOut<T> et_pixel_fast(const PixelIn<T>& x, const 
 #endif
     sh.drbl = p.rbl_max - p.rbl_min;
     T tm = x.tmin - K<T>::t0;
-    sh.m_tmin = (tm - p.tmin_close) * p.inv_dtmin;
-    sh.m_tmin = (tm < p.tmin_close) ? T(0) : sh.m_tmin;
-    sh.m_tmin = (tm >= p.tmin_open) ? T(1) : sh.m_tmin;
+    // the Tmin ramp, :1148: the product's own clamp (round 7; two compares and four v_cndmask
+    // before; 1 - 1 ulp instead of 1 where the product rounds below 1 at tm == tmin_open). Tmin is
+    // not a guarded driver: an infinite one is a ramp of 0 or 1, so only its NaN is put back.
+    typedef FastMath<T> M;
+    sh.m_tmin = M::nan_from(M::mul_unit(tm - p.tmin_close, p.inv_dtmin), tm);
     period_fast<T, true, PET, KP, RAW>(x, p, sh, tb, x.t_d, x.vpd_d, a_d, rs_d, o.canopy_d, o.soil_d, o.trans_d,
                                        &o.pet_d, dav_d);
     T rn_n = __builtin_fma(x.sw_n, sh.oma, x.lw_n);

@@ -1148,6 +1148,71 @@ MOD16_API int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, c
                                void* const* out, uint8_t* source, int where, void* stream, size_t stage_bytes);
 
 /*
+ * Hourly reanalysis aggregated into day / night drivers (added under ABI 16, new symbols only;
+ * mod16_amd.aggregate_daynight, RasterEngine.daynight): the step in front of the downscaled composite --
+ * hourly planes of T10M, QV10M, PS, SWGDN and LWGNT in, the coarse planes mod16_et_composite_downscaled_*
+ * takes out. One launch reads every hourly value once. The definition is the numpy statement
+ * mod16_amd/daynight.py (day_weights, sw_weights, split_field, aggregate); the split is this package's
+ * definition, not a transcription of the operational MOD16 preprocessing:
+ *
+ *   inputs      fields[5] = t, qv, ps, sw, lw (an entry may be NULL where no requested output needs it):
+ *               fields[f][s * in_plane + r * in_pitch + c], step s = d * steps_per_day + k (days 1 ... 4096,
+ *               steps_per_day H 1 ... 48, step k covers the UTC hours [k delta, (k + 1) delta), delta = 24 /
+ *               H), row r, column c of a rows x cols grid. NaN is the missing value. The tables are HOST
+ *               pointers (float64) in both modes: half_day[days][rows] (0 ... 12 hours), noon[days] (0 ...
+ *               24), offset[cols] (longitude / 15, -12 ... 12).
+ *   weight      per step and cell, w in [0, 1]. MOD16_DAYNIGHT_SOLAR: a = ((noon - half_day) - offset) / delta,
+ *               b = ((noon + half_day) - offset) / delta, w = min(sum over m in (-H, 0, +H), in that order, of
+ *               max(min(k + 1, b + m) - max(k, a + m), 0), 1). MOD16_DAYNIGHT_SW: 1.0 where sw > threshold,
+ *               else 0.0, NaN where sw is NaN (sw is then needed by every output).
+ *   result      per day and cell in float64, sums sequential in k from 0.0, products rounded before they are
+ *               added (no contraction): sum_w = sum w, sum_n = sum (1 - w); per field X mean = (sum X) / H,
+ *               day = (sum w X) / sum_w where sum_w > 0 else mean, night = (sum (1 - w) X) / sum_n where
+ *               sum_n > 0 else mean (polar night and polar day stay finite).
+ *   outputs     out[10] (NULL: skip), out[o][d * out_plane + r * out_pitch + c] of out_type, each value
+ *               rounded once: 0 lw_net_day, 1 lw_net_night, 2 sw_rad_day, 3 temp_day, 4 temp_night, 5 tmin
+ *               (min over k of t, NaN if any step is NaN), 6 vpd_day = vpd(qv_day, ps_day, t_day) as
+ *               mod16_method_* computes MOD16.vpd in float64, 7 vpd_night (the same of the night values,
+ *               negative values 0), 8 day_hours = delta sum_w, 9 temp_mean (mean of t). temp_annual[r *
+ *               out_pitch + c] (NULL: skip) = (sum over d of temp_mean, float64, sequential in d) / days.
+ *               sw_rad_night is not produced (callers pass 0.0). Every requested element [d][r][0, cols)
+ *               is written exactly once; padding is not touched. Pointers may have any element alignment,
+ *               in_pitch / out_pitch any value >= cols and in_plane / out_plane any value >= (rows - 1)
+ *               pitch + cols, in elements; where bases, pitches and plane strides are multiples of two
+ *               elements the kernel takes vector accesses, with the same bits. No atomics: two calls
+ *               give the same bits. temp_annual takes 8 bytes of stream-ordered device memory per cell
+ *               and day of the launch for the unrounded daily means.
+ *   where       MOD16_DEVICE: device pointers (the tables stay host pointers: they are checked, then
+ *               uploaded on `stream`), asynchronous on `stream`. MOD16_HOST: host pointers; chunks of whole
+ *               days are staged through the context's slabs, stage_bytes / (bytes of a day's inputs and
+ *               outputs) days at a time (0: 128 MiB; at least one day). The result does not depend on
+ *               stage_bytes.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_daynight: ...")
+ *               NULL spec, fields or out; "an output is requested whose field is NULL"; "no output is
+ *               requested"; rows or cols outside 0 ... 2^30, days outside 0 ... 4096, steps_per_day outside
+ *               1 ... 48; a pitch below cols or a plane stride below a plane; a NULL table or a table value
+ *               out of its range or not finite (MOD16_DAYNIGHT_SOLAR); a threshold that is not finite
+ *               (MOD16_DAYNIGHT_SW); an unknown mode, out_type or `where`; "an output overlaps an input or
+ *               another output". Zero days or zero cells is MOD16_OK.
+ */
+enum mod16_daynight_mode { MOD16_DAYNIGHT_SOLAR = 0, MOD16_DAYNIGHT_SW = 1 };
+enum mod16_daynight_out { MOD16_DAYNIGHT_F32 = 0, MOD16_DAYNIGHT_F64 = 1 };
+typedef struct mod16_daynight_spec {
+    int64_t rows, cols;                  /* the grid: latitude rows, longitude columns */
+    int32_t days, steps_per_day;
+    int32_t mode, out_type;
+    double threshold;                    /* MOD16_DAYNIGHT_SW */
+    int64_t in_pitch, in_plane;          /* elements between two rows / two steps of a field */
+    int64_t out_pitch, out_plane;        /* ... between two rows / two days of an output (temp_annual: out_pitch) */
+} mod16_daynight_spec;
+MOD16_API int mod16_daynight_f32(mod16_ctx* ctx, const mod16_daynight_spec* spec, const float* const* fields,
+                                 const double* half_day, const double* noon, const double* offset, void* const* out,
+                                 void* temp_annual, int where, void* stream, size_t stage_bytes);
+MOD16_API int mod16_daynight_f64(mod16_ctx* ctx, const mod16_daynight_spec* spec, const double* const* fields,
+                                 const double* half_day, const double* noon, const double* offset, void* const* out,
+                                 void* temp_annual, int where, void* stream, size_t stage_bytes);
+
+/*
  * Downscaled forward run (ABI 14; mod16_amd.evapotranspiration_downscaled,
  * RasterEngine.downscale_grid): ET day and night for a contiguous range of pixels of a rows x cols
  * fine raster, each of the 14 drivers a scalar, a fine array or a COARSE coarse_rows x coarse_cols

@@ -106,6 +106,20 @@ class GapfillSpec(C.Structure):
 GAPFILL_U8, GAPFILL_F32, GAPFILL_F64 = 0, 1, 2     # enum mod16_gapfill_out
 
 
+class DaynightSpec(C.Structure):
+    '''``mod16_daynight_spec`` (include/mod16_hip.h): the grid, days and steps per day, the mode and its
+    threshold, the output type, and the row pitch and plane stride of the fields and of the outputs.'''
+    _fields_ = [('rows', C.c_int64), ('cols', C.c_int64), ('days', C.c_int32), ('steps_per_day', C.c_int32),
+                ('mode', C.c_int32), ('out_type', C.c_int32), ('threshold', C.c_double), ('in_pitch', C.c_int64),
+                ('in_plane', C.c_int64), ('out_pitch', C.c_int64), ('out_plane', C.c_int64)]
+
+
+DAYNIGHT_SOLAR, DAYNIGHT_SW = 0, 1        # enum mod16_daynight_mode
+DAYNIGHT_F32, DAYNIGHT_F64 = 0, 1         # enum mod16_daynight_out
+_DAYNIGHT_ARGS = [C.c_void_p, C.POINTER(DaynightSpec), _PP, C.c_void_p, C.c_void_p, C.c_void_p, _PP, C.c_void_p,
+                  C.c_int, C.c_void_p, C.c_size_t]
+
+
 class DownscaleSpec(C.Structure):
     '''``mod16_downscale_spec`` (include/mod16_hip.h): the fine raster, the coarse grid, whether its
     column axis is periodic, the weighting method.'''
@@ -355,6 +369,8 @@ PROTOTYPES = {
     'mod16_zonal_lds_zones': (C.c_int, []),
     'mod16_et_composite_downscaled_f64': (C.c_int, _COMPOSITE_DOWNSCALED_ARGS),
     'mod16_et_composite_downscaled_f32': (C.c_int, _COMPOSITE_DOWNSCALED_ARGS),
+    'mod16_daynight_f64': (C.c_int, _DAYNIGHT_ARGS),
+    'mod16_daynight_f32': (C.c_int, _DAYNIGHT_ARGS),
 }
 
 _lib = None
@@ -592,6 +608,26 @@ class Context:
             self.handle, C.byref(spec), ptr_array(list(fields)), qc, good,
             ptr_array(list(fallback)) if fallback is not None else None, ptr_array(list(out)), source,
             int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
+
+    def daynight(self, dtype, out_type, rows, cols, days, steps_per_day, fields, tables, out, temp_annual, in_pitch,
+                 in_plane, out_pitch, out_plane, mode=DAYNIGHT_SOLAR, threshold=0.0, where=HOST, stream=None,
+                 stage_bytes=None):
+        '''Thin wrapper of mod16_daynight_f64 / _f32 (``dtype``: the fields' type). ``fields`` holds five
+        raw addresses or None (t, qv, ps, sw, lw), ``out`` ten (``daynight.OUTPUT_NAMES``), ``temp_annual``
+        one; ``tables`` is None or three contiguous float64 numpy arrays (half_day, noon, offset: host
+        memory in both modes); pitches and plane strides in elements; ``stage_bytes`` None: the
+        library's default.'''
+        spec = DaynightSpec()
+        spec.rows, spec.cols, spec.days, spec.steps_per_day = int(rows), int(cols), int(days), int(steps_per_day)
+        spec.mode, spec.out_type, spec.threshold = int(mode), int(out_type), float(threshold)
+        spec.in_pitch, spec.in_plane = int(in_pitch), int(in_plane)
+        spec.out_pitch, spec.out_plane = int(out_pitch), int(out_plane)
+        half, noon, offset = tables if tables is not None else (None, None, None)
+        fn = typed(self.lib, 'mod16_daynight', dtype)
+        self.check(fn(self.handle, C.byref(spec), ptr_array(list(fields)),
+                      None if half is None else half.ctypes.data, None if noon is None else noon.ctypes.data,
+                      None if offset is None else offset.ctypes.data, ptr_array(list(out)), temp_annual,
+                      int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
 
     @staticmethod
     def _zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch, bounds=None):

@@ -17,3 +17,4 @@
 #include "capi/downscale.hip"
 #include "capi/composite_downscale.hip"
 #include "capi/zonal.hip"
+#include "capi/daynight.hip"

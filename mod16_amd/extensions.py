@@ -512,6 +512,81 @@ def gapfill_series(fields, qc=None, good=None, max_gap=None, fallback=None, dtyp
     return filled, (srcs[0] if single else tuple(srcs))
 
 
+def aggregate_daynight(fields, half_day=None, noon=None, offset=None, sw_threshold=None, steps_per_day=24,
+                       outputs=None, dtype=None, out=None, device=0, stage_bytes=None):
+    r'''
+    (Extension.) Hourly reanalysis aggregated into the model's day / night drivers in one kernel
+    launch per staged chunk of days (``mod16_daynight_*``): the planes of ``lw_net_day/night``,
+    ``sw_rad_day``, ``temp_day/night``, ``tmin``, ``vpd_day/night``, the hours of daylight, the daily mean
+    temperature and ``temp_annual`` on the reanalysis grid -- what
+    ``evapotranspiration_composite_downscaled`` takes as its coarse arrays. The definition is
+    ``mod16_amd.daynight`` (this package's day / night split, not a transcription of the operational
+    MOD16 preprocessing).
+
+    Parameters
+    ----------
+    fields : dict
+        the hourly series by name -- ``'t'`` (K), ``'qv'``, ``'ps'`` (Pa), ``'sw'``, ``'lw'``, those the
+        requested outputs need -- each ``(D * H, R, W)``, all float32 or all float64; NaN is missing
+    half_day, noon, offset : numpy.ndarray
+        the float64 tables of ``'solar'`` mode: ``(D, R)`` half day lengths in hours, ``(D,)`` local
+        solar noon (Default: 12) and ``(W,)`` longitude / 15 (``mod16_amd.daynight.solar_tables``)
+    sw_threshold : float
+        (Optional) instead of the tables: a step counts as day where ``sw > sw_threshold``
+    steps_per_day : int
+        ``H``, 1 ... 48 (Default: 24)
+    outputs : sequence of str
+        (Optional) names of ``mod16_amd.daynight.OUTPUT_NAMES`` and ``'temp_annual'`` (Default: every one
+        the fields given allow)
+    dtype : str
+        ``'float32'`` or ``'float64'`` (Default: float32 only if the fields are float32)
+    out : dict
+        (Optional) the result arrays by name, C-contiguous, written in place
+    stage_bytes : int
+        (Optional) device memory a chunk of days may take; the result does not depend on it
+
+    Returns
+    -------
+    (DayNight, numpy.ndarray)
+        the ``(D, R, W)`` series as a namedtuple and the ``(R, W)`` ``temp_annual``; None where an output
+        was not requested. ``sw_rad_night`` is not produced: pass 0.0, as the reference's loader does.
+    '''
+    from . import daynight as _dn
+    flds = {k: np.asarray(v) for k, v in dict(fields).items() if v is not None}
+    D, H, R, W, mode, tables, threshold, names = _dn.check_call(
+        {k: v.shape for k, v in flds.items()}, steps_per_day, half_day, noon, offset, sw_threshold, outputs)
+    in_dtype = _dn.check_dtypes(flds)
+    out_dtype = _dn.check_out_dtype(dtype, in_dtype)
+    _check_stage_bytes(stage_bytes)
+    flds = {k: np.ascontiguousarray(v) for k, v in flds.items()}
+    shapes = {n: ((R, W) if n == 'temp_annual' else (D, R, W)) for n in names}
+    if out is None:
+        outs = {n: np.empty(shapes[n], out_dtype) for n in names}
+    else:
+        outs = dict(out)
+        if sorted(outs) != sorted(names):
+            raise ValueError('out must hold exactly the requested outputs: %s' % ', '.join(names))
+        for n in names:
+            o = outs[n]
+            if not (isinstance(o, np.ndarray) and o.shape == shapes[n] and o.dtype == out_dtype
+                    and o.flags.c_contiguous and o.flags.writeable):
+                raise ValueError("out['%s'] must be a writeable C-contiguous %s array of shape %s"
+                                 % (n, out_dtype, shapes[n]))
+    if D and R and W:
+        try:
+            _lib.context(device).daynight(
+                in_dtype, _dn.OUT_TYPES[out_dtype.name], R, W, D, H,
+                [flds[f].ctypes.data if f in flds else None for f in _dn.FIELD_NAMES], tables,
+                [outs[n].ctypes.data if n in outs else None for n in _dn.OUTPUT_NAMES],
+                outs['temp_annual'].ctypes.data if 'temp_annual' in outs else None, W, R * W, W, R * W,
+                mode=_dn.MODES[mode], threshold=threshold, where=_lib.HOST, stage_bytes=stage_bytes)
+        except _lib.Mod16Error as e:
+            if e.status == _lib.ERR_ARG and 'overlaps' in str(e):
+                raise ValueError(str(e))
+            raise
+    return _dn.DayNight(*[outs.get(n) for n in _dn.OUTPUT_NAMES]), outs.get('temp_annual')
+
+
 def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=None, device=0, stage_bytes=None):
     r'''
     (Extension.) Zonal statistics of a raster: per zone (river basin, country, biome, climate-grid

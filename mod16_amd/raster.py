@@ -879,6 +879,98 @@ class RasterEngine(object):
             return filled
         return filled, (src[0] if single else tuple(src[f] for f in range(len(flds))))
 
+    def daynight(self, fields, half_day=None, noon=None, offset=None, sw_threshold=None, steps_per_day=24,
+                 outputs=None, dtype=None, out=None):
+        '''Enqueue the day / night aggregation on the current stream: hourly reanalysis fields in, the
+        coarse planes ``DownscaleGrid.composite`` and ``DownscaleGrid.run`` take out
+        (``mod16_daynight_*``; the definition is ``mod16_amd.daynight``).
+
+        ``fields`` is a dict of device tensors by name -- ``'t'``, ``'qv'``, ``'ps'``, ``'sw'``, ``'lw'``,
+        those the requested outputs need -- each ``(D * H, R, W)`` with ``H = steps_per_day``, all
+        float32 or all float64, unit stride in columns and one row pitch >= W and one stride in time
+        of at least a plane for all of them (views of larger tensors are fine). The day weights come
+        from the float64 host tables ``half_day[D, R]``, ``noon[D]`` (default 12) and ``offset[W]``
+        (``mod16_amd.daynight.solar_tables``), or, with ``sw_threshold``, from ``sw > sw_threshold``.
+        ``outputs``: names of ``mod16_amd.daynight.OUTPUT_NAMES`` and ``'temp_annual'`` (default:
+        every one the fields given allow); ``dtype``: ``'float32'`` or ``'float64'`` (default: the
+        engine's, what its ``downscale_grid`` takes).
+
+        Returns ``(DayNight, temp_annual)``: ``(D, R, W)`` tensors and one ``(R, W)`` tensor with one
+        common row pitch, None where an output was not requested. ``sw_rad_night`` is not produced:
+        pass 0.0. ``out`` may give the tensors as a dict by name (one row pitch and one stride in
+        time for all; what lies between the rows is not touched); no output may overlap an input.
+        Asynchronous, like ``composite``.'''
+        from . import daynight as _dn
+        torch = _torch()
+        flds = {k: v for k, v in dict(fields).items() if v is not None}
+        for k, t in flds.items():
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or \
+                    t.dtype not in (torch.float32, torch.float64):
+                raise TypeError("fields['%s'] must be a float32 or float64 tensor on cuda:%d" % (k, self.device))
+        D, H, R, W, mode, tables, threshold, names = _dn.check_call(
+            {k: tuple(t.shape) for k, t in flds.items()}, steps_per_day, half_day, noon, offset, sw_threshold, outputs)
+        in_types = set(t.dtype for t in flds.values())
+        if len(in_types) != 1:
+            raise ValueError('fields must be all float32 or all float64')
+        in_dtype = np.dtype('float32' if in_types.pop() == torch.float32 else 'float64')
+        out_dtype = _dn.check_out_dtype(self.np_dtype if dtype is None else dtype, in_dtype)
+        tdtype = {'float32': torch.float32, 'float64': torch.float64}[out_dtype.name]
+
+        def layout(t, what, planes):
+            '''-> (row pitch, plane stride) in elements of a (planes, R, W) or (R, W) tensor'''
+            if W > 1 and t.stride(-1) != 1:
+                raise ValueError('%s must have unit stride in columns' % what)
+            pitch = t.stride(-2) if R > 1 else W
+            if pitch < W:
+                raise ValueError('%s: the distance between rows must be at least %d' % (what, W))
+            least = (R - 1) * pitch + W
+            plane = t.stride(0) if t.dim() == 3 and planes > 1 else least
+            if plane < least:
+                raise ValueError('%s: the stride in time must be at least a plane (%d elements)' % (what, least))
+            return pitch, plane
+        lay = set(layout(t, "fields['%s']" % k, D * H) for k, t in flds.items())
+        if len(lay) != 1:
+            raise ValueError('the fields must share one distance between rows and one stride in time')
+        in_pitch, in_plane = lay.pop()
+        series = [n for n in names if n != 'temp_annual']
+        if out is None:
+            outs = {n: torch.empty((D, R, W), dtype=tdtype, device=self._dev()) for n in series}
+            if 'temp_annual' in names:
+                outs['temp_annual'] = torch.empty((R, W), dtype=tdtype, device=self._dev())
+        else:
+            outs = dict(out)
+            if sorted(outs) != sorted(names):
+                raise ValueError('out must hold exactly the requested outputs: %s' % ', '.join(names))
+        olay = set()
+        for n in names:
+            o, shape = outs[n], ((R, W) if n == 'temp_annual' else (D, R, W))
+            if not isinstance(o, torch.Tensor) or not o.is_cuda or o.device.index != self.device or o.dtype != tdtype:
+                raise TypeError("out['%s'] must be a %s tensor on cuda:%d" % (n, tdtype, self.device))
+            if tuple(o.shape) != shape:
+                raise ValueError("out['%s'] must have shape %r" % (n, shape))
+            pitch, plane = layout(o, "out['%s']" % n, D)
+            olay.add((pitch, plane) if n != 'temp_annual' and D > 1 else (pitch, None))
+        pitches = set(p for p, _ in olay)
+        planes = set(q for _, q in olay if q is not None)
+        if len(pitches) > 1 or len(planes) > 1:
+            raise ValueError('the out tensors must share one distance between rows and one stride in time')
+        out_pitch = pitches.pop() if pitches else W
+        out_plane = planes.pop() if planes else (R - 1) * out_pitch + W
+        if D and R and W:
+            try:
+                self.ctx.daynight(
+                    in_dtype, _dn.OUT_TYPES[out_dtype.name], R, W, D, H,
+                    [flds[f].data_ptr() if f in flds else None for f in _dn.FIELD_NAMES], tables,
+                    [outs[n].data_ptr() if n in outs else None for n in _dn.OUTPUT_NAMES],
+                    outs['temp_annual'].data_ptr() if 'temp_annual' in outs else None, in_pitch, in_plane,
+                    out_pitch, out_plane, mode=_dn.MODES[mode], threshold=threshold, where=_lib.DEVICE,
+                    stream=self._stream())
+            except _lib.Mod16Error as e:
+                if e.status == _lib.ERR_ARG and 'overlaps' in str(e):
+                    raise ValueError(str(e))
+                raise
+        return _dn.DayNight(*[outs.get(n) for n in _dn.OUTPUT_NAMES]), outs.get('temp_annual')
+
     def _zonal_args(self, values, zones, area, cols, first_pixel):
         '''The checks ``zonal`` and ``zonal_bounds`` share: -> (K, n, value pitch, weight kind, address
         of the weights or None, cols, first_pixel).'''

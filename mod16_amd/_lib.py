@@ -54,6 +54,15 @@ class Mod16Error(RuntimeError):
         self.status = status
 
 
+def overlap_as_value_error(e):
+    '''``except Mod16Error as e: raise overlap_as_value_error(e)``: the library's refusal of an output
+    that overlaps an input (or another output) is the caller's mistake in the arguments -- ValueError, as
+    the other argument checks raise; any other error is raised again as it is.'''
+    if e.status == ERR_ARG and 'overlaps' in str(e):
+        return ValueError(str(e))
+    return e
+
+
 _PP = C.POINTER(C.c_void_p)
 _I64P = C.POINTER(C.c_int64)
 

@@ -34,7 +34,7 @@ static int comp_check_spec(mod16_ctx* ctx, const char* prefix, const mod16_compo
     if (count_pet && !out_pet) return bad("count_pet needs out_pet");
     if (out_pitch < spec->n) return bad("out_pitch must be at least n");
     if (stage_bytes < 0) return bad("stage_bytes must not be negative");
-    if (where != MOD16_DEVICE && where != MOD16_HOST) return bad("`where` must be MOD16_HOST or MOD16_DEVICE");
+    if (const char* what = check_where(where)) return bad(what);
     return MOD16_OK;
 }
 
@@ -91,7 +91,7 @@ static void comp_fill(CompCall<T>& c, const mod16_composite_spec* spec, const ui
     c.a.rescale = spec->rescale;
     c.pet = out_pet != nullptr;
     c.periods = (spec->days + spec->period_days - 1) / spec->period_days;
-    c.stage_bytes = stage_bytes ? stage_bytes : (int64_t)128 << 20;
+    c.stage_bytes = stage_budget((size_t)stage_bytes);
 }
 
 // The kernels of a family for arguments `a` (all pointers are device pointers here). K names them:
@@ -154,10 +154,7 @@ static int comp_host(mod16_ctx* ctx, const CompCall<T>& h, const T* const* resid
     // a slab holds the rows back to back (whole tiles of 256 pixels: no rounding), the stagger once per
     // array, the class bytes: a year of daily drivers (some 3900 rows of float64) still gets tiles of
     // 4096 pixels out of the default 128 MiB
-    const int64_t fixed = (int64_t)p.nwide * (int64_t)kStagger + 512;
-    const int64_t per_pixel = (int64_t)p.wide_rows * (int64_t)sizeof(T) + 1;
-    int64_t tile = (h.stage_bytes - fixed) / per_pixel / kBlock * kBlock;
-    tile = std::max<int64_t>(kBlock, std::min<int64_t>(tile, kTilePixels));
+    const int64_t tile = stage_tile(p, sizeof(T), h.stage_bytes);
     auto on_tile = [&](const HostTile& t) {
         CompArgs<T> d = a;
         d.n = t.m;

@@ -9,13 +9,6 @@ constexpr unsigned kDnNeeds[kDnOutputs] = {1u << kDnLw, 1u << kDnLw, 1u << kDnSw
                                            (1u << kDnT) | (1u << kDnQv) | (1u << kDnPs),
                                            (1u << kDnT) | (1u << kDnQv) | (1u << kDnPs), 0u, 1u << kDnT};
 
-struct DnRange { uintptr_t lo, hi; };
-// `planes` planes of `rows` rows of n elements, rows `pitch` and planes `plane` elements apart
-DnRange dn_range(const void* p, int64_t planes, int64_t plane, int64_t rows, int64_t pitch, int64_t n, size_t elem) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return DnRange{lo, lo + (uintptr_t)(((planes - 1) * plane + (rows - 1) * pitch + n) * (int64_t)elem)};
-}
-
 // The arguments of a call as the entry point checked them; pointers of the caller's side (`where`).
 struct DnCall {
     const void* field[kDnFields];
@@ -152,20 +145,12 @@ static int daynight_host(mod16_ctx* ctx, int out_type, const DnCall& h, int64_t 
     const int64_t per_day = (int64_t)nf * h.steps * cells * (int64_t)isz + (int64_t)no * cells * (int64_t)osz;
     const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(h.days, stage_bytes / std::max<int64_t>(per_day, 1)));
     const size_t in_bytes = align256((size_t)chunk * h.steps * cells * isz), out_bytes = align256((size_t)chunk * cells * osz);
-    const size_t need = in_bytes * nf + out_bytes * no + 256;
-    if (ctx->slab_bytes < need) {
-        for (int s = 0; s < kSlots; ++s) ctx->slab[s].release();
-        ctx->slab_bytes = need;
-    }
-    if (!ctx->slab[0]) {
-        int rc = ctx->slab[0].alloc(ctx, ctx->slab_bytes, "HOST mode: device memory for a staging slab");
-        if (rc != MOD16_OK) return rc;
-    }
-    HIPCHK(ctx, ctx->streams[0].ensure());
+    int rc = reserve_slabs(ctx, in_bytes * nf + out_bytes * no + 256, 1);
+    if (rc != MOD16_OK) return rc;
     hipStream_t st = ctx->streams[0];
     DnCall dev = h;
     AsyncMem tables(st), annual(st);
-    int rc = dn_upload_tables(ctx, dev, tables, st);
+    rc = dn_upload_tables(ctx, dev, tables, st);
     if (rc != MOD16_OK) return rc;
     const double* const all_half = dev.half_day;
     const double* const all_noon = dev.noon;
@@ -241,8 +226,7 @@ static int daynight_entry(mod16_ctx* ctx, const mod16_daynight_spec* spec, const
     if (spec->steps_per_day < 1 || spec->steps_per_day > kDnMaxSteps) return bad("steps_per_day must be between 1 and 48");
     if (spec->mode != MOD16_DAYNIGHT_SOLAR && spec->mode != MOD16_DAYNIGHT_SW) return bad("mode must be MOD16_DAYNIGHT_SOLAR or MOD16_DAYNIGHT_SW");
     if (spec->out_type != MOD16_DAYNIGHT_F32 && spec->out_type != MOD16_DAYNIGHT_F64) return bad("out_type must be MOD16_DAYNIGHT_F32 or MOD16_DAYNIGHT_F64");
-    if (where != MOD16_DEVICE && where != MOD16_HOST) return bad("`where` must be MOD16_HOST or MOD16_DEVICE");
-    if (stage_bytes > (size_t)std::numeric_limits<int64_t>::max()) return bad("stage_bytes is out of range");
+    if (const char* what = check_where_stage(where, stage_bytes)) return bad(what);
     const int64_t R = spec->rows, W = spec->cols;
     const int D = spec->days, H = spec->steps_per_day;
     const bool solar = spec->mode == MOD16_DAYNIGHT_SOLAR;
@@ -280,24 +264,19 @@ static int daynight_entry(mod16_ctx* ctx, const mod16_daynight_spec* spec, const
     const size_t osz = spec->out_type == MOD16_DAYNIGHT_F32 ? 4 : 8;
     // no output may share a byte with an input or with another output
     {
-        DnRange ins[kDnFields + 3], outs[kDnOutputs + 1];
+        Extent ins[kDnFields + 3], outs[kDnOutputs + 1];
         int ni = 0, no = 0;
         for (int f = 0; f < kDnFields; ++f)
-            if (fields[f]) ins[ni++] = dn_range(fields[f], (int64_t)D * H, spec->in_plane, R, spec->in_pitch, W, sizeof(IN));
+            if (fields[f]) ins[ni++] = extent(fields[f], (int64_t)D * H, spec->in_plane, R, spec->in_pitch, W, sizeof(IN));
         if (solar && where == MOD16_HOST) {
-            ins[ni++] = dn_range(half_day, 1, 0, 1, 0, (int64_t)D * R, 8);
-            ins[ni++] = dn_range(noon, 1, 0, 1, 0, D, 8);
-            ins[ni++] = dn_range(offset, 1, 0, 1, 0, W, 8);
+            ins[ni++] = extent(half_day, (int64_t)D * R, 8);
+            ins[ni++] = extent(noon, D, 8);
+            ins[ni++] = extent(offset, W, 8);
         }
         for (int o = 0; o < kDnOutputs; ++o)
-            if (out[o]) outs[no++] = dn_range(out[o], D, spec->out_plane, R, spec->out_pitch, W, osz);
-        if (temp_annual) outs[no++] = dn_range(temp_annual, 1, 0, R, spec->out_pitch, W, osz);
-        for (int o = 0; o < no; ++o) {
-            for (int i = 0; i < ni; ++i)
-                if (outs[o].lo < ins[i].hi && ins[i].lo < outs[o].hi) return bad("an output overlaps an input or another output");
-            for (int o2 = 0; o2 < o; ++o2)
-                if (outs[o].lo < outs[o2].hi && outs[o2].lo < outs[o].hi) return bad("an output overlaps an input or another output");
-        }
+            if (out[o]) outs[no++] = extent(out[o], D, spec->out_plane, R, spec->out_pitch, W, osz);
+        if (temp_annual) outs[no++] = extent(temp_annual, 1, 0, R, spec->out_pitch, W, osz);
+        if (overlaps(outs, no, ins, ni)) return bad("an output overlaps an input or another output");
     }
     c.annual = temp_annual;
     c.half_day = half_day; c.noon = noon; c.offset = offset;
@@ -306,7 +285,7 @@ static int daynight_entry(mod16_ctx* ctx, const mod16_daynight_spec* spec, const
     c.days = D; c.steps = H; c.mode = solar ? kDnModeSolar : kDnModeSw;
     c.threshold = spec->threshold;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (where == MOD16_HOST) return daynight_host<IN>(ctx, spec->out_type, c, stage_bytes ? (int64_t)stage_bytes : (int64_t)128 << 20);
+    if (where == MOD16_HOST) return daynight_host<IN>(ctx, spec->out_type, c, stage_budget(stage_bytes));
     hipStream_t st = static_cast<hipStream_t>(stream);
     AsyncMem tables(st), means(st);
     int rc = dn_upload_tables(ctx, c, tables, st);

@@ -307,7 +307,7 @@ static int downscaled_entry(mod16_ctx* ctx, const mod16_downscale* grid, const u
     if (flags & MOD16_DOMAIN_TRUSTED)
         return bad("MOD16_DOMAIN_TRUSTED is not available for the downscaled run (every launch is guarded)");
     if (flags & ~(unsigned)MOD16_MATH_EXACT) return bad("unknown flag");
-    if (where != MOD16_DEVICE && where != MOD16_HOST) return bad("`where` must be MOD16_HOST or MOD16_DEVICE");
+    if (const char* what = check_where(where)) return bad(what);
     if (grid->device != ctx->device) return bad("the grid was created on another device than this context's");
     const int64_t total = grid->spec.rows * grid->spec.cols;
     if (n < 0 || first_pixel < 0 || first_pixel > total || n > total - first_pixel)
@@ -384,7 +384,7 @@ static int fields_entry(mod16_ctx* ctx, const mod16_downscale* grid, const T* co
     auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, "mod16_downscale_fields: ", what); };
     if (!grid || !fields || !out) return bad("NULL grid, fields or out");
     if (nfields < 1 || nfields > kDsMaxFields) return bad("F must be between 1 and 16");
-    if (where != MOD16_DEVICE && where != MOD16_HOST) return bad("`where` must be MOD16_HOST or MOD16_DEVICE");
+    if (const char* what = check_where(where)) return bad(what);
     if (grid->device != ctx->device) return bad("the grid was created on another device than this context's");
     const int64_t total = grid->spec.rows * grid->spec.cols;
     if (n < 0 || first_pixel < 0 || first_pixel > total || n > total - first_pixel)

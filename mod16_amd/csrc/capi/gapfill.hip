@@ -9,13 +9,6 @@ bool gap_default_good(int q) {
     return !(q & 1) && !(q & 4) && (cloud == 0 || cloud == 3) && (q >> 5) <= 1;
 }
 size_t gap_out_size(int out_type) { return out_type == MOD16_GAPFILL_U8 ? 1 : out_type == MOD16_GAPFILL_F32 ? 4 : 8; }
-
-// a byte range of one argument: `rows` rows of n elements, `pitch` elements apart
-struct GapRange { uintptr_t lo, hi; };
-GapRange gap_range(const void* p, int64_t rows, int64_t pitch, int64_t n, size_t elem) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return GapRange{lo, lo + (uintptr_t)(((rows - 1) * pitch + n) * (int64_t)elem)};
-}
 }  // namespace
 
 // All pointers are device pointers here (a.good may be NULL: the table travels in a.good_bits).
@@ -65,10 +58,6 @@ static int gapfill_host(mod16_ctx* ctx, const GapArgs& a, int nf, int out_type, 
     p.add(kIn, a.qc, true, a.qc ? S : 1, a.qc_pitch);
     for (int f = 0; f < kGapMaxFields; ++f) p.add(kIn, a.fallback[f], true);
     p.add(kOut, a.source, true, a.source ? nf * S : 1, a.src_pitch);
-    const int64_t fixed = (int64_t)p.nwide * (int64_t)kStagger + 512;
-    const int64_t per_pixel = (int64_t)p.wide_rows * (int64_t)esz + p.byte_rows;
-    int64_t tile = (stage_bytes - fixed) / per_pixel / kBlock * kBlock;
-    tile = std::max<int64_t>(kBlock, std::min<int64_t>(tile, kTilePixels));
     auto launch = [&](const HostTile& t) {
         GapArgs d = a;
         d.n = t.m;
@@ -84,7 +73,7 @@ static int gapfill_host(mod16_ctx* ctx, const GapArgs& a, int nf, int out_type, 
         d.in_pitch = d.qc_pitch = d.src_pitch = (int64_t)t.byte_row_bytes;
         return launch_gapfill(ctx, d, nf, out_type, t.st);
     };
-    return host_tiled(ctx, p, a.n, ctx->host_threads, false, launch, nullptr, tile);
+    return host_tiled(ctx, p, a.n, ctx->host_threads, false, launch, nullptr, stage_tile(p, esz, stage_bytes));
 }
 
 extern "C" int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, const uint8_t* const* fields,
@@ -92,11 +81,7 @@ extern "C" int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, 
                                 void* const* out, uint8_t* source, int where, void* stream, size_t stage_bytes) {
     MOD16_LOCK(ctx);
     if (!ctx) return MOD16_ERR_ARG;
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_gapfill: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
+    auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, "mod16_gapfill: ", what); };
     if (!spec || !fields || !out) return bad("NULL spec, fields or out");
     if (spec->n < 0) return bad("n < 0");
     if (spec->slabs < 1 || spec->slabs > kGapMaxSlabs) return bad("slabs must be between 1 and 4096");
@@ -104,8 +89,7 @@ extern "C" int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, 
     if (spec->out_type != MOD16_GAPFILL_U8 && spec->out_type != MOD16_GAPFILL_F32 && spec->out_type != MOD16_GAPFILL_F64)
         return bad("out_type must be MOD16_GAPFILL_U8, MOD16_GAPFILL_F32 or MOD16_GAPFILL_F64");
     if (spec->max_gap < -1) return bad("max_gap must be -1 (none) or at least 0");
-    if (where != MOD16_DEVICE && where != MOD16_HOST) return bad("`where` must be MOD16_HOST or MOD16_DEVICE");
-    if (stage_bytes > (size_t)std::numeric_limits<int64_t>::max()) return bad("stage_bytes is out of range");
+    if (const char* what = check_where_stage(where, stage_bytes)) return bad(what);
     const int nf = spec->nfields, S = spec->slabs;
     const int64_t n = spec->n;
     const size_t esz = gap_out_size(spec->out_type);
@@ -119,22 +103,17 @@ extern "C" int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, 
     if (n == 0) return MOD16_OK;
     // in place is refused: no output may share a byte with an input or with another output
     {
-        GapRange ins[2 * kGapMaxFields + 2], outs[kGapMaxFields + 1];
+        Extent ins[2 * kGapMaxFields + 2], outs[kGapMaxFields + 1];
         int ni = 0, no = 0;
         for (int f = 0; f < nf; ++f) {
-            ins[ni++] = gap_range(fields[f], S, spec->in_pitch, n, 1);
-            if (fallback && fallback[f]) ins[ni++] = gap_range(fallback[f], 1, 0, n, 1);
-            outs[no++] = gap_range(out[f], S, spec->out_pitch, n, esz);
+            ins[ni++] = extent(fields[f], 1, 0, S, spec->in_pitch, n, 1);
+            if (fallback && fallback[f]) ins[ni++] = extent(fallback[f], n, 1);
+            outs[no++] = extent(out[f], 1, 0, S, spec->out_pitch, n, esz);
         }
-        if (qc) ins[ni++] = gap_range(qc, S, spec->qc_pitch, n, 1);
-        if (good256) ins[ni++] = gap_range(good256, 1, 0, 256, 1);
-        if (source) outs[no++] = gap_range(source, (int64_t)nf * S, spec->source_pitch, n, 1);
-        for (int o = 0; o < no; ++o) {
-            for (int i = 0; i < ni; ++i)
-                if (outs[o].lo < ins[i].hi && ins[i].lo < outs[o].hi) return bad("an output overlaps an input or another output");
-            for (int o2 = 0; o2 < o; ++o2)
-                if (outs[o].lo < outs[o2].hi && outs[o2].lo < outs[o].hi) return bad("an output overlaps an input or another output");
-        }
+        if (qc) ins[ni++] = extent(qc, 1, 0, S, spec->qc_pitch, n, 1);
+        if (good256) ins[ni++] = extent(good256, 256, 1);
+        if (source) outs[no++] = extent(source, 1, 0, (int64_t)nf * S, spec->source_pitch, n, 1);
+        if (overlaps(outs, no, ins, ni)) return bad("an output overlaps an input or another output");
     }
     GapArgs a;
     memset(&a, 0, sizeof a);
@@ -161,5 +140,5 @@ extern "C" int mod16_gapfill_u8(mod16_ctx* ctx, const mod16_gapfill_spec* spec, 
     a.good = where == MOD16_DEVICE ? good256 : nullptr;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (where == MOD16_DEVICE) return launch_gapfill(ctx, a, nf, spec->out_type, static_cast<hipStream_t>(stream));
-    return gapfill_host(ctx, a, nf, spec->out_type, stage_bytes ? (int64_t)stage_bytes : (int64_t)128 << 20);
+    return gapfill_host(ctx, a, nf, spec->out_type, stage_budget(stage_bytes));
 }

@@ -61,6 +61,49 @@ struct HostPlan {
     }
 };
 
+// The tile of a HOST-mode call whose arrays have many rows: a slot's slab -- `wide_rows` rows of esz
+// bytes and `byte_rows` byte rows per pixel, the stagger once per T-sized array -- fits stage_bytes
+// (whole blocks of pixels, at least one, at most kTilePixels).
+static int64_t stage_tile(const HostPlan& p, size_t esz, int64_t stage_bytes) {
+    const int64_t fixed = (int64_t)p.nwide * (int64_t)kStagger + 512;
+    const int64_t per_pixel = (int64_t)p.wide_rows * (int64_t)esz + p.byte_rows;
+    const int64_t tile = (stage_bytes - fixed) / per_pixel / kBlock * kBlock;
+    return std::max<int64_t>(kBlock, std::min<int64_t>(tile, kTilePixels));
+}
+
+// ---- the argument checks the array families share (gapfill.hip, zonal.hip, daynight.hip) ----
+// -> NULL, or what is wrong with `where`
+static const char* check_where(int where) {
+    return where != MOD16_DEVICE && where != MOD16_HOST ? "`where` must be MOD16_HOST or MOD16_DEVICE" : nullptr;
+}
+// ... or with stage_bytes, the device memory a HOST-mode call may stage through (0: stage_budget's default)
+static const char* check_where_stage(int where, size_t stage_bytes) {
+    if (const char* what = check_where(where)) return what;
+    return stage_bytes > (size_t)std::numeric_limits<int64_t>::max() ? "stage_bytes is out of range" : nullptr;
+}
+static int64_t stage_budget(size_t stage_bytes) { return stage_bytes ? (int64_t)stage_bytes : (int64_t)128 << 20; }
+
+// The bytes an argument spans: `planes` planes of `rows` rows of n elements of `elem` bytes, rows
+// `pitch` and planes `plane` elements apart.
+struct Extent { uintptr_t lo, hi; };
+static Extent extent(const void* p, int64_t planes, int64_t plane, int64_t rows, int64_t pitch, int64_t n, size_t elem) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+    return Extent{lo, lo + (uintptr_t)(((planes - 1) * plane + (rows - 1) * pitch + n) * (int64_t)elem)};
+}
+// ... one dense row of n elements
+static Extent extent(const void* p, int64_t n, size_t elem) { return extent(p, 1, 0, 1, 0, n, elem); }
+// In place is refused: does an output share a byte with an input or with an earlier output?
+static bool overlaps(const Extent* outs, int no, const Extent* ins, int ni) {
+    auto meet = [](const Extent& a, const Extent& b) { return a.lo < b.hi && b.lo < a.hi; };
+    for (int o = 0; o < no; ++o) {
+        for (int i = 0; i < ni; ++i)
+            if (meet(outs[o], ins[i])) return true;
+        for (int o2 = 0; o2 < o; ++o2)
+            if (meet(outs[o], outs[o2])) return true;
+    }
+    return false;
+}
+
 // What a family's callback gets: the device address of every array of the plan for this tile (plan
 // order), its pixels, the stream; it enqueues the tile's kernels and returns a status.
 struct HostTile {
@@ -149,6 +192,23 @@ static int host_small(mod16_ctx* ctx, const HostPlan& p, int64_t n, bool pad, La
     return MOD16_OK;
 }
 
+// The context's staging slabs hold at least `need` bytes each (they grow together: all are released,
+// the slots in use get new ones) and slots [0, nslots) have their slab and their stream.
+static int reserve_slabs(mod16_ctx* ctx, size_t need, int nslots) {
+    if (ctx->slab_bytes < need) {
+        for (int s = 0; s < kSlots; ++s) ctx->slab[s].release();
+        ctx->slab_bytes = need;
+    }
+    for (int s = 0; s < nslots; ++s) {
+        if (!ctx->slab[s]) {
+            int rc = ctx->slab[s].alloc(ctx, ctx->slab_bytes, "HOST mode: device memory for a staging slab");
+            if (rc != MOD16_OK) return rc;
+        }
+        HIPCHK(ctx, ctx->streams[s].ensure());
+    }
+    return MOD16_OK;
+}
+
 // HOST mode: tiles of kTilePixels staged through the context's slabs, one host thread and one stream
 // per slot, tile t on slot t % nslots (nslots <= max_slots). The copies from and to pageable memory
 // are what bounds this mode (the HIP runtime stages them through its own pinned buffers on the
@@ -170,18 +230,8 @@ static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slot
     const size_t row = ((size_t)tile * p.elem + 255) / 256 * 256;
     const size_t per_arr = row + kStagger;
     const size_t per_b = ((size_t)tile + 255) / 256 * 256;
-    const size_t need = p.offset(p.count, per_arr, per_b, row) + 256;
-    if (ctx->slab_bytes < need) {
-        for (int s = 0; s < kSlots; ++s) ctx->slab[s].release();
-        ctx->slab_bytes = need;
-    }
-    for (int s = 0; s < nslots; ++s) {
-        if (!ctx->slab[s]) {
-            int rc = ctx->slab[s].alloc(ctx, ctx->slab_bytes, "HOST mode: device memory for a staging slab");
-            if (rc != MOD16_OK) return rc;
-        }
-        HIPCHK(ctx, ctx->streams[s].ensure());
-    }
+    int rc = reserve_slabs(ctx, p.offset(p.count, per_arr, per_b, row) + 256, nslots);
+    if (rc != MOD16_OK) return rc;
     // broadcast scalars live in one small device array
     char hs[256] = {};
     p.put_scalars(hs);
@@ -189,7 +239,7 @@ static int host_tiled(mod16_ctx* ctx, const HostPlan& p, int64_t n, int max_slot
     char* dscal = ctx->scalars.as<char>();
     if (pipeline) {   // the kernels' shared workspace at its final size before any thread launches
         const int64_t npiece = (tile / (16 / p.elem) + 63) / 64;
-        int rc = reserve_diag(ctx, npiece / 2 + 2048);
+        rc = reserve_diag(ctx, npiece / 2 + 2048);
         if (rc != MOD16_OK) return rc;
     }
     auto stage = [&](int slot, int64_t off) -> int {

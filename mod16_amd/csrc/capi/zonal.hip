@@ -5,11 +5,6 @@
 namespace {
 size_t zonal_zone_size(int zone_type) { return zone_type == MOD16_ZONE_U8 ? 1 : zone_type == MOD16_ZONE_U16 ? 2 : 4; }
 
-struct ZonalRange { uintptr_t lo, hi; };
-ZonalRange zonal_range(const void* p, int64_t rows, int64_t pitch, int64_t n, size_t elem) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return ZonalRange{lo, lo + (uintptr_t)(((rows - 1) * pitch + n) * (int64_t)elem)};
-}
 bool zonal_aligned(const void* p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
 
 // first and last raster row of the pixels [first_pixel, first_pixel + n)
@@ -63,15 +58,6 @@ static int launch_zonal_bounds(mod16_ctx* ctx, const ZonalArgs& a, int wk, int l
     return MOD16_OK;
 }
 
-// the tile of a HOST-mode call: a slot's slab -- `wide_rows` T-sized rows and `byte_rows` byte rows per
-// pixel, the stagger between its arrays -- fits stage_bytes
-static int64_t zonal_tile(const HostPlan& p, size_t esz, int64_t stage_bytes) {
-    const int64_t fixed = (int64_t)p.nwide * (int64_t)kStagger + 512;
-    const int64_t per_pixel = (int64_t)p.wide_rows * (int64_t)esz + p.byte_rows;
-    const int64_t tile = (stage_bytes - fixed) / per_pixel / kBlock * kBlock;
-    return std::max<int64_t>(kBlock, std::min<int64_t>(tile, kTilePixels));
-}
-
 // HOST mode: values (one row per layer), zone ids and per-pixel weights staged tile by tile through
 // the shared staging path; the accumulator uploaded once, added into by the tiles of every slot's
 // stream (integer atomics: the order does not show) and downloaded once; the per-row weights the
@@ -99,7 +85,6 @@ static int zonal_host(mod16_ctx* ctx, const mod16_zonal_spec& s, ZonalArgs a, in
     p.add(kIn, pixel_w ? a.weights : nullptr, false);                            // 1
     if (zsz == 1) p.add(kIn, a.zones, true);                                     // 2: a byte row
     else p.add(kIn, a.zones, false, 1, 0, (int)zsz);                             // 2: in a T-sized place
-    const int64_t tile = zonal_tile(p, sizeof(T), stage_bytes);
     auto launch = [&](const HostTile& t) {
         ZonalArgs d = a;
         d.n = t.m;
@@ -111,7 +96,7 @@ static int zonal_host(mod16_ctx* ctx, const mod16_zonal_spec& s, ZonalArgs a, in
         d.acc = dacc.as<long long>();
         return launch_zonal<T>(ctx, d, s, t.st);
     };
-    rc = host_tiled(ctx, p, s.n, ctx->host_threads, false, launch, nullptr, tile);
+    rc = host_tiled(ctx, p, s.n, ctx->host_threads, false, launch, nullptr, stage_tile(p, sizeof(T), stage_bytes));
     if (rc != MOD16_OK) return rc;
     HIPCHK(ctx, hipMemcpy(acc, dacc.get(), acc_bytes, hipMemcpyDeviceToHost));
     return MOD16_OK;
@@ -145,32 +130,26 @@ static int zonal_entry(mod16_ctx* ctx, const mod16_zonal_spec* spec, const T* va
                        const void* weights, int64_t* acc, int where, void* stream, size_t stage_bytes) {
     MOD16_LOCK(ctx);
     if (!ctx) return MOD16_ERR_ARG;
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_zonal: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
+    auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, "mod16_zonal: ", what); };
     if (!spec || !values || !zones || !acc) return bad("NULL spec, values, zones or acc");
     if (const char* what = zonal_check_spec(spec, false)) return bad(what);
     if (spec->weight_kind != MOD16_ZONAL_WEIGHT_NONE && !weights) return bad("NULL weights");
-    if (where != MOD16_DEVICE && where != MOD16_HOST) return bad("`where` must be MOD16_HOST or MOD16_DEVICE");
-    if (stage_bytes > (size_t)std::numeric_limits<int64_t>::max()) return bad("stage_bytes is out of range");
+    if (const char* what = check_where_stage(where, stage_bytes)) return bad(what);
     const int64_t n = spec->n;
     if (n == 0) return MOD16_OK;
     {
-        const ZonalRange out = zonal_range(acc, 1, 0, (int64_t)kZonalWords * spec->layers * spec->nzones, sizeof(int64_t));
-        ZonalRange ins[3];
+        const Extent out = extent(acc, (int64_t)kZonalWords * spec->layers * spec->nzones, sizeof(int64_t));
+        Extent ins[3];
         int ni = 0;
-        ins[ni++] = zonal_range(values, spec->layers, spec->value_pitch, n, sizeof(T));
-        ins[ni++] = zonal_range(zones, 1, 0, n, zonal_zone_size(spec->zone_type));
-        if (spec->weight_kind == MOD16_ZONAL_WEIGHT_PIXEL) ins[ni++] = zonal_range(weights, 1, 0, n, sizeof(T));
+        ins[ni++] = extent(values, 1, 0, spec->layers, spec->value_pitch, n, sizeof(T));
+        ins[ni++] = extent(zones, n, zonal_zone_size(spec->zone_type));
+        if (spec->weight_kind == MOD16_ZONAL_WEIGHT_PIXEL) ins[ni++] = extent(weights, n, sizeof(T));
         if (spec->weight_kind == MOD16_ZONAL_WEIGHT_ROW) {
             int64_t r0, r1;
             zonal_rows(*spec, spec->first_pixel, n, &r0, &r1);
-            ins[ni++] = zonal_range(static_cast<const double*>(weights) + r0, 1, 0, r1 - r0 + 1, sizeof(double));
+            ins[ni++] = extent(static_cast<const double*>(weights) + r0, r1 - r0 + 1, sizeof(double));
         }
-        for (int i = 0; i < ni; ++i)
-            if (out.lo < ins[i].hi && ins[i].lo < out.hi) return bad("acc overlaps an input");
+        if (overlaps(&out, 1, ins, ni)) return bad("acc overlaps an input");
     }
     ZonalArgs a;
     memset(&a, 0, sizeof a);
@@ -191,7 +170,7 @@ static int zonal_entry(mod16_ctx* ctx, const mod16_zonal_spec* spec, const T* va
     a.f[2] = a.f[1] - spec->ex;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (where == MOD16_DEVICE) return launch_zonal<T>(ctx, a, *spec, static_cast<hipStream_t>(stream));
-    return zonal_host<T>(ctx, *spec, a, acc, stage_bytes ? (int64_t)stage_bytes : (int64_t)128 << 20);
+    return zonal_host<T>(ctx, *spec, a, acc, stage_budget(stage_bytes));
 }
 
 template <typename T>
@@ -199,17 +178,12 @@ static int zonal_bounds_entry(mod16_ctx* ctx, const mod16_zonal_spec* spec, cons
                               double* wmax, double* xmax, int where, void* stream, size_t stage_bytes) {
     MOD16_LOCK(ctx);
     if (!ctx) return MOD16_ERR_ARG;
-    auto bad = [&](const char* what) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "mod16_zonal_bounds: %s", what);
-        return fail(ctx, MOD16_ERR_ARG, msg);
-    };
+    auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, "mod16_zonal_bounds: ", what); };
     if (!spec || !values || !wmax || !xmax) return bad("NULL spec, values, wmax or xmax");
     if (const char* what = zonal_check_spec(spec, true)) return bad(what);
     const int wk = spec->weight_kind;
     if (wk != MOD16_ZONAL_WEIGHT_NONE && !weights) return bad("NULL weights");
-    if (where != MOD16_DEVICE && where != MOD16_HOST) return bad("`where` must be MOD16_HOST or MOD16_DEVICE");
-    if (stage_bytes > (size_t)std::numeric_limits<int64_t>::max()) return bad("stage_bytes is out of range");
+    if (const char* what = check_where_stage(where, stage_bytes)) return bad(what);
     *wmax = wk == MOD16_ZONAL_WEIGHT_NONE ? 1.0 : 0.0;
     *xmax = 0.0;
     if (spec->n == 0) return MOD16_OK;
@@ -250,7 +224,6 @@ static int zonal_bounds_entry(mod16_ctx* ctx, const mod16_zonal_spec* spec, cons
         HostPlan p((int)sizeof(T));
         p.add(kIn, values, false, spec->layers, spec->value_pitch);
         p.add(kIn, wk == MOD16_ZONAL_WEIGHT_PIXEL ? weights : nullptr, false);
-        const int64_t stage = stage_bytes ? (int64_t)stage_bytes : (int64_t)128 << 20;
         const int tile_wk = wk == MOD16_ZONAL_WEIGHT_PIXEL ? wk : MOD16_ZONAL_WEIGHT_NONE;
         auto launch = [&](const HostTile& t) {
             ZonalArgs d = a;
@@ -260,7 +233,7 @@ static int zonal_bounds_entry(mod16_ctx* ctx, const mod16_zonal_spec* spec, cons
             d.weights = t.dev[1];
             return launch_zonal_bounds<T>(ctx, d, tile_wk, spec->layers, t.st);
         };
-        rc = host_tiled(ctx, p, spec->n, ctx->host_threads, false, launch, nullptr, zonal_tile(p, sizeof(T), stage));
+        rc = host_tiled(ctx, p, spec->n, ctx->host_threads, false, launch, nullptr, stage_tile(p, sizeof(T), stage_budget(stage_bytes)));
         if (rc != MOD16_OK) return rc;
         HIPCHK(ctx, hipMemcpy(bits, top.get(), sizeof bits, hipMemcpyDeviceToHost));
     }

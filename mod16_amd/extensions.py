@@ -581,9 +581,7 @@ def aggregate_daynight(fields, half_day=None, noon=None, offset=None, sw_thresho
                 outs['temp_annual'].ctypes.data if 'temp_annual' in outs else None, W, R * W, W, R * W,
                 mode=_dn.MODES[mode], threshold=threshold, where=_lib.HOST, stage_bytes=stage_bytes)
         except _lib.Mod16Error as e:
-            if e.status == _lib.ERR_ARG and 'overlaps' in str(e):
-                raise ValueError(str(e))
-            raise
+            raise _lib.overlap_as_value_error(e)
     return _dn.DayNight(*[outs.get(n) for n in _dn.OUTPUT_NAMES]), outs.get('temp_annual')
 
 

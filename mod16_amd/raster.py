@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _tensors as _t
 from .downscale import MET_DRIVERS
 
 #: algorithmic HBM bytes per pixel: 14 driver loads +
@@ -244,20 +244,16 @@ class DownscaleGrid(object):
         self.row_tables, self.col_tables = self._grid.row_tables, self._grid.col_tables
         self.col_affine = self._grid.col_affine      # (col_origin, col_scale) of row-affine columns, else None
 
-    def _coarse_tensor(self, t, what):
-        '''-> (address, row pitch in elements) of an (H, W) tensor with unit stride in columns'''
-        eng, torch = self.engine, _torch()
+    def _coarse(self, t, what, series=False):
+        '''-> (address, row pitch, plane stride in elements) of an (H, W) tensor or, with ``series``, an
+        (S, H, W) one'''
+        eng = self.engine
         H, W = self.coarse_shape
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != eng.device or t.dtype != eng.dtype:
-            raise TypeError('%s must be a %s tensor on cuda:%d' % (what, eng.dtype, eng.device))
-        if tuple(t.shape) != (H, W):
-            raise ValueError('%s is a coarse array: expected shape %r, got %r' % (what, (H, W), tuple(t.shape)))
-        if W > 1 and t.stride(1) != 1:
-            raise ValueError('%s must have unit stride in columns' % what)
-        pitch = t.stride(0) if H > 1 else W
-        if pitch < W:
-            raise ValueError('%s: the distance between rows must be at least %d' % (what, W))
-        return t.data_ptr(), pitch
+        _t.check_device(t, what, eng.device, eng.dtype)
+        if tuple(t.shape[-2:]) != (H, W) or t.dim() != 2 and not (series and t.dim() == 3):
+            raise ValueError('%s is a coarse array: expected shape %r%s, got %r'
+                             % (what, (H, W), ' or (S, %d, %d)' % (H, W) if series else '', tuple(t.shape)))
+        return (t.data_ptr(),) + _t.plane_layout(t, what)
 
     def run(self, cls, drivers, coarse=MET_DRIVERS, first_pixel=0, out_day=None, out_night=None):
         '''Enqueue the downscaled forward run on the current stream: ET day and night for the
@@ -283,13 +279,11 @@ class DownscaleGrid(object):
         kinds, first, n = _d.check_call(self.shape, self.coarse_shape, shapes, coarse=names, first_pixel=first_pixel,
                                         n=n, method=self._grid.method, cls_size=n)
         cptr = eng._check_tensor(cls, torch.uint8, n, 'cls')
-        keep, ptrs, pitch = [], [], None
+        keep, ptrs, rows = [], [], []
         for name, d, kind in zip(_d.DRIVER_NAMES, drivers, kinds):
             if kind == _d.KIND_COARSE:
-                ptr, row = self._coarse_tensor(d, name)
-                if pitch is not None and row != pitch:
-                    raise ValueError('the coarse drivers must share one distance between rows')
-                pitch = row
+                ptr, row, _ = self._coarse(d, name)
+                rows.append(row)
                 keep.append(d)
             elif kind == _d.KIND_FINE:
                 ptr = eng._check_tensor(d, eng.dtype, n, name)
@@ -299,6 +293,7 @@ class DownscaleGrid(object):
                 keep.append(sc)
                 ptr = sc.data_ptr()
             ptrs.append(ptr)
+        pitch = _t.share_one(rows, 'the coarse drivers', 'distance between rows')
         if out_day is None:
             out_day = eng.empty(n)[0]
         if out_night is None:
@@ -322,47 +317,20 @@ class DownscaleGrid(object):
         if not fields:
             raise ValueError('fields needs at least one coarse field')
         first, n = _d.check_range(self.shape, first_pixel, n)
-        ptrs, pitch = [], None
-        for k, t in enumerate(fields):
-            ptr, row = self._coarse_tensor(t, 'field %d' % k)
-            if pitch is not None and row != pitch:
-                raise ValueError('the coarse fields must share one distance between rows')
-            pitch = row
-            ptrs.append(ptr)
+        ptrs, rows, _ = zip(*[self._coarse(t, 'field %d' % k) for k, t in enumerate(fields)])
+        pitch = _t.share_one(rows, 'the coarse fields', 'distance between rows')
         F = len(fields)
         if out is None:
             out = torch.empty((F, n), dtype=eng.dtype, device=eng._dev())
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != eng.device or out.dtype != eng.dtype:
-            raise TypeError('out must be a %s tensor on cuda:%d' % (eng.dtype, eng.device))
-        if tuple(out.shape) != (F, n) or (n > 1 and out.stride(1) != 1):
-            raise ValueError('out must have shape (%d, %d) and unit stride in pixels' % (F, n))
-        opitch = out.stride(0) if F > 1 else max(n, 1)
-        if opitch < n:
-            raise ValueError('the distance between the rows of out must be at least n')
+        _t.check_device(out, 'out', eng.device, eng.dtype)
+        if tuple(out.shape) != (F, n):
+            raise ValueError('out must have shape (%d, %d)' % (F, n))
+        opitch = _t.row_pitch(out, 'out')
         esz = eng.np_dtype.itemsize
         for f0 in range(0, F if n else 0, 16):       # the library takes 16 fields a call
             self._grid.fields(eng.np_dtype, ptrs[f0:f0 + 16], pitch, first, n, out.data_ptr() + f0 * opitch * esz,
                               opitch, where=_lib.DEVICE, stream=eng._stream())
         return out
-
-    def _coarse_series(self, t, what):
-        '''-> (address, row pitch, time stride in elements, slabs) of an (H, W) or (S, H, W) tensor with
-        unit stride in columns'''
-        eng, torch = self.engine, _torch()
-        H, W = self.coarse_shape
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != eng.device or t.dtype != eng.dtype:
-            raise TypeError('%s must be a %s tensor on cuda:%d' % (what, eng.dtype, eng.device))
-        if t.dim() == 2:
-            ptr, pitch = self._coarse_tensor(t, what)
-            return ptr, pitch, 0, 1
-        if t.dim() != 3 or tuple(t.shape[1:]) != (H, W):
-            raise ValueError('%s is a coarse array: expected shape %r or (S, %d, %d), got %r'
-                             % (what, (H, W), H, W, tuple(t.shape)))
-        ptr, pitch = self._coarse_tensor(t[0], what)
-        slabs = t.shape[0]
-        if slabs > 1 and t.stride(0) < (H - 1) * pitch + W:
-            raise ValueError('%s: the stride in time must be at least a plane (%d elements)' % (what, (H - 1) * pitch + W))
-        return ptr, pitch, t.stride(0) if slabs > 1 else 0, slabs
 
     def composite(self, cls, drivers, day_hours, days, period_days=8, every=None, coarse=MET_DRIVERS, first_pixel=0,
                   pet=False, min_valid=1, rescale=False, out=None):
@@ -397,38 +365,22 @@ class DownscaleGrid(object):
         kinds, slabs, first, n = _d.check_composite_call(self.shape, self.coarse_shape, shapes, K, ev, coarse=names,
                                                          first_pixel=first_pixel, n=n, cls_size=n)
         cptr = eng._check_tensor(cls, torch.uint8, n, 'cls')
-        keep, ptrs, pstride, tstride, divisor, cpitch = [], [], [], [], [], None
+        keep, ptrs, pstride, tstride, divisor, rows = [], [], [], [], [], []
         for name, d, kind, S in zip(_c.ARRAY_NAMES, arrays, kinds, slabs):
-            timed = kind in (_d.KIND_FINE_TIME, _d.KIND_COARSE_TIME)
             if kind in (_d.KIND_COARSE, _d.KIND_COARSE_TIME):
-                ptr, row, ts, _ = self._coarse_series(d, name)
-                if cpitch is not None and row != cpitch:
-                    raise ValueError('the coarse arrays must share one distance between rows')
-                cpitch = row
-                pstride.append(0)
-            elif kind == _d.KIND_SCALAR:
-                d = torch.as_tensor(d, dtype=eng.dtype).reshape(1).to(eng._dev())
-                ptr, ts = d.data_ptr(), 0
-                pstride.append(0)
-            elif kind == _d.KIND_FINE:
-                ptr, ts = eng._check_tensor(d, eng.dtype, n, name), 0
-                pstride.append(1)
+                ptr, row, plane = self._coarse(d, name, series=True)
+                rows.append(row)
+                ps, ts, div = 0, (plane if S > 1 else 0), (ev[name] if kind == _d.KIND_COARSE_TIME else K)
+            elif kind == _d.KIND_FINE:          # (contiguous: it may have the raster's shape)
+                ptr, ps, ts, div = eng._check_tensor(d, eng.dtype, n, name), 1, 0, K
             else:
-                if not d.is_cuda or d.device.index != eng.device or d.dtype != eng.dtype:
-                    raise TypeError('%s must be a %s tensor on cuda:%d' % (name, eng.dtype, eng.device))
-                if d.dim() > 2:
-                    raise ValueError('%s must be a scalar, an (n,) or an (S, n) tensor with n = %d, got %r'
-                                     % (name, n, tuple(d.shape)))
-                if n > 1 and d.stride(-1) != 1:
-                    raise ValueError('%s must have unit stride in pixels' % name)
-                if S > 1 and d.stride(0) < n:
-                    raise ValueError('%s: the stride in time must be at least n' % name)
-                ptr, ts = d.data_ptr(), (d.stride(0) if S > 1 else 0)
-                pstride.append(1)
+                d, ptr, ps, ts, div = eng._composite_array(name, d, n, K, ev)
             keep.append(d)
             ptrs.append(ptr)
+            pstride.append(ps)
             tstride.append(ts)
-            divisor.append(ev[name] if timed else K)
+            divisor.append(div)
+        cpitch = _t.share_one(rows, 'the coarse arrays', 'distance between rows')
         out, pitch = eng._composite_outputs(out, P, n, pet)
         if n:
             optr = [o.data_ptr() for o in out]
@@ -512,10 +464,8 @@ class RasterEngine(object):
         return C.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
 
     def _check_tensor(self, t, dtype, n, what):
-        torch = _torch()
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device:
-            raise TypeError('%s must be a tensor on cuda:%d' % (what, self.device))
-        if t.dtype != dtype or not t.is_contiguous():
+        _t.check_device(t, what, self.device, dtype)
+        if not t.is_contiguous():
             raise TypeError('%s must be contiguous %s' % (what, dtype))
         if t.numel() != n:
             raise ValueError('%s has %d elements, expected %d' % (what, t.numel(), n))
@@ -688,33 +638,8 @@ class RasterEngine(object):
             raise ValueError('expected 14 drivers')
         n = cls.numel()
         cptr = self._check_tensor(cls, torch.uint8, n, 'cls')
-        keep, ptrs, pstride, tstride, divisor = [], [], [], [], []
-        for name, d in zip(_c.ARRAY_NAMES, list(drivers) + [day_hours]):
-            if isinstance(d, torch.Tensor) and d.dim() > 0:
-                if not d.is_cuda or d.device.index != self.device or d.dtype != self.dtype:
-                    raise TypeError('%s must be a %s tensor on cuda:%d' % (name, self.dtype, self.device))
-                if d.dim() > 2 or d.shape[-1] != n:
-                    raise ValueError('%s must be a scalar, an (n,) or an (S, n) tensor with n = %d, got %r'
-                                     % (name, n, tuple(d.shape)))
-                if n > 1 and d.stride(-1) != 1:
-                    raise ValueError('%s must have unit stride in pixels' % name)
-                slabs = d.shape[0] if d.dim() == 2 else 1
-                if d.dim() == 2:
-                    _c.check_slabs(name, slabs, K, ev[name])
-                    if slabs > 1 and d.stride(0) < n:
-                        raise ValueError('%s: the stride in time must be at least n' % name)
-                keep.append(d)
-                ptrs.append(d.data_ptr())
-                pstride.append(1)
-                tstride.append(d.stride(0) if slabs > 1 else 0)
-                divisor.append(ev[name] if d.dim() == 2 else K)
-            else:       # broadcast scalar, constant in time
-                sc = torch.as_tensor(d, dtype=self.dtype).reshape(1).to(self._dev())
-                keep.append(sc)
-                ptrs.append(sc.data_ptr())
-                pstride.append(0)
-                tstride.append(0)
-                divisor.append(K)
+        keep, ptrs, pstride, tstride, divisor = zip(*[
+            self._composite_array(name, d, n, K, ev) for name, d in zip(_c.ARRAY_NAMES, list(drivers) + [day_hours])])
         out, pitch = self._composite_outputs(out, P, n, pet)
         if n:
             optr = [o.data_ptr() for o in out]
@@ -724,6 +649,19 @@ class RasterEngine(object):
                                pitch, min_valid=mv, rescale=rescale, flags=self.math, where=_lib.DEVICE,
                                stream=self._stream())
         return out
+
+    def _composite_array(self, name, d, n, K, every):
+        '''One array of a composite call given per pixel -- a scalar, an ``(n,)`` or an ``(S, n)`` tensor
+        -- -> (the tensor to keep alive, address, pixel stride, stride in time, divisor of the day).'''
+        from . import composite as _c
+        torch = _torch()
+        if not isinstance(d, torch.Tensor) or d.dim() == 0:       # broadcast scalar, constant in time
+            sc = torch.as_tensor(d, dtype=self.dtype).reshape(1).to(self._dev())
+            return sc, sc.data_ptr(), 0, 0, K
+        ptr, ts = _t.series(d, name, n, self.device, self.dtype)
+        if d.dim() == 2:
+            _c.check_slabs(name, d.shape[0], K, every[name])
+        return d, ptr, 1, ts, every[name] if d.dim() == 2 else K
 
     def _composite_outputs(self, out, P, n, pet):
         '''The 2 (``pet``: 4) ``(P, n)`` result tensors of a composite call -- new ones, or the caller's
@@ -736,18 +674,12 @@ class RasterEngine(object):
         out = tuple(out)
         if len(out) != want:
             raise ValueError('out must hold %d tensors' % want)
-        pitch = None
         for k, o in enumerate(out):
-            dt = self.dtype if k < want // 2 else torch.uint16
-            if not isinstance(o, torch.Tensor) or not o.is_cuda or o.device.index != self.device or o.dtype != dt:
-                raise TypeError('out[%d] must be a %s tensor on cuda:%d' % (k, dt, self.device))
-            if tuple(o.shape) != (P, n) or (n > 1 and o.stride(1) != 1):
-                raise ValueError('out[%d] must have shape (%d, %d) and unit stride in pixels' % (k, P, n))
-            row = o.stride(0) if P > 1 else max(n, 1)
-            if row < n or (pitch is not None and row != pitch):
-                raise ValueError('the out tensors must share one distance between rows, at least n')
-            pitch = row
-        return out, pitch
+            _t.check_device(o, 'out[%d]' % k, self.device, self.dtype if k < want // 2 else torch.uint16)
+            if tuple(o.shape) != (P, n):
+                raise ValueError('out[%d] must have shape (%d, %d)' % (k, P, n))
+        rows = [_t.row_pitch(o, 'out[%d]' % k) for k, o in enumerate(out)]
+        return out, _t.share_one(rows, 'the out tensors', 'distance between rows')
 
     def downscale_grid(self, shape, coarse_shape, row_pos, col_pos=None, wrap=False, method='bilinear',
                        col_affine=None):
@@ -804,10 +736,8 @@ class RasterEngine(object):
                 scale = (0.01, 0.1)
         for what, t in [('fields[%d]' % k, f) for k, f in enumerate(flds)] + [('qc', qc)] + \
                 [('fallback[%d]' % k, f) for k, f in enumerate(fallback or [])]:
-            if t is None and not what.startswith('fields'):
-                continue
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or t.dtype != torch.uint8:
-                raise TypeError('%s must be a uint8 tensor on cuda:%d' % (what, self.device))
+            if t is not None or what.startswith('fields'):
+                _t.check_device(t, what, self.device, torch.uint8)
         S, shape, table, mg, name, scales = _g.check_series(
             [tuple(f.shape) for f in flds], None if qc is None else tuple(qc.shape), good, max_gap,
             None if fallback is None else [None if f is None else tuple(f.shape) for f in fallback], dtype, scale)
@@ -815,22 +745,12 @@ class RasterEngine(object):
             raise ValueError('fields must be (S, n) tensors, got %r' % (tuple(flds[0].shape),))
         n = shape[0]
         tdtype = {'uint8': torch.uint8, 'float32': torch.float32, 'float64': torch.float64}[name]
-
-        def pitch_of(t, what, rows):
-            if n > 1 and t.stride(-1) != 1:
-                raise ValueError('%s must have unit stride in pixels' % what)
-            row = t.stride(-2) if rows > 1 else max(n, 1)
-            if row < n:
-                raise ValueError('%s: the stride in time must be at least n' % what)
-            return row
-        pitches = set(pitch_of(f, 'fields[%d]' % k, S) for k, f in enumerate(flds))
-        if len(pitches) != 1:
-            raise ValueError('the fields must share one stride in time')
-        in_pitch = pitches.pop()
-        qc_pitch = pitch_of(qc, 'qc', S) if qc is not None else n
+        in_pitch = _t.share_one([_t.row_pitch(f, 'fields[%d]' % k, 'stride in time') for k, f in enumerate(flds)],
+                                'the fields', 'stride in time')
+        qc_pitch = _t.row_pitch(qc, 'qc', 'stride in time') if qc is not None else n
         for k, f in enumerate(fallback or []):
-            if f is not None and n > 1 and f.stride(0) != 1:
-                raise ValueError('fallback[%d] must have unit stride' % k)
+            if f is not None:
+                _t.row_pitch(f, 'fallback[%d]' % k)
         want = len(flds) + (1 if source else 0)
         if out is None:
             outs = [torch.empty((S, n), dtype=tdtype, device=self._dev()) for _ in flds]
@@ -841,21 +761,17 @@ class RasterEngine(object):
                 raise ValueError('out must hold %d tensors' % want)
             src = outs.pop() if source else None
         for k, o in enumerate(outs):
-            if not isinstance(o, torch.Tensor) or not o.is_cuda or o.device.index != self.device or o.dtype != tdtype:
-                raise TypeError('out[%d] must be a %s tensor on cuda:%d' % (k, tdtype, self.device))
+            _t.check_device(o, 'out[%d]' % k, self.device, tdtype)
             if tuple(o.shape) != (S, n):
                 raise ValueError('out[%d] must have shape (%d, %d)' % (k, S, n))
-        opitches = set(pitch_of(o, 'out[%d]' % k, S) for k, o in enumerate(outs))
-        if len(opitches) != 1:
-            raise ValueError('the out tensors must share one distance between rows')
-        out_pitch = opitches.pop()
+        out_pitch = _t.share_one([_t.row_pitch(o, 'out[%d]' % k, 'stride in time') for k, o in enumerate(outs)],
+                                 'the out tensors', 'distance between rows')
         src_pitch = n
         if src is not None:
-            if not isinstance(src, torch.Tensor) or not src.is_cuda or src.device.index != self.device or \
-                    src.dtype != torch.uint8 or tuple(src.shape) != (len(flds), S, n):
-                raise TypeError('the source tensor must be uint8 of shape (%d, %d, %d) on cuda:%d'
-                                % (len(flds), S, n, self.device))
-            src_pitch = pitch_of(src, 'source', S)
+            _t.check_device(src, 'source', self.device, torch.uint8)
+            if tuple(src.shape) != (len(flds), S, n):
+                raise TypeError('source must have shape (%d, %d, %d)' % (len(flds), S, n))
+            src_pitch = _t.row_pitch(src, 'source', 'stride in time')
             if len(flds) > 1 and src.stride(0) != S * src_pitch:
                 raise ValueError('the source tensor must hold its fields back to back')
         if n:
@@ -871,9 +787,7 @@ class RasterEngine(object):
                     out_pitch, src_pitch, max_gap=mg, scale=scales + [1.0] * (3 - len(scales)),
                     where=_lib.DEVICE, stream=self._stream())
             except _lib.Mod16Error as e:
-                if e.status == _lib.ERR_ARG and 'overlaps' in str(e):
-                    raise ValueError(str(e))
-                raise
+                raise _lib.overlap_as_value_error(e)
         filled = outs[0] if single else tuple(outs)
         if not source:
             return filled
@@ -904,9 +818,7 @@ class RasterEngine(object):
         torch = _torch()
         flds = {k: v for k, v in dict(fields).items() if v is not None}
         for k, t in flds.items():
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device or \
-                    t.dtype not in (torch.float32, torch.float64):
-                raise TypeError("fields['%s'] must be a float32 or float64 tensor on cuda:%d" % (k, self.device))
+            _t.check_device(t, "fields['%s']" % k, self.device, torch.float32, torch.float64)
         D, H, R, W, mode, tables, threshold, names = _dn.check_call(
             {k: tuple(t.shape) for k, t in flds.items()}, steps_per_day, half_day, noon, offset, sw_threshold, outputs)
         in_types = set(t.dtype for t in flds.values())
@@ -915,23 +827,9 @@ class RasterEngine(object):
         in_dtype = np.dtype('float32' if in_types.pop() == torch.float32 else 'float64')
         out_dtype = _dn.check_out_dtype(self.np_dtype if dtype is None else dtype, in_dtype)
         tdtype = {'float32': torch.float32, 'float64': torch.float64}[out_dtype.name]
-
-        def layout(t, what, planes):
-            '''-> (row pitch, plane stride) in elements of a (planes, R, W) or (R, W) tensor'''
-            if W > 1 and t.stride(-1) != 1:
-                raise ValueError('%s must have unit stride in columns' % what)
-            pitch = t.stride(-2) if R > 1 else W
-            if pitch < W:
-                raise ValueError('%s: the distance between rows must be at least %d' % (what, W))
-            least = (R - 1) * pitch + W
-            plane = t.stride(0) if t.dim() == 3 and planes > 1 else least
-            if plane < least:
-                raise ValueError('%s: the stride in time must be at least a plane (%d elements)' % (what, least))
-            return pitch, plane
-        lay = set(layout(t, "fields['%s']" % k, D * H) for k, t in flds.items())
-        if len(lay) != 1:
-            raise ValueError('the fields must share one distance between rows and one stride in time')
-        in_pitch, in_plane = lay.pop()
+        both = 'distance between rows and one stride in time'
+        in_pitch, in_plane = _t.share_one([_t.plane_layout(t, "fields['%s']" % k) for k, t in flds.items()],
+                                          'the fields', both)
         series = [n for n in names if n != 'temp_annual']
         if out is None:
             outs = {n: torch.empty((D, R, W), dtype=tdtype, device=self._dev()) for n in series}
@@ -941,21 +839,20 @@ class RasterEngine(object):
             outs = dict(out)
             if sorted(outs) != sorted(names):
                 raise ValueError('out must hold exactly the requested outputs: %s' % ', '.join(names))
-        olay = set()
+        lay = {}
         for n in names:
             o, shape = outs[n], ((R, W) if n == 'temp_annual' else (D, R, W))
-            if not isinstance(o, torch.Tensor) or not o.is_cuda or o.device.index != self.device or o.dtype != tdtype:
-                raise TypeError("out['%s'] must be a %s tensor on cuda:%d" % (n, tdtype, self.device))
+            _t.check_device(o, "out['%s']" % n, self.device, tdtype)
             if tuple(o.shape) != shape:
                 raise ValueError("out['%s'] must have shape %r" % (n, shape))
-            pitch, plane = layout(o, "out['%s']" % n, D)
-            olay.add((pitch, plane) if n != 'temp_annual' and D > 1 else (pitch, None))
-        pitches = set(p for p, _ in olay)
-        planes = set(q for _, q in olay if q is not None)
-        if len(pitches) > 1 or len(planes) > 1:
-            raise ValueError('the out tensors must share one distance between rows and one stride in time')
-        out_pitch = pitches.pop() if pitches else W
-        out_plane = planes.pop() if planes else (R - 1) * out_pitch + W
+            lay[n] = _t.plane_layout(o, "out['%s']" % n)
+        out_pitch = _t.share_one([p for p, _ in lay.values()], 'the out tensors', both)
+        out_plane = _t.share_one([q for n, (_, q) in lay.items() if n != 'temp_annual' and D > 1],
+                                 'the out tensors', both)
+        if out_pitch is None:
+            out_pitch = W
+        if out_plane is None:
+            out_plane = (R - 1) * out_pitch + W
         if D and R and W:
             try:
                 self.ctx.daynight(
@@ -966,37 +863,26 @@ class RasterEngine(object):
                     out_pitch, out_plane, mode=_dn.MODES[mode], threshold=threshold, where=_lib.DEVICE,
                     stream=self._stream())
             except _lib.Mod16Error as e:
-                if e.status == _lib.ERR_ARG and 'overlaps' in str(e):
-                    raise ValueError(str(e))
-                raise
+                raise _lib.overlap_as_value_error(e)
         return _dn.DayNight(*[outs.get(n) for n in _dn.OUTPUT_NAMES]), outs.get('temp_annual')
 
     def _zonal_args(self, values, zones, area, cols, first_pixel):
         '''The checks ``zonal`` and ``zonal_bounds`` share: -> (K, n, value pitch, weight kind, address
         of the weights or None, cols, first_pixel).'''
         torch = _torch()
-        if not isinstance(values, torch.Tensor) or not values.is_cuda or values.device.index != self.device or \
-                values.dtype != self.dtype:
-            raise TypeError('values must be a %s tensor on cuda:%d' % (self.dtype, self.device))
+        _t.check_device(values, 'values', self.device, self.dtype)
         if values.dim() != 2:
             raise ValueError('values must be a (K, n) tensor, got %r' % (tuple(values.shape),))
         K, n = values.shape
-        if n > 1 and values.stride(1) != 1:
-            raise ValueError('values must have unit stride in pixels')
-        pitch = values.stride(0) if K > 1 else max(n, 1)
-        if pitch < n:
-            raise ValueError('the distance between the layers of values must be at least n')
+        pitch = _t.row_pitch(values, 'values')
         if zones is not None:
-            if not isinstance(zones, torch.Tensor) or not zones.is_cuda or zones.device.index != self.device or \
-                    zones.dtype not in (torch.uint8, torch.int32):
-                raise TypeError('zones must be a uint8 or int32 tensor on cuda:%d' % self.device)
-            if tuple(zones.shape) != (n,) or (n > 1 and zones.stride(0) != 1):
+            _t.check_device(zones, 'zones', self.device, torch.uint8, torch.int32)
+            if tuple(zones.shape) != (n,) or not zones.is_contiguous():
                 raise ValueError('zones must have shape (%d,) and unit stride' % n)
         if area is None:
             return K, n, pitch, _lib.ZONAL_WEIGHT_NONE, None, 1, 0
-        if not isinstance(area, torch.Tensor) or not area.is_cuda or area.device.index != self.device:
-            raise TypeError('area must be a tensor on cuda:%d' % self.device)
-        if area.dim() != 1 or (area.numel() > 1 and area.stride(0) != 1):
+        _t.check_device(area, 'area', self.device)
+        if area.dim() != 1 or not area.is_contiguous():
             raise ValueError('area must be a vector with unit stride')
         if cols is None:
             if area.dtype != self.dtype or area.numel() != n:
@@ -1048,11 +934,11 @@ class RasterEngine(object):
         if acc is not None:
             if bounds is None:
                 raise ValueError('acc= needs explicit bounds: their exponents are the scale of the accumulator')
-            if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.device.index != self.device or \
-                    acc.dtype != torch.int64 or not acc.is_contiguous():
-                raise TypeError('acc must be a contiguous int64 tensor on cuda:%d' % self.device)
+            _t.check_device(acc, 'acc', self.device, torch.int64)
             if tuple(acc.shape) != (K, nzones, _z.NWORDS):
                 raise ValueError('acc must have shape %r, got %r' % ((K, nzones, _z.NWORDS), tuple(acc.shape)))
+            if not acc.is_contiguous():
+                raise TypeError('acc must be contiguous %s' % torch.int64)
         if bounds is None:
             wmax, xmax = self.zonal_bounds(values, area, cols if kind == _lib.ZONAL_WEIGHT_ROW else None, first_pixel)
             bounds = (wmax if wmax > 0 else 1.0, xmax if xmax > 0 else 1.0)
@@ -1069,9 +955,7 @@ class RasterEngine(object):
                                cols=cols, first_pixel=first_pixel, value_pitch=pitch, where=_lib.DEVICE,
                                stream=self._stream())
             except _lib.Mod16Error as e:
-                if e.status == _lib.ERR_ARG and 'overlaps' in str(e):
-                    raise ValueError(str(e))
-                raise
+                raise _lib.overlap_as_value_error(e)
         return acc
 
     def ensemble(self, tables):

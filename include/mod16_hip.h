@@ -1213,6 +1213,58 @@ MOD16_API int mod16_daynight_f64(mod16_ctx* ctx, const mod16_daynight_spec* spec
                                  void* temp_annual, int where, void* stream, size_t stage_bytes);
 
 /*
+ * Per-pixel Mann-Kendall test and Theil-Sen slope over a stack of composites (added under ABI 16, new
+ * symbols only; mod16_amd.trend_series, RasterEngine.trend): is the annual ET of a pixel rising, by how
+ * much per unit of time, and is the rise significant. One launch reads every value once and orders the
+ * pairwise slopes of a pixel in LDS. The definition is the numpy statement mod16_amd/trend.py
+ * (pixel_trend), which the outputs equal bit for bit:
+ *
+ *   inputs      values[y * time_stride + i], step y of `steps` (2 ... 64), pixel i of n (0 ... 2^30),
+ *               float32 (widened to float64: exact) or float64; NaN and the infinities are missing.
+ *               times[steps]: a HOST pointer (float64) in both modes, finite and strictly increasing.
+ *               Per pixel the valid steps v, their number m, M = m (m - 1) / 2.
+ *   result      in float64, every operation rounded on its own (no contraction): S = sum over valid
+ *               pairs a < b of sign(x[b] - x[a]); the M slopes (x[b] - x[a]) / (t[b] - t[a]) + 0.0 in
+ *               ascending order q[0 ... M); the median rule med(k values) = the middle one for odd k, (lo
+ *               + hi) * 0.5 of the two middle ones for even k; slope = med(q); intercept = med(x[v] + 0.0)
+ *               - slope * med(t[v]); V18 = m (m - 1)(2 m + 5) - sum over groups of g equal valid values of g
+ *               (g - 1)(2 g + 5); sigma = sqrt(V18 / 18.0); z = 0.0 where S = 0 or V18 = 0, else (S -
+ *               sign(S)) / sigma. With zq > 0 (the normal quantile of 1 - alpha / 2): C = zq sigma,
+ *               slope_hi = q[min(rint((M + C) / 2), M - 1)], slope_lo = q[max(rint((M - C) / 2) - 1, 0)],
+ *               rint to even. Where m < min_valid: S = 0 and the five floats are NaN.
+ *   outputs     out[5] = slope, intercept, slope_lo, slope_hi, z (float64[n]), s (int32[n]), count
+ *               (uint8[n], m); a NULL entry (or out NULL) is skipped, every requested element is written
+ *               exactly once. Pointers may have any element alignment, time_stride any value >= n. No
+ *               atomics: two calls give the same bits. A stack laid out (steps, P, n) -- one trend per
+ *               8-day period -- is the same call with P n pixels.
+ *   where       MOD16_DEVICE: device pointers (times stays a host pointer: checked, then uploaded on
+ *               `stream` into stream-ordered memory), asynchronous on `stream`. MOD16_HOST: host pointers;
+ *               ranges of pixels, all `steps` rows of a range, are staged through the context's slabs,
+ *               a slab of at most stage_bytes (0: 128 MiB; at least 256 pixels). The result does not
+ *               depend on stage_bytes.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_trend: ...")
+ *               NULL spec, values or times; "no output is requested"; n outside 0 ... 2^30, steps outside
+ *               2 ... 64 (mod16_trend_max_steps()); time_stride below n; times not finite, not strictly
+ *               increasing, or with a span that is not finite; min_valid outside 2 ... steps; zq negative
+ *               or not finite; slope_lo or slope_hi given with zq = 0; an unknown `where`; "an output
+ *               overlaps an input or another output". n = 0 is MOD16_OK.
+ */
+typedef struct mod16_trend_spec {
+    int64_t n;                           /* pixels */
+    int32_t steps;                       /* Y: values per pixel */
+    int32_t min_valid;                   /* fewer valid values: no trend */
+    int64_t time_stride;                 /* elements between two steps of `values` */
+    double zq;                           /* 0: no interval */
+} mod16_trend_spec;
+MOD16_API int mod16_trend_max_steps(void);
+MOD16_API int mod16_trend_f32(mod16_ctx* ctx, const mod16_trend_spec* spec, const float* values, const double* times,
+                              double* const* out, int32_t* s, uint8_t* count, int where, void* stream,
+                              size_t stage_bytes);
+MOD16_API int mod16_trend_f64(mod16_ctx* ctx, const mod16_trend_spec* spec, const double* values, const double* times,
+                              double* const* out, int32_t* s, uint8_t* count, int where, void* stream,
+                              size_t stage_bytes);
+
+/*
  * Downscaled forward run (ABI 14; mod16_amd.evapotranspiration_downscaled,
  * RasterEngine.downscale_grid): ET day and night for a contiguous range of pixels of a rows x cols
  * fine raster, each of the 14 drivers a scalar, a fine array or a COARSE coarse_rows x coarse_cols

@@ -129,6 +129,17 @@ _DAYNIGHT_ARGS = [C.c_void_p, C.POINTER(DaynightSpec), _PP, C.c_void_p, C.c_void
                   C.c_int, C.c_void_p, C.c_size_t]
 
 
+class TrendSpec(C.Structure):
+    '''``mod16_trend_spec`` (include/mod16_hip.h): the pixels and steps of a trend call, the fewest valid
+    values a trend is computed from, the stride in time and the normal quantile of the interval.'''
+    _fields_ = [('n', C.c_int64), ('steps', C.c_int32), ('min_valid', C.c_int32), ('time_stride', C.c_int64),
+                ('zq', C.c_double)]
+
+
+_TREND_ARGS = [C.c_void_p, C.POINTER(TrendSpec), C.c_void_p, C.c_void_p, _PP, C.c_void_p, C.c_void_p, C.c_int,
+               C.c_void_p, C.c_size_t]
+
+
 class DownscaleSpec(C.Structure):
     '''``mod16_downscale_spec`` (include/mod16_hip.h): the fine raster, the coarse grid, whether its
     column axis is periodic, the weighting method.'''
@@ -380,6 +391,9 @@ PROTOTYPES = {
     'mod16_et_composite_downscaled_f32': (C.c_int, _COMPOSITE_DOWNSCALED_ARGS),
     'mod16_daynight_f64': (C.c_int, _DAYNIGHT_ARGS),
     'mod16_daynight_f32': (C.c_int, _DAYNIGHT_ARGS),
+    'mod16_trend_f64': (C.c_int, _TREND_ARGS),
+    'mod16_trend_f32': (C.c_int, _TREND_ARGS),
+    'mod16_trend_max_steps': (C.c_int, []),
 }
 
 _lib = None
@@ -636,6 +650,20 @@ class Context:
         self.check(fn(self.handle, C.byref(spec), ptr_array(list(fields)),
                       None if half is None else half.ctypes.data, None if noon is None else noon.ctypes.data,
                       None if offset is None else offset.ctypes.data, ptr_array(list(out)), temp_annual,
+                      int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
+
+    def trend(self, dtype, n, steps, values, times, out, s, count, time_stride=None, min_valid=4, zq=0.0,
+              where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_trend_f64 / _f32 (``dtype``: the values' type). ``values``, ``s`` and
+        ``count`` are raw addresses (the last two or None), ``out`` holds five or None (slope, intercept,
+        slope_lo, slope_hi, z); ``times`` is a contiguous float64 numpy array (host memory in both
+        modes); ``time_stride`` in elements (None: ``n``); ``zq`` 0: no interval; ``stage_bytes`` None:
+        the library's default.'''
+        spec = TrendSpec()
+        spec.n, spec.steps, spec.min_valid = int(n), int(steps), int(min_valid)
+        spec.time_stride, spec.zq = int(n if time_stride is None else time_stride), float(zq)
+        fn = typed(self.lib, 'mod16_trend', dtype)
+        self.check(fn(self.handle, C.byref(spec), values, times.ctypes.data, ptr_array(list(out)), s, count,
                       int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
 
     @staticmethod

@@ -18,3 +18,4 @@
 #include "capi/composite_downscale.hip"
 #include "capi/zonal.hip"
 #include "capi/daynight.hip"
+#include "capi/trend.hip"

@@ -585,6 +585,56 @@ def aggregate_daynight(fields, half_day=None, noon=None, offset=None, sw_thresho
     return _dn.DayNight(*[outs.get(n) for n in _dn.OUTPUT_NAMES]), outs.get('temp_annual')
 
 
+def trend_series(values, times=None, min_valid=4, alpha=None, device=0, stage_bytes=None):
+    r'''
+    (Extension.) Per-pixel Mann-Kendall test and Theil-Sen slope over a stack of composites -- twenty
+    annual totals of ``evapotranspiration_composite`` per pixel, say -- in one kernel launch per staged
+    range of pixels (``mod16_trend_*``): is the pixel's ET rising, by how much per unit of time, and is
+    the rise significant. The definition is ``mod16_amd.trend`` (``pixel_trend``), which the result
+    equals bit for bit.
+
+    Parameters
+    ----------
+    values : numpy.ndarray
+        ``(Y,) + pixel shape`` with ``2 <= Y <= 64``, float32 or float64; NaN and the infinities are
+        missing. A stack ``(Y, P, n)`` -- one trend per 8-day period -- is the same call: the pixel
+        shape is ``(P, n)``
+    times : sequence of float
+        (Optional) ``(Y,)``, finite and strictly increasing (Default: ``arange(Y)``)
+    min_valid : int
+        (Optional) fewest valid values a trend is computed from, ``2 ... Y`` (Default: 4)
+    alpha : float
+        (Optional) a level in (0, 0.5] for the slope's confidence interval: 0.05 gives the 95 %
+        interval, and ``abs(z) > NormalDist().inv_cdf(1 - alpha / 2)`` is the test at that level
+    stage_bytes : int
+        (Optional) device memory a staging slot may take; the result does not depend on it
+
+    Returns
+    -------
+    mod16_amd.trend.Trend
+        ``(slope, intercept, slope_lo, slope_hi, s, z, count)`` of the pixel shape: float64, ``s``
+        int32, ``count`` uint8 (the valid values); NaN (``s``: 0) where ``count < min_valid``;
+        ``slope_lo`` and ``slope_hi`` are None without ``alpha``
+    '''
+    from . import trend as _tr
+    values = np.asarray(values)
+    dtype = _tr.check_dtype(values.dtype)
+    Y, shape, t, min_valid, zq = _tr.check_call(values.shape, times, min_valid, alpha)
+    _check_stage_bytes(stage_bytes)
+    n = int(np.prod(shape, dtype=np.int64))
+    x = np.ascontiguousarray(values).reshape(Y, n)
+    floats = {name: np.empty(n, np.float64) for name in _tr.FLOAT_NAMES if zq or name not in ('slope_lo', 'slope_hi')}
+    s, count = np.empty(n, np.int32), np.empty(n, np.uint8)
+    if n:
+        _lib.context(device).trend(
+            dtype, n, Y, x.ctypes.data, t, [floats[k].ctypes.data if k in floats else None for k in _tr.FLOAT_NAMES],
+            s.ctypes.data, count.ctypes.data, time_stride=n, min_valid=min_valid, zq=zq, where=_lib.HOST,
+            stage_bytes=stage_bytes)
+    res = {k: a.reshape(shape) for k, a in floats.items()}
+    return _tr.Trend(res['slope'], res['intercept'], res.get('slope_lo'), res.get('slope_hi'), s.reshape(shape),
+                     res['z'], count.reshape(shape))
+
+
 def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=None, device=0, stage_bytes=None):
     r'''
     (Extension.) Zonal statistics of a raster: per zone (river basin, country, biome, climate-grid

@@ -866,6 +866,55 @@ class RasterEngine(object):
                 raise _lib.overlap_as_value_error(e)
         return _dn.DayNight(*[outs.get(n) for n in _dn.OUTPUT_NAMES]), outs.get('temp_annual')
 
+    def trend(self, values, times=None, min_valid=4, alpha=None, out=None):
+        '''Enqueue the trend kernel on the current stream: per pixel the Mann-Kendall test and the
+        Theil-Sen slope over a device-resident stack of composites, all outputs in one launch
+        (``mod16_trend_*``; the definition is ``mod16_amd.trend``, which the result equals bit for bit).
+
+        ``values`` is one ``(Y, n)`` float32 or float64 tensor, ``2 <= Y <= 64``, with unit stride in
+        pixels and any stride >= n in time (a view of a larger buffer is fine, at any element
+        offset); NaN and the infinities are missing. A stack ``(Y, P, n)`` -- one trend per 8-day
+        period -- is the same call on its ``(Y, P * n)`` view. ``times``: ``(Y,)`` host values, finite
+        and strictly increasing (default ``arange(Y)``); ``min_valid``: fewest valid values a trend is
+        computed from; ``alpha``: a level in (0, 0.5] for the slope's interval (default: none).
+
+        Returns ``Trend(slope, intercept, slope_lo, slope_hi, s, z, count)`` of ``(n,)`` tensors:
+        float64, ``s`` int32, ``count`` uint8; ``slope_lo`` / ``slope_hi`` are None without ``alpha``.
+        ``out`` may give the tensors as a dict by name (exactly the fields produced, contiguous); no
+        output may overlap the input. Asynchronous, like ``composite``.'''
+        from . import trend as _tr
+        torch = _torch()
+        _t.check_device(values, 'values', self.device, torch.float32, torch.float64)
+        if values.dim() != 2:
+            raise ValueError('values must be a (Y, n) tensor, got %r' % (tuple(values.shape),))
+        Y, shape, t, min_valid, zq = _tr.check_call(tuple(values.shape), times, min_valid, alpha)
+        n = shape[0]
+        stride = _t.row_pitch(values, 'values', 'stride in time')
+        names = [k for k in _tr.Trend._fields if zq or k not in ('slope_lo', 'slope_hi')]
+        kinds = {k: torch.float64 for k in _tr.FLOAT_NAMES}
+        kinds.update(s=torch.int32, count=torch.uint8)
+        if out is None:
+            outs = {k: torch.empty((n,), dtype=kinds[k], device=self._dev()) for k in names}
+        else:
+            outs = dict(out)
+            if sorted(outs) != sorted(names):
+                raise ValueError('out must hold exactly the fields produced: %s' % ', '.join(names))
+        for k in names:
+            _t.check_device(outs[k], "out['%s']" % k, self.device, kinds[k])
+            if tuple(outs[k].shape) != (n,):
+                raise ValueError("out['%s'] must have shape (%d,)" % (k, n))
+            _t.row_pitch(outs[k], "out['%s']" % k)
+        if n:
+            dtype = np.dtype('float32' if values.dtype == torch.float32 else 'float64')
+            try:
+                self.ctx.trend(
+                    dtype, n, Y, values.data_ptr(), t, [outs[k].data_ptr() if k in outs else None for k in _tr.FLOAT_NAMES],
+                    outs['s'].data_ptr(), outs['count'].data_ptr(), time_stride=stride, min_valid=min_valid, zq=zq,
+                    where=_lib.DEVICE, stream=self._stream())
+            except _lib.Mod16Error as e:
+                raise _lib.overlap_as_value_error(e)
+        return _tr.Trend(*[outs.get(k) for k in _tr.Trend._fields])
+
     def _zonal_args(self, values, zones, area, cols, first_pixel):
         '''The checks ``zonal`` and ``zonal_bounds`` share: -> (K, n, value pitch, weight kind, address
         of the weights or None, cols, first_pixel).'''

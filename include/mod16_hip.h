@@ -1265,6 +1265,62 @@ MOD16_API int mod16_trend_f64(mod16_ctx* ctx, const mod16_trend_spec* spec, cons
                               size_t stage_bytes);
 
 /*
+ * Per-pixel climatology, standardized anomalies and percentile ranks over a record of composites (added
+ * under ABI 16, new symbols only; mod16_amd.anomaly_series, RasterEngine.anomaly): how unusual is this
+ * 8-day period of this year against the same period of the baseline years. One launch reads the record
+ * and writes every result once. The definition is the numpy statement mod16_amd/anomaly.py (anomaly),
+ * which the outputs equal bit for bit:
+ *
+ *   inputs      num[s * in_stride + i], slab s = y * periods + p of years * periods (years outermost),
+ *               pixel i of n (0 ... 2^30), float32 (widened to float64: exact) or float64; den likewise
+ *               or NULL -- with den the quantity is the ratio, ET / PET say. years 2 ... 64, periods
+ *               1 ... 366, years * periods <= 4096, window W 1 ... min(periods, 16)
+ *               (mod16_anomaly_max_window()).
+ *   result      in float64, every operation rounded on its own (no contraction). r[s]: missing for
+ *               s < W - 1, else a = +0.0, a = a + num[k] for k = s - W + 1 ... s in that order, b
+ *               likewise from den, r = a / b (r = a without den), valid where r is finite and (with den)
+ *               0 < b < inf. Per period p over the baseline years base_first ... base_end - 1 in year order:
+ *               m valid values, sum from +0.0, mean = sum / m, ss the sum from +0.0 of the rounded
+ *               squares of r - mean, std = sqrt(ss / (m - 1)); mean and std NaN where m < min_valid.
+ *               Per slab of every year: z = (r - mean) / std where r is valid, m >= min_valid and std
+ *               is finite and > 0, else NaN; pct = (lt + 0.5 eq) / m with lt / eq the valid baseline
+ *               values of the period below / equal to r, NaN where r is missing or m < min_valid.
+ *   outputs     z, pct: [years * periods] rows out_stride apart, of the input type (float32: the
+ *               float64 result rounded once); mean, std (float64) and count (uint8, m):
+ *               [periods] rows clim_stride apart. A NULL output is skipped and not written; every
+ *               requested element is written exactly once. Pointers may have any element alignment,
+ *               the strides any value >= n. No atomics: two calls give the same bits.
+ *   where       MOD16_DEVICE: device pointers, asynchronous on `stream`. MOD16_HOST: host pointers;
+ *               ranges of pixels, all rows of a range, are staged through the context's slabs, a slab
+ *               of at most stage_bytes (0: 128 MiB; at least 256 pixels). The result does not depend on
+ *               stage_bytes.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_anomaly: ...")
+ *               NULL spec or num; "no output is requested"; n outside 0 ... 2^30; periods outside
+ *               1 ... 366; years outside 2 ... 64; years * periods above 4096; window outside
+ *               1 ... min(periods, 16); a baseline outside 0 <= base_first < base_end <= years or shorter
+ *               than 2 years; min_valid outside 2 ... base_end - base_first; a stride of a given array
+ *               below n; an unknown `where`; "an output overlaps an input or another output". n = 0 is
+ *               MOD16_OK.
+ */
+typedef struct mod16_anomaly_spec {
+    int64_t n;                           /* pixels */
+    int32_t years, periods;              /* Y, P: the record has Y * P slabs, years outermost */
+    int32_t window;                      /* W: periods summed into a value */
+    int32_t base_first, base_end;        /* the baseline years */
+    int32_t min_valid;                   /* fewer valid baseline values: no climatology */
+    int64_t in_stride;                   /* elements between two slabs of num and den */
+    int64_t out_stride;                  /* ... of z and pct */
+    int64_t clim_stride;                 /* ... between two periods of mean, std and count */
+} mod16_anomaly_spec;
+MOD16_API int mod16_anomaly_max_window(void);
+MOD16_API int mod16_anomaly_f32(mod16_ctx* ctx, const mod16_anomaly_spec* spec, const float* num, const float* den,
+                                float* z, float* pct, double* mean, double* std, uint8_t* count, int where,
+                                void* stream, size_t stage_bytes);
+MOD16_API int mod16_anomaly_f64(mod16_ctx* ctx, const mod16_anomaly_spec* spec, const double* num, const double* den,
+                                double* z, double* pct, double* mean, double* std, uint8_t* count, int where,
+                                void* stream, size_t stage_bytes);
+
+/*
  * Downscaled forward run (ABI 14; mod16_amd.evapotranspiration_downscaled,
  * RasterEngine.downscale_grid): ET day and night for a contiguous range of pixels of a rows x cols
  * fine raster, each of the 14 drivers a scalar, a fine array or a COARSE coarse_rows x coarse_cols

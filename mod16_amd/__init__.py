@@ -39,7 +39,7 @@ from ._args import (_F32, _F64, _address, _as_uint8, _broadcast, _broadcast_kind
                     _result_dtype, _shape, _shift)
 # the entry points the reference does not have, under the names they have always had here
 from .extensions import (
-    CompositeET, CompositeETPET, EnsembleET, EnsembleQuantiles, _ensemble_stack, aggregate_daynight, evapotranspiration_composite,
+    CompositeET, CompositeETPET, EnsembleET, EnsembleQuantiles, _ensemble_stack, aggregate_daynight, anomaly_series, evapotranspiration_composite,
     evapotranspiration_composite_downscaled, evapotranspiration_downscaled, evapotranspiration_ensemble, evapotranspiration_ensemble_quantiles,
     evapotranspiration_raw, gapfill_series, trend_series, zonal_statistics)
 

@@ -140,6 +140,18 @@ _TREND_ARGS = [C.c_void_p, C.POINTER(TrendSpec), C.c_void_p, C.c_void_p, _PP, C.
                C.c_void_p, C.c_size_t]
 
 
+class AnomalySpec(C.Structure):
+    '''``mod16_anomaly_spec`` (include/mod16_hip.h): the pixels, years and periods of an anomaly call,
+    the window, the baseline years, the fewest valid baseline values a climatology is computed from and
+    the strides of the inputs, of ``z`` / ``pct`` and of the climatology.'''
+    _fields_ = [('n', C.c_int64), ('years', C.c_int32), ('periods', C.c_int32), ('window', C.c_int32),
+                ('base_first', C.c_int32), ('base_end', C.c_int32), ('min_valid', C.c_int32),
+                ('in_stride', C.c_int64), ('out_stride', C.c_int64), ('clim_stride', C.c_int64)]
+
+
+_ANOMALY_ARGS = [C.c_void_p, C.POINTER(AnomalySpec)] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_size_t]
+
+
 class DownscaleSpec(C.Structure):
     '''``mod16_downscale_spec`` (include/mod16_hip.h): the fine raster, the coarse grid, whether its
     column axis is periodic, the weighting method.'''
@@ -394,6 +406,9 @@ PROTOTYPES = {
     'mod16_trend_f64': (C.c_int, _TREND_ARGS),
     'mod16_trend_f32': (C.c_int, _TREND_ARGS),
     'mod16_trend_max_steps': (C.c_int, []),
+    'mod16_anomaly_f64': (C.c_int, _ANOMALY_ARGS),
+    'mod16_anomaly_f32': (C.c_int, _ANOMALY_ARGS),
+    'mod16_anomaly_max_window': (C.c_int, []),
 }
 
 _lib = None
@@ -665,6 +680,24 @@ class Context:
         fn = typed(self.lib, 'mod16_trend', dtype)
         self.check(fn(self.handle, C.byref(spec), values, times.ctypes.data, ptr_array(list(out)), s, count,
                       int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
+
+    def anomaly(self, dtype, n, years, periods, num, den, z, pct, mean, std, count, window=1, base_first=0,
+                base_end=None, min_valid=3, in_stride=None, out_stride=None, clim_stride=None, where=HOST,
+                stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_anomaly_f64 / _f32 (``dtype``: the type of ``num``, ``den``, ``z`` and
+        ``pct``). The seven arrays are raw addresses, every one but ``num`` or None (``den`` None: no
+        ratio; an output None: not produced); the strides in elements (None: ``n``); ``base_end``
+        None: ``years``; ``stage_bytes`` None: the library's default.'''
+        spec = AnomalySpec()
+        spec.n, spec.years, spec.periods, spec.window = int(n), int(years), int(periods), int(window)
+        spec.base_first, spec.base_end = int(base_first), int(years if base_end is None else base_end)
+        spec.min_valid = int(min_valid)
+        spec.in_stride = int(n if in_stride is None else in_stride)
+        spec.out_stride = int(n if out_stride is None else out_stride)
+        spec.clim_stride = int(n if clim_stride is None else clim_stride)
+        fn = typed(self.lib, 'mod16_anomaly', dtype)
+        self.check(fn(self.handle, C.byref(spec), num, den, z, pct, mean, std, count, int(where), stream,
+                      0 if stage_bytes is None else int(stage_bytes)))
 
     @staticmethod
     def _zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch, bounds=None):

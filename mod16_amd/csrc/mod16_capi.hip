@@ -19,3 +19,4 @@
 #include "capi/zonal.hip"
 #include "capi/daynight.hip"
 #include "capi/trend.hip"
+#include "capi/anomaly.hip"

@@ -635,6 +635,72 @@ def trend_series(values, times=None, min_valid=4, alpha=None, device=0, stage_by
                      res['z'], count.reshape(shape))
 
 
+def anomaly_series(num, den=None, periods=None, window=1, baseline=None, min_valid=3, outputs=('z',), device=0,
+                   stage_bytes=None):
+    r'''
+    (Extension.) Per-pixel climatology, standardized anomalies and percentile ranks over a record of
+    composites -- 24 years of 46 8-day ET and PET totals of ``evapotranspiration_composite`` per pixel,
+    say -- in one kernel launch per staged range of pixels (``mod16_anomaly_*``): how unusual is this
+    period of this year against the same period of the baseline years. The definition is
+    ``mod16_amd.anomaly`` (``anomaly``), which the result equals bit for bit.
+
+    Parameters
+    ----------
+    num : numpy.ndarray
+        ``(S,) + pixel shape`` with ``S = Y * periods`` slabs in time order, years outermost,
+        ``2 <= Y <= 64`` and ``S <= 4096``, float32 or float64; NaN and the infinities are missing
+    den : numpy.ndarray
+        (Optional) the same shape and dtype: the quantity is the ratio ``num / den`` of the window
+        sums (ET / PET); a window whose ``den`` sum is not positive is missing
+    periods : int
+        periods of a year, ``1 ... 366``
+    window : int
+        (Optional) periods summed into a value, ``1 ... min(periods, 16)``; windows run across year
+        boundaries and the first ``window - 1`` slabs of the record are missing (Default: 1)
+    baseline : tuple of int
+        (Optional) ``(y0, y1)``: the climatology comes from years ``y0 ... y1 - 1``, at least two
+        (Default: all years)
+    min_valid : int
+        (Optional) fewest valid baseline values a climatology is computed from, ``2 ... y1 - y0``
+        (Default: 3)
+    outputs : sequence of str
+        (Optional) any of ``'z'``, ``'pct'``, ``'mean'``, ``'std'``, ``'count'`` (Default: ``('z',)``)
+    stage_bytes : int
+        (Optional) device memory a staging slot may take; the result does not depend on it
+
+    Returns
+    -------
+    mod16_amd.anomaly.Anomaly
+        ``(z, pct, mean, std, count)``, None for what ``outputs`` does not name: ``z`` and ``pct``
+        ``(S,) + pixel shape`` in the dtype of ``num``, ``mean`` and ``std`` ``(periods,) + pixel
+        shape`` float64, ``count`` likewise uint8 (the valid baseline values)
+    '''
+    from . import anomaly as _an
+    num = np.asarray(num)
+    if den is not None:
+        den = np.asarray(den)
+        if den.shape != num.shape:
+            raise ValueError('den must have the shape of num %r, got %r' % (num.shape, den.shape))
+    dtype = _an.check_dtype(num.dtype, None if den is None else den.dtype)
+    if periods is None:
+        raise ValueError('periods must be given')
+    Y, P, shape, W, (y0, y1), min_valid = _an.check_call(num.shape, periods, window, baseline, min_valid)
+    names = _an.check_outputs(outputs)
+    _check_stage_bytes(stage_bytes)
+    S = Y * P
+    n = int(np.prod(shape, dtype=np.int64))
+    x = np.ascontiguousarray(num).reshape(S, n)
+    d = None if den is None else np.ascontiguousarray(den).reshape(S, n)
+    kinds = dict(z=(S, dtype), pct=(S, dtype), mean=(P, np.float64), std=(P, np.float64), count=(P, np.uint8))
+    outs = {k: np.empty((kinds[k][0], n), kinds[k][1]) for k in names}
+    if n:
+        _lib.context(device).anomaly(
+            dtype, n, Y, P, x.ctypes.data, None if d is None else d.ctypes.data,
+            *[outs[k].ctypes.data if k in outs else None for k in _an.OUTPUT_NAMES], window=W, base_first=y0, base_end=y1,
+            min_valid=min_valid, where=_lib.HOST, stage_bytes=stage_bytes)
+    return _an.Anomaly(*[outs[k].reshape((kinds[k][0],) + shape) if k in outs else None for k in _an.OUTPUT_NAMES])
+
+
 def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=None, device=0, stage_bytes=None):
     r'''
     (Extension.) Zonal statistics of a raster: per zone (river basin, country, biome, climate-grid

@@ -915,6 +915,70 @@ class RasterEngine(object):
                 raise _lib.overlap_as_value_error(e)
         return _tr.Trend(*[outs.get(k) for k in _tr.Trend._fields])
 
+    def anomaly(self, num, den=None, periods=None, window=1, baseline=None, min_valid=3, outputs=('z',), out=None):
+        '''Enqueue the anomaly kernel on the current stream: per pixel and 8-day period the climatology
+        of a device-resident record of composites over the baseline years, and per slab its
+        standardized anomaly and percentile rank, in one launch (``mod16_anomaly_*``; the definition is
+        ``mod16_amd.anomaly``, which the result equals bit for bit).
+
+        ``num`` is one ``(S, n)`` float32 or float64 tensor, ``S = Y * periods`` slabs in time order
+        (years outermost, ``2 <= Y <= 64``), with unit stride in pixels and any stride >= n in time (a
+        view of a larger buffer is fine, at any element offset); ``den`` is None or a tensor of the same
+        shape, dtype and stride in time -- the quantity is then the ratio, ET / PET say. ``window``
+        sums that many periods into a value first (1 ... min(periods, 16)); ``baseline = (y0, y1)``
+        takes the climatology from years ``y0 ... y1 - 1`` (default: all); ``min_valid``: fewest valid
+        baseline values a climatology is computed from. NaN, the infinities and ``den <= 0`` are missing.
+
+        Returns ``Anomaly(z, pct, mean, std, count)`` with the fields ``outputs`` names and None for the
+        others: ``z`` / ``pct`` ``(S, n)`` in the input dtype, ``mean`` / ``std`` ``(periods, n)``
+        float64, ``count`` ``(periods, n)`` uint8. ``out`` may give the tensors as a dict by name
+        (exactly the fields produced; ``z`` and ``pct`` share one stride in time, the climatology
+        another); no output may overlap an input. Asynchronous, like ``composite``.'''
+        from . import anomaly as _an
+        torch = _torch()
+        _t.check_device(num, 'num', self.device, torch.float32, torch.float64)
+        if num.dim() != 2:
+            raise ValueError('num must be an (S, n) tensor, got %r' % (tuple(num.shape),))
+        if periods is None:
+            raise ValueError('periods must be given')
+        Y, P, shape, W, (y0, y1), min_valid = _an.check_call(tuple(num.shape), periods, window, baseline, min_valid)
+        names = _an.check_outputs(outputs)
+        S, n = Y * P, shape[0]
+        in_stride = _t.row_pitch(num, 'num', 'stride in time')
+        if den is not None:
+            _t.check_device(den, 'den', self.device, num.dtype)
+            if tuple(den.shape) != (S, n):
+                raise ValueError('den must have the shape of num %r, got %r' % ((S, n), tuple(den.shape)))
+            in_stride = _t.share_one([in_stride, _t.row_pitch(den, 'den', 'stride in time')], 'num and den', 'stride in time')
+        kinds = dict(z=num.dtype, pct=num.dtype, mean=torch.float64, std=torch.float64, count=torch.uint8)
+        rows = dict(z=S, pct=S, mean=P, std=P, count=P)
+        if out is None:
+            outs = {k: torch.empty((rows[k], n), dtype=kinds[k], device=self._dev()) for k in names}
+        else:
+            outs = dict(out)
+            if sorted(outs) != sorted(names):
+                raise ValueError('out must hold exactly the fields produced: %s' % ', '.join(names))
+        pitch = {}
+        for k in names:
+            _t.check_device(outs[k], "out['%s']" % k, self.device, kinds[k])
+            if tuple(outs[k].shape) != (rows[k], n):
+                raise ValueError("out['%s'] must have shape (%d, %d)" % (k, rows[k], n))
+            pitch[k] = _t.row_pitch(outs[k], "out['%s']" % k, 'stride in time')
+        out_stride = _t.share_one([pitch[k] for k in names if k in ('z', 'pct')], "out['z'] and out['pct']", 'stride in time')
+        clim_stride = _t.share_one([pitch[k] for k in names if k not in ('z', 'pct')],
+                                   "out['mean'], out['std'] and out['count']", 'stride between periods')
+        if n:
+            dtype = np.dtype('float32' if num.dtype == torch.float32 else 'float64')
+            try:
+                self.ctx.anomaly(
+                    dtype, n, Y, P, num.data_ptr(), None if den is None else den.data_ptr(),
+                    *[outs[k].data_ptr() if k in outs else None for k in _an.OUTPUT_NAMES], window=W, base_first=y0,
+                    base_end=y1, min_valid=min_valid, in_stride=in_stride, out_stride=out_stride, clim_stride=clim_stride,
+                    where=_lib.DEVICE, stream=self._stream())
+            except _lib.Mod16Error as e:
+                raise _lib.overlap_as_value_error(e)
+        return _an.Anomaly(*[outs.get(k) for k in _an.OUTPUT_NAMES])
+
     def _zonal_args(self, values, zones, area, cols, first_pixel):
         '''The checks ``zonal`` and ``zonal_bounds`` share: -> (K, n, value pitch, weight kind, address
         of the weights or None, cols, first_pixel).'''

@@ -1321,6 +1321,82 @@ MOD16_API int mod16_anomaly_f64(mod16_ctx* ctx, const mod16_anomaly_spec* spec, 
                                 void* stream, size_t stage_bytes);
 
 /*
+ * Upscaling (added under ABI 16, new symbols only; mod16_amd.upscale_fields / upscale_classes,
+ * RasterEngine.upscale_grid): the area-weighted mean of the valid fine pixels of every cell of a coarse
+ * grid, with the valid fraction and count, and the dominant class of a class raster per cell. The
+ * definition is the numpy statement mod16_amd/upscale.py (aggregate, majority), which the outputs
+ * equal bit for bit.
+ *
+ *   geometry    a rows x cols fine raster over coarse_rows x coarse_cols cells (each 1 ... 2^30). The
+ *               fine rows of coarse row i are row_first[i] + 0 ... row_count[i] - 1, the fine columns of
+ *               coarse column j are col_first[j] + 0 ... col_count[j] - 1 -- with wrap_cols (a global
+ *               longitude axis) modulo cols: one run may pass the last column. A count may be 0 (an
+ *               empty cell). mod16_amd.upscale.cell_table / cell_runs derive the tables from positions.
+ *               area[rows] (or NULL: 1.0) is the weight of a pixel of that fine row, cos(latitude) say.
+ *               mod16_upscale_create copies the tables to the device; the handle belongs to the context's
+ *               device and is freed with mod16_upscale_destroy (NULL is fine).
+ *   refused by mod16_upscale_create (MOD16_ERR_ARG, "mod16_upscale_create: ...")
+ *               NULL spec, tables or handle pointer; an extent outside 1 ... 2^30; wrap_cols not 0 or 1;
+ *               a count below 0 or above its axis; a run of pixels that starts outside its axis or
+ *               (rows; columns without wrap_cols) ends behind it; two runs of one axis that share a
+ *               fine index; the largest row_count times the largest col_count at or above 2^31; an area
+ *               that is not positive and finite.
+ *   mean        values[k * layer_stride + r * row_stride + c], k of `layers` (1 ... 65535), float32
+ *               (widened to float64: exact) or float64; row_stride >= cols, layer_stride at least a
+ *               plane. Per layer and cell, every operation rounded on its own (no contraction): num =
+ *               den = tot = +0.0, cnt = 0; per row r of the cell in run order s = +0.0, m = 0, per column
+ *               in run order s = s + x and m += 1 where x is not NaN; then num = num + area[r] * s, den =
+ *               den + area[r] * m, tot = tot + area[r] * col_count[j], cnt += m. fraction = den / tot (0.0
+ *               for a cell without pixels); mean = num / den where cnt >= 1 and den >= min_fraction * tot,
+ *               else NaN; count = cnt.
+ *   outputs     mean, fraction (the input type; float32: the float64 result rounded once) and count
+ *               (int32): [layers][coarse_rows][coarse_cols], each with its own layer and row stride (row
+ *               stride >= coarse_cols, layer stride at least a plane). A NULL output is skipped and not
+ *               written; every requested element is written exactly once. No atomics: two calls give
+ *               the same bits.
+ *   classes     cls[r * row_stride + c] uint8; bit c of `valid` set: code c (below 32) counts. Per cell
+ *               the code with the most pixels, the LOWEST code on a tie, 255 where no pixel counts ->
+ *               out_cls (uint8); out_share (float32) = float32(double(winner's pixels) / double(row_count
+ *               * col_count)), 0 where none counts. Either output may be NULL, not both.
+ *   where       MOD16_DEVICE: device pointers, asynchronous on `stream`. MOD16_HOST: host pointers;
+ *               bands of whole coarse rows -- their fine rows are one range of rows of the raster -- are
+ *               staged through the context's slabs, a slab of at most stage_bytes (0: 128 MiB); where the
+ *               layers of one coarse row exceed that, the layers are cut first; one coarse row of one
+ *               layer goes through whatever the budget. The result does not depend on stage_bytes.
+ *   refused (MOD16_ERR_ARG, before any device work; "mod16_upscale: ..." / "mod16_upscale_classes: ...")
+ *               NULL grid or input; a grid of another device; "no output is requested"; layers outside
+ *               1 ... 65535; a row stride below the row, a layer stride below the plane; min_fraction
+ *               outside [0, 1] or NaN; an unknown `where`; stage_bytes out of range; "an output overlaps
+ *               an input or another output".
+ */
+typedef struct mod16_upscale mod16_upscale;
+typedef struct mod16_upscale_spec {
+    int64_t rows, cols;                  /* the fine raster */
+    int64_t coarse_rows, coarse_cols;    /* the coarse grid */
+    int32_t wrap_cols;                   /* 1: the column runs are cyclic */
+    int32_t reserved_;                   /* 0 */
+} mod16_upscale_spec;
+MOD16_API int mod16_upscale_create(mod16_ctx* ctx, const mod16_upscale_spec* spec, const int32_t* row_first,
+                                   const int32_t* row_count, const int32_t* col_first, const int32_t* col_count,
+                                   const double* area, mod16_upscale** out);
+MOD16_API int mod16_upscale_destroy(mod16_upscale* grid);
+MOD16_API int mod16_upscale_f32(mod16_ctx* ctx, const mod16_upscale* grid, const float* values, int32_t layers,
+                                int64_t layer_stride, int64_t row_stride, double min_fraction, float* mean,
+                                int64_t mean_layer_stride, int64_t mean_row_stride, float* fraction,
+                                int64_t fraction_layer_stride, int64_t fraction_row_stride, int32_t* count,
+                                int64_t count_layer_stride, int64_t count_row_stride, int where, void* stream,
+                                size_t stage_bytes);
+MOD16_API int mod16_upscale_f64(mod16_ctx* ctx, const mod16_upscale* grid, const double* values, int32_t layers,
+                                int64_t layer_stride, int64_t row_stride, double min_fraction, double* mean,
+                                int64_t mean_layer_stride, int64_t mean_row_stride, double* fraction,
+                                int64_t fraction_layer_stride, int64_t fraction_row_stride, int32_t* count,
+                                int64_t count_layer_stride, int64_t count_row_stride, int where, void* stream,
+                                size_t stage_bytes);
+MOD16_API int mod16_upscale_classes(mod16_ctx* ctx, const mod16_upscale* grid, const uint8_t* cls, int64_t row_stride,
+                                    uint32_t valid, uint8_t* out_cls, int64_t cls_row_stride, float* out_share,
+                                    int64_t share_row_stride, int where, void* stream, size_t stage_bytes);
+
+/*
  * Downscaled forward run (ABI 14; mod16_amd.evapotranspiration_downscaled,
  * RasterEngine.downscale_grid): ET day and night for a contiguous range of pixels of a rows x cols
  * fine raster, each of the 14 drivers a scalar, a fine array or a COARSE coarse_rows x coarse_cols

@@ -152,6 +152,17 @@ class AnomalySpec(C.Structure):
 _ANOMALY_ARGS = [C.c_void_p, C.POINTER(AnomalySpec)] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_size_t]
 
 
+class UpscaleSpec(C.Structure):
+    '''``mod16_upscale_spec`` (include/mod16_hip.h): the fine raster, the coarse grid, whether its column
+    runs are cyclic.'''
+    _fields_ = [('rows', C.c_int64), ('cols', C.c_int64), ('coarse_rows', C.c_int64), ('coarse_cols', C.c_int64),
+                ('wrap_cols', C.c_int32), ('reserved_', C.c_int32)]
+
+
+_UPSCALE_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_double] + \
+    [C.c_void_p, C.c_int64, C.c_int64] * 3 + [C.c_int, C.c_void_p, C.c_size_t]
+
+
 class DownscaleSpec(C.Structure):
     '''``mod16_downscale_spec`` (include/mod16_hip.h): the fine raster, the coarse grid, whether its
     column axis is periodic, the weighting method.'''
@@ -409,6 +420,12 @@ PROTOTYPES = {
     'mod16_anomaly_f64': (C.c_int, _ANOMALY_ARGS),
     'mod16_anomaly_f32': (C.c_int, _ANOMALY_ARGS),
     'mod16_anomaly_max_window': (C.c_int, []),
+    'mod16_upscale_create': (C.c_int, [C.c_void_p, C.POINTER(UpscaleSpec)] + [C.c_void_p] * 5 + [C.POINTER(C.c_void_p)]),
+    'mod16_upscale_destroy': (C.c_int, [C.c_void_p]),
+    'mod16_upscale_f64': (C.c_int, _UPSCALE_ARGS),
+    'mod16_upscale_f32': (C.c_int, _UPSCALE_ARGS),
+    'mod16_upscale_classes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t]),
 }
 
 _lib = None
@@ -893,6 +910,69 @@ class Downscale:
     def close(self):
         if getattr(self, 'handle', None) and self.handle.value:
             self.ctx.lib.mod16_downscale_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Upscale:
+    '''The runs of a coarse grid's cells in a fine raster on a context's device (``mod16_upscale``): the
+    four tables of ``mod16_amd.upscale.cell_runs`` for both axes, computed here in numpy from the
+    positions (or given as ``runs = (row_runs, col_runs)``), and the area weights of the fine rows.'''
+
+    def __init__(self, ctx, shape, coarse_shape, row_pos=None, col_pos=None, wrap=False, area=None, runs=None,
+                 col_affine=None):
+        from . import upscale as _u
+        self.wrap = bool(wrap)
+        if runs is None:
+            self.shape, self.coarse_shape, self.row_runs, self.col_runs = _u.check_geometry(
+                shape, coarse_shape, row_pos, col_pos, self.wrap, col_affine)
+        else:
+            self.shape, self.coarse_shape = (int(shape[0]), int(shape[1])), (int(coarse_shape[0]), int(coarse_shape[1]))
+            self.row_runs = _u.check_runs(runs[0], self.shape[0], self.coarse_shape[0], 'row')
+            self.col_runs = _u.check_runs(runs[1], self.shape[1], self.coarse_shape[1], 'column', self.wrap)
+            _u.check_cell_size(self.row_runs, self.col_runs)
+        self.area = _u.check_area(area, self.shape[0])
+        spec = UpscaleSpec(self.shape[0], self.shape[1], self.coarse_shape[0], self.coarse_shape[1], 1 if self.wrap else 0, 0)
+        self.ctx = ctx                  # keeps the context alive as long as its grid
+        self.handle = C.c_void_p()
+        ctx.check(ctx.lib.mod16_upscale_create(
+            ctx.handle, C.byref(spec), *([t.ctypes.data for t in tuple(self.row_runs) + tuple(self.col_runs)] +
+                                         [None if self.area is None else self.area.ctypes.data]),
+            C.byref(self.handle)))
+
+    def _open(self):
+        if not self.handle.value:
+            raise ValueError('the upscale grid has been closed')
+
+    def run(self, dtype, values, layers, layer_stride, row_stride, min_fraction, outs, where=HOST, stream=None,
+            stage_bytes=None):
+        '''Thin wrapper of mod16_upscale_f64 / _f32. ``values`` is a raw address, ``outs`` three entries
+        (mean, fraction, count), each None or ``(address, layer stride, row stride)`` in elements.'''
+        self._open()
+        fn = typed(self.ctx.lib, 'mod16_upscale', dtype)
+        flat = []
+        for o in outs:
+            flat += [None, 0, 0] if o is None else [o[0], int(o[1]), int(o[2])]
+        self.ctx.check(fn(self.ctx.handle, self.handle, values, int(layers), int(layer_stride), int(row_stride),
+                          float(min_fraction), *(flat + [int(where), stream, 0 if stage_bytes is None else int(stage_bytes)])))
+
+    def classes(self, cls, row_stride, valid, out_cls, out_share, where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_upscale_classes: ``cls`` a raw address, ``valid`` the 32-bit mask, the
+        outputs None or ``(address, row stride)``.'''
+        self._open()
+        oc, os_ = out_cls or (None, 0), out_share or (None, 0)
+        self.ctx.check(self.ctx.lib.mod16_upscale_classes(
+            self.ctx.handle, self.handle, cls, int(row_stride), int(valid), oc[0], int(oc[1]), os_[0], int(os_[1]),
+            int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
+
+    def close(self):
+        if getattr(self, 'handle', None) and self.handle.value:
+            self.ctx.lib.mod16_upscale_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -20,3 +20,4 @@
 #include "capi/daynight.hip"
 #include "capi/trend.hip"
 #include "capi/anomaly.hip"
+#include "capi/upscale.hip"

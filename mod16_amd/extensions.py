@@ -701,6 +701,112 @@ def anomaly_series(num, den=None, periods=None, window=1, baseline=None, min_val
     return _an.Anomaly(*[outs[k].reshape((kinds[k][0],) + shape) if k in outs else None for k in _an.OUTPUT_NAMES])
 
 
+def upscale_fields(values, coarse_shape, row_pos, col_pos, wrap=False, area=None, min_fraction=0.0, outputs=('mean',),
+                   device=0, stage_bytes=None):
+    r'''
+    (Extension.) Upscaling: the area-weighted mean of the valid fine pixels of every cell of a coarse
+    grid -- an ET map onto the 0.5-degree grid of the reanalysis that drove it, say -- with the valid
+    fraction and count of every cell (``mod16_upscale_*``). The opposite direction of
+    ``evapotranspiration_downscaled``, with the same position tables. The definition is
+    ``mod16_amd.upscale`` (``aggregate``), which the result equals bit for bit.
+
+    Parameters
+    ----------
+    values : numpy.ndarray
+        ``(K, R, C)`` or ``(R, C)``, float32 or float64; NaN is missing
+    coarse_shape : tuple of int
+        ``(H, W)``
+    row_pos, col_pos : numpy.ndarray
+        ``(R,)`` and ``(C,)``: the positions of the fine rows and columns in units of coarse cells,
+        cell centres at the integers (``mod16_amd.downscale.positions``); a pixel belongs to the cell
+        its centre lies in, a pixel outside the grid to none
+    wrap : bool
+        (Optional) the coarse column axis is periodic (a global longitude axis)
+    area : numpy.ndarray
+        (Optional) ``(R,)``: the weight of a pixel of that fine row, ``cos(latitude)`` say (Default: 1)
+    min_fraction : float
+        (Optional) the mean is NaN where the valid weight of a cell is below this share of the cell's
+    outputs : sequence of str
+        (Optional) any of ``'mean'``, ``'fraction'``, ``'count'`` (Default: ``('mean',)``)
+    stage_bytes : int
+        (Optional) device memory a staged band may take; the result does not depend on it
+
+    Returns
+    -------
+    mod16_amd.upscale.Upscaled
+        ``(mean, fraction, count)``, None for what ``outputs`` does not name: ``(K, H, W)`` or ``(H,
+        W)``, ``mean`` and ``fraction`` in the dtype of ``values``, ``count`` int32
+    '''
+    from . import upscale as _u
+    values = np.asarray(values)
+    dtype = _u.check_dtype(values.dtype)
+    if values.ndim not in (2, 3):
+        raise ValueError('values must have shape (K, R, C) or (R, C), got %r' % (values.shape,))
+    shape = tuple(values.shape[-2:])
+    K, squeeze = _u.check_layers(values.shape, shape)
+    fine, (H, W), row_runs, col_runs = _u.check_geometry(shape, coarse_shape, row_pos, col_pos, wrap)
+    area = _u.check_area(area, shape[0])
+    min_fraction = _u.check_min_fraction(min_fraction)
+    names = _u.check_outputs(outputs)
+    _check_stage_bytes(stage_bytes)
+    x = np.ascontiguousarray(values).reshape(K, shape[0], shape[1])
+    kinds = dict(mean=dtype, fraction=dtype, count=np.dtype(np.int32))
+    outs = {k: np.empty((K, H, W), kinds[k]) for k in names}
+    grid = _lib.Upscale(_lib.context(device), fine, (H, W), wrap=wrap, area=area, runs=(row_runs, col_runs))
+    try:
+        grid.run(dtype, x.ctypes.data, K, shape[0] * shape[1], shape[1], min_fraction,
+                 [(outs[k].ctypes.data, H * W, W) if k in outs else None for k in _u.OUTPUT_NAMES], where=_lib.HOST,
+                 stage_bytes=stage_bytes)
+    finally:
+        grid.close()
+    res = (H, W) if squeeze else (K, H, W)
+    return _u.Upscaled(*[outs[k].reshape(res) if k in outs else None for k in _u.OUTPUT_NAMES])
+
+
+def upscale_classes(cls, coarse_shape, row_pos, col_pos, wrap=False, valid=None, outputs=('cls',), device=0,
+                    stage_bytes=None):
+    r'''
+    (Extension.) The dominant class of a class raster per cell of a coarse grid
+    (``mod16_upscale_classes``; the definition is ``mod16_amd.upscale.majority``): the class map a coarse
+    forward run needs. Per cell the valid code with the most pixels -- the lowest code on a tie --, 255
+    where no pixel is valid, and the winner's share of the cell's pixels.
+
+    Parameters
+    ----------
+    cls : numpy.ndarray
+        ``(R, C)`` class codes (uint8, or integers in [0, 255])
+    coarse_shape, row_pos, col_pos, wrap
+        the geometry, as ``upscale_fields`` takes it
+    valid : iterable of int
+        (Optional) the codes that count, each in [0, 32) (Default: 0 ... 12)
+    outputs : sequence of str
+        (Optional) any of ``'cls'``, ``'share'`` (Default: ``('cls',)``)
+
+    Returns
+    -------
+    mod16_amd.upscale.UpscaledClasses
+        ``(cls, share)``: ``(H, W)`` uint8 and float32, None for what ``outputs`` does not name
+    '''
+    from . import upscale as _u
+    c = _as_uint8(cls)
+    if c.ndim != 2:
+        raise ValueError('cls must be a two-dimensional class raster, got shape %r' % (c.shape,))
+    fine, (H, W), row_runs, col_runs = _u.check_geometry(c.shape, coarse_shape, row_pos, col_pos, wrap)
+    mask = _u.valid_mask(valid)
+    names = _u.check_class_outputs(outputs)
+    _check_stage_bytes(stage_bytes)
+    c = np.ascontiguousarray(c)
+    kinds = dict(cls=np.uint8, share=np.float32)
+    outs = {k: np.empty((H, W), kinds[k]) for k in names}
+    grid = _lib.Upscale(_lib.context(device), fine, (H, W), wrap=wrap, runs=(row_runs, col_runs))
+    try:
+        grid.classes(c.ctypes.data, fine[1], mask, *[(outs[k].ctypes.data, W) if k in outs else None for k in _u.CLASS_OUTPUT_NAMES],
+                     where=_lib.HOST, stage_bytes=stage_bytes)
+    finally:
+        grid.close()
+    return _u.UpscaledClasses(*[outs.get(k) for k in _u.CLASS_OUTPUT_NAMES])
+
+
 def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=None, device=0, stage_bytes=None):
     r'''
     (Extension.) Zonal statistics of a raster: per zone (river basin, country, biome, climate-grid

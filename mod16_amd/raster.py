@@ -226,6 +226,94 @@ class EnsembleRun(object):
         self._ens.close()
 
 
+class UpscaleGrid(object):
+    '''The cells of an ``H x W`` coarse grid in an ``R x C`` fine raster, resident on an engine's device
+    (``RasterEngine.upscale_grid``): the run tables uploaded once, ``run`` (the area-weighted mean of
+    the valid fine pixels of every cell, the valid fraction and the count) and ``majority`` (the
+    dominant class per cell) as often as there are rasters. The definition is ``mod16_amd.upscale``.'''
+
+    def __init__(self, engine, shape, coarse_shape, row_pos, col_pos, wrap=False, area=None, col_affine=None):
+        self.engine = engine                 # keeps the engine alive as long as its grid
+        self._grid = _lib.Upscale(engine.ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, area=area,
+                                  col_affine=col_affine)
+        self.shape, self.coarse_shape = self._grid.shape, self._grid.coarse_shape
+        self.row_runs, self.col_runs, self.wrap = self._grid.row_runs, self._grid.col_runs, self._grid.wrap
+
+    def _outputs(self, names, kinds, out, lead):
+        '''The output tensors by name -- new ones, or the caller's ``out`` dict after its checks -- and per
+        name ``(address, plane stride, row pitch)``.'''
+        eng, torch = self.engine, _torch()
+        shape = lead + self.coarse_shape
+        if out is None:
+            outs = {k: torch.empty(shape, dtype=kinds[k], device=eng._dev()) for k in names}
+        else:
+            outs = dict(out)
+            if sorted(outs) != sorted(names):
+                raise ValueError('out must hold exactly the fields produced: %s' % ', '.join(names))
+        layout = {}
+        for k in names:
+            what = "out['%s']" % k
+            _t.check_device(outs[k], what, eng.device, kinds[k])
+            if tuple(outs[k].shape) != shape:
+                raise ValueError('%s must have shape %r, got %r' % (what, shape, tuple(outs[k].shape)))
+            pitch, plane = _t.plane_layout(outs[k], what)
+            layout[k] = (outs[k].data_ptr(), plane, pitch)
+        return outs, layout
+
+    def run(self, values, min_fraction=0.0, outputs=('mean',), out=None):
+        '''Enqueue the upscaling kernel on the current stream (``mod16_upscale_*``; the definition is
+        ``mod16_amd.upscale.aggregate``, which the result equals bit for bit). ``values`` is a ``(K, R,
+        C)`` or ``(R, C)`` float32 or float64 tensor with unit stride in columns, rows at least ``C``
+        apart and layers at least a plane apart, at any element offset -- the ``(P, n)`` rows a composite
+        wrote, viewed as ``(P, R, C)``, pass as they are. NaN is missing. Returns ``Upscaled(mean,
+        fraction, count)`` on the coarse grid with the fields ``outputs`` names (None for the others,
+        which are neither computed nor written): ``mean`` is NaN where a cell has no valid pixel or its
+        valid weight is below ``min_fraction`` of the cell's. ``out`` may give the tensors as a dict by
+        name; no output may overlap the input. Asynchronous, like ``composite``.'''
+        from . import upscale as _u
+        eng, torch = self.engine, _torch()
+        _t.check_device(values, 'values', eng.device, torch.float32, torch.float64)
+        K, squeeze = _u.check_layers(tuple(values.shape), self.shape)
+        min_fraction = _u.check_min_fraction(min_fraction)
+        names = _u.check_outputs(outputs)
+        pitch, plane = _t.plane_layout(values, 'values')
+        kinds = dict(mean=values.dtype, fraction=values.dtype, count=torch.int32)
+        outs, layout = self._outputs(names, kinds, out, () if squeeze else (K,))
+        dtype = np.dtype('float32' if values.dtype == torch.float32 else 'float64')
+        try:
+            self._grid.run(dtype, values.data_ptr(), K, plane, pitch, min_fraction,
+                           [layout.get(k) for k in _u.OUTPUT_NAMES], where=_lib.DEVICE, stream=eng._stream())
+        except _lib.Mod16Error as e:
+            raise _lib.overlap_as_value_error(e)
+        return _u.Upscaled(*[outs.get(k) for k in _u.OUTPUT_NAMES])
+
+    def majority(self, cls, valid=None, outputs=('cls',), out=None):
+        '''Enqueue the class kernel on the current stream (``mod16_upscale_classes``; the definition is
+        ``mod16_amd.upscale.majority``): ``cls`` an ``(R, C)`` uint8 tensor -> ``UpscaledClasses(cls,
+        share)``, per cell the valid code with the most pixels (the lowest on a tie, 255 where none is
+        valid; ``valid``: the codes that count, default 0 ... 12) and its share of the cell's pixels
+        (float32).'''
+        from . import upscale as _u
+        eng, torch = self.engine, _torch()
+        _t.check_device(cls, 'cls', eng.device, torch.uint8)
+        if tuple(cls.shape) != self.shape:
+            raise ValueError('cls must have shape %r, got %r' % (self.shape, tuple(cls.shape)))
+        mask = _u.valid_mask(valid)
+        names = _u.check_class_outputs(outputs)
+        pitch, _ = _t.plane_layout(cls, 'cls')
+        outs, layout = self._outputs(names, dict(cls=torch.uint8, share=torch.float32), out, ())
+        pair = {k: (v[0], v[2]) for k, v in layout.items()}
+        try:
+            self._grid.classes(cls.data_ptr(), pitch, mask, pair.get('cls'), pair.get('share'), where=_lib.DEVICE,
+                               stream=eng._stream())
+        except _lib.Mod16Error as e:
+            raise _lib.overlap_as_value_error(e)
+        return _u.UpscaledClasses(*[outs.get(k) for k in _u.CLASS_OUTPUT_NAMES])
+
+    def close(self):
+        self._grid.close()
+
+
 class DownscaleGrid(object):
     '''The geometry of an ``R x C`` fine raster over an ``H x W`` coarse grid resident on an engine's
     device (``RasterEngine.downscale_grid``): the corner tables uploaded once, ``run`` (ET with coarse
@@ -698,6 +786,16 @@ class RasterEngine(object):
         one of the two must be given.'''
         return DownscaleGrid(self, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
                              col_affine=col_affine)
+
+    def upscale_grid(self, shape, coarse_shape, row_pos, col_pos, wrap=False, area=None, col_affine=None):
+        '''The cells of an ``H x W`` coarse grid (``coarse_shape``) in an ``R x C`` fine raster (``shape``)
+        on this engine's device -> ``UpscaleGrid``, the opposite direction of ``downscale_grid`` with the
+        same position tables: ``row_pos[R]`` and ``col_pos[C]`` in units of coarse cells, cell centres at
+        the integers (``mod16_amd.downscale.positions``). A pixel belongs to the cell its centre lies in,
+        a pixel outside the grid to none; ``wrap``: the coarse column axis is periodic; ``area[R]``: the
+        weight of a pixel of that fine row (``cos(latitude)``; default 1). Only the rectilinear geometry
+        is covered: ``col_affine`` (a sinusoidal tile) is refused by name.'''
+        return UpscaleGrid(self, shape, coarse_shape, row_pos, col_pos, wrap=wrap, area=area, col_affine=col_affine)
 
     def gapfill(self, fields, qc=None, good=None, max_gap=None, fallback=None, dtype=None, scale=None,
                 source=False, out=None):

@@ -1,0 +1,320 @@
+'''
+Upscaling: area-weighted means of the valid fine pixels of every cell of a coarse grid, and the
+dominant class of a class raster per cell -- the numpy statement of what ``mod16_upscale_f32`` /
+``mod16_upscale_f64`` / ``mod16_upscale_classes`` compute (``RasterEngine.upscale_grid``,
+``mod16_amd.upscale_fields``, ``mod16_amd.upscale_classes``), and the argument checks of those calls.
+Host only: nothing here touches the library or a device; the kernels (``csrc/mod16_upscale.hpp``)
+follow ``aggregate`` and ``majority`` step for step and give their bits.
+
+Geometry. A fine ``R x C`` raster lies over an ``H x W`` coarse grid; ``row_pos[R]`` and ``col_pos[C]``
+are the positions of the fine rows and columns in units of coarse cells, cell centres at the integers
+(``mod16_amd.downscale.positions``), as a ``DownscaleGrid`` takes them. A pixel belongs to the cell its
+centre lies in (``cell_table``: inside the grid the cell ``'nearest'`` interpolation picks); a pixel
+outside the grid belongs to none. The fine indices of a cell form one run of consecutive indices on
+either axis (``cell_runs``), so a cell's pixels are a rectangle of the raster: all geometry is host work
+and the device sees four int32 tables, ``(row_first, row_count)`` and ``(col_first, col_count)``.
+
+``aggregate``, per layer ``k`` and cell ``(i, j)``, in float64 (float32 values are widened first:
+exact), every operation rounded on its own:
+
+- ``num = den = tot = +0.0``, ``cnt = 0``; for the cell's rows in run order ``r = row_first[i] + 0, 1,
+  ...``: ``s = +0.0``, ``m = 0``; for the cell's columns in run order (cyclic with ``wrap``): ``x =
+  values[k, r, col]``, and where ``x`` is not NaN ``s = s + x``, ``m += 1`` (infinities take part as the
+  arithmetic has them); then ``num = num + area[r] * s``, ``den = den + area[r] * float(m)``, ``tot =
+  tot + area[r] * float(col_count[j])``, ``cnt += m``;
+- ``fraction = den / tot``, 0.0 for a cell without pixels; ``mean = num / den`` where ``cnt >= 1`` and
+  ``den >= min_fraction * tot`` (one rounded multiplication, then the comparison), else NaN; ``count =
+  cnt``.
+
+``majority``: per cell the pixels of every valid class code are counted; the winner is the code with
+the highest count, the LOWEST code on a tie (the site-level ancestor, ``Counter.most_common``, takes the
+first met, which depends on the traversal order); 255 where no pixel is valid; ``share =
+float32(float64(winner's count) / float64(pixels of the cell))``, 0 for an empty or all-invalid cell.
+'''
+import collections
+
+import numpy as np
+
+from . import downscale as _d
+
+MAX_LAYERS = 65535
+MAX_CODES = 32                                     # class codes a ``valid`` set may name: [0, 32)
+NO_CLASS = 255
+OUTPUT_NAMES = ('mean', 'fraction', 'count')
+CLASS_OUTPUT_NAMES = ('cls', 'share')
+Upscaled = collections.namedtuple('Upscaled', OUTPUT_NAMES)
+UpscaledClasses = collections.namedtuple('UpscaledClasses', CLASS_OUTPUT_NAMES)
+Runs = collections.namedtuple('Runs', ('first', 'count'))
+
+
+def _positions(pos, size):
+    size = int(size)
+    if not 1 <= size <= _d.MAX_EXTENT:
+        raise ValueError('size must be between 1 and %d, got %d' % (_d.MAX_EXTENT, size))
+    pos = np.asarray(pos, np.float64)
+    if pos.ndim != 1:
+        raise ValueError('a position table must be one-dimensional, got shape %r' % (pos.shape,))
+    if pos.size > _d.MAX_EXTENT:
+        raise ValueError('a position table must have at most %d entries, got %d' % (_d.MAX_EXTENT, pos.size))
+    if not np.all(np.isfinite(pos)):
+        raise ValueError('a position table holds a value that is not finite')
+    return pos, size
+
+
+def cell_table(pos, size, wrap=False):
+    '''One axis: positions in units of coarse cells -> the cell (int32) of every fine index, for a
+    coarse axis of ``size`` cells. Without ``wrap``: ``i0 = floor(pos)``, ``f = pos - i0``, ``cell = i0
+    + (f >= 0.5)``, and -1 where that lies outside ``[0, size)``: the pixel belongs to no cell (it is
+    NOT held to the edge, as the interpolation holds it). With ``wrap`` (a global longitude axis) ``p``
+    is reduced as ``downscale.corner_tables`` reduces it -- ``p = pos - floor(pos / size) * size``, 0
+    where that rounds up to ``size`` -- and ``cell = (floor(p) + (f >= 0.5)) % size``. ``f == 0.5``
+    goes to the far cell. ValueError for a non-finite position.'''
+    pos, size = _positions(pos, size)
+    with np.errstate(all='ignore'):
+        if wrap:
+            p = pos - np.floor(pos / np.float64(size)) * np.float64(size)
+            p = np.where((p >= size) | (p < 0), 0.0, p)
+            i0 = np.floor(p)
+            f = p - i0
+            cell = (i0.astype(np.int64) + (f >= 0.5)) % size
+        else:
+            i0 = np.floor(pos)
+            f = pos - i0
+            cell = np.clip(i0, -2.0, np.float64(size) + 1.0).astype(np.int64) + (f >= 0.5)
+            cell = np.where((cell < 0) | (cell >= size), -1, cell)
+    return cell.astype(np.int32)
+
+
+def cell_runs(cells, size, wrap=False):
+    '''``(first[size], count[size])`` (int32) of a cell table: the fine indices of a cell must form
+    ONE run of consecutive indices, ``first + k`` for ``k = 0 ... count - 1``; with ``wrap`` the run is
+    cyclic, ``(first + k) % n``, starting at the index whose cyclic predecessor is not in the cell.
+    ValueError otherwise. An empty cell has ``count = 0`` (and ``first = 0``). Increasing and decreasing
+    positions both give such runs.'''
+    cells = np.asarray(cells)
+    size = int(size)
+    if cells.ndim != 1 or cells.dtype.kind not in 'iu':
+        raise ValueError('a cell table must be a one-dimensional integer array')
+    cells = cells.astype(np.int64)
+    n = cells.size
+    if n and (cells.min() < -1 or cells.max() >= size):
+        raise ValueError('a cell table holds a cell outside [-1, %d)' % size)
+    first = np.zeros(size, np.int64)
+    count = np.zeros(size, np.int64)
+    if n:
+        inside = cells >= 0
+        count = np.bincount(cells[inside], minlength=size).astype(np.int64)
+        start = np.ones(n, bool)
+        start[1:] = cells[1:] != cells[:-1]
+        if wrap:
+            start[0] = cells[0] != cells[-1]
+            if not start.any():                    # one cell holds the whole axis
+                start[0] = True
+        at = np.flatnonzero(start & inside)
+        owner = cells[at]
+        twice = np.flatnonzero(np.bincount(owner, minlength=1) > 1)
+        if twice.size:
+            raise ValueError('the fine indices of cell %d do not form one run of consecutive indices' % int(twice[0]))
+        first[owner] = at
+    return Runs(first.astype(np.int32), count.astype(np.int32))
+
+
+def check_runs(runs, n, size, what, wrap=False):
+    '''``(first, count)`` of one axis as contiguous int32 arrays of ``size`` entries that name disjoint
+    runs inside ``n`` fine indices (cyclic with ``wrap``); ValueError otherwise.'''
+    if len(runs) != 2:
+        raise ValueError('%s runs must be (first, count)' % what)
+    first, count = (np.ascontiguousarray(t, np.int32) for t in runs)
+    n, size = int(n), int(size)
+    if first.shape != (size,) or count.shape != (size,):
+        raise ValueError('%s runs must have shape (%d,), got %r and %r' % (what, size, first.shape, count.shape))
+    f, c = first.astype(np.int64), count.astype(np.int64)
+    some = c > 0
+    if np.any(c < 0) or np.any(c > n) or np.any(some & ((f < 0) | (f >= n))) or (not wrap and np.any(some & (f + c > n))):
+        raise ValueError('a %s run leaves the %d fine indices' % (what, n))
+    order = np.argsort(f[some], kind='stable')
+    lo, hi = f[some][order], (f + c)[some][order]
+    if lo.size and (np.any(lo[1:] < hi[:-1]) or hi[-1] - n > lo[0]):
+        raise ValueError('the %s runs are not contiguous: two cells share a fine index' % what)
+    return Runs(first, count)
+
+
+def check_geometry(shape, coarse_shape, row_pos, col_pos, wrap=False, col_affine=None):
+    '''The checks of a grid: -> ``((R, C), (H, W), row_runs, col_runs)``.'''
+    if col_affine is not None:
+        raise ValueError('col_affine (row-affine columns, a sinusoidal tile) is not available for upscaling: '
+                         'give col_pos (a rectilinear geometry)')
+    try:
+        (R, C), (H, W) = (int(e) for e in shape), (int(e) for e in coarse_shape)
+    except (TypeError, ValueError):
+        raise ValueError('shape and coarse_shape must be (rows, cols) pairs, got %r and %r' % (shape, coarse_shape))
+    for e in (R, C, H, W):
+        if not 1 <= e <= _d.MAX_EXTENT:
+            raise ValueError('rows, cols, coarse rows and coarse cols must be between 1 and %d, got %r over %r'
+                             % (_d.MAX_EXTENT, (R, C), (H, W)))
+    row_pos, col_pos = np.asarray(row_pos, np.float64), np.asarray(col_pos, np.float64)
+    if row_pos.shape != (R,) or col_pos.shape != (C,):
+        raise ValueError('row_pos and col_pos must have shapes (%d,) and (%d,), got %r and %r'
+                         % (R, C, row_pos.shape, col_pos.shape))
+    rows = cell_runs(cell_table(row_pos, H), H)
+    cols = cell_runs(cell_table(col_pos, W, wrap), W, wrap)
+    check_cell_size(rows, cols)
+    return (R, C), (H, W), rows, cols
+
+
+def check_cell_size(row_runs, col_runs):
+    if int(np.max(row_runs[1], initial=0)) * int(np.max(col_runs[1], initial=0)) >= 2 ** 31:
+        raise ValueError('a cell must hold fewer than 2^31 pixels (row_count * col_count)')
+
+
+def check_area(area, R):
+    '''-> None or ``area`` as a contiguous float64 ``(R,)`` array of positive finite weights.'''
+    if area is None:
+        return None
+    area = np.ascontiguousarray(area, np.float64)
+    if area.shape != (int(R),):
+        raise ValueError('area must have shape (%d,) -- a weight per fine row --, got %r' % (R, area.shape))
+    if not (np.all(np.isfinite(area)) and np.all(area > 0)):
+        raise ValueError('area must be positive and finite')
+    return area
+
+
+def check_min_fraction(min_fraction):
+    try:
+        v = float(min_fraction)
+    except (TypeError, ValueError):
+        raise ValueError('min_fraction must be a number in [0, 1], got %r' % (min_fraction,))
+    if not 0.0 <= v <= 1.0:                        # (NaN fails both comparisons)
+        raise ValueError('min_fraction must lie in [0, 1], got %r' % (min_fraction,))
+    return v
+
+
+def check_layers(shape, fine_shape, what='values'):
+    '''``(K, R, C)`` or ``(R, C)`` against the grid's fine shape -> ``(K, squeeze)``.'''
+    shape = tuple(int(e) for e in shape)
+    if len(shape) not in (2, 3) or shape[-2:] != tuple(fine_shape):
+        raise ValueError('%s must have shape (K, %d, %d) or (%d, %d), got %r' % ((what,) + tuple(fine_shape) * 2 + (shape,)))
+    K = shape[0] if len(shape) == 3 else 1
+    if not 1 <= K <= MAX_LAYERS:
+        raise ValueError('%s must have between 1 and %d layers, got %d' % (what, MAX_LAYERS, K))
+    return K, len(shape) == 2
+
+
+def check_dtype(dtype):
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError('values must be float32 or float64, got %s' % dtype)
+    return dtype
+
+
+def _names(outputs, known):
+    if isinstance(outputs, str):
+        outputs = (outputs,)
+    outputs = tuple(outputs)
+    if not outputs or len(set(outputs)) != len(outputs) or any(k not in known for k in outputs):
+        raise ValueError('outputs must name one or more of %s, each once, got %r' % (', '.join(known), outputs))
+    return tuple(k for k in known if k in outputs)
+
+
+def check_outputs(outputs):
+    '''-> the requested names in the order of ``OUTPUT_NAMES``; at least one, no unknown one, none twice.'''
+    return _names(outputs, OUTPUT_NAMES)
+
+
+def check_class_outputs(outputs):
+    return _names(outputs, CLASS_OUTPUT_NAMES)
+
+
+def valid_mask(valid=None):
+    '''A set of class codes in ``[0, 32)`` (None: the 13 classes of the parameter table) -> the 32-bit
+    mask ``mod16_upscale_classes`` takes.'''
+    codes = range(13) if valid is None else valid
+    mask = 0
+    for c in codes:
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < MAX_CODES:
+            raise ValueError('valid must hold class codes in [0, %d), got %r' % (MAX_CODES, c))
+        mask |= 1 << int(c)
+    return mask
+
+
+def aggregate(values, row_runs, col_runs, area=None, min_fraction=0.0, outputs=OUTPUT_NAMES, wrap=False):
+    '''The definition: ``values`` ``(K, R, C)`` or ``(R, C)``, float32 or float64 -> ``Upscaled(mean,
+    fraction, count)``: ``mean`` and ``fraction`` ``(K, H, W)`` (or ``(H, W)``) in the dtype of
+    ``values`` (float32: the float64 result rounded once), ``count`` int32; None for what ``outputs``
+    does not name. ``wrap``: the column runs are cyclic. Vectorised over layers and cells, Python loops
+    over the pixels of a cell: the statement the device result is compared with, not a fast path.'''
+    values = np.asarray(values)
+    dtype = check_dtype(values.dtype)
+    if values.ndim not in (2, 3):
+        raise ValueError('values must have shape (K, R, C) or (R, C), got %r' % (values.shape,))
+    R, C = values.shape[-2:]
+    K, squeeze = check_layers(values.shape, (R, C))
+    rf, rc = check_runs(row_runs, R, len(row_runs[0]), 'row')
+    cf, cc = check_runs(col_runs, C, len(col_runs[0]), 'column', wrap)
+    check_cell_size((rf, rc), (cf, cc))
+    area = check_area(area, R)
+    min_fraction = check_min_fraction(min_fraction)
+    names = check_outputs(outputs)
+    H, W = rf.size, cf.size
+    x3 = values.reshape(K, R, C).astype(np.float64)
+    w = np.ones(R) if area is None else area
+    num, den, tot = np.zeros((K, H, W)), np.zeros((K, H, W)), np.zeros((K, H, W))
+    cnt = np.zeros((K, H, W), np.int64)
+    ccf = cc.astype(np.float64)[None, None, :]
+    with np.errstate(all='ignore'):
+        for t in range(int(rc.max(initial=0))):
+            rows_on = t < rc                               # (H,)
+            r = np.where(rows_on, rf.astype(np.int64) + t, 0)
+            s = np.zeros((K, H, W))
+            m = np.zeros((K, H, W), np.int64)
+            for k in range(int(cc.max(initial=0))):
+                cols_on = k < cc                           # (W,)
+                col = np.where(cols_on, (cf.astype(np.int64) + k) % C, 0)
+                x = x3[:, r[:, None], col[None, :]]
+                ok = cols_on[None, None, :] & ~np.isnan(x)
+                s = np.where(ok, s + x, s)
+                m += ok
+            a = w[r][None, :, None]
+            on = rows_on[None, :, None]
+            num = np.where(on, num + a * s, num)
+            den = np.where(on, den + a * m.astype(np.float64), den)
+            tot = np.where(on, tot + a * ccf, tot)
+            cnt += np.where(on, m, 0)
+        fraction = np.where(tot > 0, den / tot, 0.0)
+        mean = np.where((cnt >= 1) & (den >= min_fraction * tot), num / den, np.nan)
+    shape = (H, W) if squeeze else (K, H, W)
+    res = dict(mean=mean.astype(dtype).reshape(shape), fraction=fraction.astype(dtype).reshape(shape),
+               count=cnt.astype(np.int32).reshape(shape))
+    return Upscaled(*[res[k] if k in names else None for k in OUTPUT_NAMES])
+
+
+def majority(cls, row_runs, col_runs, valid=None, outputs=CLASS_OUTPUT_NAMES, wrap=False):
+    '''The definition for a class raster: ``cls`` ``(R, C)`` uint8 -> ``UpscaledClasses(cls uint8 (H, W),
+    share float32 (H, W))``; ``valid``: the codes that count (None: 0 ... 12).'''
+    cls = np.asarray(cls)
+    if cls.ndim != 2 or cls.dtype != np.uint8:
+        raise ValueError('cls must be a two-dimensional uint8 array, got %s %r' % (cls.dtype, cls.shape))
+    R, C = cls.shape
+    rf, rc = check_runs(row_runs, R, len(row_runs[0]), 'row')
+    cf, cc = check_runs(col_runs, C, len(col_runs[0]), 'column', wrap)
+    check_cell_size((rf, rc), (cf, cc))
+    mask = valid_mask(valid)
+    names = check_class_outputs(outputs)
+    H, W = rf.size, cf.size
+    row_cell = np.full(R, -1, np.int64)
+    col_cell = np.full(C, -1, np.int64)
+    for i in range(H):
+        row_cell[int(rf[i]):int(rf[i]) + int(rc[i])] = i
+    for j in range(W):
+        col_cell[(int(cf[j]) + np.arange(int(cc[j]))) % C] = j
+    code_ok = np.array([(mask >> c) & 1 if c < MAX_CODES else 0 for c in range(256)], bool)
+    take = (row_cell[:, None] >= 0) & (col_cell[None, :] >= 0) & code_ok[cls]
+    cell = (row_cell[:, None] * W + col_cell[None, :])[take]
+    counts = np.bincount(cls[take].astype(np.int64) * (H * W) + cell, minlength=MAX_CODES * H * W).reshape(MAX_CODES, H, W)
+    winner = counts.argmax(axis=0)                         # the first maximum: the lowest code
+    best = counts.max(axis=0)
+    pixels = rc.astype(np.float64)[:, None] * cc.astype(np.float64)[None, :]
+    with np.errstate(all='ignore'):
+        share = np.where(best > 0, best.astype(np.float64) / pixels, 0.0).astype(np.float32)
+    res = dict(cls=np.where(best > 0, winner, NO_CLASS).astype(np.uint8), share=share)
+    return UpscaledClasses(*[res[k] if k in names else None for k in CLASS_OUTPUT_NAMES])

@@ -174,6 +174,25 @@ def _outputs(out, shape, dtypes, pinned=True, indexed=False):
     return outs
 
 
+def _named_outputs(out, table):
+    '''The result arrays of an entry point whose results go by name, ``table`` stating them as name ->
+    ``(shape, numpy dtype)`` (the ``output_table`` of a definition module): new ones from ``np.empty``,
+    or the caller's ``out`` dict after a check -- exactly the table's names, then in its order that
+    every one is a writeable C-contiguous ndarray of that shape and dtype. The counterpart of
+    ``_tensors.named_outputs``.'''
+    if out is None:
+        return {k: np.empty(shape, dt) for k, (shape, dt) in table.items()}
+    outs = dict(out)
+    if sorted(outs) != sorted(table):
+        raise ValueError('out must hold exactly the requested outputs: %s' % ', '.join(table))
+    for k, (shape, dt) in table.items():
+        o = outs[k]
+        if not (isinstance(o, np.ndarray) and o.shape == shape and o.dtype == dt
+                and o.flags.c_contiguous and o.flags.writeable):
+            raise ValueError("out['%s'] must be a writeable C-contiguous %s array of shape %s" % (k, dt, shape))
+    return outs
+
+
 def _check_stage_bytes(stage_bytes):
     if stage_bytes is not None and int(stage_bytes) < 0:
         raise ValueError('stage_bytes must not be negative')

@@ -1,10 +1,12 @@
 '''
 Argument handling shared by the device-tensor entry points (``mod16_amd.raster``), the counterpart
 of ``_args.py``: is this a tensor on the engine's device, and what strided layout does it have in
-the terms of the C ABI (a row pitch, a plane stride, a stride in time, all in elements). The layout
-rules look at ``shape`` and ``stride()`` only, so they hold for CPU tensors as well (tests/
-test_tensor_args_host.py). Nothing here loads the library.
+the terms of the C ABI (a row pitch, a plane stride, a stride in time, all in elements), and the
+``out=`` protocol over a family's table of results (``named_outputs``). The layout rules look at
+``shape`` and ``stride()`` only, so they hold for CPU tensors as well (tests/
+test_tensor_args_host.py). Nothing here loads the library, or ``torch`` before a call needs it.
 '''
+import numpy as np
 
 
 _Tensor = None       # torch.Tensor, once a check has needed it (this sits on every enqueue path)
@@ -53,6 +55,49 @@ def plane_layout(t, what):
     if plane < least:
         raise ValueError('%s: the stride in time must be at least a plane (%d elements)' % (what, least))
     return pitch, plane
+
+
+def torch_dtype(dtype):
+    '''The torch dtype of a numpy dtype (or its name); ``numpy_dtype`` is the way back. The two
+    libraries share the names, which is the whole table.'''
+    import torch
+    return getattr(torch, np.dtype(dtype).name)
+
+
+def numpy_dtype(dtype):
+    return np.dtype(str(dtype).replace('torch.', ''))
+
+
+def named_outputs(out, table, device, between=None, called='fields produced'):
+    '''The ``out=`` protocol of the tensor entry points -> ``(tensors by key, layouts by key)`` in the
+    order of ``table``, which states the results as key -> ``(shape, numpy dtype)`` (a definition
+    module's ``output_table``; keys ``0, 1, ...``: positional results). ``out``: None (new tensors), or
+    the caller's dict (sequence, for positional results). ``between``: None for ``(planes, R, W)`` /
+    ``(R, W)`` results (``plane_layout``), else they are rows (``row_pitch``) that far apart.
+
+    First the key set or the count; then per result, in the table's order, ``check_device``, the shape,
+    the layout rule, under the label ``out[<key>]``: of two offences in different results the earlier
+    result's is reported, whatever its kind. What results must share is the caller's (``share_one``).'''
+    if out is None:
+        import torch
+        where = torch.device('cuda', device)
+        outs = {k: torch.empty(shape, dtype=torch_dtype(dt), device=where) for k, (shape, dt) in table.items()}
+    elif 0 in table:
+        outs = dict(enumerate(out))
+        if len(outs) != len(table):
+            raise ValueError('out must hold %d tensors' % len(table))
+    else:
+        outs = dict(out)
+        if sorted(outs) != sorted(table):
+            raise ValueError('out must hold exactly the %s: %s' % (called, ', '.join(table)))
+    layouts = {}
+    for k, (shape, dt) in table.items():
+        t, what = outs[k], 'out[%r]' % (k,)
+        check_device(t, what, device, torch_dtype(dt))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('%s must have shape %r, got %r' % (what, tuple(shape), tuple(t.shape)))
+        layouts[k] = plane_layout(t, what) if between is None else row_pitch(t, what, between)
+    return {k: outs[k] for k in table}, layouts
 
 
 def share_one(values, who, what):

@@ -53,6 +53,8 @@ def check_call(shape, periods, window=1, baseline=None, min_valid=3):
     '''The checks ``anomaly_series``, ``RasterEngine.anomaly`` and ``anomaly`` share, on the shape of
     ``num`` alone: -> ``(Y, P, pixel shape, W, (y0, y1), min_valid)``.'''
     shape = tuple(int(e) for e in shape)
+    if periods is None:
+        raise ValueError('periods must be given')
     P = _integer(periods, 'periods')
     if not 1 <= P <= MAX_PERIODS:
         raise ValueError('periods must be between 1 and %d, got %d' % (MAX_PERIODS, P))
@@ -93,6 +95,18 @@ def check_dtype(dtype, den_dtype=None):
     return dtype
 
 
+def check_den_shape(shape, den_shape):
+    if tuple(den_shape) != tuple(shape):
+        raise ValueError('den must have the shape of num %r, got %r' % (tuple(shape), tuple(den_shape)))
+
+
+def output_table(names, S, P, shape, dtype):
+    '''What a call produces, in the order of ``OUTPUT_NAMES``: name -> ``(shape, numpy dtype)`` for the
+    requested ``names``, with ``shape`` the pixel shape and ``dtype`` that of ``num``.'''
+    kinds = dict(z=(S, dtype), pct=(S, dtype), mean=(P, np.float64), std=(P, np.float64), count=(P, np.uint8))
+    return {k: ((kinds[k][0],) + tuple(shape), np.dtype(kinds[k][1])) for k in OUTPUT_NAMES if k in names}
+
+
 def check_outputs(outputs):
     '''-> the requested names in the order of ``OUTPUT_NAMES``; at least one, no unknown one, none twice.'''
     if isinstance(outputs, str):
@@ -131,11 +145,8 @@ def anomaly(num, den=None, periods=None, window=1, baseline=None, min_valid=3, o
     num = np.asarray(num)
     if den is not None:
         den = np.asarray(den)
-        if den.shape != num.shape:
-            raise ValueError('den must have the shape of num %r, got %r' % (num.shape, den.shape))
+        check_den_shape(num.shape, den.shape)
     dtype = check_dtype(num.dtype, None if den is None else den.dtype)
-    if periods is None:
-        raise ValueError('periods must be given')
     Y, P, shape, W, (y0, y1), min_valid = check_call(num.shape, periods, window, baseline, min_valid)
     outputs = check_outputs(outputs)
     S = Y * P
@@ -170,7 +181,6 @@ def anomaly(num, den=None, periods=None, window=1, baseline=None, min_valid=3, o
             good = ok[y] & enough
             z[y] = np.where(good & np.isfinite(std) & (std > 0), (v - mean) / std, np.nan)
             pct[y] = np.where(good, (lt.astype(np.float64) + 0.5 * eq.astype(np.float64)) / mf, np.nan)
-    res = dict(z=z.reshape((S,) + shape).astype(dtype), pct=pct.reshape((S,) + shape).astype(dtype),
-               mean=np.where(enough, mean, np.nan).reshape((P,) + shape), std=np.where(enough, std, np.nan).reshape((P,) + shape),
-               count=m.astype(np.uint8).reshape((P,) + shape))
-    return Anomaly(*[res[k] if k in outputs else None for k in OUTPUT_NAMES])
+    res = dict(z=z, pct=pct, mean=np.where(enough, mean, np.nan), std=np.where(enough, std, np.nan), count=m)
+    table = output_table(outputs, S, P, shape, dtype)
+    return Anomaly(*[res[k].reshape(table[k][0]).astype(table[k][1]) if k in table else None for k in OUTPUT_NAMES])

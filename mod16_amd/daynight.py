@@ -106,6 +106,12 @@ def check_outputs(outputs, given, mode):
     return tuple(n for n in every if n in names)
 
 
+def output_table(names, D, R, W, dtype):
+    '''What a call produces, in the order of ``names`` (that of ``check_outputs``): name -> ``(shape, numpy
+    dtype)``, ``(D, R, W)`` series and the ``(R, W)`` plane ``'temp_annual'``, all in the output ``dtype``.'''
+    return {n: ((R, W) if n == 'temp_annual' else (D, R, W), np.dtype(dtype)) for n in names}
+
+
 def check_call(shapes, steps_per_day=24, half_day=None, noon=None, offset=None, sw_threshold=None,
                outputs=None, mode=None):
     '''The argument checks of every day / night call. ``shapes``: field name -> shape of the fields

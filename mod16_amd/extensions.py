@@ -11,7 +11,8 @@ import collections as _collections
 import numpy as np
 
 from . import _lib
-from ._args import _U16, _as_uint8, _broadcast, _check_stage_bytes, _marshal, _outputs, _result_dtype, _shape, _shift
+from ._args import (_U16, _as_uint8, _broadcast, _check_stage_bytes, _marshal, _named_outputs, _outputs, _result_dtype,
+                    _shape, _shift)
 from .downscale import MET_DRIVERS as _MET_DRIVERS
 
 
@@ -559,19 +560,7 @@ def aggregate_daynight(fields, half_day=None, noon=None, offset=None, sw_thresho
     out_dtype = _dn.check_out_dtype(dtype, in_dtype)
     _check_stage_bytes(stage_bytes)
     flds = {k: np.ascontiguousarray(v) for k, v in flds.items()}
-    shapes = {n: ((R, W) if n == 'temp_annual' else (D, R, W)) for n in names}
-    if out is None:
-        outs = {n: np.empty(shapes[n], out_dtype) for n in names}
-    else:
-        outs = dict(out)
-        if sorted(outs) != sorted(names):
-            raise ValueError('out must hold exactly the requested outputs: %s' % ', '.join(names))
-        for n in names:
-            o = outs[n]
-            if not (isinstance(o, np.ndarray) and o.shape == shapes[n] and o.dtype == out_dtype
-                    and o.flags.c_contiguous and o.flags.writeable):
-                raise ValueError("out['%s'] must be a writeable C-contiguous %s array of shape %s"
-                                 % (n, out_dtype, shapes[n]))
+    outs = _named_outputs(out, _dn.output_table(names, D, R, W, out_dtype))
     if D and R and W:
         try:
             _lib.context(device).daynight(
@@ -623,16 +612,13 @@ def trend_series(values, times=None, min_valid=4, alpha=None, device=0, stage_by
     _check_stage_bytes(stage_bytes)
     n = int(np.prod(shape, dtype=np.int64))
     x = np.ascontiguousarray(values).reshape(Y, n)
-    floats = {name: np.empty(n, np.float64) for name in _tr.FLOAT_NAMES if zq or name not in ('slope_lo', 'slope_hi')}
-    s, count = np.empty(n, np.int32), np.empty(n, np.uint8)
+    outs = _named_outputs(None, _tr.output_table(shape, zq))          # (of the pixel shape: each is n values in a row)
     if n:
         _lib.context(device).trend(
-            dtype, n, Y, x.ctypes.data, t, [floats[k].ctypes.data if k in floats else None for k in _tr.FLOAT_NAMES],
-            s.ctypes.data, count.ctypes.data, time_stride=n, min_valid=min_valid, zq=zq, where=_lib.HOST,
+            dtype, n, Y, x.ctypes.data, t, [outs[k].ctypes.data if k in outs else None for k in _tr.FLOAT_NAMES],
+            outs['s'].ctypes.data, outs['count'].ctypes.data, time_stride=n, min_valid=min_valid, zq=zq, where=_lib.HOST,
             stage_bytes=stage_bytes)
-    res = {k: a.reshape(shape) for k, a in floats.items()}
-    return _tr.Trend(res['slope'], res['intercept'], res.get('slope_lo'), res.get('slope_hi'), s.reshape(shape),
-                     res['z'], count.reshape(shape))
+    return _tr.Trend(*[outs.get(k) for k in _tr.Trend._fields])
 
 
 def anomaly_series(num, den=None, periods=None, window=1, baseline=None, min_valid=3, outputs=('z',), device=0,
@@ -679,11 +665,8 @@ def anomaly_series(num, den=None, periods=None, window=1, baseline=None, min_val
     num = np.asarray(num)
     if den is not None:
         den = np.asarray(den)
-        if den.shape != num.shape:
-            raise ValueError('den must have the shape of num %r, got %r' % (num.shape, den.shape))
+        _an.check_den_shape(num.shape, den.shape)
     dtype = _an.check_dtype(num.dtype, None if den is None else den.dtype)
-    if periods is None:
-        raise ValueError('periods must be given')
     Y, P, shape, W, (y0, y1), min_valid = _an.check_call(num.shape, periods, window, baseline, min_valid)
     names = _an.check_outputs(outputs)
     _check_stage_bytes(stage_bytes)
@@ -691,14 +674,13 @@ def anomaly_series(num, den=None, periods=None, window=1, baseline=None, min_val
     n = int(np.prod(shape, dtype=np.int64))
     x = np.ascontiguousarray(num).reshape(S, n)
     d = None if den is None else np.ascontiguousarray(den).reshape(S, n)
-    kinds = dict(z=(S, dtype), pct=(S, dtype), mean=(P, np.float64), std=(P, np.float64), count=(P, np.uint8))
-    outs = {k: np.empty((kinds[k][0], n), kinds[k][1]) for k in names}
+    outs = _named_outputs(None, _an.output_table(names, S, P, shape, dtype))
     if n:
         _lib.context(device).anomaly(
             dtype, n, Y, P, x.ctypes.data, None if d is None else d.ctypes.data,
             *[outs[k].ctypes.data if k in outs else None for k in _an.OUTPUT_NAMES], window=W, base_first=y0, base_end=y1,
             min_valid=min_valid, where=_lib.HOST, stage_bytes=stage_bytes)
-    return _an.Anomaly(*[outs[k].reshape((kinds[k][0],) + shape) if k in outs else None for k in _an.OUTPUT_NAMES])
+    return _an.Anomaly(*[outs.get(k) for k in _an.OUTPUT_NAMES])
 
 
 def upscale_fields(values, coarse_shape, row_pos, col_pos, wrap=False, area=None, min_fraction=0.0, outputs=('mean',),
@@ -750,8 +732,7 @@ def upscale_fields(values, coarse_shape, row_pos, col_pos, wrap=False, area=None
     names = _u.check_outputs(outputs)
     _check_stage_bytes(stage_bytes)
     x = np.ascontiguousarray(values).reshape(K, shape[0], shape[1])
-    kinds = dict(mean=dtype, fraction=dtype, count=np.dtype(np.int32))
-    outs = {k: np.empty((K, H, W), kinds[k]) for k in names}
+    outs = _named_outputs(None, _u.output_table(names, (H, W) if squeeze else (K, H, W), dtype))
     grid = _lib.Upscale(_lib.context(device), fine, (H, W), wrap=wrap, area=area, runs=(row_runs, col_runs))
     try:
         grid.run(dtype, x.ctypes.data, K, shape[0] * shape[1], shape[1], min_fraction,
@@ -759,8 +740,7 @@ def upscale_fields(values, coarse_shape, row_pos, col_pos, wrap=False, area=None
                  stage_bytes=stage_bytes)
     finally:
         grid.close()
-    res = (H, W) if squeeze else (K, H, W)
-    return _u.Upscaled(*[outs[k].reshape(res) if k in outs else None for k in _u.OUTPUT_NAMES])
+    return _u.Upscaled(*[outs.get(k) for k in _u.OUTPUT_NAMES])
 
 
 def upscale_classes(cls, coarse_shape, row_pos, col_pos, wrap=False, valid=None, outputs=('cls',), device=0,
@@ -796,8 +776,7 @@ def upscale_classes(cls, coarse_shape, row_pos, col_pos, wrap=False, valid=None,
     names = _u.check_class_outputs(outputs)
     _check_stage_bytes(stage_bytes)
     c = np.ascontiguousarray(c)
-    kinds = dict(cls=np.uint8, share=np.float32)
-    outs = {k: np.empty((H, W), kinds[k]) for k in names}
+    outs = _named_outputs(None, _u.output_table(names, (H, W)))
     grid = _lib.Upscale(_lib.context(device), fine, (H, W), wrap=wrap, runs=(row_runs, col_runs))
     try:
         grid.classes(c.ctypes.data, fine[1], mask, *[(outs[k].ctypes.data, W) if k in outs else None for k in _u.CLASS_OUTPUT_NAMES],
@@ -867,9 +846,7 @@ def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=Non
         raise ValueError('between 1 and %d layers, got %d' % (_z.MAX_LAYERS, K))
     if nzones is None:
         nzones = max(int(zones.max()) + 1, 1) if n else 1
-    if isinstance(nzones, (bool, np.bool_)) or not isinstance(nzones, (int, np.integer)) or not 1 <= nzones <= _z.MAX_ZONES:
-        raise ValueError('nzones must be an integer between 1 and 2**24, got %r' % (nzones,))
-    nzones = int(nzones)
+    nzones = _z.check_nzones(nzones)
     if zones.dtype.name not in _z.ZONE_TYPES:
         if n and (int(zones.min()) < -2 ** 31 or int(zones.max()) >= 2 ** 31):
             raise ValueError('zone ids must fit an int32')
@@ -895,8 +872,7 @@ def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=Non
     if acc is not None:
         if not isinstance(acc, _z.ZonalResult):
             raise ValueError('acc must be a ZonalResult')
-        if not explicit:
-            raise ValueError('acc= needs explicit bounds: their exponents are the scale of the accumulator')
+        _z.check_acc_bounds(bounds)
         if acc.words.shape != (K, nzones, _z.NWORDS):
             raise ValueError('acc holds %r words, this call needs %r' % (acc.words.shape, (K, nzones, _z.NWORDS)))
     if explicit:

@@ -239,27 +239,6 @@ class UpscaleGrid(object):
         self.shape, self.coarse_shape = self._grid.shape, self._grid.coarse_shape
         self.row_runs, self.col_runs, self.wrap = self._grid.row_runs, self._grid.col_runs, self._grid.wrap
 
-    def _outputs(self, names, kinds, out, lead):
-        '''The output tensors by name -- new ones, or the caller's ``out`` dict after its checks -- and per
-        name ``(address, plane stride, row pitch)``.'''
-        eng, torch = self.engine, _torch()
-        shape = lead + self.coarse_shape
-        if out is None:
-            outs = {k: torch.empty(shape, dtype=kinds[k], device=eng._dev()) for k in names}
-        else:
-            outs = dict(out)
-            if sorted(outs) != sorted(names):
-                raise ValueError('out must hold exactly the fields produced: %s' % ', '.join(names))
-        layout = {}
-        for k in names:
-            what = "out['%s']" % k
-            _t.check_device(outs[k], what, eng.device, kinds[k])
-            if tuple(outs[k].shape) != shape:
-                raise ValueError('%s must have shape %r, got %r' % (what, shape, tuple(outs[k].shape)))
-            pitch, plane = _t.plane_layout(outs[k], what)
-            layout[k] = (outs[k].data_ptr(), plane, pitch)
-        return outs, layout
-
     def run(self, values, min_fraction=0.0, outputs=('mean',), out=None):
         '''Enqueue the upscaling kernel on the current stream (``mod16_upscale_*``; the definition is
         ``mod16_amd.upscale.aggregate``, which the result equals bit for bit). ``values`` is a ``(K, R,
@@ -277,12 +256,13 @@ class UpscaleGrid(object):
         min_fraction = _u.check_min_fraction(min_fraction)
         names = _u.check_outputs(outputs)
         pitch, plane = _t.plane_layout(values, 'values')
-        kinds = dict(mean=values.dtype, fraction=values.dtype, count=torch.int32)
-        outs, layout = self._outputs(names, kinds, out, () if squeeze else (K,))
-        dtype = np.dtype('float32' if values.dtype == torch.float32 else 'float64')
-        try:
+        dtype = _t.numpy_dtype(values.dtype)
+        outs, lay = _t.named_outputs(out, _u.output_table(names, (() if squeeze else (K,)) + self.coarse_shape, dtype),
+                                     eng.device)
+        try:                       # (per output: address, plane stride, row pitch)
             self._grid.run(dtype, values.data_ptr(), K, plane, pitch, min_fraction,
-                           [layout.get(k) for k in _u.OUTPUT_NAMES], where=_lib.DEVICE, stream=eng._stream())
+                           [(outs[k].data_ptr(), lay[k][1], lay[k][0]) if k in outs else None for k in _u.OUTPUT_NAMES],
+                           where=_lib.DEVICE, stream=eng._stream())
         except _lib.Mod16Error as e:
             raise _lib.overlap_as_value_error(e)
         return _u.Upscaled(*[outs.get(k) for k in _u.OUTPUT_NAMES])
@@ -301,8 +281,8 @@ class UpscaleGrid(object):
         mask = _u.valid_mask(valid)
         names = _u.check_class_outputs(outputs)
         pitch, _ = _t.plane_layout(cls, 'cls')
-        outs, layout = self._outputs(names, dict(cls=torch.uint8, share=torch.float32), out, ())
-        pair = {k: (v[0], v[2]) for k, v in layout.items()}
+        outs, lay = _t.named_outputs(out, _u.output_table(names, self.coarse_shape), eng.device)
+        pair = {k: (outs[k].data_ptr(), lay[k][0]) for k in outs}
         try:
             self._grid.classes(cls.data_ptr(), pitch, mask, pair.get('cls'), pair.get('share'), where=_lib.DEVICE,
                                stream=eng._stream())
@@ -521,9 +501,9 @@ class RasterEngine(object):
         self.ctx = _lib.Context(self.device, experiments=experiments)
         self.ctx.set_bplut(table)
         self.np_dtype = np.dtype(dtype)
-        self.dtype = {'float64': torch.float64, 'float32': torch.float32}[self.np_dtype.name]
+        self.bytes_per_pixel = BYTES_PER_PIXEL[self.np_dtype.name]       # (float32 or float64: KeyError otherwise)
+        self.dtype = _t.torch_dtype(self.np_dtype)
         self.math = int(math) | (_lib.DOMAIN_TRUSTED if trusted else 0)
-        self.bytes_per_pixel = BYTES_PER_PIXEL[self.np_dtype.name]
 
     def _gate(self):
         '''A zero-work dispatch on the compute stream in front of a step of the series runners.
@@ -754,20 +734,10 @@ class RasterEngine(object):
     def _composite_outputs(self, out, P, n, pet):
         '''The 2 (``pet``: 4) ``(P, n)`` result tensors of a composite call -- new ones, or the caller's
         ``out`` after a check -- and their common distance between rows.'''
-        torch = _torch()
-        want = 4 if pet else 2
-        if out is None:
-            out = [torch.empty((P, n), dtype=self.dtype, device=self._dev()) for _ in range(want // 2)] + \
-                  [torch.empty((P, n), dtype=torch.uint16, device=self._dev()) for _ in range(want // 2)]
-        out = tuple(out)
-        if len(out) != want:
-            raise ValueError('out must hold %d tensors' % want)
-        for k, o in enumerate(out):
-            _t.check_device(o, 'out[%d]' % k, self.device, self.dtype if k < want // 2 else torch.uint16)
-            if tuple(o.shape) != (P, n):
-                raise ValueError('out[%d] must have shape (%d, %d)' % (k, P, n))
-        rows = [_t.row_pitch(o, 'out[%d]' % k) for k, o in enumerate(out)]
-        return out, _t.share_one(rows, 'the out tensors', 'distance between rows')
+        totals = 2 if pet else 1
+        table = {k: ((P, n), self.np_dtype if k < totals else np.dtype(np.uint16)) for k in range(2 * totals)}
+        outs, rows = _t.named_outputs(out, table, self.device, 'distance between rows')
+        return tuple(outs.values()), _t.share_one(rows.values(), 'the out tensors', 'distance between rows')
 
     def downscale_grid(self, shape, coarse_shape, row_pos, col_pos=None, wrap=False, method='bilinear',
                        col_affine=None):
@@ -842,28 +812,23 @@ class RasterEngine(object):
         if len(shape) != 1:
             raise ValueError('fields must be (S, n) tensors, got %r' % (tuple(flds[0].shape),))
         n = shape[0]
-        tdtype = {'uint8': torch.uint8, 'float32': torch.float32, 'float64': torch.float64}[name]
         in_pitch = _t.share_one([_t.row_pitch(f, 'fields[%d]' % k, 'stride in time') for k, f in enumerate(flds)],
                                 'the fields', 'stride in time')
         qc_pitch = _t.row_pitch(qc, 'qc', 'stride in time') if qc is not None else n
         for k, f in enumerate(fallback or []):
             if f is not None:
                 _t.row_pitch(f, 'fallback[%d]' % k)
-        want = len(flds) + (1 if source else 0)
         if out is None:
-            outs = [torch.empty((S, n), dtype=tdtype, device=self._dev()) for _ in flds]
             src = torch.empty((len(flds), S, n), dtype=torch.uint8, device=self._dev()) if source else None
-        else:
-            outs = [out] if isinstance(out, torch.Tensor) else list(out)
-            if len(outs) != want:
-                raise ValueError('out must hold %d tensors' % want)
-            src = outs.pop() if source else None
-        for k, o in enumerate(outs):
-            _t.check_device(o, 'out[%d]' % k, self.device, tdtype)
-            if tuple(o.shape) != (S, n):
-                raise ValueError('out[%d] must have shape (%d, %d)' % (k, S, n))
-        out_pitch = _t.share_one([_t.row_pitch(o, 'out[%d]' % k, 'stride in time') for k, o in enumerate(outs)],
-                                 'the out tensors', 'distance between rows')
+        else:                      # (the source tensor comes behind the filled ones)
+            out = [out] if isinstance(out, torch.Tensor) else list(out)
+            if len(out) != len(flds) + (1 if source else 0):
+                raise ValueError('out must hold %d tensors' % (len(flds) + (1 if source else 0)))
+            src = out.pop() if source else None
+        outs, rows = _t.named_outputs(out, {k: ((S, n), np.dtype(name)) for k in range(len(flds))}, self.device,
+                                      'stride in time')
+        outs = list(outs.values())
+        out_pitch = _t.share_one(rows.values(), 'the out tensors', 'distance between rows')
         src_pitch = n
         if src is not None:
             _t.check_device(src, 'source', self.device, torch.uint8)
@@ -922,28 +887,13 @@ class RasterEngine(object):
         in_types = set(t.dtype for t in flds.values())
         if len(in_types) != 1:
             raise ValueError('fields must be all float32 or all float64')
-        in_dtype = np.dtype('float32' if in_types.pop() == torch.float32 else 'float64')
+        in_dtype = _t.numpy_dtype(in_types.pop())
         out_dtype = _dn.check_out_dtype(self.np_dtype if dtype is None else dtype, in_dtype)
-        tdtype = {'float32': torch.float32, 'float64': torch.float64}[out_dtype.name]
         both = 'distance between rows and one stride in time'
         in_pitch, in_plane = _t.share_one([_t.plane_layout(t, "fields['%s']" % k) for k, t in flds.items()],
                                           'the fields', both)
-        series = [n for n in names if n != 'temp_annual']
-        if out is None:
-            outs = {n: torch.empty((D, R, W), dtype=tdtype, device=self._dev()) for n in series}
-            if 'temp_annual' in names:
-                outs['temp_annual'] = torch.empty((R, W), dtype=tdtype, device=self._dev())
-        else:
-            outs = dict(out)
-            if sorted(outs) != sorted(names):
-                raise ValueError('out must hold exactly the requested outputs: %s' % ', '.join(names))
-        lay = {}
-        for n in names:
-            o, shape = outs[n], ((R, W) if n == 'temp_annual' else (D, R, W))
-            _t.check_device(o, "out['%s']" % n, self.device, tdtype)
-            if tuple(o.shape) != shape:
-                raise ValueError("out['%s'] must have shape %r" % (n, shape))
-            lay[n] = _t.plane_layout(o, "out['%s']" % n)
+        outs, lay = _t.named_outputs(out, _dn.output_table(names, D, R, W, out_dtype), self.device,
+                                     called='requested outputs')
         out_pitch = _t.share_one([p for p, _ in lay.values()], 'the out tensors', both)
         out_plane = _t.share_one([q for n, (_, q) in lay.items() if n != 'temp_annual' and D > 1],
                                  'the out tensors', both)
@@ -988,27 +938,14 @@ class RasterEngine(object):
         Y, shape, t, min_valid, zq = _tr.check_call(tuple(values.shape), times, min_valid, alpha)
         n = shape[0]
         stride = _t.row_pitch(values, 'values', 'stride in time')
-        names = [k for k in _tr.Trend._fields if zq or k not in ('slope_lo', 'slope_hi')]
-        kinds = {k: torch.float64 for k in _tr.FLOAT_NAMES}
-        kinds.update(s=torch.int32, count=torch.uint8)
-        if out is None:
-            outs = {k: torch.empty((n,), dtype=kinds[k], device=self._dev()) for k in names}
-        else:
-            outs = dict(out)
-            if sorted(outs) != sorted(names):
-                raise ValueError('out must hold exactly the fields produced: %s' % ', '.join(names))
-        for k in names:
-            _t.check_device(outs[k], "out['%s']" % k, self.device, kinds[k])
-            if tuple(outs[k].shape) != (n,):
-                raise ValueError("out['%s'] must have shape (%d,)" % (k, n))
-            _t.row_pitch(outs[k], "out['%s']" % k)
+        outs, _ = _t.named_outputs(out, _tr.output_table(shape, zq), self.device, 'distance between rows')
         if n:
-            dtype = np.dtype('float32' if values.dtype == torch.float32 else 'float64')
             try:
                 self.ctx.trend(
-                    dtype, n, Y, values.data_ptr(), t, [outs[k].data_ptr() if k in outs else None for k in _tr.FLOAT_NAMES],
-                    outs['s'].data_ptr(), outs['count'].data_ptr(), time_stride=stride, min_valid=min_valid, zq=zq,
-                    where=_lib.DEVICE, stream=self._stream())
+                    _t.numpy_dtype(values.dtype), n, Y, values.data_ptr(), t,
+                    [outs[k].data_ptr() if k in outs else None for k in _tr.FLOAT_NAMES], outs['s'].data_ptr(),
+                    outs['count'].data_ptr(), time_stride=stride, min_valid=min_valid, zq=zq, where=_lib.DEVICE,
+                    stream=self._stream())
             except _lib.Mod16Error as e:
                 raise _lib.overlap_as_value_error(e)
         return _tr.Trend(*[outs.get(k) for k in _tr.Trend._fields])
@@ -1037,36 +974,20 @@ class RasterEngine(object):
         _t.check_device(num, 'num', self.device, torch.float32, torch.float64)
         if num.dim() != 2:
             raise ValueError('num must be an (S, n) tensor, got %r' % (tuple(num.shape),))
-        if periods is None:
-            raise ValueError('periods must be given')
         Y, P, shape, W, (y0, y1), min_valid = _an.check_call(tuple(num.shape), periods, window, baseline, min_valid)
         names = _an.check_outputs(outputs)
         S, n = Y * P, shape[0]
         in_stride = _t.row_pitch(num, 'num', 'stride in time')
         if den is not None:
             _t.check_device(den, 'den', self.device, num.dtype)
-            if tuple(den.shape) != (S, n):
-                raise ValueError('den must have the shape of num %r, got %r' % ((S, n), tuple(den.shape)))
+            _an.check_den_shape((S, n), den.shape)
             in_stride = _t.share_one([in_stride, _t.row_pitch(den, 'den', 'stride in time')], 'num and den', 'stride in time')
-        kinds = dict(z=num.dtype, pct=num.dtype, mean=torch.float64, std=torch.float64, count=torch.uint8)
-        rows = dict(z=S, pct=S, mean=P, std=P, count=P)
-        if out is None:
-            outs = {k: torch.empty((rows[k], n), dtype=kinds[k], device=self._dev()) for k in names}
-        else:
-            outs = dict(out)
-            if sorted(outs) != sorted(names):
-                raise ValueError('out must hold exactly the fields produced: %s' % ', '.join(names))
-        pitch = {}
-        for k in names:
-            _t.check_device(outs[k], "out['%s']" % k, self.device, kinds[k])
-            if tuple(outs[k].shape) != (rows[k], n):
-                raise ValueError("out['%s'] must have shape (%d, %d)" % (k, rows[k], n))
-            pitch[k] = _t.row_pitch(outs[k], "out['%s']" % k, 'stride in time')
+        dtype = _t.numpy_dtype(num.dtype)
+        outs, pitch = _t.named_outputs(out, _an.output_table(names, S, P, shape, dtype), self.device, 'stride in time')
         out_stride = _t.share_one([pitch[k] for k in names if k in ('z', 'pct')], "out['z'] and out['pct']", 'stride in time')
         clim_stride = _t.share_one([pitch[k] for k in names if k not in ('z', 'pct')],
                                    "out['mean'], out['std'] and out['count']", 'stride between periods')
         if n:
-            dtype = np.dtype('float32' if num.dtype == torch.float32 else 'float64')
             try:
                 self.ctx.anomaly(
                     dtype, n, Y, P, num.data_ptr(), None if den is None else den.data_ptr(),
@@ -1139,12 +1060,9 @@ class RasterEngine(object):
         from . import zonal as _z
         torch = _torch()
         K, n, pitch, kind, wptr, cols, first_pixel = self._zonal_args(values, zones, area, cols, first_pixel)
-        if isinstance(nzones, bool) or not isinstance(nzones, (int, np.integer)) or not 1 <= nzones <= _z.MAX_ZONES:
-            raise ValueError('nzones must be an integer between 1 and 2**24, got %r' % (nzones,))
-        nzones = int(nzones)
+        nzones = _z.check_nzones(nzones)
         if acc is not None:
-            if bounds is None:
-                raise ValueError('acc= needs explicit bounds: their exponents are the scale of the accumulator')
+            _z.check_acc_bounds(bounds)
             _t.check_device(acc, 'acc', self.device, torch.int64)
             if tuple(acc.shape) != (K, nzones, _z.NWORDS):
                 raise ValueError('acc must have shape %r, got %r' % ((K, nzones, _z.NWORDS), tuple(acc.shape)))

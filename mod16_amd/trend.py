@@ -70,6 +70,15 @@ def check_call(shape, times=None, min_valid=4, alpha=None):
     return Y, shape[1:], t, int(min_valid), zq
 
 
+def output_table(shape, zq):
+    '''What a call produces, in the order of ``Trend``: name -> ``(shape, numpy dtype)``, every field
+    of the pixel ``shape``; float64 but for ``s`` (int32) and ``count`` (uint8); no ``slope_lo`` /
+    ``slope_hi`` where ``zq`` is 0.0 (no ``alpha``).'''
+    kinds = dict(s=np.int32, count=np.uint8)
+    return {k: (tuple(shape), np.dtype(kinds.get(k, np.float64))) for k in Trend._fields
+            if zq or k not in ('slope_lo', 'slope_hi')}
+
+
 def check_dtype(dtype):
     '''-> the numpy dtype of ``values``: float32 or float64, nothing else.'''
     dtype = np.dtype(dtype)
@@ -125,11 +134,8 @@ def trend(values, times=None, min_valid=4, alpha=None):
     Y, shape, t, min_valid, zq = check_call(values.shape, times, min_valid, alpha)
     n = int(np.prod(shape, dtype=np.int64))
     x = values.reshape(Y, n).astype(np.float64)
-    f = np.empty((5, n), np.float64)
-    s = np.empty(n, np.int32)
-    count = np.empty(n, np.uint8)
+    res = {k: np.empty(n, dt) for k, (_, dt) in output_table((n,), 1.0).items()}
     for i in range(n):
-        f[0, i], f[1, i], f[2, i], f[3, i], s[i], f[4, i], count[i] = pixel_trend(x[:, i], t, min_valid, zq)
-    out = [f[k].reshape(shape) for k in range(5)]
-    return Trend(out[0], out[1], out[2] if zq else None, out[3] if zq else None, s.reshape(shape), out[4],
-                 count.reshape(shape))
+        for k, v in zip(Trend._fields, pixel_trend(x[:, i], t, min_valid, zq)):
+            res[k][i] = v
+    return Trend(*[res[k].reshape(shape) if k in output_table(shape, zq) else None for k in Trend._fields])

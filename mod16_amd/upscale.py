@@ -225,6 +225,13 @@ def check_class_outputs(outputs):
     return _names(outputs, CLASS_OUTPUT_NAMES)
 
 
+def output_table(names, shape, dtype=None):
+    '''What ``aggregate`` or ``majority`` produces, in the order of ``OUTPUT_NAMES`` / ``CLASS_OUTPUT_NAMES``:
+    name -> ``(shape, numpy dtype)`` for the requested ``names``; ``dtype`` is that of ``values``.'''
+    kinds = dict(mean=dtype, fraction=dtype, count=np.int32, cls=np.uint8, share=np.float32)
+    return {k: (tuple(shape), np.dtype(kinds[k])) for k in OUTPUT_NAMES + CLASS_OUTPUT_NAMES if k in names}
+
+
 def valid_mask(valid=None):
     '''A set of class codes in ``[0, 32)`` (None: the 13 classes of the parameter table) -> the 32-bit
     mask ``mod16_upscale_classes`` takes.'''
@@ -282,10 +289,9 @@ def aggregate(values, row_runs, col_runs, area=None, min_fraction=0.0, outputs=O
             cnt += np.where(on, m, 0)
         fraction = np.where(tot > 0, den / tot, 0.0)
         mean = np.where((cnt >= 1) & (den >= min_fraction * tot), num / den, np.nan)
-    shape = (H, W) if squeeze else (K, H, W)
-    res = dict(mean=mean.astype(dtype).reshape(shape), fraction=fraction.astype(dtype).reshape(shape),
-               count=cnt.astype(np.int32).reshape(shape))
-    return Upscaled(*[res[k] if k in names else None for k in OUTPUT_NAMES])
+    res = dict(mean=mean, fraction=fraction, count=cnt)
+    table = output_table(names, (H, W) if squeeze else (K, H, W), dtype)
+    return Upscaled(*[res[k].astype(table[k][1]).reshape(table[k][0]) if k in table else None for k in OUTPUT_NAMES])
 
 
 def majority(cls, row_runs, col_runs, valid=None, outputs=CLASS_OUTPUT_NAMES, wrap=False):

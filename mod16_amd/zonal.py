@@ -78,6 +78,19 @@ def check_bounds(bounds):
     return wmax, xmax, ew, ex
 
 
+def check_nzones(nzones):
+    '''-> ``nzones`` as an int; ValueError unless it is an integer (no bool) in ``[1, MAX_ZONES]``.'''
+    if isinstance(nzones, (bool, np.bool_)) or not isinstance(nzones, (int, np.integer)) or not 1 <= nzones <= MAX_ZONES:
+        raise ValueError('nzones must be an integer between 1 and 2**24, got %r' % (nzones,))
+    return int(nzones)
+
+
+def check_acc_bounds(bounds):
+    '''A call that adds into ``acc=`` cannot find its own bounds: ValueError where ``bounds`` is None.'''
+    if bounds is None:
+        raise ValueError('acc= needs explicit bounds: their exponents are the scale of the accumulator')
+
+
 def key(x):
     '''The order-preserving int64 image of float64 values: the bits, with the low 63 bits flipped
     where the sign bit is set (so ``key(-0.0) < key(+0.0)``).'''

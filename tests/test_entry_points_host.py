@@ -1,9 +1,10 @@
-"""What the eight numpy entry points hand to the library, and what they refuse, without a GPU and
-without the library: `_lib.context`, `_lib.load`, `_lib.Ensemble` and `_lib.Downscale` are replaced
-by stand-ins that record their calls (and read what the addresses point at while the call's arrays
-are alive). The argument handling of `evapotranspiration_raster`, `_ensemble`,
-`_ensemble_quantiles`, `_composite`, `_downscaled`, `_raw`, `gapfill_series` and `zonal_statistics`
-is pinned here: strides and kinds, `n`, `inner`, flags and `where`, addresses relative to the arrays
+"""What the numpy entry points hand to the library, and what they refuse, without a GPU and without
+the library: `_lib.context`, `_lib.load`, `_lib.Ensemble`, `_lib.Downscale` and `_lib.Upscale` are
+replaced by stand-ins that record their calls (and read what the addresses point at while the call's
+arrays are alive). The argument handling of `evapotranspiration_raster`, `_ensemble`,
+`_ensemble_quantiles`, `_composite`, `_downscaled`, `_raw`, `gapfill_series`, `zonal_statistics`,
+`aggregate_daynight`, `trend_series`, `anomaly_series`, `upscale_fields` and `upscale_classes` is
+pinned here: strides and kinds, `n`, `inner`, flags and `where`, addresses relative to the arrays
 they must point into, output dtype / shape / return type, `set_bplut` before the call, the dealing
 of pixel ranges over `devices=`, and the exact refusals with the order in which they fire."""
 import ctypes as C
@@ -149,6 +150,48 @@ class Ctx(object):
                      weight_kind=weight_kind, cols=cols, where=where, stage_bytes=stage_bytes)
         return 2.0, 3.0
 
+    def daynight(self, dtype, out_type, rows, cols, days, steps_per_day, fields, tables, out, temp_annual, in_pitch,
+                 in_plane, out_pitch, out_plane, mode=0, threshold=0.0, where=_lib.HOST, stream=None, stage_bytes=None):
+        self.rec.log('daynight', dtype=np.dtype(dtype), out_type=out_type, grid=(rows, cols, days, steps_per_day),
+                     fields=list(fields), tables=tables, out=list(out), temp_annual=temp_annual,
+                     pitches=(in_pitch, in_plane, out_pitch, out_plane), mode=mode, threshold=threshold, where=where,
+                     stream=stream, stage_bytes=stage_bytes)
+
+    def trend(self, dtype, n, steps, values, times, out, s, count, time_stride=None, min_valid=4, zq=0.0,
+              where=_lib.HOST, stream=None, stage_bytes=None):
+        self.rec.log('trend', dtype=np.dtype(dtype), n=n, steps=steps, values=values, times=[float(v) for v in times],
+                     out=list(out), s=s, count=count, time_stride=time_stride, min_valid=min_valid, zq=zq, where=where,
+                     stream=stream, stage_bytes=stage_bytes)
+
+    def anomaly(self, dtype, n, years, periods, num, den, z, pct, mean, std, count, window=1, base_first=0,
+                base_end=None, min_valid=3, in_stride=None, out_stride=None, clim_stride=None, where=_lib.HOST,
+                stream=None, stage_bytes=None):
+        self.rec.log('anomaly', dtype=np.dtype(dtype), n=n, years=years, periods=periods, num=num, den=den,
+                     out=[z, pct, mean, std, count], window=window, baseline=(base_first, base_end),
+                     min_valid=min_valid, strides=(in_stride, out_stride, clim_stride), where=where, stream=stream,
+                     stage_bytes=stage_bytes)
+
+
+class Upscale(object):
+    def __init__(self, ctx, shape, coarse_shape, row_pos=None, col_pos=None, wrap=False, area=None, runs=None,
+                 col_affine=None):
+        self.ctx, self.pixels = ctx, int(shape[0]) * int(shape[1])
+        ctx.rec.log('cells', device=ctx.device, shape=tuple(shape), coarse_shape=tuple(coarse_shape), row_pos=row_pos,
+                    col_pos=col_pos, wrap=wrap, area=area, runs=runs, col_affine=col_affine)
+
+    def run(self, dtype, values, layers, layer_stride, row_stride, min_fraction, outs, where=_lib.HOST, stream=None,
+            stage_bytes=None):
+        self.ctx.rec.log('run', dtype=np.dtype(dtype), values=values, layers=layers, strides=(layer_stride, row_stride),
+                         min_fraction=min_fraction, outs=list(outs), where=where, stream=stream,
+                         stage_bytes=stage_bytes)
+
+    def classes(self, cls, row_stride, valid, out_cls, out_share, where=_lib.HOST, stream=None, stage_bytes=None):
+        self.ctx.rec.log('classes', cls=cls, cls_bytes=_bytes(cls, self.pixels), row_stride=row_stride, valid=valid, out=(out_cls, out_share), where=where,
+                         stream=stream, stage_bytes=stage_bytes)
+
+    def close(self):
+        self.ctx.rec.log('close')
+
 
 class Ensemble(object):
     def __init__(self, ctx, tables):
@@ -195,6 +238,7 @@ def rec(monkeypatch):
     monkeypatch.setattr(_lib, 'load', lambda: Lib(r))
     monkeypatch.setattr(_lib, 'Ensemble', Ensemble)
     monkeypatch.setattr(_lib, 'Downscale', Downscale)
+    monkeypatch.setattr(_lib, 'Upscale', Upscale)
     yield r
     multi.shutdown()
 
@@ -204,7 +248,7 @@ def no_library(monkeypatch):
     '''A refusal must come before anything of the library is asked for.'''
     def never(*a, **kw):
         raise AssertionError('the library was asked for')
-    for name in ('context', 'load', 'Ensemble', 'Downscale'):
+    for name in ('context', 'load', 'Ensemble', 'Downscale', 'Upscale'):
         monkeypatch.setattr(_lib, name, never)
 
 
@@ -632,6 +676,179 @@ def test_zonal_statistics_finds_its_bounds_then_accumulates(rec):
     assert (seen['weight_kind'], seen['cols'], seen['stage_bytes']) == (_lib.ZONAL_WEIGHT_NONE, 1, None)
 
 
+# ------------------------------------------------------------------ day / night, trend, anomaly, upscaling
+DN_DAYS, DN_STEPS = 2, 2
+
+
+def daynight_case(dtype=np.float32):
+    '''(fields 't' and 'sw' of (D H,) + SHAPE, the three solar tables)'''
+    from mod16_amd import daynight as dn
+    steps = DN_DAYS * DN_STEPS
+    fields = {'t': 280.0 + np.arange(steps * N, dtype=dtype).reshape((steps,) + SHAPE),
+              'sw': 10.0 * np.arange(steps * N, dtype=dtype).reshape((steps,) + SHAPE), 'qv': None}
+    return fields, dn.solar_tables(np.arange(1, DN_DAYS + 1), np.array([30.0, -30.0]), np.array([-90.0, 0.0, 90.0]))
+
+
+def test_aggregate_daynight_allocates_by_name_or_writes_into_the_callers_arrays(rec):
+    from mod16_amd import daynight as dn
+    R, W = SHAPE
+    fields, (half, noon, offset) = daynight_case()
+    got, annual = mod16_amd.aggregate_daynight(fields, half, noon, offset, steps_per_day=DN_STEPS, device=1,
+                                               stage_bytes=1 << 16)
+    produced = ('sw_rad_day', 'temp_day', 'temp_night', 'tmin', 'day_hours', 'temp_mean')
+    assert type(got) is dn.DayNight and type(annual) is np.ndarray
+    for name in dn.OUTPUT_NAMES:
+        o = getattr(got, name)
+        assert (o is None) == (name not in produced), name
+        assert o is None or (type(o) is np.ndarray and o.shape == (DN_DAYS,) + SHAPE and o.dtype == np.float32)
+    assert annual.shape == SHAPE and annual.dtype == np.float32
+    (name, seen), = rec.take()[None]
+    assert name == 'daynight' and seen['dtype'] == np.float32 and seen['out_type'] == dn.OUT_TYPES['float32']
+    assert seen['grid'] == (R, W, DN_DAYS, DN_STEPS)
+    assert seen['fields'] == [fields['t'].ctypes.data, None, None, fields['sw'].ctypes.data, None]     # t, qv, ps, sw, lw
+    assert all(same(t, want) and t.dtype == np.float64 for t, want in zip(seen['tables'], (half, noon, offset)))
+    assert seen['out'] == [None if getattr(got, k) is None else getattr(got, k).ctypes.data for k in dn.OUTPUT_NAMES]
+    assert seen['temp_annual'] == annual.ctypes.data
+    assert seen['pitches'] == (W, R * W, W, R * W)
+    assert (seen['mode'], seen['threshold'], seen['where'], seen['stream'], seen['stage_bytes']) == \
+        (dn.MODES['solar'], 0.0, _lib.HOST, None, 1 << 16)
+    # the caller's arrays by name, float64 out of float32 fields, a threshold on sw in place of the tables
+    out = {'tmin': np.empty((DN_DAYS,) + SHAPE), 'temp_annual': np.empty(SHAPE)}
+    got, annual = mod16_amd.aggregate_daynight(fields, sw_threshold=25.0, steps_per_day=DN_STEPS, dtype='float64',
+                                               outputs=('temp_annual', 'tmin'), out=out)
+    assert got.tmin is out['tmin'] and annual is out['temp_annual']
+    assert [k for k in dn.OUTPUT_NAMES if getattr(got, k) is not None] == ['tmin']
+    (name, seen), = rec.take()[None]
+    assert seen['dtype'] == np.float32 and seen['out_type'] == dn.OUT_TYPES['float64'] and seen['tables'] is None
+    assert seen['out'] == [out['tmin'].ctypes.data if k == 'tmin' else None for k in dn.OUTPUT_NAMES]
+    assert seen['temp_annual'] == out['temp_annual'].ctypes.data
+    assert (seen['mode'], seen['threshold'], seen['stage_bytes']) == (dn.MODES['sw'], 25.0, None)
+    # no cells: the shapes, and nothing of the library
+    empty = {'t': np.empty((DN_DAYS * DN_STEPS, 0, 3), np.float32)}
+    got, annual = mod16_amd.aggregate_daynight(empty, sw_threshold=None, half_day=np.empty((DN_DAYS, 0)), offset=offset,
+                                               steps_per_day=DN_STEPS, outputs=('tmin', 'temp_annual'))
+    assert got.tmin.shape == (DN_DAYS, 0, 3) and annual.shape == (0, 3) and rec.take() == {}
+
+
+def test_trend_series_flattens_the_pixels(rec):
+    import statistics
+    from mod16_amd import trend as tr
+    Y = 4
+    values = np.arange(Y * N, dtype=np.float32).reshape((Y,) + SHAPE)
+    got = mod16_amd.trend_series(values, times=[0, 1, 2, 4], min_valid=3, alpha=0.1, device=1, stage_bytes=1 << 16)
+    assert type(got) is tr.Trend
+    assert [o.dtype for o in got] == [np.float64] * 4 + [np.int32, np.float64, np.uint8]
+    assert all(type(o) is np.ndarray and o.shape == SHAPE for o in got)
+    (name, seen), = rec.take()[None]
+    assert name == 'trend' and (seen['dtype'], seen['n'], seen['steps']) == (np.float32, N, Y)
+    assert seen['values'] == values.ctypes.data and seen['times'] == [0.0, 1.0, 2.0, 4.0]
+    assert seen['out'] == [getattr(got, k).ctypes.data for k in tr.FLOAT_NAMES]
+    assert (seen['s'], seen['count']) == (got.s.ctypes.data, got.count.ctypes.data)
+    assert (seen['time_stride'], seen['min_valid'], seen['zq']) == (N, 3, statistics.NormalDist().inv_cdf(0.95))
+    assert (seen['where'], seen['stream'], seen['stage_bytes']) == (_lib.HOST, None, 1 << 16)
+    # without alpha: no interval, and no address for it; float64, the default times
+    got = mod16_amd.trend_series(values.astype(np.float64))
+    assert got.slope_lo is None and got.slope_hi is None and got.z.shape == SHAPE
+    (name, seen), = rec.take()[None]
+    assert seen['dtype'] == np.float64 and seen['times'] == [0.0, 1.0, 2.0, 3.0]
+    assert seen['out'] == [got.slope.ctypes.data, got.intercept.ctypes.data, None, None, got.z.ctypes.data]
+    assert (seen['min_valid'], seen['zq'], seen['stage_bytes']) == (4, 0.0, None)
+    # no pixels: the shapes and dtypes, and nothing of the library
+    got = mod16_amd.trend_series(np.empty((Y, 0, 3), np.float32), alpha=0.1)
+    assert all(o.shape == (0, 3) for o in got) and got.s.dtype == np.int32 and got.count.dtype == np.uint8
+    assert rec.take() == {}
+
+
+def test_anomaly_series_lays_out_the_record_and_the_climatology(rec):
+    from mod16_amd import anomaly as an
+    Y, P = 3, 2
+    num = np.arange(Y * P * N, dtype=np.float32).reshape((Y * P,) + SHAPE)
+    den = num + 1
+    got = mod16_amd.anomaly_series(num, den, periods=P, window=2, baseline=(0, 2), min_valid=2, outputs=an.OUTPUT_NAMES,
+                                   device=1, stage_bytes=1 << 16)
+    assert type(got) is an.Anomaly and all(type(o) is np.ndarray for o in got)
+    assert [o.dtype for o in got] == [np.float32, np.float32, np.float64, np.float64, np.uint8]
+    assert [o.shape for o in got] == [(Y * P,) + SHAPE] * 2 + [(P,) + SHAPE] * 3
+    (name, seen), = rec.take()[None]
+    assert name == 'anomaly' and (seen['dtype'], seen['n'], seen['years'], seen['periods']) == (np.float32, N, Y, P)
+    assert (seen['num'], seen['den']) == (num.ctypes.data, den.ctypes.data)
+    assert seen['out'] == [o.ctypes.data for o in got]
+    assert (seen['window'], seen['baseline'], seen['min_valid']) == (2, (0, 2), 2)
+    assert seen['strides'] == (None, None, None)                          # dense: the library's default
+    assert (seen['where'], seen['stream'], seen['stage_bytes']) == (_lib.HOST, None, 1 << 16)
+    # the defaults: z alone, no denominator, every year in the baseline; float64
+    got = mod16_amd.anomaly_series(num.astype(np.float64), periods=P)
+    assert got.z.dtype == np.float64 and got.z.shape == (Y * P,) + SHAPE and list(got[1:]) == [None] * 4
+    (name, seen), = rec.take()[None]
+    assert seen['dtype'] == np.float64 and seen['den'] is None and seen['out'] == [got.z.ctypes.data] + [None] * 4
+    assert (seen['window'], seen['baseline'], seen['min_valid'], seen['stage_bytes']) == (1, (0, Y), 3, None)
+    # no pixels: the shapes, and nothing of the library
+    got = mod16_amd.anomaly_series(np.empty((Y * P, 0), np.float32), periods=P, outputs=('pct', 'count'))
+    assert got.pct.shape == (Y * P, 0) and got.count.shape == (P, 0) and got.count.dtype == np.uint8 and got.z is None
+    assert rec.take() == {}
+
+
+UP_FINE, UP_COARSE = (4, 6), (2, 3)
+UP_ROWS, UP_COLS = np.array([0.0, 0.2, 1.0, 1.2]), np.array([0.0, 0.1, 1.0, 1.1, 2.0, 2.1])
+
+
+def check_cells(g, device, wrap, area):
+    '''The grid an upscaling entry point makes: the runs of its own geometry check, no positions.'''
+    assert (g['device'], g['shape'], g['coarse_shape'], g['wrap']) == (device, UP_FINE, UP_COARSE, wrap)
+    assert g['row_pos'] is None and g['col_pos'] is None and g['col_affine'] is None
+    assert (g['area'] is None) if area is None else (same(g['area'], area) and g['area'].dtype == np.float64)
+    (rf, rc), (cf, cc) = g['runs']
+    assert [list(t) for t in (rf, rc, cf, cc)] == [[0, 2], [2, 2], [0, 2, 4], [2, 2, 2]]
+
+
+def test_upscale_fields_hands_over_layers_and_strides_and_closes_the_grid(rec):
+    from mod16_amd import upscale as up
+    K, (R, Cc), (H, W) = 2, UP_FINE, UP_COARSE
+    values = np.arange(K * R * Cc, dtype=np.float32).reshape((K,) + UP_FINE)
+    area = np.array([1, 2, 3, 4])
+    got = mod16_amd.upscale_fields(values, UP_COARSE, UP_ROWS, UP_COLS, wrap=True, area=area, min_fraction=0.25,
+                                   outputs=up.OUTPUT_NAMES, device=1, stage_bytes=1 << 16)
+    assert type(got) is up.Upscaled and all(type(o) is np.ndarray and o.shape == (K,) + UP_COARSE for o in got)
+    assert [o.dtype for o in got] == [np.float32, np.float32, np.int32]
+    (made, g), (name, seen), (last, _) = rec.take()[None]
+    assert made == 'cells' and name == 'run' and last == 'close'
+    check_cells(g, 1, True, area)
+    assert (seen['dtype'], seen['values'], seen['layers'], seen['strides']) == (np.float32, values.ctypes.data, K, (R * Cc, Cc))
+    assert seen['min_fraction'] == 0.25 and seen['outs'] == [(o.ctypes.data, H * W, W) for o in got]
+    assert (seen['where'], seen['stream'], seen['stage_bytes']) == (_lib.HOST, None, 1 << 16)
+    # one layer without a layer axis: (H, W) back, the mean alone; float64
+    got = mod16_amd.upscale_fields(values[0].astype(np.float64), UP_COARSE, UP_ROWS, UP_COLS)
+    assert got.mean.shape == UP_COARSE and got.mean.dtype == np.float64 and got.fraction is None and got.count is None
+    (made, g), (name, seen), (last, _) = rec.take()[None]
+    check_cells(g, 0, False, None)
+    assert (seen['dtype'], seen['layers'], seen['min_fraction']) == (np.float64, 1, 0.0)
+    assert seen['outs'] == [(got.mean.ctypes.data, H * W, W), None, None] and seen['stage_bytes'] is None
+
+
+def test_upscale_classes_makes_bytes_of_the_codes(rec):
+    from mod16_amd import upscale as up
+    (R, Cc), (H, W) = UP_FINE, UP_COARSE
+    cls = np.arange(R * Cc).reshape(UP_FINE) % 13
+    got = mod16_amd.upscale_classes(cls, UP_COARSE, UP_ROWS, UP_COLS, valid=(1, 2, 31), outputs=up.CLASS_OUTPUT_NAMES,
+                                    device=1, stage_bytes=1 << 16)
+    assert type(got) is up.UpscaledClasses and all(type(o) is np.ndarray and o.shape == UP_COARSE for o in got)
+    assert (got.cls.dtype, got.share.dtype) == (np.uint8, np.float32)
+    (made, g), (name, seen), (last, _) = rec.take()[None]
+    assert made == 'cells' and name == 'classes' and last == 'close'
+    check_cells(g, 1, False, None)
+    assert seen['cls_bytes'] == [int(c) for c in cls.flat]                # int64 codes became bytes
+    assert (seen['row_stride'], seen['valid']) == (Cc, (1 << 1) | (1 << 2) | (1 << 31))
+    assert seen['out'] == ((got.cls.ctypes.data, W), (got.share.ctypes.data, W))
+    assert (seen['where'], seen['stream'], seen['stage_bytes']) == (_lib.HOST, None, 1 << 16)
+    # uint8 codes are read in place; the default: the class alone, the 13 classes of the table
+    c8 = cls.astype(np.uint8)
+    got = mod16_amd.upscale_classes(c8, UP_COARSE, UP_ROWS, UP_COLS)
+    assert got.share is None
+    seen = rec.take()[None][1][1]
+    assert seen['cls'] == c8.ctypes.data and seen['valid'] == (1 << 13) - 1
+    assert seen['out'] == ((got.cls.ctypes.data, W), None) and seen['stage_bytes'] is None
+
+
 # ------------------------------------------------------------------ refusals
 def _raster(**kw):
     kw.setdefault('cls', CLS)
@@ -675,6 +892,29 @@ def _gapfill(**kw):
 
 def _zonal(**kw):
     return mod16_amd.zonal_statistics(np.zeros(SHAPE), np.zeros(SHAPE, np.uint8), **kw)
+
+
+def _daynight(**kw):
+    fields, (half, noon, offset) = daynight_case(np.float64)
+    kw.setdefault('outputs', ('tmin', 'temp_annual'))
+    return mod16_amd.aggregate_daynight(kw.pop('fields', fields), half, noon, offset, steps_per_day=DN_STEPS, **kw)
+
+
+def _trend(**kw):
+    return mod16_amd.trend_series(kw.pop('values', np.zeros((4,) + SHAPE)), **kw)
+
+
+def _anomaly(**kw):
+    kw.setdefault('periods', 2)
+    return mod16_amd.anomaly_series(kw.pop('num', np.zeros((6,) + SHAPE)), **kw)
+
+
+def _upscale(**kw):
+    return mod16_amd.upscale_fields(kw.pop('values', np.zeros(UP_FINE)), UP_COARSE, UP_ROWS, UP_COLS, **kw)
+
+
+def _classes(**kw):
+    return mod16_amd.upscale_classes(kw.pop('cls', np.zeros(UP_FINE, np.uint8)), UP_COARSE, UP_ROWS, UP_COLS, **kw)
 
 
 BAD_CLS = np.array([[1, 2, 3], [4, 5, 256]])
@@ -739,6 +979,74 @@ REFUSALS = [
     (_zonal, dict(stage_bytes=-1, area=np.zeros(5)), ValueError,
      'area must be a scalar, (rows,) for a 2-D raster or of the shape of zones (2, 3), got (5,)'),
     (_zonal, dict(stage_bytes=-1, acc='no result'), ValueError, 'stage_bytes must not be negative'),
+    # day / night: the out= dict -- its key set, then per name dtype, shape, layout, type
+    (_daynight, dict(out={'tmin': np.empty((2,) + SHAPE)}), ValueError,
+     'out must hold exactly the requested outputs: tmin, temp_annual'),
+    (_daynight, dict(out={'tmin': np.empty((2,) + SHAPE), 'temp_annual': np.empty(SHAPE), 'temp_day': np.empty((2,) + SHAPE)}),
+     ValueError, 'out must hold exactly the requested outputs: tmin, temp_annual'),
+    (_daynight, dict(out={'tmin': np.empty((2,) + SHAPE, np.float32), 'temp_annual': np.empty(SHAPE)}), ValueError,
+     "out['tmin'] must be a writeable C-contiguous float64 array of shape (2, 2, 3)"),
+    (_daynight, dict(out={'tmin': np.empty((2,) + SHAPE), 'temp_annual': np.empty((1,) + SHAPE)}), ValueError,
+     "out['temp_annual'] must be a writeable C-contiguous float64 array of shape (2, 3)"),
+    (_daynight, dict(out={'tmin': np.empty((2, 2, 6))[:, :, ::2], 'temp_annual': np.empty(SHAPE)}), ValueError,
+     "out['tmin'] must be a writeable C-contiguous float64 array of shape (2, 2, 3)"),
+    (_daynight, dict(out={'tmin': [[0.0]], 'temp_annual': np.empty(SHAPE)}), ValueError,
+     "out['tmin'] must be a writeable C-contiguous float64 array of shape (2, 2, 3)"),
+    (_daynight, dict(stage_bytes=-1), ValueError, 'stage_bytes must not be negative'),
+    (_daynight, dict(stage_bytes=-1, out={'tmin': np.empty((2,) + SHAPE)}), ValueError, 'stage_bytes must not be negative'),
+    (_daynight, dict(stage_bytes=-1, dtype='int16'), ValueError, "dtype must be 'float32' or 'float64', got 'int16'"),
+    (_daynight, dict(outputs=('vpd_day',)), ValueError, "outputs: 'vpd_day' needs the field 'qv'"),
+    # trend
+    (_trend, dict(values=np.zeros((4,) + SHAPE, np.int64)), ValueError, 'values must be float32 or float64, got int64'),
+    (_trend, dict(values=np.zeros((1,) + SHAPE)), ValueError,
+     'values must have shape (Y,) + pixel shape with 2 <= Y <= 64, got (1, 2, 3)'),
+    (_trend, dict(times=np.arange(3.0)), ValueError, 'times must have shape (4,), got (3,)'),
+    (_trend, dict(min_valid=1), ValueError, 'min_valid must be an integer between 2 and Y = 4, got 1'),
+    (_trend, dict(alpha=0.7), ValueError, 'alpha must be None or a level in (0, 0.5], got 0.7'),
+    (_trend, dict(stage_bytes=-1), ValueError, 'stage_bytes must not be negative'),
+    (_trend, dict(stage_bytes=-1, alpha=0.7), ValueError, 'alpha must be None or a level in (0, 0.5], got 0.7'),
+    (_trend, dict(values=np.zeros((4,) + SHAPE, np.int64), min_valid=1), ValueError,
+     'values must be float32 or float64, got int64'),
+    # anomaly
+    (_anomaly, dict(den=np.zeros((6, 3))), ValueError, 'den must have the shape of num (6, 2, 3), got (6, 3)'),
+    (_anomaly, dict(den=np.zeros((6,) + SHAPE, np.float32)), ValueError,
+     'den must have the dtype of num (float64), got float32'),
+    (_anomaly, dict(periods=None), ValueError, 'periods must be given'),
+    (_anomaly, dict(num=np.zeros((6,) + SHAPE, np.int64)), ValueError, 'num must be float32 or float64, got int64'),
+    (_anomaly, dict(periods=4), ValueError,
+     'num must have shape (S,) + pixel shape with S = Y * periods and 2 <= Y <= 64, got (6, 2, 3) with periods = 4'),
+    (_anomaly, dict(window=3), ValueError, 'window must be between 1 and min(periods, 16) = 2, got 3'),
+    (_anomaly, dict(baseline=(0, 1)), ValueError, 'the baseline needs at least 2 years, got (0, 1)'),
+    (_anomaly, dict(min_valid=1), ValueError, 'min_valid must be between 2 and the baseline length 3, got 1'),
+    (_anomaly, dict(outputs=('q',)), ValueError,
+     "outputs must name one or more of z, pct, mean, std, count, each once, got ('q',)"),
+    (_anomaly, dict(stage_bytes=-1), ValueError, 'stage_bytes must not be negative'),
+    (_anomaly, dict(periods=None, den=np.zeros((6, 3))), ValueError, 'den must have the shape of num (6, 2, 3), got (6, 3)'),
+    (_anomaly, dict(periods=None, num=np.zeros((6,) + SHAPE, np.int64)), ValueError,
+     'num must be float32 or float64, got int64'),
+    (_anomaly, dict(periods=None, outputs=('q',)), ValueError, 'periods must be given'),
+    (_anomaly, dict(stage_bytes=-1, outputs=('q',)), ValueError,
+     "outputs must name one or more of z, pct, mean, std, count, each once, got ('q',)"),
+    # upscaling
+    (_upscale, dict(values=np.zeros(6)), ValueError, 'values must have shape (K, R, C) or (R, C), got (6,)'),
+    (_upscale, dict(values=np.zeros(UP_FINE, np.int64)), ValueError, 'values must be float32 or float64, got int64'),
+    (_upscale, dict(values=np.zeros((2, 3, 6))), ValueError,
+     'row_pos and col_pos must have shapes (3,) and (6,), got (4,) and (6,)'),
+    (_upscale, dict(min_fraction=2), ValueError, 'min_fraction must lie in [0, 1], got 2'),
+    (_upscale, dict(area=np.ones(3)), ValueError, 'area must have shape (4,) -- a weight per fine row --, got (3,)'),
+    (_upscale, dict(outputs=('mean', 'mean')), ValueError,
+     "outputs must name one or more of mean, fraction, count, each once, got ('mean', 'mean')"),
+    (_upscale, dict(stage_bytes=-1), ValueError, 'stage_bytes must not be negative'),
+    (_upscale, dict(stage_bytes=-1, outputs=()), ValueError,
+     'outputs must name one or more of mean, fraction, count, each once, got ()'),
+    (_classes, dict(cls=np.zeros((1,) + UP_FINE, np.uint8)), ValueError,
+     'cls must be a two-dimensional class raster, got shape (1, 4, 6)'),
+    (_classes, dict(cls=np.full(UP_FINE, 256)), IndexError, CLASS_CODE),
+    (_classes, dict(valid=[40]), ValueError, 'valid must hold class codes in [0, 32), got 40'),
+    (_classes, dict(outputs=('mean',)), ValueError,
+     "outputs must name one or more of cls, share, each once, got ('mean',)"),
+    (_classes, dict(stage_bytes=-1), ValueError, 'stage_bytes must not be negative'),
+    (_classes, dict(stage_bytes=-1, valid=[True]), ValueError, 'valid must hold class codes in [0, 32), got True'),
 ]
 
 

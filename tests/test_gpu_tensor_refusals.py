@@ -1,19 +1,25 @@
 """What the device-tensor entry points refuse, and that they take pitched, offset views: one table
 over every tensor-taking method of mod16_amd.raster -- RasterEngine.composite, .gapfill, .daynight,
-.zonal, .zonal_bounds and DownscaleGrid.run, .fields, .composite.
+.trend, .anomaly, .zonal, .zonal_bounds, DownscaleGrid.run, .fields, .composite and UpscaleGrid.run,
+.majority.
 
 A refusal case starts from a call that is accepted, commits ONE offence against one argument and
 asserts the exception type, that the message names the argument, and the phrase that names the
 condition ('unit stride', 'distance between rows', 'stride in time', 'must share one', 'tensor on
 cuda:', 'shape', 'overlaps'; a few conditions outside the strided layouts have a phrase of their
-own: a flat array that must be 'contiguous', a wrong count of outputs that 'must hold' another).
+own: a flat array that must be 'contiguous', a wrong count of outputs that 'must hold' another, a
+dict of outputs that must hold 'exactly the fields' produced or 'exactly the requested' outputs).
 Every refusal comes before any device work. An accepted call per method runs on views that start one
 element into a larger buffer with rows (and planes) further apart than they are long, and must equal
 the call on contiguous copies bit for bit: a helper that reported a wrong pitch would show there.
 
 Shapes, the smallest with every edge: n = 7 pixels; gap filling S = 3 slabs; day / night 3 x 5 cells,
 D = 2 days of H = 2 steps; zonal K = 2 layers, 3 zones; a 5 x 6 fine raster over a 3 x 4 coarse grid,
-of which the calls take the 7 pixels from pixel 11; composites of 4 days in periods of 2."""
+of which the calls take the 7 pixels from pixel 11; composites of 4 days in periods of 2; a trend over
+Y = 4 steps with min_valid = 2 and alpha = 0.1 (all seven fields); anomalies of 3 years of 2 periods
+with window = 2, min_valid = 2 and a denominator (all five outputs); upscaling of K = 2 layers of the
+5 x 6 raster onto the 3 x 4 grid (all three outputs) and its class raster (both outputs). A `(Y, n - 1)`
+stack is just another trend or anomaly call, so `wrong_shape` is no offence against `values` / `num`."""
 import numpy as np
 import pytest
 
@@ -27,6 +33,11 @@ K, NZ = 2, 3
 FINE, COARSE, FIRST = (5, 6), (3, 4), 11
 DAYS, PERIOD = 4, 2
 COARSE_DRIVERS = ('temp_day', 'temp_night', 'temp_annual')       # drivers 5, 6 and 7
+STEPS, YEARS, PERIODS = 4, 3, 2
+TREND_FIELDS = ('slope', 'intercept', 'slope_lo', 'slope_hi', 's', 'z', 'count')
+ANOMALY_FIELDS = ('z', 'pct', 'mean', 'std', 'count')
+UPSCALE_FIELDS = ('mean', 'fraction', 'count')
+CLASS_FIELDS = ('cls', 'share')
 
 
 @pytest.fixture(scope='module')
@@ -75,7 +86,17 @@ def env():
     base['zonal'] = dict(values=dev(rng.uniform(-3.0, 9.0, (K, N))), zones=dev(rng.integers(0, NZ, N).astype(np.int32)),
                          area=dev(rng.uniform(0.5, 2.0, N)), cols=None, acc=None)
     base['zonal_bounds'] = dict(values=base['zonal']['values'], area=base['zonal']['area'], cols=None)
+    # trend: a (Y, n) stack; anomaly: (Y P, n) numerator and denominator
+    base['trend'] = dict(values=dev(rng.uniform(0.0, 9.0, (STEPS, N))), out=None)
+    base['anomaly'] = dict(num=dev(rng.uniform(1.0, 9.0, (YEARS * PERIODS, N))),
+                           den=dev(rng.uniform(1.0, 9.0, (YEARS * PERIODS, N))), out=None)
+    # upscaling: the downscaled grid's geometry the other way round; (K, 5, 6) values, a (5, 6) class raster
+    up = eng.upscale_grid(FINE, COARSE, ds.positions(0.1, 0.4, FINE[0], 0.0, 1.0),
+                          ds.positions(0.2, 0.5, FINE[1], 0.0, 1.0))
+    base['upscale.run'] = dict(grid=up, values=dev(rng.uniform(0.0, 9.0, (K,) + FINE)), out=None)
+    base['upscale.majority'] = dict(grid=up, cls=dev(rng.integers(0, 13, FINE).astype(np.uint8)), out=None)
     yield torch, eng, grid, base
+    up.close()
     grid.close()
 
 
@@ -97,6 +118,15 @@ def call(env, method, a):
     if method == 'daynight':
         return eng.daynight(a['fields'], *a['tables'], steps_per_day=H, outputs=('temp_day', 'sw_rad_day', 'temp_annual'),
                             out=a['out'])
+    if method == 'trend':
+        return eng.trend(a['values'], min_valid=2, alpha=0.1, out=a['out'])
+    if method == 'anomaly':
+        return eng.anomaly(a['num'], a['den'], periods=PERIODS, window=2, min_valid=2, outputs=ANOMALY_FIELDS,
+                           out=a['out'])
+    if method == 'upscale.run':
+        return a['grid'].run(a['values'], outputs=UPSCALE_FIELDS, out=a['out'])
+    if method == 'upscale.majority':
+        return a['grid'].majority(a['cls'], outputs=CLASS_FIELDS, out=a['out'])
     if method == 'zonal':
         return eng.zonal(a['values'], a['zones'], NZ, area=a['area'], cols=a['cols'], bounds=(2.0, 9.0), acc=a['acc'])
     return eng.zonal_bounds(a['values'], a['area'], a['cols'])
@@ -271,6 +301,35 @@ ONE_ARGUMENT = [
     ('zonal_bounds', ('values',), rows_too_close, ValueError, 'values', 'distance between rows'),
     ('zonal_bounds', ('area',), not_a_tensor, TypeError, 'area', 'tensor on cuda:'),
     ('zonal_bounds', ('area',), non_unit, ValueError, 'area', 'unit stride'),
+    # ---- RasterEngine.trend: the stack
+    ('trend', ('values',), not_a_tensor, TypeError, 'values', 'tensor on cuda:'),
+    ('trend', ('values',), wrong_dtype, TypeError, 'values', 'tensor on cuda:'),
+    ('trend', ('values',), non_unit, ValueError, 'values', 'unit stride'),
+    ('trend', ('values',), rows_too_close, ValueError, 'values', 'stride in time'),
+    # ---- RasterEngine.anomaly: numerator and denominator
+    ('anomaly', ('num',), not_a_tensor, TypeError, 'num', 'tensor on cuda:'),
+    ('anomaly', ('num',), wrong_dtype, TypeError, 'num', 'tensor on cuda:'),
+    ('anomaly', ('num',), non_unit, ValueError, 'num', 'unit stride'),
+    ('anomaly', ('num',), rows_too_close, ValueError, 'num', 'stride in time'),
+    ('anomaly', ('num',), pitched, ValueError, 'num and den', 'must share one'),
+    ('anomaly', ('den',), not_a_tensor, TypeError, 'den', 'tensor on cuda:'),
+    ('anomaly', ('den',), wrong_dtype, TypeError, 'den', 'tensor on cuda:'),
+    ('anomaly', ('den',), wrong_shape, ValueError, 'den', 'shape'),
+    ('anomaly', ('den',), non_unit, ValueError, 'den', 'unit stride'),
+    ('anomaly', ('den',), rows_too_close, ValueError, 'den', 'stride in time'),
+    ('anomaly', ('den',), pitched, ValueError, 'num and den', 'must share one'),
+    # ---- UpscaleGrid.run and .majority: the layers and the class raster
+    ('upscale.run', ('values',), not_a_tensor, TypeError, 'values', 'tensor on cuda:'),
+    ('upscale.run', ('values',), wrong_dtype, TypeError, 'values', 'tensor on cuda:'),
+    ('upscale.run', ('values',), wrong_shape, ValueError, 'values', 'shape'),
+    ('upscale.run', ('values',), non_unit, ValueError, 'values', 'unit stride'),
+    ('upscale.run', ('values',), rows_too_close, ValueError, 'values', 'distance between rows'),
+    ('upscale.run', ('values',), planes_too_close, ValueError, 'values', 'stride in time'),
+    ('upscale.majority', ('cls',), not_a_tensor, TypeError, 'cls', 'tensor on cuda:'),
+    ('upscale.majority', ('cls',), wrong_dtype, TypeError, 'cls', 'tensor on cuda:'),
+    ('upscale.majority', ('cls',), wrong_shape, ValueError, 'cls', 'shape'),
+    ('upscale.majority', ('cls',), non_unit, ValueError, 'cls', 'unit stride'),
+    ('upscale.majority', ('cls',), rows_too_close, ValueError, 'cls', 'distance between rows'),
 ]
 
 
@@ -293,7 +352,16 @@ def out_shapes(torch, method):
             'grid.composite': [((DAYS // PERIOD, N), f64), ((DAYS // PERIOD, N), torch.uint16)],
             'grid.fields': [((2, N), f64)],
             'gapfill': [((S, N), torch.uint8), ((S, N), torch.uint8), ((2, S, N), torch.uint8)],
-            'daynight': [((D, R, W), f64), ((D, R, W), f64), ((R, W), f64)]}[method]
+            'daynight': [((D, R, W), f64), ((D, R, W), f64), ((R, W), f64)],
+            'trend': [((N,), torch.int32 if k == 's' else torch.uint8 if k == 'count' else f64) for k in TREND_FIELDS],
+            'anomaly': [((YEARS * PERIODS, N), f64)] * 2 + [((PERIODS, N), f64)] * 2 + [((PERIODS, N), torch.uint8)],
+            'upscale.run': [((K,) + COARSE, f64)] * 2 + [((K,) + COARSE, torch.int32)],
+            'upscale.majority': [(COARSE, torch.uint8), (COARSE, torch.float32)]}[method]
+
+
+#: the names of the outputs of the methods that take `out` as a dict, in the order of `out_shapes`
+OUT_NAMES = {'daynight': ('temp_day', 'sw_rad_day', 'temp_annual'), 'trend': TREND_FIELDS, 'anomaly': ANOMALY_FIELDS,
+             'upscale.run': UPSCALE_FIELDS, 'upscale.majority': CLASS_FIELDS}
 
 
 def with_out(torch, method, a, change=None, k=0):
@@ -303,8 +371,8 @@ def with_out(torch, method, a, change=None, k=0):
         outs[k] = change(torch, outs[k])
     if method == 'grid.fields':
         return put(a, ('out',), outs[0])
-    if method == 'daynight':
-        return put(a, ('out',), dict(zip(('temp_day', 'sw_rad_day', 'temp_annual'), outs)))
+    if method in OUT_NAMES:
+        return put(a, ('out',), dict(zip(OUT_NAMES[method], outs)))
     if method == 'gapfill':
         return put(put(a, ('out',), outs), ('source',), True)
     return put(a, ('out',), outs)
@@ -352,6 +420,33 @@ ONE_OUTPUT = [
     ('daynight', 1, planes_too_close, ValueError, "out['sw_rad_day']", 'stride in time'),
     ('daynight', 1, pitched, ValueError, 'out', 'must share one'),
     ('daynight', 2, pitched, ValueError, 'out', 'must share one'),
+    ('trend', 4, not_a_tensor, TypeError, "out['s']", 'tensor on cuda:'),
+    ('trend', 4, wrong_dtype, TypeError, "out['s']", 'tensor on cuda:'),
+    ('trend', 0, wrong_dtype, TypeError, "out['slope']", 'tensor on cuda:'),
+    ('trend', 6, wrong_shape, ValueError, "out['count']", 'shape'),
+    ('trend', 3, non_unit, ValueError, "out['slope_hi']", 'unit stride'),
+    ('anomaly', 1, not_a_tensor, TypeError, "out['pct']", 'tensor on cuda:'),
+    ('anomaly', 1, wrong_dtype, TypeError, "out['pct']", 'tensor on cuda:'),
+    ('anomaly', 4, wrong_dtype, TypeError, "out['count']", 'tensor on cuda:'),
+    ('anomaly', 1, wrong_shape, ValueError, "out['pct']", 'shape'),
+    ('anomaly', 3, wrong_shape, ValueError, "out['std']", 'shape'),
+    ('anomaly', 1, non_unit, ValueError, "out['pct']", 'unit stride'),
+    ('anomaly', 1, rows_too_close, ValueError, "out['pct']", 'stride in time'),
+    ('anomaly', 2, rows_too_close, ValueError, "out['mean']", 'stride in time'),
+    ('anomaly', 1, pitched, ValueError, "out['z'] and out['pct']", 'must share one'),
+    ('anomaly', 4, pitched, ValueError, "out['mean'], out['std'] and out['count']", 'must share one'),
+    ('upscale.run', 1, not_a_tensor, TypeError, "out['fraction']", 'tensor on cuda:'),
+    ('upscale.run', 1, wrong_dtype, TypeError, "out['fraction']", 'tensor on cuda:'),
+    ('upscale.run', 2, wrong_dtype, TypeError, "out['count']", 'tensor on cuda:'),
+    ('upscale.run', 1, wrong_shape, ValueError, "out['fraction']", 'shape'),
+    ('upscale.run', 1, non_unit, ValueError, "out['fraction']", 'unit stride'),
+    ('upscale.run', 1, rows_too_close, ValueError, "out['fraction']", 'distance between rows'),
+    ('upscale.run', 1, planes_too_close, ValueError, "out['fraction']", 'stride in time'),
+    ('upscale.majority', 1, not_a_tensor, TypeError, "out['share']", 'tensor on cuda:'),
+    ('upscale.majority', 1, wrong_dtype, TypeError, "out['share']", 'tensor on cuda:'),
+    ('upscale.majority', 0, wrong_shape, ValueError, "out['cls']", 'shape'),
+    ('upscale.majority', 1, non_unit, ValueError, "out['share']", 'unit stride'),
+    ('upscale.majority', 1, rows_too_close, ValueError, "out['share']", 'distance between rows'),
 ]
 
 
@@ -402,6 +497,21 @@ def test_a_wrong_number_of_outputs_is_refused(env):
         call(env, 'daynight', put(a, ('out',), dict(a['out'], temp_night=a['out']['temp_day'].clone())))
 
 
+@pytest.mark.parametrize('method,phrase', [('daynight', 'exactly the requested'), ('trend', 'exactly the fields'),
+                                           ('anomaly', 'exactly the fields'), ('upscale.run', 'exactly the fields'),
+                                           ('upscale.majority', 'exactly the fields')])
+def test_a_missing_and_a_surplus_output_key_are_refused(env, method, phrase):
+    torch, base = env[0], env[3]
+    a = with_out(torch, method, base[method])
+    last = OUT_NAMES[method][-1]
+    for out in ({k: t for k, t in a['out'].items() if k != last}, dict(a['out'], surplus=a['out'][last].clone())):
+        with pytest.raises(ValueError) as info:
+            call(env, method, put(a, ('out',), out))
+        assert type(info.value) is ValueError
+        assert 'out must hold' in str(info.value) and phrase in str(info.value), str(info.value)
+        assert all(k in str(info.value) for k in OUT_NAMES[method])           # the message lists what is produced
+
+
 def test_an_output_that_overlaps_an_input_is_refused(env):
     torch, eng, grid, base = env
     # gap filling: a field as its own output; day / night: a plane of t as temp_annual
@@ -424,8 +534,16 @@ def test_an_output_that_overlaps_an_input_is_refused(env):
     eng.check()
 
 
+def padding(torch, view):
+    """the elements of the buffer behind a `pitched` view that are not the view's"""
+    buf = signed(torch, view._base)
+    mine = torch.zeros(buf.shape, dtype=torch.bool, device='cuda')
+    (mine[1:-1] if view.dim() == 1 else mine[..., :-1, 1:-2]).fill_(True)
+    return buf[~mine]
+
+
 @pytest.mark.parametrize('method', ['composite', 'grid.composite', 'grid.run', 'grid.fields', 'gapfill', 'daynight',
-                                    'zonal', 'zonal_bounds'])
+                                    'zonal', 'zonal_bounds', 'trend', 'anomaly', 'upscale.run', 'upscale.majority'])
 def test_pitched_offset_views_give_the_bits_of_contiguous_copies(env, method):
     """Every tensor argument (inputs and, where the method takes them, outputs) as a view one element
     into a larger buffer with rows 3 elements and planes a row further apart than they are long."""
@@ -444,6 +562,7 @@ def test_pitched_offset_views_give_the_bits_of_contiguous_copies(env, method):
         return x
     flat = ('cls',) if method.startswith('grid') else ()     # contiguous by contract
     b = {k: (v if k in flat or k == 'tables' else view(v)) for k, v in a.items()}
+    poisoned = []
     if method == 'grid.run':      # its fine drivers and outputs are flat arrays: offset, not pitched
         b['out_day'], b['out_night'] = full(torch, (N + 1,), torch.float64)[1:], full(torch, (N + 1,), torch.float64)[1:]
     elif method == 'zonal':
@@ -457,12 +576,17 @@ def test_pitched_offset_views_give_the_bits_of_contiguous_copies(env, method):
             b['out'] = [poison(v) for v in b['out']]
         else:
             b['out'] = poison(b['out'])
+        poisoned = list(b['out'].values()) if isinstance(b['out'], dict) else list(b['out']) if isinstance(b['out'], list) \
+            else [b['out']]
         if method == 'gapfill':
             # (the source tensor holds its fields back to back: pitched rows, dense planes)
             b['out'][2] = torch.full((2, S, N + 3), 77, dtype=torch.uint8, device='cuda')[:, :, 1:-2]
+            poisoned.pop()
     got = outputs_of(torch, env, method, b)
-    if method not in ('grid.run', 'zonal', 'zonal_bounds'):
+    if method not in ('grid.run', 'zonal', 'zonal_bounds', 'trend'):      # (a trend's outputs are (n,): offset only)
         assert any(not t.is_contiguous() for t in got)
+    for t in poisoned:                       # what lies in front of, between and behind the rows is not touched
+        assert bool((padding(torch, t) == 77).all())
     assert len(got) == len(want)
     for g, w in zip(got, want):
         if isinstance(g, torch.Tensor):

@@ -8,60 +8,9 @@
 // every requested output element overwritten, no guard byte and no byte between the rows touched,
 // nothing left allocated.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
-
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                   \
-    do {                                                                               \
-        if (!(cond)) {                                                                 \
-            fprintf(stderr, "host_asan_anomaly: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                   \
-        }                                                                              \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3, kFresh = 0x11;
-
-// `rows` rows of n elements of `elem` bytes, `pitch` elements apart, between two runs of guard bytes, in
-// one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes, elem;
-    int64_t rows, pitch, n;
-    Guarded(int64_t rows_, int64_t pitch_, int64_t n_, size_t elem_, unsigned char fill)
-        : mem((size_t)((rows_ - 1) * pitch_ + n_) * elem_ + 2 * kGuard, kGuardByte),
-          bytes((size_t)((rows_ - 1) * pitch_ + n_) * elem_), elem(elem_), rows(rows_), pitch(pitch_), n(n_) {
-        memset(data(), fill, bytes);
-    }
-    unsigned char* data() { return mem.data() + kGuard; }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-    // every element of the rows overwritten (none still holds kFresh in every byte), or none; the elements
-    // between the rows untouched either way
-    void check(bool written, const char* what) {
-        EXPECT(guards_intact());
-        std::vector<unsigned char> fresh(elem, kFresh);
-        for (size_t i = 0; i < bytes / elem; ++i) {
-            const bool in_row = (int64_t)(i % (size_t)pitch) < n;
-            const bool is_fresh = memcmp(data() + i * elem, fresh.data(), elem) == 0;
-            if (is_fresh == (in_row && written)) {
-                fprintf(stderr, "host_asan_anomaly: %s, element %zu: %s\n", what, i, is_fresh ? "not overwritten" : "overwritten");
-                exit(1);
-            }
-        }
-    }
-};
+#define HARNESS_NAME "host_asan_anomaly"
+#include "harness.hpp"
 
 template <typename IN>
 static int call(mod16_ctx* ctx, const mod16_anomaly_spec* spec, const void* num, const void* den, void* z, void* pct,
@@ -92,14 +41,14 @@ static void run(mod16_ctx* ctx, const char* what) {
                         spec.in_stride = pitched ? n + 5 : n;
                         spec.out_stride = pitched ? n + 3 : n;
                         spec.clim_stride = pitched ? n + 7 : n;
-                        Guarded num(S, spec.in_stride, n, sizeof(IN), 0), den(S, spec.in_stride, n, sizeof(IN), 0);
+                        Shaped num(S, spec.in_stride, n, sizeof(IN), 0), den(S, spec.in_stride, n, sizeof(IN), 0);
                         // a slot's slab: 33 KiB per staged array and 512 bytes, then per pixel the rows of 8 bytes and the counts
                         const size_t fixed = 6 * 33 * 1024 + 512, per_pixel = (size_t)(4 * S + 2 * P) * 8 + P;
                         const size_t stages[] = {1, fixed + per_pixel * 280, 0};
                         for (size_t stage : stages) {
-                            Guarded z(S, spec.out_stride, n, sizeof(IN), kFresh), pct(S, spec.out_stride, n, sizeof(IN), kFresh);
-                            Guarded mean(P, spec.clim_stride, n, 8, kFresh), sdev(P, spec.clim_stride, n, 8, kFresh);
-                            Guarded count(P, spec.clim_stride, n, 1, kFresh);
+                            Shaped z(S, spec.out_stride, n, sizeof(IN), kFresh), pct(S, spec.out_stride, n, sizeof(IN), kFresh);
+                            Shaped mean(P, spec.clim_stride, n, 8, kFresh), sdev(P, spec.clim_stride, n, 8, kFresh);
+                            Shaped count(P, spec.clim_stride, n, 1, kFresh);
                             const int rc = call<IN>(ctx, &spec, num.data(), ratio ? den.data() : nullptr, z.data(), all ? pct.data() : nullptr,
                                                     all ? mean.data() : nullptr, sdev.data(), count.data(), MOD16_HOST, stage);
                             if (rc != MOD16_OK) {
@@ -121,8 +70,8 @@ static void run(mod16_ctx* ctx, const char* what) {
 static void refusals(mod16_ctx* ctx) {
     const int64_t n = 12;
     const int Y = 6, P = 4, S = Y * P;
-    Guarded num(S, n, n, 8, 0), den(S, n, n, 8, 0), z(S, n, n, 8, kFresh), pct(S, n, n, 8, kFresh);
-    Guarded mean(P, n, n, 8, kFresh), sdev(P, n, n, 8, kFresh), count(P, n, n, 1, kFresh);
+    Shaped num(S, n, n, 8, 0), den(S, n, n, 8, 0), z(S, n, n, 8, kFresh), pct(S, n, n, 8, kFresh);
+    Shaped mean(P, n, n, 8, kFresh), sdev(P, n, n, 8, kFresh), count(P, n, n, 1, kFresh);
     mod16_anomaly_spec spec;
     memset(&spec, 0, sizeof spec);
     spec.n = n; spec.years = Y; spec.periods = P; spec.window = 2; spec.base_first = 1; spec.base_end = 5; spec.min_valid = 3;
@@ -130,10 +79,7 @@ static void refusals(mod16_ctx* ctx) {
     auto go = [&](const mod16_anomaly_spec& sp, int where) {
         return call<double>(ctx, &sp, num.data(), den.data(), z.data(), pct.data(), mean.data(), sdev.data(), count.data(), where, 0);
     };
-    auto refused = [&](int rc, const char* part) {
-        return rc == MOD16_ERR_ARG && strncmp(mod16_last_error(ctx), "mod16_anomaly: ", 15) == 0 &&
-               strstr(mod16_last_error(ctx), part) != nullptr;
-    };
+    auto refused = [&](int rc, const char* part) { return ::refused(ctx, rc, "mod16_anomaly: ", part); };
     mod16_anomaly_spec sp = spec;
     EXPECT(refused(call<double>(ctx, nullptr, num.data(), nullptr, z.data(), nullptr, nullptr, nullptr, nullptr, MOD16_HOST, 0), "NULL spec or num"));
     EXPECT(refused(call<float>(ctx, &spec, nullptr, den.data(), z.data(), nullptr, nullptr, nullptr, nullptr, MOD16_DEVICE, 0), "NULL spec or num"));
@@ -187,9 +133,6 @@ int main() {
     run<float>(ctx, "float32");
     run<double>(ctx, "float64");
     refusals(ctx);
-    EXPECT(mod16_destroy(ctx) == MOD16_OK);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_anomaly: ok\n");
+    harness_finish(ctx);
     return 0;
 }

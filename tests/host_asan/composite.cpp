@@ -5,62 +5,14 @@
 // the sizes make the tiles ragged and the last period short. Pass: no sanitizer report, every output
 // element overwritten, no guard byte and no padding byte of a pitched output touched.
 #include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
-
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                     \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            fprintf(stderr, "host_asan_composite: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                     \
-        }                                                                                \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3, kFresh = 0x11;
-
-// `bytes` of payload between two runs of guard bytes, in one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes;
-    explicit Guarded(size_t b, unsigned char fill) : mem(b + 2 * kGuard, kGuardByte), bytes(b) { memset(data(), fill, b); }
-    unsigned char* data() { return mem.data() + kGuard; }
-    template <typename T> T* as() { return reinterpret_cast<T*>(data()); }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-};
+#define HARNESS_NAME "host_asan_composite"
+#include "harness.hpp"
 
 template <typename T> static Guarded input(size_t count, T value) {
     Guarded g(count * sizeof(T), 0);
     for (size_t i = 0; i < count; ++i) g.as<T>()[i] = value;
     return g;
-}
-
-// rows x pitch elements of `elem` bytes: [r][0, n) overwritten (no byte pattern of kFresh left in an
-// element), [r][n, pitch) untouched (the last row ends with its n elements)
-static void check_output(Guarded& g, int rows, int64_t pitch, int64_t n, size_t elem, const char* what) {
-    EXPECT(g.guards_intact());
-    std::vector<unsigned char> fresh(elem, kFresh);
-    for (int r = 0; r < rows; ++r)
-        for (int64_t i = 0; i < (r == rows - 1 ? std::max<int64_t>(n, 1) : pitch); ++i) {
-            const bool same = memcmp(g.data() + ((size_t)r * pitch + i) * elem, fresh.data(), elem) == 0;
-            if (same != (i >= n)) {
-                fprintf(stderr, "host_asan_composite: %s, row %d element %lld: %s\n", what, r, (long long)i,
-                        same ? "not overwritten" : "padding overwritten");
-                exit(1);
-            }
-        }
 }
 
 template <typename T>
@@ -116,10 +68,10 @@ static void run(mod16_ctx* ctx, int (*fn)(mod16_ctx*, const mod16_composite_spec
                 fprintf(stderr, "host_asan_composite: %s: status %d: %s\n", what, rc, mod16_last_error(ctx));
                 exit(1);
             }
-            check_output(et, P, pitch, n, sizeof(T), "out_et");
-            check_output(pet, P, pitch, all ? n : 0, sizeof(T), "out_pet");
-            check_output(cet, P, pitch, all ? n : 0, 2, "count_et");
-            check_output(cpet, P, pitch, all ? n : 0, 2, "count_pet");
+            check_written(et, P, pitch, n, sizeof(T), true, "out_et");
+            check_written(pet, P, pitch, n, sizeof(T), all != 0, "out_pet");
+            check_written(cet, P, pitch, n, 2, all != 0, "count_et");
+            check_written(cpet, P, pitch, n, 2, all != 0, "count_pet");
         }
     for (Guarded& g : in) EXPECT(g.guards_intact());
     EXPECT(hours.guards_intact() && cls.guards_intact());
@@ -147,7 +99,7 @@ static void run(mod16_ctx* ctx, int (*fn)(mod16_ctx*, const mod16_composite_spec
     EXPECT(call(spec, pitch, 0, nullptr, -1) == MOD16_ERR_ARG);
     EXPECT(strstr(mod16_last_error(ctx), "stage_bytes") != nullptr);
     s = spec; s.n = 0; EXPECT(call(s, pitch, 0, nullptr, 0) == MOD16_OK);
-    check_output(et, P, pitch, 0, sizeof(T), "out_et of the refused calls");
+    check_written(et, P, pitch, n, sizeof(T), false, "out_et of the refused calls");
     printf("host_asan_composite: %s done\n", what);
 }
 
@@ -160,9 +112,6 @@ int main() {
     EXPECT(mod16_set_bplut_f64(ctx, lut) == MOD16_OK);
     run<double>(ctx, mod16_et_composite_f64, "float64");
     run<float>(ctx, mod16_et_composite_f32, "float32");
-    EXPECT(mod16_destroy(ctx) == MOD16_OK);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_composite: ok\n");
+    harness_finish(ctx);
     return 0;
 }

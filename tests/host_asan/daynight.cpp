@@ -8,64 +8,11 @@
 // allocated.
 #include <algorithm>
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
+#define HARNESS_NAME "host_asan_daynight"
+#include "harness.hpp"
 
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                    \
-    do {                                                                                \
-        if (!(cond)) {                                                                  \
-            fprintf(stderr, "host_asan_daynight: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                    \
-        }                                                                               \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3, kFresh = 0x11;
 constexpr int kFields = 5, kOutputs = 10;
-
-// `bytes` of payload between two runs of guard bytes, in one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes;
-    Guarded(size_t b, unsigned char fill) : mem(b + 2 * kGuard, kGuardByte), bytes(b) { memset(data(), fill, b); }
-    unsigned char* data() { return mem.data() + kGuard; }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-};
-
-static size_t extent(int64_t planes, int64_t plane, int64_t rows, int64_t pitch, int64_t n, size_t elem) {
-    return (size_t)((planes - 1) * plane + (rows - 1) * pitch + n) * elem;
-}
-
-// planes x rows x pitch elements: [p][r][0, n) overwritten where `written` (no element still holds
-// kFresh in every byte), everything else of the block untouched
-static void check_output(Guarded& g, int64_t planes, int64_t plane, int64_t rows, int64_t pitch, int64_t n, size_t elem,
-                         bool written, const char* what) {
-    EXPECT(g.guards_intact());
-    std::vector<unsigned char> fresh(elem, kFresh);
-    const int64_t total = (int64_t)(g.bytes / elem);
-    for (int64_t i = 0; i < total; ++i) {
-        const int64_t p = i / plane, in_plane = i - p * plane, r = in_plane / pitch, c = in_plane - r * pitch;
-        const bool inside = written && p < planes && r < rows && c < n;
-        const bool same = memcmp(g.data() + (size_t)i * elem, fresh.data(), elem) == 0;
-        if (same == inside) {
-            fprintf(stderr, "host_asan_daynight: %s, element %lld (plane %lld row %lld column %lld): %s\n", what, (long long)i,
-                    (long long)p, (long long)r, (long long)c, same ? "not overwritten" : "padding overwritten");
-            exit(1);
-        }
-    }
-}
 
 template <typename IN>
 static int call(mod16_ctx* ctx, const mod16_daynight_spec* spec, const void* const* fields, const double* half,
@@ -105,7 +52,7 @@ static void run(mod16_ctx* ctx, int out_type, const char* what) {
                 int nf = 0, no = 0;
                 for (int f = 0; f < kFields; ++f)
                     if (need[f]) {
-                        in.emplace_back(extent((int64_t)D * H, spec.in_plane, R, spec.in_pitch, W, isz), (unsigned char)0);
+                        in.emplace_back(span((int64_t)D * H, spec.in_plane, R, spec.in_pitch, W, isz), (unsigned char)0);
                         fields[f] = in.back().data();
                         ++nf;
                     }
@@ -119,17 +66,17 @@ static void run(mod16_ctx* ctx, int out_type, const char* what) {
                     void* outs[kOutputs] = {};
                     for (int o = 0; o < kOutputs; ++o)
                         if (want[o]) {
-                            out.emplace_back(extent(D, spec.out_plane, R, spec.out_pitch, W, osz), kFresh);
+                            out.emplace_back(span(D, spec.out_plane, R, spec.out_pitch, W, osz), kFresh);
                             outs[o] = out.back().data();
                         }
-                    Guarded annual(extent(1, 0, R, spec.out_pitch, W, osz), kFresh);
+                    Guarded annual(span(1, 0, R, spec.out_pitch, W, osz), kFresh);
                     const int rc = call<IN>(ctx, &spec, fields, half.data(), noon.data(), offset.data(), outs, annual.data(), MOD16_HOST, stage);
                     if (rc != MOD16_OK) {
                         fprintf(stderr, "host_asan_daynight: %s: status %d: %s\n", what, rc, mod16_last_error(ctx));
                         exit(1);
                     }
-                    for (Guarded& g : out) check_output(g, D, spec.out_plane, R, spec.out_pitch, W, osz, true, "out");
-                    check_output(annual, 1, R * spec.out_pitch, R, spec.out_pitch, W, osz, true, "temp_annual");
+                    for (Guarded& g : out) check_written(g, D, spec.out_plane, R, spec.out_pitch, W, osz, true, "out");
+                    check_written(annual, 1, R * spec.out_pitch, R, spec.out_pitch, W, osz, true, "temp_annual");
                 }
                 for (Guarded& g : in) EXPECT(g.guards_intact());
             }
@@ -140,8 +87,8 @@ static void run(mod16_ctx* ctx, int out_type, const char* what) {
 static void refusals(mod16_ctx* ctx) {
     const int64_t R = 4, W = 6;
     const int D = 3, H = 2;
-    Guarded t(extent(D * H, R * W, R, W, W, 4), 0), sw(extent(D * H, R * W, R, W, W, 4), 0);
-    Guarded o0(extent(D, R * W, R, W, W, 8), kFresh), o1(extent(D, R * W, R, W, W, 8), kFresh), ann(extent(1, 0, R, W, W, 8), kFresh);
+    Guarded t(span(D * H, R * W, R, W, W, 4), 0), sw(span(D * H, R * W, R, W, W, 4), 0);
+    Guarded o0(span(D, R * W, R, W, W, 8), kFresh), o1(span(D, R * W, R, W, W, 8), kFresh), ann(span(1, 0, R, W, W, 8), kFresh);
     std::vector<double> half((size_t)D * R, 6.0), noon(D, 12.0), offset(W, 0.0);
     const void* fields[kFields] = {t.data(), nullptr, nullptr, sw.data(), nullptr};
     void* outs[kOutputs] = {};
@@ -156,10 +103,7 @@ static void refusals(mod16_ctx* ctx) {
     auto go = [&](const mod16_daynight_spec& s, const void* const* f, void* const* o, void* a, int where) {
         return call<float>(ctx, &s, f, half.data(), noon.data(), offset.data(), o, a, where, 0);
     };
-    auto refused = [&](int rc, const char* part) {
-        return rc == MOD16_ERR_ARG && strncmp(mod16_last_error(ctx), "mod16_daynight: ", 16) == 0 &&
-               strstr(mod16_last_error(ctx), part) != nullptr;
-    };
+    auto refused = [&](int rc, const char* part) { return ::refused(ctx, rc, "mod16_daynight: ", part); };
     mod16_daynight_spec s = spec;
     EXPECT(refused(call<float>(ctx, nullptr, fields, half.data(), noon.data(), offset.data(), outs, ann.data(), MOD16_HOST, 0), "NULL spec"));
     EXPECT(refused(go(spec, nullptr, outs, ann.data(), MOD16_HOST), "NULL fields or out"));
@@ -217,9 +161,9 @@ static void refusals(mod16_ctx* ctx) {
     s = spec; s.days = 0; EXPECT(go(s, fields, outs, ann.data(), MOD16_HOST) == MOD16_OK);
     s = spec; s.rows = 0; s.in_plane = s.out_plane = 0; EXPECT(go(s, fields, outs, ann.data(), MOD16_HOST) == MOD16_OK);
     s = spec; s.cols = 0; EXPECT(go(s, fields, outs, ann.data(), MOD16_DEVICE) == MOD16_OK);
-    check_output(o0, D, R * W, R, W, W, 8, false, "out[3] of the refused calls");
-    check_output(o1, D, R * W, R, W, W, 8, false, "out[2] of the refused calls");
-    check_output(ann, 1, R * W, R, W, W, 8, false, "temp_annual of the refused calls");
+    check_written(o0, D, R * W, R, W, W, 8, false, "out[3] of the refused calls");
+    check_written(o1, D, R * W, R, W, W, 8, false, "out[2] of the refused calls");
+    check_written(ann, 1, R * W, R, W, W, 8, false, "temp_annual of the refused calls");
     EXPECT(t.guards_intact() && sw.guards_intact());
     printf("host_asan_daynight: refusals done\n");
 }
@@ -232,9 +176,6 @@ int main() {
     run<double>(ctx, MOD16_DAYNIGHT_F32, "float64 -> float32");
     run<double>(ctx, MOD16_DAYNIGHT_F64, "float64 -> float64");
     refusals(ctx);
-    EXPECT(mod16_destroy(ctx) == MOD16_OK);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_daynight: ok\n");
+    harness_finish(ctx);
     return 0;
 }

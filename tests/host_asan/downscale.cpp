@@ -16,56 +16,11 @@
 //            memory, three tiles, the last ragged, a pitched output
 #include <algorithm>
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
+#define HARNESS_NAME "host_asan_downscale"
+#include "harness.hpp"
 
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                     \
-    do {                                                                                 \
-        if (!(cond)) {                                                                   \
-            fprintf(stderr, "host_asan_downscale: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                     \
-        }                                                                                \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3, kFresh = 0x11;
 constexpr int64_t H = 5, W = 7, kPitch = W + 3;
-
-// `bytes` of payload between two runs of guard bytes, in one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes;
-    explicit Guarded(size_t b) : mem(b + 2 * kGuard, kGuardByte), bytes(b) { memset(data(), kFresh, b); }
-    unsigned char* data() { return mem.data() + kGuard; }
-    template <typename T> T* as() { return reinterpret_cast<T*>(data()); }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-    // elements [0, n) of every row overwritten (no element still all kFresh), [n, pitch) untouched
-    void check(int rows, int64_t pitch, int64_t n, size_t elem, bool written, const char* what) {
-        EXPECT(guards_intact());
-        std::vector<unsigned char> fresh(elem, kFresh);
-        for (int r = 0; r < rows; ++r)
-            for (int64_t i = 0; i < (r == rows - 1 ? n : pitch); ++i) {
-                const bool same = memcmp(data() + ((size_t)r * pitch + i) * elem, fresh.data(), elem) == 0;
-                if (same != (i >= n || !written)) {
-                    fprintf(stderr, "host_asan_downscale: %s, row %d element %lld: %s\n", what, r, (long long)i,
-                            same ? "not overwritten" : "overwritten");
-                    exit(1);
-                }
-            }
-    }
-};
 
 static mod16_downscale* make_grid(mod16_ctx* ctx, int64_t R, int64_t C, int method, int wrap) {
     mod16_downscale_spec spec = {R, C, H, W, wrap, method};
@@ -110,8 +65,8 @@ static void run_case(mod16_ctx* ctx, const Calls<T>& fn, int64_t R, int64_t C, i
         fprintf(stderr, "host_asan_downscale: %s: status %d: %s\n", what, rc, mod16_last_error(ctx));
         exit(1);
     }
-    day.check(1, n, n, sizeof(T), written, "out_day");
-    night.check(1, n, n, sizeof(T), written, "out_night");
+    check_written(day, 1, n, n, sizeof(T), written, "out_day");
+    check_written(night, 1, n, n, sizeof(T), written, "out_night");
     // refused before any device work (the outputs keep what they hold); n = 0 is fine
     Guarded keep(64 * sizeof(T));
     auto call = [&](const int32_t* kd, int64_t pitch, int64_t f, int64_t m, unsigned fl, int where) {
@@ -130,7 +85,7 @@ static void run_case(mod16_ctx* ctx, const Calls<T>& fn, int64_t R, int64_t C, i
     EXPECT(call(kinds, kPitch, first, 1, 0, 7) == MOD16_ERR_ARG);
     EXPECT(strstr(mod16_last_error(ctx), "mod16_et_downscaled") != nullptr);
     EXPECT(call(kinds, kPitch, R * C, 0, 0, MOD16_HOST) == MOD16_OK);
-    keep.check(1, 64, 64, sizeof(T), false, "outputs of the refused calls");
+    check_written(keep, 1, 64, 64, sizeof(T), false, "outputs of the refused calls");
     EXPECT(mod16_downscale_destroy(grid) == MOD16_OK);
     printf("host_asan_downscale: %s done\n", what);
 }
@@ -154,7 +109,7 @@ static void fields_case(mod16_ctx* ctx, const Calls<T>& fn, const char* what) {
         fprintf(stderr, "host_asan_downscale: %s: status %d: %s\n", what, rc, mod16_last_error(ctx));
         exit(1);
     }
-    out.check(F, pitch, n, sizeof(T), true, "fields");
+    check_written(out, F, pitch, n, sizeof(T), true, "fields");
     Guarded keep(64 * sizeof(T));
     EXPECT(fn.fields(ctx, grid, fields, 0, kPitch, first, 8, keep.as<T>(), 8, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
     EXPECT(fn.fields(ctx, grid, fields, 17, kPitch, first, 8, keep.as<T>(), 8, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
@@ -162,7 +117,7 @@ static void fields_case(mod16_ctx* ctx, const Calls<T>& fn, const char* what) {
     EXPECT(fn.fields(ctx, grid, fields, F, kPitch, first, 8, keep.as<T>(), 7, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
     EXPECT(fn.fields(ctx, grid, fields, F, kPitch, R * C - 7, 8, keep.as<T>(), 8, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
     EXPECT(fn.fields(ctx, grid, fields, F, kPitch, first, 0, keep.as<T>(), 0, MOD16_HOST, nullptr) == MOD16_OK);
-    keep.check(1, 64, 64, sizeof(T), false, "output of the refused calls");
+    check_written(keep, 1, 64, 64, sizeof(T), false, "output of the refused calls");
     EXPECT(mod16_downscale_destroy(grid) == MOD16_OK);
     printf("host_asan_downscale: %s done\n", what);
 }
@@ -228,8 +183,6 @@ int main() {
     setenv("MOD16_HOST_THREADS", "3", 1);
     all_cases<double>(Calls<double>{mod16_et_downscaled_f64, mod16_downscale_fields_f64}, "float64", true);
     all_cases<float>(Calls<float>{mod16_et_downscaled_f32, mod16_downscale_fields_f32}, "float32", false);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_downscale: ok\n");
+    harness_finish(nullptr);
     return 0;
 }

@@ -10,58 +10,13 @@
 // overwritten, no guard byte and no padding touched, every refusal before an output is touched,
 // nothing left allocated.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
+#define HARNESS_NAME "host_asan_downscale_rows"
+#include "harness.hpp"
 
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                          \
-    do {                                                                                      \
-        if (!(cond)) {                                                                        \
-            fprintf(stderr, "host_asan_downscale_rows: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                          \
-        }                                                                                     \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3, kFresh = 0x11;
 constexpr int64_t R = 60, C = 47, H = 5, W = 7, kPitch = W + 3;
 constexpr int64_t kSpan = (H - 1) * kPitch + W, kTime = kSpan + 5;      // a plane, and the distance between two
 constexpr int64_t kFirst = 777, kN = 1237;
-
-// `bytes` of payload between two runs of guard bytes, in one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes;
-    explicit Guarded(size_t b) : mem(b + 2 * kGuard, kGuardByte), bytes(b) { memset(data(), kFresh, b); }
-    unsigned char* data() { return mem.data() + kGuard; }
-    template <typename T> T* as() { return reinterpret_cast<T*>(data()); }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-    // elements [0, n) of every row overwritten (no element still all kFresh), [n, pitch) untouched
-    void check(int rows, int64_t pitch, int64_t n, size_t elem, bool written, const char* what) {
-        EXPECT(guards_intact());
-        std::vector<unsigned char> fresh(elem, kFresh);
-        for (int r = 0; r < rows; ++r)
-            for (int64_t i = 0; i < (r == rows - 1 ? n : pitch); ++i) {
-                const bool same = memcmp(data() + ((size_t)r * pitch + i) * elem, fresh.data(), elem) == 0;
-                if (same != (i >= n || !written)) {
-                    fprintf(stderr, "host_asan_downscale_rows: %s, row %d element %lld: %s\n", what, r, (long long)i,
-                            same ? "not overwritten" : "overwritten");
-                    exit(1);
-                }
-            }
-    }
-};
 
 // a heap block of exactly `count` elements
 template <typename T> struct Exact {
@@ -130,12 +85,7 @@ static void create_errors(mod16_ctx* ctx, const Geometry& g) {
         EXPECT(rc == MOD16_OK || !grid);
         return rc;
     };
-#define REFUSED(call, text)                                                              \
-    do {                                                                                 \
-        EXPECT((call) == MOD16_ERR_ARG);                                                 \
-        EXPECT(strncmp(mod16_last_error(ctx), "mod16_downscale_create: ", 24) == 0);     \
-        EXPECT(strstr(mod16_last_error(ctx), text) != nullptr);                          \
-    } while (0)
+#define REFUSED(call, text) EXPECT(refused(ctx, (call), "mod16_downscale_create: ", text))
     mod16_downscale_spec s = spec;
     // the spec, cos4 among it
     s.method = MOD16_DOWNSCALE_COS4;
@@ -220,13 +170,13 @@ static void run_case(mod16_ctx* ctx, const Calls<T>& fn, mod16_downscale* grid, 
         fprintf(stderr, "host_asan_downscale_rows: run: status %d: %s\n", rc, mod16_last_error(ctx));
         exit(1);
     }
-    day.check(1, kN, kN, sizeof(T), true, "out_day");
-    night.check(1, kN, kN, sizeof(T), true, "out_night");
+    check_written(day, 1, kN, kN, sizeof(T), true, "out_day");
+    check_written(night, 1, kN, kN, sizeof(T), true, "out_night");
     Guarded keep(64 * sizeof(T));
     EXPECT(fn.run(ctx, grid, cls.p, drivers, kinds, kPitch, R * C - 3, 4, keep.as<T>(), keep.as<T>(), flags, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
     EXPECT(fn.run(ctx, grid, cls.p, drivers, kinds, W - 1, kFirst, 1, keep.as<T>(), keep.as<T>(), flags, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
     EXPECT(fn.run(ctx, grid, cls.p, drivers, kinds, kPitch, R * C, 0, keep.as<T>(), keep.as<T>(), flags, MOD16_HOST, nullptr) == MOD16_OK);
-    keep.check(1, 64, 64, sizeof(T), false, "outputs of the refused calls");
+    check_written(keep, 1, 64, 64, sizeof(T), false, "outputs of the refused calls");
     for (auto* e : in) delete e;
 }
 
@@ -246,11 +196,11 @@ static void fields_case(mod16_ctx* ctx, const Calls<T>& fn, mod16_downscale* gri
         fprintf(stderr, "host_asan_downscale_rows: fields: status %d: %s\n", rc, mod16_last_error(ctx));
         exit(1);
     }
-    out.check(F, pitch, kN, sizeof(T), true, "fields");
+    check_written(out, F, pitch, kN, sizeof(T), true, "fields");
     Guarded keep(64 * sizeof(T));
     EXPECT(fn.fields(ctx, grid, fields, F, kPitch, R * C - 7, 8, keep.as<T>(), 8, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
     EXPECT(fn.fields(ctx, grid, fields, F, kPitch, kFirst, 8, keep.as<T>(), 7, MOD16_HOST, nullptr) == MOD16_ERR_ARG);
-    keep.check(1, 64, 64, sizeof(T), false, "output of the refused calls");
+    check_written(keep, 1, 64, 64, sizeof(T), false, "output of the refused calls");
     for (auto* e : in) delete e;
 }
 
@@ -302,10 +252,10 @@ static void composite_case(mod16_ctx* ctx, const Calls<T>& fn, mod16_downscale* 
             fprintf(stderr, "host_asan_downscale_rows: composite: status %d: %s\n", rc, mod16_last_error(ctx));
             exit(1);
         }
-        et.check(P, pitch, kN, sizeof(T), true, "out_et");
-        pet.check(P, pitch, kN, sizeof(T), all, "out_pet");
-        cet.check(P, pitch, kN, 2, all, "count_et");
-        cpet.check(P, pitch, kN, 2, all, "count_pet");
+        check_written(et, P, pitch, kN, sizeof(T), true, "out_et");
+        check_written(pet, P, pitch, kN, sizeof(T), all, "out_pet");
+        check_written(cet, P, pitch, kN, 2, all, "count_et");
+        check_written(cpet, P, pitch, kN, 2, all, "count_pet");
     }
     Guarded keep(64 * sizeof(T));
     mod16_composite_downscaled_spec s = spec;
@@ -313,7 +263,7 @@ static void composite_case(mod16_ctx* ctx, const Calls<T>& fn, mod16_downscale* 
     EXPECT(fn.composite(ctx, grid, &s, cls.p, drivers, hours.p, keep.as<T>(), nullptr, nullptr, nullptr, pitch, flags, MOD16_HOST,
                         nullptr, 0) == MOD16_ERR_ARG);
     EXPECT(strstr(mod16_last_error(ctx), "leaves the raster") != nullptr);
-    keep.check(1, 64, 64, sizeof(T), false, "output of the refused call");
+    check_written(keep, 1, 64, 64, sizeof(T), false, "output of the refused call");
     for (auto* e : in) delete e;
 }
 
@@ -348,8 +298,6 @@ int main() {
     setenv("MOD16_HOST_THREADS", "3", 1);
     all_cases<double>(Calls<double>{mod16_et_downscaled_f64, mod16_downscale_fields_f64, mod16_et_composite_downscaled_f64}, "float64", true);
     all_cases<float>(Calls<float>{mod16_et_downscaled_f32, mod16_downscale_fields_f32, mod16_et_composite_downscaled_f32}, "float32", false);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_downscale_rows: ok\n");
+    harness_finish(nullptr);
     return 0;
 }

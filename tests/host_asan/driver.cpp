@@ -12,15 +12,12 @@
 
 #include <hip/hip_runtime_api.h>
 
-#include "../../include/mod16_hip.h"
-
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-extern "C" void mod16_stub_fail_host_malloc(int k);      // k > 0: the next k calls fail; -k: the k-th next call fails, once
-extern "C" void mod16_stub_fail_malloc(int k);           // the k-th next hipMalloc / hipMallocAsync fails, once
+#define HARNESS_NAME "host_asan"
+#include "harness.hpp"      // the stand-in's declarations; this program's EXPECT and OK count their checks
 
 static int g_checks = 0;
-#define EXPECT(cond)                                                                       \
+#undef EXPECT
+#define EXPECT(cond)                                                                      \
     do {                                                                                   \
         ++g_checks;                                                                        \
         if (!(cond)) { fprintf(stderr, "host_asan: %s:%d: %s failed\n", __FILE__, __LINE__, #cond); exit(1); } \

@@ -7,58 +7,9 @@
 // byte of a pitched output touched, nothing left allocated.
 #include <algorithm>
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
-
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                   \
-    do {                                                                               \
-        if (!(cond)) {                                                                 \
-            fprintf(stderr, "host_asan_gapfill: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                   \
-        }                                                                              \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3, kFresh = 0x11;
-
-// `bytes` of payload between two runs of guard bytes, in one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes;
-    Guarded(size_t b, unsigned char fill) : mem(b + 2 * kGuard, kGuardByte), bytes(b) { memset(data(), fill, b); }
-    unsigned char* data() { return mem.data() + kGuard; }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-};
-
-// rows x pitch elements of `elem` bytes: [r][0, n) overwritten (no element still holds kFresh in
-// every byte), [r][n, pitch) untouched (the last row ends with its n elements)
-static void check_output(Guarded& g, int rows, int64_t pitch, int64_t n, size_t elem, const char* what) {
-    EXPECT(g.guards_intact());
-    std::vector<unsigned char> fresh(elem, kFresh);
-    for (int r = 0; r < rows; ++r)
-        for (int64_t i = 0; i < (r == rows - 1 ? std::max<int64_t>(n, 1) : pitch); ++i) {
-            const bool same = memcmp(g.data() + ((size_t)r * pitch + i) * elem, fresh.data(), elem) == 0;
-            if (same != (i >= n)) {
-                fprintf(stderr, "host_asan_gapfill: %s, row %d element %lld: %s\n", what, r, (long long)i,
-                        same ? "not overwritten" : "padding overwritten");
-                exit(1);
-            }
-        }
-}
-
-static size_t rows_bytes(int rows, int64_t pitch, int64_t n, size_t elem) { return ((size_t)(rows - 1) * pitch + n) * elem; }
+#define HARNESS_NAME "host_asan_gapfill"
+#include "harness.hpp"
 
 static void run(mod16_ctx* ctx, int out_type, int S, const char* what) {
     const int64_t n = 1237, pitch = n + 19, qpitch = n + 3, opitch = n + 7, spitch = n + 1;
@@ -79,14 +30,14 @@ static void run(mod16_ctx* ctx, int out_type, int S, const char* what) {
             const uint8_t* fields[3] = {nullptr, nullptr, nullptr};
             const uint8_t* fallback[3] = {nullptr, nullptr, nullptr};
             for (int f = 0; f < nf; ++f) {
-                in.emplace_back(rows_bytes(S, pitch, n, 1), (unsigned char)(40 + f));
+                in.emplace_back(span(S, pitch, n, 1), (unsigned char)(40 + f));
                 fields[f] = in.back().data();
                 if (all && f != 1) {                 // (field 1 goes without)
                     fb.emplace_back((size_t)n, (unsigned char)7);
                     fallback[f] = fb.back().data();
                 }
             }
-            Guarded qc(rows_bytes(S, qpitch, n, 1), 0), good(256, 1);
+            Guarded qc(span(S, qpitch, n, 1), 0), good(256, 1);
             // the slab of a slot: 3 output arrays apart by the stagger, rows of outputs and bytes per pixel
             const int wide_rows = nf * S + (3 - nf);
             const int byte_rows = nf * S + (3 - nf) + (all ? S : 1) + 3 + (all ? nf * S : 1);
@@ -98,10 +49,10 @@ static void run(mod16_ctx* ctx, int out_type, int S, const char* what) {
                 out.reserve(3);
                 void* outs[3] = {nullptr, nullptr, nullptr};
                 for (int f = 0; f < nf; ++f) {
-                    out.emplace_back(rows_bytes(S, opitch, n, elem), kFresh);
+                    out.emplace_back(span(S, opitch, n, elem), kFresh);
                     outs[f] = out.back().data();
                 }
-                Guarded source(rows_bytes(nf * S, spitch, n, 1), kFresh);
+                Guarded source(span(nf * S, spitch, n, 1), kFresh);
                 const int rc = mod16_gapfill_u8(ctx, &spec, fields, all ? qc.data() : nullptr, all ? good.data() : nullptr,
                                                 all ? fallback : nullptr, outs, all ? source.data() : nullptr, MOD16_HOST,
                                                 nullptr, stage);
@@ -109,8 +60,8 @@ static void run(mod16_ctx* ctx, int out_type, int S, const char* what) {
                     fprintf(stderr, "host_asan_gapfill: %s: status %d: %s\n", what, rc, mod16_last_error(ctx));
                     exit(1);
                 }
-                for (int f = 0; f < nf; ++f) check_output(out[f], S, opitch, n, elem, "out");
-                check_output(source, nf * S, spitch, all ? n : 0, 1, "source");
+                for (int f = 0; f < nf; ++f) check_written(out[f], S, opitch, n, elem, true, "out");
+                check_written(source, nf * S, spitch, n, 1, all != 0, "source");
             }
             for (Guarded& g : in) EXPECT(g.guards_intact());
             for (Guarded& g : fb) EXPECT(g.guards_intact());
@@ -123,8 +74,8 @@ static void run(mod16_ctx* ctx, int out_type, int S, const char* what) {
 static void refusals(mod16_ctx* ctx) {
     const int64_t n = 300;
     const int S = 4;
-    Guarded a(rows_bytes(S, n, n, 1), 50), b(rows_bytes(S, n, n, 1), 60), qc(rows_bytes(S, n, n, 1), 0);
-    Guarded out0(rows_bytes(S, n, n, 8), kFresh), out1(rows_bytes(S, n, n, 8), kFresh), src(rows_bytes(2 * S, n, n, 1), kFresh);
+    Guarded a(span(S, n, n, 1), 50), b(span(S, n, n, 1), 60), qc(span(S, n, n, 1), 0);
+    Guarded out0(span(S, n, n, 8), kFresh), out1(span(S, n, n, 8), kFresh), src(span(2 * S, n, n, 1), kFresh);
     const uint8_t* fields[3] = {a.data(), b.data(), nullptr};
     void* outs[3] = {out0.data(), out1.data(), nullptr};
     mod16_gapfill_spec spec;
@@ -166,9 +117,9 @@ static void refusals(mod16_ctx* ctx) {
     EXPECT(call(s, fields, outs, out1.data() + 3, MOD16_HOST) == MOD16_ERR_ARG);
     EXPECT(call(s, fields, outs, a.data(), MOD16_DEVICE) == MOD16_ERR_ARG);
     s = spec; s.n = 0; EXPECT(call(s, fields, outs, src.data(), MOD16_HOST) == MOD16_OK);
-    check_output(out0, S, n, 0, 8, "out[0] of the refused calls");
-    check_output(out1, S, n, 0, 8, "out[1] of the refused calls");
-    check_output(src, 2 * S, n, 0, 1, "source of the refused calls");
+    check_written(out0, S, n, n, 8, false, "out[0] of the refused calls");
+    check_written(out1, S, n, n, 8, false, "out[1] of the refused calls");
+    check_written(src, 2 * S, n, n, 1, false, "source of the refused calls");
     EXPECT(a.guards_intact() && b.guards_intact() && qc.guards_intact());
     printf("host_asan_gapfill: refusals done\n");
 }
@@ -184,9 +135,6 @@ int main() {
         run(ctx, types[k], 1, names[k]);
     }
     refusals(ctx);
-    EXPECT(mod16_destroy(ctx) == MOD16_OK);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_gapfill: ok\n");
+    harness_finish(ctx);
     return 0;
 }

@@ -7,52 +7,12 @@
 // all outputs and a subset, both input types. Pass: no sanitizer report, every requested output
 // element overwritten, no guard byte and no byte between the rows touched, nothing left allocated.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
+#define HARNESS_NAME "host_asan_trend"
+#include "harness.hpp"
 
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            fprintf(stderr, "host_asan_trend: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                 \
-        }                                                                            \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3, kFresh = 0x11;
 constexpr int kOutputs = 5;
-
-// `bytes` of payload between two runs of guard bytes, in one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes;
-    Guarded(size_t b, unsigned char fill) : mem(b + 2 * kGuard, kGuardByte), bytes(b) { memset(data(), fill, b); }
-    unsigned char* data() { return mem.data() + kGuard; }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-    // every element of `elem` bytes overwritten (no element still holds kFresh in every byte), or none
-    void check(size_t elem, bool written, const char* what) {
-        EXPECT(guards_intact());
-        std::vector<unsigned char> fresh(elem, kFresh);
-        for (size_t i = 0; i < bytes / elem; ++i)
-            if ((memcmp(data() + i * elem, fresh.data(), elem) == 0) == written) {
-                fprintf(stderr, "host_asan_trend: %s, element %zu: %s\n", what, i, written ? "not overwritten" : "overwritten");
-                exit(1);
-            }
-    }
-};
 
 template <typename IN>
 static int call(mod16_ctx* ctx, const mod16_trend_spec* spec, const void* values, const double* times, double* const* out,
@@ -98,9 +58,9 @@ static void run(mod16_ctx* ctx, const char* what) {
                             fprintf(stderr, "host_asan_trend: %s: status %d: %s\n", what, rc, mod16_last_error(ctx));
                             exit(1);
                         }
-                        for (Guarded& g : out) g.check(8, true, "out");
-                        s.check(4, all != 0, "s");
-                        count.check(1, true, "count");
+                        for (Guarded& g : out) check_written(g, 8, true, "out");
+                        check_written(s, 4, all != 0, "s");
+                        check_written(count, 1, true, "count");
                     }
                     EXPECT(in.guards_intact());
                 }
@@ -123,10 +83,7 @@ static void refusals(mod16_ctx* ctx) {
     auto go = [&](const mod16_trend_spec& sp, double* const* o, int where) {
         return call<double>(ctx, &sp, x.data(), times.data(), o, s, count, where, 0);
     };
-    auto refused = [&](int rc, const char* part) {
-        return rc == MOD16_ERR_ARG && strncmp(mod16_last_error(ctx), "mod16_trend: ", 13) == 0 &&
-               strstr(mod16_last_error(ctx), part) != nullptr;
-    };
+    auto refused = [&](int rc, const char* part) { return ::refused(ctx, rc, "mod16_trend: ", part); };
     const double inf = std::numeric_limits<double>::infinity();
     mod16_trend_spec sp = spec;
     EXPECT(refused(call<double>(ctx, nullptr, x.data(), times.data(), outs, s, count, MOD16_HOST, 0), "NULL spec"));
@@ -171,10 +128,10 @@ static void refusals(mod16_ctx* ctx) {
     sp = spec; sp.n = 0; sp.time_stride = 0; EXPECT(go(sp, outs, MOD16_HOST) == MOD16_OK);
     EXPECT(go(sp, outs, MOD16_DEVICE) == MOD16_OK);
     EXPECT(mod16_trend_max_steps() == 64);
-    o0.check(8, false, "out[0] of the refused calls");
-    o1.check(8, false, "out[4] of the refused calls");
-    sv.check(4, false, "s of the refused calls");
-    cv.check(1, false, "count of the refused calls");
+    check_written(o0, 8, false, "out[0] of the refused calls");
+    check_written(o1, 8, false, "out[4] of the refused calls");
+    check_written(sv, 4, false, "s of the refused calls");
+    check_written(cv, 1, false, "count of the refused calls");
     EXPECT(x.guards_intact());
     printf("host_asan_trend: refusals done\n");
 }
@@ -185,9 +142,6 @@ int main() {
     run<float>(ctx, "float32");
     run<double>(ctx, "float64");
     refusals(ctx);
-    EXPECT(mod16_destroy(ctx) == MOD16_OK);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_trend: ok\n");
+    harness_finish(ctx);
     return 0;
 }

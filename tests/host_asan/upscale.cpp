@@ -10,62 +10,9 @@
 // sanitizer report, every requested output element overwritten, no guard byte and no element between the
 // rows or the layers touched, nothing left allocated.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
-
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                   \
-    do {                                                                               \
-        if (!(cond)) {                                                                 \
-            fprintf(stderr, "host_asan_upscale: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                   \
-        }                                                                              \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3, kFresh = 0x11;
-
-// `layers` layers of `rows` rows of n elements of `elem` bytes, rows `pitch` and layers `plane` elements
-// apart, between two runs of guard bytes, in one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes, elem;
-    int64_t layers, plane, rows, pitch, n;
-    Guarded(int64_t layers_, int64_t plane_, int64_t rows_, int64_t pitch_, int64_t n_, size_t elem_, unsigned char fill)
-        : mem((size_t)((layers_ - 1) * plane_ + (rows_ - 1) * pitch_ + n_) * elem_ + 2 * kGuard, kGuardByte),
-          bytes((size_t)((layers_ - 1) * plane_ + (rows_ - 1) * pitch_ + n_) * elem_), elem(elem_), layers(layers_),
-          plane(plane_), rows(rows_), pitch(pitch_), n(n_) {
-        memset(data(), fill, bytes);
-    }
-    unsigned char* data() { return mem.data() + kGuard; }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-    // every element of the rows overwritten (none still holds kFresh in every byte), or none; the elements
-    // between the rows and between the layers untouched either way
-    void check(bool written, const char* what) {
-        EXPECT(guards_intact());
-        std::vector<unsigned char> fresh(elem, kFresh);
-        for (size_t i = 0; i < bytes / elem; ++i) {
-            const int64_t in_plane = (int64_t)i % plane;
-            const bool in_row = in_plane / pitch < rows && in_plane % pitch < n;
-            const bool is_fresh = memcmp(data() + i * elem, fresh.data(), elem) == 0;
-            if (is_fresh == (in_row && written)) {
-                fprintf(stderr, "host_asan_upscale: %s, element %zu: %s\n", what, i, is_fresh ? "not overwritten" : "overwritten");
-                exit(1);
-            }
-        }
-    }
-};
+#define HARNESS_NAME "host_asan_upscale"
+#include "harness.hpp"
 
 struct Axis {
     std::vector<int32_t> first, count;
@@ -89,10 +36,10 @@ static Axis axis(std::vector<int32_t> lengths, int64_t margin, bool reversed) {
 
 template <typename T>
 static int call(mod16_ctx* ctx, const mod16_upscale* grid, const void* values, int32_t layers, int64_t ls, int64_t rs, double mf,
-                Guarded* mean, Guarded* fraction, Guarded* count, int where, size_t stage) {
-    auto p = [](Guarded* g) { return g ? g->data() : nullptr; };
-    auto l = [](Guarded* g) { return g ? g->plane : 0; };
-    auto r = [](Guarded* g) { return g ? g->pitch : 0; };
+                Shaped* mean, Shaped* fraction, Shaped* count, int where, size_t stage) {
+    auto p = [](Shaped* g) { return g ? g->data() : nullptr; };
+    auto l = [](Shaped* g) { return g ? g->plane : 0; };
+    auto r = [](Shaped* g) { return g ? g->pitch : 0; };
     if (sizeof(T) == 4)
         return mod16_upscale_f32(ctx, grid, static_cast<const float*>(values), layers, ls, rs, mf, reinterpret_cast<float*>(p(mean)), l(mean),
                                  r(mean), reinterpret_cast<float*>(p(fraction)), l(fraction), r(fraction),
@@ -132,13 +79,13 @@ static void run(mod16_ctx* ctx, const char* what) {
                 for (int all = 0; all < 2; ++all) {
                     const int64_t rs = pitched ? C + 5 : C, ls = pitched ? R * rs + 9 : R * C;
                     const int64_t ors = pitched ? W + 3 : W, ols = pitched ? H * ors + 7 : H * W;
-                    Guarded values(K, ls, R, rs, C, sizeof(T), 0);
+                    Shaped values(K, ls, R, rs, C, sizeof(T), 0);
                     // one layer of the tallest coarse row: its 8 fine rows and its row of the three outputs, each in whole 256-byte lines
                     const size_t coarse_row = 8 * (size_t)C * sizeof(T) + 3 * 256;
                     const size_t stages[] = {1, (size_t)K * 2 * coarse_row + 1280, 0};
                     for (size_t stage : stages) {
-                        Guarded mean(K, ols, H, ors, W, sizeof(T), kFresh), fraction(K, ols, H, ors, W, sizeof(T), kFresh);
-                        Guarded count(K, ols, H, ors, W, 4, kFresh);
+                        Shaped mean(K, ols, H, ors, W, sizeof(T), kFresh), fraction(K, ols, H, ors, W, sizeof(T), kFresh);
+                        Shaped count(K, ols, H, ors, W, 4, kFresh);
                         ok(ctx, call<T>(ctx, grid, values.data(), K, ls, rs, 0.5, &mean, all ? &fraction : nullptr, all ? &count : nullptr,
                                         MOD16_HOST, stage), what);
                         mean.check(true, "mean");
@@ -150,9 +97,9 @@ static void run(mod16_ctx* ctx, const char* what) {
         if (sizeof(T) == 4) {                              // the class raster once per geometry
             for (int pitched = 0; pitched < 2; ++pitched) {
                 const int64_t rs = pitched ? C + 5 : C, ors = pitched ? W + 3 : W;
-                Guarded cls(1, R * rs, R, rs, C, 1, 0);
+                Shaped cls(1, R * rs, R, rs, C, 1, 0);
                 for (size_t stage : {(size_t)1, (size_t)(2 * (8 * C + 2 * 256) + 1024), (size_t)0}) {
-                    Guarded out_cls(1, H * ors, H, ors, W, 1, kFresh), share(1, H * ors, H, ors, W, 4, kFresh);
+                    Shaped out_cls(1, H * ors, H, ors, W, 1, kFresh), share(1, H * ors, H, ors, W, 4, kFresh);
                     ok(ctx, mod16_upscale_classes(ctx, grid, cls.data(), rs, 0x1fffu, out_cls.data(), ors,
                                                   pitched ? nullptr : reinterpret_cast<float*>(share.data()), ors, MOD16_HOST, nullptr, stage),
                        "classes");
@@ -180,10 +127,7 @@ static void refusals(mod16_ctx* ctx) {
         grid = reinterpret_cast<mod16_upscale*>(&spec);
         return mod16_upscale_create(ctx, &sp, rf.data(), rc.data(), cf.data(), cc.data(), area, &grid);
     };
-    auto refused = [&](int rc, const char* prefix, const char* part) {
-        return rc == MOD16_ERR_ARG && strncmp(mod16_last_error(ctx), prefix, strlen(prefix)) == 0 &&
-               strstr(mod16_last_error(ctx), part) != nullptr;
-    };
+    auto refused = [&](int rc, const char* prefix, const char* part) { return ::refused(ctx, rc, prefix, part); };
     const char* const cr = "mod16_upscale_create: ";
     mod16_upscale_spec sp = spec;
     EXPECT(refused(mod16_upscale_create(ctx, nullptr, rows.first.data(), rows.count.data(), cols.first.data(), cols.count.data(), nullptr, &grid), cr, "NULL argument"));
@@ -220,8 +164,8 @@ static void refusals(mod16_ctx* ctx) {
     EXPECT(grid && grid != reinterpret_cast<mod16_upscale*>(&spec));
 
     const int32_t K = 2;
-    Guarded values(K, R * C, R, C, C, 8, 0), mean(K, H * W, H, W, W, 8, kFresh), fraction(K, H * W, H, W, W, 8, kFresh);
-    Guarded count(K, H * W, H, W, W, 4, kFresh);
+    Shaped values(K, R * C, R, C, C, 8, 0), mean(K, H * W, H, W, W, 8, kFresh), fraction(K, H * W, H, W, W, 8, kFresh);
+    Shaped count(K, H * W, H, W, W, 4, kFresh);
     const char* const up = "mod16_upscale: ";
     auto go = [&](const mod16_upscale* g, const void* v, int32_t layers, int64_t ls, int64_t rs, double mf, int where, size_t stage) {
         return call<double>(ctx, g, v, layers, ls, rs, mf, &mean, &fraction, &count, where, stage);
@@ -239,7 +183,7 @@ static void refusals(mod16_ctx* ctx) {
     EXPECT(refused(go(grid, values.data(), K, R * C, C, 0.0, 7, 0), up, "`where` must be"));
     EXPECT(refused(go(grid, values.data(), K, R * C, C, 0.0, MOD16_HOST, ~size_t(0)), up, "stage_bytes"));
     {
-        Guarded narrow(K, H * W, H, W - 1, W - 1, 8, kFresh);
+        Shaped narrow(K, H * W, H, W - 1, W - 1, 8, kFresh);
         EXPECT(refused(call<double>(ctx, grid, values.data(), K, R * C, C, 0.0, &narrow, nullptr, nullptr, MOD16_HOST, 0), up, "a row stride is below"));
         narrow.check(false, "the narrow mean");
         // an output on the input, two outputs on each other
@@ -252,7 +196,7 @@ static void refusals(mod16_ctx* ctx) {
                        up, "overlaps"));
     }
     const char* const uc = "mod16_upscale_classes: ";
-    Guarded cls(1, R * C, R, C, C, 1, 0), out_cls(1, H * W, H, W, W, 1, kFresh), share(1, H * W, H, W, W, 4, kFresh);
+    Shaped cls(1, R * C, R, C, C, 1, 0), out_cls(1, H * W, H, W, W, 1, kFresh), share(1, H * W, H, W, W, 4, kFresh);
     auto classes = [&](const mod16_upscale* g, const void* c, int64_t rs, void* oc, int64_t ors, void* os, int where, size_t stage) {
         return mod16_upscale_classes(ctx, g, static_cast<const uint8_t*>(c), rs, 0x1fffu, static_cast<uint8_t*>(oc), ors,
                                      static_cast<float*>(os), W, where, nullptr, stage);
@@ -282,9 +226,6 @@ int main() {
     run<float>(ctx, "float32");
     run<double>(ctx, "float64");
     refusals(ctx);
-    EXPECT(mod16_destroy(ctx) == MOD16_OK);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_upscale: ok\n");
+    harness_finish(ctx);
     return 0;
 }

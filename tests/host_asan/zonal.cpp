@@ -8,49 +8,19 @@
 // checked word for word. Pass: no sanitizer report, no guard byte touched, nothing left allocated,
 // every refusal returned before acc is touched.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "../../include/mod16_hip.h"
-
-extern "C" void mod16_stub_report(FILE* f);
-extern "C" size_t mod16_stub_live_allocations(void);
-
-#define EXPECT(cond)                                                                 \
-    do {                                                                             \
-        if (!(cond)) {                                                               \
-            fprintf(stderr, "host_asan_zonal: %s failed (line %d)\n", #cond, __LINE__); \
-            exit(1);                                                                 \
-        }                                                                            \
-    } while (0)
-
-constexpr size_t kGuard = 64;
-constexpr unsigned char kGuardByte = 0xC3;
-
-// `bytes` of payload between two runs of guard bytes, in one heap block of its own
-struct Guarded {
-    std::vector<unsigned char> mem;
-    size_t bytes;
-    Guarded(size_t b, unsigned char fill) : mem(b + 2 * kGuard, kGuardByte), bytes(b) { memset(data(), fill, b); }
-    unsigned char* data() { return mem.data() + kGuard; }
-    bool guards_intact() const {
-        for (size_t i = 0; i < kGuard; ++i)
-            if (mem[i] != kGuardByte || mem[kGuard + bytes + i] != kGuardByte) return false;
-        return true;
-    }
-    bool all(unsigned char v) const {
-        for (size_t i = 0; i < bytes; ++i)
-            if (mem[kGuard + i] != v) return false;
-        return true;
-    }
-};
+#define HARNESS_NAME "host_asan_zonal"
+#include "harness.hpp"
 
 constexpr int64_t kN = 1237, kCols = 67, kFirst = 5;
 constexpr int kLayers = 3, kZones = 40;
 constexpr unsigned char kAccByte = 0x17;
+
+static bool all(Guarded& g, unsigned char v) {
+    for (size_t i = 0; i < g.bytes; ++i)
+        if (g.data()[i] != v) return false;
+    return true;
+}
 
 static mod16_zonal_spec base_spec(int zone_type, int weight_kind) {
     mod16_zonal_spec s;
@@ -108,7 +78,7 @@ static void run(mod16_ctx* ctx, const char* what) {
                     exit(1);
                 }
                 // (no kernel ran: the accumulator's round trip, and the maxima the stand-in's zeroed words give)
-                EXPECT(acc.guards_intact() && acc.all(kAccByte));
+                EXPECT(acc.guards_intact() && all(acc, kAccByte));
                 EXPECT(xmax == 0.0 && wmax == (wk == MOD16_ZONAL_WEIGHT_NONE ? 1.0 : 0.0));
             }
             EXPECT(values.guards_intact() && zones.guards_intact() && weights.guards_intact());
@@ -165,8 +135,8 @@ static void refusals(mod16_ctx* ctx) {
     EXPECT(mod16_zonal_bounds_f64(ctx, &spec, v, weights.data(), nullptr, &xmax, MOD16_HOST, nullptr, 0) == MOD16_ERR_ARG);
     EXPECT(mod16_zonal_bounds_f64(ctx, &spec, v, nullptr, &wmax, &xmax, MOD16_HOST, nullptr, 0) == MOD16_ERR_ARG);
     s = spec; s.n = 0; EXPECT(call(s, v, zones.data(), weights.data(), a, MOD16_HOST) == MOD16_OK);
-    EXPECT(acc.guards_intact() && acc.all(kAccByte));
-    EXPECT(values.guards_intact() && values.all(0) && zones.guards_intact() && weights.guards_intact());
+    EXPECT(acc.guards_intact() && all(acc, kAccByte));
+    EXPECT(values.guards_intact() && all(values, 0) && zones.guards_intact() && weights.guards_intact());
     EXPECT(mod16_zonal_lds_zones() >= 256);
     printf("host_asan_zonal: refusals done\n");
 }
@@ -178,9 +148,6 @@ int main() {
     run<double>(ctx, "float64");
     run<float>(ctx, "float32");
     refusals(ctx);
-    EXPECT(mod16_destroy(ctx) == MOD16_OK);
-    mod16_stub_report(stdout);
-    EXPECT(mod16_stub_live_allocations() == 0);
-    printf("host_asan_zonal: ok\n");
+    harness_finish(ctx);
     return 0;
 }

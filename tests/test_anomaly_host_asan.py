@@ -1,7 +1,7 @@
 """The HOST mode of mod16_anomaly_f32 / _f64 under AddressSanitizer + UndefinedBehaviorSanitizer: the
 library's host half (`hipcc --cuda-host-only -fsanitize=address,undefined`, its own source) linked,
 unchanged, against the HIP stand-in of tests/host_asan, and driven by a stand-alone program
-(tests/host_asan_anomaly/driver.cpp) that calls the HOST-mode anomaly with guard bytes around every host
+(tests/host_asan/anomaly.cpp) that calls the HOST-mode anomaly with guard bytes around every host
 array: n = 37 and 300 pixels, (Y, P, W) = (3, 5, 2) and (33, 2, 1), with and without den, three
 stage_bytes (the smallest range of pixels -- 256 and 44 of 300 --, a slab cut from the bytes of a range's
 rows, one chunk), dense arrays and arrays whose three strides exceed n, every output and a subset, both
@@ -15,23 +15,12 @@ for the inputs and for z / pct, P rows of the climatology in three element sizes
 their place), the range cut from stage_bytes and the entry point's checks -- not the kernel's own
 address arithmetic, which tests/test_gpu_anomaly.py covers on the device with strided arrays at odd
 offsets. Sanitizers run on the CPU build only; nothing here is loaded into Python."""
-import os
-import subprocess
-
-from conftest import ROOT
+from host_asan_harness import launched, run_harness
 
 
 def test_host_mode_anomaly_is_clean_under_asan_and_ubsan(tmp_path):
-    script = os.path.join(ROOT, 'tests', 'host_asan_anomaly', 'build_and_run.sh')
-    proc = subprocess.run(['bash', script, str(tmp_path)], capture_output=True, text=True, timeout=900)
-    out = proc.stdout + proc.stderr
-    assert proc.returncode == 0, out[-4000:]
-    assert 'host_asan_anomaly: ok' in out, out[-2000:]
-    assert 'ERROR: AddressSanitizer' not in out and 'runtime error:' not in out and 'LeakSanitizer' not in out, out[-4000:]
+    out, lines = run_harness('anomaly', tmp_path)
     for name in ('float32', 'float64'):
         assert 'host_asan_anomaly: %s done' % name in out
     assert 'host_asan_anomaly: refusals done' in out
-    lines = out.splitlines()
-    assert any('14anomaly_kernel' in l for l in lines if l.strip().startswith('launches'))
-    report = [l for l in lines if l.startswith('hip_stub:') and 'live allocations' in l]
-    assert report and report[-1].rstrip().endswith('live allocations 0'), report
+    assert launched(lines, '14anomaly_kernel')

@@ -1,7 +1,7 @@
 """The HOST mode of mod16_daynight_f32 / _f64 under AddressSanitizer + UndefinedBehaviorSanitizer: the
 library's host half (`hipcc --cuda-host-only -fsanitize=address,undefined`, its own source) linked,
 unchanged, against the HIP stand-in of tests/host_asan, and driven by a stand-alone program
-(tests/host_asan_daynight/driver.cpp) that calls the HOST-mode aggregation with guard bytes around
+(tests/host_asan/daynight.cpp) that calls the HOST-mode aggregation with guard bytes around
 every host array: a 7 x 37 grid, D = 5 days of H = 3 steps in chunks of 2 days (ragged), of 1 day and
 in one chunk, dense and pitched fields and outputs (row pitch and plane stride of their own), every
 output and three of them, both modes, both input and both output types. Clean = no sanitizer report,
@@ -15,24 +15,13 @@ rows, by what is dense), the chunk cut from stage_bytes, the table uploads and t
 checks -- not the kernel's own address arithmetic, which tests/test_gpu_daynight.py covers on the
 device with pitched buffers at odd offsets. Sanitizers run on the CPU build only; nothing here is
 loaded into Python."""
-import os
-import subprocess
-
-from conftest import ROOT
+from host_asan_harness import launched, run_harness
 
 
 def test_host_mode_daynight_is_clean_under_asan_and_ubsan(tmp_path):
-    script = os.path.join(ROOT, 'tests', 'host_asan_daynight', 'build_and_run.sh')
-    proc = subprocess.run(['bash', script, str(tmp_path)], capture_output=True, text=True, timeout=900)
-    out = proc.stdout + proc.stderr
-    assert proc.returncode == 0, out[-4000:]
-    assert 'host_asan_daynight: ok' in out, out[-2000:]
-    assert 'ERROR: AddressSanitizer' not in out and 'runtime error:' not in out and 'LeakSanitizer' not in out, out[-4000:]
+    out, lines = run_harness('daynight', tmp_path)
     for name in ('float32 -> float32', 'float32 -> float64', 'float64 -> float32', 'float64 -> float64'):
         assert 'host_asan_daynight: %s done' % name in out
     assert 'host_asan_daynight: refusals done' in out
-    lines = out.splitlines()
-    assert any('15daynight_kernel' in l for l in lines if l.strip().startswith('launches'))
-    assert any('22daynight_annual_kernel' in l for l in lines if l.strip().startswith('launches'))
-    report = [l for l in lines if l.startswith('hip_stub:') and 'live allocations' in l]
-    assert report and report[-1].rstrip().endswith('live allocations 0'), report
+    assert launched(lines, '15daynight_kernel')
+    assert launched(lines, '22daynight_annual_kernel')

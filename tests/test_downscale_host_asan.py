@@ -2,7 +2,7 @@
 tables of mod16_downscale_create, under AddressSanitizer + UndefinedBehaviorSanitizer: the library's
 host half (`hipcc --cuda-host-only -fsanitize=address,undefined`, its own source) linked, unchanged,
 against the HIP stand-in of tests/host_asan, and driven by a stand-alone program
-(tests/host_asan_downscale/driver.cpp) for both data types:
+(tests/host_asan/downscale.cpp) for both data types:
 
   small    1237 pixels from pixel 777 of a 60 x 47 raster (not row-aligned): coarse planes with a row
            pitch of W + 3 in heap blocks of exactly their size (the last row ends with its W elements),
@@ -21,25 +21,14 @@ The downscale kernels have no shadow in the stand-in: their launches are checked
 only. Their own address arithmetic is covered on the device by tests/test_gpu_downscale.py (ranges,
 pitches, poisoned padding). Sanitizers run on the CPU build only, and nothing sanitised is loaded
 into Python."""
-import os
-import subprocess
-
-from conftest import ROOT
+from host_asan_harness import launched, run_harness
 
 
 def test_host_mode_downscale_is_clean_under_asan_and_ubsan(tmp_path):
-    script = os.path.join(ROOT, 'tests', 'host_asan_downscale', 'build_and_run.sh')
-    proc = subprocess.run(['bash', script, str(tmp_path)], capture_output=True, text=True, timeout=900)
-    out = proc.stdout + proc.stderr
-    assert proc.returncode == 0, out[-4000:]
-    assert 'host_asan_downscale: ok' in out, out[-2000:]
-    assert 'ERROR: AddressSanitizer' not in out and 'runtime error:' not in out and 'LeakSanitizer' not in out, out[-4000:]
+    out, lines = run_harness('downscale', tmp_path)
     for name in ('create', 'float64 small', 'float64 ragged', 'float64 fields', 'float32 small', 'float32 ragged',
                  'float32 fields'):
         assert 'host_asan_downscale: %s done' % name in out, name
-    lines = out.splitlines()
     # both instances, the kernel behind the fast one and the fields kernel were launched
     for kernel in ('9ds_kernel', '14ds_redo_kernel', '16ds_fields_kernel'):
-        assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
-    report = [l for l in lines if l.startswith('hip_stub:') and 'live allocations' in l]
-    assert report and report[-1].rstrip().endswith('live allocations 0'), report
+        assert launched(lines, kernel), kernel

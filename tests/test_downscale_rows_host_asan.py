@@ -3,7 +3,7 @@ UndefinedBehaviorSanitizer: mod16_downscale_create_rows and mod16_downscale_crea
 HOST mode of mod16_et_downscaled_*, mod16_downscale_fields_* and mod16_et_composite_downscaled_* on a
 row-affine handle -- the library's host half (`hipcc --cuda-host-only -fsanitize=address,undefined`, its
 own source) linked, unchanged, against the HIP stand-in of tests/host_asan, and driven by a stand-alone
-program (tests/host_asan_downscale_rows/driver.cpp) for both data types:
+program (tests/host_asan/downscale_rows.cpp) for both data types:
 
   create     both functions; every refusal (cos4, a non-finite origin, scale or far end -- in the
              LAST row, NULLs, the spec, the row tables) with its text, and the handle left NULL
@@ -19,24 +19,15 @@ nothing left allocated, and the row-affine instances of all five kernels among t
 launches. The kernels have no shadow in the stand-in: their own arithmetic is covered on the device by
 tests/test_gpu_downscale_rows.py. Sanitizers run on the CPU build only, and nothing sanitised is loaded
 into Python."""
-import os
-import subprocess
-
-from conftest import ROOT
+from host_asan_harness import run_harness
 
 
 def test_host_mode_row_affine_downscale_is_clean_under_asan_and_ubsan(tmp_path):
-    script = os.path.join(ROOT, 'tests', 'host_asan_downscale_rows', 'build_and_run.sh')
-    proc = subprocess.run(['bash', script, str(tmp_path)], capture_output=True, text=True, timeout=900)
-    out = proc.stdout + proc.stderr
-    assert proc.returncode == 0, out[-4000:]
-    assert 'host_asan_downscale_rows: ok' in out, out[-2000:]
-    assert 'ERROR: AddressSanitizer' not in out and 'runtime error:' not in out and 'LeakSanitizer' not in out, out[-4000:]
+    out, lines = run_harness('downscale_rows', tmp_path)
     assert 'host_asan_downscale_rows: create done' in out
     for dtype in ('float64', 'float32'):
         for case in ('run', 'fields', 'composite'):
             assert 'host_asan_downscale_rows: %s %s done' % (dtype, case) in out, (dtype, case)
-    lines = out.splitlines()
     # the row-affine instances of the five kernels were launched, for both data types
     shapes = [l for l in lines if l.strip().startswith('launch shape only')]
     for kernel in ('9ds_kernelI%sLb0E', '9ds_kernelI%sLb1E', '14ds_redo_kernelI%s', '16ds_fields_kernelI%s',
@@ -45,5 +36,3 @@ def test_host_mode_row_affine_downscale_is_clean_under_asan_and_ubsan(tmp_path):
         for t in 'df':
             assert any((kernel % t) + 'NS_10DsRowsGridE' in l for l in shapes), kernel % t
     assert not any('6DsGridE' in l for l in shapes)          # and no rectilinear one: the handle's geometry picks
-    report = [l for l in lines if l.startswith('hip_stub:') and 'live allocations' in l]
-    assert report and report[-1].rstrip().endswith('live allocations 0'), report

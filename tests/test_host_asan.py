@@ -11,28 +11,19 @@ Sobol entry points; and every call that builds a handle or grows a workspace onc
 makes, with that allocation failing: the call reports it, frees what it had made and leaves its
 object usable. Clean = no sanitizer report, no address outside an allocation, nothing leaked; and a
 planted fault (a raster one tile short) is reported. Sanitizers run on the CPU build only (the GPU pool refuses them)."""
-import os
-import subprocess
-
-from conftest import ROOT
+from host_asan_harness import launched, run_harness, shape_only
 
 
 def test_host_half_of_the_library_is_clean_under_asan_and_ubsan(tmp_path):
-    script = os.path.join(ROOT, 'tests', 'host_asan', 'build_and_run.sh')
-    proc = subprocess.run(['bash', script, str(tmp_path)], capture_output=True, text=True, timeout=900)
-    out = proc.stdout + proc.stderr
-    assert proc.returncode == 0, out[-4000:]
-    assert 'host_asan: ok' in out, out[-2000:]
-    assert 'ERROR: AddressSanitizer' not in out and 'runtime error:' not in out and 'LeakSanitizer' not in out, out[-4000:]
+    out, lines = run_harness('driver', tmp_path)
     assert 'planted fault detected' in out, out[-2000:]
     # the shadows that carry the launch geometry ran, on both data types and on the big rasters
     assert 'et_stream_kernel' in out and 'et_stream_redo_kernel' in out and 'et_kernel' in out
     assert 'graph lifetime: done' in out
     # the kernels of the other HOST-mode families ran under their shadows, not on launch shapes alone
-    lines = out.splitlines()
     for kernel in ('13method_kernel', '13et_raw_kernel', '18static_flag_kernel', '13static_kernel'):
-        assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
-        assert not any(kernel in l for l in lines if 'launch shape only' in l), kernel
+        assert launched(lines, kernel), kernel
+        assert not shape_only(lines, kernel), kernel
     # the calibration family: every array of the objective's, the rows' and the sampler's launches is
     # checked with the extent its kernel indexes
     for kernel in ('24static_obj_params_kernel', '17static_obj_kernel', '22static_obj_redo_kernel',
@@ -41,18 +32,15 @@ def test_host_half_of_the_library_is_clean_under_asan_and_ubsan(tmp_path):
                    '24static_batch_fast_kernel', '32static_batch_flag_skipped_kernel',
                    '29static_batch_redo_rows_kernel', '23static_batch_sse_kernel', '15zero_u32_kernel',
                    '16mcmc_init_kernel', '19mcmc_propose_kernel', '18mcmc_accept_kernel', '23mcmc_init_accept_kernel'):
-        assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
-        assert not any(kernel in l for l in lines if 'launch shape only' in l), kernel
+        assert launched(lines, kernel), kernel
+        assert not shape_only(lines, kernel), kernel
     assert 'calibration family: done' in out and 'Sobol entry points: done' in out
     # the constraint's kernels, the gather of its rows and the ensemble's kernels likewise
     for kernel in ('25static_annual_redo_kernel', '26static_annual_final_kernel', '25static_rows_gather_kernel',
                    '10ens_kernel', '15ens_redo_kernel'):
-        assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
-        assert not any(kernel in l for l in lines if 'launch shape only' in l), kernel
+        assert launched(lines, kernel), kernel
+        assert not shape_only(lines, kernel), kernel
     assert 'annual: done' in out and 'ensemble: done' in out and 'allocation failures: done' in out
-    # nothing the library allocated outlives its handles
-    report = [l for l in lines if l.startswith('hip_stub:') and 'live allocations' in l]
-    assert report and report[-1].rstrip().endswith('live allocations 0'), report
     for what in ('tiled rasters, float64', 'tiled rasters, float32', 'plain device arrays, float64',
                  'HOST mode, float64', 'HOST mode, float32'):
         assert what in out, what

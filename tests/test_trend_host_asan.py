@@ -1,7 +1,7 @@
 """The HOST mode of mod16_trend_f32 / _f64 under AddressSanitizer + UndefinedBehaviorSanitizer: the
 library's host half (`hipcc --cuda-host-only -fsanitize=address,undefined`, its own source) linked,
 unchanged, against the HIP stand-in of tests/host_asan, and driven by a stand-alone program
-(tests/host_asan_trend/driver.cpp) that calls the HOST-mode trend with guard bytes around every host
+(tests/host_asan/trend.cpp) that calls the HOST-mode trend with guard bytes around every host
 array: n = 37 and 300 pixels, Y = 5 and 33 steps, three stage_bytes (the smallest range of pixels -- 256
 and 44 of 300 --, a slab cut from the bytes of a range's rows, one chunk), a dense stack and one with
 time_stride > n, every output and a subset, both input types. Clean = no sanitizer report, every
@@ -15,23 +15,12 @@ pixels, the outputs of three element sizes), the range cut from stage_bytes, the
 and the entry point's checks -- not the kernel's own address arithmetic, which tests/test_gpu_trend.py
 covers on the device with strided stacks at odd offsets. Sanitizers run on the CPU build only;
 nothing here is loaded into Python."""
-import os
-import subprocess
-
-from conftest import ROOT
+from host_asan_harness import launched, run_harness
 
 
 def test_host_mode_trend_is_clean_under_asan_and_ubsan(tmp_path):
-    script = os.path.join(ROOT, 'tests', 'host_asan_trend', 'build_and_run.sh')
-    proc = subprocess.run(['bash', script, str(tmp_path)], capture_output=True, text=True, timeout=900)
-    out = proc.stdout + proc.stderr
-    assert proc.returncode == 0, out[-4000:]
-    assert 'host_asan_trend: ok' in out, out[-2000:]
-    assert 'ERROR: AddressSanitizer' not in out and 'runtime error:' not in out and 'LeakSanitizer' not in out, out[-4000:]
+    out, lines = run_harness('trend', tmp_path)
     for name in ('float32', 'float64'):
         assert 'host_asan_trend: %s done' % name in out
     assert 'host_asan_trend: refusals done' in out
-    lines = out.splitlines()
-    assert any('12trend_kernel' in l for l in lines if l.strip().startswith('launches'))
-    report = [l for l in lines if l.startswith('hip_stub:') and 'live allocations' in l]
-    assert report and report[-1].rstrip().endswith('live allocations 0'), report
+    assert launched(lines, '12trend_kernel')

@@ -1,7 +1,7 @@
 """mod16_upscale_create and the HOST mode of mod16_upscale_f32 / _f64 / _classes under AddressSanitizer +
 UndefinedBehaviorSanitizer: the library's host half (`hipcc --cuda-host-only -fsanitize=address,undefined`,
 its own source) linked, unchanged, against the HIP stand-in of tests/host_asan, and driven by a
-stand-alone program (tests/host_asan_upscale/driver.cpp) that calls the family with guard bytes around
+stand-alone program (tests/host_asan/upscale.cpp) that calls the family with guard bytes around
 every host array: 37 fine rows over 5 coarse rows (runs of 7, 8, 7, 8, 7) increasing and decreasing, with a
 margin of rows outside the grid and an empty coarse row, 70 columns over 9 cells with the cell that
 straddles the end of the axis, 1 and 3 layers, three stage_bytes (one coarse row of one layer per pass,
@@ -18,24 +18,13 @@ the input and up to three outputs, row-by-row copies of strided arrays) and the 
 not the kernels' own address arithmetic, which tests/test_gpu_upscale.py covers on the device with
 strided arrays at odd offsets and guard elements. Sanitizers run on the CPU build only; nothing here is
 loaded into Python."""
-import os
-import subprocess
-
-from conftest import ROOT
+from host_asan_harness import launched, run_harness
 
 
 def test_host_mode_upscale_is_clean_under_asan_and_ubsan(tmp_path):
-    script = os.path.join(ROOT, 'tests', 'host_asan_upscale', 'build_and_run.sh')
-    proc = subprocess.run(['bash', script, str(tmp_path)], capture_output=True, text=True, timeout=900)
-    out = proc.stdout + proc.stderr
-    assert proc.returncode == 0, out[-4000:]
-    assert 'host_asan_upscale: ok' in out, out[-2000:]
-    assert 'ERROR: AddressSanitizer' not in out and 'runtime error:' not in out and 'LeakSanitizer' not in out, out[-4000:]
+    out, lines = run_harness('upscale', tmp_path)
     for name in ('float32', 'float64'):
         assert 'host_asan_upscale: %s done' % name in out
     assert 'host_asan_upscale: refusals done' in out
-    lines = out.splitlines()
     for kernel in ('14upscale_kernel', '22upscale_classes_kernel'):
-        assert any(kernel in l for l in lines if l.strip().startswith('launches')), kernel
-    report = [l for l in lines if l.startswith('hip_stub:') and 'live allocations' in l]
-    assert report and report[-1].rstrip().endswith('live allocations 0'), report
+        assert launched(lines, kernel), kernel

@@ -1397,6 +1397,59 @@ MOD16_API int mod16_upscale_classes(mod16_ctx* ctx, const mod16_upscale* grid, c
                                     int64_t share_row_stride, int where, void* stream, size_t stage_bytes);
 
 /*
+ * Upscaling from rasters with row-affine columns -- MODIS sinusoidal tiles -- and mergeable cell sums
+ * (added under ABI 16, new symbols only; RasterEngine.upscale_grid(col_affine=...), UpscaleGrid.sums,
+ * mod16_amd.upscale_sums, mod16_amd.upscale.merge). The definition is mod16_amd/upscale.py
+ * (cell_table_rows, aggregate_rows, sums_rows, majority_rows), which the outputs equal bit for bit.
+ *
+ *   geometry    the rows as above (row_first, row_count). The column position of pixel (r, c) is
+ *               col_origin[r] + col_scale[r] * c in units of coarse cells (one multiplication, one
+ *               addition, each rounded; mod16_amd.downscale.sinusoidal_positions), and the pixel belongs
+ *               to the cell mod16_amd.upscale.cell_table gives that position: without wrap_cols i0 =
+ *               floor(pos), f = pos - i0, cell = i0 + (f >= 0.5), none outside [0, coarse_cols); with
+ *               wrap_cols p = pos - floor(pos / W) W (0 where that is not in [0, W)), cell = (floor(p) +
+ *               (f >= 0.5)) mod W. col_first[rows], col_count[rows] (both NULL: every column): only the
+ *               columns col_first[r] ... col_first[r] + col_count[r] - 1 of fine row r can belong to a
+ *               cell, the others are not read (the on-globe pixels of an edge tile:
+ *               mod16_amd.downscale.sinusoidal_columns). The column run of a cell in a fine row is found
+ *               on the device from the row's two float64; the cell's pixels in that row are col_count[j]
+ *               of the statement above, and out_share divides by their sum over the cell's rows.
+ *               The handle is a mod16_upscale like any other: mod16_upscale_f32 / _f64 / _classes and
+ *               the sums take it, mod16_upscale_destroy frees it.
+ *   refused by mod16_upscale_create_rows (MOD16_ERR_ARG, "mod16_upscale_create_rows: ...")
+ *               NULL spec, row tables, col_origin, col_scale or handle pointer; one of col_first and
+ *               col_count NULL alone; an extent outside 1 ... 2^30; wrap_cols not 0 or 1; bad row runs
+ *               (as mod16_upscale_create); col_origin, col_scale or col_origin + col_scale (cols - 1) not
+ *               finite; a column range outside [0, cols); with wrap_cols a row of n = col_count > 1
+ *               columns with abs(col_scale) * (n - 1) > coarse_cols - 2 (it may lap the periodic axis:
+ *               narrow the range or cut the raster; sufficient for one run of columns per cell and
+ *               row); the largest row_count times the largest col_count at or above 2^31; a bad area.
+ *   sums        mod16_upscale_sums_f32 / _f64, for handles of both kinds: num, den, tot (float64 whatever
+ *               the input type) and count (int32) of the statement above, before the divisions --
+ *               what a tile contributes to cells it covers in part; add the sums of several tiles in
+ *               a fixed order and divide once (mod16_amd.upscale.merge). Each output
+ *               [layers][coarse_rows][coarse_cols] with its own layer and row stride; a NULL output is
+ *               skipped, at least one is required. where, stage_bytes and the refusals
+ *               ("mod16_upscale_sums: ...") are those of mod16_upscale_f32.
+ */
+MOD16_API int mod16_upscale_create_rows(mod16_ctx* ctx, const mod16_upscale_spec* spec, const int32_t* row_first,
+                                        const int32_t* row_count, const double* col_origin, const double* col_scale,
+                                        const int32_t* col_first, const int32_t* col_count, const double* area,
+                                        mod16_upscale** out);
+MOD16_API int mod16_upscale_sums_f32(mod16_ctx* ctx, const mod16_upscale* grid, const float* values, int32_t layers,
+                                     int64_t layer_stride, int64_t row_stride, double* num, int64_t num_layer_stride,
+                                     int64_t num_row_stride, double* den, int64_t den_layer_stride, int64_t den_row_stride,
+                                     double* tot, int64_t tot_layer_stride, int64_t tot_row_stride, int32_t* count,
+                                     int64_t count_layer_stride, int64_t count_row_stride, int where, void* stream,
+                                     size_t stage_bytes);
+MOD16_API int mod16_upscale_sums_f64(mod16_ctx* ctx, const mod16_upscale* grid, const double* values, int32_t layers,
+                                     int64_t layer_stride, int64_t row_stride, double* num, int64_t num_layer_stride,
+                                     int64_t num_row_stride, double* den, int64_t den_layer_stride, int64_t den_row_stride,
+                                     double* tot, int64_t tot_layer_stride, int64_t tot_row_stride, int32_t* count,
+                                     int64_t count_layer_stride, int64_t count_row_stride, int where, void* stream,
+                                     size_t stage_bytes);
+
+/*
  * Downscaled forward run (ABI 14; mod16_amd.evapotranspiration_downscaled,
  * RasterEngine.downscale_grid): ET day and night for a contiguous range of pixels of a rows x cols
  * fine raster, each of the 14 drivers a scalar, a fine array or a COARSE coarse_rows x coarse_cols

@@ -161,6 +161,8 @@ class UpscaleSpec(C.Structure):
 
 _UPSCALE_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_double] + \
     [C.c_void_p, C.c_int64, C.c_int64] * 3 + [C.c_int, C.c_void_p, C.c_size_t]
+_UPSCALE_SUMS_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64] + \
+    [C.c_void_p, C.c_int64, C.c_int64] * 4 + [C.c_int, C.c_void_p, C.c_size_t]
 
 
 class DownscaleSpec(C.Structure):
@@ -426,6 +428,9 @@ PROTOTYPES = {
     'mod16_upscale_f32': (C.c_int, _UPSCALE_ARGS),
     'mod16_upscale_classes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t]),
+    'mod16_upscale_create_rows': (C.c_int, [C.c_void_p, C.POINTER(UpscaleSpec)] + [C.c_void_p] * 7 + [C.POINTER(C.c_void_p)]),
+    'mod16_upscale_sums_f64': (C.c_int, _UPSCALE_SUMS_ARGS),
+    'mod16_upscale_sums_f32': (C.c_int, _UPSCALE_SUMS_ARGS),
 }
 
 _lib = None
@@ -922,13 +927,30 @@ class Downscale:
 class Upscale:
     '''The runs of a coarse grid's cells in a fine raster on a context's device (``mod16_upscale``): the
     four tables of ``mod16_amd.upscale.cell_runs`` for both axes, computed here in numpy from the
-    positions (or given as ``runs = (row_runs, col_runs)``), and the area weights of the fine rows.'''
+    positions (or given as ``runs = (row_runs, col_runs)``), and the area weights of the fine rows. With
+    ``col_affine = (col_origin, col_scale)`` and ``col_pos=None`` (row-affine columns, a sinusoidal tile:
+    ``mod16_upscale_create_rows``) the rows keep their runs, ``col_runs`` is None and the device finds the
+    column runs per fine row; ``col_range = (col_first, col_count)`` names the columns that can belong to a
+    cell (``runs`` is then the row runs alone).'''
 
     def __init__(self, ctx, shape, coarse_shape, row_pos=None, col_pos=None, wrap=False, area=None, runs=None,
-                 col_affine=None):
+                 col_affine=None, col_range=None):
         from . import upscale as _u
         self.wrap = bool(wrap)
-        if runs is None:
+        self.col_affine = self.col_range = None
+        if col_affine is not None and col_pos is None:
+            if runs is None:
+                self.shape, self.coarse_shape, self.row_runs, self.col_affine, self.col_range = _u.check_geometry_rows(
+                    shape, coarse_shape, row_pos, col_affine, self.wrap, col_range)
+            else:
+                self.shape, self.coarse_shape = (int(shape[0]), int(shape[1])), (int(coarse_shape[0]), int(coarse_shape[1]))
+                self.row_runs = _u.check_runs(runs, self.shape[0], self.coarse_shape[0], 'row')
+                self.col_affine, self.col_range = _u.check_rows(self.shape, self.coarse_shape[1], col_affine, self.wrap, col_range)
+                _u.check_cell_size(self.row_runs, self.col_range)
+            self.col_runs = None
+        elif col_range is not None:
+            raise ValueError('col_range goes with col_affine (row-affine columns)')
+        elif runs is None:
             self.shape, self.coarse_shape, self.row_runs, self.col_runs = _u.check_geometry(
                 shape, coarse_shape, row_pos, col_pos, self.wrap, col_affine)
         else:
@@ -940,10 +962,18 @@ class Upscale:
         spec = UpscaleSpec(self.shape[0], self.shape[1], self.coarse_shape[0], self.coarse_shape[1], 1 if self.wrap else 0, 0)
         self.ctx = ctx                  # keeps the context alive as long as its grid
         self.handle = C.c_void_p()
-        ctx.check(ctx.lib.mod16_upscale_create(
-            ctx.handle, C.byref(spec), *([t.ctypes.data for t in tuple(self.row_runs) + tuple(self.col_runs)] +
-                                         [None if self.area is None else self.area.ctypes.data]),
-            C.byref(self.handle)))
+        area_ptr = None if self.area is None else self.area.ctypes.data
+        if self.col_affine is not None:
+            whole = col_range is None    # (the library takes NULL for "every column")
+            ctx.check(ctx.lib.mod16_upscale_create_rows(
+                ctx.handle, C.byref(spec), self.row_runs[0].ctypes.data, self.row_runs[1].ctypes.data,
+                self.col_affine[0].ctypes.data, self.col_affine[1].ctypes.data,
+                None if whole else self.col_range[0].ctypes.data, None if whole else self.col_range[1].ctypes.data,
+                area_ptr, C.byref(self.handle)))
+        else:
+            ctx.check(ctx.lib.mod16_upscale_create(
+                ctx.handle, C.byref(spec), *([t.ctypes.data for t in tuple(self.row_runs) + tuple(self.col_runs)] + [area_ptr]),
+                C.byref(self.handle)))
 
     def _open(self):
         if not self.handle.value:
@@ -960,6 +990,17 @@ class Upscale:
             flat += [None, 0, 0] if o is None else [o[0], int(o[1]), int(o[2])]
         self.ctx.check(fn(self.ctx.handle, self.handle, values, int(layers), int(layer_stride), int(row_stride),
                           float(min_fraction), *(flat + [int(where), stream, 0 if stage_bytes is None else int(stage_bytes)])))
+
+    def sums(self, dtype, values, layers, layer_stride, row_stride, outs, where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_upscale_sums_f64 / _f32. ``values`` is a raw address, ``outs`` four entries
+        (num, den, tot, count), each None or ``(address, layer stride, row stride)`` in elements.'''
+        self._open()
+        fn = typed(self.ctx.lib, 'mod16_upscale_sums', dtype)
+        flat = []
+        for o in outs:
+            flat += [None, 0, 0] if o is None else [o[0], int(o[1]), int(o[2])]
+        self.ctx.check(fn(self.ctx.handle, self.handle, values, int(layers), int(layer_stride), int(row_stride),
+                          *(flat + [int(where), stream, 0 if stage_bytes is None else int(stage_bytes)])))
 
     def classes(self, cls, row_stride, valid, out_cls, out_share, where=HOST, stream=None, stage_bytes=None):
         '''Thin wrapper of mod16_upscale_classes: ``cls`` a raw address, ``valid`` the 32-bit mask, the

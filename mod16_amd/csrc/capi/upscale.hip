@@ -1,4 +1,4 @@
-// libmod16hip.so -- upscaling: mod16_upscale_create / _destroy (the runs of a coarse grid's cells in a fine raster), mod16_upscale_f32 / _f64 (per layer and cell the area-weighted mean of the valid fine pixels, the valid fraction and the count), mod16_upscale_classes (the dominant class per cell)
+// libmod16hip.so -- upscaling: mod16_upscale_create / _create_rows / _destroy (the runs of a coarse grid's cells in a fine raster; row-affine columns: the rows' runs and two float64 per fine row), mod16_upscale_sums_f32 / _f64 (the sums before the divisions), mod16_upscale_f32 / _f64 (per layer and cell the area-weighted mean of the valid fine pixels, the valid fraction and the count), mod16_upscale_classes (the dominant class per cell)
 #include "host.hpp"
 #include "../mod16_upscale.hpp"
 
@@ -13,8 +13,11 @@ constexpr int64_t kUpMaxBlocks = (int64_t(1) << 31) - 1;
 struct mod16_upscale {
     int device = 0;
     mod16_upscale_spec spec = {};
-    DevMem tables;               // row_first, row_count (int32 [H]), col_first, col_count (int32 [W]), area (double [R]) or nothing
+    DevMem tables;               // row_first, row_count (int32 [H]), col_first, col_count (int32 [W]), area (double [R]) or nothing;
+                                 // by_rows: row_first, row_count, origin, scale (double [R]), col_first, col_count (int32 [R]) or nothing, area
     UpGeom g = {};               // views into `tables`; the launch fills in what depends on it
+    bool by_rows = false;        // row-affine columns (mod16_upscale_create_rows): g.col_first / g.col_count are NULL, rg holds the rows'
+    UpRowsGeom rg = {};
     std::vector<int32_t> row_first, row_count;
 };
 
@@ -105,6 +108,85 @@ extern "C" int mod16_upscale_create(mod16_ctx* ctx, const mod16_upscale_spec* s,
     return MOD16_OK;
 }
 
+extern "C" int mod16_upscale_create_rows(mod16_ctx* ctx, const mod16_upscale_spec* s, const int32_t* row_first,
+                                         const int32_t* row_count, const double* col_origin, const double* col_scale,
+                                         const int32_t* col_first, const int32_t* col_count, const double* area,
+                                         mod16_upscale** out) {
+    MOD16_LOCK(ctx);
+    if (!ctx) return MOD16_ERR_ARG;
+    auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, "mod16_upscale_create_rows: ", what); };
+    if (out) *out = nullptr;
+    if (!s || !row_first || !row_count || !col_origin || !col_scale || !out) return bad("NULL argument");
+    if ((col_first == nullptr) != (col_count == nullptr)) return bad("col_first and col_count must both be given or both be NULL");
+    if (s->rows < 1 || s->rows > kUpMaxExtent || s->cols < 1 || s->cols > kUpMaxExtent)
+        return bad("rows and cols must be between 1 and 2^30");
+    if (s->coarse_rows < 1 || s->coarse_rows > kUpMaxExtent || s->coarse_cols < 1 || s->coarse_cols > kUpMaxExtent)
+        return bad("coarse_rows and coarse_cols must be between 1 and 2^30");
+    if (s->wrap_cols != 0 && s->wrap_cols != 1) return bad("wrap_cols must be 0 or 1");
+    const int64_t R = s->rows, C = s->cols, H = s->coarse_rows, W = s->coarse_cols;
+    int64_t tallest = 0, widest = 0;
+    if (const char* what = up_check_runs(row_first, row_count, H, R, false, &tallest)) return bad(what);
+    for (int64_t r = 0; r < R; ++r) {
+        const double far = col_origin[r] + col_scale[r] * (double)(C - 1);
+        if (!(std::isfinite(col_origin[r]) && std::isfinite(col_scale[r]) && std::isfinite(far)))
+            return bad("col_origin, col_scale and col_origin + col_scale * (cols - 1) must be finite in every row");
+        const int64_t f = col_first ? col_first[r] : 0, n = col_first ? col_count[r] : C;
+        if (f < 0 || n < 0 || f + n > C) return bad("a column range leaves its row (0 <= first, 0 <= count, first + count <= cols)");
+        // sufficient for one run of consecutive columns per cell and fine row (upscale.check_rows)
+        if (s->wrap_cols && n > 1 && !(std::fabs(col_scale[r]) * (double)(n - 1) <= (double)(W - 2)))
+            return bad("a fine row may lap the periodic axis (abs(col_scale) * (columns - 1) > coarse_cols - 2): give a narrower column range or cut the raster");
+        widest = std::max(widest, n);
+    }
+    if (tallest * widest >= (int64_t(1) << 31)) return bad("a cell must hold fewer than 2^31 pixels (row_count * col_count)");
+    if (area)
+        for (int64_t r = 0; r < R; ++r)
+            if (!(std::isfinite(area[r]) && area[r] > 0.0)) return bad("area must be positive and finite");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    mod16_upscale* g = new (std::nothrow) mod16_upscale;
+    if (!g) return MOD16_ERR_NOMEM;
+    g->device = ctx->device;
+    g->spec = *s;
+    g->by_rows = true;
+    g->row_first.assign(row_first, row_first + H);
+    g->row_count.assign(row_count, row_count + H);
+    struct Piece { const void* src; size_t bytes; };
+    const Piece pieces[7] = {{col_origin, (size_t)R * 8}, {col_scale, (size_t)R * 8}, {area, area ? (size_t)R * 8 : 0},
+                             {row_first, (size_t)H * 4}, {row_count, (size_t)H * 4},
+                             {col_first, col_first ? (size_t)R * 4 : 0}, {col_count, col_first ? (size_t)R * 4 : 0}};
+    Carver size;
+    for (const Piece& p : pieces) size.take<char>(p.bytes);
+    int rc = g->tables.alloc(ctx, size.used + 256, "mod16_upscale_create_rows: device memory for the tables");
+    if (rc == MOD16_OK) {
+        Carver block(g->tables.get());
+        const char* at[7];
+        for (int k = 0; k < 7; ++k) {
+            at[k] = block.take<char>(pieces[k].bytes);
+            if (rc == MOD16_OK && pieces[k].bytes &&
+                hipMemcpy(const_cast<char*>(at[k]), pieces[k].src, pieces[k].bytes, hipMemcpyHostToDevice) != hipSuccess)
+                rc = fail(ctx, MOD16_ERR_HIP, "mod16_upscale_create_rows: upload of the tables failed");
+        }
+        auto i32 = [&](int k) { return reinterpret_cast<const int32_t*>(at[k]); };
+        auto f64 = [&](int k) { return reinterpret_cast<const double*>(at[k]); };
+        g->rg.origin = f64(0);
+        g->rg.scale = f64(1);
+        g->g.area = area ? f64(2) : nullptr;
+        g->g.row_first = i32(3);
+        g->g.row_count = i32(4);
+        g->rg.col_first = col_first ? i32(5) : nullptr;
+        g->rg.col_count = col_first ? i32(6) : nullptr;
+        g->rg.wrap = s->wrap_cols;
+        g->g.col_first = g->g.col_count = nullptr;
+        g->g.cols = C;
+        g->g.coarse_cols = (int32_t)W;
+    }
+    if (rc != MOD16_OK) {
+        mod16_upscale_destroy(g);
+        return rc;
+    }
+    *out = g;
+    return MOD16_OK;
+}
+
 // The lanes of a block = the cells of its span: 256, halved down to a wave while the launch would leave
 // the device short of blocks (8 per CU); -> the geometry of a launch over `cell_rows` coarse rows from
 // `cell_row_first`, whose input starts at fine row `row_base`
@@ -124,18 +206,43 @@ static UpGeom up_launch_geom(const mod16_ctx* ctx, const mod16_upscale* grid, in
     return g;
 }
 
-// All pointers are device pointers here; a.g holds the launch's rows (up_launch_geom).
+template <typename T, bool ROWS, bool SUMS>
+static void launch_upscale_ext(const UpArgs<T>& a, const UpRowsGeom& rg, const UpSumArgs& sm, int lanes, int64_t blocks, hipStream_t st) {
+    if (lanes == 64) hipLaunchKernelGGL((upscale_ext_kernel<T, 64, ROWS, SUMS>), dim3((unsigned)blocks), dim3(64), 0, st, a, rg, sm);
+    else if (lanes == 128) hipLaunchKernelGGL((upscale_ext_kernel<T, 128, ROWS, SUMS>), dim3((unsigned)blocks), dim3(128), 0, st, a, rg, sm);
+    else hipLaunchKernelGGL((upscale_ext_kernel<T, 256, ROWS, SUMS>), dim3((unsigned)blocks), dim3(256), 0, st, a, rg, sm);
+}
+
+// All pointers are device pointers here; a.g holds the launch's rows (up_launch_geom). sm: the outputs of
+// a sums call, or NULL (mean, fraction and count); the grid's geometry picks the walk.
 template <typename T>
-static int launch_upscale(mod16_ctx* ctx, const UpArgs<T>& a, int lanes, int64_t blocks, hipStream_t st) {
+static int launch_upscale(mod16_ctx* ctx, const mod16_upscale* grid, const UpArgs<T>& a, const UpSumArgs* sm, int lanes,
+                          int64_t blocks, hipStream_t st) {
     if (blocks <= 0) return MOD16_OK;
+    if (grid->by_rows || sm) {
+        const UpSumArgs none = {};
+        if (grid->by_rows && sm) launch_upscale_ext<T, true, true>(a, grid->rg, *sm, lanes, blocks, st);
+        else if (grid->by_rows) launch_upscale_ext<T, true, false>(a, grid->rg, none, lanes, blocks, st);
+        else launch_upscale_ext<T, false, true>(a, grid->rg, *sm, lanes, blocks, st);
+        HIPCHK(ctx, hipGetLastError());
+        return MOD16_OK;
+    }
     if (lanes == 64) hipLaunchKernelGGL((upscale_kernel<T, 64>), dim3((unsigned)blocks), dim3(64), 0, st, a);
     else if (lanes == 128) hipLaunchKernelGGL((upscale_kernel<T, 128>), dim3((unsigned)blocks), dim3(128), 0, st, a);
     else hipLaunchKernelGGL((upscale_kernel<T, 256>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     HIPCHK(ctx, hipGetLastError());
     return MOD16_OK;
 }
-static int launch_upscale_classes(mod16_ctx* ctx, const UpClassArgs& a, int lanes, int64_t blocks, hipStream_t st) {
+static int launch_upscale_classes(mod16_ctx* ctx, const mod16_upscale* grid, const UpClassArgs& a, int lanes, int64_t blocks,
+                                  hipStream_t st) {
     if (blocks <= 0) return MOD16_OK;
+    if (grid->by_rows) {
+        if (lanes == 64) hipLaunchKernelGGL(upscale_classes_rows_kernel<64>, dim3((unsigned)blocks), dim3(64), 0, st, a, grid->rg);
+        else if (lanes == 128) hipLaunchKernelGGL(upscale_classes_rows_kernel<128>, dim3((unsigned)blocks), dim3(128), 0, st, a, grid->rg);
+        else hipLaunchKernelGGL(upscale_classes_rows_kernel<256>, dim3((unsigned)blocks), dim3(256), 0, st, a, grid->rg);
+        HIPCHK(ctx, hipGetLastError());
+        return MOD16_OK;
+    }
     if (lanes == 64) hipLaunchKernelGGL(upscale_classes_kernel<64>, dim3((unsigned)blocks), dim3(64), 0, st, a);
     else if (lanes == 128) hipLaunchKernelGGL(upscale_classes_kernel<128>, dim3((unsigned)blocks), dim3(128), 0, st, a);
     else hipLaunchKernelGGL(upscale_classes_kernel<256>, dim3((unsigned)blocks), dim3(256), 0, st, a);
@@ -153,7 +260,7 @@ struct UpBand {
     int64_t r0, fine_rows;       // its fine rows
     int32_t k0, layers;          // its layers
     char* in;                    // device: [layers][fine_rows][cols]
-    char* out[3];                // device: [layers][rows][coarse_cols] each, NULL for an absent output
+    char* out[4];                // device: [layers][rows][coarse_cols] each, NULL for an absent output
     hipStream_t st;
 };
 
@@ -214,7 +321,7 @@ static int up_host_bands(mod16_ctx* ctx, const mod16_upscale* grid, int K, const
             b.k0 = (int32_t)k0; b.layers = (int32_t)kl;
             b.st = ctx->streams[0];
             b.in = slab.take<char>((size_t)(kl * b.fine_rows * C) * in.elem);
-            for (int o = 0; o < 3; ++o)
+            for (int o = 0; o < 4; ++o)
                 b.out[o] = o < nout && outs[o].host ? slab.take<char>((size_t)(kl * b.rows * W) * outs[o].elem) : nullptr;
             for (int64_t k = 0; k < kl; ++k) {
                 rc = up_copy_rows(ctx, b.in + (size_t)(k * b.fine_rows * C) * in.elem, C,
@@ -248,66 +355,84 @@ static const char* up_check_strides(int64_t layers, int64_t rows, int64_t n, int
     return nullptr;
 }
 
+// one output of a call: [layers][coarse_rows][coarse_cols] with its strides in elements
+struct UpOut { void* p; int64_t ls, rs; size_t elem; };
+
+// mod16_upscale_f32 / _f64 (outs: mean, fraction, count) and mod16_upscale_sums_f32 / _f64 (sums: outs are
+// num, den, tot, count)
 template <typename T>
-static int upscale_entry(mod16_ctx* ctx, const mod16_upscale* grid, const T* values, int32_t layers, int64_t layer_stride,
-                         int64_t row_stride, double min_fraction, T* mean, int64_t mean_ls, int64_t mean_rs, T* fraction,
-                         int64_t frac_ls, int64_t frac_rs, int32_t* count, int64_t count_ls, int64_t count_rs, int where,
+static int upscale_entry(mod16_ctx* ctx, const char* name, const mod16_upscale* grid, const T* values, int32_t layers,
+                         int64_t layer_stride, int64_t row_stride, double min_fraction, bool sums, const UpOut* o, int where,
                          void* stream, size_t stage_bytes) {
     if (!ctx) return MOD16_ERR_ARG;
-    auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, "mod16_upscale: ", what); };
+    auto bad = [&](const char* what) { return fail(ctx, MOD16_ERR_ARG, name, what); };
+    const int nout = sums ? 4 : 3;
     if (!grid || !values) return bad("NULL grid or values");
     if (grid->device != ctx->device) return bad("the grid was created on another device than this context's");
-    if (!mean && !fraction && !count) return bad("no output is requested");
+    bool any = false;
+    for (int k = 0; k < nout; ++k) any = any || o[k].p;
+    if (!any) return bad("no output is requested");
     if (layers < 1 || layers > kUpMaxLayers) return bad("layers must be between 1 and 65535");
     if (!(min_fraction >= 0.0 && min_fraction <= 1.0)) return bad("min_fraction must lie in [0, 1]");
     const int64_t R = grid->spec.rows, C = grid->spec.cols, H = grid->spec.coarse_rows, W = grid->spec.coarse_cols;
     if (const char* what = up_check_strides(layers, R, C, layer_stride, row_stride)) return bad(what);
-    if (mean) if (const char* what = up_check_strides(layers, H, W, mean_ls, mean_rs)) return bad(what);
-    if (fraction) if (const char* what = up_check_strides(layers, H, W, frac_ls, frac_rs)) return bad(what);
-    if (count) if (const char* what = up_check_strides(layers, H, W, count_ls, count_rs)) return bad(what);
+    for (int k = 0; k < nout; ++k)
+        if (o[k].p) if (const char* what = up_check_strides(layers, H, W, o[k].ls, o[k].rs)) return bad(what);
     if (const char* what = check_where_stage(where, stage_bytes)) return bad(what);
     if ((int64_t)layers * H * ((W + 63) / 64) > kUpMaxBlocks) return bad("layers * coarse_rows * ceil(coarse_cols / 64) must stay below 2^31");
     {
-        Extent ins[1], outs[3];
+        Extent ins[1], outs[4];
         int no = 0;
         ins[0] = extent(values, layers, layer_stride, R, row_stride, C, sizeof(T));
-        if (mean) outs[no++] = extent(mean, layers, mean_ls, H, mean_rs, W, sizeof(T));
-        if (fraction) outs[no++] = extent(fraction, layers, frac_ls, H, frac_rs, W, sizeof(T));
-        if (count) outs[no++] = extent(count, layers, count_ls, H, count_rs, W, sizeof(int32_t));
+        for (int k = 0; k < nout; ++k)
+            if (o[k].p) outs[no++] = extent(o[k].p, layers, o[k].ls, H, o[k].rs, W, o[k].elem);
         if (overlaps(outs, no, ins, 1)) return bad("an output overlaps an input or another output");
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     UpArgs<T> a;
     memset(&a, 0, sizeof a);
     a.min_fraction = min_fraction;
+    UpSumArgs sm = {};
+    // the outputs into the kernels' arguments: p[k] with layer stride ls[k] and row stride rs[k]
+    auto place = [&](UpArgs<T>& d, UpSumArgs& m, void* const* p, const int64_t* ls, const int64_t* rs) {
+        if (sums) {
+            m.num = static_cast<double*>(p[0]); m.num_layer = ls[0]; m.num_row = rs[0];
+            m.den = static_cast<double*>(p[1]); m.den_layer = ls[1]; m.den_row = rs[1];
+            m.tot = static_cast<double*>(p[2]); m.tot_layer = ls[2]; m.tot_row = rs[2];
+        } else {
+            d.mean = static_cast<T*>(p[0]); d.mean_layer = ls[0]; d.mean_row = rs[0];
+            d.fraction = static_cast<T*>(p[1]); d.fraction_layer = ls[1]; d.fraction_row = rs[1];
+        }
+        d.count = static_cast<int32_t*>(p[nout - 1]); d.count_layer = ls[nout - 1]; d.count_row = rs[nout - 1];
+    };
     int lanes = 0;
     int64_t blocks = 0;
     if (where == MOD16_DEVICE) {
         a.g = up_launch_geom(ctx, grid, layers, 0, (int32_t)H, 0, &lanes, &blocks);
         a.values = values; a.layer_stride = layer_stride; a.row_stride = row_stride;
-        a.mean = mean; a.mean_layer = mean_ls; a.mean_row = mean_rs;
-        a.fraction = fraction; a.fraction_layer = frac_ls; a.fraction_row = frac_rs;
-        a.count = count; a.count_layer = count_ls; a.count_row = count_rs;
-        return launch_upscale<T>(ctx, a, lanes, blocks, static_cast<hipStream_t>(stream));
+        void* p[4];
+        int64_t ls[4], rs[4];
+        for (int k = 0; k < nout; ++k) { p[k] = o[k].p; ls[k] = o[k].ls; rs[k] = o[k].rs; }
+        place(a, sm, p, ls, rs);
+        return launch_upscale<T>(ctx, grid, a, sums ? &sm : nullptr, lanes, blocks, static_cast<hipStream_t>(stream));
     }
     const UpHostArray in = {reinterpret_cast<char*>(const_cast<T*>(values)), layer_stride, row_stride, sizeof(T)};
-    const UpHostArray outs[3] = {{reinterpret_cast<char*>(mean), mean_ls, mean_rs, sizeof(T)},
-                                 {reinterpret_cast<char*>(fraction), frac_ls, frac_rs, sizeof(T)},
-                                 {reinterpret_cast<char*>(count), count_ls, count_rs, sizeof(int32_t)}};
-    return up_host_bands(ctx, grid, layers, in, outs, 3, stage_budget(stage_bytes), [&](const UpBand& b) {
+    UpHostArray outs[4];
+    for (int k = 0; k < nout; ++k) outs[k] = UpHostArray{static_cast<char*>(o[k].p), o[k].ls, o[k].rs, o[k].elem};
+    return up_host_bands(ctx, grid, layers, in, outs, nout, stage_budget(stage_bytes), [&](const UpBand& b) {
         UpArgs<T> d = a;
+        UpSumArgs m = {};
         int l = 0;
         int64_t n = 0;
         d.g = up_launch_geom(ctx, grid, b.layers, b.i0, b.rows, b.r0, &l, &n);
         d.values = reinterpret_cast<const T*>(b.in);
         d.row_stride = C;
         d.layer_stride = b.fine_rows * C;
-        d.mean = reinterpret_cast<T*>(b.out[0]);
-        d.fraction = reinterpret_cast<T*>(b.out[1]);
-        d.count = reinterpret_cast<int32_t*>(b.out[2]);
-        d.mean_row = d.fraction_row = d.count_row = W;
-        d.mean_layer = d.fraction_layer = d.count_layer = (int64_t)b.rows * W;
-        return launch_upscale<T>(ctx, d, l, n, b.st);
+        void* p[4];
+        int64_t ls[4], rs[4];
+        for (int k = 0; k < nout; ++k) { p[k] = b.out[k]; ls[k] = (int64_t)b.rows * W; rs[k] = W; }
+        place(d, m, p, ls, rs);
+        return launch_upscale<T>(ctx, grid, d, sums ? &m : nullptr, l, n, b.st);
     });
 }
 
@@ -318,9 +443,11 @@ extern "C" int mod16_upscale_f32(mod16_ctx* ctx, const mod16_upscale* grid, cons
                                  int64_t count_layer_stride, int64_t count_row_stride, int where, void* stream,
                                  size_t stage_bytes) {
     MOD16_LOCK(ctx);
-    return upscale_entry<float>(ctx, grid, values, layers, layer_stride, row_stride, min_fraction, mean, mean_layer_stride,
-                                mean_row_stride, fraction, fraction_layer_stride, fraction_row_stride, count,
-                                count_layer_stride, count_row_stride, where, stream, stage_bytes);
+    const UpOut outs[3] = {{mean, mean_layer_stride, mean_row_stride, sizeof(float)},
+                           {fraction, fraction_layer_stride, fraction_row_stride, sizeof(float)},
+                           {count, count_layer_stride, count_row_stride, sizeof(int32_t)}};
+    return upscale_entry<float>(ctx, "mod16_upscale: ", grid, values, layers, layer_stride, row_stride, min_fraction, false, outs,
+                             where, stream, stage_bytes);
 }
 extern "C" int mod16_upscale_f64(mod16_ctx* ctx, const mod16_upscale* grid, const double* values, int32_t layers,
                                  int64_t layer_stride, int64_t row_stride, double min_fraction, double* mean,
@@ -329,9 +456,11 @@ extern "C" int mod16_upscale_f64(mod16_ctx* ctx, const mod16_upscale* grid, cons
                                  int64_t count_layer_stride, int64_t count_row_stride, int where, void* stream,
                                  size_t stage_bytes) {
     MOD16_LOCK(ctx);
-    return upscale_entry<double>(ctx, grid, values, layers, layer_stride, row_stride, min_fraction, mean, mean_layer_stride,
-                                 mean_row_stride, fraction, fraction_layer_stride, fraction_row_stride, count,
-                                 count_layer_stride, count_row_stride, where, stream, stage_bytes);
+    const UpOut outs[3] = {{mean, mean_layer_stride, mean_row_stride, sizeof(double)},
+                           {fraction, fraction_layer_stride, fraction_row_stride, sizeof(double)},
+                           {count, count_layer_stride, count_row_stride, sizeof(int32_t)}};
+    return upscale_entry<double>(ctx, "mod16_upscale: ", grid, values, layers, layer_stride, row_stride, min_fraction, false, outs,
+                             where, stream, stage_bytes);
 }
 
 extern "C" int mod16_upscale_classes(mod16_ctx* ctx, const mod16_upscale* grid, const uint8_t* cls, int64_t row_stride,
@@ -368,7 +497,7 @@ extern "C" int mod16_upscale_classes(mod16_ctx* ctx, const mod16_upscale* grid, 
         a.cls = cls; a.row_stride = row_stride;
         a.out_cls = out_cls; a.cls_row = cls_row_stride;
         a.out_share = out_share; a.share_row = share_row_stride;
-        return launch_upscale_classes(ctx, a, lanes, blocks, static_cast<hipStream_t>(stream));
+        return launch_upscale_classes(ctx, grid, a, lanes, blocks, static_cast<hipStream_t>(stream));
     }
     const UpHostArray in = {reinterpret_cast<char*>(const_cast<uint8_t*>(cls)), 0, row_stride, 1};
     const UpHostArray outs[2] = {{reinterpret_cast<char*>(out_cls), 0, cls_row_stride, 1},
@@ -383,6 +512,31 @@ extern "C" int mod16_upscale_classes(mod16_ctx* ctx, const mod16_upscale* grid, 
         d.out_cls = reinterpret_cast<uint8_t*>(b.out[0]);
         d.out_share = reinterpret_cast<float*>(b.out[1]);
         d.cls_row = d.share_row = W;
-        return launch_upscale_classes(ctx, d, l, n, b.st);
+        return launch_upscale_classes(ctx, grid, d, l, n, b.st);
     });
+}
+
+extern "C" int mod16_upscale_sums_f32(mod16_ctx* ctx, const mod16_upscale* grid, const float* values, int32_t layers,
+                                      int64_t layer_stride, int64_t row_stride, double* num, int64_t num_layer_stride,
+                                      int64_t num_row_stride, double* den, int64_t den_layer_stride, int64_t den_row_stride,
+                                      double* tot, int64_t tot_layer_stride, int64_t tot_row_stride, int32_t* count,
+                                      int64_t count_layer_stride, int64_t count_row_stride, int where, void* stream,
+                                      size_t stage_bytes) {
+    MOD16_LOCK(ctx);
+    const UpOut outs[4] = {{num, num_layer_stride, num_row_stride, sizeof(double)}, {den, den_layer_stride, den_row_stride, sizeof(double)},
+                           {tot, tot_layer_stride, tot_row_stride, sizeof(double)}, {count, count_layer_stride, count_row_stride, sizeof(int32_t)}};
+    return upscale_entry<float>(ctx, "mod16_upscale_sums: ", grid, values, layers, layer_stride, row_stride, 0.0, true, outs, where,
+                                stream, stage_bytes);
+}
+extern "C" int mod16_upscale_sums_f64(mod16_ctx* ctx, const mod16_upscale* grid, const double* values, int32_t layers,
+                                      int64_t layer_stride, int64_t row_stride, double* num, int64_t num_layer_stride,
+                                      int64_t num_row_stride, double* den, int64_t den_layer_stride, int64_t den_row_stride,
+                                      double* tot, int64_t tot_layer_stride, int64_t tot_row_stride, int32_t* count,
+                                      int64_t count_layer_stride, int64_t count_row_stride, int where, void* stream,
+                                      size_t stage_bytes) {
+    MOD16_LOCK(ctx);
+    const UpOut outs[4] = {{num, num_layer_stride, num_row_stride, sizeof(double)}, {den, den_layer_stride, den_row_stride, sizeof(double)},
+                           {tot, tot_layer_stride, tot_row_stride, sizeof(double)}, {count, count_layer_stride, count_row_stride, sizeof(int32_t)}};
+    return upscale_entry<double>(ctx, "mod16_upscale_sums: ", grid, values, layers, layer_stride, row_stride, 0.0, true, outs, where,
+                                 stream, stage_bytes);
 }

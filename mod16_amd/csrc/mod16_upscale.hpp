@@ -271,4 +271,261 @@ __global__ __launch_bounds__(LANES) void upscale_classes_kernel(UpClassArgs a) {
     if (a.out_share) a.out_share[(int64_t)blk.il * a.share_row + j] = share;
 }
 
+// ---- Row-affine columns (a sinusoidal tile; mod16_amd/upscale.py: cell_table_rows, aggregate_rows,
+// majority_rows). The rows keep their run tables; the column position of pixel (r, c) is origin[r] +
+// scale[r] * c, so the column run [a, b) of a cell differs from fine row to fine row and every lane finds
+// its own from the two float64 of the row. up_cell alone decides which cell a pixel belongs to; the runs
+// are where it changes value, found by bisection over the row's column range [first, first + n): within
+// a row the host accepted (upscale.check_rows) up_cell is monotone in c -- without wrap in the unclipped
+// index, with wrap as the cyclic offset from the cell of the row's first pixel, which does not lap -- in
+// the direction of the scale's sign. A lane bisects for its `a`; its `b` is the `a` of the lane that owns
+// the next cell in that direction (an LDS exchange), bisected only where that lane is in another block.
+// Every search has at most 31 steps (n <= 2^30) and ends inside [first, first + n], whatever the
+// arithmetic gave: no float result steers an address unclamped. The cost is per (fine row, cell); the walk
+// has no up_cell and no division per pixel.
+struct UpRowsGeom {
+    const double* origin;                // [rows] position of column 0 in units of coarse cells
+    const double* scale;                 // [rows] coarse cells per fine column
+    const int32_t* col_first;            // [rows] the columns of a fine row that can belong to a cell, or NULL: all
+    const int32_t* col_count;
+    int32_t wrap;                        // 1: the coarse column axis is periodic
+};
+
+struct UpSumArgs {                       // the outputs of the sums kernels ([layers][cell_rows][coarse_cols] each, or NULL)
+    double* num;
+    double* den;
+    double* tot;
+    int64_t num_layer, num_row, den_layer, den_row, tot_layer, tot_row;
+};
+
+// upscale.cell_table on origin + scale * c, operation for operation (no contraction). wrap: the cell in
+// [0, W); the quotient of pos / W is the correctly rounded IEEE division, as in ds_corners(DsRowsGrid).
+// No wrap: the UNCLIPPED cell clip(floor(pos), -2, W + 1) + (f >= 0.5) in [-2, W + 2]: a value outside
+// [0, W) is cell_table's -1 (no cell), and no lane looks for one.
+__device__ __forceinline__ int up_cell(double origin, double scale, int c, int W, bool wrap) {
+#pragma clang fp contract(off)
+    const double step = scale * (double)c;
+    const double pos = origin + step;
+    const double size = (double)W;
+    if (wrap) {
+        const double turns = floor(pos / size) * size;
+        double p = pos - turns;
+        p = (p >= 0.0 && p < size) ? p : 0.0;
+        const double fl = floor(p);
+        const double f = p - fl;
+        int cell = (int)fl + (f >= 0.5 ? 1 : 0);
+        cell = cell >= W ? cell - W : cell;
+        return cell < 0 ? 0 : (cell > W - 1 ? W - 1 : cell);         // (never taken: index safety)
+    }
+    const double fl = floor(pos);
+    const double f = pos - fl;
+    return (int)fmin(fmax(fl, -2.0), size + 1.0) + (f >= 0.5 ? 1 : 0);
+}
+
+// the runs of one fine row in a block: this lane's [a, b), the block's [lo, hi) (lo == INT_MAX: no lane
+// has a pixel) and whether the runs lie back to back in it
+struct UpRowRun { int a, b, lo, hi; bool dense; };
+
+template <int LANES>
+__device__ __forceinline__ UpRowRun up_find_runs(const UpGeom& g, const UpRowsGeom& rg, int64_t r, int j, int* bnd, int64_t* red) {
+    const int W = g.coarse_cols, C = (int)g.cols, tid = (int)threadIdx.x;
+    const bool wrap = rg.wrap != 0;
+    const double origin = rg.origin[r], scale = rg.scale[r];
+    int first = rg.col_first ? rg.col_first[r] : 0, n = rg.col_count ? rg.col_count[r] : C;
+    first = first < 0 ? 0 : (first > C ? C : first);                  // (the host has checked the range: index safety)
+    n = n < 0 ? 0 : (n > C - first ? C - first : n);
+    const int end = first + n;
+    UpRowRun run{end, end, INT32_MAX, 0, true};
+    if (n == 0) return run;                                           // (block-uniform)
+    const int sgn = scale < 0.0 ? -1 : 1;
+    const int k0 = wrap ? up_cell(origin, scale, first, W, true) : 0;
+    // the key of a cell: non-decreasing in c along the row
+    auto key = [&](int cell) {
+        int k = sgn * (cell - k0);
+        return wrap && k < 0 ? k + W : k;
+    };
+    // the first column of [first, end) whose key is at least `want`, `end` where there is none
+    auto search = [&](int want) {
+        int lo = first, hi = end;
+        for (int step = 0; step < 31 && lo < hi; ++step) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (key(up_cell(origin, scale, mid, W, wrap)) >= want) hi = mid;
+            else lo = mid + 1;
+        }
+        return lo;
+    };
+    const bool mine = j < W;
+    const int want = key(j);
+    const int a = mine ? search(want) : end;
+    bnd[tid] = a;
+    __syncthreads();
+    const int nb = tid + sgn, jn = j + sgn;
+    int b = end;
+    if (mine && !(wrap && want + 1 >= W)) b = (nb >= 0 && nb < LANES && jn >= 0 && jn < W) ? bnd[nb] : search(want + 1);
+    run.a = a;
+    run.b = b < a ? a : b;
+    const int cnt = run.b - run.a;
+    const int64_t none = INT64_MAX;
+    const int64_t lo = up_block_min(cnt ? (int64_t)run.a : none, red);      // (its barriers also free bnd)
+    if (lo == none) return run;
+    run.lo = (int)lo;
+    run.hi = (int)-up_block_min(cnt ? -(int64_t)run.b : none, red);
+    run.dense = up_block_sum(cnt, red) == (int64_t)run.hi - run.lo;
+    return run;
+}
+
+// upscale_walk with the runs per fine row: for every fine row of coarse row i in run order, acc.value(x)
+// for the pixels of this lane's run in increasing c, then acc.count(pixels of the run) and acc.row(r). The
+// runs of the NEXT row that has a pixel in this span are found while the loads of the current chunk are in
+// flight, so that the first chunk of that row can be issued right after the barrier, like any other next
+// chunk. A fine row without a pixel in the span costs no load (and no acc.row: it would add +0.0 to every
+// sum, which changes none of them). -> the pixels of the lane's cell. Every lane of the block calls this.
+template <typename T, int LANES, typename Acc>
+__device__ __forceinline__ int upscale_walk_rows(const UpGeom& g, const UpRowsGeom& rg, const T* src, int64_t row_stride,
+                                                 int i, int j0, T* tile, int64_t* red, int* bnd, Acc& acc) {
+    constexpr int lanes = LANES, LOADS = kUpSpan / LANES, chunk = kUpSpan;
+    const int tid = (int)threadIdx.x;
+    const int j = j0 + tid;
+    const int nrows = g.row_count[i];
+    const int64_t rf = g.row_first[i], r0 = rf - g.row_base;
+    int pixels = 0;
+    UpRowRun cur{0, 0, INT32_MAX, 0, true}, nxt = cur;
+    // the next fine row from `t` on that has a pixel in the span (nrows: none)
+    auto seek = [&](int t, UpRowRun& run) {
+        for (; t < nrows; ++t) {
+            run = up_find_runs<LANES>(g, rg, rf + t, j, bnd, red);
+            if (run.lo != INT32_MAX) break;
+        }
+        return t;
+    };
+    int t = seek(0, cur);
+    if (t >= nrows) return 0;
+    T v[LOADS];
+    auto load = [&](int row, int u, int len) {
+        const T* p = src + (r0 + row) * row_stride + u;
+#pragma unroll
+        for (int q = 0; q < LOADS; ++q) v[q] = p[min(q * lanes + tid, len - 1)];
+    };
+    const int64_t none = INT64_MAX;
+    auto start = [&](const UpRowRun& run, int from) {
+        return run.dense ? from : (int)up_block_min(run.b > from ? (int64_t)max(run.a, from) : none, red);
+    };
+    int u = start(cur, cur.lo);
+    int len = min(chunk, cur.hi - u);
+    load(t, u, len);
+    int tn = 0;
+    bool sought = false;
+    for (;;) {
+        if (!sought) {                                          // (block-uniform) while the loads are in flight
+            tn = seek(t + 1, nxt);
+            sought = true;
+        }
+#pragma unroll
+        for (int q = 0; q < LOADS; ++q) {
+            const int e = q * lanes + tid;
+            if (e < len) tile[up_pad(e)] = v[q];
+        }
+        __syncthreads();
+        const bool row_ends = u + len >= cur.hi;
+        const bool more = row_ends ? tn < nrows : true;
+        int u2 = 0, len2 = 0;
+        if (more) {                                             // (block-uniform)
+            u2 = row_ends ? start(nxt, nxt.lo) : start(cur, u + len);
+            len2 = min(chunk, (row_ends ? nxt.hi : cur.hi) - u2);
+            load(row_ends ? tn : t, u2, len2);
+        }
+        const int s0 = max(cur.a, u) - u, s1 = min(cur.b, u + len) - u;      // s1 <= s0: nothing of this run
+        for (int e = s0; e < s1; ++e) acc.value(tile[up_pad(e)]);
+        if (row_ends) {
+            acc.count(cur.b - cur.a);
+            acc.row(rf + t);
+            pixels += cur.b - cur.a;
+        }
+        if (!more) break;
+        __syncthreads();                                        // the tile is free again
+        if (row_ends) {
+            cur = nxt;
+            t = tn;
+            sought = false;
+        }
+        u = u2;
+        len = len2;
+    }
+    return pixels;
+}
+
+// UpMeanAcc with the pixel count of the lane's run set per fine row
+struct UpRowsMeanAcc : UpMeanAcc {
+    __device__ __forceinline__ void count(int n) { ccf = (double)n; }
+};
+struct UpRowsClassAcc : UpClassAcc {
+    __device__ __forceinline__ void count(int) {}
+};
+
+// The mean kernel of the row-affine geometry (ROWS) and the sums kernels of both geometries (SUMS: num,
+// den, tot and count instead of mean, fraction and count): upscale_kernel with another walk and / or
+// other stores. (ROWS = false, SUMS = false is upscale_kernel itself and is not instantiated.)
+template <typename T, int LANES, bool ROWS, bool SUMS>
+__global__ __launch_bounds__(LANES) void upscale_ext_kernel(UpArgs<T> a, UpRowsGeom rg, UpSumArgs sm) {
+#pragma clang fp contract(off)
+    __shared__ T tile[kUpTile];
+    __shared__ int64_t red[kUpMaxLanes / 64];
+    __shared__ int bnd[ROWS ? LANES : 1];
+    const UpGeom& g = a.g;
+    const UpBlock blk = up_block(g);
+    const int i = g.cell_row_first + blk.il, j0 = blk.span * LANES, j = j0 + (int)threadIdx.x;
+    UpRowsMeanAcc acc;
+    acc.area = g.area;
+    const T* src = a.values + (int64_t)blk.layer * a.layer_stride;
+    if constexpr (ROWS) {
+        acc.ccf = 0.0;
+        upscale_walk_rows<T, LANES>(g, rg, src, a.row_stride, i, j0, tile, red, bnd, acc);
+    } else {
+        acc.ccf = j < g.coarse_cols ? (double)g.col_count[j] : 0.0;
+        upscale_walk<T, LANES>(g, src, a.row_stride, i, j0, tile, red, acc);
+    }
+    if (j >= g.coarse_cols) return;
+    if constexpr (SUMS) {
+        if (sm.num) sm.num[(int64_t)blk.layer * sm.num_layer + (int64_t)blk.il * sm.num_row + j] = acc.num;
+        if (sm.den) sm.den[(int64_t)blk.layer * sm.den_layer + (int64_t)blk.il * sm.den_row + j] = acc.den;
+        if (sm.tot) sm.tot[(int64_t)blk.layer * sm.tot_layer + (int64_t)blk.il * sm.tot_row + j] = acc.tot;
+    } else {
+        const double fraction = acc.tot > 0.0 ? acc.den / acc.tot : 0.0;
+        const double need = a.min_fraction * acc.tot;
+        const double mean = acc.cnt >= 1 && acc.den >= need ? acc.num / acc.den : __builtin_nan("");
+        if (a.mean) a.mean[(int64_t)blk.layer * a.mean_layer + (int64_t)blk.il * a.mean_row + j] = (T)mean;
+        if (a.fraction) a.fraction[(int64_t)blk.layer * a.fraction_layer + (int64_t)blk.il * a.fraction_row + j] = (T)fraction;
+    }
+    if (a.count) a.count[(int64_t)blk.layer * a.count_layer + (int64_t)blk.il * a.count_row + j] = acc.cnt;
+}
+
+template <int LANES>
+__global__ __launch_bounds__(LANES) void upscale_classes_rows_kernel(UpClassArgs a, UpRowsGeom rg) {
+    __shared__ uint8_t tile[kUpTile];
+    __shared__ unsigned counters[kUpCodes * LANES];
+    __shared__ int64_t red[kUpMaxLanes / 64];
+    __shared__ int bnd[LANES];
+    const UpGeom& g = a.g;
+    const UpBlock blk = up_block(g);
+    constexpr int lanes = LANES;
+    const int i = g.cell_row_first + blk.il, j0 = blk.span * lanes, j = j0 + (int)threadIdx.x;
+    UpRowsClassAcc acc{{counters + threadIdx.x, a.valid, lanes}};
+    for (int c = 0; c < kUpCodes; ++c) acc.col[c * lanes] = 0u;
+    const int cell = upscale_walk_rows<uint8_t, LANES>(g, rg, a.cls, a.row_stride, i, j0, tile, red, bnd, acc);
+    if (j >= g.coarse_cols) return;
+    unsigned best = 0u;
+    int winner = kUpNoClass;
+    for (int c = 0; c < kUpCodes; ++c) {                  // a later code needs MORE pixels: the lowest code wins a tie
+        const unsigned v = acc.col[c * lanes];
+        if (v > best) {
+            best = v;
+            winner = c;
+        }
+    }
+    const double pixels = (double)cell;
+    const float share = best ? (float)((double)best / pixels) : 0.0f;
+    if (a.out_cls) a.out_cls[(int64_t)blk.il * a.cls_row + j] = (uint8_t)winner;
+    if (a.out_share) a.out_share[(int64_t)blk.il * a.share_row + j] = share;
+}
+
 }  // namespace mod16

@@ -322,6 +322,38 @@ def sinusoidal_positions(h, v, size, coarse_lat_first, coarse_lat_step, coarse_l
     return row_pos, col_origin, col_scale
 
 
+def sinusoidal_columns(h, v, size):
+    '''The columns of MODIS sinusoidal tile ``(h, v)`` with ``size`` pixels per side whose centre lies on
+    the globe -> ``(col_first[size], col_count[size])`` int32, per tile row the one range of such
+    columns (a count of 0: the row lies beyond the outline): ``abs(x_c) <= pi * across[r]`` with the
+    centre ``x_c = x0 + c * pixel`` of column ``c`` and ``x0``, ``pixel`` and ``across`` formed as
+    ``sinusoidal_positions`` forms them. What ``col_range`` of the upscaling takes, so that the
+    off-globe pixels of an edge tile do not alias onto cells on the far side of a periodic axis.'''
+    h, v, size = int(h), int(v), int(size)
+    if h < 0 or h >= SINUSOIDAL_TILES[0]:
+        raise ValueError('h must be between 0 and 35, got %d' % h)
+    if v < 0 or v >= SINUSOIDAL_TILES[1]:
+        raise ValueError('v must be between 0 and 17, got %d' % v)
+    if size < 1 or size > MAX_EXTENT:
+        raise ValueError('size must be between 1 and %d, got %d' % (MAX_EXTENT, size))
+    radius, edge = np.float64(SINUSOIDAL_RADIUS), np.float64(SINUSOIDAL_TILE_EDGE)
+    pixel = edge / np.float64(size)
+    k = np.arange(size, dtype=np.float64)
+    y = np.float64(9 - v) * edge - (k + 0.5) * pixel
+    across = radius * np.cos(y / radius)
+    x0 = np.float64(h - 18) * edge + 0.5 * pixel
+    first, count = np.zeros(size, np.int32), np.zeros(size, np.int32)
+    step = max(1, (1 << 22) // size)
+    for r0 in range(0, size, step):                    # (blocks of rows: size x size booleans at 4800 are 23 MB)
+        on = np.abs(x0 + k[None, :] * pixel) <= np.pi * across[r0:r0 + step, None]
+        n = on.sum(axis=1)
+        f = np.where(n > 0, on.argmax(axis=1), 0)
+        last = size - 1 - on[:, ::-1].argmax(axis=1)
+        assert np.all((n == 0) | (last - f + 1 == n)), 'the on-globe columns of a row are one range'
+        first[r0:r0 + step], count[r0:r0 + step] = f, n
+    return first, count
+
+
 def check_coarse(coarse):
     '''``coarse`` of a downscaled call -> the tuple of driver names it holds, in driver order;
     ValueError for a name that is no driver or one named twice.'''

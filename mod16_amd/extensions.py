@@ -683,8 +683,23 @@ def anomaly_series(num, den=None, periods=None, window=1, baseline=None, min_val
     return _an.Anomaly(*[outs.get(k) for k in _an.OUTPUT_NAMES])
 
 
-def upscale_fields(values, coarse_shape, row_pos, col_pos, wrap=False, area=None, min_fraction=0.0, outputs=('mean',),
-                   device=0, stage_bytes=None):
+def _upscale_handle(shape, coarse_shape, row_pos, col_pos, wrap, area, col_affine, col_range, device):
+    '''The checked geometry of a numpy upscaling call -> ``(Upscale handle, (H, W))``.'''
+    from . import upscale as _u
+    if col_affine is None and col_range is None:
+        fine, (H, W), row_runs, col_runs = _u.check_geometry(shape, coarse_shape, row_pos, col_pos, wrap)
+        area = _u.check_area(area, shape[0])
+        return _lib.Upscale(_lib.context(device), fine, (H, W), wrap=wrap, area=area, runs=(row_runs, col_runs)), (H, W)
+    if col_pos is not None or col_affine is None:
+        raise ValueError('exactly one of col_pos and col_affine must be given (col_range goes with col_affine)')
+    fine, (H, W), row_runs, affine, col_range = _u.check_geometry_rows(shape, coarse_shape, row_pos, col_affine, wrap, col_range)
+    area = _u.check_area(area, shape[0])
+    return _lib.Upscale(_lib.context(device), fine, (H, W), wrap=wrap, area=area, runs=row_runs, col_affine=affine,
+                        col_range=col_range), (H, W)
+
+
+def upscale_fields(values, coarse_shape, row_pos, col_pos=None, wrap=False, area=None, min_fraction=0.0, outputs=('mean',),
+                   device=0, stage_bytes=None, col_affine=None, col_range=None):
     r'''
     (Extension.) Upscaling: the area-weighted mean of the valid fine pixels of every cell of a coarse
     grid -- an ET map onto the 0.5-degree grid of the reanalysis that drove it, say -- with the valid
@@ -712,6 +727,13 @@ def upscale_fields(values, coarse_shape, row_pos, col_pos, wrap=False, area=None
         (Optional) any of ``'mean'``, ``'fraction'``, ``'count'`` (Default: ``('mean',)``)
     stage_bytes : int
         (Optional) device memory a staged band may take; the result does not depend on it
+    col_affine : tuple of numpy.ndarray
+        (Optional, instead of ``col_pos``) ``(col_origin, col_scale)``, ``(R,)`` each: row-affine columns,
+        a sinusoidal tile (``mod16_amd.downscale.sinusoidal_positions``); the definition is then
+        ``mod16_amd.upscale.aggregate_rows``
+    col_range : tuple of numpy.ndarray
+        (Optional, with ``col_affine``) ``(col_first, col_count)``, ``(R,)`` int32: the columns of every
+        fine row that can belong to a cell (``mod16_amd.downscale.sinusoidal_columns``)
 
     Returns
     -------
@@ -726,14 +748,12 @@ def upscale_fields(values, coarse_shape, row_pos, col_pos, wrap=False, area=None
         raise ValueError('values must have shape (K, R, C) or (R, C), got %r' % (values.shape,))
     shape = tuple(values.shape[-2:])
     K, squeeze = _u.check_layers(values.shape, shape)
-    fine, (H, W), row_runs, col_runs = _u.check_geometry(shape, coarse_shape, row_pos, col_pos, wrap)
-    area = _u.check_area(area, shape[0])
     min_fraction = _u.check_min_fraction(min_fraction)
     names = _u.check_outputs(outputs)
     _check_stage_bytes(stage_bytes)
+    grid, (H, W) = _upscale_handle(shape, coarse_shape, row_pos, col_pos, wrap, area, col_affine, col_range, device)
     x = np.ascontiguousarray(values).reshape(K, shape[0], shape[1])
     outs = _named_outputs(None, _u.output_table(names, (H, W) if squeeze else (K, H, W), dtype))
-    grid = _lib.Upscale(_lib.context(device), fine, (H, W), wrap=wrap, area=area, runs=(row_runs, col_runs))
     try:
         grid.run(dtype, x.ctypes.data, K, shape[0] * shape[1], shape[1], min_fraction,
                  [(outs[k].ctypes.data, H * W, W) if k in outs else None for k in _u.OUTPUT_NAMES], where=_lib.HOST,
@@ -743,8 +763,50 @@ def upscale_fields(values, coarse_shape, row_pos, col_pos, wrap=False, area=None
     return _u.Upscaled(*[outs.get(k) for k in _u.OUTPUT_NAMES])
 
 
-def upscale_classes(cls, coarse_shape, row_pos, col_pos, wrap=False, valid=None, outputs=('cls',), device=0,
-                    stage_bytes=None):
+def upscale_sums(values, coarse_shape, row_pos, col_pos=None, wrap=False, area=None, outputs=None, device=0,
+                 stage_bytes=None, col_affine=None, col_range=None):
+    r'''
+    (Extension.) ``upscale_fields`` stopped before its divisions (``mod16_upscale_sums_*``; the
+    definition is ``mod16_amd.upscale.sums`` / ``sums_rows``): what one raster -- a tile -- contributes
+    to the cells of a coarse grid it covers only in part. ``mod16_amd.upscale.merge`` adds the sums of
+    several rasters in a fixed order and divides once.
+
+    Parameters
+    ----------
+    values, coarse_shape, row_pos, col_pos, wrap, area, stage_bytes, col_affine, col_range
+        as ``upscale_fields`` takes them
+    outputs : sequence of str
+        (Optional) any of ``'num'``, ``'den'``, ``'tot'``, ``'count'`` (Default: all four)
+
+    Returns
+    -------
+    mod16_amd.upscale.UpscaledSums
+        ``(num, den, tot, count)``, None for what ``outputs`` does not name: ``(K, H, W)`` or ``(H, W)``,
+        float64 whatever the type of ``values``, ``count`` int32
+    '''
+    from . import upscale as _u
+    values = np.asarray(values)
+    dtype = _u.check_dtype(values.dtype)
+    if values.ndim not in (2, 3):
+        raise ValueError('values must have shape (K, R, C) or (R, C), got %r' % (values.shape,))
+    shape = tuple(values.shape[-2:])
+    K, squeeze = _u.check_layers(values.shape, shape)
+    names = _u.check_sum_outputs(_u.SUM_NAMES if outputs is None else outputs)
+    _check_stage_bytes(stage_bytes)
+    grid, (H, W) = _upscale_handle(shape, coarse_shape, row_pos, col_pos, wrap, area, col_affine, col_range, device)
+    x = np.ascontiguousarray(values).reshape(K, shape[0], shape[1])
+    outs = _named_outputs(None, _u.sum_table(names, (H, W) if squeeze else (K, H, W)))
+    try:
+        grid.sums(dtype, x.ctypes.data, K, shape[0] * shape[1], shape[1],
+                  [(outs[k].ctypes.data, H * W, W) if k in outs else None for k in _u.SUM_NAMES], where=_lib.HOST,
+                  stage_bytes=stage_bytes)
+    finally:
+        grid.close()
+    return _u.UpscaledSums(*[outs.get(k) for k in _u.SUM_NAMES])
+
+
+def upscale_classes(cls, coarse_shape, row_pos, col_pos=None, wrap=False, valid=None, outputs=('cls',), device=0,
+                    stage_bytes=None, col_affine=None, col_range=None):
     r'''
     (Extension.) The dominant class of a class raster per cell of a coarse grid
     (``mod16_upscale_classes``; the definition is ``mod16_amd.upscale.majority``): the class map a coarse
@@ -755,8 +817,8 @@ def upscale_classes(cls, coarse_shape, row_pos, col_pos, wrap=False, valid=None,
     ----------
     cls : numpy.ndarray
         ``(R, C)`` class codes (uint8, or integers in [0, 255])
-    coarse_shape, row_pos, col_pos, wrap
-        the geometry, as ``upscale_fields`` takes it
+    coarse_shape, row_pos, col_pos, wrap, col_affine, col_range
+        the geometry, as ``upscale_fields`` takes it (row-affine columns: ``mod16_amd.upscale.majority_rows``)
     valid : iterable of int
         (Optional) the codes that count, each in [0, 32) (Default: 0 ... 12)
     outputs : sequence of str
@@ -771,15 +833,14 @@ def upscale_classes(cls, coarse_shape, row_pos, col_pos, wrap=False, valid=None,
     c = _as_uint8(cls)
     if c.ndim != 2:
         raise ValueError('cls must be a two-dimensional class raster, got shape %r' % (c.shape,))
-    fine, (H, W), row_runs, col_runs = _u.check_geometry(c.shape, coarse_shape, row_pos, col_pos, wrap)
     mask = _u.valid_mask(valid)
     names = _u.check_class_outputs(outputs)
     _check_stage_bytes(stage_bytes)
+    grid, (H, W) = _upscale_handle(c.shape, coarse_shape, row_pos, col_pos, wrap, None, col_affine, col_range, device)
     c = np.ascontiguousarray(c)
     outs = _named_outputs(None, _u.output_table(names, (H, W)))
-    grid = _lib.Upscale(_lib.context(device), fine, (H, W), wrap=wrap, runs=(row_runs, col_runs))
     try:
-        grid.classes(c.ctypes.data, fine[1], mask, *[(outs[k].ctypes.data, W) if k in outs else None for k in _u.CLASS_OUTPUT_NAMES],
+        grid.classes(c.ctypes.data, c.shape[1], mask, *[(outs[k].ctypes.data, W) if k in outs else None for k in _u.CLASS_OUTPUT_NAMES],
                      where=_lib.HOST, stage_bytes=stage_bytes)
     finally:
         grid.close()

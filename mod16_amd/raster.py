@@ -230,14 +230,19 @@ class UpscaleGrid(object):
     '''The cells of an ``H x W`` coarse grid in an ``R x C`` fine raster, resident on an engine's device
     (``RasterEngine.upscale_grid``): the run tables uploaded once, ``run`` (the area-weighted mean of
     the valid fine pixels of every cell, the valid fraction and the count) and ``majority`` (the
-    dominant class per cell) as often as there are rasters. The definition is ``mod16_amd.upscale``.'''
+    dominant class per cell) as often as there are rasters, ``sums`` for what several rasters (tiles) add
+    up before ``mod16_amd.upscale.merge`` divides. The definition is ``mod16_amd.upscale``. With row-affine
+    columns (``col_affine``: a sinusoidal tile) ``col_runs`` is None -- the device finds the column runs per
+    fine row -- and ``col_affine`` and ``col_range`` hold the checked geometry.'''
 
-    def __init__(self, engine, shape, coarse_shape, row_pos, col_pos, wrap=False, area=None, col_affine=None):
+    def __init__(self, engine, shape, coarse_shape, row_pos, col_pos=None, wrap=False, area=None, col_affine=None,
+                 col_range=None):
         self.engine = engine                 # keeps the engine alive as long as its grid
         self._grid = _lib.Upscale(engine.ctx, shape, coarse_shape, row_pos, col_pos, wrap=wrap, area=area,
-                                  col_affine=col_affine)
+                                  col_affine=col_affine, col_range=col_range)
         self.shape, self.coarse_shape = self._grid.shape, self._grid.coarse_shape
         self.row_runs, self.col_runs, self.wrap = self._grid.row_runs, self._grid.col_runs, self._grid.wrap
+        self.col_affine, self.col_range = self._grid.col_affine, self._grid.col_range
 
     def run(self, values, min_fraction=0.0, outputs=('mean',), out=None):
         '''Enqueue the upscaling kernel on the current stream (``mod16_upscale_*``; the definition is
@@ -266,6 +271,27 @@ class UpscaleGrid(object):
         except _lib.Mod16Error as e:
             raise _lib.overlap_as_value_error(e)
         return _u.Upscaled(*[outs.get(k) for k in _u.OUTPUT_NAMES])
+
+    def sums(self, values, outputs=None, out=None):
+        '''Enqueue the sums kernel on the current stream (``mod16_upscale_sums_*``; the definition is
+        ``mod16_amd.upscale.sums`` / ``sums_rows``): ``values`` as ``run`` takes them -> ``UpscaledSums(num,
+        den, tot, count)``, float64 whatever the type of ``values`` and int32, with the fields ``outputs``
+        names (default: all four). What a raster contributes to cells it covers only in part: add the
+        tensors of several tiles in a fixed order, or download them and ``mod16_amd.upscale.merge``.'''
+        from . import upscale as _u
+        eng, torch = self.engine, _torch()
+        _t.check_device(values, 'values', eng.device, torch.float32, torch.float64)
+        K, squeeze = _u.check_layers(tuple(values.shape), self.shape)
+        names = _u.check_sum_outputs(_u.SUM_NAMES if outputs is None else outputs)
+        pitch, plane = _t.plane_layout(values, 'values')
+        outs, lay = _t.named_outputs(out, _u.sum_table(names, (() if squeeze else (K,)) + self.coarse_shape), eng.device)
+        try:
+            self._grid.sums(_t.numpy_dtype(values.dtype), values.data_ptr(), K, plane, pitch,
+                            [(outs[k].data_ptr(), lay[k][1], lay[k][0]) if k in outs else None for k in _u.SUM_NAMES],
+                            where=_lib.DEVICE, stream=eng._stream())
+        except _lib.Mod16Error as e:
+            raise _lib.overlap_as_value_error(e)
+        return _u.UpscaledSums(*[outs.get(k) for k in _u.SUM_NAMES])
 
     def majority(self, cls, valid=None, outputs=('cls',), out=None):
         '''Enqueue the class kernel on the current stream (``mod16_upscale_classes``; the definition is
@@ -757,15 +783,21 @@ class RasterEngine(object):
         return DownscaleGrid(self, shape, coarse_shape, row_pos, col_pos, wrap=wrap, method=method,
                              col_affine=col_affine)
 
-    def upscale_grid(self, shape, coarse_shape, row_pos, col_pos, wrap=False, area=None, col_affine=None):
+    def upscale_grid(self, shape, coarse_shape, row_pos, col_pos=None, wrap=False, area=None, col_affine=None, col_range=None):
         '''The cells of an ``H x W`` coarse grid (``coarse_shape``) in an ``R x C`` fine raster (``shape``)
         on this engine's device -> ``UpscaleGrid``, the opposite direction of ``downscale_grid`` with the
         same position tables: ``row_pos[R]`` and ``col_pos[C]`` in units of coarse cells, cell centres at
         the integers (``mod16_amd.downscale.positions``). A pixel belongs to the cell its centre lies in,
         a pixel outside the grid to none; ``wrap``: the coarse column axis is periodic; ``area[R]``: the
-        weight of a pixel of that fine row (``cos(latitude)``; default 1). Only the rectilinear geometry
-        is covered: ``col_affine`` (a sinusoidal tile) is refused by name.'''
-        return UpscaleGrid(self, shape, coarse_shape, row_pos, col_pos, wrap=wrap, area=area, col_affine=col_affine)
+        weight of a pixel of that fine row (``cos(latitude)``; default 1). Exactly one of ``col_pos`` and
+        ``col_affine`` is given: ``col_affine = (col_origin[R], col_scale[R])`` are row-affine columns (a
+        sinusoidal tile, ``mod16_amd.downscale.sinusoidal_positions``), the column position of pixel ``(r,
+        c)`` being ``col_origin[r] + col_scale[r] * c``; ``col_range = (col_first[R], col_count[R])``
+        (int32; ``downscale.sinusoidal_columns``) then names the columns of every fine row that can
+        belong to a cell, the others being neither counted nor read. With ``wrap`` a fine row must not
+        span the whole periodic axis (``mod16_amd.upscale.check_rows``).'''
+        return UpscaleGrid(self, shape, coarse_shape, row_pos, col_pos, wrap=wrap, area=area, col_affine=col_affine,
+                           col_range=col_range)
 
     def gapfill(self, fields, qc=None, good=None, max_gap=None, fallback=None, dtype=None, scale=None,
                 source=False, out=None):

@@ -30,6 +30,25 @@ exact), every operation rounded on its own:
 the highest count, the LOWEST code on a tie (the site-level ancestor, ``Counter.most_common``, takes the
 first met, which depends on the traversal order); 255 where no pixel is valid; ``share =
 float32(float64(winner's count) / float64(pixels of the cell))``, 0 for an empty or all-invalid cell.
+
+Row-affine columns (a sinusoidal tile; ``col_affine = (col_origin[R], col_scale[R])`` as
+``mod16_amd.downscale`` has them). The column position of pixel ``(r, c)`` is ``col_origin[r] +
+col_scale[r] * c`` and its coarse column ``cell_table`` of that position, so the column run of a cell
+differs from fine row to fine row: ``cell_table_rows`` and ``cell_runs_rows`` state the geometry as ``(R,
+C)`` and ``(R, W)`` tables -- the tests' oracle; the device never sees them, it finds the runs from the
+two float64 of a row -- and ``aggregate_rows`` / ``majority_rows`` are ``aggregate`` / ``majority`` with
+the column run of cell ``j`` taken per fine row (``tot = tot + area[r] * float64(count[r, j])``; the
+pixels of a cell are ``sum_r count[r, j]``). ``col_range = (col_first[R], col_count[R])`` names the
+columns of every fine row that can belong to a cell (the on-globe pixels of an edge tile:
+``downscale.sinusoidal_columns``); the others belong to none and are not read. The pixels of one cell
+in one fine row must be ONE run of consecutive columns, never cyclic in ``c``; ``check_rows`` accepts a
+row without ``wrap``, or with ``n = col_count[r] <= 1``, or where ``abs(col_scale[r]) * float64(n - 1)
+<= float64(W - 2)``, which is sufficient for that: a row that spans the whole periodic axis (a mosaic
+row of 36 tiles) is refused -- upscale per tile or per half and ``merge``.
+
+``sums_rows`` / ``aggregate_rows(..., sums=True)`` stop before the divisions: ``UpscaledSums(num, den,
+tot, count)`` (float64 whatever the input type, int32), what a tile contributes to cells it covers
+only in part; ``merge`` adds the parts of several tiles IN THE GIVEN ORDER and divides once.
 '''
 import collections
 
@@ -45,6 +64,8 @@ CLASS_OUTPUT_NAMES = ('cls', 'share')
 Upscaled = collections.namedtuple('Upscaled', OUTPUT_NAMES)
 UpscaledClasses = collections.namedtuple('UpscaledClasses', CLASS_OUTPUT_NAMES)
 Runs = collections.namedtuple('Runs', ('first', 'count'))
+SUM_NAMES = ('num', 'den', 'tot', 'count')
+UpscaledSums = collections.namedtuple('UpscaledSums', SUM_NAMES)
 
 
 def _positions(pos, size):
@@ -139,11 +160,7 @@ def check_runs(runs, n, size, what, wrap=False):
     return Runs(first, count)
 
 
-def check_geometry(shape, coarse_shape, row_pos, col_pos, wrap=False, col_affine=None):
-    '''The checks of a grid: -> ``((R, C), (H, W), row_runs, col_runs)``.'''
-    if col_affine is not None:
-        raise ValueError('col_affine (row-affine columns, a sinusoidal tile) is not available for upscaling: '
-                         'give col_pos (a rectilinear geometry)')
+def _shapes(shape, coarse_shape):
     try:
         (R, C), (H, W) = (int(e) for e in shape), (int(e) for e in coarse_shape)
     except (TypeError, ValueError):
@@ -152,6 +169,17 @@ def check_geometry(shape, coarse_shape, row_pos, col_pos, wrap=False, col_affine
         if not 1 <= e <= _d.MAX_EXTENT:
             raise ValueError('rows, cols, coarse rows and coarse cols must be between 1 and %d, got %r over %r'
                              % (_d.MAX_EXTENT, (R, C), (H, W)))
+    return (R, C), (H, W)
+
+
+def check_geometry(shape, coarse_shape, row_pos, col_pos, wrap=False, col_affine=None):
+    '''The checks of a rectilinear grid: -> ``((R, C), (H, W), row_runs, col_runs)``. Row-affine columns
+    (``col_affine`` with ``col_pos=None``) have ``check_geometry_rows``.'''
+    if (col_pos is None) == (col_affine is None):
+        raise ValueError('exactly one of col_pos and col_affine must be given')
+    if col_affine is not None:
+        raise ValueError('col_affine (row-affine columns) has no column runs: its checks are check_geometry_rows')
+    (R, C), (H, W) = _shapes(shape, coarse_shape)
     row_pos, col_pos = np.asarray(row_pos, np.float64), np.asarray(col_pos, np.float64)
     if row_pos.shape != (R,) or col_pos.shape != (C,):
         raise ValueError('row_pos and col_pos must have shapes (%d,) and (%d,), got %r and %r'
@@ -160,6 +188,93 @@ def check_geometry(shape, coarse_shape, row_pos, col_pos, wrap=False, col_affine
     cols = cell_runs(cell_table(col_pos, W, wrap), W, wrap)
     check_cell_size(rows, cols)
     return (R, C), (H, W), rows, cols
+
+
+def check_col_range(col_range, R, C):
+    '''``(col_first[R], col_count[R])`` or None (the whole row) -> two contiguous int32 arrays with ``0 <=
+    first``, ``count >= 0`` and ``first + count <= C``; ValueError otherwise.'''
+    R, C = int(R), int(C)
+    if col_range is None:
+        return Runs(np.zeros(R, np.int32), np.full(R, C, np.int32))
+    if len(col_range) != 2:
+        raise ValueError('col_range must be (col_first, col_count)')
+    first, count = (np.asarray(t) for t in col_range)
+    if first.dtype != np.int32 or count.dtype != np.int32:
+        raise ValueError('col_range must hold two int32 arrays, got %s and %s' % (first.dtype, count.dtype))
+    if first.shape != (R,) or count.shape != (R,):
+        raise ValueError('col_range must hold two arrays of shape (%d,), got %r and %r' % (R, first.shape, count.shape))
+    f, n = first.astype(np.int64), count.astype(np.int64)
+    if np.any(f < 0) or np.any(n < 0) or np.any(f + n > C):
+        raise ValueError('col_range leaves the %d columns of a row (0 <= first, 0 <= count, first + count <= cols)' % C)
+    return Runs(np.ascontiguousarray(first), np.ascontiguousarray(count))
+
+
+def check_rows(shape, coarse_cols, col_affine, wrap=False, col_range=None):
+    '''The checks of row-affine columns -> ``((col_origin, col_scale), (col_first, col_count))``:
+    ``downscale.check_affine``, ``check_col_range`` and the acceptance rule of the module docstring, O(R).'''
+    R, C = int(shape[0]), int(shape[1])
+    W = int(coarse_cols)
+    if col_affine is None or len(col_affine) != 2:
+        raise ValueError('col_affine must be (col_origin, col_scale)')
+    origin, scale = _d.check_affine((R, C), col_affine[0], col_affine[1])
+    first, count = check_col_range(col_range, R, C)
+    if wrap:
+        n = count.astype(np.int64)
+        with np.errstate(all='ignore'):
+            laps = (n > 1) & ~(np.abs(scale) * (n - 1).astype(np.float64) <= np.float64(W - 2))
+        if laps.any():
+            r = int(np.flatnonzero(laps)[0])
+            raise ValueError('fine row %d may lap the periodic axis (abs(col_scale) * (columns - 1) = %r exceeds the %d '
+                             'coarse columns - 2): give a narrower col_range or cut the raster' %
+                             (r, float(abs(scale[r]) * float(n[r] - 1)), W))
+    return (origin, scale), Runs(first, count)
+
+
+def check_geometry_rows(shape, coarse_shape, row_pos, col_affine, wrap=False, col_range=None):
+    '''The checks of a grid with row-affine columns: -> ``((R, C), (H, W), row_runs, (col_origin, col_scale),
+    (col_first, col_count))``; ``col_range`` None comes back as the whole rows.'''
+    (R, C), (H, W) = _shapes(shape, coarse_shape)
+    row_pos = np.asarray(row_pos, np.float64)
+    if row_pos.shape != (R,):
+        raise ValueError('row_pos must have shape (%d,), got %r' % (R, row_pos.shape))
+    rows = cell_runs(cell_table(row_pos, H), H)
+    affine, col_range = check_rows((R, C), W, col_affine, wrap, col_range)
+    check_cell_size(rows, col_range)
+    return (R, C), (H, W), rows, affine, col_range
+
+
+def cell_table_rows(col_origin, col_scale, cols, size, wrap=False, col_range=None):
+    '''Row-affine columns: -> ``(R, C)`` int32, the coarse column of every pixel, -1 for "no cell":
+    ``cell_table`` (both of its branches as they are) applied to ``downscale.column_positions(col_origin,
+    col_scale, cols)``, and -1 outside the row's ``col_range``.'''
+    pos = _d.column_positions(col_origin, col_scale, cols)
+    R, C = pos.shape
+    if R > _d.MAX_EXTENT:
+        raise ValueError('col_origin must have at most %d entries, got %d' % (_d.MAX_EXTENT, R))
+    _positions(np.zeros(0), size)
+    cells = np.stack([cell_table(pos[r], size, wrap) for r in range(R)]) if R else np.zeros((0, C), np.int32)
+    first, count = check_col_range(col_range, R, C)
+    c = np.arange(C, dtype=np.int64)[None, :]
+    inside = (c >= first.astype(np.int64)[:, None]) & (c < (first.astype(np.int64) + count)[:, None])
+    return np.where(inside, cells, -1).astype(np.int32)
+
+
+def cell_runs_rows(cells, size):
+    '''``(first[R, W], count[R, W])`` (int32) of an ``(R, C)`` cell table: per fine row ``cell_runs(cells[r],
+    size, wrap=False)`` -- the pixels of one cell in one fine row must be ONE run of consecutive columns,
+    never cyclic in ``c``; ValueError naming the row and the cell otherwise.'''
+    cells = np.asarray(cells)
+    size = int(size)
+    if cells.ndim != 2 or cells.dtype.kind not in 'iu':
+        raise ValueError('a cell table of rows must be a two-dimensional integer array')
+    R = cells.shape[0]
+    first, count = np.zeros((R, size), np.int32), np.zeros((R, size), np.int32)
+    for r in range(R):
+        try:
+            first[r], count[r] = cell_runs(cells[r], size, wrap=False)
+        except ValueError as e:
+            raise ValueError('fine row %d: %s' % (r, e))
+    return Runs(first, count)
 
 
 def check_cell_size(row_runs, col_runs):
@@ -264,34 +379,177 @@ def aggregate(values, row_runs, col_runs, area=None, min_fraction=0.0, outputs=O
     names = check_outputs(outputs)
     H, W = rf.size, cf.size
     x3 = values.reshape(K, R, C).astype(np.float64)
+    first2, count2 = np.broadcast_to(cf.astype(np.int64), (R, W)), np.broadcast_to(cc.astype(np.int64), (R, W))
+    num, den, tot, cnt = _sums(x3, rf, rc, first2, count2, area)
+    return _finish(num, den, tot, cnt, min_fraction, names, (H, W) if squeeze else (K, H, W), dtype)
+
+
+def _sums(x3, rf, rc, first2, count2, area):
+    '''The sums of the definition: ``x3`` ``(K, R, C)`` float64, the row runs, the column run of cell ``j`` in
+    fine row ``r`` as ``first2[r, j]``, ``count2[r, j]`` (int64; rectilinear: the same in every row; cyclic
+    mod ``C``) -> ``(num, den, tot, cnt)``, ``(K, H, W)`` float64 and int64. Vectorised over layers and
+    cells, Python loops over the pixels of a cell.'''
+    K, R, C = x3.shape
+    H, W = rf.size, first2.shape[1]
     w = np.ones(R) if area is None else area
     num, den, tot = np.zeros((K, H, W)), np.zeros((K, H, W)), np.zeros((K, H, W))
     cnt = np.zeros((K, H, W), np.int64)
-    ccf = cc.astype(np.float64)[None, None, :]
     with np.errstate(all='ignore'):
         for t in range(int(rc.max(initial=0))):
             rows_on = t < rc                               # (H,)
             r = np.where(rows_on, rf.astype(np.int64) + t, 0)
+            cf, cc = first2[r], np.where(rows_on[:, None], count2[r], 0)       # (H, W)
             s = np.zeros((K, H, W))
             m = np.zeros((K, H, W), np.int64)
             for k in range(int(cc.max(initial=0))):
-                cols_on = k < cc                           # (W,)
-                col = np.where(cols_on, (cf.astype(np.int64) + k) % C, 0)
-                x = x3[:, r[:, None], col[None, :]]
-                ok = cols_on[None, None, :] & ~np.isnan(x)
+                cols_on = k < cc                           # (H, W)
+                col = np.where(cols_on, (cf + k) % C, 0)
+                x = x3[:, r[:, None], col]
+                ok = cols_on[None] & ~np.isnan(x)
                 s = np.where(ok, s + x, s)
                 m += ok
             a = w[r][None, :, None]
             on = rows_on[None, :, None]
             num = np.where(on, num + a * s, num)
             den = np.where(on, den + a * m.astype(np.float64), den)
-            tot = np.where(on, tot + a * ccf, tot)
+            tot = np.where(on, tot + a * cc.astype(np.float64)[None], tot)
             cnt += np.where(on, m, 0)
+    return num, den, tot, cnt
+
+
+def _finish(num, den, tot, cnt, min_fraction, names, shape, dtype):
+    '''``fraction``, ``mean`` and ``count`` from the sums, by the rules of the module docstring.'''
+    with np.errstate(all='ignore'):
         fraction = np.where(tot > 0, den / tot, 0.0)
         mean = np.where((cnt >= 1) & (den >= min_fraction * tot), num / den, np.nan)
     res = dict(mean=mean, fraction=fraction, count=cnt)
-    table = output_table(names, (H, W) if squeeze else (K, H, W), dtype)
+    table = output_table(names, shape, dtype)
     return Upscaled(*[res[k].astype(table[k][1]).reshape(table[k][0]) if k in table else None for k in OUTPUT_NAMES])
+
+
+def check_sum_outputs(outputs):
+    return _names(outputs, SUM_NAMES)
+
+
+def sum_table(names, shape):
+    '''What ``sums`` / ``sums_rows`` produce: name -> ``(shape, numpy dtype)`` for the requested ``names``.'''
+    return {k: (tuple(shape), np.dtype(np.int32 if k == 'count' else np.float64)) for k in SUM_NAMES if k in names}
+
+
+def _as_sums(num, den, tot, cnt, names, shape):
+    res = dict(num=num, den=den, tot=tot, count=cnt)
+    table = sum_table(names, shape)
+    return UpscaledSums(*[res[k].astype(table[k][1]).reshape(table[k][0]) if k in table else None for k in SUM_NAMES])
+
+
+def _values(values):
+    values = np.asarray(values)
+    dtype = check_dtype(values.dtype)
+    if values.ndim not in (2, 3):
+        raise ValueError('values must have shape (K, R, C) or (R, C), got %r' % (values.shape,))
+    R, C = values.shape[-2:]
+    K, squeeze = check_layers(values.shape, (R, C))
+    return values.reshape(K, R, C).astype(np.float64), dtype, (K, R, C), squeeze
+
+
+def sums(values, row_runs, col_runs, area=None, outputs=SUM_NAMES, wrap=False):
+    '''``aggregate`` stopped before its divisions (rectilinear): -> ``UpscaledSums(num, den, tot, count)``,
+    ``num``, ``den`` and ``tot`` float64 whatever the type of ``values``, ``count`` int32.'''
+    x3, _, (K, R, C), squeeze = _values(values)
+    rf, rc = check_runs(row_runs, R, len(row_runs[0]), 'row')
+    cf, cc = check_runs(col_runs, C, len(col_runs[0]), 'column', wrap)
+    check_cell_size((rf, rc), (cf, cc))
+    area = check_area(area, R)
+    names = check_sum_outputs(outputs)
+    H, W = rf.size, cf.size
+    first2, count2 = np.broadcast_to(cf.astype(np.int64), (R, W)), np.broadcast_to(cc.astype(np.int64), (R, W))
+    return _as_sums(*_sums(x3, rf, rc, first2, count2, area), names, (H, W) if squeeze else (K, H, W))
+
+
+def _rows_tables(shape, row_runs, col_affine, W, wrap, col_range):
+    R, C = shape
+    W = int(W)
+    rf, rc = check_runs(row_runs, R, len(row_runs[0]), 'row')
+    (origin, scale), col_range = check_rows((R, C), W, col_affine, wrap, col_range)
+    check_cell_size((rf, rc), col_range)
+    first2, count2 = cell_runs_rows(cell_table_rows(origin, scale, C, W, wrap, col_range), W)
+    return rf, rc, first2.astype(np.int64), count2.astype(np.int64)
+
+
+def sums_rows(values, row_runs, col_affine, W, wrap=False, col_range=None, area=None, outputs=SUM_NAMES):
+    '''``aggregate_rows`` stopped before its divisions: -> ``UpscaledSums``, as ``sums`` gives them.'''
+    x3, _, (K, R, C), squeeze = _values(values)
+    rf, rc, first2, count2 = _rows_tables((R, C), row_runs, col_affine, W, wrap, col_range)
+    area = check_area(area, R)
+    names = check_sum_outputs(outputs)
+    shape = (rf.size, int(W)) if squeeze else (K, rf.size, int(W))
+    return _as_sums(*_sums(x3, rf, rc, first2, count2, area), names, shape)
+
+
+def aggregate_rows(values, row_runs, col_affine, W, wrap=False, col_range=None, area=None, min_fraction=0.0,
+                   outputs=OUTPUT_NAMES):
+    '''``aggregate`` with row-affine columns: the column run of cell ``j`` is taken per fine row
+    (``cell_runs_rows`` of ``cell_table_rows``), in the same order -- per fine row of the cell in run
+    order, the columns in increasing ``c``, then the fold with ``area[r]`` and ``tot = tot + area[r] *
+    float64(count[r, j])`` -- with the same ``fraction``, ``mean`` and ``count`` rules and rounding.'''
+    x3, dtype, (K, R, C), squeeze = _values(values)
+    rf, rc, first2, count2 = _rows_tables((R, C), row_runs, col_affine, W, wrap, col_range)
+    area = check_area(area, R)
+    min_fraction = check_min_fraction(min_fraction)
+    names = check_outputs(outputs)
+    shape = (rf.size, int(W)) if squeeze else (K, rf.size, int(W))
+    return _finish(*_sums(x3, rf, rc, first2, count2, area), min_fraction, names, shape, dtype)
+
+
+def merge(parts, min_fraction=0.0, dtype=np.float64, shape=None, offsets=None, wrap=False):
+    '''The sums of several rasters (tiles) over one coarse grid -> ``Upscaled(mean, fraction, count)`` by the
+    rules of ``aggregate``, in ``dtype`` (float32: the float64 result rounded once). ``parts`` is a sequence
+    of ``UpscaledSums`` with all four fields, of equal shape -- or, with ``shape = (..., H, W)`` and ``offsets
+    = ((i0, j0), ...)``, each part a window of the accumulator that starts at coarse row ``i0`` and column
+    ``j0`` (columns modulo ``W`` with ``wrap``). The parts are added IN THE GIVEN ORDER, ``num = (num0 +
+    num1) + num2 ...`` from +0.0, likewise ``den`` and ``tot``, ``count`` as int64: float64 addition is not
+    associative, so the last bits of the result depend on the order of ``parts`` -- merge in a fixed order
+    (by tile number, say) for reproducible products. ValueError if a count leaves int32.'''
+    parts = [UpscaledSums(*p) for p in parts]
+    if not parts:
+        raise ValueError('merge needs at least one part')
+    for p in parts:
+        if any(a is None for a in p):
+            raise ValueError('every part must have all of %s' % ', '.join(SUM_NAMES))
+        if len({np.shape(a) for a in p}) != 1:
+            raise ValueError('the fields of a part must have one shape')
+    dtype = check_dtype(dtype)
+    min_fraction = check_min_fraction(min_fraction)
+    if (shape is None) != (offsets is None):
+        raise ValueError('shape and offsets must be given together')
+    if shape is None:
+        shape = np.shape(parts[0].num)
+        if any(np.shape(p.num) != shape for p in parts):
+            raise ValueError('the parts must have equal shape (or give shape and offsets)')
+        offsets = [(0, 0)] * len(parts)
+    shape = tuple(int(e) for e in shape)
+    offsets = [tuple(int(e) for e in o) for o in offsets]
+    if len(shape) < 2 or len(offsets) != len(parts) or any(len(o) != 2 for o in offsets):
+        raise ValueError('shape must be (..., H, W) and offsets one (i0, j0) per part')
+    H, W = shape[-2:]
+    num, den, tot = np.zeros(shape), np.zeros(shape), np.zeros(shape)
+    cnt = np.zeros(shape, np.int64)
+    with np.errstate(all='ignore'):
+        for p, (i0, j0) in zip(parts, offsets):
+            ps = np.shape(p.num)
+            if len(ps) != len(shape) or ps[:-2] != shape[:-2]:
+                raise ValueError('a part of shape %r does not fit an accumulator of shape %r' % (ps, shape))
+            h, w = ps[-2:]
+            if i0 < 0 or i0 + h > H or w > W or (not wrap and (j0 < 0 or j0 + w > W)):
+                raise ValueError('a part of %d x %d cells at offset %r leaves the %d x %d accumulator' % (h, w, (i0, j0), H, W))
+            rows = slice(i0, i0 + h)
+            cols = (j0 + np.arange(w)) % W
+            for acc, add, kind in ((num, p.num, np.float64), (den, p.den, np.float64), (tot, p.tot, np.float64),
+                                   (cnt, p.count, np.int64)):
+                acc[..., rows, cols] = acc[..., rows, cols] + np.asarray(add).astype(kind)
+    if cnt.size and cnt.max() > np.iinfo(np.int32).max:
+        raise ValueError('a merged count leaves int32')
+    return _finish(num, den, tot, cnt, min_fraction, OUTPUT_NAMES, shape, dtype)
 
 
 def majority(cls, row_runs, col_runs, valid=None, outputs=CLASS_OUTPUT_NAMES, wrap=False):
@@ -322,5 +580,37 @@ def majority(cls, row_runs, col_runs, valid=None, outputs=CLASS_OUTPUT_NAMES, wr
     pixels = rc.astype(np.float64)[:, None] * cc.astype(np.float64)[None, :]
     with np.errstate(all='ignore'):
         share = np.where(best > 0, best.astype(np.float64) / pixels, 0.0).astype(np.float32)
+    res = dict(cls=np.where(best > 0, winner, NO_CLASS).astype(np.uint8), share=share)
+    return UpscaledClasses(*[res[k] if k in names else None for k in CLASS_OUTPUT_NAMES])
+
+
+def majority_rows(cls, row_runs, col_affine, W, wrap=False, col_range=None, valid=None, outputs=CLASS_OUTPUT_NAMES):
+    '''``majority`` with row-affine columns: the pixels of cell ``(i, j)`` are those of its fine rows whose
+    coarse column (``cell_table_rows``) is ``j``, their number ``sum_r count[r, j]`` is taken as an integer
+    and then widened to float64; the same tie rule, ``valid`` mask and 255.'''
+    cls = np.asarray(cls)
+    if cls.ndim != 2 or cls.dtype != np.uint8:
+        raise ValueError('cls must be a two-dimensional uint8 array, got %s %r' % (cls.dtype, cls.shape))
+    R, C = cls.shape
+    W = int(W)
+    rf, rc, _, count2 = _rows_tables((R, C), row_runs, col_affine, W, wrap, col_range)
+    mask = valid_mask(valid)
+    names = check_class_outputs(outputs)
+    H = rf.size
+    (origin, scale), col_range = check_rows((R, C), W, col_affine, wrap, col_range)
+    col_cell = cell_table_rows(origin, scale, C, W, wrap, col_range).astype(np.int64)
+    row_cell = np.full(R, -1, np.int64)
+    for i in range(H):
+        row_cell[int(rf[i]):int(rf[i]) + int(rc[i])] = i
+    code_ok = np.array([(mask >> c) & 1 if c < MAX_CODES else 0 for c in range(256)], bool)
+    take = (row_cell[:, None] >= 0) & (col_cell >= 0) & code_ok[cls]
+    cell = (row_cell[:, None] * W + col_cell)[take]
+    counts = np.bincount(cls[take].astype(np.int64) * (H * W) + cell, minlength=MAX_CODES * H * W).reshape(MAX_CODES, H, W)
+    winner = counts.argmax(axis=0)                         # the first maximum: the lowest code
+    best = counts.max(axis=0)
+    pixels = np.zeros((H, W), np.int64)
+    np.add.at(pixels, row_cell[row_cell >= 0], count2[row_cell >= 0])
+    with np.errstate(all='ignore'):
+        share = np.where(best > 0, best.astype(np.float64) / pixels.astype(np.float64), 0.0).astype(np.float32)
     res = dict(cls=np.where(best > 0, winner, NO_CLASS).astype(np.uint8), share=share)
     return UpscaledClasses(*[res[k] if k in names else None for k in CLASS_OUTPUT_NAMES])

@@ -1645,6 +1645,94 @@ MOD16_API int mod16_zonal_bounds_f32(mod16_ctx* ctx, const mod16_zonal_spec* spe
 MOD16_API int mod16_zonal_lds_zones(void);
 
 /*
+ * Zonal histograms and exact zonal quantiles (added under ABI 16, new symbols only; mod16_amd.zonal_histogram,
+ * mod16_amd.zonal_quantiles, RasterEngine.zonal_histogram / zonal_selection / zonal_quantiles): per zone and layer the histogram
+ * of the values and exact order statistics -- the median and the spread of ET per biome, basin or
+ * country -- from int64 tables that 64-bit integer adds fill, so that, as for mod16_zonal_*, one
+ * launch, a call staged in tiles, calls that accumulate part after part and the sum of several
+ * devices' tables give the same words. The definition is the numpy statement mod16_amd/zonalq.py
+ * (histogram, digits, select):
+ *
+ *   inputs      values, zones, weights, zone_type, weight_kind, cols, first_pixel, value_pitch: as in
+ *               mod16_zonal_spec. width: 32 (float32) or 64 (float64), the bits of the values' type.
+ *   per pixel and layer
+ *               a zone id outside [0, nzones): skipped; x NaN or w NaN: skipped; !(0 <= w <= wmax):
+ *               skipped (infinite x takes part). The weight word is 1 (MOD16_ZONAL_WEIGHT_NONE) or qw =
+ *               (int64)rint(ldexp(w, 31 - ew)) <= 2^31, 0 < wmax <= 2^ew; a weight below 2^(ew - 32)
+ *               quantises to 0 and counts for nothing. The key is the order-preserving unsigned image
+ *               of the value in its own width: the bits, all flipped where the sign is set, else the
+ *               sign bit set (-0.0 < +0.0).
+ *   MOD16_ZONAL_HIST_UNIFORM
+ *               hist is int64 [layers][nzones][bins + 2], 1 <= bins <= 4094: word 0 the under bin (x <
+ *               lo), word bins + 1 the over bin (!(x < hi)), else word min(bins, 1 + (int)floor((x -
+ *               lo) * scale)) with x widened to float64, the subtraction and the multiply rounded once
+ *               each (no fused multiply-add); scale = bins / (hi - lo) is the caller's.
+ *   MOD16_ZONAL_HIST_DIGIT
+ *               hist is int64 [layers][nzones][slots][2^bits], 4 <= bits <= 12, 1 <= slots <= 16,
+ *               0 <= level < ceil(width / bits). Level 0 counts the top `bits` bits of every valid
+ *               pixel's key into slot 0 only (prefix is not looked at). On a level l >= 1 a pixel is
+ *               counted into every slot s for which the top l * bits bits of its key equal
+ *               prefix[layer][zone][s], under the next min(bits, width - l * bits) bits of its key.
+ *   hist        the call ADDS into it (the caller starts it with zeros). Valid while a zone and layer
+ *               holds fewer than 2^31 valid pixels over everything added into it. Two tables of the
+ *               same call shape add word by word.
+ *   mod16_zonal_select
+ *               closes a level of the digit form for every (layer, zone, slot). Level 0: W = the sum
+ *               of hist[layer][zone][0][*] goes to weight[layer][zone], and the target of slot s is
+ *               max(1, ceil(q_mant[s] * W / 2^q_exp[s])) in 128-bit integers (0 <= q_mant < 2^53, the
+ *               quantile q = q_mant / 2^q_exp in [0, 1] exactly: m, e = frexp(q), q_mant = m 2^53,
+ *               q_exp = 53 - e; q_mant and q_exp are host arrays of `slots` entries in both modes);
+ *               W = 0 leaves remaining = 0, which marks "no value". Every level: the first bin whose
+ *               running sum reaches remaining (level 0: the target; slot s reads slot 0's row) is
+ *               appended to prefix, and remaining drops by the sum before that bin. After the last
+ *               level the prefix is the key of the answer: out_values (of the values' type,
+ *               [layers][nzones][slots]) takes the value, NaN where remaining is 0 -- the smallest
+ *               value of the zone whose cumulative weight word reaches the target, the weighted
+ *               inverted-CDF quantile, an exact order statistic. The caller zeroes hist between levels.
+ *   kernel      zonal_kernel's traversal; tables of up to mod16_zonal_hist_lds_bytes() bytes (per
+ *               layer: nzones * slots * 2^bits words, one slot on level 0; nzones * (bins + 2)) are
+ *               filled in LDS with 64-bit LDS integer adds and flushed, the words that are not zero,
+ *               with global 64-bit integer atomic adds; larger ones take the adds in global memory.
+ *               A lane merges runs of equal table word in registers. No float atomics.
+ *   where       MOD16_DEVICE: device pointers, asynchronous on `stream` (no host synchronisation between
+ *               the levels). MOD16_HOST: host pointers; mod16_zonal_hist_* stage values, zones and
+ *               per-pixel weights tile by tile as mod16_zonal_* do, the table goes up once, every tile
+ *               adds into it, and it comes down once: the result does not depend on stage_bytes;
+ *               mod16_zonal_select runs the same integer loop on the CPU, with no device work.
+ *   refused (MOD16_ERR_ARG, before any device work and before an output is touched; "mod16_zonal_hist:
+ *   ...", "mod16_zonal_select: ...")
+ *               everything mod16_zonal_* refuses; an unknown mode; a width that is not that of the
+ *               values; bins, bits, slots or level out of range; lo, hi or scale not finite, hi <= lo,
+ *               scale <= 0; a NULL prefix on a level above 0; "the table overlaps an input";
+ *               mod16_zonal_select: a quantile outside [0, 1], a missing q_mant, q_exp or weight on
+ *               level 0, a missing out_values on the last level, an output on the table. n = 0 is
+ *               MOD16_OK and leaves hist untouched.
+ */
+enum mod16_zonal_hist_mode { MOD16_ZONAL_HIST_UNIFORM = 0, MOD16_ZONAL_HIST_DIGIT = 1 };
+typedef struct mod16_zonal_hist_spec {
+    int64_t n;                                   /* pixels */
+    int32_t layers, nzones;
+    int32_t zone_type, weight_kind;              /* enum mod16_zone_type, enum mod16_zonal_weight */
+    int64_t cols, first_pixel;                   /* per-row weights: raster columns, raster index of pixel 0 */
+    int64_t value_pitch;                         /* elements between two layers */
+    int32_t ew, mode;                            /* wmax <= 2^ew; enum mod16_zonal_hist_mode */
+    double wmax;                                 /* what a weight is tested against */
+    int32_t bins, width;                         /* uniform: bins; both: 32 or 64, the bits of a value */
+    double lo, hi, scale;                        /* uniform: the range and bins / (hi - lo) */
+    int32_t bits, level, slots, reserved;        /* digit: bits per level, the level, slots per zone */
+} mod16_zonal_hist_spec;
+MOD16_API int mod16_zonal_hist_f64(mod16_ctx* ctx, const mod16_zonal_hist_spec* spec, const double* values,
+                                   const void* zones, const void* weights, const uint64_t* prefix, int64_t* hist,
+                                   int where, void* stream, size_t stage_bytes);
+MOD16_API int mod16_zonal_hist_f32(mod16_ctx* ctx, const mod16_zonal_hist_spec* spec, const float* values,
+                                   const void* zones, const void* weights, const uint64_t* prefix, int64_t* hist,
+                                   int where, void* stream, size_t stage_bytes);
+MOD16_API int mod16_zonal_select(mod16_ctx* ctx, const mod16_zonal_hist_spec* spec, const int64_t* hist,
+                                 const int64_t* q_mant, const int32_t* q_exp, int64_t* remaining, uint64_t* prefix,
+                                 void* out_values, int64_t* weight, int where, void* stream);
+MOD16_API int mod16_zonal_hist_lds_bytes(void);
+
+/*
  * Composites over coarse-grid meteorology (ABI 16; mod16_amd.evapotranspiration_composite_downscaled,
  * DownscaleGrid.composite): the period totals of mod16_et_composite_* for a contiguous range of pixels
  * of a grid handle's fine raster, with any of the 15 arrays (the 14 drivers and day_hours) a series

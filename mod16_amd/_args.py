@@ -196,3 +196,54 @@ def _named_outputs(out, table):
 def _check_stage_bytes(stage_bytes):
     if stage_bytes is not None and int(stage_bytes) < 0:
         raise ValueError('stage_bytes must not be negative')
+
+
+def _zonal_inputs(values, zones, nzones, area):
+    '''What the zonal entry points (``zonal_statistics``, ``zonal_histogram``, ``zonal_quantiles``) make of
+    their arrays: -> ``(values (K, n), zones (n,), nzones, layered, weight kind, cols, weights or None)``.
+    ``values``: float32 or float64 of the zones' shape or ``(K,) +`` that shape; ``zones``: integers
+    (uint8, uint16 and int32 as they are, others range-checked and cast to int32); ``nzones`` None:
+    ``zones.max() + 1``; ``area``: None, a scalar (one "row" that holds every pixel), ``(R,)`` float64 for a
+    2-D raster of R rows, or an array of the zones' shape taken in the values' dtype.'''
+    from . import zonal as _z
+    values, zones = np.asarray(values), np.asarray(zones)
+    if values.dtype not in (np.float32, np.float64):
+        raise ValueError('values must be float32 or float64, got %s' % values.dtype)
+    if zones.dtype.kind not in 'iu':
+        raise ValueError('zones must be integers, got %s' % zones.dtype)
+    shape = zones.shape
+    if values.shape == shape:
+        layered, K = False, 1
+    elif values.ndim == zones.ndim + 1 and values.shape[1:] == shape:
+        layered, K = True, values.shape[0]
+    else:
+        raise ValueError('values must have the shape of zones %r or (K,) + that shape, got %r' % (shape, values.shape))
+    n = int(np.prod(shape, dtype=np.int64))
+    if n > _z.MAX_PIXELS:
+        raise ValueError('a call takes at most 2**30 pixels (accumulate parts with acc=), got %d' % n)
+    if not 1 <= K <= _z.MAX_LAYERS:
+        raise ValueError('between 1 and %d layers, got %d' % (_z.MAX_LAYERS, K))
+    if nzones is None:
+        nzones = max(int(zones.max()) + 1, 1) if n else 1
+    nzones = _z.check_nzones(nzones)
+    if zones.dtype.name not in _z.ZONE_TYPES:
+        if n and (int(zones.min()) < -2 ** 31 or int(zones.max()) >= 2 ** 31):
+            raise ValueError('zone ids must fit an int32')
+        zones = zones.astype(np.int32)
+    zones = np.ascontiguousarray(zones).reshape(n)
+    values = np.ascontiguousarray(values).reshape(K, n)
+    kind, cols, weights = _lib.ZONAL_WEIGHT_NONE, 1, None
+    if area is not None:
+        area = np.asarray(area)
+        if area.dtype.kind not in 'fiu':
+            raise ValueError('area must be numeric, got %s' % area.dtype)
+        if area.ndim == 0:               # one weight for every pixel: one "row" that holds them all
+            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(n, 1), np.array([area], np.float64)
+        elif len(shape) == 2 and area.shape == (shape[0],):
+            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(shape[1], 1), np.ascontiguousarray(area, np.float64)
+        elif area.shape == shape:
+            kind, weights = _lib.ZONAL_WEIGHT_PIXEL, np.ascontiguousarray(area, values.dtype).reshape(n)
+        else:
+            raise ValueError('area must be a scalar, (rows,) for a 2-D raster or of the shape of zones %r, got %r'
+                             % (shape, area.shape))
+    return values, zones, nzones, layered, kind, cols, weights

@@ -189,6 +189,25 @@ _ZONAL_ARGS = [C.c_void_p, C.POINTER(ZonalSpec), C.c_void_p, C.c_void_p, C.c_voi
 _ZONAL_BOUNDS_ARGS = [C.c_void_p, C.POINTER(ZonalSpec), C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
                       C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_size_t]
 
+
+class ZonalHistSpec(C.Structure):
+    '''``mod16_zonal_hist_spec`` (include/mod16_hip.h): the geometry fields of ``mod16_zonal_spec``, the
+    weight bound with its exponent, the mode, the uniform histogram's bins, range and scale, the
+    width of a value and the digit histogram's bits, level and slots.'''
+    _fields_ = [('n', C.c_int64), ('layers', C.c_int32), ('nzones', C.c_int32), ('zone_type', C.c_int32),
+                ('weight_kind', C.c_int32), ('cols', C.c_int64), ('first_pixel', C.c_int64),
+                ('value_pitch', C.c_int64), ('ew', C.c_int32), ('mode', C.c_int32), ('wmax', C.c_double),
+                ('bins', C.c_int32), ('width', C.c_int32), ('lo', C.c_double), ('hi', C.c_double),
+                ('scale', C.c_double), ('bits', C.c_int32), ('level', C.c_int32), ('slots', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+ZONAL_HIST_UNIFORM, ZONAL_HIST_DIGIT = 0, 1                     # enum mod16_zonal_hist_mode
+_ZONAL_HIST_ARGS = [C.c_void_p, C.POINTER(ZonalHistSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                    C.c_int, C.c_void_p, C.c_size_t]
+_ZONAL_SELECT_ARGS = [C.c_void_p, C.POINTER(ZonalHistSpec), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+
 _I32P = C.POINTER(C.c_int32)
 _DOWNSCALED_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, _PP, _I32P, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                     C.c_void_p, C.c_uint, C.c_int, C.c_void_p]
@@ -412,6 +431,10 @@ PROTOTYPES = {
     'mod16_zonal_bounds_f64': (C.c_int, _ZONAL_BOUNDS_ARGS),
     'mod16_zonal_bounds_f32': (C.c_int, _ZONAL_BOUNDS_ARGS),
     'mod16_zonal_lds_zones': (C.c_int, []),
+    'mod16_zonal_hist_f64': (C.c_int, _ZONAL_HIST_ARGS),
+    'mod16_zonal_hist_f32': (C.c_int, _ZONAL_HIST_ARGS),
+    'mod16_zonal_select': (C.c_int, _ZONAL_SELECT_ARGS),
+    'mod16_zonal_hist_lds_bytes': (C.c_int, []),
     'mod16_et_composite_downscaled_f64': (C.c_int, _COMPOSITE_DOWNSCALED_ARGS),
     'mod16_et_composite_downscaled_f32': (C.c_int, _COMPOSITE_DOWNSCALED_ARGS),
     'mod16_daynight_f64': (C.c_int, _DAYNIGHT_ARGS),
@@ -745,6 +768,44 @@ class Context:
         self.check(fn(self.handle, C.byref(spec), values, zones, weights, acc, int(where), stream,
                       0 if stage_bytes is None else int(stage_bytes)))
 
+    @staticmethod
+    def zonal_hist_spec(dtype, n, layers, nzones, zone_type=0, weight_kind=0, cols=1, first_pixel=0, value_pitch=None,
+                        wmax=1.0, ew=31, bins=None, lo=0.0, hi=0.0, scale=0.0, bits=0, level=0, slots=1):
+        '''A ``mod16_zonal_hist_spec``: uniform mode where ``bins`` is given, else digit mode.'''
+        for what, v in (('layers', layers), ('nzones', nzones), ('zone_type', zone_type), ('weight_kind', weight_kind),
+                        ('ew', ew), ('bins', bins or 0), ('bits', bits), ('level', level), ('slots', slots)):
+            if not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError('%s must fit an int32, got %r' % (what, v))
+        spec = ZonalHistSpec()
+        spec.n, spec.layers, spec.nzones = int(n), int(layers), int(nzones)
+        spec.zone_type, spec.weight_kind = int(zone_type), int(weight_kind)
+        spec.cols, spec.first_pixel = int(cols), int(first_pixel)
+        spec.value_pitch = int(n if value_pitch is None else value_pitch)
+        spec.ew, spec.wmax = int(ew), float(wmax)
+        spec.width = 8 * np.dtype(dtype).itemsize
+        if bins is not None:
+            spec.mode, spec.bins, spec.lo, spec.hi, spec.scale = ZONAL_HIST_UNIFORM, int(bins), float(lo), float(hi), float(scale)
+        else:
+            spec.mode, spec.bits, spec.level, spec.slots = ZONAL_HIST_DIGIT, int(bits), int(level), int(slots)
+        return spec
+
+    def zonal_hist(self, spec, dtype, values, zones, weights, prefix, hist, where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_zonal_hist_f64 / _f32 (raw addresses; ``spec`` from ``zonal_hist_spec``):
+        ADDS the uniform histogram, or one level's digit histogram, into ``hist``.'''
+        fn = typed(self.lib, 'mod16_zonal_hist', dtype)
+        self.check(fn(self.handle, C.byref(spec), values, zones, weights, prefix, hist, int(where), stream,
+                      0 if stage_bytes is None else int(stage_bytes)))
+
+    def zonal_select(self, spec, hist, remaining, prefix, out_values=None, weight=None, q=None, where=HOST, stream=None):
+        '''Thin wrapper of mod16_zonal_select (raw addresses): closes level ``spec.level``; ``q`` (level 0):
+        the quantiles as ``(M, E)`` pairs (``zonalq.rational``).'''
+        mant = exp = None
+        if q is not None:
+            mant = (C.c_int64 * len(q))(*[m for m, _ in q])
+            exp = (C.c_int32 * len(q))(*[e for _, e in q])
+        self.check(self.lib.mod16_zonal_select(self.handle, C.byref(spec), hist, mant, exp, remaining, prefix, out_values,
+                                               weight, int(where), stream))
+
     def zonal_bounds(self, dtype, n, layers, values, weights, weight_kind=0, cols=1, first_pixel=0,
                      value_pitch=None, where=HOST, stream=None, stage_bytes=None):
         '''Thin wrapper of mod16_zonal_bounds_f64 / _f32 (raw addresses): ``(wmax, xmax)``, the
@@ -778,6 +839,11 @@ def fill_composite_spec(spec, n, days, period_days, pixel_stride, time_stride, e
 def zonal_lds_zones():
     '''``mod16_zonal_lds_zones()``: the zone count up to which a block accumulates in LDS.'''
     return int(load().mod16_zonal_lds_zones())
+
+
+def zonal_hist_lds_bytes():
+    '''``mod16_zonal_hist_lds_bytes()``: the bytes of a layer's table up to which a block fills it in LDS.'''
+    return int(load().mod16_zonal_hist_lds_bytes())
 
 
 class Ensemble:

@@ -17,6 +17,7 @@
 #include "capi/downscale.hip"
 #include "capi/composite_downscale.hip"
 #include "capi/zonal.hip"
+#include "capi/zonalq.hip"
 #include "capi/daynight.hip"
 #include "capi/trend.hip"
 #include "capi/anomaly.hip"

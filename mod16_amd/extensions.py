@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._args import (_U16, _as_uint8, _broadcast, _check_stage_bytes, _marshal, _named_outputs, _outputs, _result_dtype,
-                    _shape, _shift)
+                    _shape, _shift, _zonal_inputs)
 from .downscale import MET_DRIVERS as _MET_DRIVERS
 
 
@@ -888,46 +888,8 @@ def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=Non
         ``(K, Z, 10)`` int64 accumulator; ``merge(other)``
     '''
     from . import zonal as _z
-    values, zones = np.asarray(values), np.asarray(zones)
-    if values.dtype not in (np.float32, np.float64):
-        raise ValueError('values must be float32 or float64, got %s' % values.dtype)
-    if zones.dtype.kind not in 'iu':
-        raise ValueError('zones must be integers, got %s' % zones.dtype)
-    shape = zones.shape
-    if values.shape == shape:
-        layered, K = False, 1
-    elif values.ndim == zones.ndim + 1 and values.shape[1:] == shape:
-        layered, K = True, values.shape[0]
-    else:
-        raise ValueError('values must have the shape of zones %r or (K,) + that shape, got %r' % (shape, values.shape))
-    n = int(np.prod(shape, dtype=np.int64))
-    if n > _z.MAX_PIXELS:
-        raise ValueError('a call takes at most 2**30 pixels (accumulate parts with acc=), got %d' % n)
-    if not 1 <= K <= _z.MAX_LAYERS:
-        raise ValueError('between 1 and %d layers, got %d' % (_z.MAX_LAYERS, K))
-    if nzones is None:
-        nzones = max(int(zones.max()) + 1, 1) if n else 1
-    nzones = _z.check_nzones(nzones)
-    if zones.dtype.name not in _z.ZONE_TYPES:
-        if n and (int(zones.min()) < -2 ** 31 or int(zones.max()) >= 2 ** 31):
-            raise ValueError('zone ids must fit an int32')
-        zones = zones.astype(np.int32)
-    zones = np.ascontiguousarray(zones).reshape(n)
-    values = np.ascontiguousarray(values).reshape(K, n)
-    kind, cols, weights = _lib.ZONAL_WEIGHT_NONE, 1, None
-    if area is not None:
-        area = np.asarray(area)
-        if area.dtype.kind not in 'fiu':
-            raise ValueError('area must be numeric, got %s' % area.dtype)
-        if area.ndim == 0:               # one weight for every pixel: one "row" that holds them all
-            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(n, 1), np.array([area], np.float64)
-        elif len(shape) == 2 and area.shape == (shape[0],):
-            kind, cols, weights = _lib.ZONAL_WEIGHT_ROW, max(shape[1], 1), np.ascontiguousarray(area, np.float64)
-        elif area.shape == shape:
-            kind, weights = _lib.ZONAL_WEIGHT_PIXEL, np.ascontiguousarray(area, values.dtype).reshape(n)
-        else:
-            raise ValueError('area must be a scalar, (rows,) for a 2-D raster or of the shape of zones %r, got %r'
-                             % (shape, area.shape))
+    values, zones, nzones, layered, kind, cols, weights = _zonal_inputs(values, zones, nzones, area)
+    K, n = values.shape
     _check_stage_bytes(stage_bytes)
     explicit = bounds is not None
     if acc is not None:
@@ -959,6 +921,143 @@ def zonal_statistics(values, zones, nzones=None, area=None, bounds=None, acc=Non
             raise ValueError('%d pixels of zone %d, layer %d lie outside the bounds (wmax %r, xmax %r)'
                              % (words[k, z, _z.REJECTED] - before[k, z], z, k, bounds[0], bounds[1]))
     return _z.ZonalResult(words, bounds[2], bounds[3], squeeze=not layered)
+
+
+def _zonalq_wmax(ctx, values, weights, kind, cols, wmax, stage_bytes):
+    '''``(wmax, ew)`` of a histogram call on host arrays: ``(1.0, 31)`` without weights, the given bound,
+    or what the ``mod16_zonal_bounds_*`` pre-pass finds.'''
+    from . import zonalq as _q
+    if kind == _lib.ZONAL_WEIGHT_NONE:
+        return 1.0, 31
+    K, n = values.shape
+    if wmax is None:
+        wmax = ctx.zonal_bounds(values.dtype, n, K, values.ctypes.data, weights.ctypes.data, weight_kind=kind, cols=cols,
+                                where=_lib.HOST, stage_bytes=stage_bytes)[0] if n else 1.0
+        wmax = wmax if wmax > 0 else 1.0
+    return _q.check_wmax(wmax)
+
+
+def zonal_histogram(values, zones, bins, range, nzones=None, area=None, wmax=None, acc=None, device=0, stage_bytes=None):
+    r'''
+    (Extension.) Zonal histograms of a raster: per zone and layer the weight of the valid pixels in
+    ``bins`` equal bins over ``range = (lo, hi)``, with an under bin (``x < lo``) and an over bin (``not x
+    < hi``), in one pass over the values (``mod16_zonal_hist_*``). The words are integers that integer
+    adds fill, so the result does not depend on ``stage_bytes``, on how a raster is cut into calls
+    that accumulate (``acc=``) or on the device that ran a part (``ZonalHistogram.merge``). The
+    definition is ``mod16_amd.zonalq`` (``histogram``).
+
+    Parameters
+    ----------
+    values, zones, nzones, area, device, stage_bytes
+        as in ``zonal_statistics``; infinite values take part (they land in the under or over bin)
+    bins : int
+        between 1 and 4094
+    range : (float, float)
+        ``(lo, hi)``, finite, ``lo < hi``; bin ``i`` holds ``lo + i (hi - lo) / bins <= x <`` the next edge
+    wmax : float
+        (Optional) the largest weight the call accepts (a pixel whose weight lies outside ``[0, wmax]``
+        is skipped); its exponent fixes the scale of the words, so calls that are to be accumulated
+        or merged must share it. Default: a pre-pass over the weights finds it
+    acc : ZonalHistogram
+        (Optional) a histogram to add into (it is not modified); with an ``area`` it needs ``wmax``
+
+    Returns
+    -------
+    mod16_amd.zonalq.ZonalHistogram
+        ``counts`` ``(K, Z, bins)``, ``under``, ``over`` ``(K, Z)`` (without the ``K`` for values without a
+        layer axis), ``edges``, ``words``, ``lo``, ``hi``, ``bins``, ``ew``, ``merge(other)``. A word times
+        ``2**(ew - 31)`` is a sum of weights; without weights ``ew`` is 31 and a word is a count.
+    '''
+    from . import zonal as _z, zonalq as _q
+    values, zones, nzones, layered, kind, cols, weights = _zonal_inputs(values, zones, nzones, area)
+    K, n = values.shape
+    bins = _q.check_bins(bins)
+    try:
+        lo, hi = range
+    except (TypeError, ValueError):
+        raise ValueError('range must be a pair (lo, hi), got %r' % (range,))
+    lo, hi, scale = _q.check_range(bins, lo, hi)
+    _check_stage_bytes(stage_bytes)
+    if acc is not None:
+        if not isinstance(acc, _q.ZonalHistogram):
+            raise ValueError('acc must be a ZonalHistogram')
+        if kind != _lib.ZONAL_WEIGHT_NONE:
+            _q.check_acc_wmax(wmax)
+        if acc.words.shape != (K, nzones, bins + 2) or (acc.lo, acc.hi) != (lo, hi):
+            raise ValueError('acc holds %r words over %r, this call needs %r over %r'
+                             % (acc.words.shape, (acc.lo, acc.hi), (K, nzones, bins + 2), (lo, hi)))
+    ctx = _lib.context(device)
+    wmax, ew = _zonalq_wmax(ctx, values, weights, kind, cols, wmax, stage_bytes)
+    if acc is not None and acc.ew != ew:
+        raise ValueError('the exponent of wmax, %d, differs from the histogram\'s %d' % (ew, acc.ew))
+    words = np.zeros((K, nzones, bins + 2), np.int64) if acc is None else acc.words.copy()
+    if n:
+        spec = ctx.zonal_hist_spec(values.dtype, n, K, nzones, _z.ZONE_TYPES[zones.dtype.name], kind, cols, 0, n, wmax, ew,
+                                   bins=bins, lo=lo, hi=hi, scale=scale)
+        ctx.zonal_hist(spec, values.dtype, values.ctypes.data, zones.ctypes.data, None if weights is None else weights.ctypes.data,
+                       None, words.ctypes.data, where=_lib.HOST, stage_bytes=stage_bytes)
+    return _q.ZonalHistogram(words, lo, hi, ew, squeeze=not layered)
+
+
+def zonal_quantiles(values, zones, q=(0.05, 0.5, 0.95), nzones=None, area=None, wmax=None, bits=None, device=0,
+                    stage_bytes=None):
+    r'''
+    (Extension.) Exact zonal quantiles of a raster: per zone, layer and ``q`` the smallest value of the
+    zone whose cumulative weight reaches ``q`` of the zone's total weight -- the weighted inverted-CDF
+    quantile, a value of the raster, found by radix selection over integer histograms of the values'
+    order-preserving keys (``mod16_zonal_hist_*``, ``mod16_zonal_select``). It does not depend on the
+    order of the pixels, on ``stage_bytes`` or on ``bits``. ``q`` is taken as the exact rational of its
+    double. The definition is ``mod16_amd.zonalq`` (``quantiles``).
+
+    The values are staged to the device once per level and the level is closed on the host: the call
+    crosses PCIe ``levels = ceil(width / bits)`` times (4 for float32 and 8 for float64 at 8 bits).
+    ``RasterEngine.zonal_quantiles`` keeps a resident stack on the device.
+
+    Parameters
+    ----------
+    values, zones, nzones, area, device, stage_bytes
+        as in ``zonal_statistics``; infinite values take part
+    q : float or sequence of float
+        between 1 and 16 quantiles in ``[0, 1]``
+    wmax : float
+        (Optional) the largest weight the call accepts (Default: a pre-pass finds it); a weight below
+        ``2**-32`` of the power of two above it counts for nothing
+    bits : int
+        (Optional) bits of the key a level resolves, 4 to 12 (Default: 8)
+
+    Returns
+    -------
+    mod16_amd.zonalq.ZonalQuantiles
+        ``values`` ``(K, Z, S)`` in the values' dtype (``(Z, S)`` for values without a layer axis; NaN where
+        a zone holds no weight), ``weight`` ``(K, Z)`` int64, ``q``, ``ew``
+    '''
+    from . import zonal as _z, zonalq as _q
+    values, zones, nzones, layered, kind, cols, weights = _zonal_inputs(values, zones, nzones, area)
+    K, n = values.shape
+    qs = _q.check_q(q)
+    bits = _q.DEFAULT_BITS if bits is None else _q.check_bits(bits)
+    _check_stage_bytes(stage_bytes)
+    ctx = _lib.context(device)
+    wmax, ew = _zonalq_wmax(ctx, values, weights, kind, cols, wmax, stage_bytes)
+    wd = _q.width(values.dtype)
+    nlevels, S = _q.levels(wd, bits), len(qs)
+    hist = np.zeros((K, nzones, S, 1 << bits), np.int64)
+    remaining = np.zeros((K, nzones, S), np.int64)
+    prefix = np.zeros((K, nzones, S), np.uint64)
+    weight = np.zeros((K, nzones), np.int64)
+    out = np.full((K, nzones, S), np.nan, values.dtype)
+    wptr = None if weights is None else weights.ctypes.data
+    for level in range(nlevels):
+        spec = ctx.zonal_hist_spec(values.dtype, n, K, nzones, _z.ZONE_TYPES[zones.dtype.name], kind, cols, 0, n, wmax, ew,
+                                   bits=bits, level=level, slots=S)
+        if n:
+            ctx.zonal_hist(spec, values.dtype, values.ctypes.data, zones.ctypes.data, wptr,
+                           prefix.ctypes.data if level else None, hist.ctypes.data, where=_lib.HOST, stage_bytes=stage_bytes)
+        ctx.zonal_select(spec, hist.ctypes.data, remaining.ctypes.data, prefix.ctypes.data,
+                         out.ctypes.data if level == nlevels - 1 else None, weight.ctypes.data if level == 0 else None,
+                         q=[_q.rational(v) for v in qs] if level == 0 else None, where=_lib.HOST)
+        hist[...] = 0
+    return _q.ZonalQuantiles(out, weight, qs, ew, squeeze=not layered)
 
 
 EnsembleQuantiles = _collections.namedtuple('EnsembleQuantiles', 'q day night total')

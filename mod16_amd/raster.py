@@ -489,6 +489,113 @@ class DownscaleGrid(object):
         self._grid.close()
 
 
+class ZonalSelection(object):
+    '''The state of a radix selection of zonal quantiles on one device (``RasterEngine.zonal_selection``):
+    ``hist`` ``(K, Z, S, 2**bits)`` int64, the digit histogram of the current ``level``; ``remaining`` and
+    ``prefix`` ``(K, Z, S)`` int64 (the prefix holds the bits of an unsigned key); ``weight`` ``(K, Z)``;
+    ``level``; ``done``. A level is ``add`` for every part of the raster, ``merge`` for every other device's
+    selection, then ``select()``. The first ``add`` fixes the weight bound ``wmax`` of the selection.'''
+
+    def __init__(self, engine, layers, nzones, q, bits=None):
+        from . import zonal as _z, zonalq as _q
+        torch = _torch()
+        self.engine = engine
+        self.q = _q.check_q(q)
+        self.bits = _q.DEFAULT_BITS if bits is None else _q.check_bits(bits)
+        self.layers, self.nzones = int(layers), _z.check_nzones(nzones)
+        if not 1 <= self.layers <= _z.MAX_LAYERS:
+            raise ValueError('between 1 and %d layers, got %d' % (_z.MAX_LAYERS, self.layers))
+        self.width = 8 * engine.np_dtype.itemsize
+        self.levels = _q.levels(self.width, self.bits)
+        dev, shape = engine._dev(), (self.layers, self.nzones, len(self.q))
+        self.hist = torch.zeros(shape + (1 << self.bits,), dtype=torch.int64, device=dev)
+        self.remaining = torch.zeros(shape, dtype=torch.int64, device=dev)
+        self.prefix = torch.zeros(shape, dtype=torch.int64, device=dev)
+        self.weight = torch.zeros(shape[:2], dtype=torch.int64, device=dev)
+        self.values = torch.full(shape, float('nan'), dtype=engine.dtype, device=dev)
+        self.level, self.done = 0, False
+        self.wmax = self.ew = None
+
+    def _spec(self, n=0, zone_type=0, kind=0, cols=1, first_pixel=0, pitch=None, wmax=1.0, ew=31):
+        return self.engine.ctx.zonal_hist_spec(self.engine.np_dtype, n, self.layers, self.nzones, zone_type, kind, cols,
+                                               first_pixel, pitch, wmax, ew, bits=self.bits, level=self.level,
+                                               slots=len(self.q))
+
+    def add(self, values, zones, area=None, cols=None, first_pixel=0, wmax=None):
+        '''Adds a part of the raster to the histogram of the current level (asynchronous). ``values``
+        ``(K, n)``, ``zones``, ``area``, ``cols``, ``first_pixel``: as in ``RasterEngine.zonal``. ``wmax``: with an
+        ``area``, the largest weight of the WHOLE raster -- every part and every level must use one
+        bound; None takes the selection's (the first ``add`` finds it with the ``zonal_bounds`` pre-pass
+        over its own part if none is given).'''
+        from . import zonal as _z
+        torch = _torch()
+        if self.done:
+            raise ValueError('the selection is finished')
+        eng = self.engine
+        K, n, pitch, kind, wptr, cols, first_pixel = eng._zonal_args(values, zones, area, cols, first_pixel)
+        if K != self.layers:
+            raise ValueError('values must have %d layers, got %d' % (self.layers, K))
+        if wmax is None and self.wmax is not None:
+            wmax = self.wmax
+        wmax, ew = eng._zonalq_wmax(values, area, cols, first_pixel, kind, wmax)
+        if self.wmax is not None and (wmax, ew) != (self.wmax, self.ew):
+            raise ValueError('every part and level of a selection must use one wmax: %r, then %r' % (self.wmax, wmax))
+        self.wmax, self.ew = wmax, ew
+        if n:
+            spec = self._spec(n, _z.ZONE_U8 if zones.dtype == torch.uint8 else _z.ZONE_I32, kind, cols, first_pixel, pitch, wmax, ew)
+            try:
+                eng.ctx.zonal_hist(spec, eng.np_dtype, values.data_ptr(), zones.data_ptr(), wptr,
+                                   self.prefix.data_ptr() if self.level else None, self.hist.data_ptr(),
+                                   where=_lib.DEVICE, stream=eng._stream())
+            except _lib.Mod16Error as e:
+                raise _lib.overlap_as_value_error(e)
+        return self
+
+    def merge(self, other):
+        '''Adds another selection's histogram of the same level (another device's share of the pixels).'''
+        if (other.level, other.bits, other.q, tuple(other.hist.shape)) != (self.level, self.bits, self.q, tuple(self.hist.shape)):
+            raise ValueError('selections of another level, shape or q cannot be merged')
+        if None not in (self.ew, other.ew) and (self.wmax, self.ew) != (other.wmax, other.ew):
+            raise ValueError('selections with the bounds %r and %r cannot be merged' % (self.wmax, other.wmax))
+        if self.ew is None:
+            self.wmax, self.ew = other.wmax, other.ew
+        self.hist += other.hist.to(self.hist.device)
+        return self
+
+    def adopt(self, other):
+        '''Takes ``remaining`` and ``prefix`` of a selection that closed the level for all devices.'''
+        self.remaining.copy_(other.remaining)
+        self.prefix.copy_(other.prefix)
+        self.weight.copy_(other.weight)
+        self.values.copy_(other.values)
+        self.hist.zero_()
+        self.level, self.done = other.level, other.done
+        return self
+
+    def select(self):
+        '''Closes the level on the device (``mod16_zonal_select``; asynchronous) and clears the histogram.'''
+        from . import zonalq as _q
+        if self.done:
+            raise ValueError('the selection is finished')
+        eng = self.engine
+        last = self.level == self.levels - 1
+        eng.ctx.zonal_select(self._spec(), self.hist.data_ptr(), self.remaining.data_ptr(), self.prefix.data_ptr(),
+                             self.values.data_ptr() if last else None, self.weight.data_ptr() if self.level == 0 else None,
+                             q=[_q.rational(v) for v in self.q] if self.level == 0 else None, where=_lib.DEVICE,
+                             stream=eng._stream())
+        self.hist.zero_()
+        self.level += 1
+        self.done = last
+        return self
+
+    def result(self):
+        '''The ``ZonalQuantiles`` of a finished selection (downloads: waits).'''
+        from . import zonalq as _q
+        if not self.done:
+            raise ValueError('the selection has %d of %d levels' % (self.level, self.levels))
+        return _q.ZonalQuantiles(self.values.cpu().numpy(), self.weight.cpu().numpy(), self.q, 31 if self.ew is None else self.ew)
+
+
 class RasterEngine(object):
     '''
     Parameters
@@ -1118,6 +1225,105 @@ class RasterEngine(object):
             except _lib.Mod16Error as e:
                 raise _lib.overlap_as_value_error(e)
         return acc
+
+    def _zonalq_wmax(self, values, area, cols, first_pixel, kind, wmax):
+        '''``(wmax, ew)`` of a histogram call: ``(1.0, 31)`` without weights (a word is a count), else the
+        given bound or, for None, what the ``zonal_bounds`` pre-pass finds (it waits for its result).'''
+        from . import zonalq as _q
+        if kind == _lib.ZONAL_WEIGHT_NONE:
+            return 1.0, 31
+        if wmax is None:
+            wmax = self.zonal_bounds(values, area, cols if kind == _lib.ZONAL_WEIGHT_ROW else None, first_pixel)[0]
+            wmax = wmax if wmax > 0 else 1.0
+        return _q.check_wmax(wmax)
+
+    def zonal_histogram(self, values, zones, nzones, bins, range, area=None, cols=None, first_pixel=0, wmax=None, acc=None):
+        '''Enqueue the uniform zonal histogram on the current stream: per zone and layer the weight
+        words of the valid pixels in ``bins`` equal bins over ``range = (lo, hi)``, with an under bin
+        in front and an over bin behind (``mod16_zonal_hist_*``; the definition is
+        ``mod16_amd.zonalq.histogram``). The words are integers: calls that add parts of a raster
+        into one ``acc`` give the words of one call over the whole.
+
+        ``values``, ``zones``, ``area``, ``cols``, ``first_pixel``: as in ``zonal``. ``wmax``: the largest
+        weight the call accepts; None runs the ``zonal_bounds`` pre-pass (which waits for its result).
+        ``acc``: a ``(K, nzones, bins + 2)`` int64 tensor to add into (then an ``area`` needs an explicit
+        ``wmax``); default a fresh one.
+
+        Returns the table tensor with ``ew`` (a word times ``2**(ew - 31)`` is a sum of weights; 31
+        without weights: a count) and ``range`` recorded on it;
+        ``mod16_amd.zonalq.ZonalHistogram(t.cpu().numpy(), *t.range, ew=t.ew)`` reads it. Asynchronous.'''
+        from . import zonal as _z, zonalq as _q
+        torch = _torch()
+        K, n, pitch, kind, wptr, cols, first_pixel = self._zonal_args(values, zones, area, cols, first_pixel)
+        nzones = _z.check_nzones(nzones)
+        bins = _q.check_bins(bins)
+        try:
+            lo, hi = range
+        except (TypeError, ValueError):
+            raise ValueError('range must be a pair (lo, hi), got %r' % (range,))
+        lo, hi, scale = _q.check_range(bins, lo, hi)
+        if acc is not None:
+            if kind != _lib.ZONAL_WEIGHT_NONE:
+                _q.check_acc_wmax(wmax)
+            _t.check_device(acc, 'acc', self.device, torch.int64)
+            if tuple(acc.shape) != (K, nzones, bins + 2):
+                raise ValueError('acc must have shape %r, got %r' % ((K, nzones, bins + 2), tuple(acc.shape)))
+            if not acc.is_contiguous():
+                raise TypeError('acc must be contiguous %s' % torch.int64)
+        wmax, ew = self._zonalq_wmax(values, area, cols, first_pixel, kind, wmax)
+        if acc is not None and getattr(acc, 'ew', ew) != ew:
+            raise ValueError('the exponent of wmax, %d, differs from the table\'s %d' % (ew, acc.ew))
+        if acc is None:
+            acc = torch.zeros((K, nzones, bins + 2), dtype=torch.int64, device=self._dev())
+        acc.ew, acc.range = ew, (lo, hi)
+        if n:
+            spec = self.ctx.zonal_hist_spec(self.np_dtype, n, K, nzones, _z.ZONE_U8 if zones.dtype == torch.uint8 else _z.ZONE_I32,
+                                            kind, cols, first_pixel, pitch, wmax, ew, bins=bins, lo=lo, hi=hi, scale=scale)
+            try:
+                self.ctx.zonal_hist(spec, self.np_dtype, values.data_ptr(), zones.data_ptr(), wptr, None, acc.data_ptr(),
+                                    where=_lib.DEVICE, stream=self._stream())
+            except _lib.Mod16Error as e:
+                raise _lib.overlap_as_value_error(e)
+        return acc
+
+    def zonal_selection(self, layers, nzones, q, bits=None):
+        '''A ``ZonalSelection``: the radix selection of exact zonal quantiles for rasters that arrive
+        in tiles or are dealt over devices. Every level sees every part once: ``.add`` each part,
+        ``.merge`` the other devices' selections of the same level, ``.select()``; after ``levels``
+        levels ``.result()`` gives the ``ZonalQuantiles``.'''
+        return ZonalSelection(self, layers, nzones, q, bits)
+
+    def zonal_quantiles(self, values, zones, nzones, q=(0.05, 0.5, 0.95), area=None, cols=None, first_pixel=0, wmax=None,
+                        bits=None, slab_bytes=None):
+        '''Exact weighted quantiles per zone and layer of a device-resident stack (the loop over the
+        levels of a ``ZonalSelection``; the definition is ``mod16_amd.zonalq.quantiles``): the smallest
+        value of the zone whose cumulative weight reaches ``q`` of the zone's total, an order statistic
+        that does not depend on the order of the pixels. Layers are processed in groups so that the
+        ``(K', Z, S, 2**bits)`` int64 table stays within ``slab_bytes`` (default 128 MiB; at least one
+        layer). Every level reads the values once and nothing waits for the host between levels.
+        Returns a ``mod16_amd.zonalq.ZonalQuantiles`` (downloads the results: waits).'''
+        from . import zonal as _z, zonalq as _q
+        K, n, pitch, kind, wptr, cols_, first_ = self._zonal_args(values, zones, area, cols, first_pixel)
+        nzones = _z.check_nzones(nzones)
+        qs = _q.check_q(q)
+        bits = _q.DEFAULT_BITS if bits is None else _q.check_bits(bits)
+        slab_bytes = (128 << 20) if slab_bytes is None else int(slab_bytes)
+        if slab_bytes < 0:
+            raise ValueError('slab_bytes must not be negative')
+        wmax, _ = self._zonalq_wmax(values, area, cols_, first_, kind, wmax)
+        group = max(1, min(K, slab_bytes // (nzones * len(qs) * (8 << bits))))
+        out, weight, ew = [], [], 31
+        for k0 in range(0, K, group):
+            part = values[k0:k0 + group]
+            sel = ZonalSelection(self, part.shape[0], nzones, qs, bits)
+            while not sel.done:
+                sel.add(part, zones, area=area, cols=cols, first_pixel=first_pixel, wmax=wmax)
+                sel.select()
+            res = sel.result()
+            out.append(res.values)
+            weight.append(res.weight)
+            ew = res.ew
+        return _q.ZonalQuantiles(np.concatenate(out), np.concatenate(weight), qs, ew)
 
     def ensemble(self, tables):
         '''The members of an ensemble forward run on this engine's device: ``tables`` is a (D, 13,

@@ -745,14 +745,21 @@ class Context:
                       0 if stage_bytes is None else int(stage_bytes)))
 
     @staticmethod
-    def _zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch, bounds=None):
-        for what, v in (('layers', layers), ('nzones', nzones), ('zone_type', zone_type), ('weight_kind', weight_kind)):
+    def _zonal_geometry(spec, n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch, **int32):
+        '''Fills the eight fields a ``ZonalSpec`` and a ``ZonalHistSpec`` share; ValueError where one of
+        their int32 fields, or of the further ones given by name, does not fit.'''
+        for what, v in dict(layers=layers, nzones=nzones, zone_type=zone_type, weight_kind=weight_kind, **int32).items():
             if not -2 ** 31 <= int(v) < 2 ** 31:
                 raise ValueError('%s must fit an int32, got %r' % (what, v))
-        spec = ZonalSpec()
         spec.n, spec.layers, spec.nzones = int(n), int(layers), int(nzones)
         spec.zone_type, spec.weight_kind = int(zone_type), int(weight_kind)
-        spec.cols, spec.first_pixel, spec.value_pitch = int(cols), int(first_pixel), int(value_pitch)
+        spec.cols, spec.first_pixel = int(cols), int(first_pixel)
+        spec.value_pitch = int(n if value_pitch is None else value_pitch)
+        return spec
+
+    @staticmethod
+    def _zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch, bounds=None):
+        spec = Context._zonal_geometry(ZonalSpec(), n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch)
         if bounds is not None:
             spec.wmax, spec.xmax, spec.ew, spec.ex = float(bounds[0]), float(bounds[1]), int(bounds[2]), int(bounds[3])
         return spec
@@ -762,8 +769,7 @@ class Context:
         '''Thin wrapper of mod16_zonal_f64 / _f32. ``values``, ``zones``, ``weights`` (or None) and
         ``acc`` are raw addresses; ``bounds`` is ``(wmax, xmax, ew, ex)`` (``zonal.check_bounds``);
         ``value_pitch`` None: ``n``; ``stage_bytes`` None: the library's default.'''
-        spec = self._zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel,
-                                n if value_pitch is None else value_pitch, bounds)
+        spec = self._zonal_spec(n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch, bounds)
         fn = typed(self.lib, 'mod16_zonal', dtype)
         self.check(fn(self.handle, C.byref(spec), values, zones, weights, acc, int(where), stream,
                       0 if stage_bytes is None else int(stage_bytes)))
@@ -772,15 +778,8 @@ class Context:
     def zonal_hist_spec(dtype, n, layers, nzones, zone_type=0, weight_kind=0, cols=1, first_pixel=0, value_pitch=None,
                         wmax=1.0, ew=31, bins=None, lo=0.0, hi=0.0, scale=0.0, bits=0, level=0, slots=1):
         '''A ``mod16_zonal_hist_spec``: uniform mode where ``bins`` is given, else digit mode.'''
-        for what, v in (('layers', layers), ('nzones', nzones), ('zone_type', zone_type), ('weight_kind', weight_kind),
-                        ('ew', ew), ('bins', bins or 0), ('bits', bits), ('level', level), ('slots', slots)):
-            if not -2 ** 31 <= int(v) < 2 ** 31:
-                raise ValueError('%s must fit an int32, got %r' % (what, v))
-        spec = ZonalHistSpec()
-        spec.n, spec.layers, spec.nzones = int(n), int(layers), int(nzones)
-        spec.zone_type, spec.weight_kind = int(zone_type), int(weight_kind)
-        spec.cols, spec.first_pixel = int(cols), int(first_pixel)
-        spec.value_pitch = int(n if value_pitch is None else value_pitch)
+        spec = Context._zonal_geometry(ZonalHistSpec(), n, layers, nzones, zone_type, weight_kind, cols, first_pixel, value_pitch,
+                                       ew=ew, bins=bins or 0, bits=bits, level=level, slots=slots)
         spec.ew, spec.wmax = int(ew), float(wmax)
         spec.width = 8 * np.dtype(dtype).itemsize
         if bins is not None:
@@ -811,7 +810,7 @@ class Context:
         '''Thin wrapper of mod16_zonal_bounds_f64 / _f32 (raw addresses): ``(wmax, xmax)``, the
         largest finite weight >= 0 (1.0 without weights) and the largest finite ``|x|`` of a call's
         inputs; synchronous.'''
-        spec = self._zonal_spec(n, layers, 1, 0, weight_kind, cols, first_pixel, n if value_pitch is None else value_pitch)
+        spec = self._zonal_spec(n, layers, 1, 0, weight_kind, cols, first_pixel, value_pitch)
         fn = typed(self.lib, 'mod16_zonal_bounds', dtype)
         wmax, xmax = C.c_double(0.0), C.c_double(0.0)
         self.check(fn(self.handle, C.byref(spec), values, weights, C.byref(wmax), C.byref(xmax), int(where), stream,

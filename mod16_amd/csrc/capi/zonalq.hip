@@ -1,14 +1,8 @@
 // libmod16hip.so -- zonal histograms and exact zonal quantiles: mod16_zonal_hist_f64 / _f32 (the uniform histogram, or one level's digit histogram under the prefix filter, ADDED into an int64 table), mod16_zonal_select (closes a level: target, prefix scan, the next prefix, the value at the end), mod16_zonal_hist_lds_bytes
-#include "host.hpp"
+#include "zonal_common.hpp"
 #include "../mod16_zonalq.hpp"
 
 namespace {
-size_t zonalq_zone_size(int zone_type) { return zone_type == MOD16_ZONE_U8 ? 1 : zone_type == MOD16_ZONE_U16 ? 2 : 4; }
-bool zonalq_aligned(const void* p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
-void zonalq_rows(const mod16_zonal_hist_spec& s, int64_t* r0, int64_t* r1) {
-    *r0 = s.first_pixel / s.cols;
-    *r1 = (s.first_pixel + s.n - 1) / s.cols;
-}
 int zonalq_levels(const mod16_zonal_hist_spec& s) { return (s.width + s.bits - 1) / s.bits; }
 // words per zone and slot, slots of the table in memory, words of the whole table
 int64_t zonalq_nb(const mod16_zonal_hist_spec& s) { return s.mode == MOD16_ZONAL_HIST_UNIFORM ? (int64_t)s.bins + 2 : (int64_t)1 << s.bits; }
@@ -33,80 +27,18 @@ static void zonalq_launch_lw(const ZonalHistArgs& a, int cus, int layers, hipStr
     else
         hipLaunchKernelGGL((zonal_hist_kernel<T, ZT, WK, MODE, 0>), grid(4), dim3(kBlock), 0, st, a);
 }
-template <typename T, typename ZT, int WK>
-static void zonalq_launch_mode(const ZonalHistArgs& a, int mode, int cus, int layers, hipStream_t st) {
-    if (mode == MOD16_ZONAL_HIST_UNIFORM) zonalq_launch_lw<T, ZT, WK, kZonalqUniform>(a, cus, layers, st);
-    else zonalq_launch_lw<T, ZT, WK, kZonalqDigit>(a, cus, layers, st);
-}
-template <typename T, typename ZT>
-static void zonalq_launch_wk(const ZonalHistArgs& a, int wk, int mode, int cus, int layers, hipStream_t st) {
-    if (wk == MOD16_ZONAL_WEIGHT_NONE) zonalq_launch_mode<T, ZT, kZonalWeightNone>(a, mode, cus, layers, st);
-    else if (wk == MOD16_ZONAL_WEIGHT_ROW) zonalq_launch_mode<T, ZT, kZonalWeightRow>(a, mode, cus, layers, st);
-    else zonalq_launch_mode<T, ZT, kZonalWeightPixel>(a, mode, cus, layers, st);
-}
 
 // All pointers are device pointers here; a.n > 0.
 template <typename T>
 static int launch_zonal_hist(mod16_ctx* ctx, ZonalHistArgs a, const mod16_zonal_hist_spec& s, hipStream_t st) {
-    constexpr size_t V = 16 / sizeof(T);
-    a.wide = zonalq_aligned(a.values, 16) && (s.layers == 1 || (size_t)a.pitch % V == 0) &&
-             zonalq_aligned(a.zones, V * zonalq_zone_size(s.zone_type)) &&
-             (s.weight_kind != MOD16_ZONAL_WEIGHT_PIXEL || zonalq_aligned(a.weights, 16));
-    if (s.zone_type == MOD16_ZONE_U8) zonalq_launch_wk<T, uint8_t>(a, s.weight_kind, s.mode, ctx->cus, s.layers, st);
-    else if (s.zone_type == MOD16_ZONE_U16) zonalq_launch_wk<T, uint16_t>(a, s.weight_kind, s.mode, ctx->cus, s.layers, st);
-    else zonalq_launch_wk<T, int32_t>(a, s.weight_kind, s.mode, ctx->cus, s.layers, st);
+    a.wide = zonal_wide<T>(a, s);
+    zonal_dispatch(s.zone_type, s.weight_kind, [&](auto zt, auto wk) {
+        using ZT = decltype(zt);
+        constexpr int WK = decltype(wk)::value;
+        if (s.mode == MOD16_ZONAL_HIST_UNIFORM) zonalq_launch_lw<T, ZT, WK, kZonalqUniform>(a, ctx->cus, s.layers, st);
+        else zonalq_launch_lw<T, ZT, WK, kZonalqDigit>(a, ctx->cus, s.layers, st);
+    });
     HIPCHK(ctx, hipGetLastError());
-    return MOD16_OK;
-}
-
-// HOST mode: as zonal_host -- values, zone ids and per-pixel weights staged tile by tile; the table
-// uploaded once, added into by the tiles of every slot's stream (integer atomics: the order does not
-// show) and downloaded once; the prefixes and the per-row weights the range touches uploaded once.
-template <typename T>
-static int zonal_hist_host(mod16_ctx* ctx, const mod16_zonal_hist_spec& s, ZonalHistArgs a, const uint64_t* prefix,
-                           int64_t* hist, int64_t stage_bytes) {
-    const size_t zsz = zonalq_zone_size(s.zone_type);
-    const size_t hist_bytes = sizeof(int64_t) * (size_t)zonalq_words(s);
-    DevMem dhist, drow, dpre;
-    int rc = dhist.alloc(ctx, hist_bytes, "mod16_zonal_hist: device memory for the table");
-    if (rc != MOD16_OK) return rc;
-    if (s.weight_kind == MOD16_ZONAL_WEIGHT_ROW) {
-        int64_t r0, r1;
-        zonalq_rows(s, &r0, &r1);
-        const size_t bytes = sizeof(double) * (size_t)(r1 - r0 + 1);
-        rc = drow.alloc(ctx, bytes, "mod16_zonal_hist: device memory for the per-row weights");
-        if (rc != MOD16_OK) return rc;
-        HIPCHK(ctx, hipMemcpy(drow.get(), static_cast<const double*>(a.weights) + r0, bytes, hipMemcpyHostToDevice));
-        a.row0 = r0;
-    }
-    if (prefix) {
-        const size_t bytes = sizeof(uint64_t) * (size_t)s.layers * (size_t)s.nzones * (size_t)s.slots;
-        rc = dpre.alloc(ctx, bytes, "mod16_zonal_hist: device memory for the prefixes");
-        if (rc != MOD16_OK) return rc;
-        HIPCHK(ctx, hipMemcpy(dpre.get(), prefix, bytes, hipMemcpyHostToDevice));
-        a.prefix = dpre.as<unsigned long long>();
-    }
-    HIPCHK(ctx, hipMemcpy(dhist.get(), hist, hist_bytes, hipMemcpyHostToDevice));
-    HostPlan p((int)sizeof(T));
-    const bool pixel_w = s.weight_kind == MOD16_ZONAL_WEIGHT_PIXEL;
-    p.add(kIn, a.values, false, s.layers, s.value_pitch);                       // 0
-    p.add(kIn, pixel_w ? a.weights : nullptr, false);                            // 1
-    if (zsz == 1) p.add(kIn, a.zones, true);                                     // 2: a byte row
-    else p.add(kIn, a.zones, false, 1, 0, (int)zsz);                             // 2: in a T-sized place
-    auto launch = [&](const HostTile& t) {
-        ZonalHistArgs d = a;
-        d.n = t.m;
-        d.values = t.dev[0];
-        d.pitch = (int64_t)(t.row_bytes / sizeof(T));
-        d.zones = t.dev[2];
-        d.weights = pixel_w ? t.dev[1] : drow.get();
-        d.first_pixel = a.first_pixel + t.off;
-        d.hist = dhist.as<unsigned long long>();
-        return launch_zonal_hist<T>(ctx, d, s, t.st);
-    };
-    rc = host_tiled(ctx, p, s.n, ctx->host_threads, false, launch, nullptr, stage_tile(p, sizeof(T), stage_bytes));
-    if (rc != MOD16_OK) return rc;
-    HIPCHK(ctx, hipMemcpy(hist, dhist.get(), hist_bytes, hipMemcpyDeviceToHost));
     return MOD16_OK;
 }
 
@@ -133,14 +65,8 @@ static const char* zonal_hist_check_table(const mod16_zonal_hist_spec* s) {
 static const char* zonal_hist_check_spec(const mod16_zonal_hist_spec* s) {
     if (s->n < 0 || s->n > (int64_t(1) << 30)) return "n must be between 0 and 2^30";
     if (const char* what = zonal_hist_check_table(s)) return what;
-    if (s->weight_kind != MOD16_ZONAL_WEIGHT_NONE && s->weight_kind != MOD16_ZONAL_WEIGHT_ROW && s->weight_kind != MOD16_ZONAL_WEIGHT_PIXEL)
-        return "weight_kind must be MOD16_ZONAL_WEIGHT_NONE, MOD16_ZONAL_WEIGHT_ROW or MOD16_ZONAL_WEIGHT_PIXEL";
-    if (s->weight_kind == MOD16_ZONAL_WEIGHT_ROW && s->cols < 1) return "per-row weights need cols >= 1";
-    if (s->weight_kind == MOD16_ZONAL_WEIGHT_ROW && (s->first_pixel < 0 || s->first_pixel > (int64_t(1) << 50)))
-        return "first_pixel must be between 0 and 2^50";
-    if (s->value_pitch < s->n) return "value_pitch must be at least n";
-    if (s->zone_type != MOD16_ZONE_U8 && s->zone_type != MOD16_ZONE_U16 && s->zone_type != MOD16_ZONE_I32)
-        return "zone_type must be MOD16_ZONE_U8, MOD16_ZONE_U16 or MOD16_ZONE_I32";
+    if (const char* what = zonal_check_geometry(s)) return what;
+    if (const char* what = zonal_check_zone_type(s->zone_type)) return what;
     const int64_t f = 31 - (int64_t)s->ew;                 // (in 64 bits: the exponent is the caller's)
     if (f > 900 || f < -900) return "the exponent ew puts the weight scale outside 2^-900 ... 2^900";
     if (!(s->wmax > 0.0) || !(s->wmax <= std::ldexp(1.0, s->ew))) return "the bound must satisfy 0 < wmax <= 2^ew";
@@ -161,38 +87,22 @@ static int zonal_hist_entry(mod16_ctx* ctx, const mod16_zonal_hist_spec* spec, c
     const bool filtered = spec->mode == MOD16_ZONAL_HIST_DIGIT && spec->level > 0;
     if (filtered && !prefix) return bad("NULL prefix on a level above 0");
     if (const char* what = check_where_stage(where, stage_bytes)) return bad(what);
-    const int64_t n = spec->n;
-    if (n == 0) return MOD16_OK;
+    if (spec->n == 0) return MOD16_OK;
+    const int64_t nprefix = filtered ? (int64_t)spec->layers * spec->nzones * spec->slots : 0;
     {
         const Extent out = extent(hist, zonalq_words(*spec), sizeof(int64_t));
         Extent ins[4];
-        int ni = 0;
-        ins[ni++] = extent(values, 1, 0, spec->layers, spec->value_pitch, n, sizeof(T));
-        ins[ni++] = extent(zones, n, zonalq_zone_size(spec->zone_type));
-        if (spec->weight_kind == MOD16_ZONAL_WEIGHT_PIXEL) ins[ni++] = extent(weights, n, sizeof(T));
-        if (spec->weight_kind == MOD16_ZONAL_WEIGHT_ROW) {
-            int64_t r0, r1;
-            zonalq_rows(*spec, &r0, &r1);
-            ins[ni++] = extent(static_cast<const double*>(weights) + r0, r1 - r0 + 1, sizeof(double));
-        }
-        if (filtered) ins[ni++] = extent(prefix, (int64_t)spec->layers * spec->nzones * spec->slots, sizeof(uint64_t));
+        int ni = zonal_input_extents(*spec, values, zones, weights, ins);
+        if (filtered) ins[ni++] = extent(prefix, nprefix, sizeof(uint64_t));
         if (overlaps(&out, 1, ins, ni)) return bad("the table overlaps an input");
     }
     ZonalHistArgs a;
     memset(&a, 0, sizeof a);
-    a.values = values;
-    a.zones = zones;
-    a.weights = weights;
+    zonal_fill_geometry(a, *spec, values, zones, weights);
     a.prefix = filtered ? reinterpret_cast<const unsigned long long*>(prefix) : nullptr;
     a.hist = reinterpret_cast<unsigned long long*>(hist);
-    a.n = n;
-    a.pitch = spec->value_pitch;
-    a.cols = spec->weight_kind == MOD16_ZONAL_WEIGHT_ROW ? spec->cols : 1;
-    a.inv_cols = 1.0 / (double)a.cols;
-    a.first_pixel = spec->weight_kind == MOD16_ZONAL_WEIGHT_ROW ? spec->first_pixel : 0;
     a.wmax = spec->wmax;
     a.wexp = 31 - spec->ew;
-    a.nzones = spec->nzones;
     a.nb = (int)zonalq_nb(*spec);
     a.slots = (int)zonalq_slots(*spec);
     a.seff = filtered ? spec->slots : 1;
@@ -211,7 +121,24 @@ static int zonal_hist_entry(mod16_ctx* ctx, const mod16_zonal_hist_spec* spec, c
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (where == MOD16_DEVICE) return launch_zonal_hist<T>(ctx, a, *spec, static_cast<hipStream_t>(stream));
-    return zonal_hist_host<T>(ctx, *spec, a, filtered ? prefix : nullptr, hist, stage_budget(stage_bytes));
+    // HOST mode: as mod16_zonal_* (zonal_host_tiled); the prefixes go up once, before the table
+    DevMem dpre;
+    if (filtered) {
+        const size_t bytes = sizeof(uint64_t) * (size_t)nprefix;
+        const int rc = dpre.alloc(ctx, bytes, "mod16_zonal_hist: device memory for the prefixes");
+        if (rc != MOD16_OK) return rc;
+        HIPCHK(ctx, hipMemcpy(dpre.get(), prefix, bytes, hipMemcpyHostToDevice));
+        a.prefix = dpre.as<unsigned long long>();
+    }
+    return zonal_host_tiled<T>(ctx, *spec, a, hist, sizeof(int64_t) * (size_t)zonalq_words(*spec),
+                               "mod16_zonal_hist: device memory for the table",
+                               "mod16_zonal_hist: device memory for the per-row weights", stage_budget(stage_bytes),
+                               [&](const ZonalGeom& g, void* dhist, hipStream_t st) {
+                                   ZonalHistArgs d = a;
+                                   static_cast<ZonalGeom&>(d) = g;
+                                   d.hist = static_cast<unsigned long long*>(dhist);
+                                   return launch_zonal_hist<T>(ctx, d, *spec, st);
+                               });
 }
 
 // the loop of zonal_select_kernel on the CPU (HOST mode: no device work)

@@ -42,18 +42,24 @@ enum { kZonalWeightNone = 0, kZonalWeightRow = 1, kZonalWeightPixel = 2 };     /
 constexpr long long kZonalKeyMax = 0x7fffffffffffffffLL;
 constexpr long long kZonalKeyMin = -kZonalKeyMax - 1;
 
-struct ZonalArgs {
+// what the kernels of both zonal families (this file, mod16_zonalq.hpp) read of a call: the pixels, their
+// zones and weights; zonal_traverse walks them
+struct ZonalGeom {
     const void* values;      // [layers][pitch] of T
     const void* zones;       // [n] of ZT
     const void* weights;     // per row: double, entry r is raster row row0 + r; per pixel: [n] of T
+    int64_t n, pitch, cols, first_pixel, row0;
+    double inv_cols;
+    int nzones;
+    int wide;                // every row allows vector access
+};
+
+struct ZonalArgs : ZonalGeom {
     long long* acc;          // [layers][nzones][10]
     unsigned long long* bounds;   // zonal_bounds_kernel: the bits of max w, max |x|
-    int64_t n, pitch, cols, first_pixel, row0;
     int64_t rows;            // zonal_bounds_kernel, per-row weights: the entries of `weights` the range touches
-    double wmax, xmax, inv_cols;
-    int nzones;
+    double wmax, xmax;
     int f[3];                // fractional bits of w, w x, w x x
-    int wide;                // every row allows vector access
 };
 
 template <typename E, int N> struct alignas(sizeof(E) * N) ZonalVec { E v[N]; };
@@ -196,6 +202,74 @@ __device__ __forceinline__ void zonal_row(int64_t g, int64_t cols, double inv_co
     if (col >= cols) { ++row; col -= cols; }
 }
 
+// The traversal of both families: blockIdx.y is the layer; the block owns one contiguous range of
+// 16-byte vectors and strides through it, consecutive lanes on consecutive vectors, every lane of the
+// block with the same number of trips (a lane past the range has nv = 0: `step` may use wave-wide
+// operations). Per trip the lane loads its V = 16 / sizeof(T) values, zone ids and (per pixel)
+// weights -- as vectors where g.wide and the vector is whole, else element by element, 0 past the
+// range -- and calls step(nv, x, z, weight): the pixels k < nv count, and weight(k) is pixel k's weight
+// as a double. `step` asks for it once per pixel, k = 0 ... V - 1 in this order: per row it is one
+// lookup where the vector begins and one more wherever a row ends inside it, a walk that moves on.
+template <typename T, typename ZT, int WK, typename Step>
+__device__ __forceinline__ void zonal_traverse(const ZonalGeom& g, Step&& step) {
+    constexpr int V = 16 / (int)sizeof(T);
+    const T* const vrow = static_cast<const T*>(g.values) + (int64_t)blockIdx.y * g.pitch;
+    const ZT* const zrow = static_cast<const ZT*>(g.zones);
+    const int64_t nvec = (g.n + V - 1) / V;
+    const int64_t per = (nvec + gridDim.x - 1) / gridDim.x;
+    const int64_t v0 = (int64_t)blockIdx.x * per;
+    const int64_t v1 = v0 + per < nvec ? v0 + per : nvec;
+    for (int64_t vb = v0; vb < v1; vb += kBlock) {
+        const int64_t v = vb + threadIdx.x;
+        const int64_t p0 = v * V;
+        const int nv = v >= v1 ? 0 : g.n - p0 < V ? (int)(g.n - p0) : V;
+        T x[V];
+        ZT z[V];
+        [[maybe_unused]] T wp[V];
+        if (nv == V && g.wide) {
+            const ZonalVec<T, V> xv = *reinterpret_cast<const ZonalVec<T, V>*>(vrow + p0);
+            const ZonalVec<ZT, V> zv = *reinterpret_cast<const ZonalVec<ZT, V>*>(zrow + p0);
+#pragma unroll
+            for (int k = 0; k < V; ++k) { x[k] = xv.v[k]; z[k] = zv.v[k]; }
+            if constexpr (WK == kZonalWeightPixel) {
+                const ZonalVec<T, V> wv = *reinterpret_cast<const ZonalVec<T, V>*>(static_cast<const T*>(g.weights) + p0);
+#pragma unroll
+                for (int k = 0; k < V; ++k) wp[k] = wv.v[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const bool in = k < nv;
+                x[k] = in ? vrow[p0 + k] : (T)0;
+                z[k] = in ? zrow[p0 + k] : (ZT)0;
+                if constexpr (WK == kZonalWeightPixel) wp[k] = in ? static_cast<const T*>(g.weights)[p0 + k] : (T)0;
+            }
+        }
+        [[maybe_unused]] int64_t row = 0, col = 0;
+        [[maybe_unused]] double wr = 1.0;
+        if constexpr (WK == kZonalWeightRow) {
+            if (nv > 0) {
+                zonal_row(g.first_pixel + p0, g.cols, g.inv_cols, row, col);
+                wr = static_cast<const double*>(g.weights)[row - g.row0];
+            }
+        }
+        step(nv, x, z, [&](int k) {
+            if constexpr (WK == kZonalWeightRow) {
+                if (k > 0 && k < nv && ++col == g.cols) {
+                    col = 0;
+                    ++row;
+                    wr = static_cast<const double*>(g.weights)[row - g.row0];
+                }
+                return wr;
+            } else if constexpr (WK == kZonalWeightPixel) {
+                return (double)wp[k];
+            } else {
+                return 1.0;
+            }
+        });
+    }
+}
+
 template <typename T, typename ZT, int WK, int LZ>
 __global__ __launch_bounds__(kBlock) void zonal_kernel(ZonalArgs a) {
     constexpr int V = 16 / (int)sizeof(T);
@@ -211,64 +285,12 @@ __global__ __launch_bounds__(kBlock) void zonal_kernel(ZonalArgs a) {
         }
         __syncthreads();
     }
-    const T* const vrow = static_cast<const T*>(a.values) + (int64_t)blockIdx.y * a.pitch;
-    const ZT* const zrow = static_cast<const ZT*>(a.zones);
-    const int64_t nvec = (a.n + V - 1) / V;
-    const int64_t per = (nvec + gridDim.x - 1) / gridDim.x;
-    const int64_t v0 = (int64_t)blockIdx.x * per;
-    const int64_t v1 = v0 + per < nvec ? v0 + per : nvec;
     ZonalRun run;
     zonal_reset(run, -1);
-    for (int64_t vb = v0; vb < v1; vb += kBlock) {         // (the same trips for every lane of the block)
-        const int64_t v = vb + threadIdx.x;
-        const int64_t p0 = v * V;
-        const int nv = v >= v1 ? 0 : a.n - p0 < V ? (int)(a.n - p0) : V;
-        T x[V];
-        ZT z[V];
-        [[maybe_unused]] T wp[V];
-        if (nv == V && a.wide) {
-            const ZonalVec<T, V> xv = *reinterpret_cast<const ZonalVec<T, V>*>(vrow + p0);
-            const ZonalVec<ZT, V> zv = *reinterpret_cast<const ZonalVec<ZT, V>*>(zrow + p0);
+    zonal_traverse<T, ZT, WK>(a, [&](int nv, const T (&x)[V], const ZT (&z)[V], auto&& weight) {
 #pragma unroll
-            for (int k = 0; k < V; ++k) { x[k] = xv.v[k]; z[k] = zv.v[k]; }
-            if constexpr (WK == kZonalWeightPixel) {
-                const ZonalVec<T, V> wv = *reinterpret_cast<const ZonalVec<T, V>*>(static_cast<const T*>(a.weights) + p0);
-#pragma unroll
-                for (int k = 0; k < V; ++k) wp[k] = wv.v[k];
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                const bool in = k < nv;
-                x[k] = in ? vrow[p0 + k] : (T)0;
-                z[k] = in ? zrow[p0 + k] : (ZT)0;
-                if constexpr (WK == kZonalWeightPixel) wp[k] = in ? static_cast<const T*>(a.weights)[p0 + k] : (T)0;
-            }
-        }
-        [[maybe_unused]] int64_t row = 0, col = 0;
-        [[maybe_unused]] double wr = 1.0;
-        if constexpr (WK == kZonalWeightRow) {
-            if (nv > 0) {
-                zonal_row(a.first_pixel + p0, a.cols, a.inv_cols, row, col);
-                wr = static_cast<const double*>(a.weights)[row - a.row0];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            double w = 1.0;
-            if constexpr (WK == kZonalWeightRow) {
-                if (k > 0 && k < nv && ++col == a.cols) {
-                    col = 0;
-                    ++row;
-                    wr = static_cast<const double*>(a.weights)[row - a.row0];
-                }
-                w = wr;
-            } else if constexpr (WK == kZonalWeightPixel) {
-                w = (double)wp[k];
-            }
-            zonal_pixel<LDS>(run, k < nv, (int64_t)z[k], (double)x[k], w, a, table);
-        }
-    }
+        for (int k = 0; k < V; ++k) zonal_pixel<LDS>(run, k < nv, (int64_t)z[k], (double)x[k], weight(k), a, table);
+    });
     if constexpr (LDS) zonal_flush<true>(run, table);
     else zonal_flush_wave(run, true, table);
     if constexpr (LDS) {

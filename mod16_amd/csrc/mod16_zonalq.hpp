@@ -9,15 +9,16 @@
 // first: an exact order statistic. A word is valid while a zone and layer holds fewer than 2^31
 // valid pixels over everything added into it.
 //
-// zonal_hist_kernel keeps zonal_kernel's traversal: blockIdx.y is the layer; a block owns one
-// contiguous range of 16-byte vectors and strides through it, consecutive lanes on consecutive
-// vectors; rows that are not 16-byte aligned, and a ragged last vector, take scalar accesses; the row
-// of a pixel comes without a 64-bit division (zonal_row). Per valid pixel the lane forms the uniform
-// bin (UNIFORM; explicit round-once subtraction and multiply) or the key's digit (DIGIT; at a level
-// >= 1 under the prefix filter of up to `slots` slots of its zone) and adds its weight word to one
-// table word per matching slot. A lane merges runs of equal table word in registers before it adds
-// (one run: the slots of a vector's pixels are visited slot by slot, so the pixels of a vector that
-// share a word leave as one add).
+// zonal_hist_kernel walks a ZonalGeom as zonal_traverse does (mod16_zonal.hpp: the block's range of
+// 16-byte vectors, the loads, the per-row weight walk) but keeps a loop of its own: as a step of
+// zonal_traverse its float64 histogram into a global table (2025 zones, 46 layers of 5.76 M pixels)
+// took 8.5846 ms against 8.5778 ms, 0.0068 ms more where this loop's own repeats spread over 0.0065 ms
+// (profiles/zonal_shared_traversal_speed.txt). A change to the walk is made in both. Per valid pixel
+// the lane forms the uniform bin (UNIFORM; explicit round-once subtraction and multiply) or the key's
+// digit (DIGIT; at a level >= 1 under the prefix filter of up to `slots` slots of its zone) and adds
+// its weight word to one table word per matching slot. A lane merges runs of equal table word in
+// registers before it adds (one run: the slots of a vector's pixels are visited slot by slot, so the
+// pixels of a vector that share a word leave as one add).
 //   LW > 0   the block's LDS table of nzones * S_eff * nb words (S_eff = 1 on level 0 and in uniform
 //            mode) with 64-bit LDS integer adds (ds_add_u64); at its end the block flushes the words
 //            that are not zero with global 64-bit integer atomic adds.
@@ -45,16 +46,11 @@ constexpr int kZonalqLdsPrefix = 256;        // prefixes of a layer a block keep
 constexpr int kZonalqMaxSlots = 16;
 enum { kZonalqUniform = 0, kZonalqDigit = 1 };       // enum mod16_zonal_hist_mode
 
-struct ZonalHistArgs {
-    const void* values;      // [layers][pitch] of T
-    const void* zones;       // [n] of ZT
-    const void* weights;     // per row: double, entry r is raster row row0 + r; per pixel: [n] of T
+struct ZonalHistArgs : ZonalGeom {
     const unsigned long long* prefix;   // [layers][nzones][slots]; level >= 1
     unsigned long long* hist;           // [layers][nzones][slots][nb] (digit) or [layers][nzones][nb] (uniform)
-    int64_t n, pitch, cols, first_pixel, row0;
-    double wmax, inv_cols, lo, hi, scale;
-    int nzones, wexp;        // wexp = 31 - ew
-    int wide;                // every row allows vector access
+    double wmax, lo, hi, scale;
+    int wexp;                // 31 - ew
     int nb;                  // words per zone and slot: 2^bits, or bins + 2
     int bins;
     int slots;               // slots of the table in memory

@@ -174,6 +174,27 @@ def test_small_shapes(dtype, n):
 
 
 @pytest.mark.parametrize('dtype', ['float64', 'float32'])
+@pytest.mark.parametrize('cols', [1, 3])
+def test_rows_narrower_than_a_vector(dtype, cols):
+    """Per-row weights over rows of 1 and 3 pixels: a 16-byte vector of 2 or 4 values crosses a row end
+    more than once. The range starts at raster pixel 2; 2051 pixels are several blocks, the last vector
+    ragged; the weights are positive, (first_pixel + n - 1) // cols + 1 of them."""
+    import torch
+    n, first, layers, nzones = 2051, 2, 2, 5
+    rng = np.random.default_rng(11)
+    x = rng.gamma(2.0, 1.5, size=(layers, n)).astype(dtype)
+    z = np.where(rng.random(n) < 0.2, rng.integers(0, nzones, n), (np.arange(n) // 29) % nzones)
+    wr = 1e5 * (1.5 + np.cos(np.arange((first + n - 1) // cols + 1)))
+    assert len(wr) == {1: 2053, 3: 685}[cols] and (wr > 0).all()
+    want = zs.accumulate(x, z, nzones, weights=wr, cols=cols, first_pixel=first, bounds=BOUNDS['odd'])
+    assert want[..., zs.COUNT].sum() == layers * n
+    got = engine(dtype).zonal(dev(x), dev(z.astype(np.uint8)), nzones, area=dev(wr), cols=cols, first_pixel=first,
+                              bounds=BOUNDS['odd'])
+    torch.cuda.synchronize()
+    assert np.array_equal(got.cpu().numpy(), want)
+
+
+@pytest.mark.parametrize('dtype', ['float64', 'float32'])
 @pytest.mark.parametrize('ztype', [np.uint8, np.int32])
 def test_unaligned_views_and_value_pitch(dtype, ztype):
     import torch

@@ -207,6 +207,36 @@ def test_histogram_equals_the_definition(dtype, n, K, zones, bins, zone_dtype, k
 
 
 @pytest.mark.parametrize('dtype', ('float32', 'float64'))
+@pytest.mark.parametrize('cols', (1, 3))
+def test_rows_narrower_than_a_vector(dtype, cols):
+    """Per-row weights over rows of 1 and 3 pixels: a 16-byte vector of 2 or 4 values crosses a row end
+    more than once. The range starts at raster pixel 2; 2051 pixels are several blocks, the last vector
+    ragged; the weights are positive, (first_pixel + n - 1) // cols + 1 of them. The uniform histogram
+    with 8 bins and the digit table of level 0 with bits = 8, word for word."""
+    import torch
+    from mod16_amd import _lib
+    n, first, K, nzones = 2051, 2, 2, 5
+    eng = engine(dtype)
+    rng = np.random.default_rng(13)
+    x = rng.normal(3.0, 2.0, (K, n)).astype(dtype)
+    z = np.where(rng.random(n) < 0.2, rng.integers(0, nzones, n), (np.arange(n) // 29) % nzones)
+    wr = 1e5 * (1.5 + np.cos(np.arange((first + n - 1) // cols + 1)))
+    assert len(wr) == {1: 2053, 3: 685}[cols] and (wr > 0).all()
+    kw = dict(weights=wr, cols=cols, first_pixel=first, wmax=WMAX)
+    vals, zones, area = (torch.from_numpy(a).to(eng._dev()) for a in (x, z.astype(np.uint8), wr))
+    got = eng.zonal_histogram(vals, zones, nzones, 8, RANGE, area=area, cols=cols, first_pixel=first, wmax=WMAX)
+    want = Q.histogram(x, z, nzones, 8, *RANGE, **kw)
+    assert want.sum() > 0 and np.array_equal(got.cpu().numpy(), want)
+    spec = eng.ctx.zonal_hist_spec(eng.np_dtype, n, K, nzones, _lib.ZONE_U8, _lib.ZONAL_WEIGHT_ROW, cols, first, n, WMAX, 18,
+                                   bits=8, level=0, slots=1)
+    table = torch.zeros((K, nzones, 1, 256), dtype=torch.int64, device=eng._dev())
+    eng.ctx.zonal_hist(spec, eng.np_dtype, vals.data_ptr(), zones.data_ptr(), area.data_ptr(), None, table.data_ptr(),
+                       where=_lib.DEVICE, stream=eng._stream())
+    torch.cuda.synchronize()
+    assert np.array_equal(table.cpu().numpy(), Q.digits(x, z, nzones, 0, 8, slots=1, **kw))
+
+
+@pytest.mark.parametrize('dtype', ('float32', 'float64'))
 @pytest.mark.parametrize('zmap,raster,nzones,S,bits', [
     ('blocks', 'constant', 13, 3, 8),           # every pixel of every level on one word per zone and slot
     ('single', 'constant', 1, 3, 8),

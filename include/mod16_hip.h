@@ -1793,6 +1793,72 @@ MOD16_API int mod16_et_composite_downscaled_f32(mod16_ctx* ctx, const mod16_down
                                                 int64_t out_pitch, unsigned flags, int where, void* stream,
                                                 int64_t stage_bytes);
 
+/*
+ * Whittaker smoothing of 8-day series, weighted by QC (added under ABI 16, new symbols only;
+ * mod16_amd.smooth_series, RasterEngine.smooth): the step behind -- or instead of -- mod16_gapfill_u8.
+ * One launch smooths the profile of every pixel. The definition is the numpy statement
+ * mod16_amd/smooth.py (weights_of, penalty_bands, factor, solve, encode):
+ *
+ *   inputs      values[t * in_pitch + i], slab t (0 ... slabs - 1, slabs 1 ... mod16_smooth_max_slabs()
+ *               = 4096), pixel i: uint8 codes (missing where >= 249), float32 or float64 (missing where
+ *               not finite). weight_mode MOD16_SMOOTH_WEIGHT_NONE: w = 1, `weights` is NULL;
+ *               _STACK: `weights` is float32 [t * weight_pitch + i], the slab is missing unless w is
+ *               finite and > 0; _QC: `weights` is a uint8 QC layer of that layout and w =
+ *               qc_weight256[qc] (256 float64, finite and >= 0; NULL: 1.0 for the codes mod16_gapfill_u8
+ *               accepts by default, else 0.0), the slab is missing where that is 0. A missing slab has
+ *               w = 0 and y = 0. count = the slabs with w > 0.
+ *   result      per pixel, in float64 and without contraction, with a0, a1, a2 the diagonals of D'D (D:
+ *               the difference matrix of `order` 1 or 2; all zero where slabs <= order), terms with an
+ *               index below 0 being 0.0:
+ *                 d[i] = ((w[i] + lam*a0[i]) - (c[i-1]*c[i-1])*d[i-1]) - (e[i-2]*e[i-2])*d[i-2]
+ *                 c[i] = (lam*a1[i] - (d[i-1]*c[i-1])*e[i-1]) / d[i]
+ *                 e[i] = (lam*a2[i]) / d[i]
+ *                 f[i] = (w[i]*y[i] - c[i-1]*f[i-1]) - e[i-2]*f[i-2]             i ascending
+ *                 z[i] = (f[i]/d[i] - c[i]*z[i+1]) - e[i]*z[i+2]                 i descending
+ *               then `envelope` (0 ... 8) times: y[t] = z[t] where w[t] > 0 and z[t] > y[t], and f, z
+ *               again with the same d, c, e.
+ *   outputs     out[t * out_pitch + i] of out_type: MOD16_SMOOTH_F32 / _F64 (T)(z * scale),
+ *               MOD16_SMOOTH_U8 clip(floor(z + 0.5), 0, 248); a pixel with count < min_valid (min_valid >=
+ *               order) is unsmoothed: NaN, or 255, in every slab. mod16_smooth_u8 takes any out_type (scale
+ *               is looked at for its float outputs only), mod16_smooth_f32 / _f64 their own. Optional
+ *               count[i], uint16. Every element [t][0, n) is written exactly once; [t][n, pitch) is not
+ *               touched. Pointers may have any alignment of their type and the pitches any value >= n
+ *               (in elements). No atomics: two calls give the same bits.
+ *   workspace   the columns c, e, f/d (then z) and, with an envelope, y and d of the pixels in flight live
+ *               in one block of device memory the context owns (at most 256 MiB, allocated on first use,
+ *               kept); launches of one context on several streams are ordered one behind the other.
+ *   where       MOD16_DEVICE: device pointers (qc_weight256 too), asynchronous on `stream`. MOD16_HOST:
+ *               host pointers; pixel tiles are staged through the context's slabs as for
+ *               mod16_gapfill_u8 (stage_bytes as there). The result does not depend on stage_bytes.
+ *   refused (MOD16_ERR_ARG, before any device work and before an output is touched; "mod16_smooth: ...")
+ *               NULL spec, values or out; n < 0; "slabs must be between 1 and 4096"; "order must be 1 or
+ *               2"; "envelope must be between 0 and 8"; "min_valid must be at least the order"; "lam must
+ *               be finite and > 0"; an unknown out_type or one the entry point does not give; an unknown
+ *               weight_mode; weights given without a mode or a mode without weights; qc_weight256
+ *               without MOD16_SMOOTH_WEIGHT_QC, or (HOST) with an entry that is not finite or negative; a
+ *               scale that is not finite; a pitch below n; `where` other than the two modes; "an output
+ *               overlaps an input or another output". n = 0 is MOD16_OK.
+ */
+enum mod16_smooth_out { MOD16_SMOOTH_U8 = 0, MOD16_SMOOTH_F32 = 1, MOD16_SMOOTH_F64 = 2 };
+enum mod16_smooth_weight { MOD16_SMOOTH_WEIGHT_NONE = 0, MOD16_SMOOTH_WEIGHT_STACK = 1, MOD16_SMOOTH_WEIGHT_QC = 2 };
+typedef struct mod16_smooth_spec {
+    int64_t n;                                   /* pixels */
+    int32_t slabs, order, envelope, min_valid;
+    int32_t weight_mode, out_type;               /* enum mod16_smooth_weight, enum mod16_smooth_out */
+    double lam, scale;                           /* scale: float outputs of uint8 values only */
+    int64_t in_pitch, weight_pitch, out_pitch;   /* elements between two slabs */
+} mod16_smooth_spec;
+MOD16_API int mod16_smooth_u8(mod16_ctx* ctx, const mod16_smooth_spec* spec, const uint8_t* values, const void* weights,
+                              const double* qc_weight256, void* out, uint16_t* count, int where, void* stream,
+                              size_t stage_bytes);
+MOD16_API int mod16_smooth_f32(mod16_ctx* ctx, const mod16_smooth_spec* spec, const float* values, const void* weights,
+                               const double* qc_weight256, void* out, uint16_t* count, int where, void* stream,
+                               size_t stage_bytes);
+MOD16_API int mod16_smooth_f64(mod16_ctx* ctx, const mod16_smooth_spec* spec, const double* values, const void* weights,
+                               const double* qc_weight256, void* out, uint16_t* count, int where, void* stream,
+                               size_t stage_bytes);
+MOD16_API int mod16_smooth_max_slabs(void);
+
 #ifdef __cplusplus
 }
 #endif

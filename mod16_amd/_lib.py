@@ -115,6 +115,21 @@ class GapfillSpec(C.Structure):
 GAPFILL_U8, GAPFILL_F32, GAPFILL_F64 = 0, 1, 2     # enum mod16_gapfill_out
 
 
+class SmoothSpec(C.Structure):
+    '''``mod16_smooth_spec`` (include/mod16_hip.h): the pixels and slabs of a smoothing call, the order
+    of the penalty, the envelope rounds, the fewest weighted slabs a pixel is smoothed from, the weight
+    mode and output type, ``lam``, the scale and the pitches.'''
+    _fields_ = [('n', C.c_int64), ('slabs', C.c_int32), ('order', C.c_int32), ('envelope', C.c_int32),
+                ('min_valid', C.c_int32), ('weight_mode', C.c_int32), ('out_type', C.c_int32),
+                ('lam', C.c_double), ('scale', C.c_double), ('in_pitch', C.c_int64),
+                ('weight_pitch', C.c_int64), ('out_pitch', C.c_int64)]
+
+
+SMOOTH_U8, SMOOTH_F32, SMOOTH_F64 = 0, 1, 2                         # enum mod16_smooth_out
+SMOOTH_WEIGHT_NONE, SMOOTH_WEIGHT_STACK, SMOOTH_WEIGHT_QC = 0, 1, 2    # enum mod16_smooth_weight
+_SMOOTH_ARGS = [C.c_void_p, C.POINTER(SmoothSpec)] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_size_t]
+
+
 class DaynightSpec(C.Structure):
     '''``mod16_daynight_spec`` (include/mod16_hip.h): the grid, days and steps per day, the mode and its
     threshold, the output type, and the row pitch and plane stride of the fields and of the outputs.'''
@@ -454,6 +469,10 @@ PROTOTYPES = {
     'mod16_upscale_create_rows': (C.c_int, [C.c_void_p, C.POINTER(UpscaleSpec)] + [C.c_void_p] * 7 + [C.POINTER(C.c_void_p)]),
     'mod16_upscale_sums_f64': (C.c_int, _UPSCALE_SUMS_ARGS),
     'mod16_upscale_sums_f32': (C.c_int, _UPSCALE_SUMS_ARGS),
+    'mod16_smooth_u8': (C.c_int, _SMOOTH_ARGS),
+    'mod16_smooth_f32': (C.c_int, _SMOOTH_ARGS),
+    'mod16_smooth_f64': (C.c_int, _SMOOTH_ARGS),
+    'mod16_smooth_max_slabs': (C.c_int, []),
 }
 
 _lib = None
@@ -691,6 +710,22 @@ class Context:
             self.handle, C.byref(spec), ptr_array(list(fields)), qc, good,
             ptr_array(list(fallback)) if fallback is not None else None, ptr_array(list(out)), source,
             int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
+
+    def smooth(self, in_dtype, out_type, n, slabs, values, weights, qc_weight, out, count, in_pitch, weight_pitch,
+               out_pitch, lam, order=2, envelope=0, min_valid=3, weight_mode=SMOOTH_WEIGHT_NONE, scale=1.0,
+               where=HOST, stream=None, stage_bytes=None):
+        '''Thin wrapper of mod16_smooth_u8 / _f32 / _f64 (``in_dtype``: the type of ``values``).
+        ``values`` and ``out`` are raw addresses; ``weights`` (a float32 stack or a uint8 QC layer, as
+        ``weight_mode`` says), ``qc_weight`` (256 float64) and ``count`` (uint16) are raw addresses or
+        None; pitches in elements; ``stage_bytes`` None: the library's default.'''
+        spec = SmoothSpec()
+        spec.n, spec.slabs, spec.order, spec.envelope = int(n), int(slabs), int(order), int(envelope)
+        spec.min_valid, spec.weight_mode, spec.out_type = int(min_valid), int(weight_mode), int(out_type)
+        spec.lam, spec.scale = float(lam), float(scale)
+        spec.in_pitch, spec.weight_pitch, spec.out_pitch = int(in_pitch), int(weight_pitch), int(out_pitch)
+        fn = getattr(self.lib, 'mod16_smooth_' + {'uint8': 'u8', 'float32': 'f32', 'float64': 'f64'}[np.dtype(in_dtype).name])
+        self.check(fn(self.handle, C.byref(spec), values, weights, qc_weight, out, count, int(where), stream,
+                      0 if stage_bytes is None else int(stage_bytes)))
 
     def daynight(self, dtype, out_type, rows, cols, days, steps_per_day, fields, tables, out, temp_annual, in_pitch,
                  in_plane, out_pitch, out_plane, mode=DAYNIGHT_SOLAR, threshold=0.0, where=HOST, stream=None,

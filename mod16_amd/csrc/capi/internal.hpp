@@ -105,6 +105,8 @@ struct mod16_ctx {
     unsigned long long* force_counter = nullptr;   // ticket counter to use instead of the ring (graph capture); a view
     DevMem bc_buf;                   // HOST mode: device copies of (N,) / (T, 1) inputs (mod16_et2_*); only grows
     DevMem batch_buf;                // HOST-mode workspace of mod16_et_static_batch_*; only grows
+    DevMem smooth_ws;                // mod16_smooth_*: 2 KiB for a HOST-mode weight table, then the columns of the pixels
+                                     // in flight; only grows (the outgrown block is retired), launches ordered by ws_event
     std::string err;
     Stream streams[kSlots];          // one per staging slot, made on first use; [0] also serves the other HOST-mode calls
 };

@@ -1,10 +1,10 @@
 '''
 The extension entry points of the numpy surface -- what the reference package does not have: the
 ensemble forward run and its quantiles, multi-day composites, the downscaled forward run, gap
-filling of the 8-day series, zonal statistics and the forward run on raw drivers. numpy in, numpy
-out, as ``evapotranspiration_raster``; ``mod16_amd`` re-exports every name here. The definitions
-they are checked against live in ``mod16_amd.composite``, ``.downscale``, ``.gapfill``, ``.zonal``
-and ``.calibration``; the argument rules they share with the package root in ``mod16_amd._args``.
+filling and smoothing of the 8-day series, zonal statistics and the forward run on raw drivers. numpy
+in, numpy out, as ``evapotranspiration_raster``; ``mod16_amd`` re-exports every name here. The
+definitions they are checked against live in ``mod16_amd.composite``, ``.downscale``, ``.gapfill``,
+``.smooth``, ``.zonal`` and ``.calibration``; the argument rules they share with the package root in ``mod16_amd._args``.
 '''
 import collections as _collections
 
@@ -511,6 +511,92 @@ def gapfill_series(fields, qc=None, good=None, max_gap=None, fallback=None, dtyp
         return filled
     srcs = [src[f].reshape(full) for f in range(len(flds))]
     return filled, (srcs[0] if single else tuple(srcs))
+
+
+def smooth_series(values, weights=None, qc=None, qc_weight=None, lam=None, order=2, envelope=0, min_valid=3,
+                  dtype=None, scale=None, count=False, out=None, device=0, stage_bytes=None):
+    r'''
+    (Extension.) Whittaker smoothing of an 8-day series (MOD15A2H fPAR / LAI codes, or float values),
+    weighted by QC, in one kernel launch per staged tile (``mod16_smooth_*``): per pixel the solution
+    ``z`` of ``(W + lam D'D) z = W y`` by a banded factorisation, then ``envelope`` passes that lift the
+    fit towards the upper envelope of the weighted values. A slab with zero weight is interpolated by
+    the smoother itself, so this step can follow ``gapfill_series`` or take its place. The definition
+    is ``mod16_amd.smooth`` (``weights_of``, ``factor``, ``solve``, ``encode``); the result has its bits.
+
+    Parameters
+    ----------
+    values : numpy.ndarray
+        ``(S,) + pixel shape`` with ``1 <= S <= 4096``: uint8 codes (>= 249 are fill values), float32
+        or float64 (not finite: missing)
+    weights : numpy.ndarray
+        (Optional) float32 weights of the same shape; a slab counts where its weight is finite and > 0
+    qc : numpy.ndarray
+        (Optional, instead of ``weights``) uint8 QC layer of the same shape
+    qc_weight : sequence of 256 numbers
+        (Optional) the weight of every QC byte, finite and >= 0 (Default: 1 where
+        ``mod16_amd.gapfill.default_good()`` holds, else 0; ``mod16_amd.smooth`` shows a graded table)
+    lam : float
+        the smoothing parameter, finite and > 0
+    order : int
+        1 or 2, the order of the differences that are penalised (Default: 2)
+    envelope : int
+        0 ... 8 upper-envelope passes (Default: 0)
+    min_valid : int
+        a pixel with fewer weighted slabs is left unsmoothed: NaN, or 255, in every slab (Default: 3;
+        at least ``order``)
+    dtype : str
+        (uint8 values only) ``'uint8'`` (Default: codes, rounded half up and clipped to 0 ... 248),
+        ``'float32'`` or ``'float64'`` (``z * scale``); float values return their own type
+    scale : float
+        (Optional) uint8 values with float output only, e.g. 0.01 for fPAR
+    count : bool
+        True to return a pair ``(smoothed, count)``, ``count`` being the uint16 number of weighted
+        slabs of every pixel
+    out : numpy.ndarray or sequence
+        (Optional) the result arrays, C-contiguous: the smoothed array, and with ``count`` the counts
+    stage_bytes : int
+        (Optional) device memory a staging slot may take; the result does not depend on it
+
+    Returns
+    -------
+    numpy.ndarray or tuple
+    '''
+    from . import smooth as _s
+    values = np.asarray(values)
+    weights = None if weights is None else np.asarray(weights)
+    qc = None if qc is None else np.asarray(qc)
+    S, shape, mode, table, lam, order, envelope, min_valid, name, scale = _s.check_call(
+        values.shape, values.dtype, None if weights is None else weights.shape, None if qc is None else qc.shape,
+        qc_weight, lam, order, envelope, min_valid, dtype, scale)
+    if weights is not None and weights.dtype != np.float32:
+        raise ValueError('weights must be float32, got %s' % weights.dtype)
+    if qc is not None and qc.dtype != np.uint8:
+        raise ValueError('qc must be uint8, got %s' % qc.dtype)
+    _check_stage_bytes(stage_bytes)
+    full = (S,) + tuple(shape)
+    if out is not None:
+        out = [out] if isinstance(out, np.ndarray) else list(out)
+        if len(out) != (2 if count else 1):
+            raise ValueError('out must hold %d arrays' % (2 if count else 1))
+    smoothed, = _outputs(None if out is None else out[:1], full, [np.dtype(name)], pinned=False, indexed=True)
+    cnt = None
+    if count:
+        cnt = np.empty(tuple(shape), _U16) if out is None else out[1]
+        if not (isinstance(cnt, np.ndarray) and cnt.shape == tuple(shape) and cnt.dtype == _U16
+                and cnt.flags.c_contiguous and cnt.flags.writeable):
+            raise ValueError('out[1] must be a writeable C-contiguous uint16 array of shape %s' % (tuple(shape),))
+    n = int(np.prod(shape, dtype=np.int64))
+    if n:
+        values = np.ascontiguousarray(values).reshape(S, n)
+        stack = weights if mode == _s.WEIGHT_STACK else qc if mode == _s.WEIGHT_QC else None
+        stack = None if stack is None else np.ascontiguousarray(stack).reshape(S, n)
+        table = None if (table is None or qc_weight is None) else np.ascontiguousarray(table, np.float64)
+        _lib.context(device).smooth(
+            values.dtype, _s.OUT_TYPES[name], n, S, values.ctypes.data, None if stack is None else stack.ctypes.data,
+            None if table is None else table.ctypes.data, smoothed.ctypes.data, None if cnt is None else cnt.ctypes.data,
+            n, n, n, lam, order=order, envelope=envelope, min_valid=min_valid, weight_mode=mode, scale=scale,
+            where=_lib.HOST, stage_bytes=stage_bytes)
+    return (smoothed, cnt) if count else smoothed
 
 
 def aggregate_daynight(fields, half_day=None, noon=None, offset=None, sw_threshold=None, steps_per_day=24,

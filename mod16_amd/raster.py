@@ -995,6 +995,75 @@ class RasterEngine(object):
             return filled
         return filled, (src[0] if single else tuple(src[f] for f in range(len(flds))))
 
+    def smooth(self, values, weights=None, qc=None, qc_weight=None, lam=None, order=2, envelope=0, min_valid=3,
+               dtype=None, scale=None, count=False, out=None):
+        '''Enqueue the Whittaker smoother on the current stream: the profile of every pixel of one
+        device-resident series smoothed in one launch (``mod16_smooth_*``; the definition is
+        ``mod16_amd.smooth``, whose bits the result has) -- per pixel the banded solve of ``(W + lam
+        D'D) z = W y`` and ``envelope`` passes towards the upper envelope of the weighted values.
+
+        ``values`` is an ``(S, n)`` uint8, float32 or float64 tensor; ``weights`` an optional float32
+        one or ``qc`` an optional uint8 one, each with unit stride in pixels and any stride >= n in
+        time (views of a larger buffer are fine, at any element offset); ``qc_weight`` a 256-entry
+        table of weights per QC byte (default: 1 for the codes ``gapfill`` accepts, else 0). ``dtype``:
+        for uint8 values ``'uint8'`` (default: codes, 255 where unsmoothed -- a row goes into
+        ``run_raw``), ``'float32'`` / ``'float64'`` or ``'engine'`` (the engine's type; ``scale``
+        applies); float values return their own type. The other arguments are those of
+        ``mod16_amd.smooth_series``.
+
+        Returns the smoothed tensor, and with ``count`` a pair ``(smoothed, count)``, ``count`` being
+        the ``(n,)`` uint16 number of weighted slabs. ``out`` may give the tensors; no output may
+        overlap an input. Asynchronous, like ``gapfill``.'''
+        from . import smooth as _s
+        torch = _torch()
+        _t.check_device(values, 'values', self.device, torch.uint8, torch.float32, torch.float64)
+        if weights is not None:
+            _t.check_device(weights, 'weights', self.device, torch.float32)
+        if qc is not None:
+            _t.check_device(qc, 'qc', self.device, torch.uint8)
+        if dtype == 'engine':
+            dtype = self.np_dtype.name
+        S, shape, mode, table, lam, order, envelope, min_valid, name, scale = _s.check_call(
+            tuple(values.shape), _t.numpy_dtype(values.dtype), None if weights is None else tuple(weights.shape),
+            None if qc is None else tuple(qc.shape), qc_weight, lam, order, envelope, min_valid, dtype, scale)
+        if len(shape) != 1:
+            raise ValueError('values must be an (S, n) tensor, got %r' % (tuple(values.shape),))
+        n = shape[0]
+        in_pitch = _t.row_pitch(values, 'values', 'stride in time')
+        stack = weights if weights is not None else qc
+        w_pitch = n if stack is None else _t.row_pitch(stack, 'weights' if weights is not None else 'qc', 'stride in time')
+        if out is not None:
+            out = [out] if isinstance(out, torch.Tensor) else list(out)
+            if len(out) != (2 if count else 1):
+                raise ValueError('out must hold %d tensors' % (2 if count else 1))
+        outs, rows = _t.named_outputs(None if out is None else out[:1], {0: ((S, n), np.dtype(name))}, self.device,
+                                      'stride in time')
+        smoothed, out_pitch = outs[0], rows[0]
+        cnt = None
+        if count:
+            if out is None:
+                cnt = torch.empty((n,), dtype=torch.uint16, device=self._dev())
+            else:
+                cnt = out[1]
+                _t.check_device(cnt, 'out[1]', self.device, torch.uint16)
+                if tuple(cnt.shape) != (n,):
+                    raise ValueError('out[1] must have shape %r, got %r' % ((n,), tuple(cnt.shape)))
+                _t.row_pitch(cnt, 'out[1]')
+        if n:
+            table64 = None
+            if qc_weight is not None:       # (the default table is the library's own)
+                table64 = torch.from_numpy(np.ascontiguousarray(table, np.float64)).to(self._dev())
+            try:
+                self.ctx.smooth(
+                    _t.numpy_dtype(values.dtype), _s.OUT_TYPES[name], n, S, values.data_ptr(),
+                    None if stack is None else stack.data_ptr(), None if table64 is None else table64.data_ptr(),
+                    smoothed.data_ptr(), None if cnt is None else cnt.data_ptr(), in_pitch, w_pitch, out_pitch, lam,
+                    order=order, envelope=envelope, min_valid=min_valid, weight_mode=mode, scale=scale,
+                    where=_lib.DEVICE, stream=self._stream())
+            except _lib.Mod16Error as e:
+                raise _lib.overlap_as_value_error(e)
+        return (smoothed, cnt) if count else smoothed
+
     def daynight(self, fields, half_day=None, noon=None, offset=None, sw_threshold=None, steps_per_day=24,
                  outputs=None, dtype=None, out=None):
         '''Enqueue the day / night aggregation on the current stream: hourly reanalysis fields in, the

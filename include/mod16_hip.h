@@ -1859,6 +1859,72 @@ MOD16_API int mod16_smooth_f64(mod16_ctx* ctx, const mod16_smooth_spec* spec, co
                                size_t stage_bytes);
 MOD16_API int mod16_smooth_max_slabs(void);
 
+/*
+ * Per-pixel weighted least squares over a stack, with shared and per-pixel terms (added under ABI 16, new
+ * symbols only; mod16_amd.regress_series, RasterEngine.regress): y = X b fitted for every pixel in one
+ * launch -- a harmonic model plus trend over a long 8-day record, an OLS trend, ET regressed on
+ * precipitation, net radiation and VPD stacks. The definition is the numpy statement
+ * mod16_amd/regress.py (accumulate, factor, solve, residual_sums, inverse_diagonal):
+ *
+ *   inputs      values[i * value_pitch + p], step i (0 ... steps - 1, steps 1 ... mod16_regress_max_steps()
+ *               = 4096), pixel p, float32 or float64 (widened to float64; missing where not finite).
+ *               The predictors of a sample are x[0 .. P - 1], P = ks + kp between 1 and
+ *               mod16_regress_max_terms() = 8: first the ks columns design[i * ks + a] (float64, the same
+ *               for every pixel, finite), then the kp per-pixel stacks terms[k][i * term_pitch + p] of the
+ *               values' type. weights: NULL (w = 1) or float32 [i * weight_pitch + p]. A sample is valid
+ *               where y and every per-pixel term are finite and the weight is finite and > 0; count = the
+ *               valid samples.
+ *   result      per pixel, in float64 and without contraction, the valid samples in ascending i:
+ *                 wx[a] = w * x[a];  h[a] += wx[a] * y;  G[a][b] += wx[a] * x[b] (b >= a);  Sw += w;  Sy += w * y
+ *               G = L diag(d) L' without pivoting, column by column (k = 0 .. j - 1):
+ *                 d[j]    = (G[j][j] - (L[j][0] * L[j][0]) * d[0]) - ...
+ *                 L[i][j] = ((G[j][i] - (L[i][0] * L[j][0]) * d[0]) - ...) / d[j]
+ *               the pixel is degenerate if a test d[j] > 2^-40 * G[j][j] fails (a NaN fails it);
+ *                 z[i] = (h[i] - L[i][0] * z[0]) - ...;  c[i] = z[i] / d[i];  b[i] = (c[i] - L[i+1][i] * b[i+1]) - ...
+ *               and over the samples again: f = (x[0] * b[0] + x[1] * b[1]) + ..., r = y - f,
+ *                 rss += w * (r * r);  tss += w * ((y - Sy / Sw) * (y - Sy / Sw))
+ *               r2 = 1 - rss / tss, sigma2 = rss / (count - P), se[j] = sqrt(sigma2 * inv[j]) with inv the
+ *               diagonal of the inverse of L diag(d) L' (regress.py: inverse_diagonal). Nothing is
+ *               special-cased: count == P gives what 0 / 0 or x / 0 gives.
+ *   outputs     coef[j * coef_pitch + p]; optional se[j * se_pitch + p], rss[p], tss[p], r2[p] (float64),
+ *               count[p] (uint16) and series[i * series_pitch + p] in the values' type:
+ *               MOD16_REGRESS_SERIES_RESIDUALS r, NaN where the sample is not valid; _FITTED f wherever every
+ *               per-pixel term of the step is finite (with ks = P: every step). Where count < min_valid
+ *               (min_valid >= P) or the pixel is degenerate every float output is NaN; count is kept.
+ *               Every element [.][0, n) is written exactly once; [.][n, pitch) is not touched. Pointers may
+ *               have any alignment of their type and the pitches any value >= n (in elements). No atomics:
+ *               two calls give the same bits.
+ *   where       MOD16_DEVICE: device pointers (design too; `terms` itself is a host array of kp device
+ *               pointers), asynchronous on `stream`. MOD16_HOST: host pointers; pixel tiles are staged
+ *               through the context's slabs as for mod16_smooth_*, the design is uploaded whole to memory
+ *               the context owns (stage_bytes as there). The result does not depend on stage_bytes.
+ *   refused (MOD16_ERR_ARG, before any device work and before an output is touched; "mod16_regress: ...")
+ *               NULL spec, values or coef; n < 0; "steps must be between 1 and 4096"; ks or kp negative or
+ *               ks + kp outside 1 ... 8; design given without ks or ks without design, likewise terms and
+ *               kp; a NULL term; "min_valid must be at least ks + kp"; an unknown series mode, or a series
+ *               output without a mode or a mode without the output; a pitch below n; (HOST) "design must be
+ *               finite"; `where` other than the two modes; "an output overlaps an input or another
+ *               output". n = 0 is MOD16_OK.
+ */
+enum mod16_regress_series { MOD16_REGRESS_SERIES_NONE = 0, MOD16_REGRESS_SERIES_RESIDUALS = 1, MOD16_REGRESS_SERIES_FITTED = 2 };
+typedef struct mod16_regress_spec {
+    int64_t n;                                   /* pixels */
+    int32_t steps, ks, kp, min_valid;
+    int32_t series, flags;                       /* enum mod16_regress_series; flags: 0 */
+    int64_t value_pitch, term_pitch, weight_pitch;   /* elements between two steps */
+    int64_t coef_pitch, se_pitch, series_pitch;      /* elements between two coefficients, two steps */
+} mod16_regress_spec;
+MOD16_API int mod16_regress_f32(mod16_ctx* ctx, const mod16_regress_spec* spec, const float* values, const double* design,
+                                const float* const* terms, const float* weights, double* coef, double* se, double* rss,
+                                double* tss, double* r2, uint16_t* count, float* series, int where, void* stream,
+                                size_t stage_bytes);
+MOD16_API int mod16_regress_f64(mod16_ctx* ctx, const mod16_regress_spec* spec, const double* values, const double* design,
+                                const double* const* terms, const float* weights, double* coef, double* se, double* rss,
+                                double* tss, double* r2, uint16_t* count, double* series, int where, void* stream,
+                                size_t stage_bytes);
+MOD16_API int mod16_regress_max_steps(void);
+MOD16_API int mod16_regress_max_terms(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ from mod16_amd import (          # noqa: F401  (names a star import leaves out o
     TEMP_LAPSE_RATE, GRAV_ACCEL, GAS_LAW_CONST, AIR_MOL_WEIGHT, STD_TEMP_K, STD_PRESSURE_PASCALS,
     AIR_PRESSURE_RATE, latent_heat_vaporization, psychrometric_constant, radiation_net, svp,
     svp_slope, evapotranspiration_raster, evapotranspiration_raw, evapotranspiration_composite, gapfill_series,
-    smooth_series, aggregate_daynight, trend_series, anomaly_series, upscale_fields, upscale_classes, upscale_sums,
+    smooth_series, regress_series, aggregate_daynight, trend_series, anomaly_series, upscale_fields, upscale_classes, upscale_sums,
     evapotranspiration_downscaled, evapotranspiration_composite_downscaled, downscale, zonal_statistics, zonal, zonal_histogram,
     zonal_quantiles, zonalq, pinned_empty,
     __version__)

@@ -41,7 +41,7 @@ from ._args import (_F32, _F64, _address, _as_uint8, _broadcast, _broadcast_kind
 from .extensions import (
     CompositeET, CompositeETPET, EnsembleET, EnsembleQuantiles, _ensemble_stack, aggregate_daynight, anomaly_series, evapotranspiration_composite,
     evapotranspiration_composite_downscaled, evapotranspiration_downscaled, evapotranspiration_ensemble, evapotranspiration_ensemble_quantiles,
-    evapotranspiration_raw, gapfill_series, smooth_series, trend_series, upscale_classes, upscale_fields, upscale_sums, zonal_histogram, zonal_quantiles, zonal_statistics)
+    evapotranspiration_raw, gapfill_series, regress_series, smooth_series, trend_series, upscale_classes, upscale_fields, upscale_sums, zonal_histogram, zonal_quantiles, zonal_statistics)
 
 # Module constants, same names and values as reference mod16/__init__.py:106-118
 PFT_VALID = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12)

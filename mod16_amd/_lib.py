@@ -130,6 +130,20 @@ SMOOTH_WEIGHT_NONE, SMOOTH_WEIGHT_STACK, SMOOTH_WEIGHT_QC = 0, 1, 2    # enum mo
 _SMOOTH_ARGS = [C.c_void_p, C.POINTER(SmoothSpec)] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_size_t]
 
 
+class RegressSpec(C.Structure):
+    '''``mod16_regress_spec`` (include/mod16_hip.h): the pixels and steps of a regression call, the shared
+    and the per-pixel terms, the fewest valid samples a pixel is fitted from, the series mode and the
+    pitches.'''
+    _fields_ = [('n', C.c_int64), ('steps', C.c_int32), ('ks', C.c_int32), ('kp', C.c_int32),
+                ('min_valid', C.c_int32), ('series', C.c_int32), ('flags', C.c_int32),
+                ('value_pitch', C.c_int64), ('term_pitch', C.c_int64), ('weight_pitch', C.c_int64),
+                ('coef_pitch', C.c_int64), ('se_pitch', C.c_int64), ('series_pitch', C.c_int64)]
+
+
+REGRESS_SERIES_NONE, REGRESS_SERIES_RESIDUALS, REGRESS_SERIES_FITTED = 0, 1, 2     # enum mod16_regress_series
+_REGRESS_ARGS = [C.c_void_p, C.POINTER(RegressSpec)] + [C.c_void_p] * 11 + [C.c_int, C.c_void_p, C.c_size_t]
+
+
 class DaynightSpec(C.Structure):
     '''``mod16_daynight_spec`` (include/mod16_hip.h): the grid, days and steps per day, the mode and its
     threshold, the output type, and the row pitch and plane stride of the fields and of the outputs.'''
@@ -473,6 +487,10 @@ PROTOTYPES = {
     'mod16_smooth_f32': (C.c_int, _SMOOTH_ARGS),
     'mod16_smooth_f64': (C.c_int, _SMOOTH_ARGS),
     'mod16_smooth_max_slabs': (C.c_int, []),
+    'mod16_regress_f32': (C.c_int, _REGRESS_ARGS),
+    'mod16_regress_f64': (C.c_int, _REGRESS_ARGS),
+    'mod16_regress_max_steps': (C.c_int, []),
+    'mod16_regress_max_terms': (C.c_int, []),
 }
 
 _lib = None
@@ -726,6 +744,27 @@ class Context:
         fn = getattr(self.lib, 'mod16_smooth_' + {'uint8': 'u8', 'float32': 'f32', 'float64': 'f64'}[np.dtype(in_dtype).name])
         self.check(fn(self.handle, C.byref(spec), values, weights, qc_weight, out, count, int(where), stream,
                       0 if stage_bytes is None else int(stage_bytes)))
+
+    def regress(self, dtype, n, steps, values, design, ks, terms, weights, coef, se, rss, tss, r2, count, series,
+                value_pitch=None, term_pitch=None, weight_pitch=None, coef_pitch=None, se_pitch=None,
+                series_pitch=None, min_valid=None, series_mode=REGRESS_SERIES_NONE, where=HOST, stream=None,
+                stage_bytes=None):
+        '''Thin wrapper of mod16_regress_f32 / _f64 (``dtype``: the type of ``values``, of the terms and
+        of ``series``). ``values`` and ``coef`` are raw addresses; ``design`` (``steps x ks`` float64),
+        ``weights`` (float32), ``se``, ``rss``, ``tss``, ``r2``, ``count`` (uint16) and ``series`` raw
+        addresses or None; ``terms`` a sequence of raw addresses; pitches in elements (None: ``n``);
+        ``min_valid`` None: ``ks + len(terms) + 1``; ``stage_bytes`` None: the library's default.'''
+        terms = list(terms)
+        spec = RegressSpec()
+        spec.n, spec.steps, spec.ks, spec.kp = int(n), int(steps), int(ks), len(terms)
+        spec.min_valid = int(ks) + len(terms) + 1 if min_valid is None else int(min_valid)
+        spec.series, spec.flags = int(series_mode), 0
+        for name, pitch in (('value_pitch', value_pitch), ('term_pitch', term_pitch), ('weight_pitch', weight_pitch),
+                            ('coef_pitch', coef_pitch), ('se_pitch', se_pitch), ('series_pitch', series_pitch)):
+            setattr(spec, name, int(n if pitch is None else pitch))
+        fn = typed(self.lib, 'mod16_regress', dtype)
+        self.check(fn(self.handle, C.byref(spec), values, design, ptr_array(terms) if terms else None, weights, coef, se,
+                      rss, tss, r2, count, series, int(where), stream, 0 if stage_bytes is None else int(stage_bytes)))
 
     def daynight(self, dtype, out_type, rows, cols, days, steps_per_day, fields, tables, out, temp_annual, in_pitch,
                  in_plane, out_pitch, out_plane, mode=DAYNIGHT_SOLAR, threshold=0.0, where=HOST, stream=None,

@@ -107,6 +107,7 @@ struct mod16_ctx {
     DevMem batch_buf;                // HOST-mode workspace of mod16_et_static_batch_*; only grows
     DevMem smooth_ws;                // mod16_smooth_*: 2 KiB for a HOST-mode weight table, then the columns of the pixels
                                      // in flight; only grows (the outgrown block is retired), launches ordered by ws_event
+    DevMem regress_design;           // mod16_regress_*: a HOST-mode call's design on the device; only grows (the outgrown block is retired)
     std::string err;
     Stream streams[kSlots];          // one per staging slot, made on first use; [0] also serves the other HOST-mode calls
 };

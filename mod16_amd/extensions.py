@@ -599,6 +599,82 @@ def smooth_series(values, weights=None, qc=None, qc_weight=None, lam=None, order
     return (smoothed, cnt) if count else smoothed
 
 
+def regress_series(values, design=None, terms=(), weights=None, min_valid=None, stderr=False, series=None, out=None,
+                   device=0, stage_bytes=None):
+    r'''
+    (Extension.) Per-pixel weighted least squares ``y = X b`` over a stack, in one kernel launch per
+    staged tile (``mod16_regress_*``): a harmonic (seasonal) model plus trend over a long 8-day record,
+    an OLS trend on more steps than ``trend_series`` takes, or ET regressed per pixel on precipitation,
+    net radiation and VPD stacks. Missing values are left out sample by sample. The definition is
+    ``mod16_amd.regress`` (``regress``); the result has its bits.
+
+    Parameters
+    ----------
+    values : numpy.ndarray
+        ``(T,) + pixel shape`` with ``1 <= T <= 4096``, float32 or float64; a value that is not finite
+        is missing
+    design : numpy.ndarray
+        (Optional) ``(T, Ks)`` float64, finite: the columns every pixel shares (intercept, time,
+        harmonics; ``mod16_amd.regress.harmonic_design`` builds one)
+    terms : sequence of numpy.ndarray
+        (Optional) ``Kp`` per-pixel predictors of ``values``' shape and dtype; ``1 <= Ks + Kp <= 8``, the
+        coefficients come in the order design columns, then terms
+    weights : numpy.ndarray
+        (Optional) float32 weights of ``values``' shape; a sample counts where its weight is finite
+        and > 0
+    min_valid : int
+        (Optional) a pixel with fewer valid samples is left empty: NaN in every float output (Default:
+        ``Ks + Kp + 1``; at least ``Ks + Kp``)
+    stderr : bool
+        True for the standard errors of the coefficients
+    series : str
+        (Optional) ``'residuals'`` (NaN where the sample is not valid) or ``'fitted'`` (wherever every
+        per-pixel term is finite: with a shared-only design the model-based fill of every slab)
+    out : dict
+        (Optional) the result arrays by name, C-contiguous: exactly the fields produced
+    stage_bytes : int
+        (Optional) device memory a staging slot may take; the result does not depend on it
+
+    Returns
+    -------
+    mod16_amd.regress.Regression
+        ``(coef, stderr, rss, tss, r2, count, series)``: ``coef`` and ``stderr`` ``(Ks + Kp,) + pixel
+        shape``, ``rss``, ``tss``, ``r2`` of the pixel shape, float64; ``count`` uint16 (the valid
+        samples); ``series`` ``(T,) + pixel shape`` in the dtype of ``values``; ``stderr`` and
+        ``series`` are None where they are not asked for
+    '''
+    from . import regress as _r
+    values = np.asarray(values)
+    terms = [np.asarray(t) for t in terms]
+    weights = None if weights is None else np.asarray(weights)
+    T, shape, Ks, Kp, min_valid, stderr, code = _r.check_call(
+        values.shape, values.dtype, None if design is None else np.shape(design), [t.shape for t in terms],
+        [t.dtype for t in terms], None if weights is None else weights.shape, min_valid, stderr, series)
+    design = _r.check_design(design, T)
+    if weights is not None and weights.dtype != np.float32:
+        raise ValueError('weights must be float32, got %s' % weights.dtype)
+    _check_stage_bytes(stage_bytes)
+    P = Ks + Kp
+    outs = _named_outputs(out, _r.output_table(shape, T, P, values.dtype, stderr, code))
+    n = int(np.prod(shape, dtype=np.int64))
+    if n:
+        x = np.ascontiguousarray(values).reshape(T, n)
+        cols = [np.ascontiguousarray(t).reshape(T, n) for t in terms]
+        w = None if weights is None else np.ascontiguousarray(weights).reshape(T, n)
+
+        def address(k):
+            return outs[k].ctypes.data if k in outs else None
+        try:
+            _lib.context(device).regress(
+                values.dtype, n, T, x.ctypes.data, design.ctypes.data if Ks else None, Ks, [c.ctypes.data for c in cols],
+                None if w is None else w.ctypes.data, address('coef'), address('stderr'), address('rss'), address('tss'),
+                address('r2'), address('count'), address('series'), min_valid=min_valid, series_mode=code, where=_lib.HOST,
+                stage_bytes=stage_bytes)
+        except _lib.Mod16Error as e:
+            raise _lib.overlap_as_value_error(e)
+    return _r.Regression(*[outs.get(k) for k in _r.Regression._fields])
+
+
 def aggregate_daynight(fields, half_day=None, noon=None, offset=None, sw_threshold=None, steps_per_day=24,
                        outputs=None, dtype=None, out=None, device=0, stage_bytes=None):
     r'''

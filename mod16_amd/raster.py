@@ -1064,6 +1064,74 @@ class RasterEngine(object):
                 raise _lib.overlap_as_value_error(e)
         return (smoothed, cnt) if count else smoothed
 
+    def regress(self, values, design=None, terms=(), weights=None, min_valid=None, stderr=False, series=None,
+                out=None):
+        '''Enqueue the regression kernel on the current stream: per pixel the weighted least-squares fit
+        ``y = X b`` over a device-resident stack, every output in one launch (``mod16_regress_*``; the
+        definition is ``mod16_amd.regress``, whose bits the result has).
+
+        ``values`` is one ``(T, n)`` float32 or float64 tensor, ``1 <= T <= 4096``, with unit stride in
+        pixels and any stride >= n in time (a view of a larger buffer is fine, at any element offset);
+        a value that is not finite is missing. ``design``: the ``(T, Ks)`` float64 columns every pixel
+        shares, as a numpy array (checked finite, uploaded) or as a contiguous float64 tensor on the
+        engine's device (its values are the caller's: they must be finite); ``terms``: ``Kp`` per-pixel
+        predictors, tensors of ``values``' shape and dtype that share one stride in time; ``1 <= Ks +
+        Kp <= 8``. ``weights``: an optional float32 tensor of that shape. The other arguments are those
+        of ``mod16_amd.regress_series``.
+
+        Returns ``Regression(coef, stderr, rss, tss, r2, count, series)``: ``coef`` / ``stderr`` ``(Ks +
+        Kp, n)``, ``rss`` / ``tss`` / ``r2`` ``(n,)`` float64, ``count`` ``(n,)`` uint16, ``series``
+        ``(T, n)`` in the dtype of ``values``; ``stderr`` and ``series`` are None where they are not
+        asked for. ``out`` may give the tensors as a dict by name (exactly the fields produced); no
+        output may overlap an input. Asynchronous, like ``smooth``.'''
+        from . import regress as _r
+        torch = _torch()
+        _t.check_device(values, 'values', self.device, torch.float32, torch.float64)
+        if values.dim() != 2:
+            raise ValueError('values must be a (T, n) tensor, got %r' % (tuple(values.shape),))
+        terms = list(terms)
+        for k, t in enumerate(terms):
+            _t.check_device(t, 'terms[%d]' % k, self.device, values.dtype)
+        if weights is not None:
+            _t.check_device(weights, 'weights', self.device, torch.float32)
+        on_device = isinstance(design, torch.Tensor)
+        if on_device:
+            _t.check_device(design, 'design', self.device, torch.float64)
+        dtype = _t.numpy_dtype(values.dtype)
+        T, shape, Ks, Kp, min_valid, stderr, code = _r.check_call(
+            tuple(values.shape), dtype, None if design is None else tuple(design.shape), [tuple(t.shape) for t in terms],
+            [dtype] * len(terms), None if weights is None else tuple(weights.shape), min_valid, stderr, series)
+        if on_device:
+            if not design.is_contiguous():
+                raise ValueError('design must be contiguous')
+            design64 = design
+        else:
+            design64 = _r.check_design(design, T)
+        n = shape[0]
+        value_pitch = _t.row_pitch(values, 'values', 'stride in time')
+        term_pitch = _t.share_one([_t.row_pitch(t, 'terms[%d]' % k, 'stride in time') for k, t in enumerate(terms)],
+                                  'the terms', 'stride in time')
+        weight_pitch = None if weights is None else _t.row_pitch(weights, 'weights', 'stride in time')
+        outs, pitch = _t.named_outputs(out, _r.output_table(shape, T, Ks + Kp, dtype, stderr, code), self.device,
+                                       'stride in time')
+        if n:
+            if Ks and not on_device:
+                design64 = torch.from_numpy(design64).to(self._dev())
+
+            def address(k):
+                return outs[k].data_ptr() if k in outs else None
+            try:
+                self.ctx.regress(
+                    dtype, n, T, values.data_ptr(), design64.data_ptr() if Ks else None, Ks, [t.data_ptr() for t in terms],
+                    None if weights is None else weights.data_ptr(), address('coef'), address('stderr'), address('rss'),
+                    address('tss'), address('r2'), address('count'), address('series'), value_pitch=value_pitch,
+                    term_pitch=term_pitch, weight_pitch=weight_pitch, coef_pitch=pitch['coef'], se_pitch=pitch.get('stderr'),
+                    series_pitch=pitch.get('series'), min_valid=min_valid, series_mode=code, where=_lib.DEVICE,
+                    stream=self._stream())
+            except _lib.Mod16Error as e:
+                raise _lib.overlap_as_value_error(e)
+        return _r.Regression(*[outs.get(k) for k in _r.Regression._fields])
+
     def daynight(self, fields, half_day=None, noon=None, offset=None, sw_threshold=None, steps_per_day=24,
                  outputs=None, dtype=None, out=None):
         '''Enqueue the day / night aggregation on the current stream: hourly reanalysis fields in, the
